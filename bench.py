@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MCTS simulations/s (+ measured self-play games/hour) of the MI355X self-play path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES: it starts N fresh children (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set as torchrun would) before anything has touched the GPU,
@@ -16,14 +16,22 @@ terminal leaves; root evaluations are reported separately)
 
 Workload at any N: BASELINE.json configs[2] per GPU -- 8192 concurrent games, 800 sims/move, 256ch x 10blk ResNet,
 fp32, synthetic data (games from the opening + random opening plies, counter-generated weights).  Weak scaling: every
-rank runs its own 8192 games; no collective in the data path.  The same line also carries
+rank runs its own 8192 games; no collective in the data path.  A plain run does only what the headline needs: set-up,
+prewarm, W warm-up steps, the K timed steps and the line (plus --dump-outputs).  With --full the same line also carries
   * "peaked": the same measurement with peaked-policy weights (deep, narrow trees: SURVEY.md section 8d's second
     synthetic variant), unless --no-peaked;
   * "games_per_hour_measured": COMPLETE games under the reference's termination rules at BASELINE configs[1]
     (1024 games, 400 sims/move, 128x6) played inside this run, unless --complete-games 0;
-  * "cpu_baseline" (N = 1, rank 0): the reference's mode-1 worker restated on the host cores;
-  * "throughput_mode" (only with --throughput-mode): a labelled REDUCED-PRECISION second measurement (the hand-written bf16
-    convolution, hip_net.HipBf16Evaluator) -- never the headline, outside the 1e-5 contract.
+  * "cpu_baseline" (N = 1, rank 0): the reference's mode-1 worker restated on the host cores, unless --cpu-seconds 0;
+  * the engine clock and socket power sampled during the timed steps, in "roofline".
+With or without --full, "throughput_mode" (only with --throughput-mode): a labelled REDUCED-PRECISION second measurement
+(the hand-written bf16 convolution, hip_net.HipBf16Evaluator) -- never the headline, outside the 1e-5 contract.
+
+--dump-outputs DIR writes what the last timed step of the headline measurement computed, as float32 / float64 .npy files
+(rank 0; at most 64 MB, a fixed seeded sample of the games beyond that): the network input the select stage produced
+("planes"), the ordered legal moves and their count the evaluator was asked for, the evaluator's legal-move logits
+(dense [G, 8100] logits for the library evaluators) and value, and the engine counters summed over the timed steps.
+Inputs are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -90,7 +98,14 @@ def parse_args():
     ap.add_argument("--prewarm", type=int, default=-1,
                     help="untimed network-free steps that bring the staggered slots to the steady-state mix of search "
                          "depths before warm-up (-1: sims+64, 0: off)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: peaked weights, complete games, cpu_baseline, clock / power sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -170,8 +185,28 @@ def profiler_region(resume: bool):
     (lib.roctxProfilerResume if resume else lib.roctxProfilerPause)(0)
 
 
-def measure(args, dev, rank, world, dist, backend, peaked):
-    """One timed region: prewarm -> W warm-up steps -> barrier+sync, K steps, barrier+sync.  Returns the per-rank dict."""
+DUMP_BYTES = 64 << 20
+COUNTERS = ("sims", "depth_sum", "children_scanned", "nodes_created", "leaf_evals", "root_evals", "terminal_sims")
+
+
+def dump_outputs(out_dir, per_game, counters):
+    """per_game: name -> float32 array with one row per game; counters: float64 [len(COUNTERS)].  Writes out_dir/<name>.npy;
+    when the rows would pass DUMP_BYTES, a fixed seeded sample of the games (their indices are games.npy either way)."""
+    import numpy as np
+    n = len(next(iter(per_game.values())))
+    row_bytes = sum(a[0].nbytes for a in per_game.values()) + 8
+    keep = min(n, (DUMP_BYTES - counters.nbytes - 4096) // row_bytes)
+    games = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "games.npy"), games.astype(np.float64))
+    np.save(os.path.join(out_dir, "engine_counters.npy"), counters)
+    for name, a in per_game.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[games]))
+
+
+def measure(args, dev, rank, world, dist, backend, peaked, dump_dir=None):
+    """One timed region: prewarm -> W warm-up steps -> barrier+sync, K steps, barrier+sync.  Returns the per-rank dict.
+    With dump_dir, rank 0 then writes what the last timed step computed (dump_outputs)."""
     import torch
     from xiangqi_alphazero_amd import engine, evaluator, model, weights
 
@@ -217,7 +252,7 @@ def measure(args, dev, rank, world, dist, backend, peaked):
     smi = {}
     # not under a profiler: its preloaded library has the GPU initialised in every child before that child execs rocm-smi
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
-    smi_thread = threading.Thread(target=smi_sample, args=(smi,)) if (rank == 0 and not profiled) else None
+    smi_thread = threading.Thread(target=smi_sample, args=(smi,)) if (args.full and rank == 0 and not profiled) else None
     graphed = bool(args.graph and sparse and eng.capture_step(warmup=0))
     if hasattr(ev, "timing") and not graphed:
         ev.timing = True            # HIP events around each launch of the dominant kernel, timed region only
@@ -234,9 +269,9 @@ def measure(args, dev, rank, world, dist, backend, peaked):
         x = eng.select()
         e[1].record()
         if sparse:                                 # logits of the legal moves only (xq_policy_head_legal), no dense row
-            ll, value = ev.evaluate_legal(x, eng.req_moves, eng.req_counts)
+            logits, value = ev.evaluate_legal(x, eng.req_moves, eng.req_counts)
             e[2].record()
-            eng.expand_legal(ll, value)
+            eng.expand_legal(logits, value)
         else:
             logits, value = ev(x)
             e[2].record()
@@ -248,6 +283,17 @@ def measure(args, dev, rank, world, dist, backend, peaked):
     if smi_thread is not None:
         smi_thread.join()
     s1 = eng.stats()
+    if dump_dir is not None and rank == 0:
+        import numpy as np
+        if graphed:                                # the replayed step's outputs live in the buffers the recording holds
+            logits, value = eng._keep
+        counts = eng.req_counts.to(torch.int64)
+        legal = torch.arange(eng.req_moves.shape[1], device=dev)[None, :] < counts[:, None]
+        moves = torch.where(legal, eng.req_moves.to(torch.int64) & 0xFFFF, -1)
+        per_game = {"planes": eng.nn_input, "legal_moves": moves, "legal_counts": counts,
+                    "logits": torch.where(legal, logits, 0.0) if sparse else logits, "value": value.reshape(-1)}
+        dump_outputs(dump_dir, {k: v.float().cpu().numpy() for k, v in per_game.items()},
+                     np.array([s1[k] - s0[k] for k in COUNTERS], dtype=np.float64))
     if hasattr(ev, "timing"):
         ev.timing = False
     n = args.steps
@@ -257,8 +303,7 @@ def measure(args, dev, rank, world, dist, backend, peaked):
         sel_ms = sum(ev_t[4 * k].elapsed_time(ev_t[4 * k + 1]) for k in range(n)) / n
         nn_ms = sum(ev_t[4 * k + 1].elapsed_time(ev_t[4 * k + 2]) for k in range(n)) / n
         exp_ms = sum(ev_t[4 * k + 2].elapsed_time(ev_t[4 * k + 3]) for k in range(n)) / n
-    d = {k: s1[k] - s0[k] for k in ("sims", "depth_sum", "children_scanned", "nodes_created", "leaf_evals", "root_evals",
-                                    "terminal_sims")}
+    d = {k: s1[k] - s0[k] for k in COUNTERS}
     if hasattr(ev, "roofline") and graphed:
         # one launch per step, no per-kernel events: book the WHOLE step to the 2*blocks conv launches -- an upper bound on
         # the launch time, so `frac` is a lower bound here
@@ -451,13 +496,13 @@ def main():
         if dist.get_world_size() != args.gpus:
             raise SystemExit("bench.py: process group has %d ranks, --gpus %d" % (dist.get_world_size(), args.gpus))
 
-    m = measure(args, dev, rank, world, dist, backend, args.peaked)
+    m = measure(args, dev, rank, world, dist, backend, args.peaked, dump_dir=args.dump_outputs)
     elapsed_max, sims_all, per_rank = reduce_ranks(m, dev, world, dist, backend)
     mp = None
-    if not args.peaked and not args.no_peaked:
+    if args.full and not args.peaked and not args.no_peaked:
         mp = measure(args, dev, rank, world, dist, backend, True)
         mp_el, mp_sims, mp_rank = reduce_ranks(mp, dev, world, dist, backend)
-    gph = complete_games_leg(args, dev, rank, world, dist, backend) if args.complete_games > 0 else None
+    gph = complete_games_leg(args, dev, rank, world, dist, backend) if args.full and args.complete_games > 0 else None
     mt = None
     if args.throughput_mode and args.evaluator != "bf16":
         saved = args.evaluator
@@ -544,7 +589,7 @@ def main():
             out["games_per_hour_derived"] = {"at_200_plies": round(value * 3600 / (args.sims * 200.0), 1)}
         not_measured.append("games_per_hour_derived")
         out["not_measured_in_this_run"] = not_measured
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             from oracle import cpu_baseline                      # the checker, timed beside the product path
             cb = cpu_baseline.run(args.channels, args.blocks, budget_s=args.cpu_seconds)
             out["cpu_baseline"] = {"value": round(cb["value"], 2), "unit": "simulations/s", "cores": cb["cores"], "kind": "port",

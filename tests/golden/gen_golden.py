@@ -20,6 +20,8 @@ Fixtures written (all small):
   arena_traces.json     reference AlphaZeroTrainer._serial_evaluate with stub models: per-game winner/steps, totals
   train_trace.json      reference AlphaZeroTrainer.train_network on a recorded game's augmented samples (fixed batch order);
                         train_trace_64x2.json: the same at 64x2 (the smallest net the hand-written convolution takes)
+  checkpoint_loader.json  reference AlphaZeroTrainer.load_checkpoint: the keys it reads, and the 16x1 state_dict layout
+                        it loads into
   nn_golden.npz         reference XiangqiNet outputs for generator weights (xiangqi-alphazero_amd/weights.py)
   nn_golden2.npz        the same for 256x20 and for peaked policies (policy_gain 8), plus the reference's priors over
                         the ordered legal moves (MCTS._mask_and_normalize of predict)
@@ -658,13 +660,70 @@ def gen_train():
         print("train", fname, stats)
 
 
+def gen_checkpoint_loader():
+    """What the reference's AlphaZeroTrainer.load_checkpoint (train.py:569-579) needs of a checkpoint file: the reference
+    XiangqiNet(16, 1)'s state_dict layout (name, shape, dtype, parameter or buffer; parameters() order) and the keys the
+    loader reads, recorded by running it unbound on a stand-in `self` over a file written by the reference's own
+    save_checkpoint (train.py:537-567)."""
+    import tempfile
+    import types
+    import torch
+    cwd = os.getcwd()
+    os.chdir("/tmp")
+    try:
+        import train as ref_train                      # reference
+    finally:
+        os.chdir(cwd)
+    import model as ref_model
+
+    def trainer(tmp):
+        cur, best = ref_model.XiangqiNet(num_channels=16, num_res_blocks=1), ref_model.XiangqiNet(num_channels=16, num_res_blocks=1)
+        opt = torch.optim.Adam(cur.parameters(), lr=0.002, weight_decay=1e-4)
+        sch = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=[50, 80], gamma=0.1)
+        cfg = types.SimpleNamespace(num_channels=16, num_res_blocks=1, checkpoint_dir=tmp)
+        return types.SimpleNamespace(device="cpu", current_model=cur, best_model=best, optimizer=opt, scheduler=sch,
+                                     config=cfg, total_games=40)
+
+    reads = []
+
+    class Recorder(dict):
+        def __getitem__(self, k):
+            reads.append(["[]", k])
+            return dict.__getitem__(self, k)
+
+        def get(self, k, default=None):
+            reads.append(["get", k])
+            return dict.get(self, k, default)
+
+        def __contains__(self, k):
+            reads.append(["in", k])
+            return dict.__contains__(self, k)
+
+    real_load = torch.load
+    with tempfile.TemporaryDirectory() as tmp:
+        ref_train.AlphaZeroTrainer.save_checkpoint(trainer(tmp), 3)
+        torch.load = lambda *a, **kw: Recorder(real_load(*a, **kw))
+        try:
+            ref_train.AlphaZeroTrainer.load_checkpoint(trainer(tmp), os.path.join(tmp, "checkpoint_iter3.pt"))
+        finally:
+            torch.load = real_load
+    net = ref_model.XiangqiNet(num_channels=16, num_res_blocks=1)
+    params = {n for n, _ in net.named_parameters()}
+    layout = [[k, list(v.shape), str(v.dtype).replace("torch.", ""), "parameter" if k in params else "buffer"]
+              for k, v in net.state_dict().items()]
+    out = dict(net=[16, 1], state_dict=layout, parameters=[n for n, _ in net.named_parameters()], reads=reads)
+    json.dump(out, open(os.path.join(HERE, "checkpoint_loader.json"), "w"))
+    print("checkpoint loader reads", reads)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--perft5", action="store_true")
     ap.add_argument("--only", default="")
     args = ap.parse_args()
     steps = dict(perft=lambda: gen_perft(args.perft5), corpus=gen_corpus, crafted=gen_crafted,
-                 mcts=gen_mcts_traces, games=gen_game_traces, nn=gen_nn, nn2=gen_nn2, arena=gen_arena, train=gen_train)
+                 mcts=gen_mcts_traces, games=gen_game_traces, nn=gen_nn, nn2=gen_nn2, arena=gen_arena, train=gen_train,
+                 ckpt=gen_checkpoint_loader)
     for k, fn in steps.items():
         if not args.only or k in args.only.split(","):
             fn()

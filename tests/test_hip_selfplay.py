@@ -77,3 +77,38 @@ def test_graph_replayed_steps_equal_eager_steps():
     a0, a1 = (np.sort(a, order=["slot", "game_seq", "ply"]) for a in (a0, a1))
     r0, r1 = (np.sort(r, order=["slot", "game_seq"]) for r in (r0, r1))
     assert a0.tobytes() == a1.tobytes() and r0.tobytes() == r1.tobytes()
+
+
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and carries none of the --full legs; --dump-outputs writes the last
+    timed step's outputs, and the same arguments give the same arrays, eager or replayed from the HIP graph.  --full adds
+    the peaked leg."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    tiny = ["--games", "256", "--sims", "16", "--channels", "64", "--blocks", "2", "--steps", "3", "--warmup", "1"]
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + tiny + list(extra),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+
+    lines = [run("--dump-outputs", str(tmp_path / d), *x) for d, x in (("a", ()), ("b", ()), ("g", ("--graph",)))]
+    for o in lines:
+        assert o["steps"] == 3 and o["ms_per_step"] > 0 and o["value"] > 0 and o["unit"] == "simulations/s"
+        assert not {"peaked", "games_per_hour_measured", "cpu_baseline"} & set(o)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["engine_counters.npy", "games.npy", "legal_counts.npy", "legal_moves.npy", "logits.npy", "planes.npy",
+                     "value.npy"]
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert a["planes"].shape == (256, 15, 10, 9) and a["logits"].shape == (256, 128) and a["value"].shape == (256,)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["engine_counters"][0] > 0 and a["legal_counts"].max() > 0
+    for d in ("b", "g"):
+        for n in names:
+            assert np.array_equal(np.load(tmp_path / d / n), a[n[:-4]]), (d, n)
+    full = run("--full", "--complete-games", "0", "--cpu-seconds", "0")
+    assert full["peaked"]["value"] > 0

@@ -377,6 +377,33 @@ def test_bench_workload_label_follows_the_arguments():
     assert abs(flops / 1e6 - 2178.0) < 0.5 and abs(b.net_flops(128, 6)[0] / 1e6 - 369.2) < 0.5
 
 
+def test_bench_dump_outputs_stays_under_its_cap(tmp_path):
+    """bench.py --dump-outputs: every file float32 / float64, all rows while they fit, beyond the 64 MB cap the same fixed
+    seeded sample of the games on every call (games.npy holds its indices)."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("xq_bench", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    counters = np.arange(len(b.COUNTERS), dtype=np.float64)
+    small = {"value": np.linspace(-1, 1, 100, dtype=np.float32), "logits": np.ones((100, 128), np.float32)}
+    b.dump_outputs(str(tmp_path / "small"), small, counters)
+    assert np.array_equal(np.load(tmp_path / "small" / "games.npy"), np.arange(100))
+    assert np.array_equal(np.load(tmp_path / "small" / "value.npy"), small["value"])
+    big = {"logits": np.tile(np.arange(20000, dtype=np.float32)[:, None], (1, 1000))}      # 80 MB of rows
+    for d in ("big1", "big2"):
+        b.dump_outputs(str(tmp_path / d), big, counters)
+    total = sum(os.path.getsize(tmp_path / "big1" / f) for f in os.listdir(tmp_path / "big1"))
+    assert total <= 64 << 20
+    games = np.load(tmp_path / "big1" / "games.npy")
+    assert 10000 < len(games) < 20000 and np.all(np.diff(games) > 0)
+    assert np.array_equal(games, np.load(tmp_path / "big2" / "games.npy"))
+    assert np.array_equal(np.load(tmp_path / "big1" / "logits.npy")[:, 0], games)
+    for f in os.listdir(tmp_path / "big1"):
+        assert np.load(tmp_path / "big1" / f).dtype in (np.float32, np.float64)
+    assert np.array_equal(np.load(tmp_path / "big1" / "engine_counters.npy"), counters)
+
+
 def test_inline_asm_mfmas_keep_their_wait_states():
     """tools/check_asm_mfma_hazards.py: every MFMA issued through inline asm (accumulator tiles pinned to VGPRs) either carries its own
     s_nop or has no vector write of its A/B source registers within the two instructions in front of it in the gfx950 assembly the

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 ( while true; do sleep 50; date >> "$OUT/heartbeat.log"; done ) &
 HB=$!
 trap "kill $HB 2>/dev/null" EXIT
-PMCARGS="--steps 4 --warmup 2 --prewarm ${XQ_PMC_PREWARM:-400} --no-stagger --complete-games 0 --cpu-seconds 0"
+PMCARGS="--steps 4 --warmup 2 --prewarm ${XQ_PMC_PREWARM:-400} --no-stagger --full --complete-games 0 --cpu-seconds 0"
 export XQ_BENCH_ROCTX=1          # bench.py brackets the real steps; --selected-regions keeps the prewarm out of the counter passes
 [ -n "$XQ_SKIP_STATS" ] || rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof" -- python3 bench.py --no-peaked --complete-games 0 --cpu-seconds 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err"
 python3 bench.py $PMCARGS > "$OUT/bench_pmc_unprofiled.json" 2> "$OUT/bench_pmc_unprofiled.err" && \

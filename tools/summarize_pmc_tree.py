@@ -70,7 +70,7 @@ def main():
     passes = dict(p.split("=", 1) for p in a.passes)
     data = {name: real_steps(load(d)) for name, d in passes.items()}
     variants = [("near-uniform (headline weights)", bench), ("peaked (policy_gain 8)", bench.get("peaked"))]
-    out = {"command": "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --steps %d --warmup %d --complete-games 0 --cpu-seconds 0; "
+    out = {"command": "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --steps %d --warmup %d --full --complete-games 0 --cpu-seconds 0; "
                       "one pass per counter set" % (bench["steps"], bench["warmup"]),
            "selection": "k_select / k_expand launches of real steps only (a k_stem_conv launch between this k_select and the next); "
                         "the network-free prewarm is excluded", "variants": {}}
