@@ -90,7 +90,7 @@ class XiangqiNet(nn.Module):
     def forward(self, x):
         """x f32[B,15,10,9] -> (policy logits f32[B,8100], value f32[B,1])  (model.py:87-107)."""
         h = None
-        if self.res_blocks and self.res_blocks[0].native_conv and x.is_cuda:
+        if self.res_blocks and self.res_blocks[0].native_conv and x.is_cuda and x.dtype == torch.float32:
             x = x.contiguous(memory_format=torch.channels_last)
             from .native_conv import bn_act, bn_supported
             if bn_supported(self.input_conv[1]):
