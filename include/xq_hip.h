@@ -149,7 +149,8 @@ typedef struct xq_engine_stats {
     uint64_t samples_written, samples_dropped;
     uint64_t overflow;        /* non-zero: a device capacity was exceeded (results invalid) */
     uint64_t games_started;
-    uint64_t reserved[14];
+    uint64_t rows_evaluated;  /* sum over xq_engine_compact calls of n_live: rows the evaluator ran on in packed steps */
+    uint64_t reserved[13];
 } xq_engine_stats;
 
 /* Bytes of device workspace the engine needs for cfg (tree arenas dominate:
@@ -184,6 +185,34 @@ int xq_engine_expand(const xq_engine *eng, const float *dev_policy, const float 
  * underflows (a logit gap above ~87), where the reference degrades to denormal or uniform priors and this stays exact. */
 int xq_engine_requests(const xq_engine *eng, const uint16_t **dev_moves, const int32_t **dev_counts);
 int xq_engine_expand_legal(const xq_engine *eng, const float *dev_legal_logits, const float *dev_value, void *stream);
+
+/* Packed step: the evaluator runs only over the slots that asked for an evaluation.  A C host calls, on one stream,
+ *     xq_engine_select(eng, nn_input)                 as before
+ *     xq_engine_compact(eng, nn_input)                stable, slot-ordered compaction of the waiting slots (phase
+ *                                                     WAIT_ROOT / WAIT_LEAF: exactly k_expand's test) into engine-owned
+ *                                                     buffers: *n_live, rows[r] = slot of packed row r, x[r] = nn_input[rows[r]],
+ *                                                     moves[r] / counts[r] = that slot's request (xq_engine_requests)
+ *     <evaluator over x, moves, counts>               the *_live entry points below, capacity = n_games, dev_n = n_live:
+ *                                                     rows [0, *n_live) are computed, nothing past them is read or written
+ *     xq_engine_expand_packed(eng, logits, value)     scatters packed row r's float32[XQ_MAXM] legal logits and value back to
+ *                                                     slot rows[r] of slot_logits / slot_value and runs xq_engine_expand_legal
+ *                                                     on them (slots that asked for nothing are ignored there, as always)
+ * The row count stays in device memory: no host synchronisation, and the sequence records into one replayable graph whose
+ * launch grids are sized for n_games.  n_live = 0 is a valid step.  Results are identical to the full-width step (select,
+ * evaluator over all n_games rows, xq_engine_expand_legal): a row's arithmetic in every evaluator kernel does not depend on
+ * its position in the batch.  xq_engine_packed returns the buffers' addresses (workspace, valid for the engine's lifetime). */
+typedef struct xq_engine_packed_buffers {
+    const int32_t *n_live;        /* int32, device */
+    const int32_t *rows;          /* int32[G] */
+    const float *x;               /* float32[G][15][10][9], rows [0, n_live) valid */
+    const uint16_t *moves;        /* uint16[G][XQ_MAXM] */
+    const int32_t *counts;        /* int32[G] */
+    const float *slot_logits;     /* float32[G][XQ_MAXM], slot-ordered hand-back of xq_engine_expand_packed */
+    const float *slot_value;      /* float32[G] */
+} xq_engine_packed_buffers;
+int xq_engine_compact(const xq_engine *eng, const float *dev_nn_input, void *stream);
+int xq_engine_packed(const xq_engine *eng, xq_engine_packed_buffers *out);
+int xq_engine_expand_packed(const xq_engine *eng, const float *dev_packed_logits, const float *dev_packed_value, void *stream);
 
 /* Synchronises `stream`, copies the counters to host. */
 int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *stream);
@@ -232,6 +261,16 @@ int xq_stem_conv(const float *dev_planes, const float *dev_wt, const float *dev_
 int xq_heads_1x1(const float *dev_h, const float *dev_w, const float *dev_bias, float *dev_p, float *dev_v,
                  long long rows, int channels, void *stream);
 
+/* Live-row variants of the evaluator kernels (the packed step above).  Each takes the CAPACITY where its plain twin takes
+ * the batch -- launch grids are sized by it, so a recorded graph stays valid -- and dev_n, an int32 in device memory that
+ * holds the live count n (clamped to [0, capacity]): positions [0, n) are computed bit-identically to the plain entry point,
+ * positions past n are neither read nor written, n = 0 does nothing.  Capacity 0 is a no-op; a negative capacity or a null
+ * dev_n is XQ_ERR_ARG.  xq_heads_1x1_live: `rows` = capacity x 90 and n counts positions (90 rows each). */
+int xq_stem_conv_live(const float *dev_planes, const float *dev_wt, const float *dev_bias, float *dev_y, int capacity,
+                      const int32_t *dev_n, int channels, void *stream);
+int xq_heads_1x1_live(const float *dev_h, const float *dev_w, const float *dev_bias, float *dev_p, float *dev_v,
+                      long long rows, const int32_t *dev_n, int channels, void *stream);
+
 /* Policy head's Linear(2880, 8100) (model.py:64-71) evaluated ONLY at the ordered legal moves of each pending evaluation
  * -- what mcts.py:176-188 keeps of the 8 100 logits:  dev_out[g][m] = dev_bias[a] + <dev_feat[g], dev_w[a]>,
  * a = dev_moves[g][m], m < dev_counts[g] (counts <= 0: the game is skipped, its row is left untouched).
@@ -247,6 +286,11 @@ int xq_policy_head_legal(const float *dev_feat, const float *dev_w, const float 
  * dev_b1 float32[128]; dev_w2 float32[128] = value_head.6.weight[0]; dev_b2 float32[1];  dev_value : float32[games]. */
 int xq_value_head(const float *dev_vfeat, const float *dev_w1t, const float *dev_b1, const float *dev_w2,
                   const float *dev_b2, int games, float *dev_value, void *stream);
+/* live-row variants (see xq_stem_conv_live) */
+int xq_policy_head_legal_live(const float *dev_feat, const float *dev_w, const float *dev_bias, const uint16_t *dev_moves,
+                              const int32_t *dev_counts, int capacity, const int32_t *dev_n, float *dev_out, void *stream);
+int xq_value_head_live(const float *dev_vfeat, const float *dev_w1t, const float *dev_b1, const float *dev_w2,
+                       const float *dev_b2, int capacity, const int32_t *dev_n, float *dev_value, void *stream);
 
 /* 3x3 convolution, stride 1, pad 1, C -> C channels (ResBlock.conv1/conv2 with BatchNorm folded, model.py:25-36)
  * as fused Winograd F(2x3,3x3) -- F(2,3) along the 10 rows, F(3,3) at the points 0, +-1, 2, inf along the 9 columns -- on
@@ -268,6 +312,9 @@ int xq_wino_conv3x3(const float *dev_x, const float *dev_u, const float *dev_bia
 /* bit 2: "wide" variant -- 128 output channels per workgroup (one workgroup per CU, 320 accumulators per wave): dev_u is then
  * float32[C/128][C/8][20][2][128][4] (the same element formula with 128-channel blocks), channels in {128, 256, 512}. */
 #define XQ_CONV_WIDE 4
+/* live-row variant (see xq_stem_conv_live): tile groups, the XQ_CONV_REVERSE walk and the buffer extents follow *dev_n */
+int xq_wino_conv3x3_live(const float *dev_x, const float *dev_u, const float *dev_bias, const float *dev_residual,
+                         float *dev_y, int capacity, const int32_t *dev_n, int channels, int flags, void *stream);
 
 /* The filter transform of xq_wino_conv3x3 on the device (the train step re-transforms after every optimizer step; self-play
  * transforms once per weight update and may use this or the host's float64 einsum, which give the same float32 values):
@@ -318,6 +365,9 @@ int xq_wino_wgrad(const float *dev_x, const float *dev_dy, float *dev_dw, void *
 size_t xq_wino_weight_bytes_bf16(int channels);
 int xq_wino_conv3x3_bf16(const float *dev_x, const void *dev_u_bf16, const float *dev_bias, const float *dev_residual,
                          float *dev_y, int batch, int channels, int flags, void *stream);
+/* live-row variant (see xq_stem_conv_live) */
+int xq_wino_conv3x3_bf16_live(const float *dev_x, const void *dev_u_bf16, const float *dev_bias, const float *dev_residual,
+                              float *dev_y, int capacity, const int32_t *dev_n, int channels, int flags, void *stream);
 
 /* =====================================================================================
  * Next row (section 8f.1) -- training-batch materialisation.  Replaces SelfPlayDataset.__getitem__ + augment_data

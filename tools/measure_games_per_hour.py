@@ -3,7 +3,12 @@
 reference's termination rules, and reports games/hour, simulations/s and the game-length statistics that bench.py's
 derived games/hour figure needs.  Default = BASELINE configs[1]: 1024 concurrent games, 400 sims/move, 128ch x 6blk.
 
-    python tools/measure_games_per_hour.py [--games 1024 --slots 1024 --sims 400 --channels 128 --blocks 6]
+    python tools/measure_games_per_hour.py [--games 1024 --slots 1024 --sims 400 --channels 128 --blocks 6] [--full-width]
+
+By default the games run through `selfplay.run_games`, i.e. the engine's packed step (the evaluator covers only the slots
+that asked for an evaluation).  --full-width is the A/B control: the same games, replaying a HIP graph of the explicit stage
+calls (select -> evaluate_legal over all slots -> expand_legal), what the engine did before the packed step.  Both report
+`rows_evaluated_share` = rows evaluated / (steps x slots).
 """
 import argparse
 import json
@@ -65,6 +70,45 @@ def refill(args, net, cfg):
         "games_finished_before_window": a[1], "overflow": int(st["overflow"]), "samples_dropped": int(st["samples_dropped"])}))
 
 
+def full_width(args, net, cfg):
+    """run_games' engine and settings, stepped by a recorded graph of the full-width stage calls (A/B control only)."""
+    import torch
+    from xiangqi_alphazero_amd import engine, evaluator
+    ev, ev_name = evaluator.make_evaluator(net, "cuda", "hip" if args.evaluator == "auto" else args.evaluator)
+    games, slots = args.games, max(1, min(args.slots, args.games))
+    ecfg = engine.make_config(slots, int(cfg.num_simulations), c_puct=float(cfg.c_puct),
+                              temperature_threshold=int(cfg.temperature_threshold), max_game_length=int(cfg.max_game_length),
+                              random_opening_moves=int(cfg.random_opening_moves), enable_resign=bool(cfg.enable_resign),
+                              resign_threshold=float(cfg.resign_threshold), resign_check_steps=int(cfg.resign_check_steps),
+                              add_noise=True, seed=11, games_target=games, max_out_samples=games * 201, max_out_results=games + 8)
+    eng = engine.SelfPlayEngine(ecfg, "cuda", evaluator=ev)
+
+    def stages():
+        x = eng.select()
+        ll, v = ev.evaluate_legal(x, eng.req_moves, eng.req_counts)
+        eng.expand_legal(ll, v)
+
+    t0 = time.time()
+    for _ in range(2):                                      # as capture_step: two eager steps, then the recording
+        stages()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+        stages()
+    steps = 2                                               # the recording itself runs nothing
+    while True:
+        for _ in range(256):
+            g.replay()
+        steps += 256
+        st = eng.stats()
+        if st["games_finished"] >= games:
+            break
+    samples, results = eng.drain()
+    st = eng.stats()
+    st.update(evaluator=ev_name, launch="graph", path="full", steps=steps, rows_evaluated=steps * slots)
+    return samples, results, st, time.time() - t0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--games", type=int, default=1024)
@@ -77,6 +121,8 @@ def main():
                     help="steady state of a REFILLING engine: finished slots start new games at once (games_target unbounded); the "
                          "rate is taken over --measure-s seconds after --warm-s seconds (several game lengths, so that the mix of "
                          "game ages is stationary: a fresh engine first finishes its SHORT games)")
+    ap.add_argument("--full-width", action="store_true",
+                    help="A/B control: the full-width step (every slot evaluated every step) instead of the packed one")
     ap.add_argument("--warm-s", type=float, default=240.0)
     ap.add_argument("--measure-s", type=float, default=180.0)
     args = ap.parse_args()
@@ -91,22 +137,32 @@ def main():
     if args.refill:
         return refill(args, net, cfg)
     t0 = time.time()
-    samples, results, st, elapsed = selfplay.run_games(net, cfg, args.games, "cuda", n_slots=args.slots, seed=11,
-                                                       evaluator_kind=args.evaluator, poll_every=256)
+    if args.full_width:
+        samples, results, st, elapsed = full_width(args, net, cfg)
+    else:
+        samples, results, st, elapsed = selfplay.run_games(net, cfg, args.games, "cuda", n_slots=args.slots, seed=11,
+                                                           evaluator_kind=args.evaluator, poll_every=256)
     torch.cuda.synchronize()
+    import hashlib
+    res_sorted = np.sort(results, order=["slot", "game_seq"])
+    smp_sorted = np.sort(samples, order=["slot", "game_seq", "ply"])
+    digest = hashlib.sha256(res_sorted.tobytes() + smp_sorted.tobytes()).hexdigest()[:16]
     steps = np.array([int(r["steps"]) for r in results])
     reasons = np.array([int(r["reason"]) for r in results])
     out = {
         "config": {"games": args.games, "slots": args.slots, "sims_per_move": args.sims,
-                   "net": "%dx%d" % (args.channels, args.blocks), "evaluator": st["evaluator"]},
+                   "net": "%dx%d" % (args.channels, args.blocks), "evaluator": st["evaluator"], "path": st["path"],
+                   "launch": st["launch"]},
         "games_finished": int(len(results)), "wall_s": round(elapsed, 2),
         "games_per_hour": round(len(results) * 3600.0 / elapsed, 1),
         "simulations_per_s": round(st["sims"] / elapsed, 1),
+        "steps": int(st["steps"]), "rows_evaluated": int(st["rows_evaluated"]),
+        "rows_evaluated_share": round(st["rows_evaluated"] / (st["steps"] * min(args.slots, args.games)), 4),
         "plies_per_game": {"mean": round(float(steps.mean()), 2), "p10": int(np.percentile(steps, 10)),
                            "p50": int(np.percentile(steps, 50)), "p90": int(np.percentile(steps, 90)), "max": int(steps.max())},
         "endings": {"rules": int((reasons == 1).sum()), "max_length": int((reasons == 2).sum()), "resign": int((reasons == 3).sum())},
         "winners": {"red": st["red_wins"], "black": st["black_wins"], "draw": st["draws"]},
-        "samples": int(len(samples)), "root_evals": st["root_evals"], "leaf_evals": st["leaf_evals"],
+        "samples": int(len(samples)), "records_sha256_16": digest, "root_evals": st["root_evals"], "leaf_evals": st["leaf_evals"],
         "terminal_sims": st["terminal_sims"], "note": "games_target == games: the tail of the run has idle slots, so this "
         "under-states the steady-state rate of an engine that keeps refilling",
     }

@@ -186,9 +186,17 @@ __device__ __forceinline__ f32x4 pk_fms4(f32x4 x, f32x2 c, f32x4 y) {
 template <int NT>
 __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void k_wino_conv(const float *__restrict__ X, const float *__restrict__ Ug,
                                                    const float *__restrict__ bias, const float *__restrict__ R,
-                                                   float *__restrict__ Y, int B, int C, int flags, int n_groups) {
+                                                   float *__restrict__ Y, int B, int C, int flags, int n_groups,
+                                                   const int32_t *__restrict__ live) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char *Xr = lds;
+    // live-row variant: the grid is sized for the capacity B, the batch is the first *live boards of it.  Everything below --
+    // tile groups, the reverse walk, the buffer descriptors' extents -- follows the live count, so boards past it are neither
+    // read nor written and a live board's arithmetic does not depend on the capacity.
+    if (live) {
+        B = min(max(*live, 0), B);
+        n_groups = (B * 15 + TILES - 1) / TILES;
+    }
     constexpr int NCO = 32 * NT;                      // output channels per workgroup
     constexpr int UBUF_BYTES = 20 * 2 * NCO * 16;    // one 8-channel chunk of weights for them
     // Weight fragments per chunk, and fragment registers.  Narrow: 5 registers, each fragment fetched half a chunk (20 MFMAs)
@@ -668,8 +676,8 @@ extern "C" {
 /* bytes of the pre-transformed weight tensor Ug for C channels: 20 * C * C floats */
 size_t xq_wino_weight_bytes(int channels) { return (size_t)20 * channels * channels * sizeof(float); }
 
-int xq_wino_conv3x3(const float *dev_x, const float *dev_u, const float *dev_bias, const float *dev_residual, float *dev_y,
-                      int batch, int channels, int flags, void *stream) {
+static int wino_conv3x3(const float *dev_x, const float *dev_u, const float *dev_bias, const float *dev_residual, float *dev_y,
+                        int batch, int channels, int flags, const int32_t *dev_live, void *stream) {
     if (!dev_x || !dev_u || !dev_bias || !dev_y || batch <= 0) return XQ_ERR_ARG;
     const bool wide = (flags & XQ_CONV_WIDE) != 0;
     const int nco = wide ? 128 : 64;
@@ -689,11 +697,24 @@ int xq_wino_conv3x3(const float *dev_x, const float *dev_u, const float *dev_bia
     const int rows = (n_groups + per - 1) / per;
     if (wide)
         hipLaunchKernelGGL(k_wino_conv<4>, dim3(rows * 8), dim3(256), LDS_BYTES_WIDE, (hipStream_t)stream, dev_x, dev_u, dev_bias,
-                           dev_residual, dev_y, batch, channels, flags, n_groups);
+                           dev_residual, dev_y, batch, channels, flags, n_groups, dev_live);
     else
         hipLaunchKernelGGL(k_wino_conv<2>, dim3(rows * 8), dim3(256), lds_bytes, (hipStream_t)stream, dev_x, dev_u, dev_bias,
-                           dev_residual, dev_y, batch, channels, flags, n_groups);
+                           dev_residual, dev_y, batch, channels, flags, n_groups, dev_live);
     return xq::launch_status();
+}
+
+int xq_wino_conv3x3(const float *dev_x, const float *dev_u, const float *dev_bias, const float *dev_residual, float *dev_y,
+                      int batch, int channels, int flags, void *stream) {
+    return wino_conv3x3(dev_x, dev_u, dev_bias, dev_residual, dev_y, batch, channels, flags, nullptr, stream);
+}
+
+int xq_wino_conv3x3_live(const float *dev_x, const float *dev_u, const float *dev_bias, const float *dev_residual, float *dev_y,
+                         int capacity, const int32_t *dev_n, int channels, int flags, void *stream) {
+    if (capacity < 0) return XQ_ERR_ARG;
+    if (capacity == 0) return XQ_OK;
+    if (!dev_n) return XQ_ERR_ARG;
+    return wino_conv3x3(dev_x, dev_u, dev_bias, dev_residual, dev_y, capacity, channels, flags, dev_n, stream);
 }
 
 int xq_wino_transform_filters(const float *dev_w, float *dev_u, int channels, int flags, void *stream) {

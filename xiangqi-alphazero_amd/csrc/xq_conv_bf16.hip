@@ -63,8 +63,13 @@ __device__ __forceinline__ bf16x8 to_bf16(f32x4 lo, f32x4 hi) {
 
 __global__ __launch_bounds__(256, 1) void k_wino_conv_bf16(const float *__restrict__ X, const void *__restrict__ Ub,
                                                              const float *__restrict__ bias, const float *__restrict__ R,
-                                                             float *__restrict__ Y, int B, int C, int flags, int n_groups) {
+                                                             float *__restrict__ Y, int B, int C, int flags, int n_groups,
+                                                             const int32_t *__restrict__ live) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (live) {                                      // live-row variant: as k_wino_conv, the batch is the first *live boards
+        B = min(max(*live, 0), B);
+        n_groups = (B * 15 + TILES - 1) / TILES;
+    }
     char *Xr = lds;
     const int tid = threadIdx.x, lane = tid & 63, wp = tid >> 6;
     const int NG = C / NCO, per = 8 / NG;
@@ -310,8 +315,8 @@ extern "C" {
 /* bytes of the bf16 pre-transformed weight tensor for C channels: 20 * C * C bf16 values */
 size_t xq_wino_weight_bytes_bf16(int channels) { return (size_t)20 * channels * channels * 2; }
 
-int xq_wino_conv3x3_bf16(const float *dev_x, const void *dev_u_bf16, const float *dev_bias, const float *dev_residual, float *dev_y,
-                         int batch, int channels, int flags, void *stream) {
+static int wino_conv3x3_bf16(const float *dev_x, const void *dev_u_bf16, const float *dev_bias, const float *dev_residual, float *dev_y,
+                             int batch, int channels, int flags, const int32_t *dev_live, void *stream) {
     if (!dev_x || !dev_u_bf16 || !dev_bias || !dev_y || batch <= 0) return XQ_ERR_ARG;
     if (channels < NCO || channels % NCO || 8 % (channels / NCO) || (channels / 16) % 4) return XQ_ERR_ARG;
     if (dev_x == dev_y || dev_residual == dev_y) return XQ_ERR_ARG;
@@ -326,8 +331,21 @@ int xq_wino_conv3x3_bf16(const float *dev_x, const void *dev_u_bf16, const float
     const int per = 8 / (channels / NCO);
     const int rows = (n_groups + per - 1) / per;
     hipLaunchKernelGGL(k_wino_conv_bf16, dim3(rows * 8), dim3(256), LDS_BYTES, (hipStream_t)stream, dev_x, dev_u_bf16, dev_bias,
-                       dev_residual, dev_y, batch, channels, flags, n_groups);
+                       dev_residual, dev_y, batch, channels, flags, n_groups, dev_live);
     return xq::launch_status();
+}
+
+int xq_wino_conv3x3_bf16(const float *dev_x, const void *dev_u_bf16, const float *dev_bias, const float *dev_residual, float *dev_y,
+                         int batch, int channels, int flags, void *stream) {
+    return wino_conv3x3_bf16(dev_x, dev_u_bf16, dev_bias, dev_residual, dev_y, batch, channels, flags, nullptr, stream);
+}
+
+int xq_wino_conv3x3_bf16_live(const float *dev_x, const void *dev_u_bf16, const float *dev_bias, const float *dev_residual, float *dev_y,
+                              int capacity, const int32_t *dev_n, int channels, int flags, void *stream) {
+    if (capacity < 0) return XQ_ERR_ARG;
+    if (capacity == 0) return XQ_OK;
+    if (!dev_n) return XQ_ERR_ARG;
+    return wino_conv3x3_bf16(dev_x, dev_u_bf16, dev_bias, dev_residual, dev_y, capacity, channels, flags, dev_n, stream);
 }
 
 }  // extern "C"

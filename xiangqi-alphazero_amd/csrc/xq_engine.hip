@@ -39,10 +39,11 @@ enum Gi : int { GI_SIDE = 0, GI_MC, GI_NOCAP, GI_PHASE, GI_SIMS, GI_NSAMP, GI_GS
                 GI_FREASON, GI_MANNOISE, GI_DELAY, GI_N = 32 };
 
 enum St : int { ST_SIMS = 0, ST_TERM, ST_LEAF, ST_ROOT, ST_MOVES, ST_GAMES, ST_RED, ST_BLACK, ST_DRAW, ST_PLIES, ST_NODES,
-                ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_N = 32 };
+                ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_N = 32 };
 
 enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_TW, P_TP, P_TA, P_TC, P_TM, P_ROOTP,
-                 P_STAGE, P_OUTS, P_OUTR, P_CNT, P_STATS, P_INJECT, P_SQRT, P_MNOISE, P_STATSUM, P_REQ };
+                 P_STAGE, P_OUTS, P_OUTR, P_CNT, P_STATS, P_INJECT, P_SQRT, P_MNOISE, P_STATSUM, P_REQ,
+                 P_PK_N, P_PK_ROWS, P_PK_X, P_PK_MOVES, P_PK_COUNTS, P_PK_LOGITS, P_PK_VALUE };
 
 enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM = 3 };
 
@@ -818,6 +819,79 @@ __global__ __launch_bounds__(256) void k_reduce_stats(Dev E, unsigned long long 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Packed step (xq_engine_compact / xq_engine_expand_packed): the evaluator sees only the slots that asked for an
+// evaluation, packed to the front of engine-owned buffers in slot order.  The predicate is k_expand's own (phase
+// WAIT_ROOT / WAIT_LEAF after select), so the two kernels cannot disagree about which slots need output.
+
+// Stable compaction by ONE workgroup for any G: thread t owns the contiguous slots [t K, t K + K), K = ceil(G / 1024); it
+// counts its waiting slots, a block-wide exclusive scan of the counts gives its first packed row, and it writes rows[] in
+// slot order.  G = 8192: eight strided 4-byte reads per thread, a few microseconds.
+constexpr int CPT = 1024;
+__global__ __launch_bounds__(CPT) void k_compact(Dev E, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
+    __shared__ int wsum[CPT / 64];
+    const int G = E.cfg.n_games, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int K = (G + CPT - 1) / CPT;
+    const int s0 = t * K, s1 = min(s0 + K, G);
+    int cnt = 0;
+    for (int s = s0; s < s1; ++s) {
+        const int ph = E.gi[(size_t)s * GI_N + GI_PHASE];
+        cnt += (ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF);
+    }
+    int inc = cnt;                                    // inclusive scan within the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(inc, off);
+        if (lane >= off) inc += v;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < CPT / 64; ++w) {
+        const int v = wsum[w];
+        base += w < wave ? v : 0;
+        total += v;
+    }
+    int r = base + inc - cnt;
+    for (int s = s0; s < s1; ++s) {
+        const int ph = E.gi[(size_t)s * GI_N + GI_PHASE];
+        if (ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF) rows[r++] = s;
+    }
+    if (t == 0) {
+        *n_live = total;
+        E.stats[ST_ROWS] += (unsigned long long)total;   // slot 0's counter row: k_reduce_stats sums the column
+    }
+}
+
+// Gather of the packed rows: one workgroup per row of the capacity, rows past *n_live exit.  Per row the 5 400-byte
+// planes (8-byte aligned: float2), the 256-byte ordered move list and its count.
+__global__ __launch_bounds__(256) void k_gather_rows(Dev E, const int32_t *__restrict__ n_live, const int32_t *__restrict__ rows,
+                                                     const float *__restrict__ nn_in, float *__restrict__ x, uint16_t *__restrict__ moves,
+                                                     int32_t *__restrict__ counts) {
+    const int r = blockIdx.x;
+    if (r >= *n_live) return;
+    const int slot = rows[r], t = threadIdx.x;
+    const float2 *src = (const float2 *)(nn_in + (size_t)slot * XQ_STATE_FLOATS);
+    float2 *dst = (float2 *)(x + (size_t)r * XQ_STATE_FLOATS);
+    for (int i = t; i < XQ_STATE_FLOATS / 2; i += 256) dst[i] = src[i];
+    if (t < XQ_MAXM / 2)
+        ((uint32_t *)(moves + (size_t)r * XQ_MAXM))[t] = ((const uint32_t *)(E.pmoves + (size_t)slot * XQ_MAXM))[t];
+    if (t == 0) counts[r] = E.req[slot];
+}
+
+// Hand-back: packed row r's legal-move logits and value go to slot rows[r] of the slot-ordered buffers k_expand reads.
+// One wave per row (two floats per lane), four rows per workgroup.
+__global__ __launch_bounds__(256) void k_scatter_rows(const int32_t *__restrict__ n_live, const int32_t *__restrict__ rows,
+                                                      const float *__restrict__ logits, const float *__restrict__ value,
+                                                      float *__restrict__ slot_logits, float *__restrict__ slot_value, int G) {
+    const int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (r >= G || r >= *n_live) return;
+    const int slot = rows[r];
+    ((float2 *)(slot_logits + (size_t)slot * XQ_MAXM))[lane] = ((const float2 *)(logits + (size_t)r * XQ_MAXM))[lane];
+    if (lane == 0) slot_value[slot] = value[r];
+}
+
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout {
@@ -859,6 +933,13 @@ Layout make_layout(const xq_engine_config *c) {
     put(P_MNOISE, G * XQ_MAXM * 8);
     put(P_STATSUM, ST_N * 8);
     put(P_REQ, G * 4);
+    put(P_PK_N, 4);
+    put(P_PK_ROWS, G * 4);
+    put(P_PK_X, G * XQ_STATE_FLOATS * 4);
+    put(P_PK_MOVES, G * XQ_MAXM * 2);
+    put(P_PK_COUNTS, G * 4);
+    put(P_PK_LOGITS, G * XQ_MAXM * 4);
+    put(P_PK_VALUE, G * 4);
     l.total = o;
     return l;
 }
@@ -894,6 +975,9 @@ int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t
     XQ_TRY(hipMemsetAsync(eng->p[P_ROOTP], 0, (size_t)cfg->n_games * XQ_MAXM * 8, s));
     XQ_TRY(hipMemsetAsync(eng->p[P_MNOISE], 0, (size_t)cfg->n_games * XQ_MAXM * 8, s));
     XQ_TRY(hipMemsetAsync(eng->p[P_REQ], 0, (size_t)cfg->n_games * 4, s));
+    // packed-step buffers: zero count, rows, requests, hand-back (the packed planes are written before they are read)
+    XQ_TRY(hipMemsetAsync(eng->p[P_PK_N], 0, l.off[P_PK_X] - l.off[P_PK_N], s));
+    XQ_TRY(hipMemsetAsync(eng->p[P_PK_MOVES], 0, l.total - l.off[P_PK_MOVES], s));
     {
         const int n = cfg->num_simulations + 2;
         double *tab = (double *)malloc(sizeof(double) * n);
@@ -940,6 +1024,43 @@ int xq_engine_expand_legal(const xq_engine *eng, const float *dev_legal_logits, 
     return launch_status();
 }
 
+int xq_engine_compact(const xq_engine *eng, const float *dev_nn_input, void *stream) {
+    if (!eng || !dev_nn_input || eng->cfg.n_games <= 0) return XQ_ERR_ARG;
+    const Dev d = make_dev(eng);
+    hipStream_t s = (hipStream_t)stream;
+    int32_t *n_live = (int32_t *)eng->p[P_PK_N], *rows = (int32_t *)eng->p[P_PK_ROWS];
+    hipLaunchKernelGGL(k_compact, dim3(1), dim3(CPT), 0, s, d, n_live, rows);
+    int rc = launch_status();
+    if (rc != XQ_OK) return rc;
+    hipLaunchKernelGGL(k_gather_rows, dim3(eng->cfg.n_games), dim3(256), 0, s, d, (const int32_t *)n_live, (const int32_t *)rows,
+                       dev_nn_input, (float *)eng->p[P_PK_X], (uint16_t *)eng->p[P_PK_MOVES], (int32_t *)eng->p[P_PK_COUNTS]);
+    return launch_status();
+}
+
+int xq_engine_packed(const xq_engine *eng, xq_engine_packed_buffers *out) {
+    if (!eng || !out) return XQ_ERR_ARG;
+    out->n_live = (const int32_t *)eng->p[P_PK_N];
+    out->rows = (const int32_t *)eng->p[P_PK_ROWS];
+    out->x = (const float *)eng->p[P_PK_X];
+    out->moves = (const uint16_t *)eng->p[P_PK_MOVES];
+    out->counts = (const int32_t *)eng->p[P_PK_COUNTS];
+    out->slot_logits = (const float *)eng->p[P_PK_LOGITS];
+    out->slot_value = (const float *)eng->p[P_PK_VALUE];
+    return XQ_OK;
+}
+
+int xq_engine_expand_packed(const xq_engine *eng, const float *dev_packed_logits, const float *dev_packed_value, void *stream) {
+    if (!eng || !dev_packed_logits || !dev_packed_value || eng->cfg.n_games <= 0) return XQ_ERR_ARG;
+    if (((uintptr_t)dev_packed_logits) & 7) return XQ_ERR_ARG;
+    const int G = eng->cfg.n_games;
+    float *slot_logits = (float *)eng->p[P_PK_LOGITS], *slot_value = (float *)eng->p[P_PK_VALUE];
+    hipLaunchKernelGGL(k_scatter_rows, dim3((G + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const int32_t *)eng->p[P_PK_N],
+                       (const int32_t *)eng->p[P_PK_ROWS], dev_packed_logits, dev_packed_value, slot_logits, slot_value, G);
+    const int rc = launch_status();
+    if (rc != XQ_OK) return rc;
+    return xq_engine_expand_legal(eng, slot_logits, slot_value, stream);
+}
+
 int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *stream) {
     if (!eng || !host_out) return XQ_ERR_ARG;
     const Dev d = make_dev(eng);
@@ -961,6 +1082,7 @@ int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *
     host_out->plies_finished = h[ST_PLIES]; host_out->nodes_created = h[ST_NODES]; host_out->depth_sum = h[ST_DEPTH];
     host_out->children_scanned = h[ST_SCAN]; host_out->resigns = h[ST_RESIGN]; host_out->samples_written = h[ST_SAMP];
     host_out->samples_dropped = h[ST_DROP]; host_out->overflow = h[ST_OVF]; host_out->games_started = h[ST_STARTED];
+    host_out->rows_evaluated = h[ST_ROWS];
     return h[ST_OVF] ? XQ_ERR_OVERFLOW : XQ_OK;
 }
 

@@ -88,7 +88,12 @@ constexpr int HEAD_OUT = 36;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void k_heads_1x1(const float *__restrict__ H, const float *__restrict__ W,
                                                    const float *__restrict__ bias, float *__restrict__ P,
-                                                   float *__restrict__ V, long long rows, int C) {
+                                                   float *__restrict__ V, long long rows, int C,
+                                                   const int32_t *__restrict__ live) {
+    if (live) {                                        // live-row variant: positions [0, *live) of the capacity, 90 rows each
+        const long long n = (long long)max(*live, 0) * 90;
+        rows = n < rows ? n : rows;
+    }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *Ws = (float *)smem;                         // [36][C]
     for (int i = threadIdx.x * 4; i < HEAD_OUT * C; i += 256 * 4) *(float4 *)(Ws + i) = *(const float4 *)(W + i);
@@ -143,9 +148,11 @@ __global__ __launch_bounds__(256) void k_heads_1x1(const float *__restrict__ H, 
 // ANY input (zeros contribute nothing), ~10x fewer multiply-adds than the dense form, and the kernel is bound by the
 // 4 C bytes it writes per position.  Weights: float[135][C], entry = plane * 9 + (dy + 1) * 3 + (dx + 1).
 __global__ __launch_bounds__(256) void k_stem_conv(const float *__restrict__ X, const float *__restrict__ Wt,
-                                                   const float *__restrict__ bias, float *__restrict__ Y, int C) {
+                                                   const float *__restrict__ bias, float *__restrict__ Y, int C,
+                                                   const int32_t *__restrict__ live) {
     __shared__ float xs[15 * 90];
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (live && g >= *live) return;                   // live-row variant: positions past *live are neither read nor written
     for (int i = tid; i < 15 * 90; i += 256) xs[i] = X[(size_t)g * (15 * 90) + i];
     __syncthreads();
     for (int pos = wave; pos < 90; pos += 4) {
@@ -193,9 +200,10 @@ __global__ __launch_bounds__(256) void k_stem_conv(const float *__restrict__ X, 
 constexpr int PF4 = 2880 / 4;             // float4 per feature / weight row
 __global__ __launch_bounds__(256) void k_policy_legal(const float *__restrict__ feat, const float *__restrict__ W,
                                                       const float *__restrict__ bias, const uint16_t *__restrict__ moves,
-                                                      const int32_t *__restrict__ counts, int games, float *__restrict__ out) {
+                                                      const int32_t *__restrict__ counts, int games, float *__restrict__ out,
+                                                      const int32_t *__restrict__ live) {
     const int g = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    if (g >= games) return;
+    if (g >= games || (live && g >= *live)) return;
     const int lane = threadIdx.x & 63;
     int cnt = counts[g];
     cnt = cnt < 0 ? 0 : (cnt > XQ_MAXM ? XQ_MAXM : cnt);
@@ -242,10 +250,13 @@ __global__ __launch_bounds__(256) void k_policy_legal(const float *__restrict__ 
 constexpr int VGB = 4;        // games per block: 4 keeps >= 256 blocks in flight from G = 1024 up (16: 47 us at G = 1024)
 __global__ __launch_bounds__(128) void k_value_head(const float *__restrict__ vf, const float *__restrict__ w1t,
                                                     const float *__restrict__ b1, const float *__restrict__ w2,
-                                                    const float *__restrict__ b2, int games, float *__restrict__ value) {
+                                                    const float *__restrict__ b2, int games, float *__restrict__ value,
+                                                    const int32_t *__restrict__ live) {
     __shared__ __attribute__((aligned(16))) float vs[VGB][360];
     __shared__ float part[2][VGB];
     const int g0 = blockIdx.x * VGB, j = threadIdx.x;
+    if (live) games = min(games, *live);               // live-row variant: games [0, *live) only
+    if (g0 >= games) return;                          // block-uniform, ahead of the barriers
     for (int i = j; i < VGB * 360; i += 128) {
         const int g = i / 360;
         vs[g][i - g * 360] = g0 + g < games ? vf[(size_t)(g0 + g) * 360 + (i - g * 360)] : 0.0f;
@@ -299,8 +310,8 @@ extern "C" int xq_samples_to_batch(const void *dev_samples, const int32_t *dev_i
     return xq::launch_status();
 }
 
-extern "C" int xq_heads_1x1(const float *dev_h, const float *dev_w, const float *dev_bias, float *dev_p, float *dev_v,
-                            long long rows, int channels, void *stream) {
+static int heads_1x1(const float *dev_h, const float *dev_w, const float *dev_bias, float *dev_p, float *dev_v, long long rows,
+                     int channels, const int32_t *dev_live, void *stream) {
     if (!dev_h || !dev_w || !dev_bias || !dev_p || !dev_v || rows < 0 || channels < 16 || channels % 16 || channels > 1024) return XQ_ERR_ARG;
     if (((uintptr_t)dev_h | (uintptr_t)dev_w) & 15) return XQ_ERR_ARG;
     if (rows == 0) return XQ_OK;
@@ -313,34 +324,87 @@ extern "C" int xq_heads_1x1(const float *dev_h, const float *dev_w, const float 
     long long blocks = ((rows + 15) / 16 + 3) / 4;
     if (blocks > 256 * 8) blocks = 256 * 8;
     hipLaunchKernelGGL(k_heads_1x1, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, dev_h, dev_w, dev_bias, dev_p,
-                       dev_v, rows, channels);
+                       dev_v, rows, channels, dev_live);
+    return xq::launch_status();
+}
+
+extern "C" int xq_heads_1x1(const float *dev_h, const float *dev_w, const float *dev_bias, float *dev_p, float *dev_v,
+                            long long rows, int channels, void *stream) {
+    return heads_1x1(dev_h, dev_w, dev_bias, dev_p, dev_v, rows, channels, nullptr, stream);
+}
+
+extern "C" int xq_heads_1x1_live(const float *dev_h, const float *dev_w, const float *dev_bias, float *dev_p, float *dev_v,
+                                 long long rows, const int32_t *dev_n, int channels, void *stream) {
+    if (rows < 0) return XQ_ERR_ARG;
+    if (rows == 0) return XQ_OK;
+    if (!dev_n || rows % 90) return XQ_ERR_ARG;
+    return heads_1x1(dev_h, dev_w, dev_bias, dev_p, dev_v, rows, channels, dev_n, stream);
+}
+
+static int stem_conv(const float *dev_planes, const float *dev_wt, const float *dev_bias, float *dev_y, int games, int channels,
+                     const int32_t *dev_live, void *stream) {
+    if (!dev_planes || !dev_wt || !dev_bias || !dev_y || games < 0 || channels < 4 || channels % 4) return XQ_ERR_ARG;
+    if (((uintptr_t)dev_wt | (uintptr_t)dev_bias | (uintptr_t)dev_y) & 15) return XQ_ERR_ARG;
+    if (games == 0) return XQ_OK;
+    hipLaunchKernelGGL(k_stem_conv, dim3(games), dim3(256), 0, (hipStream_t)stream, dev_planes, dev_wt, dev_bias, dev_y, channels,
+                       dev_live);
     return xq::launch_status();
 }
 
 extern "C" int xq_stem_conv(const float *dev_planes, const float *dev_wt, const float *dev_bias, float *dev_y, int games,
                             int channels, void *stream) {
-    if (!dev_planes || !dev_wt || !dev_bias || !dev_y || games < 0 || channels < 4 || channels % 4) return XQ_ERR_ARG;
-    if (((uintptr_t)dev_wt | (uintptr_t)dev_bias | (uintptr_t)dev_y) & 15) return XQ_ERR_ARG;
+    return stem_conv(dev_planes, dev_wt, dev_bias, dev_y, games, channels, nullptr, stream);
+}
+
+extern "C" int xq_stem_conv_live(const float *dev_planes, const float *dev_wt, const float *dev_bias, float *dev_y, int capacity,
+                                 const int32_t *dev_n, int channels, void *stream) {
+    if (capacity < 0) return XQ_ERR_ARG;
+    if (capacity == 0) return XQ_OK;
+    if (!dev_n) return XQ_ERR_ARG;
+    return stem_conv(dev_planes, dev_wt, dev_bias, dev_y, capacity, channels, dev_n, stream);
+}
+
+static int policy_head_legal(const float *dev_feat, const float *dev_w, const float *dev_bias, const uint16_t *dev_moves,
+                             const int32_t *dev_counts, int games, float *dev_out, const int32_t *dev_live, void *stream) {
+    if (games < 0 || (games > 0 && (!dev_feat || !dev_w || !dev_bias || !dev_moves || !dev_counts || !dev_out))) return XQ_ERR_ARG;
+    if (((uintptr_t)dev_feat | (uintptr_t)dev_w) & 15) return XQ_ERR_ARG;
     if (games == 0) return XQ_OK;
-    hipLaunchKernelGGL(k_stem_conv, dim3(games), dim3(256), 0, (hipStream_t)stream, dev_planes, dev_wt, dev_bias, dev_y, channels);
+    hipLaunchKernelGGL(k_policy_legal, dim3((games + 3) / 4), dim3(256), 0, (hipStream_t)stream, dev_feat, dev_w, dev_bias, dev_moves,
+                       dev_counts, games, dev_out, dev_live);
     return xq::launch_status();
 }
 
 extern "C" int xq_policy_head_legal(const float *dev_feat, const float *dev_w, const float *dev_bias, const uint16_t *dev_moves,
                                     const int32_t *dev_counts, int games, float *dev_out, void *stream) {
-    if (games < 0 || (games > 0 && (!dev_feat || !dev_w || !dev_bias || !dev_moves || !dev_counts || !dev_out))) return XQ_ERR_ARG;
-    if (((uintptr_t)dev_feat | (uintptr_t)dev_w) & 15) return XQ_ERR_ARG;
+    return policy_head_legal(dev_feat, dev_w, dev_bias, dev_moves, dev_counts, games, dev_out, nullptr, stream);
+}
+
+extern "C" int xq_policy_head_legal_live(const float *dev_feat, const float *dev_w, const float *dev_bias, const uint16_t *dev_moves,
+                                         const int32_t *dev_counts, int capacity, const int32_t *dev_n, float *dev_out, void *stream) {
+    if (capacity < 0) return XQ_ERR_ARG;
+    if (capacity == 0) return XQ_OK;
+    if (!dev_n) return XQ_ERR_ARG;
+    return policy_head_legal(dev_feat, dev_w, dev_bias, dev_moves, dev_counts, capacity, dev_out, dev_n, stream);
+}
+
+static int value_head(const float *dev_vfeat, const float *dev_w1t, const float *dev_b1, const float *dev_w2, const float *dev_b2,
+                      int games, float *dev_value, const int32_t *dev_live, void *stream) {
+    if (games < 0 || (games > 0 && (!dev_vfeat || !dev_w1t || !dev_b1 || !dev_w2 || !dev_b2 || !dev_value))) return XQ_ERR_ARG;
     if (games == 0) return XQ_OK;
-    hipLaunchKernelGGL(k_policy_legal, dim3((games + 3) / 4), dim3(256), 0, (hipStream_t)stream, dev_feat, dev_w, dev_bias, dev_moves,
-                       dev_counts, games, dev_out);
+    hipLaunchKernelGGL(k_value_head, dim3((games + VGB - 1) / VGB), dim3(128), 0, (hipStream_t)stream, dev_vfeat, dev_w1t, dev_b1,
+                       dev_w2, dev_b2, games, dev_value, dev_live);
     return xq::launch_status();
 }
 
 extern "C" int xq_value_head(const float *dev_vfeat, const float *dev_w1t, const float *dev_b1, const float *dev_w2,
                              const float *dev_b2, int games, float *dev_value, void *stream) {
-    if (games < 0 || (games > 0 && (!dev_vfeat || !dev_w1t || !dev_b1 || !dev_w2 || !dev_b2 || !dev_value))) return XQ_ERR_ARG;
-    if (games == 0) return XQ_OK;
-    hipLaunchKernelGGL(k_value_head, dim3((games + VGB - 1) / VGB), dim3(128), 0, (hipStream_t)stream, dev_vfeat, dev_w1t, dev_b1,
-                       dev_w2, dev_b2, games, dev_value);
-    return xq::launch_status();
+    return value_head(dev_vfeat, dev_w1t, dev_b1, dev_w2, dev_b2, games, dev_value, nullptr, stream);
+}
+
+extern "C" int xq_value_head_live(const float *dev_vfeat, const float *dev_w1t, const float *dev_b1, const float *dev_w2,
+                                  const float *dev_b2, int capacity, const int32_t *dev_n, float *dev_value, void *stream) {
+    if (capacity < 0) return XQ_ERR_ARG;
+    if (capacity == 0) return XQ_OK;
+    if (!dev_n) return XQ_ERR_ARG;
+    return value_head(dev_vfeat, dev_w1t, dev_b1, dev_w2, dev_b2, capacity, dev_value, dev_n, stream);
 }

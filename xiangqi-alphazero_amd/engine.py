@@ -8,6 +8,15 @@ all enqueued on torch's current stream; no host round-trip per simulation and no
 per-evaluation socket hop, training/inference_server.py:333-349, does not exist here).  torch provides
 device memory, the stream and (optionally) the network; search, rules, sampling and bookkeeping are the
 hand-written kernels.  There is no CPU fallback.
+
+`step()` / `capture_step()` take the PACKED step when the evaluator offers `live_rows` (the HIP evaluators):
+
+    select  ->  compact (the waiting slots, packed to the front, slot order)  ->  evaluator over the first n_live rows
+            ->  scatter back to slot order + expand
+
+The live count never leaves the device, so the packed step records into one HIP graph like the full-width one; once games
+finish (games_target reached: idle slots) the evaluator's work follows the slots that are still playing.  Results are
+identical to the full-width step.  The explicit stage calls (`select`, `evaluate_and_expand`, `expand_legal`) stay full width.
 """
 from __future__ import annotations
 
@@ -81,6 +90,22 @@ class SelfPlayEngine:
         mo, co = int(pm.value) - int(self.ws.data_ptr()), int(pc.value) - int(self.ws.data_ptr())
         self.req_moves = self.ws[mo:mo + self.G * hip.MAXM * 2].view(torch.int16).view(self.G, hip.MAXM)
         self.req_counts = self.ws[co:co + self.G * 4].view(torch.int32)
+        # packed-step buffers (xq_engine_packed): live count, row -> slot map, packed planes / requests, slot-ordered hand-back
+        pb = hip.PackedBuffers()
+        hip.check(self.lib.xq_engine_packed(C.byref(self.h), C.byref(pb)), "xq_engine_packed")
+
+        def ws_view(addr, nbytes, dtype):
+            off = int(addr) - int(self.ws.data_ptr())
+            return self.ws[off:off + nbytes].view(dtype)
+
+        G = self.G
+        self.n_live = ws_view(pb.n_live, 4, torch.int32)
+        self.packed_rows = ws_view(pb.rows, G * 4, torch.int32)
+        self.packed_x = ws_view(pb.x, G * hip.STATE_FLOATS * 4, torch.float32).view(G, 15, 10, 9)
+        self.packed_moves = ws_view(pb.moves, G * hip.MAXM * 2, torch.int16).view(G, hip.MAXM)
+        self.packed_counts = ws_view(pb.counts, G * 4, torch.int32)
+        self.slot_logits = ws_view(pb.slot_logits, G * hip.MAXM * 4, torch.float32).view(G, hip.MAXM)
+        self.slot_value = ws_view(pb.slot_value, G * 4, torch.float32)
         self.steps = 0
         self._graph = None
         self._graph_generation = 0
@@ -128,15 +153,49 @@ class SelfPlayEngine:
             logits, value = ev(x)
             self.expand(logits, value, False)
 
+    def compact(self):
+        """After `select`: pack the slots waiting for an evaluation (xq_engine_compact) into `packed_x`, `packed_moves`,
+        `packed_counts` (rows [0, n_live) valid, slot order; `packed_rows[r]` is row r's slot).  Asynchronous."""
+        hip.check(self.lib.xq_engine_compact(C.byref(self.h), self.nn_input.data_ptr(), hip.stream_ptr(self.device)),
+                  "xq_engine_compact")
+
+    def expand_packed(self, legal_logits: torch.Tensor, value: torch.Tensor):
+        """Expansion from PACKED evaluator outputs (rows [0, n_live) of float32[G, 128] / [G]): scattered back to
+        `slot_logits` / `slot_value` in slot order, then xq_engine_expand_legal (xq_engine_expand_packed)."""
+        if legal_logits.dtype != torch.float32 or value.dtype != torch.float32:
+            raise hip.XqError("legal_logits/value must be float32")
+        legal_logits = legal_logits.contiguous()
+        value = value.contiguous().view(-1)
+        if legal_logits.shape != (self.G, hip.MAXM) or value.shape != (self.G,):
+            raise hip.XqError(f"bad evaluator output shapes {tuple(legal_logits.shape)} {tuple(value.shape)}")
+        hip.check(self.lib.xq_engine_expand_packed(C.byref(self.h), legal_logits.data_ptr(), value.data_ptr(),
+                                                   hip.stream_ptr(self.device)), "xq_engine_expand_packed")
+        self._keep = (self.slot_logits, self.slot_value)    # slot-ordered, as the full-width step's (bench.py --dump-outputs)
+        self._keep_packed = (legal_logits, value)          # keep alive until the stream has consumed them
+
+    @property
+    def path(self) -> str:
+        """The step `step()` runs: "packed" when the evaluator evaluates a device-side live row count, else "full"."""
+        return "packed" if getattr(self.evaluator, "live_rows", False) else "full"
+
+    def _one_step(self):
+        if self.path == "packed":
+            self.select()
+            self.compact()
+            ll, value = self.evaluator.evaluate_legal(self.packed_x, self.packed_moves, self.packed_counts, n_live=self.n_live)
+            self.expand_packed(ll, value)
+        else:
+            self.evaluate_and_expand(self.select())
+
     def step(self):
         """select -> evaluator -> expand, all asynchronous on the current stream (one graph launch once `capture_step`
-        has recorded it)."""
+        has recorded it); the packed step (module docstring) when the evaluator has `live_rows`."""
         if self._graph is not None and getattr(self.evaluator, "generation", 0) != self._graph_generation:
             self.release_graph()                       # the evaluator reallocated a buffer: the recording holds stale pointers
         if self._graph is not None:
             self._graph.replay()
         else:
-            self.evaluate_and_expand(self.select())
+            self._one_step()
         self.steps += 1
 
     def capture_step(self, warmup: int = 2) -> bool:
@@ -150,7 +209,7 @@ class SelfPlayEngine:
         if self.evaluator is None:
             raise hip.XqError("capture_step needs an evaluator")
         for _ in range(warmup):
-            self.evaluate_and_expand(self.select())
+            self._one_step()
             self.steps += 1
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
@@ -158,7 +217,7 @@ class SelfPlayEngine:
             # thread_local: other threads of the process (the RCCL watchdog of a multi-rank run polls events) must not
             # invalidate the capture
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self.evaluate_and_expand(self.select())
+                self._one_step()
         except hip.XqError:
             raise                                      # argument / shape / launch errors of our own entry points: never hidden
         except RuntimeError as e:

@@ -56,10 +56,15 @@ class EngineStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in
                 ("sims", "terminal_sims", "leaf_evals", "root_evals", "moves_played", "games_finished", "red_wins",
                  "black_wins", "draws", "plies_finished", "nodes_created", "depth_sum", "children_scanned", "resigns",
-                 "samples_written", "samples_dropped", "overflow", "games_started")] + [("reserved", C.c_uint64 * 14)]
+                 "samples_written", "samples_dropped", "overflow", "games_started", "rows_evaluated")] + [("reserved", C.c_uint64 * 13)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class PackedBuffers(C.Structure):
+    """xq_engine_packed_buffers: device addresses of the packed step's buffers in the engine workspace."""
+    _fields_ = [(n, C.c_void_p) for n in ("n_live", "rows", "x", "moves", "counts", "slot_logits", "slot_value")]
 
 
 _lib = None
@@ -117,6 +122,15 @@ def lib():
     L.xq_value_head.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
     L.xq_engine_requests.argtypes = [C.POINTER(Engine), C.POINTER(vp), C.POINTER(vp)]
     L.xq_engine_expand_legal.argtypes = [C.POINTER(Engine), vp, vp, vp]
+    L.xq_engine_compact.argtypes = [C.POINTER(Engine), vp, vp]
+    L.xq_engine_packed.argtypes = [C.POINTER(Engine), C.POINTER(PackedBuffers)]
+    L.xq_engine_expand_packed.argtypes = [C.POINTER(Engine), vp, vp, vp]
+    L.xq_stem_conv_live.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]
+    L.xq_heads_1x1_live.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, vp, i32, vp]
+    L.xq_wino_conv3x3_live.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, i32, vp]
+    L.xq_wino_conv3x3_bf16_live.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, i32, vp]
+    L.xq_policy_head_legal_live.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.xq_value_head_live.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -128,7 +142,9 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_bias_act", "xq_stem_conv", "xq_heads_1x1", "xq_wino_weight_bytes", "xq_wino_conv3x3", "xq_samples_to_batch",
            "xq_policy_head_legal", "xq_value_head", "xq_engine_requests", "xq_engine_expand_legal", "xq_engine_drain_device",
            "xq_wino_weight_bytes_bf16", "xq_wino_conv3x3_bf16", "xq_wino_transform_filters",
-           "xq_bn_scratch_bytes", "xq_bn_train_forward", "xq_bn_train_backward", "xq_wino_wgrad_scratch_bytes", "xq_wino_wgrad"]
+           "xq_bn_scratch_bytes", "xq_bn_train_forward", "xq_bn_train_backward", "xq_wino_wgrad_scratch_bytes", "xq_wino_wgrad",
+           "xq_engine_compact", "xq_engine_packed", "xq_engine_expand_packed", "xq_stem_conv_live", "xq_heads_1x1_live",
+           "xq_wino_conv3x3_live", "xq_wino_conv3x3_bf16_live", "xq_policy_head_legal_live", "xq_value_head_live"]
 
 
 def check(rc: int, what: str):
@@ -242,26 +258,50 @@ def stem_weights(w_in: torch.Tensor) -> torch.Tensor:
     return w_in.detach().permute(1, 2, 3, 0).reshape(135, c).contiguous()
 
 
-def stem_conv(planes: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-    """planes float32[G,15,10,9] contiguous -> out float32[G,90,C] = relu(conv3x3(planes) + bias), NHWC."""
+def _live_ptr(n_live, device) -> int:
+    """The live-row count of the *_live entry points: an int32 scalar tensor on the computing device (read there, never
+    on the host)."""
+    if n_live.dtype != torch.int32 or n_live.numel() != 1 or n_live.device != device:
+        raise XqError("n_live: one int32 element on the computing device required")
+    return n_live.data_ptr()
+
+
+def stem_conv(planes: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, n_live=None) -> torch.Tensor:
+    """planes float32[G,15,10,9] contiguous -> out float32[G,90,C] = relu(conv3x3(planes) + bias), NHWC.  With `n_live`
+    (int32 device scalar) only boards [0, n_live) are read and written (xq_stem_conv_live); G is the capacity."""
     g = planes.shape[0]
     c = wt.shape[1]
     if planes.shape[1:] != (15, 10, 9) or not planes.is_contiguous() or wt.shape != (135, c) or not wt.is_contiguous() \
             or out.shape != (g, 90, c) or not out.is_contiguous() or planes.dtype != torch.float32:
         raise XqError("stem_conv: planes [G,15,10,9], wt [135,C], out [G,90,C] contiguous float32 required")
+    if n_live is not None:
+        check(lib().xq_stem_conv_live(planes.data_ptr(), wt.data_ptr(), bias.data_ptr(), out.data_ptr(), g,
+                                      _live_ptr(n_live, planes.device), c, stream_ptr(planes.device)), "xq_stem_conv_live")
+        return out
     check(lib().xq_stem_conv(planes.data_ptr(), wt.data_ptr(), bias.data_ptr(), out.data_ptr(), g, c,
                              stream_ptr(planes.device)), "xq_stem_conv")
     return out
 
 
-def heads_1x1(rows: torch.Tensor, w: torch.Tensor, bias: torch.Tensor):
+def heads_1x1(rows: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, n_live=None, out=None):
     """rows float32[R, C] (NHWC rows of the tower output), w float32[36, C], bias float32[36] ->
-    (policy features float32[R, 32], value features float32[R, 4]), ReLU applied (model.py:43-62)."""
+    (policy features float32[R, 32], value features float32[R, 4]), ReLU applied (model.py:43-62).  With `n_live` (int32
+    device scalar, in POSITIONS of 90 rows) only rows [0, 90 n_live) are read and written (xq_heads_1x1_live); `out` = (p, v)
+    preallocated."""
     r, c = rows.shape
     if not rows.is_contiguous() or w.shape != (36, c) or not w.is_contiguous() or bias.shape != (36,):
         raise XqError("heads_1x1: rows [R,C] contiguous, w [36,C], bias [36] required")
-    p = torch.empty((r, 32), dtype=torch.float32, device=rows.device)
-    v = torch.empty((r, 4), dtype=torch.float32, device=rows.device)
+    if out is not None:
+        p, v = out
+        if p.shape != (r, 32) or v.shape != (r, 4) or not p.is_contiguous() or not v.is_contiguous():
+            raise XqError("heads_1x1: out = (float32[R,32], float32[R,4]) contiguous")
+    else:
+        p = torch.empty((r, 32), dtype=torch.float32, device=rows.device)
+        v = torch.empty((r, 4), dtype=torch.float32, device=rows.device)
+    if n_live is not None:
+        check(lib().xq_heads_1x1_live(rows.data_ptr(), w.data_ptr(), bias.data_ptr(), p.data_ptr(), v.data_ptr(), r,
+                                      _live_ptr(n_live, rows.device), c, stream_ptr(rows.device)), "xq_heads_1x1_live")
+        return p, v
     check(lib().xq_heads_1x1(rows.data_ptr(), w.data_ptr(), bias.data_ptr(), p.data_ptr(), v.data_ptr(), r, c,
                              stream_ptr(rows.device)), "xq_heads_1x1")
     return p, v
@@ -333,12 +373,18 @@ def wino_transform_weights_bf16(w: torch.Tensor) -> torch.Tensor:
 
 
 def wino_conv3x3_bf16(x: torch.Tensor, u: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, residual=None,
-                      relu: bool = True, reverse: bool = False) -> torch.Tensor:
+                      relu: bool = True, reverse: bool = False, n_live=None) -> torch.Tensor:
     """REDUCED-PRECISION convolution (xq_wino_conv3x3_bf16): x, out, residual float32[B, 90, C]; u from
-    `wino_transform_weights_bf16`."""
+    `wino_transform_weights_bf16`.  `n_live`: as `wino_conv3x3`."""
     b, n, c = x.shape
     if n != 90 or not x.is_contiguous() or not out.is_contiguous() or out.shape != x.shape or u.dtype != torch.bfloat16:
         raise XqError("wino_conv3x3_bf16: float32[B,90,C] contiguous tensors and bf16 weights required")
+    if n_live is not None:
+        check(lib().xq_wino_conv3x3_bf16_live(x.data_ptr(), u.data_ptr(), bias.data_ptr(),
+                                              None if residual is None else residual.data_ptr(), out.data_ptr(), b,
+                                              _live_ptr(n_live, x.device), c, int(relu) | (2 if reverse else 0),
+                                              stream_ptr(x.device)), "xq_wino_conv3x3_bf16_live")
+        return out
     check(lib().xq_wino_conv3x3_bf16(x.data_ptr(), u.data_ptr(), bias.data_ptr(),
                                      None if residual is None else residual.data_ptr(), out.data_ptr(), b, c,
                                      int(relu) | (2 if reverse else 0), stream_ptr(x.device)), "xq_wino_conv3x3_bf16")
@@ -346,13 +392,20 @@ def wino_conv3x3_bf16(x: torch.Tensor, u: torch.Tensor, bias: torch.Tensor, out:
 
 
 def wino_conv3x3(x: torch.Tensor, u: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, residual=None,
-                 relu: bool = True, reverse: bool = False) -> torch.Tensor:
+                 relu: bool = True, reverse: bool = False, n_live=None) -> torch.Tensor:
     """x, out, residual: float32[B, 90, C] contiguous (NHWC); out must not alias x / residual.  `reverse` walks the batch
     back to front (identical results; see XQ_CONV_REVERSE).  The kernel variant follows the weight layout: `u` from
-    `wino_transform_weights(w, 128)` (shape [C/128, ...]) selects XQ_CONV_WIDE."""
+    `wino_transform_weights(w, 128)` (shape [C/128, ...]) selects XQ_CONV_WIDE.  With `n_live` (int32 device scalar) B is the
+    capacity and only boards [0, n_live) are read and written (xq_wino_conv3x3_live)."""
     b, n, c = x.shape
     if n != 90 or not x.is_contiguous() or not out.is_contiguous() or out.shape != x.shape:
         raise XqError("wino_conv3x3: float32[B,90,C] contiguous tensors required")
+    flags = int(relu) | (2 if reverse else 0) | (4 if u.shape[4] == 128 else 0)
+    if n_live is not None:
+        check(lib().xq_wino_conv3x3_live(x.data_ptr(), u.data_ptr(), bias.data_ptr(),
+                                         None if residual is None else residual.data_ptr(), out.data_ptr(), b,
+                                         _live_ptr(n_live, x.device), c, flags, stream_ptr(x.device)), "xq_wino_conv3x3_live")
+        return out
     check(lib().xq_wino_conv3x3(x.data_ptr(), u.data_ptr(), bias.data_ptr(),
                                 None if residual is None else residual.data_ptr(), out.data_ptr(), b, c,
                                 int(relu) | (2 if reverse else 0) | (4 if u.shape[4] == 128 else 0), stream_ptr(x.device)),
@@ -362,7 +415,7 @@ def wino_conv3x3(x: torch.Tensor, u: torch.Tensor, bias: torch.Tensor, out: torc
 
 
 def policy_head_legal(feat: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, moves: torch.Tensor, counts: torch.Tensor,
-                      out: torch.Tensor) -> torch.Tensor:
+                      out: torch.Tensor, n_live=None) -> torch.Tensor:
     """feat float32[G, 2880] (NHWC policy features), w float32[8100, 2880] (columns in that order), bias float32[8100],
     moves int16[G, 128] (uint16 action ids), counts int32[G] -> out float32[G, 128]: logits of the listed moves only."""
     g = feat.shape[0]
@@ -370,17 +423,31 @@ def policy_head_legal(feat: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, m
             or out.shape != (g, MAXM) or counts.dtype != torch.int32 or moves.element_size() != 2 \
             or not (feat.is_contiguous() and w.is_contiguous() and moves.is_contiguous() and counts.is_contiguous() and out.is_contiguous()):
         raise XqError("policy_head_legal: feat [G,2880], w [8100,2880], moves 16-bit [G,128], counts int32 [G], out [G,128]")
+    if n_live is not None:
+        check(lib().xq_policy_head_legal_live(feat.data_ptr(), w.data_ptr(), bias.data_ptr(), moves.data_ptr(), counts.data_ptr(), g,
+                                              _live_ptr(n_live, feat.device), out.data_ptr(), stream_ptr(feat.device)),
+              "xq_policy_head_legal_live")
+        return out
     check(lib().xq_policy_head_legal(feat.data_ptr(), w.data_ptr(), bias.data_ptr(), moves.data_ptr(), counts.data_ptr(), g,
                                      out.data_ptr(), stream_ptr(feat.device)), "xq_policy_head_legal")
     return out
 
 
-def value_head(vfeat: torch.Tensor, w1t: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
-    """vfeat float32[G, 360] (NHWC value features), w1t float32[360, 128], b1 [128], w2 [128], b2 [1] -> value float32[G]."""
+def value_head(vfeat: torch.Tensor, w1t: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, n_live=None,
+               out=None) -> torch.Tensor:
+    """vfeat float32[G, 360] (NHWC value features), w1t float32[360, 128], b1 [128], w2 [128], b2 [1] -> value float32[G].
+    With `n_live` (int32 device scalar) only games [0, n_live) are read and written (xq_value_head_live); `out` preallocated."""
     g = vfeat.shape[0]
     if vfeat.shape != (g, 360) or w1t.shape != (360, 128) or not vfeat.is_contiguous() or not w1t.is_contiguous():
         raise XqError("value_head: vfeat [G,360], w1t [360,128] contiguous required")
-    out = torch.empty(g, dtype=torch.float32, device=vfeat.device)
+    if out is None:
+        out = torch.empty(g, dtype=torch.float32, device=vfeat.device)
+    elif out.shape != (g,) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise XqError("value_head: out float32[G] contiguous")
+    if n_live is not None:
+        check(lib().xq_value_head_live(vfeat.data_ptr(), w1t.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), g,
+                                       _live_ptr(n_live, vfeat.device), out.data_ptr(), stream_ptr(vfeat.device)), "xq_value_head_live")
+        return out
     check(lib().xq_value_head(vfeat.data_ptr(), w1t.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), g, out.data_ptr(),
                               stream_ptr(vfeat.device)), "xq_value_head")
     return out

@@ -26,6 +26,9 @@ from .sample_format import reachable_actions
 
 class HipResNetEvaluator:
     conv_dtype = "f32"               # HipBf16Evaluator: "bf16" (reduced precision, never the default)
+    # evaluate_legal(..., n_live=) runs over the first *n_live rows only, the count read on the device (the *_live kernels):
+    # SelfPlayEngine then packs the pending evaluations of a step and evaluates just those (its packed step)
+    live_rows = True
 
     def __init__(self, net: XiangqiNet, device="cuda", engine_policy: bool = False):
         self.engine_policy = bool(engine_policy)
@@ -48,6 +51,8 @@ class HipResNetEvaluator:
         self.alternate_order = os.environ.get("XQ_CONV_ALTERNATE", "1") != "0"
         # conv kernel variant: 128 output channels per workgroup (XQ_CONV_WIDE) where the width allows, else 64
         self.micro_batch = int(os.environ.get("XQ_CONV_MICRO_BATCH", "0"))
+        if self.micro_batch:
+            self.live_rows = False                                  # the micro-batch trial keeps the full-width step
         want = os.environ.get("XQ_CONV_BLOCK", "")                 # "64" / "128": force one variant (A/B runs)
         if want in ("64", "128") and self.C % int(want) == 0:
             self.co_blocks = [int(want)]
@@ -138,9 +143,11 @@ class HipResNetEvaluator:
         return logits, value
 
     @torch.no_grad()
-    def _tower(self, x: torch.Tensor):
+    def _tower(self, x: torch.Tensor, n_live=None):
         b = x.shape[0]
         x = x.contiguous()
+        if n_live is not None:
+            return self._tower_once(x, n_live)
         mb = self.micro_batch
         if mb and b > mb:
             # trial (XQ_CONV_MICRO_BATCH): the tower run over micro-batches whose activations (3 buffers x mb x 90 x C x 4 B) stay
@@ -152,46 +159,49 @@ class HipResNetEvaluator:
             return torch.cat(ps), torch.cat(vs)
         return self._tower_once(x)
 
-    def _tower_once(self, x: torch.Tensor):
+    def _tower_once(self, x: torch.Tensor, n_live=None):
+        """`n_live` (int32 device scalar): only the first *n_live of the b rows are computed; the kernel variant is still
+        chosen from the capacity b, so launch grids and a recorded graph do not depend on the count."""
         b = x.shape[0]
         t0, t1, t2, t3 = self._buffers(b)
-        h = hip.stem_conv(x, self.wt_in, self.b_in, t0)
+        h = hip.stem_conv(x, self.wt_in, self.b_in, t0, n_live)
         free = [t1, t2, t3]
         rev = self.alternate_order                                   # launches alternate front-to-back / back-to-front:
         for u1, b1, u2, b2 in self._blocks_for(b):                   # each starts on what the previous one wrote last
             y = next(t for t in free if t.data_ptr() != h.data_ptr())
-            self._conv(h, u1, b1, y, None, rev)
+            self._conv(h, u1, b1, y, None, rev, n_live)
             o = next(t for t in free if t.data_ptr() != h.data_ptr() and t.data_ptr() != y.data_ptr())
-            self._conv(y, u2, b2, o, h, False)
+            self._conv(y, u2, b2, o, h, False, n_live)
             h = o
-        return hip.heads_1x1(h.view(b * 90, self.C), self.w_pv, self.b_pv)
+        return hip.heads_1x1(h.view(b * 90, self.C), self.w_pv, self.b_pv, n_live)
 
     @torch.no_grad()
-    def evaluate_legal(self, x: torch.Tensor, moves: torch.Tensor, counts: torch.Tensor):
+    def evaluate_legal(self, x: torch.Tensor, moves: torch.Tensor, counts: torch.Tensor, n_live=None):
         """The engine's protocol (engine.evaluate_and_expand): logits of the ordered legal moves of every pending
         evaluation, float32[G, 128], and the value float32[G] -- every kernel hand-written, no dense policy row.
-        Rows of slots that asked for nothing (count 0) are left as they were."""
+        Rows of slots that asked for nothing (count 0) are left as they were.  With `n_live` (int32 device scalar, the
+        engine's packed step) the whole evaluation covers rows [0, *n_live) only; later rows of both outputs are not written."""
         b = x.shape[0]
-        p, v = self._tower(x)
+        p, v = self._tower(x, n_live)
         if self._legal is None or self._legal.shape[0] < b:
             self.generation += self._legal is not None
             self._legal = torch.zeros((b, hip.MAXM), dtype=torch.float32, device=self.device)
         legal = self._legal[:b]
-        hip.policy_head_legal(p.view(b, 2880), self.fc_p_w, self.fc_p_b, moves, counts, legal)
-        value = hip.value_head(v.view(b, 360), self.fc_v1_wt, self.fc_v1_b, self.fc_v2_vec, self.fc_v2_b)
+        hip.policy_head_legal(p.view(b, 2880), self.fc_p_w, self.fc_p_b, moves, counts, legal, n_live)
+        value = hip.value_head(v.view(b, 360), self.fc_v1_wt, self.fc_v1_b, self.fc_v2_vec, self.fc_v2_b, n_live)
         return legal, value
 
     _conv_launch = staticmethod(hip.wino_conv3x3)
 
-    def _conv(self, x, u, b, out, residual, reverse=False):
+    def _conv(self, x, u, b, out, residual, reverse=False, n_live=None):
         if self.timing:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            self._conv_launch(x, u, b, out, residual, True, reverse)
+            self._conv_launch(x, u, b, out, residual, True, reverse, n_live)
             e1.record()
             self._events.append((e0, e1))
         else:
-            self._conv_launch(x, u, b, out, residual, True, reverse)
+            self._conv_launch(x, u, b, out, residual, True, reverse, n_live)
 
     def roofline(self, batch: int, nn_ms: float, launch_ms: float = None):
         """bench.py roofline object for the dominant kernel (k_wino_conv): algorithmic FLOPs of the 3x3 convolution
