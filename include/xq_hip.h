@@ -347,6 +347,36 @@ int xq_bn_train_backward(const float *dev_dy, const float *dev_x, const float *d
                          const float *dev_save_invstd, long long rows, int channels, int relu, float *dev_dx, float *dev_dresidual,
                          float *dev_dgamma, float *dev_dbeta, void *dev_scratch, void *stream);
 
+/* The same BatchNorm with the statistics of a whole GROUP of ranks (torch.nn.SyncBatchNorm semantics: the data-parallel train step),
+ * split where the host runs its collective.  dev_sums: xq_bn_sync_sums_count(channels) = 2 * channels + 1 doubles on the device,
+ * 8-byte aligned.  A stats call writes this rank's per-channel sums, the host all-reduces them (SUM, float64) over the group, the
+ * apply call reads the group's:
+ *   forward :  xq_bn_sync_forward_stats   -> sums = [sum x (C) | sum x^2 (C) | rows]
+ *              all-reduce(sums)
+ *              xq_bn_sync_forward_apply   -> y, save_mean / save_invstd of the group's batch, running statistics updated with the
+ *                                            group's count n (unbiased variance var * n / (n - 1)), num_batches_tracked += 1;
+ *   backward:  xq_bn_sync_backward_stats  -> sums = [sum g (C) | sum g * xhat (C) | rows]; dev_dgamma / dev_dbeta receive this rank's
+ *                                            LOCAL sums (what SyncBatchNorm's backward returns; the data-parallel gradient all-reduce
+ *                                            combines them with the other gradients)
+ *              all-reduce(sums)
+ *              xq_bn_sync_backward_apply  -> dx with the group's sum g, sum g * xhat and n; dev_dresidual (nullable) receives g.
+ * rows is this rank's row count in every call (ranks may hold different counts); dev_scratch: xq_bn_scratch_bytes(channels) bytes, free
+ * again when the stats call's kernels have run.  Argument rules as the fused entry points.  With one rank (the all-reduce leaves the sums
+ * as they are) every output is bit-identical to xq_bn_train_forward / xq_bn_train_backward: the same partials, summed in the same order,
+ * the same finalize arithmetic. */
+size_t xq_bn_sync_sums_count(int channels);
+int xq_bn_sync_forward_stats(const float *dev_x, long long rows, int channels, double *dev_sums, void *dev_scratch, void *stream);
+int xq_bn_sync_forward_apply(const float *dev_x, const float *dev_residual, const float *dev_gamma, const float *dev_beta,
+                             float *dev_running_mean, float *dev_running_var, float momentum, float eps, long long rows, int channels,
+                             int relu, const double *dev_sums, float *dev_y, float *dev_save_mean, float *dev_save_invstd,
+                             long long *dev_batches_tracked, void *stream);
+int xq_bn_sync_backward_stats(const float *dev_dy, const float *dev_x, const float *dev_y, const float *dev_save_mean,
+                              const float *dev_save_invstd, long long rows, int channels, int relu, double *dev_sums, float *dev_dgamma,
+                              float *dev_dbeta, void *dev_scratch, void *stream);
+int xq_bn_sync_backward_apply(const float *dev_dy, const float *dev_x, const float *dev_y, const float *dev_gamma, const float *dev_save_mean,
+                              const float *dev_save_invstd, long long rows, int channels, int relu, const double *dev_sums, float *dev_dx,
+                              float *dev_dresidual, void *stream);
+
 /* Weight gradient of y = conv3x3(x, w) (stride 1, pad 1, C -> C; what torch autograd's convolution_backward returns for
  * ResBlock.conv1/conv2.weight under training/train.py:376-447), in the Winograd domain of xq_wino_conv3x3 on the fp32 MFMA:
  *   dev_x, dev_dy : float32[batch][90][channels] (NHWC);  dev_dw : float32[channels][channels][3][3] (torch's layout), overwritten;

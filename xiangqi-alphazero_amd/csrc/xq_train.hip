@@ -189,6 +189,81 @@ __global__ __launch_bounds__(256) void k_bn_dx(const float *__restrict__ DY, con
     }
 }
 
+// ---- cross-rank (SyncBatchNorm) form: the same partials and the same reduction, cut at the per-channel sums so that the host can
+// all-reduce them between two launches.  sums[0, C) = a, sums[C, 2C) = b (the k_bn_partial meanings), sums[2C] = rows.  After a SUM
+// all-reduce they are the whole group's; with one rank the kernels below compute exactly what the fused ones do.
+
+// grid C / 4 workgroups of 256 threads (reduce_partials); dgamma / dbeta (backward, nullable): this rank's local values, as
+// k_bn_bwd_finalize writes them
+__global__ __launch_bounds__(256) void k_bn_sums(const double *__restrict__ part, long long rows, int C, double *__restrict__ sums,
+                                                  float *__restrict__ dgamma, float *__restrict__ dbeta) {
+    double s, q;
+    reduce_partials(part, C, s, q);
+    if (blockIdx.x == 0 && threadIdx.x == 0) sums[2 * C] = (double)rows;
+    if (threadIdx.x >= 4) return;
+    const int c = blockIdx.x * 4 + threadIdx.x;
+    sums[c] = s;
+    sums[C + c] = q;
+    if (dgamma != nullptr) {
+        dbeta[c] = (float)s;
+        dgamma[c] = (float)q;
+    }
+}
+
+// k_bn_fwd_finalize's arithmetic on the (all-reduced) sums, n = sums[2C]: grid C / 64 workgroups of 64 threads, one channel each
+__global__ __launch_bounds__(64) void k_bn_fwd_finalize_sums(const double *__restrict__ sums, int C, float momentum, float eps,
+                                                              float *__restrict__ run_mean, float *__restrict__ run_var,
+                                                              float *__restrict__ save_mean, float *__restrict__ save_invstd,
+                                                              long long *__restrict__ batches_tracked) {
+    if (batches_tracked != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *batches_tracked += 1;
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    const double s = sums[c], q = sums[C + c];
+    const double n = sums[2 * C], m = s / n;
+    double var = q / n - m * m;
+    if (var < 0.0) var = 0.0;
+    save_mean[c] = (float)m;
+    save_invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (run_mean != nullptr) {
+        const double unb = n > 1.0 ? var * n / (n - 1.0) : var;        // unbiased with the GROUP's count, as SyncBatchNorm does
+        run_mean[c] = (float)((1.0 - (double)momentum) * (double)run_mean[c] + (double)momentum * m);
+        run_var[c] = (float)((1.0 - (double)momentum) * (double)run_var[c] + (double)momentum * unb);
+    }
+}
+
+// k_bn_dx with dbeta, dgamma and the row count taken from the (all-reduced) sums, converted exactly as k_bn_bwd_finalize and k_bn_dx do
+__global__ __launch_bounds__(256) void k_bn_dx_sums(const float *__restrict__ DY, const float *__restrict__ X, const float *__restrict__ Yout,
+                                                    const float *__restrict__ gamma, const float *__restrict__ mean,
+                                                    const float *__restrict__ invstd, const double *__restrict__ sums, long long quads, int C,
+                                                    int relu, float *__restrict__ DX, float *__restrict__ DR) {
+    const long long stride = (long long)gridDim.x * 256;
+    const float inv_n = (float)(1.0 / sums[2 * C]);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < quads; i += stride) {
+        const int c = (int)((i * 4) % C);
+        f32x4 g = *(const f32x4 *)(DY + i * 4);
+        if (relu) {
+            const f32x4 y = *(const f32x4 *)(Yout + i * 4);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = y[k] > 0.0f ? g[k] : 0.0f;
+        }
+        const f32x4 x = *(const f32x4 *)(X + i * 4);
+        const f32x4 mu = *(const f32x4 *)(mean + c), is = *(const f32x4 *)(invstd + c), ga = *(const f32x4 *)(gamma + c);
+        f32x4 dg, db;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            db[k] = (float)sums[c + k];
+            dg[k] = (float)sums[C + c + k];
+        }
+        f32x4 dx;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float xh = (x[k] - mu[k]) * is[k];
+            dx[k] = ga[k] * is[k] * (g[k] - db[k] * inv_n - xh * dg[k] * inv_n);
+        }
+        *(f32x4 *)(DX + i * 4) = dx;
+        if (DR != nullptr) *(f32x4 *)(DR + i * 4) = g;
+    }
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // Weight gradient of the 3x3 convolution in the Winograd domain (the transpose of xq_conv.hip's algorithm):
@@ -492,6 +567,69 @@ int xq_bn_train_backward(const float *dev_dy, const float *dev_x, const float *d
     const int grid = (int)((quads + 255) / 256 < 4096 ? (quads + 255) / 256 : 4096);
     hipLaunchKernelGGL(k_bn_dx, dim3(grid), dim3(256), 0, s, dev_dy, dev_x, dev_y, dev_gamma, dev_save_mean, dev_save_invstd, dev_dgamma,
                        dev_dbeta, quads, rows, channels, relu, dev_dx, dev_dresidual);
+    return xq::launch_status();
+}
+
+size_t xq_bn_sync_sums_count(int channels) { return channels > 0 ? (size_t)2 * channels + 1 : 0; }
+
+int xq_bn_sync_forward_stats(const float *dev_x, long long rows, int channels, double *dev_sums, void *dev_scratch, void *stream) {
+    if (!dev_x || !dev_sums || !dev_scratch || !bn_args_ok(rows, channels)) return XQ_ERR_ARG;
+    if ((((uintptr_t)dev_x | (uintptr_t)dev_scratch) & 15) || ((uintptr_t)dev_sums & 7)) return XQ_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)dev_scratch;
+    hipLaunchKernelGGL(k_bn_partial<0>, dim3(NSEG), dim3(256), 0, s, dev_x, nullptr, nullptr, nullptr, nullptr, rows, channels, 0, part);
+    hipLaunchKernelGGL(k_bn_sums, dim3(channels / 4), dim3(256), 0, s, part, rows, channels, dev_sums, nullptr, nullptr);
+    return xq::launch_status();
+}
+
+int xq_bn_sync_forward_apply(const float *dev_x, const float *dev_residual, const float *dev_gamma, const float *dev_beta,
+                             float *dev_running_mean, float *dev_running_var, float momentum, float eps, long long rows, int channels,
+                             int relu, const double *dev_sums, float *dev_y, float *dev_save_mean, float *dev_save_invstd,
+                             long long *dev_batches_tracked, void *stream) {
+    if (!dev_x || !dev_gamma || !dev_beta || !dev_y || !dev_save_mean || !dev_save_invstd || !dev_sums) return XQ_ERR_ARG;
+    if (!bn_args_ok(rows, channels) || (dev_running_mean == nullptr) != (dev_running_var == nullptr)) return XQ_ERR_ARG;
+    if ((((uintptr_t)dev_x | (uintptr_t)dev_residual | (uintptr_t)dev_y | (uintptr_t)dev_gamma | (uintptr_t)dev_beta |
+          (uintptr_t)dev_save_mean | (uintptr_t)dev_save_invstd) & 15) || ((uintptr_t)dev_sums & 7))
+        return XQ_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_bn_fwd_finalize_sums, dim3(channels / 64), dim3(64), 0, s, dev_sums, channels, momentum, eps, dev_running_mean,
+                       dev_running_var, dev_save_mean, dev_save_invstd, dev_batches_tracked);
+    const long long quads = rows * channels / 4;
+    const int grid = (int)((quads + 255) / 256 < 4096 ? (quads + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_bn_apply, dim3(grid), dim3(256), 0, s, dev_x, dev_residual, dev_gamma, dev_beta, dev_save_mean, dev_save_invstd,
+                       quads, channels, relu, dev_y);
+    return xq::launch_status();
+}
+
+int xq_bn_sync_backward_stats(const float *dev_dy, const float *dev_x, const float *dev_y, const float *dev_save_mean,
+                              const float *dev_save_invstd, long long rows, int channels, int relu, double *dev_sums, float *dev_dgamma,
+                              float *dev_dbeta, void *dev_scratch, void *stream) {
+    if (!dev_dy || !dev_x || !dev_save_mean || !dev_save_invstd || !dev_sums || !dev_dgamma || !dev_dbeta || !dev_scratch)
+        return XQ_ERR_ARG;
+    if (!bn_args_ok(rows, channels) || (relu && !dev_y)) return XQ_ERR_ARG;
+    if ((((uintptr_t)dev_dy | (uintptr_t)dev_x | (uintptr_t)dev_y | (uintptr_t)dev_save_mean | (uintptr_t)dev_save_invstd |
+          (uintptr_t)dev_dgamma | (uintptr_t)dev_dbeta | (uintptr_t)dev_scratch) & 15) || ((uintptr_t)dev_sums & 7))
+        return XQ_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)dev_scratch;
+    hipLaunchKernelGGL(k_bn_partial<1>, dim3(NSEG), dim3(256), 0, s, dev_x, dev_dy, dev_y, dev_save_mean, dev_save_invstd, rows, channels,
+                       relu, part);
+    hipLaunchKernelGGL(k_bn_sums, dim3(channels / 4), dim3(256), 0, s, part, rows, channels, dev_sums, dev_dgamma, dev_dbeta);
+    return xq::launch_status();
+}
+
+int xq_bn_sync_backward_apply(const float *dev_dy, const float *dev_x, const float *dev_y, const float *dev_gamma, const float *dev_save_mean,
+                              const float *dev_save_invstd, long long rows, int channels, int relu, const double *dev_sums, float *dev_dx,
+                              float *dev_dresidual, void *stream) {
+    if (!dev_dy || !dev_x || !dev_gamma || !dev_save_mean || !dev_save_invstd || !dev_sums || !dev_dx) return XQ_ERR_ARG;
+    if (!bn_args_ok(rows, channels) || (relu && !dev_y)) return XQ_ERR_ARG;
+    if ((((uintptr_t)dev_dy | (uintptr_t)dev_x | (uintptr_t)dev_y | (uintptr_t)dev_dx | (uintptr_t)dev_dresidual | (uintptr_t)dev_gamma |
+          (uintptr_t)dev_save_mean | (uintptr_t)dev_save_invstd) & 15) || ((uintptr_t)dev_sums & 7))
+        return XQ_ERR_ARG;
+    const long long quads = rows * channels / 4;
+    const int grid = (int)((quads + 255) / 256 < 4096 ? (quads + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_bn_dx_sums, dim3(grid), dim3(256), 0, (hipStream_t)stream, dev_dy, dev_x, dev_y, dev_gamma, dev_save_mean,
+                       dev_save_invstd, dev_sums, quads, channels, relu, dev_dx, dev_dresidual);
     return xq::launch_status();
 }
 

@@ -115,6 +115,12 @@ def lib():
     L.xq_bn_scratch_bytes.restype = C.c_size_t
     L.xq_bn_train_forward.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_longlong, i32, i32, vp, vp, vp, vp, vp, vp]
     L.xq_bn_train_backward.argtypes = [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.xq_bn_sync_sums_count.argtypes = [i32]
+    L.xq_bn_sync_sums_count.restype = C.c_size_t
+    L.xq_bn_sync_forward_stats.argtypes = [vp, C.c_longlong, i32, vp, vp, vp]
+    L.xq_bn_sync_forward_apply.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_longlong, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.xq_bn_sync_backward_stats.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, i32, i32, vp, vp, vp, vp, vp]
+    L.xq_bn_sync_backward_apply.argtypes = [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, vp, vp, vp, vp]
     L.xq_wino_weight_bytes_bf16.argtypes = [i32]
     L.xq_wino_weight_bytes_bf16.restype = C.c_size_t
     L.xq_wino_conv3x3_bf16.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
@@ -144,7 +150,9 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_wino_weight_bytes_bf16", "xq_wino_conv3x3_bf16", "xq_wino_transform_filters",
            "xq_bn_scratch_bytes", "xq_bn_train_forward", "xq_bn_train_backward", "xq_wino_wgrad_scratch_bytes", "xq_wino_wgrad",
            "xq_engine_compact", "xq_engine_packed", "xq_engine_expand_packed", "xq_stem_conv_live", "xq_heads_1x1_live",
-           "xq_wino_conv3x3_live", "xq_wino_conv3x3_bf16_live", "xq_policy_head_legal_live", "xq_value_head_live"]
+           "xq_wino_conv3x3_live", "xq_wino_conv3x3_bf16_live", "xq_policy_head_legal_live", "xq_value_head_live",
+           "xq_bn_sync_sums_count", "xq_bn_sync_forward_stats", "xq_bn_sync_forward_apply", "xq_bn_sync_backward_stats",
+           "xq_bn_sync_backward_apply"]
 
 
 def check(rc: int, what: str):

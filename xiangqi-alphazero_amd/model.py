@@ -38,10 +38,13 @@ class ResBlock(nn.Module):
 
     def forward(self, x):
         if self.native_conv and x.is_cuda and x.dtype == torch.float32:
-            from .native_conv import bn_act, bn_supported
+            from .native_conv import bn_act, bn_supported, native_sync_bn, sync_bn_act
             if bn_supported(self.bn1) and bn_supported(self.bn2):      # training mode: BatchNorm + ReLU (+ skip) fused, hand-written
                 y = bn_act(self._conv(self.conv1, x), self.bn1, None, True)
                 return bn_act(self._conv(self.conv2, y), self.bn2, x, True)
+            if native_sync_bn(self.bn1) and native_sync_bn(self.bn2):  # the data-parallel step (SyncBatchNorm marked by prepare_ddp)
+                y = sync_bn_act(self._conv(self.conv1, x), self.bn1, None, True)
+                return sync_bn_act(self._conv(self.conv2, y), self.bn2, x, True)
         y = F.relu(self.bn1(self._conv(self.conv1, x)))
         y = self.bn2(self._conv(self.conv2, y))
         return F.relu(y + x)
@@ -92,9 +95,11 @@ class XiangqiNet(nn.Module):
         h = None
         if self.res_blocks and self.res_blocks[0].native_conv and x.is_cuda and x.dtype == torch.float32:
             x = x.contiguous(memory_format=torch.channels_last)
-            from .native_conv import bn_act, bn_supported
+            from .native_conv import bn_act, bn_supported, native_sync_bn, sync_bn_act
             if bn_supported(self.input_conv[1]):
                 h = bn_act(self.input_conv[0](x), self.input_conv[1], None, True)
+            elif native_sync_bn(self.input_conv[1]):
+                h = sync_bn_act(self.input_conv[0](x), self.input_conv[1], None, True)
         if h is None:
             h = self.input_conv(x)
         for blk in self.res_blocks:

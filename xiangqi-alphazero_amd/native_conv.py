@@ -10,6 +10,10 @@ trains through torch.nn.Conv2d, training/train.py:376-447 over model.py:20-36).
 `BnAct.apply(...)` / `bn_act(x, bn, residual, relu)` is BatchNorm2d in TRAINING mode fused with the ReLU and the skip-add that follow it in a
 ResBlock (`xq_bn_train_forward` / `xq_bn_train_backward`, csrc/xq_train.hip): batch statistics and every reduction of the backward pass in
 float64 partial sums reduced in a fixed order, running statistics updated in place as torch.nn.BatchNorm2d does.
+`SyncBnAct.apply(...)` / `sync_bn_act(x, bn, residual, relu)` is the same for a torch.nn.SyncBatchNorm (the data-parallel step): the
+statistics of the whole process group, as SyncBatchNorm computes them.  Each direction is a stats launch, a float64 all-reduce of the
+2 C + 1 per-channel sums over `bn.process_group`, and an apply launch (`xq_bn_sync_*`); with one rank every output is bit-identical to
+`BnAct`'s.
 No CPU fallback: the functions raise off the GPU; `ResBlock` only routes here when `native_conv` is set and the input is a CUDA tensor.
 """
 from __future__ import annotations
@@ -147,3 +151,91 @@ def bn_act(x: torch.Tensor, bn: torch.nn.BatchNorm2d, residual=None, relu: bool 
     if nbt.dtype != torch.int64 or not nbt.is_cuda:
         raise hip.XqError("bn_act: num_batches_tracked must be an int64 tensor on the GPU")
     return BnAct.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, relu, nbt)
+
+
+def _all_reduce_sums(sums: torch.Tensor, group) -> None:
+    import torch.distributed as dist
+    dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+
+
+class SyncBnAct(torch.autograd.Function):
+    """BnAct with the batch statistics of every rank of `group` (torch.nn.SyncBatchNorm semantics): dx from the group's sums and count,
+    dgamma / dbeta this rank's local sums (DistributedDataParallel averages them with the other gradients, as it does for SyncBatchNorm)."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, momentum: float, eps: float, relu: bool, batches_tracked, group):
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+            raise hip.XqError("SyncBnAct: float32 [B, C, H, W] on the GPU")
+        b, c, h, w = x.shape
+        L = hip.lib()
+        xv = x.permute(0, 2, 3, 1)
+        xv = xv if xv.is_contiguous() else xv.contiguous()
+        rv = None
+        if residual is not None:
+            rv = residual.permute(0, 2, 3, 1)
+            rv = rv if rv.is_contiguous() else rv.contiguous()
+        y = torch.empty_like(xv)
+        mean = torch.empty(c, dtype=torch.float32, device=x.device)
+        invstd = torch.empty_like(mean)
+        sums = torch.empty(L.xq_bn_sync_sums_count(c), dtype=torch.float64, device=x.device)
+        scratch = torch.empty(L.xq_bn_scratch_bytes(c) // 8, dtype=torch.float64, device=x.device)
+        stream = hip.stream_ptr(x.device)
+        hip.check(L.xq_bn_sync_forward_stats(xv.data_ptr(), b * h * w, c, sums.data_ptr(), scratch.data_ptr(), stream),
+                  "xq_bn_sync_forward_stats")
+        _all_reduce_sums(sums, group)
+        gamma_c, beta_c = gamma.detach().contiguous(), beta.detach().contiguous()
+        hip.check(L.xq_bn_sync_forward_apply(xv.data_ptr(), None if rv is None else rv.data_ptr(), gamma_c.data_ptr(), beta_c.data_ptr(),
+                                             None if running_mean is None else running_mean.data_ptr(),
+                                             None if running_var is None else running_var.data_ptr(), float(momentum), float(eps),
+                                             b * h * w, c, int(relu), sums.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                             None if batches_tracked is None else batches_tracked.data_ptr(), stream),
+                  "xq_bn_sync_forward_apply")
+        ctx.relu, ctx.has_res, ctx.group = bool(relu), residual is not None, group
+        ctx.save_for_backward(xv, y, gamma_c, mean, invstd)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xv, y, gamma, mean, invstd = ctx.saved_tensors
+        b, h, w, c = xv.shape
+        L = hip.lib()
+        gv = gy.permute(0, 2, 3, 1)
+        gv = gv if gv.is_contiguous() else gv.contiguous()
+        dx = torch.empty_like(xv)
+        dres = torch.empty_like(xv) if ctx.has_res else None
+        dgamma, dbeta = torch.empty_like(mean), torch.empty_like(mean)
+        sums = torch.empty(L.xq_bn_sync_sums_count(c), dtype=torch.float64, device=xv.device)
+        scratch = torch.empty(L.xq_bn_scratch_bytes(c) // 8, dtype=torch.float64, device=xv.device)
+        stream = hip.stream_ptr(xv.device)
+        hip.check(L.xq_bn_sync_backward_stats(gv.data_ptr(), xv.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), b * h * w, c,
+                                              int(ctx.relu), sums.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(),
+                                              stream), "xq_bn_sync_backward_stats")
+        _all_reduce_sums(sums, ctx.group)
+        hip.check(L.xq_bn_sync_backward_apply(gv.data_ptr(), xv.data_ptr(), y.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+                                              invstd.data_ptr(), b * h * w, c, int(ctx.relu), sums.data_ptr(), dx.data_ptr(),
+                                              None if dres is None else dres.data_ptr(), stream), "xq_bn_sync_backward_apply")
+        return (dx.permute(0, 3, 1, 2), None if dres is None else dres.permute(0, 3, 1, 2), dgamma, dbeta,
+                None, None, None, None, None, None, None)
+
+
+def sync_bn_supported(bn: torch.nn.Module) -> bool:
+    """`bn_supported` for a torch.nn.SyncBatchNorm in training mode under an initialised process group."""
+    import torch.distributed as dist
+    return isinstance(bn, torch.nn.SyncBatchNorm) and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None \
+        and bn.num_features in (64, 128, 256, 512, 1024) and dist.is_available() and dist.is_initialized()
+
+
+def sync_bn_act(x: torch.Tensor, bn: torch.nn.SyncBatchNorm, residual=None, relu: bool = True) -> torch.Tensor:
+    """`relu(bn(x) + residual)` of a training-mode SyncBatchNorm forward through the hand-written kernels: a collective over
+    `bn.process_group` (the default group when None) in the forward and in the backward pass; every rank must take part."""
+    nbt = bn.num_batches_tracked
+    if nbt.dtype != torch.int64 or not nbt.is_cuda:
+        raise hip.XqError("sync_bn_act: num_batches_tracked must be an int64 tensor on the GPU")
+    return SyncBnAct.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, relu, nbt,
+                           bn.process_group)
+
+
+def native_sync_bn(bn: torch.nn.Module) -> bool:
+    """True when `bn` is a SyncBatchNorm marked for the hand-written kernels (`training.prepare_ddp(native_bn=True)` sets the plain
+    attribute `native_bn`; not a buffer, not in the state_dict) and `sync_bn_supported`."""
+    return bool(getattr(bn, "native_bn", False)) and sync_bn_supported(bn)

@@ -100,14 +100,15 @@ class AlphaZeroLoop:
         """World 1: the reference's step.  World > 1: the same full-batch update computed data-parallel -- every rank
         holds the same buffer and weights, takes its slice of every batch, SyncBatchNorm + bucketed gradient all-reduce
         (`training.train_network(ddp=True)`); `config.ddp = False` falls back to training on rank 0 alone.  Either way one
-        flat weight broadcast from rank 0 closes the step, so the replicas cannot drift."""
+        flat weight broadcast from rank 0 closes the step, so the replicas cannot drift.  `config.native_sync_bn = True` (opt-in)
+        runs the data-parallel step's synchronised BatchNorm on the hand-written kernels (`training.prepare_ddp(native_bn=True)`)."""
         stats = {}
         ddp = self.grouped and bool(getattr(self.config, "ddp", True)) and self.device.type == "cuda"
         # the batch order is a function of (seed, iteration): the same on every rank, and the same in a resumed run
         gen = torch.Generator().manual_seed(self.seed * 1000003 + 7919 * self.iteration + 17)
         if ddp or self.rank == 0:
             stats = training.train_network(self.current_model, self.optimizer, self.scheduler, self.buffer, self.config,
-                                           generator=gen, ddp=ddp)
+                                           generator=gen, ddp=ddp, native_bn=bool(getattr(self.config, "native_sync_bn", False)))
         if self.grouped:
             xdist.broadcast_weights(self.current_model, src=0, device=self.device)
         return stats

@@ -78,13 +78,16 @@ class ReplayBuffer:
         return states, pi, z
 
 
-def prepare_ddp(model, device, group=None):
+def prepare_ddp(model, device, group=None, native_bn: bool = False):
     """The data-parallel form of `model`, built ONCE and kept for the model's lifetime: BatchNorm -> SyncBatchNorm IN PLACE
     (same Parameters and buffers, same state_dict keys: checkpoints, `broadcast_weights` and the evaluators are unaffected)
     and one DistributedDataParallel wrapper (its construction broadcasts the parameters, so it is not repeated per call).
     SIDE EFFECT on the caller's model: from here on a training-mode forward is a collective -- every rank of `group` must
     take part in it; `train_network(ddp=False)` refuses such a model under a multi-rank group (`revert_sync_batchnorm`
-    undoes the conversion)."""
+    undoes the conversion).
+    `native_bn` sets (or clears) on every converted layer the plain attribute `native_bn` (not a buffer, not in the state_dict): with
+    it, the tower's and the stem's SyncBatchNorm run on the hand-written kernels when the model's `native_conv` is on
+    (native_conv.sync_bn_act: the same group statistics, summed in float64); the heads' 32- and 4-channel layers stay with torch."""
     wrapper = model.__dict__.get("_xq_ddp")
     if wrapper is None:
         torch.nn.SyncBatchNorm.convert_sync_batchnorm(model, group)       # in place for the children
@@ -92,6 +95,9 @@ def prepare_ddp(model, device, group=None):
         wrapper = torch.nn.parallel.DistributedDataParallel(
             model, device_ids=[device.index] if device.type == "cuda" else None, process_group=group, broadcast_buffers=False)
         model.__dict__["_xq_ddp"] = wrapper       # not a registered submodule (the wrapper already holds the model)
+    for m in model.modules():
+        if isinstance(m, torch.nn.SyncBatchNorm):
+            m.native_bn = bool(native_bn)
     return wrapper
 
 
@@ -113,7 +119,8 @@ def revert_sync_batchnorm(model) -> None:
 
 
 def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shuffle: bool = True,
-                  generator: Optional[torch.Generator] = None, ddp: bool = False, group=None) -> Dict[str, float]:
+                  generator: Optional[torch.Generator] = None, ddp: bool = False, group=None,
+                  native_bn: bool = False) -> Dict[str, float]:
     """One call of the reference's train_network (train.py:376-447) on the device-resident buffer.
 
     `ddp=True` under an initialised torch.distributed group (every rank holds the same buffer and the same weights, as
@@ -122,7 +129,8 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     all-reduce overlapped with backward (DistributedDataParallel) -- the update is the reference's full-batch update, the
     replicas stay identical, and each GPU runs 1/world of the forward/backward work.  The conversion and the wrapper are
     made once per model (`prepare_ddp`, which documents the side effect on the caller's model).  The batch order comes
-    from `generator` (or a generator seeded identically on every rank)."""
+    from `generator` (or a generator seeded identically on every rank).  `native_bn=True` (ddp only; opt-in) runs the synchronised
+    BatchNorm of the tower and the stem on the hand-written kernels instead of torch's SyncBatchNorm (`prepare_ddp`)."""
     if len(buffer) < config.min_buffer_size:
         return {}
     import torch.distributed as dist
@@ -133,7 +141,7 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     model.train()
     net = model
     if use_ddp:
-        net = prepare_ddp(model, buffer.device, group)
+        net = prepare_ddp(model, buffer.device, group, native_bn)
         if generator is None:                                              # one order for all ranks
             generator = torch.Generator().manual_seed(int(scheduler.last_epoch) * 7919 + 17)
     elif dist.is_initialized() and dist.get_world_size(group) > 1 and any(isinstance(m, torch.nn.SyncBatchNorm) for m in model.modules()):
