@@ -214,6 +214,54 @@ int xq_engine_compact(const xq_engine *eng, const float *dev_nn_input, void *str
 int xq_engine_packed(const xq_engine *eng, xq_engine_packed_buffers *out);
 int xq_engine_expand_packed(const xq_engine *eng, const float *dev_packed_logits, const float *dev_packed_value, void *stream);
 
+/* Evaluation cache (opt-in): a table private to each slot that remembers the legal-move logits and value the network
+ * returned for a position, so the next search, which revisits most of the previous move's subtree, does not ask again.
+ * A request's output depends only on its 15 input planes, so a cached row is bit-identical to a recomputed one and the
+ * games do not change.  The cached step, on one stream:
+ *     xq_engine_select(eng, nn_input)
+ *     xq_evcache_probe(cache, eng, nn_input)          per waiting slot: key from nn_input, probe the slot's set; a hit writes
+ *                                                     the slot's row of slot_logits / slot_value and sets its hit flag
+ *     xq_engine_compact_misses(eng, nn_input, hit)    xq_engine_compact restricted to waiting slots whose flag is 0
+ *                                                     (rows_evaluated counts only these rows)
+ *     <evaluator over the packed rows>                as in the packed step
+ *     xq_engine_expand_packed(eng, logits, value)     as in the packed step
+ *     xq_evcache_commit(cache, eng, logits, value)    each evaluated row inserts its slot's key, logits, value and count
+ *                                                     (it reads only the packed rows: before or after the expansion alike)
+ * Every count stays in device memory and every grid is sized by n_games: the sequence records into one graph.
+ * Table: per slot `entries_per_slot` (K, a power of two) entries in sets of min(4, K) ways, one caller-owned allocation of
+ * xq_evcache_bytes(n_slots, K) bytes: per entry a 12-word key (90 squares x 4 bits + the side to move), generation, stamp,
+ * legal-move count, float32 value and float32[XQ_MAXM] logits -- 576 B -- plus ~100 B per slot.  A hit needs the whole key,
+ * the current generation and the count to match (a key match with another count is a "mismatch": counted, never expected,
+ * treated as a miss).  The victim is an entry of an older generation, else the least recently stamped (lowest way on ties).
+ * xq_evcache_invalidate bumps the device-side generation (after a weight update): older entries never hit again.
+ * Errors: K zero or not a power of two, null pointers, logits not 8-byte aligned, or a cache whose n_slots differs from the
+ * engine's n_games return XQ_ERR_ARG before any launch.  xq_evcache_bytes returns 0 for invalid arguments. */
+typedef struct xq_evcache {
+    int32_t n_slots, entries, ways, sets;
+    void *p[16];                  /* device addresses in the caller's allocation; treat as opaque */
+} xq_evcache;
+typedef struct xq_evcache_stats {
+    uint64_t probes;              /* waiting slots probed */
+    uint64_t hits;                /* probes answered from the table (their rows were not evaluated) */
+    uint64_t inserts, evictions;  /* evictions: inserts that replaced a current-generation entry */
+    uint64_t mismatches;          /* key and generation matched, legal-move count did not: must stay 0 */
+    uint64_t reserved[3];
+} xq_evcache_stats;
+size_t xq_evcache_bytes(int n_slots, int entries_per_slot);
+/* Carves dev_mem (256-byte aligned, >= xq_evcache_bytes) and clears the table (asynchronous on stream). */
+int xq_evcache_init(xq_evcache *cache, int n_slots, int entries_per_slot, void *dev_mem, size_t bytes, void *stream);
+/* *dev_hit = int32[n_slots] hit flags written by xq_evcache_probe (valid for waiting slots of the current step). */
+int xq_evcache_hit_flags(const xq_evcache *cache, const int32_t **dev_hit);
+int xq_evcache_probe(const xq_evcache *cache, const xq_engine *eng, const float *dev_nn_input, void *stream);
+int xq_engine_compact_misses(const xq_engine *eng, const float *dev_nn_input, const int32_t *dev_hit_flags, void *stream);
+int xq_evcache_commit(const xq_evcache *cache, const xq_engine *eng, const float *dev_packed_logits,
+                      const float *dev_packed_value, void *stream);
+int xq_evcache_invalidate(const xq_evcache *cache, void *stream);
+/* Synchronises `stream`, sums the per-slot counters. */
+int xq_evcache_stats_read(const xq_evcache *cache, xq_evcache_stats *host_out, void *stream);
+/* The key the probe builds, computed on the host from one position's float32[15][90] planes (tests). */
+int xq_evcache_key_host(const float *host_planes, uint32_t *host_out12);
+
 /* Synchronises `stream`, copies the counters to host. */
 int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *stream);
 

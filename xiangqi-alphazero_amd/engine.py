@@ -17,6 +17,17 @@ hand-written kernels.  There is no CPU fallback.
 The live count never leaves the device, so the packed step records into one HIP graph like the full-width one; once games
 finish (games_target reached: idle slots) the evaluator's work follows the slots that are still playing.  Results are
 identical to the full-width step.  The explicit stage calls (`select`, `evaluate_and_expand`, `expand_legal`) stay full width.
+
+With `eval_cache_entries = K > 0` (opt-in, a power of two) the engine owns a per-slot evaluation cache (xq_evcache_*) and
+`step()` / `capture_step()` take the CACHED step:
+
+    select  ->  probe (hits answered from the slot's table)  ->  compact the misses + gather  ->  evaluator over n_live rows
+            ->  scatter back to slot order + expand  ->  commit (insert the evaluated rows)
+
+A cached row is bit-identical to a recomputed one, so the games are those of the packed step; `rows_evaluated` counts only
+the rows the network ran on.  The table costs `eval_cache_bytes(G, K)` (576 B per entry); `recommended_cache_entries(S)`
+is the next power of two >= 2 S, about two moves of evaluations.  A weight update of the evaluator (`weights_version`) or
+another evaluator invalidates the table before the next step.
 """
 from __future__ import annotations
 
@@ -52,9 +63,23 @@ def make_config(n_games: int, num_simulations: int, *, c_puct: float = 1.5, temp
                             games_target, max_out_samples, max_out_results, int(manual_moves), int(start_stagger))
 
 
+def recommended_cache_entries(num_simulations: int) -> int:
+    """Evaluation-cache entries per slot that hold about two moves of a slot's evaluations: the next power of two >= 2 S."""
+    n = 1
+    while n < 2 * max(1, int(num_simulations)):
+        n *= 2
+    return n
+
+
+def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
+    """Device bytes of an evaluation cache (xq_evcache_bytes): 576 B per entry plus ~100 B per slot; 0 for invalid sizes.
+    BASELINE configs[2] (8192 slots, 800 simulations, K = 2048): 9.7 GB, next to the engine's 20 GB tree arenas."""
+    return int(hip.lib().xq_evcache_bytes(int(n_slots), int(entries_per_slot)))
+
+
 class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
-                 inject: Optional[np.ndarray] = None):
+                 inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0):
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
@@ -106,11 +131,41 @@ class SelfPlayEngine:
         self.packed_counts = ws_view(pb.counts, G * 4, torch.int32)
         self.slot_logits = ws_view(pb.slot_logits, G * hip.MAXM * 4, torch.float32).view(G, hip.MAXM)
         self.slot_value = ws_view(pb.slot_value, G * 4, torch.float32)
+        self.cache = None
+        if eval_cache_entries:
+            self._init_cache(int(eval_cache_entries))
         self.steps = 0
         self._graph = None
         self._graph_generation = 0
         self.launch_mode = "eager"                     # "graph" once capture_step has recorded a step
         self.capture_error = None
+
+    def _init_cache(self, entries: int):
+        if not getattr(self.evaluator, "live_rows", False):
+            raise hip.XqError("eval_cache_entries needs an evaluator with live_rows (the HIP evaluators): the cached step "
+                              "evaluates the packed misses")
+        nbytes = eval_cache_bytes(self.G, entries)
+        if nbytes == 0:
+            raise hip.XqError(f"eval_cache_entries must be a positive power of two, got {entries}")
+        self.cache_entries = entries
+        self.cache_bytes = nbytes
+        self.cache_ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        self.cache = hip.EvCache()
+        with torch.cuda.device(self.device):
+            hip.check(self.lib.xq_evcache_init(C.byref(self.cache), self.G, entries, (self.cache_ws.data_ptr() + 255) & ~255,
+                                               nbytes, hip.stream_ptr(self.device)), "xq_evcache_init")
+        hf = C.c_void_p()
+        hip.check(self.lib.xq_evcache_hit_flags(C.byref(self.cache), C.byref(hf)), "xq_evcache_hit_flags")
+        self._cache_hit_ptr = int(hf.value)
+        self._cache_seen = (self.evaluator, getattr(self.evaluator, "weights_version", 0))
+
+    def _sync_cache(self):
+        """Invalidate the evaluation cache (a device-side generation bump, outside any recorded graph) when the evaluator or
+        its weights changed since the cache last saw them: stale hits are the one way the cache could alter the games."""
+        seen = (self.evaluator, getattr(self.evaluator, "weights_version", 0))
+        if seen[0] is not self._cache_seen[0] or seen[1] != self._cache_seen[1]:
+            hip.check(self.lib.xq_evcache_invalidate(C.byref(self.cache), hip.stream_ptr(self.device)), "xq_evcache_invalidate")
+            self._cache_seen = seen
 
     # ---- the three stages of a step --------------------------------------------------------------------
     def select(self):
@@ -175,11 +230,25 @@ class SelfPlayEngine:
 
     @property
     def path(self) -> str:
-        """The step `step()` runs: "packed" when the evaluator evaluates a device-side live row count, else "full"."""
+        """The step `step()` runs: "cached" with an evaluation cache, "packed" when the evaluator evaluates a device-side live
+        row count, else "full"."""
+        if self.cache is not None:
+            return "cached"
         return "packed" if getattr(self.evaluator, "live_rows", False) else "full"
 
     def _one_step(self):
-        if self.path == "packed":
+        if self.cache is not None:
+            sp = hip.stream_ptr(self.device)
+            x = self.select()
+            hip.check(self.lib.xq_evcache_probe(C.byref(self.cache), C.byref(self.h), x.data_ptr(), sp), "xq_evcache_probe")
+            hip.check(self.lib.xq_engine_compact_misses(C.byref(self.h), x.data_ptr(), self._cache_hit_ptr, sp),
+                      "xq_engine_compact_misses")
+            ll, value = self.evaluator.evaluate_legal(self.packed_x, self.packed_moves, self.packed_counts, n_live=self.n_live)
+            self.expand_packed(ll, value)
+            ll, value = self._keep_packed                # checked float32 [G, 128] / [G], contiguous
+            hip.check(self.lib.xq_evcache_commit(C.byref(self.cache), C.byref(self.h), ll.data_ptr(), value.data_ptr(), sp),
+                      "xq_evcache_commit")
+        elif self.path == "packed":
             self.select()
             self.compact()
             ll, value = self.evaluator.evaluate_legal(self.packed_x, self.packed_moves, self.packed_counts, n_live=self.n_live)
@@ -192,6 +261,8 @@ class SelfPlayEngine:
         has recorded it); the packed step (module docstring) when the evaluator has `live_rows`."""
         if self._graph is not None and getattr(self.evaluator, "generation", 0) != self._graph_generation:
             self.release_graph()                       # the evaluator reallocated a buffer: the recording holds stale pointers
+        if self.cache is not None:
+            self._sync_cache()
         if self._graph is not None:
             self._graph.replay()
         else:
@@ -208,6 +279,8 @@ class SelfPlayEngine:
         False, and stays eager, for evaluators that are not capturable (they synchronise or allocate outside torch)."""
         if self.evaluator is None:
             raise hip.XqError("capture_step needs an evaluator")
+        if self.cache is not None:
+            self._sync_cache()
         for _ in range(warmup):
             self._one_step()
             self.steps += 1
@@ -244,7 +317,15 @@ class SelfPlayEngine:
         rc = self.lib.xq_engine_stats_read(C.byref(self.h), C.byref(s), hip.stream_ptr(self.device))
         if rc != 0 and (check or rc != -4):
             hip.check(rc, "xq_engine_stats_read")
-        return s.as_dict()
+        out = s.as_dict()
+        if self.cache is not None:
+            cs = hip.EvCacheStats()
+            hip.check(self.lib.xq_evcache_stats_read(C.byref(self.cache), C.byref(cs), hip.stream_ptr(self.device)),
+                      "xq_evcache_stats_read")
+            out.update({"eval_cache_" + k: v for k, v in cs.as_dict().items()})
+            out["eval_cache_entries"] = self.cache_entries
+            out["eval_cache_bytes"] = self.cache_bytes
+        return out
 
     def drain(self):
         """-> (samples structured array, results structured array); empties the device rings."""

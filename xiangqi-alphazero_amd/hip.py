@@ -67,6 +67,19 @@ class PackedBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("n_live", "rows", "x", "moves", "counts", "slot_logits", "slot_value")]
 
 
+class EvCache(C.Structure):
+    """xq_evcache: the evaluation cache's geometry and device addresses (opaque)."""
+    _fields_ = [("n_slots", C.c_int32), ("entries", C.c_int32), ("ways", C.c_int32), ("sets", C.c_int32),
+                ("p", C.c_void_p * 16)]
+
+
+class EvCacheStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("probes", "hits", "inserts", "evictions", "mismatches")] + [("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 _lib = None
 
 
@@ -137,6 +150,16 @@ def lib():
     L.xq_wino_conv3x3_bf16_live.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, i32, vp]
     L.xq_policy_head_legal_live.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.xq_value_head_live.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.xq_evcache_bytes.argtypes = [i32, i32]
+    L.xq_evcache_bytes.restype = C.c_size_t
+    L.xq_evcache_init.argtypes = [C.POINTER(EvCache), i32, i32, vp, C.c_size_t, vp]
+    L.xq_evcache_hit_flags.argtypes = [C.POINTER(EvCache), C.POINTER(vp)]
+    L.xq_evcache_probe.argtypes = [C.POINTER(EvCache), C.POINTER(Engine), vp, vp]
+    L.xq_engine_compact_misses.argtypes = [C.POINTER(Engine), vp, vp, vp]
+    L.xq_evcache_commit.argtypes = [C.POINTER(EvCache), C.POINTER(Engine), vp, vp, vp]
+    L.xq_evcache_invalidate.argtypes = [C.POINTER(EvCache), vp]
+    L.xq_evcache_stats_read.argtypes = [C.POINTER(EvCache), C.POINTER(EvCacheStats), vp]
+    L.xq_evcache_key_host.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -152,7 +175,9 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_compact", "xq_engine_packed", "xq_engine_expand_packed", "xq_stem_conv_live", "xq_heads_1x1_live",
            "xq_wino_conv3x3_live", "xq_wino_conv3x3_bf16_live", "xq_policy_head_legal_live", "xq_value_head_live",
            "xq_bn_sync_sums_count", "xq_bn_sync_forward_stats", "xq_bn_sync_forward_apply", "xq_bn_sync_backward_stats",
-           "xq_bn_sync_backward_apply"]
+           "xq_bn_sync_backward_apply", "xq_evcache_bytes", "xq_evcache_init", "xq_evcache_hit_flags", "xq_evcache_probe",
+           "xq_engine_compact_misses", "xq_evcache_commit", "xq_evcache_invalidate", "xq_evcache_stats_read",
+           "xq_evcache_key_host"]
 
 
 def check(rc: int, what: str):

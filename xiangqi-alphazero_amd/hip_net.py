@@ -66,12 +66,16 @@ class HipResNetEvaluator:
         # bumped whenever a device buffer a recorded step points at is REALLOCATED (a weight tensor whose shape changed, a
         # grown activation / logits buffer): `SelfPlayEngine.step` drops its HIP graph then instead of replaying stale pointers
         self.generation = 0
+        # bumped by every update(): an engine's evaluation cache compares it before each step and invalidates on a change
+        self.weights_version = 0
         self.update(net)
 
     def update(self, net: XiangqiNet):
         """(Re)build the folded / pre-transformed device weights.  After the first call every tensor is refreshed IN PLACE:
         device pointers stay what they were, so a HIP graph recorded over this evaluator (`engine.capture_step`) keeps
-        replaying with the new weights (the reference's `InferenceServer.update_model`, inference_server.py:476-487)."""
+        replaying with the new weights (the reference's `InferenceServer.update_model`, inference_server.py:476-487).
+        Every call bumps `weights_version`."""
+        self.weights_version += 1
         ref = InferenceNet(net)
         new = {}
         new["wt_in"] = hip.stem_weights(ref.w_in)                    # [135, C] for xq_stem_conv
