@@ -94,7 +94,10 @@ int xq_game_over_batch(const int8_t *dev_boards, const int8_t *dev_side, const i
  *     <evaluator>        B2: any batched policy/value function over dev_nn_input (the ResNet)
  *     xq_engine_expand   consumes dev_policy[slot] / dev_value[slot]: root or leaf expansion with the
  *                        reference's mask-and-normalise, backup along the recorded path
- * Simulations of one game stay strictly sequential (as in mcts.py:126-153); parallelism is across games.
+ * By default the simulations of one game stay strictly sequential (as in mcts.py:126-153) and parallelism is across
+ * games.  Opt-in leaf batching (xq_engine_init_leaves, K = leaves_per_step > 1) lets a slot hand the evaluator up to K
+ * leaves per step, collected under virtual loss -- for few slots, where there is nothing to be parallel across.  K > 1 is
+ * knowingly NOT the reference's sequential search (outside the reference-parity contract); K = 1 is today's engine.
  * ===================================================================================== */
 
 typedef struct xq_engine_config {
@@ -150,8 +153,17 @@ typedef struct xq_engine_stats {
     uint64_t overflow;        /* non-zero: a device capacity was exceeded (results invalid) */
     uint64_t games_started;
     uint64_t rows_evaluated;  /* sum over xq_engine_compact calls of n_live: rows the evaluator ran on in packed steps */
-    uint64_t reserved[13];
+    uint64_t reserved[13];    /* [XQ_STAT_COLLISIONS], [XQ_STAT_LEAVES_SUM], [XQ_STAT_LEAF_STEPS]: the leaf-batching counters below */
+
 } xq_engine_stats;
+/* Leaf-batching counters (xq_engine_init_leaves), kept in the reserved words so the struct's layout is unchanged:
+ *   reserved[XQ_STAT_COLLISIONS]  descents dropped because they ended on a leaf already pending in their step
+ *   reserved[XQ_STAT_LEAVES_SUM]  pending leaves handed to the evaluator, summed over slot-steps
+ *   reserved[XQ_STAT_LEAF_STEPS]  slot-steps that handed leaves: mean batch per slot = LEAVES_SUM / LEAF_STEPS
+ * All three are 0 with K = 1; the other reserved words stay 0. */
+#define XQ_STAT_COLLISIONS 0
+#define XQ_STAT_LEAVES_SUM 1
+#define XQ_STAT_LEAF_STEPS 2
 
 /* Bytes of device workspace the engine needs for cfg (tree arenas dominate:
  * n_games * (1 + (num_simulations+1)*XQ_MAXM) nodes * 24 B -- sized for 288 GB HBM, no per-node malloc). */
@@ -165,6 +177,31 @@ size_t xq_engine_workspace_bytes(const xq_engine_config *cfg);
  * dev_inject: uint64[n_games][4][inject_len] or NULL. */
 int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t ws_bytes,
                    const uint64_t *dev_inject, void *stream);
+
+/* Leaf batching (opt-in): K = leaves_per_step leaves per slot and step, 1 <= K <= 64 (K = 1: exactly xq_engine_init).
+ * In one step a searching slot runs descents j = 0, 1, ... from the root until K leaves are pending, or sims_done + pending
+ * == num_simulations, or a collision occurs.  Virtual loss is a separate per-node counter vl (never folded into N or W):
+ * child i of parent p is scored with n = N_i + vl_i (in q = w / n and in 1 + n), w = W_i - vl_i (float64) and
+ * sqrt(N_p + vl_p); otherwise the arithmetic above, for all three prior kinds, first maximum wins; with every vl = 0 the
+ * score is bit-identical to K = 1's.  A descent that chooses a non-terminal leaf adds 1 to vl along its path (the root
+ * included); a terminal leaf is backed up at once and counts as a simulation (at most 48 per launch, as with K = 1); a
+ * descent that ends on a leaf an earlier descent of the same step waits on is a COLLISION: not a simulation, and it ends
+ * the slot's collection for this step.  xq_engine_expand* expands and backs up the pending leaves in descent order (child
+ * blocks bump-allocated in that order), each backup removing its descent's virtual loss: every vl is 0 after every step.
+ * Roots, noise, the resign probe, move choice and samples are unchanged; every move still ends with exactly num_simulations
+ * simulations.
+ * Request ROWS are slot-major: row slot*K + j carries pending leaf j (the root request is row slot*K): dev_nn_input is
+ * [G*K][15][90], dev_policy / dev_legal_logits / dev_value have G*K rows, xq_engine_requests' moves / counts are
+ * [G*K][XQ_MAXM] / [G*K] (count 0: the row asks for nothing), and the packed buffers hold G*K rows whose rows[r] is the
+ * packed row's REQUEST ROW (slot = rows[r] / K); the *_live evaluator entry points then take capacity G*K.  Every count
+ * stays on the device and every grid is sized by G*K: the step records into one graph as with K = 1.  K is kept in the
+ * handle (pad0); select, expand, expand_legal, requests, compact, packed and expand_packed read it.
+ * XQ_ERR_ARG (before any launch): K < 1 or K > 64, K > 1 with manual_moves == 2 (arena), and the evaluation cache
+ * (xq_evcache_probe / _commit, xq_engine_compact_misses) on an engine with K > 1.  The workspace adds G * node_cap int32
+ * virtual-loss counters and the G*K request rows; xq_engine_workspace_bytes_leaves returns 0 for invalid arguments. */
+size_t xq_engine_workspace_bytes_leaves(const xq_engine_config *cfg, int leaves_per_step);
+int xq_engine_init_leaves(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, void *ws, size_t ws_bytes,
+                          const uint64_t *dev_inject, void *stream);
 
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 

@@ -36,14 +36,14 @@ enum Phase : int { PH_NEWGAME = 0, PH_NEWPOS = 1, PH_WAIT_ROOT = 2, PH_SEARCH = 
 
 enum Gi : int { GI_SIDE = 0, GI_MC, GI_NOCAP, GI_PHASE, GI_SIMS, GI_NSAMP, GI_GSEQ, GI_ALLOC, GI_PLEAF, GI_PDEPTH,
                 GI_PCOUNT, GI_RSTATUS, GI_RWINNER, GI_RESIGN_N, GI_RNG0, GI_RNG1, GI_RNG2, GI_RNG3, GI_FWINNER,
-                GI_FREASON, GI_MANNOISE, GI_DELAY, GI_N = 32 };
+                GI_FREASON, GI_MANNOISE, GI_DELAY, GI_NPEND, GI_N = 32 };
 
 enum St : int { ST_SIMS = 0, ST_TERM, ST_LEAF, ST_ROOT, ST_MOVES, ST_GAMES, ST_RED, ST_BLACK, ST_DRAW, ST_PLIES, ST_NODES,
-                ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_N = 32 };
+                ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_COLL, ST_LPS, ST_LSTEPS, ST_N = 32 };
 
 enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_TW, P_TP, P_TA, P_TC, P_TM, P_ROOTP,
                  P_STAGE, P_OUTS, P_OUTR, P_CNT, P_STATS, P_INJECT, P_SQRT, P_MNOISE, P_STATSUM, P_REQ,
-                 P_PK_N, P_PK_ROWS, P_PK_X, P_PK_MOVES, P_PK_COUNTS, P_PK_LOGITS, P_PK_VALUE };
+                 P_PK_N, P_PK_ROWS, P_PK_X, P_PK_MOVES, P_PK_COUNTS, P_PK_LOGITS, P_PK_VALUE, P_VL, P_LEAF };
 
 enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM = 3 };
 
@@ -115,7 +115,7 @@ __device__ inline uint64_t draw_u64(const Dev &E, int slot, int kind, int ctr, u
 __device__ inline double u64_to_unit(uint64_t x) { return (double)(x >> 11) * (1.0 / 9007199254740992.0); }
 
 // Gamma(alpha) variate for lane-private use (Marsaglia-Tsang on alpha+1, boosted by U^(1/alpha))
-__device__ inline double gamma_variate(const Dev &E, int slot, int ctr, double alpha) {
+__device__ __forceinline__ double gamma_variate(const Dev &E, int slot, int ctr, double alpha) {
     const double d = alpha + 1.0 - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
     double g = d;
     for (uint32_t it = 0; it < 64; ++it) {
@@ -785,6 +785,591 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Leaf batching (xq_engine_init_leaves, K > 1): k_select_multi / k_expand_multi replace k_select / k_expand; k_select,
+// k_expand and the K = 1 step are untouched.  Per step a searching slot runs up to K descents under virtual loss (a
+// separate int32 counter per node, never folded into N / W): child i of parent p is scored with n = N_i + vl_i (in q and in
+// 1 + n), w = W_i - vl_i (fp64) and sqrt_tab[N_p + vl_p], otherwise the arithmetic of k_select term by term.  A descent
+// that chooses a non-terminal leaf adds 1 to vl along its path (the root included) and hands the leaf to the evaluator in
+// row slot K + j; a terminal leaf is backed up at once; a descent that ends on a leaf already pending in this step (a
+// collision) is dropped and ends the slot's collection.  k_expand_multi expands and backs up the pending leaves in
+// descent order and removes each one's virtual loss: every vl is 0 again after every step.
+struct Mx {
+    int K;                          // leaves per step (2..64)
+    int32_t *vl;                    // [G][node_cap] in-flight descents through each node
+    int32_t *leaf;                  // [G][K][4] pending leaf j of a slot: node, depth, legal-move count, -
+};
+
+// One game per 64-thread workgroup: at the small G where leaf batching pays, each slot's K descents are its step's
+// critical path, and a workgroup of its own gives the slot a CU's LDS instead of a quarter of it (k_select: four per CU).
+__global__ __launch_bounds__(64) void k_select_multi(Dev E, Mx X, float *__restrict__ nn_in) {
+    __shared__ SelectLds L;
+    const int slot = blockIdx.x;
+    if (slot >= E.cfg.n_games) return;
+    const int lane = lane_id();
+    int32_t *gi = E.gi + (size_t)slot * GI_N;
+    unsigned long long *st = E.stats + (size_t)slot * ST_N;
+    const size_t nb = (size_t)slot * E.node_cap;
+    int32_t *tN = E.tN + nb; double *tW = E.tW + nb; float *tP = E.tP + nb;
+    uint16_t *tA = E.tA + nb; int32_t *tC = E.tC + nb; uint16_t *tM = E.tM + nb;
+    const int K = X.K;
+    const size_t row0 = (size_t)slot * K;                // the slot's first request row; descent j uses row row0 + j
+    int32_t *vl = X.vl + nb;
+    int32_t *path = E.path + row0 * E.path_cap;
+    int8_t *g_board = E.board + (size_t)slot * XQ_BS;
+    int8_t *g_hist = E.hist + (size_t)slot * XQ_HIST * XQ_BS;
+    uint16_t *pmoves = E.pmoves + row0 * XQ_MAXM;
+    const double *rootP = E.rootP + (size_t)slot * XQ_MAXM;
+    const int S = E.cfg.num_simulations;
+    const bool manual = E.cfg.manual_moves == 1;     // search only (MCTS.search parity / serving)
+    const bool arena = E.cfg.manual_moves == 2;      // evaluation games (train.py:453-535): T = 0, no opening, no samples
+
+    int phase = __builtin_amdgcn_readfirstlane(gi[GI_PHASE]);
+    if (phase == PH_WAIT_ROOT || phase == PH_WAIT_LEAF) return;        // still waiting: the request stands
+    if (phase == PH_IDLE || phase == PH_HOLD) { for (int j = lane; j < K; j += 64) E.req[row0 + j] = 0; return; }
+    const int delay = __builtin_amdgcn_readfirstlane(gi[GI_DELAY]);
+    if (delay > 0) {                                  // start_stagger: not started yet
+        if (lane == 0) gi[GI_DELAY] = delay - 1;
+        for (int j = lane; j < K; j += 64) E.req[row0 + j] = 0;
+        return;
+    }
+
+    int g_side = __builtin_amdgcn_readfirstlane(gi[GI_SIDE]);
+    int g_mc = __builtin_amdgcn_readfirstlane(gi[GI_MC]);
+    int g_nocap = __builtin_amdgcn_readfirstlane(gi[GI_NOCAP]);
+    int sims_done = __builtin_amdgcn_readfirstlane(gi[GI_SIMS]);
+    int n_samples = __builtin_amdgcn_readfirstlane(gi[GI_NSAMP]);
+    int game_seq = __builtin_amdgcn_readfirstlane(gi[GI_GSEQ]);
+    int rng_ctr[4] = {__builtin_amdgcn_readfirstlane(gi[GI_RNG0]), __builtin_amdgcn_readfirstlane(gi[GI_RNG1]),
+                      __builtin_amdgcn_readfirstlane(gi[GI_RNG2]), __builtin_amdgcn_readfirstlane(gi[GI_RNG3])};
+    int ovf = 0;
+    // per-lane stat deltas are kept wave-uniform and written by lane 0 at the end
+    unsigned long long d_sims = 0, d_term = 0, d_moves = 0, d_depth = 0, d_scan = 0;
+    int term_run = 0;
+    // pending leaves of this step: lane j holds leaf j's node and legal-move count (K <= 64)
+    int npend = 0, my_node = -1, my_cnt = 0;
+    unsigned long long d_coll = 0;
+
+    lds_copy_dwords(L.root, g_board, XQ_BS / 4);
+    lds_copy_dwords(L.rhist, g_hist, XQ_HIST * XQ_BS / 4);
+    wave_sync();
+
+    bool state_dirty = false;  // real game state changed -> write back
+    for (int guard = 0; guard < 4 * S + 64; ++guard) {
+        if (phase == PH_FINISHED) {
+            // ---- flush the finished game's samples with z (parallel_selfplay.py:123-132) and its result
+            const int winner = __builtin_amdgcn_readfirstlane(gi[GI_FWINNER]);
+            const int reason = __builtin_amdgcn_readfirstlane(gi[GI_FREASON]);
+            unsigned base = 0;
+            bool fits = true;
+            if (n_samples > 0) {
+                if (lane == 0) base = atomicAdd(&E.cnt[0], (unsigned)n_samples);
+                base = __builtin_amdgcn_readfirstlane(base);
+                fits = (unsigned long long)base + (unsigned)n_samples <= (unsigned)E.cfg.max_out_samples;
+                if (fits) {
+                    const uint8_t *src = E.stage + (size_t)slot * E.stage_cap * XQ_SAMPLE_BYTES;
+                    uint8_t *dst = E.outs + (size_t)base * XQ_SAMPLE_BYTES;
+                    const int ndw = n_samples * (XQ_SAMPLE_BYTES / 4);
+                    for (int i = lane; i < ndw; i += 64) ((uint32_t *)dst)[i] = ((const uint32_t *)src)[i];
+                    for (int i = lane; i < n_samples; i += 64) {
+                        const int sside = ((const int8_t *)src)[(size_t)i * XQ_SAMPLE_BYTES + 90];
+                        ((int8_t *)dst)[(size_t)i * XQ_SAMPLE_BYTES + 91] = (int8_t)(winner == 0 ? 0 : (winner == sside ? 1 : -1));
+                    }
+                }
+            }
+            if (lane == 0) {
+                if (fits) st[ST_SAMP] += (unsigned)n_samples; else st[ST_DROP] += (unsigned)n_samples;
+                const unsigned r = atomicAdd(&E.cnt[1], 1u);
+                if (r < (unsigned)E.cfg.max_out_results) {
+                    xq_game_result res;
+                    res.slot = (uint32_t)slot; res.game_seq = (uint32_t)game_seq; res.winner = (int8_t)winner;
+                    res.reason = (uint8_t)reason; res.steps = (uint16_t)g_mc; res.n_samples = (uint16_t)n_samples;
+                    res.reserved = 0;
+                    *(xq_game_result *)(E.outr + (size_t)r * XQ_RESULT_BYTES) = res;
+                }
+                st[ST_GAMES] += 1;
+                st[winner == 1 ? ST_RED : (winner == -1 ? ST_BLACK : ST_DRAW)] += 1;
+                st[ST_PLIES] += (unsigned)g_mc;
+                if (reason == 3) st[ST_RESIGN] += 1;
+            }
+            phase = PH_NEWGAME;
+        }
+        if (phase == PH_NEWGAME) {
+            // ---- new game + random opening (parallel_selfplay.py:58-72)
+            unsigned long long idx = 0;
+            if (lane == 0) idx = atomicAdd(E.started, 1ull);
+            idx = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(idx >> 32)) << 32) |
+                  (unsigned)__builtin_amdgcn_readfirstlane((unsigned)idx);
+            if (E.cfg.games_target > 0 && idx >= (unsigned long long)E.cfg.games_target) { phase = PH_IDLE; break; }
+            game_seq += 1;
+            n_samples = 0;
+            init_board_lds(L.root);
+            g_side = 1; g_mc = 0; g_nocap = 0;
+            if (lane == 0) { gi[GI_RESIGN_N] = 0; st[ST_STARTED] += 1; }
+            wave_sync();
+            const int R = arena ? 0 : E.cfg.random_opening_moves;
+            const int k = R > 0 ? (int)(draw_u64(E, slot, RNG_RANDINT, rng_ctr[RNG_RANDINT], st) % (uint64_t)(R + 1)) : 0;
+            if (!arena) rng_ctr[RNG_RANDINT] += 1;   // random.randint is called even when R == 0
+            for (int i = 0; i < k; ++i) {
+                const int cnt = wave_movegen(L.root, g_side, L.mg, L.moves, &ovf);
+                if (cnt == 0) break;
+                const int pick = (int)(draw_u64(E, slot, RNG_CHOICE, rng_ctr[RNG_CHOICE], st) % (uint64_t)cnt);
+                rng_ctr[RNG_CHOICE] += 1;
+                const int action = L.moves[pick];
+                wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
+                int c2, w2;
+                if (wave_game_over(L.root, L.rhist, g_side, g_mc, g_nocap, L.mg, L.moves, &c2, &w2, &ovf)) {
+                    init_board_lds(L.root);
+                    g_side = 1; g_mc = 0; g_nocap = 0;
+                    wave_sync();
+                    break;
+                }
+            }
+            state_dirty = true;
+            phase = PH_NEWPOS;
+        }
+        if (phase == PH_NEWPOS) {
+            // ---- root request: terminal status of the real position + its planes + its ordered legal moves
+            int cnt, winner;
+            int status = 0;
+            const bool done = wave_game_over(L.root, L.rhist, g_side, g_mc, g_nocap, L.mg, L.moves, &cnt, &winner, &ovf);
+            if (done) status = 1;
+            else if (arena && g_mc >= E.cfg.max_game_length) {     // train.py:477,494-496: not over after max plies => draw
+                winner = 0;
+                status = 2;
+            } else if (!manual && !arena && g_mc >= E.cfg.max_game_length) {   // parallel_selfplay.py:79-89
+                int red, black;
+                wave_material(L.root, red, black);
+                const int diff = red - black;
+                winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
+                status = 2;
+            }
+            wave_encode(L.root, g_side, nn_in + row0 * XQ_STATE_FLOATS);
+            for (int j = lane; j < cnt; j += 64) pmoves[j] = L.moves[j];
+            my_cnt = lane == 0 ? cnt : 0;
+            if (lane == 0) {
+                gi[GI_PCOUNT] = cnt; gi[GI_RSTATUS] = status; gi[GI_RWINNER] = winner;
+                gi[GI_ALLOC] = 1;
+                tN[0] = 0; tW[0] = 0.0; tC[0] = -1; tM[0] = 0; tA[0] = 0; tP[0] = 0.0f;
+            }
+            sims_done = 0;
+            phase = PH_WAIT_ROOT;
+            break;
+        }
+        // ---- phase == PH_SEARCH
+        // stop collecting: K leaves pending, or the pending leaves complete the move's S simulations
+        if (npend > 0 && (npend >= K || sims_done + npend >= S)) { phase = PH_WAIT_LEAF; break; }
+        if (sims_done >= S) {
+            if (manual) { phase = PH_HOLD; break; }
+            const int nch = __builtin_amdgcn_readfirstlane((int)(tM[0] & 0x3FFF));
+            const int first = __builtin_amdgcn_readfirstlane(tC[0]);
+            if (arena) {
+                // MCTS.get_action(temperature=0) (mcts.py:166-174, 197-200): first maximum of the visit counts, move order
+                int bn = -1, bi = 0x7FFFFFFF;
+                for (int i = lane; i < nch; i += 64) {
+                    const int n = tN[first + i];
+                    if (n > bn) { bn = n; bi = i; }
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
+                    if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+                }
+                bi = __builtin_amdgcn_readfirstlane(bi);
+                const int action = __builtin_amdgcn_readfirstlane((int)tA[first + bi]);
+                wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
+                d_moves += 1;
+                state_dirty = true;
+                phase = PH_NEWPOS;
+                continue;
+            }
+            // ---- end of move: sample (parallel_selfplay.py:97-107), pi from visit counts (mcts.py:190-206)
+            const bool late = g_mc >= E.cfg.temperature_threshold;
+            const double inv_t = 1.0 / E.cfg.late_temperature;
+            uint8_t *rec = E.stage + ((size_t)slot * E.stage_cap + (n_samples < E.stage_cap ? n_samples : E.stage_cap - 1)) * XQ_SAMPLE_BYTES;
+            if (n_samples >= E.stage_cap) ovf |= 4;
+            for (int i = lane; i < XQ_SAMPLE_BYTES / 4; i += 64) ((uint32_t *)rec)[i] = 0u;
+            wave_sync_mem();
+            for (int i = lane; i < 90; i += 64) rec[i] = (uint8_t)L.root[i];
+            if (lane == 0) {
+                xq_sample *s = (xq_sample *)rec;
+                s->side = (int8_t)g_side; s->z = 0; s->n_moves = (uint8_t)nch; s->late_temp = late ? 1 : 0;
+                s->ply = (uint16_t)g_mc; s->slot = (uint32_t)slot; s->game_seq = (uint32_t)game_seq;
+            }
+            for (int i = lane; i < nch; i += 64) {
+                const int a = tA[first + i], n = tN[first + i];
+                ((xq_sample *)rec)->actions[i] = (uint16_t)a;
+                ((xq_sample *)rec)->visits[i] = (uint16_t)(n > 65535 ? 65535 : n);
+                L.a_tmp[i] = (uint16_t)a;
+                L.w_tmp[i] = late ? (n > 0 ? pow((double)n, inv_t) : 0.0) : (double)n;
+            }
+            wave_sync();
+            // np.random.choice walks the dense pi in ACTION-ID order: sort the (action, weight) pairs by id
+            for (int i = lane; i < nch; i += 64) {
+                const int a = L.a_tmp[i];
+                int rank = 0;
+                for (int j = 0; j < nch; ++j) rank += (L.a_tmp[j] < a) ? 1 : 0;
+                L.sa[rank] = (uint16_t)a;
+                L.sw[rank] = L.w_tmp[i];
+            }
+            wave_sync();
+            const double u = u64_to_unit(draw_u64(E, slot, RNG_UNIFORM, rng_ctr[RNG_UNIFORM], st));
+            rng_ctr[RNG_UNIFORM] += 1;
+            int action = 0;
+            {
+                // every lane runs the same short sequential scan (LDS broadcast reads); result is wave-uniform
+                double total = 0.0;
+                for (int i = 0; i < nch; ++i) total += L.sw[i];
+                double run = 0.0;
+                for (int i = 0; i < nch; ++i) run += L.sw[i] / total;
+                const double last = run;
+                run = 0.0;
+                int pick = nch - 1;
+                for (int i = 0; i < nch; ++i) {
+                    run += L.sw[i] / total;
+                    if (run / last > u) { pick = i; break; }
+                }
+                action = L.sa[pick];
+            }
+            action = __builtin_amdgcn_readfirstlane(action);
+            wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
+            n_samples += 1;
+            d_moves += 1;
+            state_dirty = true;
+            phase = PH_NEWPOS;
+            continue;
+        }
+        // ---- one simulation (mcts.py:126-153): descend from the root replaying moves on the LDS board
+        lds_copy_dwords(L.board, L.root, XQ_BS / 4);
+        lds_copy_dwords(L.hist, L.rhist, XQ_HIST * XQ_BS / 4);
+        wave_sync();
+        int side = g_side, mc = g_mc, nocap = g_nocap, node = 0, depth = 0;
+        int32_t *pathj = path + (size_t)npend * E.path_cap;   // this descent's row (reused after a terminal leaf / collision)
+        if (lane == 0) pathj[0] = 0;
+        // One dependent round trip to memory per level: every lane reads, with its candidate child's N / W / P, that child's own
+        // node words (children count + kind, first child, action) as well, so the winner's are already in a register when the arg-max
+        // is known -- the next level starts from a lane read instead of three more dependent loads (tM -> tC/tN -> ... -> tA).  The
+        // winner's N, read here, IS the next level's parent count.  Same values, same arithmetic, same order as before.
+        int m = __builtin_amdgcn_readfirstlane((int)tM[0]);
+        int first = __builtin_amdgcn_readfirstlane(tC[0]);
+        int pn = __builtin_amdgcn_readfirstlane(tN[0] + vl[0]);     // visits + in-flight descents
+        for (;;) {
+            const int nch = m & 0x3FFF, kind = m >> 14;
+            if (nch == 0) break;
+            const double sqrtp = E.sqrt_tab[pn];
+            const float sqrtp_f = (float)sqrtp, c_f = (float)E.cfg.c_puct;
+            const double uni = 1.0 / (double)nch;
+            double best = -INFINITY;
+            int best_i = 0x7FFFFFFF;
+            int c_m = 0, c_first = 0, c_n = 0, c_a = 0;              // node words of this lane's best candidate
+            for (int base = 0; base < nch; base += 64) {
+                const int i = base + lane;
+                if (i < nch) {
+                    // virtual loss: each in-flight descent through child i counts as a visit and as a loss for the
+                    // side choosing here (W is from the chooser's view); vl = 0 gives today's values exactly
+                    const int v = vl[first + i];
+                    const int n = tN[first + i] + v;
+                    const double w = tW[first + i] - (double)v;
+                    const int cm = (int)tM[first + i], cf = tC[first + i], ca = (int)tA[first + i];
+                    const double q = n ? w / (double)n : 0.0;
+                    double ucb;
+                    if (kind == 0) {
+                        float t = c_f * tP[first + i];
+                        t = t * sqrtp_f;
+                        t = t / (float)(1 + n);
+                        t = (float)q + t;
+                        ucb = (double)t;
+                    } else {
+                        const double p = kind == 1 ? rootP[i] : uni;
+                        double t = E.cfg.c_puct * p;
+                        t = t * sqrtp;
+                        t = t / (double)(1 + n);
+                        ucb = q + t;
+                    }
+                    if (ucb > best) { best = ucb; best_i = i; c_m = cm; c_first = cf; c_n = n; c_a = ca; }
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const double ov = __shfl_xor(best, off);
+                const int oi = __shfl_xor(best_i, off);
+                if (ov > best || (ov == best && oi < best_i)) { best = ov; best_i = oi; }
+            }
+            best_i = __builtin_amdgcn_readfirstlane(best_i);
+            int action;
+            if (best_i == 0x7FFFFFFF) {                              // all-NaN scores: the reference would raise
+                ovf |= 8; best_i = 0;
+                m = __builtin_amdgcn_readfirstlane((int)tM[first]);
+                pn = __builtin_amdgcn_readfirstlane(tN[first] + vl[first]);
+                action = __builtin_amdgcn_readfirstlane((int)tA[first]);
+                const int nf = __builtin_amdgcn_readfirstlane(tC[first]);
+                d_scan += (unsigned)nch;
+                const int child0 = first;
+                first = nf;
+                wave_make_move(L.board, L.hist, action, side, mc, nocap);
+                depth += 1;
+                if (depth >= E.path_cap) { ovf |= 16; depth = E.path_cap - 1; }
+                if (lane == 0) pathj[depth] = child0;
+                node = child0;
+                continue;
+            }
+            d_scan += (unsigned)nch;
+            const int child = first + best_i;
+            const int src = best_i & 63;                              // child i was lane i % 64's candidate, and its best (it won)
+            action = __builtin_amdgcn_readlane(c_a, src);
+            m = __builtin_amdgcn_readlane(c_m, src);
+            pn = __builtin_amdgcn_readlane(c_n, src);
+            first = __builtin_amdgcn_readlane(c_first, src);
+            wave_make_move(L.board, L.hist, action, side, mc, nocap);
+            depth += 1;
+            if (depth >= E.path_cap) { ovf |= 16; depth = E.path_cap - 1; }
+            if (lane == 0) pathj[depth] = child;
+            node = child;
+        }
+        // collision: the descent ended on a leaf an earlier descent of this step already waits on -- it is not a simulation
+        // (it added no virtual loss yet) and ends this step's collection
+        if (__ballot(lane < npend && my_node == node) != 0ull) { d_coll += 1; phase = PH_WAIT_LEAF; break; }
+        d_depth += (unsigned)depth;
+        int cnt, winner;
+        const bool term = wave_game_over(L.board, L.hist, side, mc, nocap, L.mg, L.moves, &cnt, &winner, &ovf);
+        if (term) {
+            wave_sync_mem();   // path[] stores of lane 0 must be visible to the other lanes
+            wave_backup(tN, tW, pathj, depth, winner == 0 ? 0.0 : 1.0);   // mcts.py:137-140
+            wave_sync_mem();   // the next descent reads N/W written here by other lanes
+            sims_done += 1; d_sims += 1; d_term += 1;
+            // A root with a mating reply re-tests that terminal child on every visit (as mcts.py does); bound how
+            // many such simulations one launch runs so a single slot cannot stretch the step (it resumes next step
+            // and hands the evaluator no position this time).
+            if (++term_run >= 48) { if (npend > 0) phase = PH_WAIT_LEAF; break; }
+            continue;
+        }
+        // ---- pending leaf j = npend: its request goes to row row0 + j; virtual loss along its path, the root included
+        wave_encode(L.board, side, nn_in + (row0 + npend) * XQ_STATE_FLOATS);
+        uint16_t *pm = pmoves + (size_t)npend * XQ_MAXM;
+        for (int j = lane; j < cnt; j += 64) pm[j] = L.moves[j];
+        if (lane == npend) { my_node = node; my_cnt = cnt; }
+        if (lane == 0) { int32_t *lf = X.leaf + (row0 + npend) * 4; lf[0] = node; lf[1] = depth; lf[2] = cnt; }
+        wave_sync_mem();   // pathj[] stores of lane 0 must be visible to the other lanes
+        for (int j = lane; j <= depth; j += 64) vl[pathj[j]] += 1;
+        wave_sync_mem();   // the next descent reads vl written here by other lanes
+        npend += 1;
+    }
+
+    if (state_dirty) {
+        lds_copy_dwords(g_board, L.root, XQ_BS / 4);
+        lds_copy_dwords(g_hist, L.rhist, XQ_HIST * XQ_BS / 4);
+    }
+    const int nrows = phase == PH_WAIT_ROOT ? 1 : (phase == PH_WAIT_LEAF ? npend : 0);
+    for (int j = lane; j < K; j += 64) E.req[row0 + j] = j < nrows ? my_cnt : 0;
+    if (lane == 0) {
+        gi[GI_NPEND] = nrows;
+        if (phase == PH_WAIT_LEAF) { st[ST_LPS] += (unsigned)npend; st[ST_LSTEPS] += 1; }
+        st[ST_COLL] += d_coll;
+        gi[GI_SIDE] = g_side; gi[GI_MC] = g_mc; gi[GI_NOCAP] = g_nocap; gi[GI_PHASE] = phase; gi[GI_SIMS] = sims_done;
+        gi[GI_NSAMP] = n_samples; gi[GI_GSEQ] = game_seq;
+        gi[GI_RNG0] = rng_ctr[0]; gi[GI_RNG1] = rng_ctr[1]; gi[GI_RNG2] = rng_ctr[2]; gi[GI_RNG3] = rng_ctr[3];
+        st[ST_SIMS] += d_sims; st[ST_TERM] += d_term; st[ST_MOVES] += d_moves; st[ST_DEPTH] += d_depth; st[ST_SCAN] += d_scan;
+        if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8;
+    }
+}
+
+// mcts.py:66-73 along path[0..depth] of one pending descent, removing its virtual loss
+__device__ __forceinline__ void wave_backup_vl(int32_t *tN, double *tW, int32_t *vl, const int32_t *path, int depth, double v) {
+    for (int j = lane_id(); j <= depth; j += 64) {
+        const int nd = path[j];
+        const double s = ((depth - j) & 1) ? -v : v;
+        tN[nd] += 1;
+        tW[nd] += s;
+        vl[nd] -= 1;
+    }
+}
+
+// k_expand for request rows slot K + j: the root (one row, j = 0) exactly as k_expand; the pending leaves j = 0 .. npend-1
+// expanded (children bump-allocated in j order) and backed up in j order
+__global__ __launch_bounds__(64) void k_expand_multi(Dev E, Mx X, const float *__restrict__ policy, const float *__restrict__ value,
+                                                     int is_probs) {
+    __shared__ ExpandLds L;
+    const int slot = blockIdx.x;
+    if (slot >= E.cfg.n_games) return;
+    const int lane = lane_id();
+    int32_t *gi = E.gi + (size_t)slot * GI_N;
+    unsigned long long *st = E.stats + (size_t)slot * ST_N;
+    int phase = __builtin_amdgcn_readfirstlane(gi[GI_PHASE]);
+    if (phase != PH_WAIT_ROOT && phase != PH_WAIT_LEAF) return;
+    const int K = X.K;
+    const size_t row0 = (size_t)slot * K;
+    const size_t nb = (size_t)slot * E.node_cap;
+    int32_t *tN = E.tN + nb; double *tW = E.tW + nb; float *tP = E.tP + nb;
+    uint16_t *tA = E.tA + nb; int32_t *tC = E.tC + nb; uint16_t *tM = E.tM + nb;
+    int32_t *vl = X.vl + nb;
+    double *rootP = E.rootP + (size_t)slot * XQ_MAXM;
+    const bool manual = E.cfg.manual_moves == 1;
+    const bool is_root = phase == PH_WAIT_ROOT;
+    const int nrows = is_root ? 1 : __builtin_amdgcn_readfirstlane(gi[GI_NPEND]);
+    int sims_done = __builtin_amdgcn_readfirstlane(gi[GI_SIMS]);
+    int alloc = __builtin_amdgcn_readfirstlane(gi[GI_ALLOC]);
+    int ovf = 0;
+
+    if (is_root) {
+        const double v_net = (double)value[row0];
+        if (lane == 0) st[ST_ROOT] += 1;
+        const int side = gi[GI_SIDE];
+        int fin = 0, fwinner = 0, freason = 0;
+        // resign probe on the position after the move (parallel_selfplay.py:110-121)
+        if (!manual && E.cfg.enable_resign && gi[GI_NSAMP] > 10) {
+            const int RK = E.cfg.resign_check_steps;
+            double *rh = E.resign + (size_t)slot * 16;
+            int rn = gi[GI_RESIGN_N];
+            wave_sync_mem();
+            if (lane == 0) { rh[rn % 16] = v_net; gi[GI_RESIGN_N] = rn + 1; }
+            wave_sync_mem();
+            rn += 1;
+            if (rn >= RK) {
+                bool all_low = true;
+                for (int i = rn - RK; i < rn; ++i) all_low = all_low && (rh[i % 16] < E.cfg.resign_threshold);
+                if (all_low) { fin = 1; fwinner = -side; freason = 3; }
+            }
+        }
+        const int rstatus = gi[GI_RSTATUS];
+        if (!fin && rstatus != 0) { fin = 1; fwinner = gi[GI_RWINNER]; freason = rstatus; }
+        fin = __builtin_amdgcn_readfirstlane(fin);
+        if (fin) {
+            if (lane == 0) {
+                gi[GI_FWINNER] = fwinner; gi[GI_FREASON] = freason;
+                gi[GI_PHASE] = manual ? PH_HOLD : PH_FINISHED;
+            }
+            return;
+        }
+    }
+
+    for (int j = 0; j < nrows; ++j) {
+        const size_t row = row0 + j;
+        const int32_t *lf = X.leaf + row * 4;
+        const uint16_t *pmoves = E.pmoves + row * XQ_MAXM;
+        const int cnt = is_root ? __builtin_amdgcn_readfirstlane(gi[GI_PCOUNT]) : __builtin_amdgcn_readfirstlane(lf[2]);
+        // ---- priors of the legal moves, as k_expand (is_probs: 0 logits over 8100, 1 probabilities over 8100, 2 legal logits)
+        const float *pol = policy + row * (is_probs == 2 ? XQ_MAXM : XQ_ACTION_SPACE);
+        float mx = 0.0f, den = 1.0f;
+        if (is_probs == 2) {
+            float m = -INFINITY;
+            for (int i = lane; i < cnt; i += 64) m = fmaxf(m, pol[i]);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+            mx = m;
+        } else if (!is_probs) {
+            const float4 *p4 = (const float4 *)pol;
+            float m = -INFINITY;
+            for (int i = lane; i < XQ_ACTION_SPACE / 4; i += 64) {
+                const float4 x = p4[i];
+                m = fmaxf(fmaxf(m, fmaxf(x.x, x.y)), fmaxf(x.z, x.w));
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+            float s = 0.0f;
+            for (int i = lane; i < XQ_ACTION_SPACE / 4; i += 64) {
+                const float4 x = p4[i];
+                s += expf(x.x - m) + expf(x.y - m) + expf(x.z - m) + expf(x.w - m);
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            mx = m; den = s;
+        }
+        wave_sync();       // the previous row's readers of L are done
+        for (int i = lane; i < cnt; i += 64) {
+            const int a = pmoves[i];
+            const float x = pol[is_probs == 2 ? i : a];
+            L.p[i] = is_probs == 1 ? x : expf(x - mx) / den;
+            L.act[i] = (uint16_t)a;
+        }
+        wave_sync();
+        float sum = 0.0f;
+        for (int i = 0; i < cnt; ++i) sum = sum + L.p[i];      // builtin sum(): sequential float32, move order
+
+        const bool noisy = is_root && (E.cfg.add_noise != 0 || gi[GI_MANNOISE] != 0);
+        if (noisy) {
+            if (gi[GI_MANNOISE] != 0) {
+                const double *mn = E.mnoise + (size_t)slot * XQ_MAXM;
+                for (int i = lane; i < cnt; i += 64) L.eta[i] = mn[i];
+            } else {
+                const int ctr0 = gi[GI_RNG0 + RNG_DIRICHLET];
+                for (int i = lane; i < cnt; i += 64) {
+                    double g;
+                    if (E.cfg.inject_len > 0) {
+                        const double w = (double)(1 + (int)((draw_u64(E, slot, RNG_DIRICHLET, ctr0 + i, st) >> 40) % 4096ull));
+                        g = w * w * w;
+                    } else {
+                        g = gamma_variate(E, slot, ctr0 + i, E.cfg.dirichlet_alpha);
+                    }
+                    L.eta[i] = g;
+                }
+                wave_sync();
+                double tot = 0.0;
+                for (int i = 0; i < cnt; ++i) tot += L.eta[i];
+                wave_sync();
+                for (int i = lane; i < cnt; i += 64) L.eta[i] = L.eta[i] / tot;
+                if (lane == 0) gi[GI_RNG0 + RNG_DIRICHLET] = ctr0 + cnt;
+            }
+            wave_sync();
+        }
+
+        const int node = is_root ? 0 : __builtin_amdgcn_readfirstlane(lf[0]);
+        const int first = alloc;
+        if (cnt > 0) {
+            if (first + cnt > E.node_cap) {
+                ovf |= 32;
+            } else {
+                int kind;
+                const double eps = E.cfg.noise_eps;
+                const float keep_f = (float)(1.0 - eps);
+                if (sum > 0.0f) {
+                    kind = noisy ? 1 : 0;
+                    for (int i = lane; i < cnt; i += 64) {
+                        const float pr = L.p[i] / sum;
+                        if (noisy) { const float sc = keep_f * pr; rootP[i] = (double)sc + eps * L.eta[i]; }
+                        tP[first + i] = pr;
+                    }
+                } else {
+                    kind = noisy ? 1 : 2;
+                    const double uni = 1.0 / (double)cnt;
+                    for (int i = lane; i < cnt; i += 64) {
+                        if (noisy) rootP[i] = (1.0 - eps) * uni + eps * L.eta[i];
+                        tP[first + i] = (float)uni;
+                    }
+                }
+                for (int i = lane; i < cnt; i += 64) {
+                    tN[first + i] = 0; tW[first + i] = 0.0; tA[first + i] = L.act[i]; tC[first + i] = -1; tM[first + i] = 0;
+                }
+                if (lane == 0) {
+                    tC[node] = first; tM[node] = (uint16_t)(cnt | (kind << 14));
+                    st[ST_NODES] += (unsigned)cnt;
+                }
+                alloc = first + cnt;
+            }
+        }
+        if (is_root) break;
+        // ---- leaf j: value = -v (mcts.py:150), backup along its path, its virtual loss removed
+        const double v_net = (double)value[row];
+        const int depth = __builtin_amdgcn_readfirstlane(lf[1]);
+        wave_sync_mem();
+        wave_backup_vl(tN, tW, vl, E.path + row * E.path_cap, depth, -v_net);
+        wave_sync_mem();   // the next leaf's backup updates nodes of this path from other lanes
+    }
+    if (lane == 0) gi[GI_ALLOC] = alloc;
+    if (is_root) {
+        if (lane == 0) { gi[GI_PHASE] = PH_SEARCH; gi[GI_SIMS] = 0; gi[GI_NPEND] = 0; if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8; }
+        return;
+    }
+    sims_done += nrows;
+    if (lane == 0) {
+        gi[GI_SIMS] = sims_done;
+        gi[GI_NPEND] = 0;
+        gi[GI_PHASE] = (manual && sims_done >= E.cfg.num_simulations) ? PH_HOLD : PH_SEARCH;
+        st[ST_SIMS] += (unsigned)nrows;
+        st[ST_LEAF] += (unsigned)nrows;
+        if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8;
+    }
+}
+
 __global__ void k_init(Dev E) {
     const int slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= E.cfg.n_games) return;
@@ -890,6 +1475,47 @@ __global__ __launch_bounds__(256) void k_scatter_rows(const int32_t *__restrict_
     const int slot = rows[r];
     ((float2 *)(slot_logits + (size_t)slot * XQ_MAXM))[lane] = ((const float2 *)(logits + (size_t)r * XQ_MAXM))[lane];
     if (lane == 0) slot_value[slot] = value[r];
+}
+
+// Leaf batching (K > 1): k_compact over the G K request rows, slot-major.  Row slot K + j is live when the slot waits and
+// j < its request-row count (1 for a root, the pending leaves for a leaf step); rows[r] is then that ROW's index, so
+// k_gather_rows / k_scatter_rows serve it unchanged over the row-indexed request buffers.
+__global__ __launch_bounds__(CPT) void k_compact_multi(Dev E, int K, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
+    __shared__ int wsum[CPT / 64];
+    const int R = E.cfg.n_games * K, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int RPT = (R + CPT - 1) / CPT;
+    const int r0 = t * RPT, r1 = min(r0 + RPT, R);
+    int cnt = 0;
+    for (int r = r0; r < r1; ++r) {
+        const int32_t *g = E.gi + (size_t)(r / K) * GI_N;
+        const int ph = g[GI_PHASE];
+        cnt += (ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF) && (r % K) < g[GI_NPEND];
+    }
+    int inc = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(inc, off);
+        if (lane >= off) inc += v;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < CPT / 64; ++w) {
+        const int v = wsum[w];
+        base += w < wave ? v : 0;
+        total += v;
+    }
+    int o = base + inc - cnt;
+    for (int r = r0; r < r1; ++r) {
+        const int32_t *g = E.gi + (size_t)(r / K) * GI_N;
+        const int ph = g[GI_PHASE];
+        if ((ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF) && (r % K) < g[GI_NPEND]) rows[o++] = r;
+    }
+    if (t == 0) {
+        *n_live = total;
+        E.stats[ST_ROWS] += (unsigned long long)total;
+    }
 }
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1136,10 +1762,12 @@ struct Layout {
     int node_cap, path_cap, stage_cap;
 };
 
-Layout make_layout(const xq_engine_config *c) {
+// K > 1 (leaf batching): the request rows (moves, counts, paths, packed buffers) are G K, slot-major; the virtual-loss
+// counters and the pending-leaf records follow the K = 1 layout, which is unchanged.
+Layout make_layout(const xq_engine_config *c, int K = 1) {
     Layout l;
     memset(&l, 0, sizeof(l));
-    const size_t G = (size_t)c->n_games, S = (size_t)c->num_simulations;
+    const size_t G = (size_t)c->n_games, S = (size_t)c->num_simulations, GK = G * (size_t)K;
     l.node_cap = (int)(1 + (S + 1) * XQ_MAXM);
     l.path_cap = (int)(S + 2);
     int sc = c->max_game_length < 200 ? c->max_game_length : 200;
@@ -1151,8 +1779,8 @@ Layout make_layout(const xq_engine_config *c) {
     put(P_HIST, G * XQ_HIST * XQ_BS);
     put(P_GI, G * GI_N * 4);
     put(P_RESIGN, G * 16 * 8);
-    put(P_PMOVES, G * XQ_MAXM * 2);
-    put(P_PATH, G * (size_t)l.path_cap * 4);
+    put(P_PMOVES, GK * XQ_MAXM * 2);
+    put(P_PATH, GK * (size_t)l.path_cap * 4);
     put(P_TN, G * (size_t)l.node_cap * 4);
     put(P_TW, G * (size_t)l.node_cap * 8);
     put(P_TP, G * (size_t)l.node_cap * 4);
@@ -1165,17 +1793,21 @@ Layout make_layout(const xq_engine_config *c) {
     put(P_OUTR, (size_t)(c->max_out_results > 0 ? c->max_out_results : 1) * XQ_RESULT_BYTES);
     put(P_CNT, 64);
     put(P_STATS, G * ST_N * 8);
-    put(P_SQRT, (S + 2) * 8);
+    put(P_SQRT, (S + 2 + (K > 1 ? (size_t)K : 0)) * 8);
     put(P_MNOISE, G * XQ_MAXM * 8);
     put(P_STATSUM, ST_N * 8);
-    put(P_REQ, G * 4);
+    put(P_REQ, GK * 4);
     put(P_PK_N, 4);
-    put(P_PK_ROWS, G * 4);
-    put(P_PK_X, G * XQ_STATE_FLOATS * 4);
-    put(P_PK_MOVES, G * XQ_MAXM * 2);
-    put(P_PK_COUNTS, G * 4);
-    put(P_PK_LOGITS, G * XQ_MAXM * 4);
-    put(P_PK_VALUE, G * 4);
+    put(P_PK_ROWS, GK * 4);
+    put(P_PK_X, GK * XQ_STATE_FLOATS * 4);
+    put(P_PK_MOVES, GK * XQ_MAXM * 2);
+    put(P_PK_COUNTS, GK * 4);
+    put(P_PK_LOGITS, GK * XQ_MAXM * 4);
+    put(P_PK_VALUE, GK * 4);
+    if (K > 1) {
+        put(P_VL, G * (size_t)l.node_cap * 4);
+        put(P_LEAF, GK * 4 * 4);
+    }
     l.total = o;
     return l;
 }
@@ -1183,6 +1815,19 @@ Layout make_layout(const xq_engine_config *c) {
 bool config_ok(const xq_engine_config *c) {
     return c && c->n_games > 0 && c->num_simulations > 0 && c->num_simulations < 16000 && c->resign_check_steps >= 1 &&
            c->resign_check_steps <= 16 && c->random_opening_moves >= 0 && c->late_temperature > 0.0 && c->inject_len >= 0;
+}
+
+bool leaves_ok(const xq_engine_config *c, int K) { return K >= 1 && K <= 64 && !(K > 1 && c->manual_moves == 2); }
+
+// leaves per step of an engine handle (pad0; 0 = 1)
+int leaves_of(const xq_engine *e) { return e->pad0 > 1 ? e->pad0 : 1; }
+
+Mx make_mx(const xq_engine *e) {
+    Mx x;
+    x.K = leaves_of(e);
+    x.vl = (int32_t *)e->p[P_VL];
+    x.leaf = (int32_t *)e->p[P_LEAF];
+    return x;
 }
 
 }  // namespace
@@ -1194,15 +1839,27 @@ size_t xq_engine_workspace_bytes(const xq_engine_config *cfg) {
     return make_layout(cfg).total;
 }
 
+size_t xq_engine_workspace_bytes_leaves(const xq_engine_config *cfg, int leaves_per_step) {
+    if (!config_ok(cfg) || !leaves_ok(cfg, leaves_per_step)) return 0;
+    return make_layout(cfg, leaves_per_step).total;
+}
+
 int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t ws_bytes, const uint64_t *dev_inject,
                    void *stream) {
-    if (!eng || !config_ok(cfg) || !ws || ((uintptr_t)ws & 255)) return XQ_ERR_ARG;
+    return xq_engine_init_leaves(eng, cfg, 1, ws, ws_bytes, dev_inject, stream);
+}
+
+int xq_engine_init_leaves(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, void *ws, size_t ws_bytes,
+                          const uint64_t *dev_inject, void *stream) {
+    if (!eng || !config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !ws || ((uintptr_t)ws & 255)) return XQ_ERR_ARG;
     if (cfg->inject_len > 0 && !dev_inject) return XQ_ERR_ARG;
-    const Layout l = make_layout(cfg);
+    const int K = leaves_per_step;
+    const Layout l = make_layout(cfg, K);
     if (ws_bytes < l.total) return XQ_ERR_WORKSPACE;
     memset(eng, 0, sizeof(*eng));
     eng->cfg = *cfg;
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
+    eng->pad0 = K > 1 ? K : 0;
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -1210,12 +1867,13 @@ int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t
     XQ_TRY(hipMemsetAsync(eng->p[P_BOARD], 0, l.off[P_PATH] - l.off[P_BOARD], s));
     XQ_TRY(hipMemsetAsync(eng->p[P_ROOTP], 0, (size_t)cfg->n_games * XQ_MAXM * 8, s));
     XQ_TRY(hipMemsetAsync(eng->p[P_MNOISE], 0, (size_t)cfg->n_games * XQ_MAXM * 8, s));
-    XQ_TRY(hipMemsetAsync(eng->p[P_REQ], 0, (size_t)cfg->n_games * 4, s));
-    // packed-step buffers: zero count, rows, requests, hand-back (the packed planes are written before they are read)
+    XQ_TRY(hipMemsetAsync(eng->p[P_REQ], 0, (size_t)cfg->n_games * K * 4, s));
+    // packed-step buffers: zero count, rows, requests, hand-back (the packed planes are written before they are read);
+    // with K > 1 the virtual-loss counters and pending-leaf records behind them as well
     XQ_TRY(hipMemsetAsync(eng->p[P_PK_N], 0, l.off[P_PK_X] - l.off[P_PK_N], s));
     XQ_TRY(hipMemsetAsync(eng->p[P_PK_MOVES], 0, l.total - l.off[P_PK_MOVES], s));
     {
-        const int n = cfg->num_simulations + 2;
+        const int n = cfg->num_simulations + 2 + (K > 1 ? K : 0);   // K > 1: N_parent + vl_parent < S + K
         double *tab = (double *)malloc(sizeof(double) * n);
         if (!tab) return XQ_ERR_ARG;
         for (int i = 0; i < n; ++i) tab[i] = sqrt((double)i);   // math.sqrt(visit_count), mcts.py:49
@@ -1232,6 +1890,10 @@ int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input, void *stream) {
     if (!eng || !dev_nn_input) return XQ_ERR_ARG;
     const Dev d = make_dev(eng);
+    if (leaves_of(eng) > 1) {
+        hipLaunchKernelGGL(k_select_multi, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, make_mx(eng), dev_nn_input);
+        return launch_status();
+    }
     hipLaunchKernelGGL(k_select, dim3((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), dim3(64 * WAVES_PER_WG), 0,
                        (hipStream_t)stream, d, dev_nn_input);
     return launch_status();
@@ -1241,6 +1903,11 @@ int xq_engine_expand(const xq_engine *eng, const float *dev_policy, const float 
                      void *stream) {
     if (!eng || !dev_policy || !dev_value) return XQ_ERR_ARG;
     const Dev d = make_dev(eng);
+    if (leaves_of(eng) > 1) {
+        hipLaunchKernelGGL(k_expand_multi, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, make_mx(eng), dev_policy,
+                           dev_value, policy_is_probs ? 1 : 0);
+        return launch_status();
+    }
     hipLaunchKernelGGL(k_expand, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_policy, dev_value,
                        policy_is_probs ? 1 : 0);
     return launch_status();
@@ -1256,6 +1923,11 @@ int xq_engine_requests(const xq_engine *eng, const uint16_t **dev_moves, const i
 int xq_engine_expand_legal(const xq_engine *eng, const float *dev_legal_logits, const float *dev_value, void *stream) {
     if (!eng || !dev_legal_logits || !dev_value) return XQ_ERR_ARG;
     const Dev d = make_dev(eng);
+    if (leaves_of(eng) > 1) {
+        hipLaunchKernelGGL(k_expand_multi, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, make_mx(eng), dev_legal_logits,
+                           dev_value, 2);
+        return launch_status();
+    }
     hipLaunchKernelGGL(k_expand, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_legal_logits, dev_value, 2);
     return launch_status();
 }
@@ -1265,10 +1937,12 @@ int xq_engine_compact(const xq_engine *eng, const float *dev_nn_input, void *str
     const Dev d = make_dev(eng);
     hipStream_t s = (hipStream_t)stream;
     int32_t *n_live = (int32_t *)eng->p[P_PK_N], *rows = (int32_t *)eng->p[P_PK_ROWS];
-    hipLaunchKernelGGL(k_compact, dim3(1), dim3(CPT), 0, s, d, n_live, rows);
+    const int K = leaves_of(eng);
+    if (K > 1) hipLaunchKernelGGL(k_compact_multi, dim3(1), dim3(CPT), 0, s, d, K, n_live, rows);
+    else hipLaunchKernelGGL(k_compact, dim3(1), dim3(CPT), 0, s, d, n_live, rows);
     int rc = launch_status();
     if (rc != XQ_OK) return rc;
-    hipLaunchKernelGGL(k_gather_rows, dim3(eng->cfg.n_games), dim3(256), 0, s, d, (const int32_t *)n_live, (const int32_t *)rows,
+    hipLaunchKernelGGL(k_gather_rows, dim3(eng->cfg.n_games * K), dim3(256), 0, s, d, (const int32_t *)n_live, (const int32_t *)rows,
                        dev_nn_input, (float *)eng->p[P_PK_X], (uint16_t *)eng->p[P_PK_MOVES], (int32_t *)eng->p[P_PK_COUNTS]);
     return launch_status();
 }
@@ -1288,7 +1962,7 @@ int xq_engine_packed(const xq_engine *eng, xq_engine_packed_buffers *out) {
 int xq_engine_expand_packed(const xq_engine *eng, const float *dev_packed_logits, const float *dev_packed_value, void *stream) {
     if (!eng || !dev_packed_logits || !dev_packed_value || eng->cfg.n_games <= 0) return XQ_ERR_ARG;
     if (((uintptr_t)dev_packed_logits) & 7) return XQ_ERR_ARG;
-    const int G = eng->cfg.n_games;
+    const int G = eng->cfg.n_games * leaves_of(eng);   // request rows
     float *slot_logits = (float *)eng->p[P_PK_LOGITS], *slot_value = (float *)eng->p[P_PK_VALUE];
     hipLaunchKernelGGL(k_scatter_rows, dim3((G + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const int32_t *)eng->p[P_PK_N],
                        (const int32_t *)eng->p[P_PK_ROWS], dev_packed_logits, dev_packed_value, slot_logits, slot_value, G);
@@ -1319,6 +1993,8 @@ int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *
     host_out->children_scanned = h[ST_SCAN]; host_out->resigns = h[ST_RESIGN]; host_out->samples_written = h[ST_SAMP];
     host_out->samples_dropped = h[ST_DROP]; host_out->overflow = h[ST_OVF]; host_out->games_started = h[ST_STARTED];
     host_out->rows_evaluated = h[ST_ROWS];
+    host_out->reserved[XQ_STAT_COLLISIONS] = h[ST_COLL]; host_out->reserved[XQ_STAT_LEAVES_SUM] = h[ST_LPS];
+    host_out->reserved[XQ_STAT_LEAF_STEPS] = h[ST_LSTEPS];
     return h[ST_OVF] ? XQ_ERR_OVERFLOW : XQ_OK;
 }
 
@@ -1449,7 +2125,8 @@ int xq_evcache_hit_flags(const xq_evcache *cache, const int32_t **dev_hit) {
 }
 
 int xq_evcache_probe(const xq_evcache *cache, const xq_engine *eng, const float *dev_nn_input, void *stream) {
-    if (!evcache_ok(cache) || !eng || !dev_nn_input || eng->cfg.n_games <= 0 || cache->n_slots != eng->cfg.n_games)
+    if (!eng || leaves_of(eng) > 1) return XQ_ERR_ARG;            // the cache serves one request row per slot
+    if (!evcache_ok(cache) || !dev_nn_input || eng->cfg.n_games <= 0 || cache->n_slots != eng->cfg.n_games)
         return XQ_ERR_ARG;
     const int G = eng->cfg.n_games;
     hipLaunchKernelGGL(k_evcache_probe, dim3((G + 3) / 4), dim3(256), 0, (hipStream_t)stream, make_dev(eng), make_evdev(cache),
@@ -1458,7 +2135,7 @@ int xq_evcache_probe(const xq_evcache *cache, const xq_engine *eng, const float 
 }
 
 int xq_engine_compact_misses(const xq_engine *eng, const float *dev_nn_input, const int32_t *dev_hit_flags, void *stream) {
-    if (!eng || !dev_nn_input || !dev_hit_flags || eng->cfg.n_games <= 0) return XQ_ERR_ARG;
+    if (!eng || !dev_nn_input || !dev_hit_flags || eng->cfg.n_games <= 0 || leaves_of(eng) > 1) return XQ_ERR_ARG;
     const Dev d = make_dev(eng);
     hipStream_t s = (hipStream_t)stream;
     int32_t *n_live = (int32_t *)eng->p[P_PK_N], *rows = (int32_t *)eng->p[P_PK_ROWS];
@@ -1472,7 +2149,7 @@ int xq_engine_compact_misses(const xq_engine *eng, const float *dev_nn_input, co
 
 int xq_evcache_commit(const xq_evcache *cache, const xq_engine *eng, const float *dev_packed_logits,
                       const float *dev_packed_value, void *stream) {
-    if (!evcache_ok(cache) || !eng || !dev_packed_logits || !dev_packed_value || eng->cfg.n_games <= 0 ||
+    if (!evcache_ok(cache) || !eng || leaves_of(eng) > 1 || !dev_packed_logits || !dev_packed_value || eng->cfg.n_games <= 0 ||
         cache->n_slots != eng->cfg.n_games || (((uintptr_t)dev_packed_logits) & 7))
         return XQ_ERR_ARG;
     const int G = eng->cfg.n_games;

@@ -28,6 +28,13 @@ A cached row is bit-identical to a recomputed one, so the games are those of the
 the rows the network ran on.  The table costs `eval_cache_bytes(G, K)` (576 B per entry); `recommended_cache_entries(S)`
 is the next power of two >= 2 S, about two moves of evaluations.  A weight update of the evaluator (`weights_version`) or
 another evaluator invalidates the table before the next step.
+
+With `leaves_per_step = K > 1` (opt-in, K <= 64; xq_engine_init_leaves) a searching slot hands the evaluator up to K leaves
+per step, collected under virtual loss (include/xq_hip.h), so a move needs about S / K steps instead
+of S.  Every request buffer then has G K rows, slot-major (row slot K + j is pending leaf j): `nn_input`, `req_moves`,
+`req_counts`, the packed buffers and the evaluator's outputs.  Dense, sparse and packed protocols, eager and replayed, work
+as with K = 1.  K > 1 is knowingly not the reference's sequential search; it cannot be combined with the evaluation cache
+or with arena games (manual_moves = 2).  K = 1 is the engine as before.
 """
 from __future__ import annotations
 
@@ -79,15 +86,25 @@ def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
 
 class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
-                 inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0):
+                 inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1):
+        K = int(leaves_per_step)
+        if not 1 <= K <= 64:
+            raise hip.XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
+        if K > 1 and eval_cache_entries:
+            raise hip.XqError("leaves_per_step > 1 cannot be combined with an evaluation cache (eval_cache_entries > 0)")
+        if K > 1 and int(cfg.manual_moves) == 2:
+            raise hip.XqError("leaves_per_step > 1 is not available for arena games (manual_moves = 2)")
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
         self.device = torch.device(device)
         self.cfg = cfg
         self.G = cfg.n_games
+        self.K = K
+        self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
-        nbytes = self.lib.xq_engine_workspace_bytes(C.byref(cfg))
+        nbytes = (self.lib.xq_engine_workspace_bytes(C.byref(cfg)) if K == 1 else
+                  self.lib.xq_engine_workspace_bytes_leaves(C.byref(cfg), K))
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
@@ -101,10 +118,14 @@ class SelfPlayEngine:
             self._inject = torch.from_numpy(inj.view(np.int64)).to(self.device)
             inj_ptr = self._inject.data_ptr()
         self.h = hip.Engine()
-        self.nn_input = torch.zeros((self.G, 15, 10, 9), dtype=torch.float32, device=self.device)
+        self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            hip.check(self.lib.xq_engine_init(C.byref(self.h), C.byref(cfg), base, self.workspace_bytes, inj_ptr,
-                                              hip.stream_ptr(self.device)), "xq_engine_init")
+            if K == 1:
+                hip.check(self.lib.xq_engine_init(C.byref(self.h), C.byref(cfg), base, self.workspace_bytes, inj_ptr,
+                                                  hip.stream_ptr(self.device)), "xq_engine_init")
+            else:
+                hip.check(self.lib.xq_engine_init_leaves(C.byref(self.h), C.byref(cfg), K, base, self.workspace_bytes, inj_ptr,
+                                                         hip.stream_ptr(self.device)), "xq_engine_init_leaves")
         # zero-copy int32 view of the per-slot state words (side to move of the REAL game in column 0, move_count 1,
         # phase 3, simulations done 4): host-side policies such as the arena's model choice read it between stages
         gi_off = int(self.h.p[2]) - int(self.ws.data_ptr())
@@ -113,8 +134,8 @@ class SelfPlayEngine:
         pm, pc = C.c_void_p(), C.c_void_p()
         hip.check(self.lib.xq_engine_requests(C.byref(self.h), C.byref(pm), C.byref(pc)), "xq_engine_requests")
         mo, co = int(pm.value) - int(self.ws.data_ptr()), int(pc.value) - int(self.ws.data_ptr())
-        self.req_moves = self.ws[mo:mo + self.G * hip.MAXM * 2].view(torch.int16).view(self.G, hip.MAXM)
-        self.req_counts = self.ws[co:co + self.G * 4].view(torch.int32)
+        self.req_moves = self.ws[mo:mo + self.rows * hip.MAXM * 2].view(torch.int16).view(self.rows, hip.MAXM)
+        self.req_counts = self.ws[co:co + self.rows * 4].view(torch.int32)
         # packed-step buffers (xq_engine_packed): live count, row -> slot map, packed planes / requests, slot-ordered hand-back
         pb = hip.PackedBuffers()
         hip.check(self.lib.xq_engine_packed(C.byref(self.h), C.byref(pb)), "xq_engine_packed")
@@ -123,7 +144,7 @@ class SelfPlayEngine:
             off = int(addr) - int(self.ws.data_ptr())
             return self.ws[off:off + nbytes].view(dtype)
 
-        G = self.G
+        G = self.rows                                  # packed buffers hold request rows (= slots when K = 1)
         self.n_live = ws_view(pb.n_live, 4, torch.int32)
         self.packed_rows = ws_view(pb.rows, G * 4, torch.int32)
         self.packed_x = ws_view(pb.x, G * hip.STATE_FLOATS * 4, torch.float32).view(G, 15, 10, 9)
@@ -178,7 +199,7 @@ class SelfPlayEngine:
             raise hip.XqError("policy/value must be float32")
         policy = policy.contiguous()
         value = value.contiguous().view(-1)
-        if policy.shape != (self.G, hip.ACTION_SPACE) or value.shape != (self.G,):
+        if policy.shape != (self.rows, hip.ACTION_SPACE) or value.shape != (self.rows,):
             raise hip.XqError(f"bad evaluator output shapes {tuple(policy.shape)} {tuple(value.shape)}")
         hip.check(self.lib.xq_engine_expand(C.byref(self.h), policy.data_ptr(), value.data_ptr(), int(is_probs),
                                             hip.stream_ptr(self.device)), "xq_engine_expand")
@@ -190,7 +211,7 @@ class SelfPlayEngine:
             raise hip.XqError("legal_logits/value must be float32")
         legal_logits = legal_logits.contiguous()
         value = value.contiguous().view(-1)
-        if legal_logits.shape != (self.G, hip.MAXM) or value.shape != (self.G,):
+        if legal_logits.shape != (self.rows, hip.MAXM) or value.shape != (self.rows,):
             raise hip.XqError(f"bad evaluator output shapes {tuple(legal_logits.shape)} {tuple(value.shape)}")
         hip.check(self.lib.xq_engine_expand_legal(C.byref(self.h), legal_logits.data_ptr(), value.data_ptr(),
                                                   hip.stream_ptr(self.device)), "xq_engine_expand_legal")
@@ -221,7 +242,7 @@ class SelfPlayEngine:
             raise hip.XqError("legal_logits/value must be float32")
         legal_logits = legal_logits.contiguous()
         value = value.contiguous().view(-1)
-        if legal_logits.shape != (self.G, hip.MAXM) or value.shape != (self.G,):
+        if legal_logits.shape != (self.rows, hip.MAXM) or value.shape != (self.rows,):
             raise hip.XqError(f"bad evaluator output shapes {tuple(legal_logits.shape)} {tuple(value.shape)}")
         hip.check(self.lib.xq_engine_expand_packed(C.byref(self.h), legal_logits.data_ptr(), value.data_ptr(),
                                                    hip.stream_ptr(self.device)), "xq_engine_expand_packed")
@@ -363,9 +384,22 @@ class SelfPlayEngine:
             nbytes = self.G * cols * torch.empty(0, dtype=dtype).element_size()
             return self.ws[off:off + nbytes].view(dtype).view(self.G, cols)
 
-        return dict(N=view(6, torch.int32, cap), W=view(7, torch.float64, cap), P=view(8, torch.float32, cap),
-                    action=view(9, torch.int16, cap), first=view(10, torch.int32, cap), meta=view(11, torch.int16, cap),
-                    board=view(0, torch.int8, 96), node_cap=cap)
+        out = dict(N=view(6, torch.int32, cap), W=view(7, torch.float64, cap), P=view(8, torch.float32, cap),
+                   action=view(9, torch.int16, cap), first=view(10, torch.int32, cap), meta=view(11, torch.int16, cap),
+                   board=view(0, torch.int8, 96), node_cap=cap)
+        if self.K > 1:
+            out["vl"] = view(30, torch.int32, cap)     # virtual-loss counters: all 0 between steps
+        return out
+
+    def slot_counters(self) -> torch.Tensor:
+        """Zero-copy int64 [G, 32] view of the per-slot counters that xq_engine_stats_read sums (column 19: collisions, 20:
+        pending leaves handed out, 21: slot-steps that handed leaves).  For tests."""
+        off = int(self.h.p[17]) - int(self.ws.data_ptr())
+        return self.ws[off:off + self.G * 32 * 8].view(torch.int64).view(self.G, 32)
+
+    def held(self) -> bool:
+        """Search-only engines: every slot holds its finished search (phase HOLD).  Synchronises."""
+        return bool((self.slot_ints[:, 3] == 7).all().item())
 
     # ---- MCTS.search for a given position (manual_moves engines; mcts.py:94-155) ---------------------------
     def set_position(self, slot: int, board, side: int, move_count: int = 0, no_capture: int = 0, hist12=None,

@@ -56,7 +56,8 @@ class EngineStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in
                 ("sims", "terminal_sims", "leaf_evals", "root_evals", "moves_played", "games_finished", "red_wins",
                  "black_wins", "draws", "plies_finished", "nodes_created", "depth_sum", "children_scanned", "resigns",
-                 "samples_written", "samples_dropped", "overflow", "games_started", "rows_evaluated")] + [("reserved", C.c_uint64 * 13)]
+                 "samples_written", "samples_dropped", "overflow", "games_started", "rows_evaluated", "collisions",
+                 "leaves_per_step_sum", "leaf_steps")] + [("reserved", C.c_uint64 * 10)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
@@ -105,6 +106,9 @@ def lib():
     L.xq_engine_workspace_bytes.argtypes = [C.POINTER(EngineConfig)]
     L.xq_engine_workspace_bytes.restype = C.c_size_t
     L.xq_engine_init.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), vp, C.c_size_t, vp, vp]
+    L.xq_engine_workspace_bytes_leaves.argtypes = [C.POINTER(EngineConfig), i32]
+    L.xq_engine_workspace_bytes_leaves.restype = C.c_size_t
+    L.xq_engine_init_leaves.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, vp, C.c_size_t, vp, vp]
     L.xq_engine_select.argtypes = [C.POINTER(Engine), vp, vp]
     L.xq_engine_expand.argtypes = [C.POINTER(Engine), vp, vp, i32, vp]
     L.xq_engine_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(EngineStats), vp]
@@ -177,7 +181,7 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_bn_sync_sums_count", "xq_bn_sync_forward_stats", "xq_bn_sync_forward_apply", "xq_bn_sync_backward_stats",
            "xq_bn_sync_backward_apply", "xq_evcache_bytes", "xq_evcache_init", "xq_evcache_hit_flags", "xq_evcache_probe",
            "xq_engine_compact_misses", "xq_evcache_commit", "xq_evcache_invalidate", "xq_evcache_stats_read",
-           "xq_evcache_key_host"]
+           "xq_evcache_key_host", "xq_engine_workspace_bytes_leaves", "xq_engine_init_leaves"]
 
 
 def check(rc: int, what: str):

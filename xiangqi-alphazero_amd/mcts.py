@@ -9,6 +9,10 @@
 `.no_capture_count`, `.history` (list of the pre-move boards as 90-byte `bytes`).  `n_parallel` positions can be
 searched at once with `search_many`.  One slot of a search-only engine (`manual_moves = 1`) per position; the network
 is evaluated on the GPU.  With `add_noise=True` the root noise comes from the device Dirichlet(0.3) generator.
+
+`leaves_per_step = K > 1` (opt-in, K <= 64) batches up to K leaves per position and step under virtual loss
+(engine.SelfPlayEngine): a search of S simulations takes about S / K + 1 steps instead of S + 1.  It is knowingly not the
+reference's sequential search (the visit counts differ); K = 1 is.
 """
 from __future__ import annotations
 
@@ -22,7 +26,11 @@ from .sample_format import ACTION_SPACE, dense_pi
 
 class MCTS:
     def __init__(self, model, num_simulations: int = 200, c_puct: float = 1.5, device: str = "cuda",
-                 evaluator_kind: str = "auto", seed: int = 0):
+                 evaluator_kind: str = "auto", seed: int = 0, leaves_per_step: int = 1):
+        if not 1 <= int(leaves_per_step) <= 64:
+            from .hip import XqError
+            raise XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
+        self.leaves_per_step = int(leaves_per_step)
         self.model = model
         self.num_simulations = num_simulations
         self.c_puct = c_puct
@@ -46,7 +54,8 @@ class MCTS:
         if key not in self._engines:
             cfg = engine.make_config(n, self.num_simulations, c_puct=self.c_puct, add_noise=add_noise, manual_moves=1,
                                      seed=self.seed)
-            self._engines[key] = engine.SelfPlayEngine(cfg, self.device, evaluator=self.evaluator)
+            self._engines[key] = engine.SelfPlayEngine(cfg, self.device, evaluator=self.evaluator,
+                                                       leaves_per_step=self.leaves_per_step)
         return self._engines[key]
 
     def search_many(self, games: Sequence, temperature: float = 1.0, add_noise: bool = True) -> List[np.ndarray]:
@@ -55,8 +64,18 @@ class MCTS:
             hist = [np.frombuffer(h, dtype=np.int8) for h in list(g.history)[-12:]]
             eng.set_position(slot, np.asarray(g.board, dtype=np.int8), int(g.current_player), int(g.move_count),
                              int(g.no_capture_count), np.stack(hist) if hist else None)
-        for _ in range(self.num_simulations + 1):
+        # the root, then S simulations in at least ceil(S / K) steps; collisions (K > 1) and long runs of terminal leaves
+        # can add steps, so the engine is stepped on in small chunks until every slot holds its finished search
+        K = self.leaves_per_step
+        for _ in range(-(-self.num_simulations // K) + 1):
             eng.step()
+        extra = 0
+        while not eng.held():
+            for _ in range(8):
+                eng.step()
+            extra += 8
+            if extra > 4 * self.num_simulations + 64:
+                raise RuntimeError("search did not finish")
         out = []
         for slot in range(len(games)):
             r = eng.read_root(slot)

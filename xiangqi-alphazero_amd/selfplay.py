@@ -24,13 +24,17 @@ _CFG_KEYS = ("num_simulations", "c_puct", "temperature_threshold", "max_game_len
 
 def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[int] = None, seed: int = 0, rank: int = 0,
               evaluator_kind: str = "hip", poll_every: int = 64, device_records: bool = False, use_graph: bool = True,
-              eval_cache_entries: Optional[int] = None):
+              eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
-    many entries (engine.recommended_cache_entries); the games are the same, the network runs on fewer rows."""
+    many entries (engine.recommended_cache_entries); the games are the same, the network runs on fewer rows.
+    `leaves_per_step` (None: `config.leaves_per_step`, absent = 1) batches up to that many leaves per slot and step under
+    virtual loss (engine.SelfPlayEngine); K > 1 is not the reference's sequential search and excludes the cache."""
     if eval_cache_entries is None:
         eval_cache_entries = int(getattr(config, "eval_cache_entries", 0) or 0)
+    if leaves_per_step is None:
+        leaves_per_step = int(getattr(config, "leaves_per_step", 1) or 1)
     slots = int(n_slots or min(num_games, 8192))
     slots = max(1, min(slots, num_games))
     ev, ev_name = evaluator.make_evaluator(model, device, evaluator_kind)
@@ -41,7 +45,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
         resign_threshold=float(config.resign_threshold), resign_check_steps=int(config.resign_check_steps),
         add_noise=True, seed=seed, rank=rank, games_target=num_games,
         max_out_samples=num_games * 201, max_out_results=num_games + 8)
-    eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries)
+    eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries,
+                                leaves_per_step=leaves_per_step)
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -57,6 +62,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     st["launch"] = eng.launch_mode                     # "graph" (one HIP-graph replay per step) or "eager"
     st["path"] = eng.path                              # "packed": the evaluator ran over the waiting slots only; "full": all
     st["steps"] = eng.steps                            # rows_evaluated / (steps * slots): the share of the full width evaluated
+    st["leaves_per_step"] = eng.K
     st.setdefault("eval_cache_probes", 0)              # the cache's keys are present (0) when it is off
     st.setdefault("eval_cache_hits", 0)
     if eng.capture_error:
@@ -66,13 +72,16 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
 
 def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu_server: bool = False,
                        gpu_device: str = "cuda", *, n_slots: Optional[int] = None, seed: int = 0,
-                       return_compact: bool = False, eval_cache_entries: Optional[int] = None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
+                       return_compact: bool = False, eval_cache_entries: Optional[int] = None,
+                       leaves_per_step: Optional[int] = None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
     for k in _CFG_KEYS + ("num_games_per_iter",):
         if not hasattr(config, k):
             raise AttributeError(f"config lacks '{k}' (see training/train.py:55-111)")
     num_games = int(config.num_games_per_iter)
+    if leaves_per_step is None:
+        leaves_per_step = int(getattr(config, "leaves_per_step", 1) or 1)   # a reference TrainingConfig has no such key
     samples, results, st, elapsed = run_games(model, config, num_games, gpu_device, n_slots, seed,
-                                              eval_cache_entries=eval_cache_entries)
+                                              eval_cache_entries=eval_cache_entries, leaves_per_step=leaves_per_step)
     all_data, per_game = to_reference_tuples(samples, results, augment=True)
     wins = {1: 0, -1: 0, 0: 0}
     total_steps = 0

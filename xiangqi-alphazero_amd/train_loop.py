@@ -76,7 +76,9 @@ class AlphaZeroLoop:
                     torch.empty((0, 16), dtype=torch.uint8, device=self.device))
         samples, results, _, _ = selfplay.run_games(self.best_model, self.config, n_games, self.device,
                                                     seed=self.seed + 1000 * self.iteration, rank=self.rank,
-                                                    evaluator_kind=self.evaluator_kind, device_records=True)
+                                                    evaluator_kind=self.evaluator_kind, device_records=True,
+                                                    # leaf batching is a self-play option only: the arena stays sequential
+                                                    leaves_per_step=int(getattr(self.config, "leaves_per_step", 1) or 1))
         return samples, results
 
     def self_play(self) -> dict:
