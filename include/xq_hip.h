@@ -153,7 +153,8 @@ typedef struct xq_engine_stats {
     uint64_t overflow;        /* non-zero: a device capacity was exceeded (results invalid) */
     uint64_t games_started;
     uint64_t rows_evaluated;  /* sum over xq_engine_compact calls of n_live: rows the evaluator ran on in packed steps */
-    uint64_t reserved[13];    /* [XQ_STAT_COLLISIONS], [XQ_STAT_LEAVES_SUM], [XQ_STAT_LEAF_STEPS]: the leaf-batching counters below */
+    uint64_t reserved[13];    /* [XQ_STAT_COLLISIONS], [XQ_STAT_LEAVES_SUM], [XQ_STAT_LEAF_STEPS]: the leaf-batching counters below;
+                                 [XQ_STAT_REUSED_VISITS], [XQ_STAT_REROOTS]: the tree-reuse counters (xq_engine_init_ex) */
 
 } xq_engine_stats;
 /* Leaf-batching counters (xq_engine_init_leaves), kept in the reserved words so the struct's layout is unchanged:
@@ -164,6 +165,12 @@ typedef struct xq_engine_stats {
 #define XQ_STAT_COLLISIONS 0
 #define XQ_STAT_LEAVES_SUM 1
 #define XQ_STAT_LEAF_STEPS 2
+/* Tree-reuse counters (XQ_ENGINE_TREE_REUSE), 0 without it:
+ *   reserved[XQ_STAT_REUSED_VISITS]  visits a search started with from the previous move's tree (sum over re-rooted roots)
+ *   reserved[XQ_STAT_REROOTS]        searches that started from the previous move's subtree
+ * `sims` keeps counting new simulations only: the samples' visits sum to sims + REUSED_VISITS over finished moves. */
+#define XQ_STAT_REUSED_VISITS 3
+#define XQ_STAT_REROOTS 4
 
 /* Bytes of device workspace the engine needs for cfg (tree arenas dominate:
  * n_games * (1 + (num_simulations+1)*XQ_MAXM) nodes * 24 B -- sized for 288 GB HBM, no per-node malloc). */
@@ -202,6 +209,31 @@ int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t
 size_t xq_engine_workspace_bytes_leaves(const xq_engine_config *cfg, int leaves_per_step);
 int xq_engine_init_leaves(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, void *ws, size_t ws_bytes,
                           const uint64_t *dev_inject, void *stream);
+
+/* Tree reuse across moves (opt-in flag XQ_ENGINE_TREE_REUSE of xq_engine_init_ex; flags = 0 is xq_engine_init_leaves).
+ * When a self-play move ends, the chosen child c becomes the next search's root with its whole subtree: every kept node keeps
+ * its N, W, P, action, child count and kind, its children stay in order; the old root and the sibling subtrees are discarded.
+ * Within the step of the move's end, xq_engine_select also launches k_reroot, which compacts c's subtree in place to the front
+ * of the slot's arena (c at node 0, the allocation mark at 1 + the kept nodes).  The new position still issues its root
+ * request: resign probe, terminal / adjudication status and the evaluation cache are unchanged.  The reused root's children
+ * get their float32 priors from this evaluation (bit-identical to the stored ones under unchanged weights) and fresh Dirichlet
+ * noise (the same draws a fresh root takes), and the search starts at sims_done = root N = the sum of its children's visits:
+ * it stops at num_simulations as always, so a sample still holds exactly num_simulations visits, some of them gathered before
+ * that root's noise was drawn, and a move costs num_simulations minus the reused visits in new simulations.
+ * A slot starts a fresh tree on a new game, when the chosen child was never expanded, and when xq_engine_drop_reroots ran
+ * since the move began (call it after every weight update: graph-safe, one device-side word per slot, no host sync).  A
+ * reused root whose child count differs from the position's legal-move count (a defect) sets overflow bit 64 << 8.
+ * XQ_ERR_ARG before any launch: unknown flags, and tree reuse with manual_moves 1 or 2, leaves_per_step > 1 or
+ * num_simulations > XQ_REUSE_MAX_SIMS (k_reroot keeps a bitmap of the arena in at most 64 KiB of LDS).  The flag lives in the
+ * handle (pad0's upper 16 bits); it adds no workspace: xq_engine_workspace_bytes_ex is xq_engine_workspace_bytes_leaves for
+ * valid flags and 0 otherwise.  Combining it with the evaluation cache is supported. */
+#define XQ_ENGINE_TREE_REUSE 1u
+#define XQ_REUSE_MAX_SIMS 1600
+size_t xq_engine_workspace_bytes_ex(const xq_engine_config *cfg, int leaves_per_step, unsigned flags);
+int xq_engine_init_ex(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, void *ws,
+                      size_t ws_bytes, const uint64_t *dev_inject, void *stream);
+/* No slot of a tree-reuse engine re-roots at the end of the move it is searching now (XQ_ERR_ARG without the flag). */
+int xq_engine_drop_reroots(const xq_engine *eng, void *stream);
 
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 

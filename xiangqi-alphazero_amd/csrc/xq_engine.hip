@@ -11,6 +11,8 @@
 //                reference's sequential-float32 mask-and-normalise (mcts.py:176-188), children appended to the
 //                slot's bump arena, Dirichlet noise at the root (mcts.py:117-121), resign probe
 //                (parallel_selfplay.py:110-121), backup along the recorded path (mcts.py:66-73).
+//   k_reroot : tree reuse (opt-in, XQ_ENGINE_TREE_REUSE; k_select<true> / k_expand<true>): the chosen child's subtree moved to the
+//                front of the slot's arena, in place, between select and expand of the step that ends a move.
 //
 // Numeric contract (pinned by tests against the reference's MCTS under a stub evaluator): priors float32,
 // PUCT evaluated in float32 as f32(q) + ((f32(c)*P)*f32(sqrt(N_parent)))/f32(1+N); at a noisy root (and for the
@@ -36,10 +38,11 @@ enum Phase : int { PH_NEWGAME = 0, PH_NEWPOS = 1, PH_WAIT_ROOT = 2, PH_SEARCH = 
 
 enum Gi : int { GI_SIDE = 0, GI_MC, GI_NOCAP, GI_PHASE, GI_SIMS, GI_NSAMP, GI_GSEQ, GI_ALLOC, GI_PLEAF, GI_PDEPTH,
                 GI_PCOUNT, GI_RSTATUS, GI_RWINNER, GI_RESIGN_N, GI_RNG0, GI_RNG1, GI_RNG2, GI_RNG3, GI_FWINNER,
-                GI_FREASON, GI_MANNOISE, GI_DELAY, GI_NPEND, GI_N = 32 };
+                GI_FREASON, GI_MANNOISE, GI_DELAY, GI_NPEND, GI_RR_NODE, GI_RR_MARK, GI_RR_DROP, GI_N = 32 };
 
 enum St : int { ST_SIMS = 0, ST_TERM, ST_LEAF, ST_ROOT, ST_MOVES, ST_GAMES, ST_RED, ST_BLACK, ST_DRAW, ST_PLIES, ST_NODES,
-                ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_COLL, ST_LPS, ST_LSTEPS, ST_N = 32 };
+                ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_COLL, ST_LPS, ST_LSTEPS, ST_REUSED,
+                ST_REROOTS, ST_N = 32 };
 
 enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_TW, P_TP, P_TA, P_TC, P_TM, P_ROOTP,
                  P_STAGE, P_OUTS, P_OUTR, P_CNT, P_STATS, P_INJECT, P_SQRT, P_MNOISE, P_STATSUM, P_REQ,
@@ -251,6 +254,9 @@ constexpr int WAVES_PER_WG = 4;
 #else
 #define XQ_SELECT_OCC
 #endif
+// REUSE (tree reuse): at the end of a move the chosen child and the old allocation mark are handed to k_reroot and
+// k_expand<true> of the same step (GI_RR_NODE / GI_RR_MARK); k_select<false> is k_select as it always was.
+template <bool REUSE>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev E, float *__restrict__ nn_in) {
     __shared__ SelectLds Ls[WAVES_PER_WG];
     SelectLds &L = Ls[threadIdx.x >> 6];
@@ -350,6 +356,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
             init_board_lds(L.root);
             g_side = 1; g_mc = 0; g_nocap = 0;
             if (lane == 0) { gi[GI_RESIGN_N] = 0; st[ST_STARTED] += 1; }
+            if (REUSE && lane == 0) gi[GI_RR_NODE] = 0;     // a new game never sees a hand-off
             wave_sync();
             const int R = arena ? 0 : E.cfg.random_opening_moves;
             const int k = R > 0 ? (int)(draw_u64(E, slot, RNG_RANDINT, rng_ctr[RNG_RANDINT], st) % (uint64_t)(R + 1)) : 0;
@@ -395,6 +402,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                 gi[GI_ALLOC] = 1;
                 tN[0] = 0; tW[0] = 0.0; tC[0] = -1; tM[0] = 0; tA[0] = 0; tP[0] = 0.0f;
             }
+            if (REUSE && lane == 0) gi[GI_RR_DROP] = 0;      // this move's tree is grown under the current weights
             sims_done = 0;
             req_cnt = cnt;
             phase = PH_WAIT_ROOT;
@@ -474,6 +482,19 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                 action = L.sa[pick];
             }
             action = __builtin_amdgcn_readfirstlane(action);
+            if (REUSE) {
+                // hand the chosen child c to k_reroot / k_expand<true> of this step when it was expanded and no drop
+                // (xq_engine_drop_reroots) ran since this move began; L.a_tmp[i] is child i's action
+                int c = 0;
+                for (int base = 0; base < nch; base += 64) {
+                    const unsigned long long b = __ballot(base + lane < nch && (int)L.a_tmp[base + lane] == action);
+                    if (b) { c = first + base + (int)__builtin_ctzll(b); break; }
+                }
+                c = __builtin_amdgcn_readfirstlane(c);
+                const bool keep = c > 0 && __builtin_amdgcn_readfirstlane(tC[c]) >= 0 &&
+                                  __builtin_amdgcn_readfirstlane(gi[GI_RR_DROP]) == 0;
+                if (lane == 0) { gi[GI_RR_NODE] = keep ? c : 0; gi[GI_RR_MARK] = keep ? gi[GI_ALLOC] : 0; }
+            }
             wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
             n_samples += 1;
             d_moves += 1;
@@ -609,6 +630,10 @@ struct ExpandLds {
 
 // one game per 64-thread workgroup: this kernel streams 32 KB of logits per game and measured faster with more,
 // smaller workgroups in flight (0.111 vs 0.132 ms at G = 8192) than with four games per workgroup
+// REUSE (k_expand<true>): a root request of a slot that k_select<true> handed a chosen child to (GI_RR_NODE; k_reroot has moved
+// that child's subtree to the front of the arena) keeps the children, their N, W, first-child and meta words, rewrites their
+// float32 priors, draws fresh noise into rootP and starts the search at sims_done = root N = the sum of their visits.
+template <bool REUSE>
 __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ policy, const float *__restrict__ value,
                                                int is_probs) {
     __shared__ ExpandLds L;
@@ -632,8 +657,15 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
     const int cnt = __builtin_amdgcn_readfirstlane(gi[GI_PCOUNT]);
     int sims_done = __builtin_amdgcn_readfirstlane(gi[GI_SIMS]);
     int ovf = 0;
+    int rr = 0;                                       // REUSE: the re-rooted child of this step's hand-off (0: none)
 
     if (is_root) {
+        if (REUSE) {
+            rr = __builtin_amdgcn_readfirstlane(gi[GI_RR_NODE]);
+            // consumed: a hand-off lives for one step.  The store depends on rr: the word is read by a scalar load, and a
+            // vector store issued before that load returns could overtake it (the load would then see the cleared word)
+            if (rr != 0 && lane == 0) gi[GI_RR_NODE] = 0;
+        }
         if (lane == 0) st[ST_ROOT] += 1;
         const int side = gi[GI_SIDE];
         int fin = 0, fwinner = 0, freason = 0;
@@ -735,7 +767,20 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
     }
 
     const int node = is_root ? 0 : __builtin_amdgcn_readfirstlane(gi[GI_PLEAF]);
-    const int first = __builtin_amdgcn_readfirstlane(gi[GI_ALLOC]);
+    int first = __builtin_amdgcn_readfirstlane(gi[GI_ALLOC]);
+    bool reused = false;
+    int root_sims = 0;                                // the search's first sims_done: 0, or the reused root's visits
+    if (REUSE && rr > 0) {
+        // node 0 holds the chosen child's words (k_reroot); its children must be this position's legal moves
+        const int m0 = __builtin_amdgcn_readfirstlane((int)tM[0]), f0 = __builtin_amdgcn_readfirstlane(tC[0]);
+        reused = cnt > 0 && (m0 & 0x3FFF) == cnt && f0 >= 1 && f0 + cnt <= E.node_cap;
+        if (reused) {
+            first = f0;
+        } else {                                      // a defect: reported, and the root is expanded afresh
+            ovf |= 64;
+            if (lane == 0) { tN[0] = 0; tW[0] = 0.0; }
+        }
+    }
     if (cnt > 0) {
         if (first + cnt > E.node_cap) {
             ovf |= 32;
@@ -758,18 +803,35 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
                     tP[first + i] = (float)uni;
                 }
             }
-            for (int i = lane; i < cnt; i += 64) {
-                tN[first + i] = 0; tW[first + i] = 0.0; tA[first + i] = L.act[i]; tC[first + i] = -1; tM[first + i] = 0;
-            }
-            if (lane == 0) {
-                tC[node] = first; tM[node] = (uint16_t)(cnt | (kind << 14));
-                gi[GI_ALLOC] = first + cnt;
-                st[ST_NODES] += (unsigned)cnt;
+            if (REUSE && reused) {
+                // the kept children keep N, W, action, first child and meta; the budget is visits: sims_done = root N = sum N
+                int vis = 0, bad = 0;
+                for (int i = lane; i < cnt; i += 64) {
+                    vis += tN[first + i];
+                    bad |= tA[first + i] != L.act[i];
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) { vis += __shfl_xor(vis, off); bad |= __shfl_xor(bad, off); }
+                root_sims = __builtin_amdgcn_readfirstlane(vis);
+                if (__builtin_amdgcn_readfirstlane(bad)) ovf |= 64;
+                if (lane == 0) {
+                    tM[0] = (uint16_t)(cnt | (kind << 14)); tN[0] = root_sims;
+                    st[ST_REUSED] += (unsigned)root_sims; st[ST_REROOTS] += 1;
+                }
+            } else {
+                for (int i = lane; i < cnt; i += 64) {
+                    tN[first + i] = 0; tW[first + i] = 0.0; tA[first + i] = L.act[i]; tC[first + i] = -1; tM[first + i] = 0;
+                }
+                if (lane == 0) {
+                    tC[node] = first; tM[node] = (uint16_t)(cnt | (kind << 14));
+                    gi[GI_ALLOC] = first + cnt;
+                    st[ST_NODES] += (unsigned)cnt;
+                }
             }
         }
     }
     if (is_root) {
-        if (lane == 0) { gi[GI_PHASE] = PH_SEARCH; gi[GI_SIMS] = 0; if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8; }
+        if (lane == 0) { gi[GI_PHASE] = PH_SEARCH; gi[GI_SIMS] = root_sims; if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8; }
         return;
     }
     // ---- leaf: value = -v (mcts.py:150), backup
@@ -783,6 +845,143 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
         st[ST_SIMS] += 1;
         if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Tree reuse (xq_engine_init_ex, XQ_ENGINE_TREE_REUSE): k_reroot moves the subtree of the chosen child c that k_select<true>
+// handed over (GI_RR_NODE, with the old allocation mark GI_RR_MARK) to the front of the slot's arena, in place.
+//   * [1, mark) is the child blocks laid end to end in allocation order, and a block is allocated when its parent is expanded:
+//     allocation order is topological, every kept node lies after its parent and c's children block is the first kept one.
+//   * The kept nodes are c's descendants (whole blocks), marked level by level from c in an LDS bitmap over [0, mark).  A kept
+//     node's new index is 1 + the number of kept nodes before it (per-word prefix counts); c's words go to node 0.  This stable
+//     compaction moves every kept node to an index below its old one, so an ascending copy whose chunks read everything into
+//     registers and pass a barrier before writing never overwrites a word that is still to be read.
+// The tree is validated before the first write: a malformed one drops the hand-off (k_expand<true> then expands a fresh root)
+// and sets overflow bit 64 << 8.  LDS atomics only build the bitmap and the level queue, whose order does not change the
+// result.  One 256-thread workgroup per slot (grid G: the step stays one graph); slots without a hand-off exit at once.
+constexpr int RR_THREADS = 256, RR_PER_THREAD = 4;
+
+// dynamic LDS of k_reroot: bitmap and prefix words over node_cap, and the level queue of kept expanded nodes (at most S + 1)
+size_t reroot_lds_bytes(int node_cap, int num_simulations) {
+    return ((size_t)2 * ((node_cap + 31) / 32) + (size_t)num_simulations + 2) * 4;
+}
+
+__global__ __launch_bounds__(RR_THREADS) void k_reroot(Dev E) {
+    extern __shared__ uint32_t rr_lds[];
+    __shared__ int s_tail, s_bad, s_wsum[RR_THREADS / 64];
+    const int slot = blockIdx.x;
+    if (slot >= E.cfg.n_games) return;
+    int32_t *gi = E.gi + (size_t)slot * GI_N;
+    const int c = __builtin_amdgcn_readfirstlane(gi[GI_RR_NODE]);
+    if (c <= 0) return;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    unsigned long long *st = E.stats + (size_t)slot * ST_N;
+    const size_t nb = (size_t)slot * E.node_cap;
+    int32_t *tN = E.tN + nb; double *tW = E.tW + nb; float *tP = E.tP + nb;
+    uint16_t *tA = E.tA + nb; int32_t *tC = E.tC + nb; uint16_t *tM = E.tM + nb;
+    const int mark = __builtin_amdgcn_readfirstlane(gi[GI_RR_MARK]);
+    const int nw = (E.node_cap + 31) >> 5, qcap = E.cfg.num_simulations + 2;
+    uint32_t *bits = rr_lds;                          // [nw]   kept-node bitmap
+    int32_t *pre = (int32_t *)(rr_lds + nw);          // [nw]   kept nodes before each bitmap word
+    int32_t *q = pre + nw;                            // [qcap] kept expanded nodes, level after level
+
+    // c's words first: its index may be a destination of the compaction
+    const bool c_in = c < mark && mark <= E.node_cap;
+    const int cN = c_in ? tN[c] : 0, cF = c_in ? tC[c] : -1, cM = c_in ? (int)tM[c] : 0;
+    const double cW = c_in ? tW[c] : 0.0;
+    const float cP = c_in ? tP[c] : 0.0f;
+    const uint16_t cA = c_in ? tA[c] : 0;
+    if (!(c_in && cF > c && (cM & 0x3FFF) > 0 && cF + (cM & 0x3FFF) <= mark)) {
+        if (t == 0) { gi[GI_RR_NODE] = 0; st[ST_OVF] |= 64ull << 8; }
+        return;
+    }
+    const int mw = (mark + 31) >> 5;
+    for (int w = t; w < mw; w += RR_THREADS) bits[w] = 0u;
+    if (t == 0) { q[0] = c; s_tail = 1; s_bad = 0; }
+    __syncthreads();
+    // ---- mark c's descendants: level by level, the children blocks of the queue entries [lo, hi), one wave per entry
+    int lo = 0, hi = 1;
+    while (lo < hi) {
+        for (int e = lo + wave; e < hi; e += RR_THREADS / 64) {
+            const int x = q[e];
+            const int f = tC[x], n = tM[x] & 0x3FFF;
+            if (!(f > x && n > 0 && f + n <= mark)) { s_bad = 1; continue; }
+            for (int i = lane; i < n; i += 64) {
+                const int y = f + i;
+                atomicOr(&bits[y >> 5], 1u << (y & 31));
+                if (tC[y] >= 0) {
+                    const int k = atomicAdd(&s_tail, 1);
+                    if (k < qcap) q[k] = y; else s_bad = 1;
+                }
+            }
+        }
+        __syncthreads();
+        lo = hi;
+        hi = min(s_tail, qcap);
+        __syncthreads();                              // every thread has read s_tail before the next level appends
+    }
+    if (s_bad) {
+        if (t == 0) { gi[GI_RR_NODE] = 0; st[ST_OVF] |= 64ull << 8; }
+        return;
+    }
+    // ---- exclusive prefix of the per-word counts: thread t owns the contiguous words [w0, w1)
+    const int per = (mw + RR_THREADS - 1) / RR_THREADS;
+    const int w0 = min(t * per, mw), w1 = min(w0 + per, mw);
+    int cnt = 0;
+    for (int w = w0; w < w1; ++w) cnt += __popc(bits[w]);
+    int inc = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(inc, off);
+        if (lane >= off) inc += v;
+    }
+    if (lane == 63) s_wsum[wave] = inc;
+    __syncthreads();
+    int base = 0, kept = 0;
+#pragma unroll
+    for (int w = 0; w < RR_THREADS / 64; ++w) {
+        const int v = s_wsum[w];
+        base += w < wave ? v : 0;
+        kept += v;
+    }
+    int run = base + inc - cnt;
+    for (int w = w0; w < w1; ++w) { pre[w] = run; run += __popc(bits[w]); }
+    __syncthreads();
+    auto new_index = [&](int x) { return 1 + pre[x >> 5] + __popc(bits[x >> 5] & ((1u << (x & 31)) - 1u)); };
+    // ---- ascending copy of [cF, mark): read a chunk into registers, barrier, write it below
+    for (int a = cF; a < mark; a += RR_THREADS * RR_PER_THREAD) {
+        int dst[RR_PER_THREAD], vN[RR_PER_THREAD], vC[RR_PER_THREAD];
+        double vW[RR_PER_THREAD];
+        float vP[RR_PER_THREAD];
+        uint16_t vA[RR_PER_THREAD], vM[RR_PER_THREAD];
+#pragma unroll
+        for (int r = 0; r < RR_PER_THREAD; ++r) {
+            const int x = a + r * RR_THREADS + t;
+            dst[r] = -1; vN[r] = 0; vC[r] = -1; vW[r] = 0.0; vP[r] = 0.0f; vA[r] = 0; vM[r] = 0;
+            if (x < mark && ((bits[x >> 5] >> (x & 31)) & 1u)) {
+                dst[r] = new_index(x);
+                vN[r] = tN[x]; vW[r] = tW[x]; vP[r] = tP[x]; vA[r] = tA[x]; vM[r] = tM[x];
+                const int f = tC[x];
+                vC[r] = f < 0 ? -1 : new_index(f);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < RR_PER_THREAD; ++r) {
+            const int d = dst[r];
+            if (d >= 0) { tN[d] = vN[r]; tW[d] = vW[r]; tP[d] = vP[r]; tA[d] = vA[r]; tC[d] = vC[r]; tM[d] = vM[r]; }
+        }
+    }
+    if (t == 0) {
+        tN[0] = cN; tW[0] = cW; tP[0] = cP; tA[0] = cA; tM[0] = (uint16_t)cM; tC[0] = new_index(cF);
+        gi[GI_ALLOC] = 1 + kept;
+    }
+}
+
+// xq_engine_drop_reroots: no slot hands its chosen child over at the end of the move it is searching now
+__global__ void k_drop_reroots(Dev E) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot < E.cfg.n_games) E.gi[(size_t)slot * GI_N + GI_RR_DROP] = 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1819,8 +2018,16 @@ bool config_ok(const xq_engine_config *c) {
 
 bool leaves_ok(const xq_engine_config *c, int K) { return K >= 1 && K <= 64 && !(K > 1 && c->manual_moves == 2); }
 
-// leaves per step of an engine handle (pad0; 0 = 1)
-int leaves_of(const xq_engine *e) { return e->pad0 > 1 ? e->pad0 : 1; }
+// tree reuse: self-play only, one leaf per step, S within k_reroot's LDS (64 KiB at S = XQ_REUSE_MAX_SIMS)
+bool flags_ok(const xq_engine_config *c, int K, unsigned flags) {
+    if (flags & ~(unsigned)XQ_ENGINE_TREE_REUSE) return false;
+    if (!(flags & XQ_ENGINE_TREE_REUSE)) return true;
+    return c->manual_moves == 0 && K == 1 && c->num_simulations <= XQ_REUSE_MAX_SIMS;
+}
+
+// pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them
+int leaves_of(const xq_engine *e) { return (e->pad0 & 0xFFFF) > 1 ? (e->pad0 & 0xFFFF) : 1; }
+bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE_TREE_REUSE; }
 
 Mx make_mx(const xq_engine *e) {
     Mx x;
@@ -1840,18 +2047,29 @@ size_t xq_engine_workspace_bytes(const xq_engine_config *cfg) {
 }
 
 size_t xq_engine_workspace_bytes_leaves(const xq_engine_config *cfg, int leaves_per_step) {
-    if (!config_ok(cfg) || !leaves_ok(cfg, leaves_per_step)) return 0;
-    return make_layout(cfg, leaves_per_step).total;
+    return xq_engine_workspace_bytes_ex(cfg, leaves_per_step, 0u);
+}
+
+size_t xq_engine_workspace_bytes_ex(const xq_engine_config *cfg, int leaves_per_step, unsigned flags) {
+    if (!config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags)) return 0;
+    return make_layout(cfg, leaves_per_step).total;   // tree reuse needs no workspace of its own
 }
 
 int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t ws_bytes, const uint64_t *dev_inject,
                    void *stream) {
-    return xq_engine_init_leaves(eng, cfg, 1, ws, ws_bytes, dev_inject, stream);
+    return xq_engine_init_ex(eng, cfg, 1, 0u, ws, ws_bytes, dev_inject, stream);
 }
 
 int xq_engine_init_leaves(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, void *ws, size_t ws_bytes,
                           const uint64_t *dev_inject, void *stream) {
-    if (!eng || !config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !ws || ((uintptr_t)ws & 255)) return XQ_ERR_ARG;
+    return xq_engine_init_ex(eng, cfg, leaves_per_step, 0u, ws, ws_bytes, dev_inject, stream);
+}
+
+int xq_engine_init_ex(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, void *ws,
+                      size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
+    if (!eng || !config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags) || !ws ||
+        ((uintptr_t)ws & 255))
+        return XQ_ERR_ARG;
     if (cfg->inject_len > 0 && !dev_inject) return XQ_ERR_ARG;
     const int K = leaves_per_step;
     const Layout l = make_layout(cfg, K);
@@ -1859,7 +2077,7 @@ int xq_engine_init_leaves(xq_engine *eng, const xq_engine_config *cfg, int leave
     memset(eng, 0, sizeof(*eng));
     eng->cfg = *cfg;
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
-    eng->pad0 = K > 1 ? K : 0;
+    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -1894,8 +2112,24 @@ int xq_engine_select(const xq_engine *eng, float *dev_nn_input, void *stream) {
         hipLaunchKernelGGL(k_select_multi, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, make_mx(eng), dev_nn_input);
         return launch_status();
     }
-    hipLaunchKernelGGL(k_select, dim3((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), dim3(64 * WAVES_PER_WG), 0,
+    if (reuse_of(eng)) {
+        // the re-root runs here, between k_select<true> and the expansion, so every step variant (full, packed, cached) has it
+        hipLaunchKernelGGL(k_select<true>, dim3((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), dim3(64 * WAVES_PER_WG), 0,
+                           (hipStream_t)stream, d, dev_nn_input);
+        const int rc = launch_status();
+        if (rc != XQ_OK) return rc;
+        hipLaunchKernelGGL(k_reroot, dim3(eng->cfg.n_games), dim3(RR_THREADS),
+                           (unsigned)reroot_lds_bytes(eng->node_cap, eng->cfg.num_simulations), (hipStream_t)stream, d);
+        return launch_status();
+    }
+    hipLaunchKernelGGL(k_select<false>, dim3((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), dim3(64 * WAVES_PER_WG), 0,
                        (hipStream_t)stream, d, dev_nn_input);
+    return launch_status();
+}
+
+int xq_engine_drop_reroots(const xq_engine *eng, void *stream) {
+    if (!eng || !reuse_of(eng) || eng->cfg.n_games <= 0) return XQ_ERR_ARG;
+    hipLaunchKernelGGL(k_drop_reroots, dim3((eng->cfg.n_games + 255) / 256), dim3(256), 0, (hipStream_t)stream, make_dev(eng));
     return launch_status();
 }
 
@@ -1908,7 +2142,12 @@ int xq_engine_expand(const xq_engine *eng, const float *dev_policy, const float 
                            dev_value, policy_is_probs ? 1 : 0);
         return launch_status();
     }
-    hipLaunchKernelGGL(k_expand, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_policy, dev_value,
+    if (reuse_of(eng)) {
+        hipLaunchKernelGGL(k_expand<true>, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_policy, dev_value,
+                           policy_is_probs ? 1 : 0);
+        return launch_status();
+    }
+    hipLaunchKernelGGL(k_expand<false>, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_policy, dev_value,
                        policy_is_probs ? 1 : 0);
     return launch_status();
 }
@@ -1928,7 +2167,11 @@ int xq_engine_expand_legal(const xq_engine *eng, const float *dev_legal_logits, 
                            dev_value, 2);
         return launch_status();
     }
-    hipLaunchKernelGGL(k_expand, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_legal_logits, dev_value, 2);
+    if (reuse_of(eng)) {
+        hipLaunchKernelGGL(k_expand<true>, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_legal_logits, dev_value, 2);
+        return launch_status();
+    }
+    hipLaunchKernelGGL(k_expand<false>, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_legal_logits, dev_value, 2);
     return launch_status();
 }
 
@@ -1995,6 +2238,7 @@ int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *
     host_out->rows_evaluated = h[ST_ROWS];
     host_out->reserved[XQ_STAT_COLLISIONS] = h[ST_COLL]; host_out->reserved[XQ_STAT_LEAVES_SUM] = h[ST_LPS];
     host_out->reserved[XQ_STAT_LEAF_STEPS] = h[ST_LSTEPS];
+    host_out->reserved[XQ_STAT_REUSED_VISITS] = h[ST_REUSED]; host_out->reserved[XQ_STAT_REROOTS] = h[ST_REROOTS];
     return h[ST_OVF] ? XQ_ERR_OVERFLOW : XQ_OK;
 }
 

@@ -35,6 +35,12 @@ of S.  Every request buffer then has G K rows, slot-major (row slot K + j is pen
 `req_counts`, the packed buffers and the evaluator's outputs.  Dense, sparse and packed protocols, eager and replayed, work
 as with K = 1.  K > 1 is knowingly not the reference's sequential search; it cannot be combined with the evaluation cache
 or with arena games (manual_moves = 2).  K = 1 is the engine as before.
+
+With `tree_reuse=True` (opt-in; xq_engine_init_ex, XQ_ENGINE_TREE_REUSE) a slot keeps the chosen child's subtree when a move
+ends: the next search starts from it with its visits, stops at S visits as always and so costs S minus
+the reused visits in new simulations.  `stats()` adds `reused_visits` and `reroots`.  A weight update of the evaluator
+(`weights_version`) or another evaluator drops the pending re-roots before the next step (`drop_reroots`).  Self-play only
+(manual_moves = 0), K = 1 and S <= 1600; it combines with the evaluation cache.
 """
 from __future__ import annotations
 
@@ -86,10 +92,18 @@ def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
 
 class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
-                 inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1):
+                 inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
+                 tree_reuse: bool = False):
         K = int(leaves_per_step)
         if not 1 <= K <= 64:
             raise hip.XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
+        tree_reuse = bool(tree_reuse)
+        if tree_reuse and int(cfg.manual_moves) != 0:
+            raise hip.XqError("tree_reuse is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
+        if tree_reuse and K > 1:
+            raise hip.XqError("tree_reuse cannot be combined with leaves_per_step > 1")
+        if tree_reuse and int(cfg.num_simulations) > hip.REUSE_MAX_SIMS:
+            raise hip.XqError(f"tree_reuse supports num_simulations <= {hip.REUSE_MAX_SIMS}, got {cfg.num_simulations}")
         if K > 1 and eval_cache_entries:
             raise hip.XqError("leaves_per_step > 1 cannot be combined with an evaluation cache (eval_cache_entries > 0)")
         if K > 1 and int(cfg.manual_moves) == 2:
@@ -101,10 +115,15 @@ class SelfPlayEngine:
         self.cfg = cfg
         self.G = cfg.n_games
         self.K = K
+        self.tree_reuse = tree_reuse
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
-        nbytes = (self.lib.xq_engine_workspace_bytes(C.byref(cfg)) if K == 1 else
-                  self.lib.xq_engine_workspace_bytes_leaves(C.byref(cfg), K))
+        flags = hip.ENGINE_TREE_REUSE if tree_reuse else 0
+        if tree_reuse:
+            nbytes = self.lib.xq_engine_workspace_bytes_ex(C.byref(cfg), K, flags)
+        else:
+            nbytes = (self.lib.xq_engine_workspace_bytes(C.byref(cfg)) if K == 1 else
+                      self.lib.xq_engine_workspace_bytes_leaves(C.byref(cfg), K))
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
@@ -120,7 +139,10 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            if K == 1:
+            if tree_reuse:
+                hip.check(self.lib.xq_engine_init_ex(C.byref(self.h), C.byref(cfg), K, flags, base, self.workspace_bytes, inj_ptr,
+                                                     hip.stream_ptr(self.device)), "xq_engine_init_ex")
+            elif K == 1:
                 hip.check(self.lib.xq_engine_init(C.byref(self.h), C.byref(cfg), base, self.workspace_bytes, inj_ptr,
                                                   hip.stream_ptr(self.device)), "xq_engine_init")
             else:
@@ -155,6 +177,7 @@ class SelfPlayEngine:
         self.cache = None
         if eval_cache_entries:
             self._init_cache(int(eval_cache_entries))
+        self._reuse_seen = (self.evaluator, getattr(self.evaluator, "weights_version", 0))
         self.steps = 0
         self._graph = None
         self._graph_generation = 0
@@ -187,6 +210,19 @@ class SelfPlayEngine:
         if seen[0] is not self._cache_seen[0] or seen[1] != self._cache_seen[1]:
             hip.check(self.lib.xq_evcache_invalidate(C.byref(self.cache), hip.stream_ptr(self.device)), "xq_evcache_invalidate")
             self._cache_seen = seen
+
+    def drop_reroots(self):
+        """Tree reuse: no slot keeps its tree at the end of the move it is searching now (xq_engine_drop_reroots, one
+        device-side word per slot; asynchronous).  For trees grown partly under weights that have since changed."""
+        hip.check(self.lib.xq_engine_drop_reroots(C.byref(self.h), hip.stream_ptr(self.device)), "xq_engine_drop_reroots")
+
+    def _sync_reuse(self):
+        """Drop the pending re-roots (outside any recorded graph) when the evaluator or its weights changed since the engine
+        last saw them: a kept subtree would carry the old network's priors and values into the next search."""
+        seen = (self.evaluator, getattr(self.evaluator, "weights_version", 0))
+        if seen[0] is not self._reuse_seen[0] or seen[1] != self._reuse_seen[1]:
+            self.drop_reroots()
+            self._reuse_seen = seen
 
     # ---- the three stages of a step --------------------------------------------------------------------
     def select(self):
@@ -284,6 +320,8 @@ class SelfPlayEngine:
             self.release_graph()                       # the evaluator reallocated a buffer: the recording holds stale pointers
         if self.cache is not None:
             self._sync_cache()
+        if self.tree_reuse:
+            self._sync_reuse()
         if self._graph is not None:
             self._graph.replay()
         else:
@@ -302,6 +340,8 @@ class SelfPlayEngine:
             raise hip.XqError("capture_step needs an evaluator")
         if self.cache is not None:
             self._sync_cache()
+        if self.tree_reuse:
+            self._sync_reuse()
         for _ in range(warmup):
             self._one_step()
             self.steps += 1
@@ -393,7 +433,7 @@ class SelfPlayEngine:
 
     def slot_counters(self) -> torch.Tensor:
         """Zero-copy int64 [G, 32] view of the per-slot counters that xq_engine_stats_read sums (column 19: collisions, 20:
-        pending leaves handed out, 21: slot-steps that handed leaves).  For tests."""
+        pending leaves handed out, 21: slot-steps that handed leaves, 22: reused visits, 23: re-rooted searches).  For tests."""
         off = int(self.h.p[17]) - int(self.ws.data_ptr())
         return self.ws[off:off + self.G * 32 * 8].view(torch.int64).view(self.G, 32)
 

@@ -20,6 +20,8 @@ SAMPLE_BYTES = 640
 RESULT_BYTES = 16
 ACTION_SPACE = 8100
 STATE_FLOATS = 1350
+ENGINE_TREE_REUSE = 1          # XQ_ENGINE_TREE_REUSE
+REUSE_MAX_SIMS = 1600          # XQ_REUSE_MAX_SIMS
 
 
 class XqError(RuntimeError):
@@ -57,7 +59,7 @@ class EngineStats(C.Structure):
                 ("sims", "terminal_sims", "leaf_evals", "root_evals", "moves_played", "games_finished", "red_wins",
                  "black_wins", "draws", "plies_finished", "nodes_created", "depth_sum", "children_scanned", "resigns",
                  "samples_written", "samples_dropped", "overflow", "games_started", "rows_evaluated", "collisions",
-                 "leaves_per_step_sum", "leaf_steps")] + [("reserved", C.c_uint64 * 10)]
+                 "leaves_per_step_sum", "leaf_steps", "reused_visits", "reroots")] + [("reserved", C.c_uint64 * 8)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
@@ -109,6 +111,10 @@ def lib():
     L.xq_engine_workspace_bytes_leaves.argtypes = [C.POINTER(EngineConfig), i32]
     L.xq_engine_workspace_bytes_leaves.restype = C.c_size_t
     L.xq_engine_init_leaves.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, vp, C.c_size_t, vp, vp]
+    L.xq_engine_workspace_bytes_ex.argtypes = [C.POINTER(EngineConfig), i32, C.c_uint]
+    L.xq_engine_workspace_bytes_ex.restype = C.c_size_t
+    L.xq_engine_init_ex.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, C.c_uint, vp, C.c_size_t, vp, vp]
+    L.xq_engine_drop_reroots.argtypes = [C.POINTER(Engine), vp]
     L.xq_engine_select.argtypes = [C.POINTER(Engine), vp, vp]
     L.xq_engine_expand.argtypes = [C.POINTER(Engine), vp, vp, i32, vp]
     L.xq_engine_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(EngineStats), vp]
@@ -181,7 +187,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_bn_sync_sums_count", "xq_bn_sync_forward_stats", "xq_bn_sync_forward_apply", "xq_bn_sync_backward_stats",
            "xq_bn_sync_backward_apply", "xq_evcache_bytes", "xq_evcache_init", "xq_evcache_hit_flags", "xq_evcache_probe",
            "xq_engine_compact_misses", "xq_evcache_commit", "xq_evcache_invalidate", "xq_evcache_stats_read",
-           "xq_evcache_key_host", "xq_engine_workspace_bytes_leaves", "xq_engine_init_leaves"]
+           "xq_evcache_key_host", "xq_engine_workspace_bytes_leaves", "xq_engine_init_leaves", "xq_engine_workspace_bytes_ex",
+           "xq_engine_init_ex", "xq_engine_drop_reroots"]
 
 
 def check(rc: int, what: str):
