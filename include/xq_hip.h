@@ -154,7 +154,8 @@ typedef struct xq_engine_stats {
     uint64_t games_started;
     uint64_t rows_evaluated;  /* sum over xq_engine_compact calls of n_live: rows the evaluator ran on in packed steps */
     uint64_t reserved[13];    /* [XQ_STAT_COLLISIONS], [XQ_STAT_LEAVES_SUM], [XQ_STAT_LEAF_STEPS]: the leaf-batching counters below;
-                                 [XQ_STAT_REUSED_VISITS], [XQ_STAT_REROOTS]: the tree-reuse counters (xq_engine_init_ex) */
+                                 [XQ_STAT_REUSED_VISITS], [XQ_STAT_REROOTS]: the tree-reuse counters (xq_engine_init_ex);
+                                 [XQ_STAT_FAST_MOVES], [XQ_STAT_FAST_SIMS]: the playout-cap counters (xq_engine_init_cap) */
 
 } xq_engine_stats;
 /* Leaf-batching counters (xq_engine_init_leaves), kept in the reserved words so the struct's layout is unchanged:
@@ -234,6 +235,40 @@ int xq_engine_init_ex(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       size_t ws_bytes, const uint64_t *dev_inject, void *stream);
 /* No slot of a tree-reuse engine re-roots at the end of the move it is searching now (XQ_ERR_ARG without the flag). */
 int xq_engine_drop_reroots(const xq_engine *eng, void *stream);
+
+/* Playout cap randomization (opt-in; cap == NULL is xq_engine_init_ex exactly, and xq_engine_init_ex is that call).  Outside the
+ * reference-parity contract, like leaf batching and tree reuse: the reference searches every move at one size.
+ *   fast_simulations = S_fast, 1 <= S_fast < num_simulations;  full_search_prob = p, 0 < p <= 1 (NaN refused);  reserved = 0.
+ * The draw: for every position of a self-play game that will be searched (its root request is issued with status 0: neither
+ * game over nor adjudicated at max_game_length) xq_engine_select takes ONE uniform draw u from the slot's existing uniform
+ * stream (the stream of the move-choice draw; injected runs: stream 3 of dev_inject, whose layout is unchanged) when it issues
+ * that root request; the move is FULL iff u < p.  Per searched position that stream so yields the cap draw first and the
+ * move-choice draw at the move's end (size inject_len for two draws per position); a position whose root evaluation ends the
+ * game by resignation has taken its cap draw and no move-choice draw.
+ *   FULL move: exactly the move of an engine without the cap: Dirichlet noise at the root, budget num_simulations, a sample is
+ *              staged, n_samples grows.
+ *   FAST move: no root noise and no Dirichlet draws taken (the root is a root with add_noise = 0), budget S_fast, NO sample
+ *              staged, n_samples unchanged.  The move choice is unchanged (temperature 1 before temperature_threshold,
+ *              late_temperature after, one uniform draw).
+ * Everything keyed on the sample count keeps that key: the resign rule starts after 10 RECORDED samples (with p = 0.25 about four
+ * times later in plies: intended, not tuned), xq_game_result.n_samples is the recorded count, z is written to recorded samples
+ * only; a game may record no sample at all.  Random opening moves, terminal handling, the resign probe, adjudication: unchanged.
+ * With XQ_ENGINE_TREE_REUSE the hand-off happens at the end of full and fast moves alike and the budget stays visits: a search
+ * starts at sims_done = reused visits and ends when sims_done >= THIS move's budget, so a fast search that inherits >= S_fast
+ * visits runs no new simulation and its root may hold more than S_fast visits (it is not sampled); a full search still ends with
+ * exactly num_simulations visits.  A reused root of a fast move gets its float32 priors from the new evaluation, keeps the prior
+ * kind it had as an inner node and uses no float64 root priors.  The evaluation cache combines with the cap unchanged.
+ * XQ_ERR_ARG before any launch (xq_engine_workspace_bytes_cap: 0): manual_moves 1 or 2, leaves_per_step > 1, parameters out of
+ * range, reserved != 0, and whatever xq_engine_init_ex refuses.  No workspace is added; the parameters live in free per-slot
+ * state words, "cap on" in the handle (pad0, above the public flag bits).  Counters, 0 without the cap:
+ *   reserved[XQ_STAT_FAST_MOVES]  moves played after a fast search
+ *   reserved[XQ_STAT_FAST_SIMS]   new simulations run by fast searches (`sims` keeps counting all new simulations) */
+typedef struct xq_playout_cap { int32_t fast_simulations; int32_t reserved; double full_search_prob; } xq_playout_cap;
+#define XQ_STAT_FAST_MOVES 5
+#define XQ_STAT_FAST_SIMS 6
+size_t xq_engine_workspace_bytes_cap(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap);
+int xq_engine_init_cap(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags,
+                       const xq_playout_cap *cap, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream);
 
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 

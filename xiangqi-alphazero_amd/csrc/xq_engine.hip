@@ -38,11 +38,14 @@ enum Phase : int { PH_NEWGAME = 0, PH_NEWPOS = 1, PH_WAIT_ROOT = 2, PH_SEARCH = 
 
 enum Gi : int { GI_SIDE = 0, GI_MC, GI_NOCAP, GI_PHASE, GI_SIMS, GI_NSAMP, GI_GSEQ, GI_ALLOC, GI_PLEAF, GI_PDEPTH,
                 GI_PCOUNT, GI_RSTATUS, GI_RWINNER, GI_RESIGN_N, GI_RNG0, GI_RNG1, GI_RNG2, GI_RNG3, GI_FWINNER,
-                GI_FREASON, GI_MANNOISE, GI_DELAY, GI_NPEND, GI_RR_NODE, GI_RR_MARK, GI_RR_DROP, GI_N = 32 };
+                GI_FREASON, GI_MANNOISE, GI_DELAY, GI_NPEND, GI_RR_NODE, GI_RR_MARK, GI_RR_DROP,
+                // playout cap (xq_engine_init_cap): this move's kind (1 full, 0 fast) and budget, written by k_select<.., true> at
+                // PH_NEWPOS; S_fast and the two halves of the float64 threshold p, written once by k_init_cap
+                GI_CAP_FULL, GI_CAP_BUDGET, GI_CAP_SFAST, GI_CAP_PLO, GI_CAP_PHI, GI_N = 32 };
 
 enum St : int { ST_SIMS = 0, ST_TERM, ST_LEAF, ST_ROOT, ST_MOVES, ST_GAMES, ST_RED, ST_BLACK, ST_DRAW, ST_PLIES, ST_NODES,
                 ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_COLL, ST_LPS, ST_LSTEPS, ST_REUSED,
-                ST_REROOTS, ST_N = 32 };
+                ST_REROOTS, ST_FASTM, ST_FASTS, ST_N = 32 };
 
 enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_TW, P_TP, P_TA, P_TC, P_TM, P_ROOTP,
                  P_STAGE, P_OUTS, P_OUTR, P_CNT, P_STATS, P_INJECT, P_SQRT, P_MNOISE, P_STATSUM, P_REQ,
@@ -256,7 +259,11 @@ constexpr int WAVES_PER_WG = 4;
 #endif
 // REUSE (tree reuse): at the end of a move the chosen child and the old allocation mark are handed to k_reroot and
 // k_expand<true> of the same step (GI_RR_NODE / GI_RR_MARK); k_select<false> is k_select as it always was.
-template <bool REUSE>
+// CAP (playout cap randomization, xq_engine_init_cap): every searched position takes one draw of the slot's uniform stream when
+// its root request is issued; u < p makes the move FULL (today's move), otherwise FAST: budget S_fast, no root noise
+// (k_expand), no sample.  The kind and the budget live in GI_CAP_FULL / GI_CAP_BUDGET from the root request to the move's end.
+// k_select<.., false> is k_select as it always was.
+template <bool REUSE, bool CAP = false>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev E, float *__restrict__ nn_in) {
     __shared__ SelectLds Ls[WAVES_PER_WG];
     SelectLds &L = Ls[threadIdx.x >> 6];
@@ -299,6 +306,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
     // per-lane stat deltas are kept wave-uniform and written by lane 0 at the end
     unsigned long long d_sims = 0, d_term = 0, d_moves = 0, d_depth = 0, d_scan = 0;
     int term_run = 0;
+    // CAP: the kind and budget of the move being searched.  A launch never searches a move whose root request it issued
+    // itself (PH_NEWPOS ends the launch), so the words read here hold for the whole launch.
+    const bool full_move = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_FULL]) != 0 : true;
+    const int budget = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_BUDGET]) : S;
+    unsigned long long d_fast_moves = 0, d_fast_sims = 0;
 
     lds_copy_dwords(L.root, g_board, XQ_BS / 4);
     lds_copy_dwords(L.rhist, g_hist, XQ_HIST * XQ_BS / 4);
@@ -403,13 +415,26 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                 tN[0] = 0; tW[0] = 0.0; tC[0] = -1; tM[0] = 0; tA[0] = 0; tP[0] = 0.0f;
             }
             if (REUSE && lane == 0) gi[GI_RR_DROP] = 0;      // this move's tree is grown under the current weights
+            if (CAP) {
+                // the cap draw: one uniform per position that will be searched, ahead of that move's move-choice draw
+                bool full = true;
+                if (status == 0) {
+                    const double u = u64_to_unit(draw_u64(E, slot, RNG_UNIFORM, rng_ctr[RNG_UNIFORM], st));
+                    rng_ctr[RNG_UNIFORM] += 1;
+                    const unsigned long long pb = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(gi[GI_CAP_PHI]) << 32) |
+                                                  (unsigned)__builtin_amdgcn_readfirstlane(gi[GI_CAP_PLO]);
+                    full = u < __longlong_as_double((long long)pb);
+                }
+                const int sfast = __builtin_amdgcn_readfirstlane(gi[GI_CAP_SFAST]);
+                if (lane == 0) { gi[GI_CAP_FULL] = full ? 1 : 0; gi[GI_CAP_BUDGET] = full ? S : sfast; }
+            }
             sims_done = 0;
             req_cnt = cnt;
             phase = PH_WAIT_ROOT;
             break;
         }
         // ---- phase == PH_SEARCH
-        if (sims_done >= S) {
+        if (sims_done >= budget) {
             if (manual) { phase = PH_HOLD; break; }
             const int nch = __builtin_amdgcn_readfirstlane((int)(tM[0] & 0x3FFF));
             const int first = __builtin_amdgcn_readfirstlane(tC[0]);
@@ -437,19 +462,23 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
             const bool late = g_mc >= E.cfg.temperature_threshold;
             const double inv_t = 1.0 / E.cfg.late_temperature;
             uint8_t *rec = E.stage + ((size_t)slot * E.stage_cap + (n_samples < E.stage_cap ? n_samples : E.stage_cap - 1)) * XQ_SAMPLE_BYTES;
-            if (n_samples >= E.stage_cap) ovf |= 4;
-            for (int i = lane; i < XQ_SAMPLE_BYTES / 4; i += 64) ((uint32_t *)rec)[i] = 0u;
-            wave_sync_mem();
-            for (int i = lane; i < 90; i += 64) rec[i] = (uint8_t)L.root[i];
-            if (lane == 0) {
-                xq_sample *s = (xq_sample *)rec;
-                s->side = (int8_t)g_side; s->z = 0; s->n_moves = (uint8_t)nch; s->late_temp = late ? 1 : 0;
-                s->ply = (uint16_t)g_mc; s->slot = (uint32_t)slot; s->game_seq = (uint32_t)game_seq;
+            if (full_move) {                                  // a fast move stages no sample
+                if (n_samples >= E.stage_cap) ovf |= 4;
+                for (int i = lane; i < XQ_SAMPLE_BYTES / 4; i += 64) ((uint32_t *)rec)[i] = 0u;
+                wave_sync_mem();
+                for (int i = lane; i < 90; i += 64) rec[i] = (uint8_t)L.root[i];
+                if (lane == 0) {
+                    xq_sample *s = (xq_sample *)rec;
+                    s->side = (int8_t)g_side; s->z = 0; s->n_moves = (uint8_t)nch; s->late_temp = late ? 1 : 0;
+                    s->ply = (uint16_t)g_mc; s->slot = (uint32_t)slot; s->game_seq = (uint32_t)game_seq;
+                }
             }
             for (int i = lane; i < nch; i += 64) {
                 const int a = tA[first + i], n = tN[first + i];
-                ((xq_sample *)rec)->actions[i] = (uint16_t)a;
-                ((xq_sample *)rec)->visits[i] = (uint16_t)(n > 65535 ? 65535 : n);
+                if (full_move) {
+                    ((xq_sample *)rec)->actions[i] = (uint16_t)a;
+                    ((xq_sample *)rec)->visits[i] = (uint16_t)(n > 65535 ? 65535 : n);
+                }
                 L.a_tmp[i] = (uint16_t)a;
                 L.w_tmp[i] = late ? (n > 0 ? pow((double)n, inv_t) : 0.0) : (double)n;
             }
@@ -496,7 +525,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                 if (lane == 0) { gi[GI_RR_NODE] = keep ? c : 0; gi[GI_RR_MARK] = keep ? gi[GI_ALLOC] : 0; }
             }
             wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
-            n_samples += 1;
+            if (full_move) n_samples += 1; else d_fast_moves += 1;
             d_moves += 1;
             state_dirty = true;
             phase = PH_NEWPOS;
@@ -593,6 +622,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
             wave_backup(tN, tW, path, depth, winner == 0 ? 0.0 : 1.0);   // mcts.py:137-140
             wave_sync_mem();   // the next descent reads N/W written here by other lanes
             sims_done += 1; d_sims += 1; d_term += 1;
+            if (CAP && !full_move) d_fast_sims += 1;
             // A root with a mating reply re-tests that terminal child on every visit (as mcts.py does); bound how
             // many such simulations one launch runs so a single slot cannot stretch the step (it resumes next step
             // and hands the evaluator no position this time).
@@ -617,6 +647,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
         gi[GI_NSAMP] = n_samples; gi[GI_GSEQ] = game_seq;
         gi[GI_RNG0] = rng_ctr[0]; gi[GI_RNG1] = rng_ctr[1]; gi[GI_RNG2] = rng_ctr[2]; gi[GI_RNG3] = rng_ctr[3];
         st[ST_SIMS] += d_sims; st[ST_TERM] += d_term; st[ST_MOVES] += d_moves; st[ST_DEPTH] += d_depth; st[ST_SCAN] += d_scan;
+        if (CAP) { st[ST_FASTM] += d_fast_moves; st[ST_FASTS] += d_fast_sims; }
         if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8;
     }
 }
@@ -633,7 +664,9 @@ struct ExpandLds {
 // REUSE (k_expand<true>): a root request of a slot that k_select<true> handed a chosen child to (GI_RR_NODE; k_reroot has moved
 // that child's subtree to the front of the arena) keeps the children, their N, W, first-child and meta words, rewrites their
 // float32 priors, draws fresh noise into rootP and starts the search at sims_done = root N = the sum of their visits.
-template <bool REUSE>
+// CAP (k_expand<.., true>): the root of a fast move (GI_CAP_FULL == 0) takes the no-noise path: no Dirichlet draw, rootP unused,
+// prior kind 0 (or 2), also when it is a reused root; a leaf backed up under a fast move counts in ST_FASTS.
+template <bool REUSE, bool CAP = false>
 __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ policy, const float *__restrict__ value,
                                                int is_probs) {
     __shared__ ExpandLds L;
@@ -738,7 +771,8 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
     float sum = 0.0f;
     for (int i = 0; i < cnt; ++i) sum = sum + L.p[i];      // builtin sum(): sequential float32, move order
 
-    const bool noisy = is_root && (E.cfg.add_noise != 0 || gi[GI_MANNOISE] != 0);
+    const bool full_move = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_FULL]) != 0 : true;
+    const bool noisy = is_root && full_move && (E.cfg.add_noise != 0 || gi[GI_MANNOISE] != 0);
     if (noisy) {
         // eta ~ Dirichlet(alpha) over the legal moves, in move order
         if (gi[GI_MANNOISE] != 0) {
@@ -843,6 +877,7 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
         gi[GI_SIMS] = sims_done;
         gi[GI_PHASE] = (manual && sims_done >= E.cfg.num_simulations) ? PH_HOLD : PH_SEARCH;
         st[ST_SIMS] += 1;
+        if (CAP && !full_move) st[ST_FASTS] += 1;
         if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8;
     }
 }
@@ -1583,6 +1618,17 @@ __global__ void k_init(Dev E) {
     if (slot == 0) { E.cnt[0] = 0; E.cnt[1] = 0; *E.started = 0; }
 }
 
+// xq_engine_init_cap: the playout cap's parameters, after k_init, in free state words of every slot (the handle and the config
+// struct are full): S_fast and the float64 threshold p as two words.  The kernels read them with their other scalar loads.
+__global__ void k_init_cap(Dev E, int fast_simulations, double full_search_prob) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= E.cfg.n_games) return;
+    int32_t *gi = E.gi + (size_t)slot * GI_N;
+    const unsigned long long pb = (unsigned long long)__double_as_longlong(full_search_prob);
+    gi[GI_CAP_FULL] = 1; gi[GI_CAP_BUDGET] = E.cfg.num_simulations;
+    gi[GI_CAP_SFAST] = fast_simulations; gi[GI_CAP_PLO] = (int32_t)(uint32_t)pb; gi[GI_CAP_PHI] = (int32_t)(uint32_t)(pb >> 32);
+}
+
 // Column sums of the per-slot counters [G][ST_N] (OR for the overflow word): each 256-thread block sweeps slot rows
 // (8 rows x 32 columns per pass, 256 contiguous bytes per row), folds its eight partial rows through LDS and adds the
 // result to the zeroed output with one atomic per column.
@@ -2025,9 +2071,37 @@ bool flags_ok(const xq_engine_config *c, int K, unsigned flags) {
     return c->manual_moves == 0 && K == 1 && c->num_simulations <= XQ_REUSE_MAX_SIMS;
 }
 
-// pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them
+// playout cap: self-play only, one leaf per step, 1 <= S_fast < S, 0 < p <= 1 (a NaN fails both comparisons)
+bool cap_ok(const xq_engine_config *c, int K, const xq_playout_cap *cap) {
+    return c->manual_moves == 0 && K == 1 && cap->reserved == 0 && cap->fast_simulations >= 1 &&
+           cap->fast_simulations < c->num_simulations && cap->full_search_prob > 0.0 && cap->full_search_prob <= 1.0;
+}
+
+// pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
+// flag bits "playout cap on" (xq_engine_init_cap)
+constexpr int PAD0_CAP = 1 << 30;
 int leaves_of(const xq_engine *e) { return (e->pad0 & 0xFFFF) > 1 ? (e->pad0 & 0xFFFF) : 1; }
 bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE_TREE_REUSE; }
+bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
+
+// the K = 1 step's two kernels, by the engine's options
+void launch_select(const xq_engine *eng, const Dev &d, float *nn_in, hipStream_t s) {
+    const dim3 grid((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), block(64 * WAVES_PER_WG);
+    const bool reuse = reuse_of(eng), cap = cap_of(eng);
+    if (reuse && cap) hipLaunchKernelGGL((k_select<true, true>), grid, block, 0, s, d, nn_in);
+    else if (reuse) hipLaunchKernelGGL((k_select<true, false>), grid, block, 0, s, d, nn_in);
+    else if (cap) hipLaunchKernelGGL((k_select<false, true>), grid, block, 0, s, d, nn_in);
+    else hipLaunchKernelGGL((k_select<false, false>), grid, block, 0, s, d, nn_in);
+}
+
+void launch_expand(const xq_engine *eng, const Dev &d, const float *policy, const float *value, int is_probs, hipStream_t s) {
+    const dim3 grid(eng->cfg.n_games), block(64);
+    const bool reuse = reuse_of(eng), cap = cap_of(eng);
+    if (reuse && cap) hipLaunchKernelGGL((k_expand<true, true>), grid, block, 0, s, d, policy, value, is_probs);
+    else if (reuse) hipLaunchKernelGGL((k_expand<true, false>), grid, block, 0, s, d, policy, value, is_probs);
+    else if (cap) hipLaunchKernelGGL((k_expand<false, true>), grid, block, 0, s, d, policy, value, is_probs);
+    else hipLaunchKernelGGL((k_expand<false, false>), grid, block, 0, s, d, policy, value, is_probs);
+}
 
 Mx make_mx(const xq_engine *e) {
     Mx x;
@@ -2051,8 +2125,13 @@ size_t xq_engine_workspace_bytes_leaves(const xq_engine_config *cfg, int leaves_
 }
 
 size_t xq_engine_workspace_bytes_ex(const xq_engine_config *cfg, int leaves_per_step, unsigned flags) {
+    return xq_engine_workspace_bytes_cap(cfg, leaves_per_step, flags, nullptr);
+}
+
+size_t xq_engine_workspace_bytes_cap(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap) {
     if (!config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags)) return 0;
-    return make_layout(cfg, leaves_per_step).total;   // tree reuse needs no workspace of its own
+    if (cap && !cap_ok(cfg, leaves_per_step, cap)) return 0;
+    return make_layout(cfg, leaves_per_step).total;   // neither tree reuse nor the playout cap needs workspace of its own
 }
 
 int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t ws_bytes, const uint64_t *dev_inject,
@@ -2067,9 +2146,15 @@ int xq_engine_init_leaves(xq_engine *eng, const xq_engine_config *cfg, int leave
 
 int xq_engine_init_ex(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, void *ws,
                       size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
+    return xq_engine_init_cap(eng, cfg, leaves_per_step, flags, nullptr, ws, ws_bytes, dev_inject, stream);
+}
+
+int xq_engine_init_cap(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                       void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
     if (!eng || !config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags) || !ws ||
         ((uintptr_t)ws & 255))
         return XQ_ERR_ARG;
+    if (cap && !cap_ok(cfg, leaves_per_step, cap)) return XQ_ERR_ARG;
     if (cfg->inject_len > 0 && !dev_inject) return XQ_ERR_ARG;
     const int K = leaves_per_step;
     const Layout l = make_layout(cfg, K);
@@ -2077,7 +2162,7 @@ int xq_engine_init_ex(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
     memset(eng, 0, sizeof(*eng));
     eng->cfg = *cfg;
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
-    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16);
+    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16) | (cap ? PAD0_CAP : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -2102,6 +2187,12 @@ int xq_engine_init_ex(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
     }
     const Dev d = make_dev(eng);
     hipLaunchKernelGGL(k_init, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d);
+    if (cap) {
+        const int rc = launch_status();
+        if (rc != XQ_OK) return rc;
+        hipLaunchKernelGGL(k_init_cap, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d, (int)cap->fast_simulations,
+                           cap->full_search_prob);
+    }
     return launch_status();
 }
 
@@ -2112,18 +2203,14 @@ int xq_engine_select(const xq_engine *eng, float *dev_nn_input, void *stream) {
         hipLaunchKernelGGL(k_select_multi, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, make_mx(eng), dev_nn_input);
         return launch_status();
     }
+    launch_select(eng, d, dev_nn_input, (hipStream_t)stream);
     if (reuse_of(eng)) {
         // the re-root runs here, between k_select<true> and the expansion, so every step variant (full, packed, cached) has it
-        hipLaunchKernelGGL(k_select<true>, dim3((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), dim3(64 * WAVES_PER_WG), 0,
-                           (hipStream_t)stream, d, dev_nn_input);
         const int rc = launch_status();
         if (rc != XQ_OK) return rc;
         hipLaunchKernelGGL(k_reroot, dim3(eng->cfg.n_games), dim3(RR_THREADS),
                            (unsigned)reroot_lds_bytes(eng->node_cap, eng->cfg.num_simulations), (hipStream_t)stream, d);
-        return launch_status();
     }
-    hipLaunchKernelGGL(k_select<false>, dim3((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), dim3(64 * WAVES_PER_WG), 0,
-                       (hipStream_t)stream, d, dev_nn_input);
     return launch_status();
 }
 
@@ -2142,13 +2229,7 @@ int xq_engine_expand(const xq_engine *eng, const float *dev_policy, const float 
                            dev_value, policy_is_probs ? 1 : 0);
         return launch_status();
     }
-    if (reuse_of(eng)) {
-        hipLaunchKernelGGL(k_expand<true>, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_policy, dev_value,
-                           policy_is_probs ? 1 : 0);
-        return launch_status();
-    }
-    hipLaunchKernelGGL(k_expand<false>, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_policy, dev_value,
-                       policy_is_probs ? 1 : 0);
+    launch_expand(eng, d, dev_policy, dev_value, policy_is_probs ? 1 : 0, (hipStream_t)stream);
     return launch_status();
 }
 
@@ -2167,11 +2248,7 @@ int xq_engine_expand_legal(const xq_engine *eng, const float *dev_legal_logits, 
                            dev_value, 2);
         return launch_status();
     }
-    if (reuse_of(eng)) {
-        hipLaunchKernelGGL(k_expand<true>, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_legal_logits, dev_value, 2);
-        return launch_status();
-    }
-    hipLaunchKernelGGL(k_expand<false>, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, dev_legal_logits, dev_value, 2);
+    launch_expand(eng, d, dev_legal_logits, dev_value, 2, (hipStream_t)stream);
     return launch_status();
 }
 
@@ -2239,6 +2316,7 @@ int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *
     host_out->reserved[XQ_STAT_COLLISIONS] = h[ST_COLL]; host_out->reserved[XQ_STAT_LEAVES_SUM] = h[ST_LPS];
     host_out->reserved[XQ_STAT_LEAF_STEPS] = h[ST_LSTEPS];
     host_out->reserved[XQ_STAT_REUSED_VISITS] = h[ST_REUSED]; host_out->reserved[XQ_STAT_REROOTS] = h[ST_REROOTS];
+    host_out->reserved[XQ_STAT_FAST_MOVES] = h[ST_FASTM]; host_out->reserved[XQ_STAT_FAST_SIMS] = h[ST_FASTS];
     return h[ST_OVF] ? XQ_ERR_OVERFLOW : XQ_OK;
 }
 

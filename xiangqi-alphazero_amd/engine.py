@@ -41,6 +41,11 @@ ends: the next search starts from it with its visits, st
 the reused visits in new simulations.  `stats()` adds `reused_visits` and `reroots`.  A weight update of the evaluator
 (`weights_version`) or another evaluator drops the pending re-roots before the next step (`drop_reroots`).  Self-play only
 (manual_moves = 0), K = 1 and S <= 1600; it combines with the evaluation cache.
+
+With `playout_cap=(full_search_prob, fast_simulations)` (opt-in; xq_engine_init_cap) every searched
+position takes one draw of the slot's uniform stream: with probability p the move is a full move (noise, S simulations, a
+sample), otherwise a fast one (no noise, `fast_simulations`, no sample).  `stats()` adds `fast_moves` and `fast_sims`.
+Self-play only, K = 1; it combines with tree reuse and the evaluation cache.
 """
 from __future__ import annotations
 
@@ -93,7 +98,7 @@ def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
 class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
-                 tree_reuse: bool = False):
+                 tree_reuse: bool = False, playout_cap=None):
         K = int(leaves_per_step)
         if not 1 <= K <= 64:
             raise hip.XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
@@ -104,6 +109,21 @@ class SelfPlayEngine:
             raise hip.XqError("tree_reuse cannot be combined with leaves_per_step > 1")
         if tree_reuse and int(cfg.num_simulations) > hip.REUSE_MAX_SIMS:
             raise hip.XqError(f"tree_reuse supports num_simulations <= {hip.REUSE_MAX_SIMS}, got {cfg.num_simulations}")
+        cap = None
+        if playout_cap is not None:
+            try:
+                p_full, s_fast = float(playout_cap[0]), int(playout_cap[1])
+            except (TypeError, ValueError, IndexError):
+                raise hip.XqError("playout_cap must be (full_search_prob, fast_simulations)")
+            if int(cfg.manual_moves) != 0:
+                raise hip.XqError("playout_cap is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
+            if K > 1:
+                raise hip.XqError("playout_cap cannot be combined with leaves_per_step > 1")
+            if not 1 <= s_fast < int(cfg.num_simulations):
+                raise hip.XqError(f"playout_cap: fast_simulations must be in [1, num_simulations), got {s_fast}")
+            if not 0.0 < p_full <= 1.0:                    # a NaN fails both comparisons
+                raise hip.XqError(f"playout_cap: full_search_prob must be in (0, 1], got {p_full}")
+            cap = hip.PlayoutCap(s_fast, 0, p_full)
         if K > 1 and eval_cache_entries:
             raise hip.XqError("leaves_per_step > 1 cannot be combined with an evaluation cache (eval_cache_entries > 0)")
         if K > 1 and int(cfg.manual_moves) == 2:
@@ -116,10 +136,13 @@ class SelfPlayEngine:
         self.G = cfg.n_games
         self.K = K
         self.tree_reuse = tree_reuse
+        self.playout_cap = None if cap is None else (cap.full_search_prob, cap.fast_simulations)
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         flags = hip.ENGINE_TREE_REUSE if tree_reuse else 0
-        if tree_reuse:
+        if cap is not None:
+            nbytes = self.lib.xq_engine_workspace_bytes_cap(C.byref(cfg), K, flags, C.byref(cap))
+        elif tree_reuse:
             nbytes = self.lib.xq_engine_workspace_bytes_ex(C.byref(cfg), K, flags)
         else:
             nbytes = (self.lib.xq_engine_workspace_bytes(C.byref(cfg)) if K == 1 else
@@ -139,7 +162,11 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            if tree_reuse:
+            if cap is not None:
+                hip.check(self.lib.xq_engine_init_cap(C.byref(self.h), C.byref(cfg), K, flags, C.byref(cap), base,
+                                                      self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
+                          "xq_engine_init_cap")
+            elif tree_reuse:
                 hip.check(self.lib.xq_engine_init_ex(C.byref(self.h), C.byref(cfg), K, flags, base, self.workspace_bytes, inj_ptr,
                                                      hip.stream_ptr(self.device)), "xq_engine_init_ex")
             elif K == 1:
@@ -433,7 +460,8 @@ class SelfPlayEngine:
 
     def slot_counters(self) -> torch.Tensor:
         """Zero-copy int64 [G, 32] view of the per-slot counters that xq_engine_stats_read sums (column 19: collisions, 20:
-        pending leaves handed out, 21: slot-steps that handed leaves, 22: reused visits, 23: re-rooted searches).  For tests."""
+        pending leaves handed out, 21: slot-steps that handed leaves, 22: reused visits, 23: re-rooted searches, 24: fast moves,
+        25: simulations of fast searches).  For tests."""
         off = int(self.h.p[17]) - int(self.ws.data_ptr())
         return self.ws[off:off + self.G * 32 * 8].view(torch.int64).view(self.G, 32)
 
