@@ -155,7 +155,9 @@ typedef struct xq_engine_stats {
     uint64_t rows_evaluated;  /* sum over xq_engine_compact calls of n_live: rows the evaluator ran on in packed steps */
     uint64_t reserved[13];    /* [XQ_STAT_COLLISIONS], [XQ_STAT_LEAVES_SUM], [XQ_STAT_LEAF_STEPS]: the leaf-batching counters below;
                                  [XQ_STAT_REUSED_VISITS], [XQ_STAT_REROOTS]: the tree-reuse counters (xq_engine_init_ex);
-                                 [XQ_STAT_FAST_MOVES], [XQ_STAT_FAST_SIMS]: the playout-cap counters (xq_engine_init_cap) */
+                                 [XQ_STAT_FAST_MOVES], [XQ_STAT_FAST_SIMS]: the playout-cap counters (xq_engine_init_cap);
+                                 [XQ_STAT_FORCED_SIMS], [XQ_STAT_PRUNED_VISITS], [XQ_STAT_PRUNED_CHILDREN]: forced playouts
+                                 (xq_engine_init_fp) */
 
 } xq_engine_stats;
 /* Leaf-batching counters (xq_engine_init_leaves), kept in the reserved words so the struct's layout is unchanged:
@@ -269,6 +271,45 @@ typedef struct xq_playout_cap { int32_t fast_simulations; int32_t reserved; doub
 size_t xq_engine_workspace_bytes_cap(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap);
 int xq_engine_init_cap(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags,
                        const xq_playout_cap *cap, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream);
+
+/* Forced playouts and policy target pruning (opt-in; forced == NULL is xq_engine_init_cap exactly, and xq_engine_init_cap is
+ * that call).  The two rules the KataGo scheme pairs with the playout cap; outside the reference-parity contract like the cap.
+ * Parameter k, 0 < k <= 16 (KataGo: 2; NaN refused), reserved = 0.  k is rounded to float32 ONCE at init and kept as that float32
+ * in a per-slot state word; every use widens the float32 to double.
+ * WHERE: only at a root of prior kind 1, i.e. the noisy root of a full self-play move, which is always node 0 (a reused root of a
+ * full move becomes kind 1).  Not on fast moves of the cap (their roots carry no noise), not at inner nodes.
+ * FORCING, in the descent at node 0.  Nr = the root's visit count as used for sqrt_tab[Nr].  Child i is FORCED iff
+ *     N_i > 0  and  (double)N_i * (double)N_i < f_i,   f_i = (k * rootP[i]) * (double)Nr   (two float64 products, that order),
+ * with rootP the float64 noisy root priors.  A forced child scores +infinity; the first-maximum rule then picks the forced child
+ * of lowest index.  Everything else in the descent is unchanged.  A simulation whose root choice was a forced child counts in
+ * reserved[XQ_STAT_FORCED_SIMS].
+ * PRUNING, at the end of a full move, before the sample is staged and before the move-choice weights are formed.  Nr = the root's
+ * visits (the move's budget S), c* = the first maximum of the children's N,
+ *     PUCT(i, n) = q_i + ((c_puct * rootP[i]) * sqrt_tab[Nr]) / (double)(1 + n),   q_i = W_i / N_i held constant
+ * (the kind-1 float64 arithmetic of the descent), P* = PUCT(c*, N_c*).  For every other child with N_i > 0: n = N_i, d = 0;
+ * while n > 1 and (d+1)*(d+1) < f_i and PUCT(i, n-1) < P*: n -= 1, d += 1.  If d > 0 and n == 1 then n = 0 (a child reduced to a
+ * single playout is removed).  v_i = n; v_c* = N_c*.  The loop runs at most ceil(sqrt(k * S)) times per child.
+ * The sample's visits[] AND the move-choice weights (temperature 1 and late_temperature alike, the same single uniform draw) use
+ * v; n_moves and the action list are unchanged.  The tree keeps its real N and W: tree reuse, `sims`, REUSED_VISITS, the budget
+ * and xq_engine_read_root are unaffected.  Counters, 0 without the option:
+ *   reserved[XQ_STAT_FORCED_SIMS]      simulations that took a forced child at the root
+ *   reserved[XQ_STAT_PRUNED_VISITS]    sum over full moves and children of N_i - v_i
+ *   reserved[XQ_STAT_PRUNED_CHILDREN]  children with N_i > 0 and v_i == 0
+ * Consequences: a sample's visits sum to AT MOST num_simulations, no longer exactly; with k * num_simulations < 1 no child is
+ * ever forced (N_i^2 >= 1 > f_i) and no visit is subtracted ((d+1)^2 >= 1 > f_i), so every record equals an engine's without the
+ * option byte for byte.
+ * It combines with XQ_ENGINE_TREE_REUSE, with the playout cap (full moves only) and with the evaluation cache (unchanged).
+ * XQ_ERR_ARG before any launch (xq_engine_workspace_bytes_fp: 0): manual_moves 1 or 2, add_noise == 0, leaves_per_step > 1, k not
+ * finite, k <= 0 or k > 16, a non-zero reserved word, and whatever xq_engine_init_cap refuses.  No workspace is added: k lives in
+ * the last free per-slot state word, "forced on" in the handle (pad0, above the public flag bits). */
+typedef struct xq_forced_playouts { double k; uint32_t reserved[2]; } xq_forced_playouts;
+#define XQ_STAT_FORCED_SIMS 7
+#define XQ_STAT_PRUNED_VISITS 8
+#define XQ_STAT_PRUNED_CHILDREN 9
+size_t xq_engine_workspace_bytes_fp(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced);
+int xq_engine_init_fp(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream);
 
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 

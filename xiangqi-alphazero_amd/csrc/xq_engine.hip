@@ -41,11 +41,14 @@ enum Gi : int { GI_SIDE = 0, GI_MC, GI_NOCAP, GI_PHASE, GI_SIMS, GI_NSAMP, GI_GS
                 GI_FREASON, GI_MANNOISE, GI_DELAY, GI_NPEND, GI_RR_NODE, GI_RR_MARK, GI_RR_DROP,
                 // playout cap (xq_engine_init_cap): this move's kind (1 full, 0 fast) and budget, written by k_select<.., true> at
                 // PH_NEWPOS; S_fast and the two halves of the float64 threshold p, written once by k_init_cap
-                GI_CAP_FULL, GI_CAP_BUDGET, GI_CAP_SFAST, GI_CAP_PLO, GI_CAP_PHI, GI_N = 32 };
+                GI_CAP_FULL, GI_CAP_BUDGET, GI_CAP_SFAST, GI_CAP_PLO, GI_CAP_PHI,
+                // forced playouts (xq_engine_init_fp): k as float32 bits, written once by k_init_fp
+                GI_FP_K, GI_N = 32 };
+static_assert(GI_FP_K == 31, "the forced-playout parameter takes the last free state word");
 
 enum St : int { ST_SIMS = 0, ST_TERM, ST_LEAF, ST_ROOT, ST_MOVES, ST_GAMES, ST_RED, ST_BLACK, ST_DRAW, ST_PLIES, ST_NODES,
                 ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_COLL, ST_LPS, ST_LSTEPS, ST_REUSED,
-                ST_REROOTS, ST_FASTM, ST_FASTS, ST_N = 32 };
+                ST_REROOTS, ST_FASTM, ST_FASTS, ST_FORCED, ST_PRUNEDV, ST_PRUNEDC, ST_N = 32 };
 
 enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_TW, P_TP, P_TA, P_TC, P_TM, P_ROOTP,
                  P_STAGE, P_OUTS, P_OUTR, P_CNT, P_STATS, P_INJECT, P_SQRT, P_MNOISE, P_STATSUM, P_REQ,
@@ -255,7 +258,10 @@ constexpr int WAVES_PER_WG = 4;
 #if XQ_SELECT_WAVES_PER_EU > 0
 #define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu(XQ_SELECT_WAVES_PER_EU, XQ_SELECT_WAVES_PER_EU)))
 #else
-#define XQ_SELECT_OCC
+// Nothing for the instances without forced playouts (0, 0 emits no attribute: they compile as they always did).  The FORCED
+// instances are held to the same two waves per SIMD: left alone, the two with CAP take 256 VGPRs plus a few AGPRs and halve
+// their occupancy.
+#define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu(FORCED ? 2 : 0, FORCED ? 2 : 0)))
 #endif
 // REUSE (tree reuse): at the end of a move the chosen child and the old allocation mark are handed to k_reroot and
 // k_expand<true> of the same step (GI_RR_NODE / GI_RR_MARK); k_select<false> is k_select as it always was.
@@ -263,7 +269,11 @@ constexpr int WAVES_PER_WG = 4;
 // its root request is issued; u < p makes the move FULL (today's move), otherwise FAST: budget S_fast, no root noise
 // (k_expand), no sample.  The kind and the budget live in GI_CAP_FULL / GI_CAP_BUDGET from the root request to the move's end.
 // k_select<.., false> is k_select as it always was.
-template <bool REUSE, bool CAP = false>
+// FORCED (forced playouts and policy target pruning, xq_engine_init_fp): at a root of prior kind 1 -- the noisy root of a full
+// move, always node 0 -- a visited child i with N_i^2 < (k rootP[i]) N_root scores +infinity in the descent (the first maximum
+// then takes the lowest-index forced child), and at the move's end the sample's visits and the move-choice weights are the
+// PRUNED counts v_i (include/xq_hip.h); the tree keeps its N and W.  k_select<.., .., false> is k_select as it always was.
+template <bool REUSE, bool CAP = false, bool FORCED = false>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev E, float *__restrict__ nn_in) {
     __shared__ SelectLds Ls[WAVES_PER_WG];
     SelectLds &L = Ls[threadIdx.x >> 6];
@@ -311,6 +321,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
     const bool full_move = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_FULL]) != 0 : true;
     const int budget = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_BUDGET]) : S;
     unsigned long long d_fast_moves = 0, d_fast_sims = 0;
+    // FORCED: k, a float32 widened at every use; the counters of this launch (one launch runs fewer than 2^31 simulations)
+    const float fp_k = FORCED ? __int_as_float(__builtin_amdgcn_readfirstlane(gi[GI_FP_K])) : 0.0f;
+    unsigned d_forced = 0, d_prunedv = 0, d_prunedc = 0;
 
     lds_copy_dwords(L.root, g_board, XQ_BS / 4);
     lds_copy_dwords(L.rhist, g_hist, XQ_HIST * XQ_BS / 4);
@@ -473,8 +486,61 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                     s->ply = (uint16_t)g_mc; s->slot = (uint32_t)slot; s->game_seq = (uint32_t)game_seq;
                 }
             }
+            // FORCED: policy target pruning at a kind-1 root.  c* = first maximum of N; P* its PUCT score at the root's final
+            // count, in the kind-1 float64 arithmetic of the descent; every other visited child gives back, one at a time and
+            // at most while (d + 1)^2 < f_i, the visits after which its score (q held constant) would still be below P*.
+            // The pruned counts go through L.w_tmp (every lane reads back only what it wrote), so that nothing of this block is
+            // live in the staging loop below.
+            bool prune = false;
+            if (FORCED && (__builtin_amdgcn_readfirstlane((int)tM[0]) >> 14) == 1) {
+                prune = true;
+                int bn = -1, bi = 0x7FFFFFFF;
+                for (int i = lane; i < nch; i += 64) {
+                    const int n = tN[first + i];
+                    if (n > bn) { bn = n; bi = i; }
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
+                    if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+                }
+                const int p_star_i = __builtin_amdgcn_readfirstlane(bi);
+                bn = __builtin_amdgcn_readfirstlane(bn);
+                const int nr = __builtin_amdgcn_readfirstlane(tN[0]);
+                const double p_nr = (double)nr, p_sqrt = E.sqrt_tab[nr];
+                double p_star;
+                {
+                    const double w = tW[first + p_star_i];
+                    double t = E.cfg.c_puct * rootP[p_star_i];
+                    t = t * p_sqrt;
+                    t = t / (double)(1 + bn);
+                    p_star = (bn ? w / (double)bn : 0.0) + t;
+                }
+                int l_prunedv = 0, l_prunedc = 0;
+                for (int i = lane; i < nch; i += 64) {
+                    int n = tN[first + i];
+                    if (i != p_star_i && n > 0) {
+                        const int n0 = n;
+                        const double p = rootP[i];
+                        const double f = ((double)fp_k * p) * p_nr;
+                        const double q = tW[first + i] / (double)n0;
+                        double e = E.cfg.c_puct * p;
+                        e = e * p_sqrt;
+                        int d = 0;
+                        while (n > 1 && (double)(d + 1) * (double)(d + 1) < f && q + e / (double)n < p_star) { n -= 1; d += 1; }
+                        if (d > 0 && n == 1) n = 0;               // reduced to a single playout: removed
+                        l_prunedv += n0 - n;
+                        l_prunedc += n == 0 ? 1 : 0;
+                    }
+                    L.w_tmp[i] = (double)n;
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) { l_prunedv += __shfl_xor(l_prunedv, off); l_prunedc += __shfl_xor(l_prunedc, off); }
+                d_prunedv += (unsigned)l_prunedv; d_prunedc += (unsigned)l_prunedc;
+            }
             for (int i = lane; i < nch; i += 64) {
-                const int a = tA[first + i], n = tN[first + i];
+                const int a = tA[first + i];
+                const int n = (FORCED && prune) ? (int)L.w_tmp[i] : tN[first + i];
                 if (full_move) {
                     ((xq_sample *)rec)->actions[i] = (uint16_t)a;
                     ((xq_sample *)rec)->visits[i] = (uint16_t)(n > 65535 ? 65535 : n);
@@ -573,6 +639,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                         t = t * sqrtp;
                         t = t / (double)(1 + n);
                         ucb = q + t;
+                        // forced playout: a visited child of the noisy root below its minimum share of the root's visits
+                        if (FORCED && kind == 1 && n > 0 && (double)n * (double)n < ((double)fp_k * p) * (double)pn) ucb = INFINITY;
                     }
                     if (ucb > best) { best = ucb; best_i = i; c_m = cm; c_first = cf; c_n = n; c_a = ca; }
                 }
@@ -584,6 +652,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                 if (ov > best || (ov == best && oi < best_i)) { best = ov; best_i = oi; }
             }
             best_i = __builtin_amdgcn_readfirstlane(best_i);
+            if (FORCED && kind == 1 && best == INFINITY) d_forced += 1;   // wave-uniform after the reduction
             int action;
             if (best_i == 0x7FFFFFFF) {                              // all-NaN scores: the reference would raise
                 ovf |= 8; best_i = 0;
@@ -648,6 +717,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
         gi[GI_RNG0] = rng_ctr[0]; gi[GI_RNG1] = rng_ctr[1]; gi[GI_RNG2] = rng_ctr[2]; gi[GI_RNG3] = rng_ctr[3];
         st[ST_SIMS] += d_sims; st[ST_TERM] += d_term; st[ST_MOVES] += d_moves; st[ST_DEPTH] += d_depth; st[ST_SCAN] += d_scan;
         if (CAP) { st[ST_FASTM] += d_fast_moves; st[ST_FASTS] += d_fast_sims; }
+        if (FORCED) { st[ST_FORCED] += d_forced; st[ST_PRUNEDV] += d_prunedv; st[ST_PRUNEDC] += d_prunedc; }
         if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8;
     }
 }
@@ -1629,6 +1699,13 @@ __global__ void k_init_cap(Dev E, int fast_simulations, double full_search_prob)
     gi[GI_CAP_SFAST] = fast_simulations; gi[GI_CAP_PLO] = (int32_t)(uint32_t)pb; gi[GI_CAP_PHI] = (int32_t)(uint32_t)(pb >> 32);
 }
 
+// xq_engine_init_fp: the forced-playout parameter k, rounded to float32 by the host, in the last free state word of every slot.
+__global__ void k_init_fp(Dev E, float k) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= E.cfg.n_games) return;
+    E.gi[(size_t)slot * GI_N + GI_FP_K] = __float_as_int(k);
+}
+
 // Column sums of the per-slot counters [G][ST_N] (OR for the overflow word): each 256-thread block sweeps slot rows
 // (8 rows x 32 columns per pass, 256 contiguous bytes per row), folds its eight partial rows through LDS and adds the
 // result to the zeroed output with one atomic per column.
@@ -2077,18 +2154,32 @@ bool cap_ok(const xq_engine_config *c, int K, const xq_playout_cap *cap) {
            cap->fast_simulations < c->num_simulations && cap->full_search_prob > 0.0 && cap->full_search_prob <= 1.0;
 }
 
+// forced playouts: self-play with root noise only, one leaf per step, 0 < k <= 16 (a NaN fails both comparisons)
+bool forced_ok(const xq_engine_config *c, int K, const xq_forced_playouts *fp) {
+    if (c->manual_moves != 0 || c->add_noise == 0 || K != 1) return false;
+    for (uint32_t r : fp->reserved) if (r != 0) return false;
+    return fp->k > 0.0 && fp->k <= 16.0;
+}
+
 // pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
-// flag bits "playout cap on" (xq_engine_init_cap)
+// flag bits "playout cap on" (xq_engine_init_cap) and "forced playouts on" (xq_engine_init_fp)
 constexpr int PAD0_CAP = 1 << 30;
+constexpr int PAD0_FORCED = 1 << 29;
 int leaves_of(const xq_engine *e) { return (e->pad0 & 0xFFFF) > 1 ? (e->pad0 & 0xFFFF) : 1; }
 bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE_TREE_REUSE; }
 bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
+bool forced_of(const xq_engine *e) { return (e->pad0 & PAD0_FORCED) != 0; }
 
 // the K = 1 step's two kernels, by the engine's options
 void launch_select(const xq_engine *eng, const Dev &d, float *nn_in, hipStream_t s) {
     const dim3 grid((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), block(64 * WAVES_PER_WG);
     const bool reuse = reuse_of(eng), cap = cap_of(eng);
-    if (reuse && cap) hipLaunchKernelGGL((k_select<true, true>), grid, block, 0, s, d, nn_in);
+    if (forced_of(eng)) {
+        if (reuse && cap) hipLaunchKernelGGL((k_select<true, true, true>), grid, block, 0, s, d, nn_in);
+        else if (reuse) hipLaunchKernelGGL((k_select<true, false, true>), grid, block, 0, s, d, nn_in);
+        else if (cap) hipLaunchKernelGGL((k_select<false, true, true>), grid, block, 0, s, d, nn_in);
+        else hipLaunchKernelGGL((k_select<false, false, true>), grid, block, 0, s, d, nn_in);
+    } else if (reuse && cap) hipLaunchKernelGGL((k_select<true, true>), grid, block, 0, s, d, nn_in);
     else if (reuse) hipLaunchKernelGGL((k_select<true, false>), grid, block, 0, s, d, nn_in);
     else if (cap) hipLaunchKernelGGL((k_select<false, true>), grid, block, 0, s, d, nn_in);
     else hipLaunchKernelGGL((k_select<false, false>), grid, block, 0, s, d, nn_in);
@@ -2129,9 +2220,15 @@ size_t xq_engine_workspace_bytes_ex(const xq_engine_config *cfg, int leaves_per_
 }
 
 size_t xq_engine_workspace_bytes_cap(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap) {
+    return xq_engine_workspace_bytes_fp(cfg, leaves_per_step, flags, cap, nullptr);
+}
+
+size_t xq_engine_workspace_bytes_fp(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced) {
     if (!config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags)) return 0;
     if (cap && !cap_ok(cfg, leaves_per_step, cap)) return 0;
-    return make_layout(cfg, leaves_per_step).total;   // neither tree reuse nor the playout cap needs workspace of its own
+    if (forced && !forced_ok(cfg, leaves_per_step, forced)) return 0;
+    return make_layout(cfg, leaves_per_step).total;   // tree reuse, the playout cap and forced playouts need no workspace of their own
 }
 
 int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t ws_bytes, const uint64_t *dev_inject,
@@ -2151,10 +2248,16 @@ int xq_engine_init_ex(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
 
 int xq_engine_init_cap(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
                        void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
+    return xq_engine_init_fp(eng, cfg, leaves_per_step, flags, cap, nullptr, ws, ws_bytes, dev_inject, stream);
+}
+
+int xq_engine_init_fp(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
     if (!eng || !config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags) || !ws ||
         ((uintptr_t)ws & 255))
         return XQ_ERR_ARG;
     if (cap && !cap_ok(cfg, leaves_per_step, cap)) return XQ_ERR_ARG;
+    if (forced && !forced_ok(cfg, leaves_per_step, forced)) return XQ_ERR_ARG;
     if (cfg->inject_len > 0 && !dev_inject) return XQ_ERR_ARG;
     const int K = leaves_per_step;
     const Layout l = make_layout(cfg, K);
@@ -2162,7 +2265,7 @@ int xq_engine_init_cap(xq_engine *eng, const xq_engine_config *cfg, int leaves_p
     memset(eng, 0, sizeof(*eng));
     eng->cfg = *cfg;
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
-    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16) | (cap ? PAD0_CAP : 0);
+    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16) | (cap ? PAD0_CAP : 0) | (forced ? PAD0_FORCED : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -2192,6 +2295,11 @@ int xq_engine_init_cap(xq_engine *eng, const xq_engine_config *cfg, int leaves_p
         if (rc != XQ_OK) return rc;
         hipLaunchKernelGGL(k_init_cap, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d, (int)cap->fast_simulations,
                            cap->full_search_prob);
+    }
+    if (forced) {
+        const int rc = launch_status();
+        if (rc != XQ_OK) return rc;
+        hipLaunchKernelGGL(k_init_fp, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d, (float)forced->k);
     }
     return launch_status();
 }
@@ -2317,6 +2425,8 @@ int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *
     host_out->reserved[XQ_STAT_LEAF_STEPS] = h[ST_LSTEPS];
     host_out->reserved[XQ_STAT_REUSED_VISITS] = h[ST_REUSED]; host_out->reserved[XQ_STAT_REROOTS] = h[ST_REROOTS];
     host_out->reserved[XQ_STAT_FAST_MOVES] = h[ST_FASTM]; host_out->reserved[XQ_STAT_FAST_SIMS] = h[ST_FASTS];
+    host_out->reserved[XQ_STAT_FORCED_SIMS] = h[ST_FORCED]; host_out->reserved[XQ_STAT_PRUNED_VISITS] = h[ST_PRUNEDV];
+    host_out->reserved[XQ_STAT_PRUNED_CHILDREN] = h[ST_PRUNEDC];
     return h[ST_OVF] ? XQ_ERR_OVERFLOW : XQ_OK;
 }
 

@@ -46,6 +46,13 @@ With `playout_cap=(full_search_prob, fast_simulations)` (opt-in; xq_engine_init_
 position takes one draw of the slot's uniform stream: with probability p the move is a full move (noise, S simulations, a
 sample), otherwise a fast one (no noise, `fast_simulations`, no sample).  `stats()` adds `fast_moves` and `fast_sims`.
 Self-play only, K = 1; it combines with tree reuse and the evaluation cache.
+
+With `forced_playouts=k` (opt-in, 0 < k <= 16, KataGo uses 2; xq_engine_init_fp) a visited child of a
+noisy root is forced until its visits reach sqrt(k * noisy prior * root visits), and the forced visits the search would not have
+spent by itself are subtracted again before the visit counts become the sample's target and the move distribution, so a
+sample's visits sum to at most S.  The tree keeps its real counts.  `stats()` adds `forced_sims`, `pruned_visits` and
+`pruned_children`.  Self-play with root noise only, K = 1; it combines with tree reuse, the playout cap (full moves only) and
+the evaluation cache.
 """
 from __future__ import annotations
 
@@ -98,7 +105,7 @@ def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
 class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
-                 tree_reuse: bool = False, playout_cap=None):
+                 tree_reuse: bool = False, playout_cap=None, forced_playouts=None):
         K = int(leaves_per_step)
         if not 1 <= K <= 64:
             raise hip.XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
@@ -124,6 +131,21 @@ class SelfPlayEngine:
             if not 0.0 < p_full <= 1.0:                    # a NaN fails both comparisons
                 raise hip.XqError(f"playout_cap: full_search_prob must be in (0, 1], got {p_full}")
             cap = hip.PlayoutCap(s_fast, 0, p_full)
+        forced = None
+        if forced_playouts is not None:
+            try:
+                fk = float(forced_playouts)
+            except (TypeError, ValueError):
+                raise hip.XqError("forced_playouts must be a number k with 0 < k <= 16")
+            if int(cfg.manual_moves) != 0:
+                raise hip.XqError("forced_playouts is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
+            if not int(cfg.add_noise):
+                raise hip.XqError("forced_playouts acts at noisy roots only: not available with add_noise = 0")
+            if K > 1:
+                raise hip.XqError("forced_playouts cannot be combined with leaves_per_step > 1")
+            if not 0.0 < fk <= 16.0:                       # a NaN fails both comparisons
+                raise hip.XqError(f"forced_playouts: k must be in (0, 16], got {fk}")
+            forced = hip.ForcedPlayouts(fk)
         if K > 1 and eval_cache_entries:
             raise hip.XqError("leaves_per_step > 1 cannot be combined with an evaluation cache (eval_cache_entries > 0)")
         if K > 1 and int(cfg.manual_moves) == 2:
@@ -137,10 +159,14 @@ class SelfPlayEngine:
         self.K = K
         self.tree_reuse = tree_reuse
         self.playout_cap = None if cap is None else (cap.full_search_prob, cap.fast_simulations)
+        self.forced_playouts = None if forced is None else float(np.float32(forced.k))   # k as the kernels use it
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         flags = hip.ENGINE_TREE_REUSE if tree_reuse else 0
-        if cap is not None:
+        cap_ref = None if cap is None else C.byref(cap)
+        if forced is not None:
+            nbytes = self.lib.xq_engine_workspace_bytes_fp(C.byref(cfg), K, flags, cap_ref, C.byref(forced))
+        elif cap is not None:
             nbytes = self.lib.xq_engine_workspace_bytes_cap(C.byref(cfg), K, flags, C.byref(cap))
         elif tree_reuse:
             nbytes = self.lib.xq_engine_workspace_bytes_ex(C.byref(cfg), K, flags)
@@ -162,7 +188,11 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            if cap is not None:
+            if forced is not None:
+                hip.check(self.lib.xq_engine_init_fp(C.byref(self.h), C.byref(cfg), K, flags, cap_ref, C.byref(forced), base,
+                                                     self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
+                          "xq_engine_init_fp")
+            elif cap is not None:
                 hip.check(self.lib.xq_engine_init_cap(C.byref(self.h), C.byref(cfg), K, flags, C.byref(cap), base,
                                                       self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
                           "xq_engine_init_cap")
@@ -461,7 +491,7 @@ class SelfPlayEngine:
     def slot_counters(self) -> torch.Tensor:
         """Zero-copy int64 [G, 32] view of the per-slot counters that xq_engine_stats_read sums (column 19: collisions, 20:
         pending leaves handed out, 21: slot-steps that handed leaves, 22: reused visits, 23: re-rooted searches, 24: fast moves,
-        25: simulations of fast searches).  For tests."""
+        25: simulations of fast searches, 26: forced simulations, 27: pruned visits, 28: pruned children).  For tests."""
         off = int(self.h.p[17]) - int(self.ws.data_ptr())
         return self.ws[off:off + self.G * 32 * 8].view(torch.int64).view(self.G, 32)
 

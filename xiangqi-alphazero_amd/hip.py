@@ -59,8 +59,8 @@ class EngineStats(C.Structure):
                 ("sims", "terminal_sims", "leaf_evals", "root_evals", "moves_played", "games_finished", "red_wins",
                  "black_wins", "draws", "plies_finished", "nodes_created", "depth_sum", "children_scanned", "resigns",
                  "samples_written", "samples_dropped", "overflow", "games_started", "rows_evaluated", "collisions",
-                 "leaves_per_step_sum", "leaf_steps", "reused_visits", "reroots", "fast_moves", "fast_sims")] + \
-               [("reserved", C.c_uint64 * 6)]
+                 "leaves_per_step_sum", "leaf_steps", "reused_visits", "reroots", "fast_moves", "fast_sims", "forced_sims",
+                 "pruned_visits", "pruned_children")] + [("reserved", C.c_uint64 * 3)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
@@ -69,6 +69,11 @@ class EngineStats(C.Structure):
 class PlayoutCap(C.Structure):
     """xq_playout_cap: playout cap randomization (xq_engine_init_cap): S_fast and the probability p of a full search."""
     _fields_ = [("fast_simulations", C.c_int32), ("reserved", C.c_int32), ("full_search_prob", C.c_double)]
+
+
+class ForcedPlayouts(C.Structure):
+    """xq_forced_playouts: forced playouts and policy target pruning (xq_engine_init_fp): the parameter k."""
+    _fields_ = [("k", C.c_double), ("reserved", C.c_uint32 * 2)]
 
 
 class PackedBuffers(C.Structure):
@@ -125,6 +130,11 @@ def lib():
     L.xq_engine_workspace_bytes_cap.restype = C.c_size_t
     L.xq_engine_init_cap.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap), vp,
                                      C.c_size_t, vp, vp]
+    L.xq_engine_workspace_bytes_fp.argtypes = [C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap),
+                                               C.POINTER(ForcedPlayouts)]
+    L.xq_engine_workspace_bytes_fp.restype = C.c_size_t
+    L.xq_engine_init_fp.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap),
+                                    C.POINTER(ForcedPlayouts), vp, C.c_size_t, vp, vp]
     L.xq_engine_select.argtypes = [C.POINTER(Engine), vp, vp]
     L.xq_engine_expand.argtypes = [C.POINTER(Engine), vp, vp, i32, vp]
     L.xq_engine_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(EngineStats), vp]
@@ -198,7 +208,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_bn_sync_backward_apply", "xq_evcache_bytes", "xq_evcache_init", "xq_evcache_hit_flags", "xq_evcache_probe",
            "xq_engine_compact_misses", "xq_evcache_commit", "xq_evcache_invalidate", "xq_evcache_stats_read",
            "xq_evcache_key_host", "xq_engine_workspace_bytes_leaves", "xq_engine_init_leaves", "xq_engine_workspace_bytes_ex",
-           "xq_engine_init_ex", "xq_engine_drop_reroots", "xq_engine_workspace_bytes_cap", "xq_engine_init_cap"]
+           "xq_engine_init_ex", "xq_engine_drop_reroots", "xq_engine_workspace_bytes_cap", "xq_engine_init_cap",
+           "xq_engine_workspace_bytes_fp", "xq_engine_init_fp"]
 
 
 def check(rc: int, what: str):

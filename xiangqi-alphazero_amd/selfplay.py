@@ -25,7 +25,7 @@ _CFG_KEYS = ("num_simulations", "c_puct", "temperature_threshold", "max_game_len
 def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[int] = None, seed: int = 0, rank: int = 0,
               evaluator_kind: str = "hip", poll_every: int = 64, device_records: bool = False, use_graph: bool = True,
               eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None,
-              tree_reuse: Optional[bool] = None, playout_cap=None):
+              tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -37,7 +37,10 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     `playout_cap` = (full_search_prob, fast_simulations) (None: `config.playout_cap_full_prob` and
     `config.playout_cap_fast_simulations`, absent = off) searches only that share of the moves at full size and records only
     those as samples; the others get `fast_simulations`, no noise and no sample (stats `fast_moves`, `fast_sims`,
-    `playout_cap`).  Games finish sooner and carry fewer samples each; it needs K = 1."""
+    `playout_cap`).  Games finish sooner and carry fewer samples each; it needs K = 1.
+    `forced_playouts` = k (None: `config.forced_playouts_k`, absent or 0 = off) forces visited children of a noisy root up to
+    sqrt(k * prior * root visits) visits and prunes those visits from the samples' targets and the move distribution again
+    (stats `forced_sims`, `pruned_visits`, `pruned_children`, `forced_playouts`); it needs K = 1."""
     if eval_cache_entries is None:
         eval_cache_entries = int(getattr(config, "eval_cache_entries", 0) or 0)
     if leaves_per_step is None:
@@ -51,6 +54,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
             raise ValueError("config.playout_cap_full_prob and config.playout_cap_fast_simulations go together")
         if p_full is not None:
             playout_cap = (float(p_full), int(s_fast))
+    if forced_playouts is None:
+        forced_playouts = float(getattr(config, "forced_playouts_k", 0) or 0) or None
     slots = int(n_slots or min(num_games, 8192))
     slots = max(1, min(slots, num_games))
     ev, ev_name = evaluator.make_evaluator(model, device, evaluator_kind)
@@ -62,7 +67,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
         add_noise=True, seed=seed, rank=rank, games_target=num_games,
         max_out_samples=num_games * 201, max_out_results=num_games + 8)
     eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries,
-                                leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap)
+                                leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
+                                forced_playouts=forced_playouts)
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -81,6 +87,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     st["leaves_per_step"] = eng.K
     st["tree_reuse"] = eng.tree_reuse
     st["playout_cap"] = eng.playout_cap                # None, or (full_search_prob, fast_simulations)
+    st["forced_playouts"] = eng.forced_playouts        # None, or k
     st.setdefault("eval_cache_probes", 0)              # the cache's keys are present (0) when it is off
     st.setdefault("eval_cache_hits", 0)
     if eng.capture_error:
@@ -92,7 +99,8 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
                        gpu_device: str = "cuda", *, n_slots: Optional[int] = None, seed: int = 0,
                        return_compact: bool = False, eval_cache_entries: Optional[int] = None,
                        leaves_per_step: Optional[int] = None,
-                       tree_reuse: Optional[bool] = None, playout_cap=None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
+                       tree_reuse: Optional[bool] = None, playout_cap=None,
+                       forced_playouts: Optional[float] = None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
     for k in _CFG_KEYS + ("num_games_per_iter",):
         if not hasattr(config, k):
             raise AttributeError(f"config lacks '{k}' (see training/train.py:55-111)")
@@ -101,7 +109,8 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
         leaves_per_step = int(getattr(config, "leaves_per_step", 1) or 1)   # a reference TrainingConfig has no such key
     samples, results, st, elapsed = run_games(model, config, num_games, gpu_device, n_slots, seed,
                                               eval_cache_entries=eval_cache_entries, leaves_per_step=leaves_per_step,
-                                              tree_reuse=tree_reuse, playout_cap=playout_cap)
+                                              tree_reuse=tree_reuse, playout_cap=playout_cap,
+                                              forced_playouts=forced_playouts)
     all_data, per_game = to_reference_tuples(samples, results, augment=True)
     wins = {1: 0, -1: 0, 0: 0}
     total_steps = 0
@@ -117,6 +126,8 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
         "eval_cache_probes": st["eval_cache_probes"], "eval_cache_hits": st["eval_cache_hits"],
         "reused_visits": st["reused_visits"], "reroots": st["reroots"],
         "fast_moves": st["fast_moves"], "fast_sims": st["fast_sims"], "playout_cap": st["playout_cap"],
+        "forced_sims": st["forced_sims"], "pruned_visits": st["pruned_visits"], "pruned_children": st["pruned_children"],
+        "forced_playouts": st["forced_playouts"],
     }
     if return_compact:
         stats["compact_samples"], stats["compact_results"] = samples, results

@@ -78,7 +78,10 @@ class AlphaZeroLoop:
                                                     seed=self.seed + 1000 * self.iteration, rank=self.rank,
                                                     evaluator_kind=self.evaluator_kind, device_records=True,
                                                     # leaf batching is a self-play option only: the arena stays sequential
-                                                    leaves_per_step=int(getattr(self.config, "leaves_per_step", 1) or 1))
+                                                    leaves_per_step=int(getattr(self.config, "leaves_per_step", 1) or 1),
+                                                    # forced playouts too (config.forced_playouts_k; absent or 0: off): the
+                                                    # arena (arena.py) never takes it
+                                                    forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None)
         return samples, results
 
     def self_play(self) -> dict:
