@@ -231,14 +231,412 @@ __device__ __forceinline__ void wave_make_move(int8_t *b, int8_t (*ring)[XQ_BS],
     mc += 1;
 }
 
-// mcts.py:66-73 along path[0..depth]
-__device__ __forceinline__ void wave_backup(int32_t *tN, double *tW, const int32_t *path, int depth, double v) {
+// One slot's tree: six arrays of node_cap entries (node 0 is the root)
+struct Tree {
+    int32_t *N; double *W; float *P; uint16_t *A; int32_t *C; uint16_t *M;
+};
+
+__device__ __forceinline__ Tree slot_tree(const Dev &E, int slot) {
+    const size_t nb = (size_t)slot * E.node_cap;
+    return Tree{E.tN + nb, E.tW + nb, E.tP + nb, E.tA + nb, E.tC + nb, E.tM + nb};
+}
+
+// mcts.py:66-73 along path[0..depth].  VL (leaf batching): the pending descent's virtual loss is removed on the way.
+template <bool VL>
+__device__ __forceinline__ void wave_backup(const Tree &T, int32_t *vl, const int32_t *path, int depth, double v) {
     for (int j = lane_id(); j <= depth; j += 64) {
         const int nd = path[j];
         const double s = ((depth - j) & 1) ? -v : v;
-        tN[nd] += 1;
-        tW[nd] += s;
+        T.N[nd] += 1;
+        T.W[nd] += s;
+        if (VL) vl[nd] -= 1;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The per-slot phases of the select kernels (k_select<REUSE, CAP, FORCED> and k_select_multi), one copy each.
+//
+// Wave-uniform state of the slot a select kernel works on: slot_load reads it from gi[], slot_store writes it back.  The
+// counter deltas are kept wave-uniform and written by lane 0 at the end.
+struct Slot {
+    int slot, lane;
+    int32_t *gi;
+    unsigned long long *st;
+    Tree T;
+    int side, mc, nocap;                    // the real game (its board and ring are SelectLds.root / .rhist)
+    int sims_done, n_samples, game_seq;
+    int rng_ctr[4];
+    int ovf;
+    bool dirty;                             // real game state changed -> write back
+    unsigned long long d_sims, d_term, d_moves, d_depth, d_scan;
+    unsigned d_forced, d_prunedv, d_prunedc;    // FORCED only (one launch runs fewer than 2^31 simulations)
+};
+
+__device__ __forceinline__ void slot_load(Slot &s) {
+    const int32_t *gi = s.gi;
+    s.side = __builtin_amdgcn_readfirstlane(gi[GI_SIDE]);
+    s.mc = __builtin_amdgcn_readfirstlane(gi[GI_MC]);
+    s.nocap = __builtin_amdgcn_readfirstlane(gi[GI_NOCAP]);
+    s.sims_done = __builtin_amdgcn_readfirstlane(gi[GI_SIMS]);
+    s.n_samples = __builtin_amdgcn_readfirstlane(gi[GI_NSAMP]);
+    s.game_seq = __builtin_amdgcn_readfirstlane(gi[GI_GSEQ]);
+    s.rng_ctr[0] = __builtin_amdgcn_readfirstlane(gi[GI_RNG0]); s.rng_ctr[1] = __builtin_amdgcn_readfirstlane(gi[GI_RNG1]);
+    s.rng_ctr[2] = __builtin_amdgcn_readfirstlane(gi[GI_RNG2]); s.rng_ctr[3] = __builtin_amdgcn_readfirstlane(gi[GI_RNG3]);
+    s.ovf = 0;
+    s.dirty = false;
+    s.d_sims = s.d_term = s.d_moves = s.d_depth = s.d_scan = 0;
+    s.d_forced = s.d_prunedv = s.d_prunedc = 0;
+}
+
+// the real game's board and ring (when a move or a new game changed them), the state words and the common counters
+__device__ __forceinline__ void slot_store(const Dev &E, const Slot &s, const SelectLds &L, int phase) {
+    if (s.dirty) {
+        lds_copy_dwords(E.board + (size_t)s.slot * XQ_BS, L.root, XQ_BS / 4);
+        lds_copy_dwords(E.hist + (size_t)s.slot * XQ_HIST * XQ_BS, L.rhist, XQ_HIST * XQ_BS / 4);
+    }
+    if (s.lane == 0) {
+        int32_t *gi = s.gi;
+        unsigned long long *st = s.st;
+        gi[GI_SIDE] = s.side; gi[GI_MC] = s.mc; gi[GI_NOCAP] = s.nocap; gi[GI_PHASE] = phase; gi[GI_SIMS] = s.sims_done;
+        gi[GI_NSAMP] = s.n_samples; gi[GI_GSEQ] = s.game_seq;
+        gi[GI_RNG0] = s.rng_ctr[0]; gi[GI_RNG1] = s.rng_ctr[1]; gi[GI_RNG2] = s.rng_ctr[2]; gi[GI_RNG3] = s.rng_ctr[3];
+        st[ST_SIMS] += s.d_sims; st[ST_TERM] += s.d_term; st[ST_MOVES] += s.d_moves; st[ST_DEPTH] += s.d_depth;
+        st[ST_SCAN] += s.d_scan;
+        if (s.ovf) st[ST_OVF] |= (unsigned long long)s.ovf << 8;
+    }
+}
+
+// PH_FINISHED: flush the finished game's samples with z (parallel_selfplay.py:123-132) and its result
+__device__ __forceinline__ void slot_flush_finished(const Dev &E, const Slot &s) {
+    const int lane = s.lane, n_samples = s.n_samples;
+    unsigned long long *st = s.st;
+    const int winner = __builtin_amdgcn_readfirstlane(s.gi[GI_FWINNER]);
+    const int reason = __builtin_amdgcn_readfirstlane(s.gi[GI_FREASON]);
+    unsigned base = 0;
+    bool fits = true;
+    if (n_samples > 0) {
+        if (lane == 0) base = atomicAdd(&E.cnt[0], (unsigned)n_samples);
+        base = __builtin_amdgcn_readfirstlane(base);
+        fits = (unsigned long long)base + (unsigned)n_samples <= (unsigned)E.cfg.max_out_samples;
+        if (fits) {
+            const uint8_t *src = E.stage + (size_t)s.slot * E.stage_cap * XQ_SAMPLE_BYTES;
+            uint8_t *dst = E.outs + (size_t)base * XQ_SAMPLE_BYTES;
+            const int ndw = n_samples * (XQ_SAMPLE_BYTES / 4);
+            for (int i = lane; i < ndw; i += 64) ((uint32_t *)dst)[i] = ((const uint32_t *)src)[i];
+            for (int i = lane; i < n_samples; i += 64) {
+                const int sside = ((const int8_t *)src)[(size_t)i * XQ_SAMPLE_BYTES + 90];
+                ((int8_t *)dst)[(size_t)i * XQ_SAMPLE_BYTES + 91] = (int8_t)(winner == 0 ? 0 : (winner == sside ? 1 : -1));
+            }
+        }
+    }
+    if (lane == 0) {
+        if (fits) st[ST_SAMP] += (unsigned)n_samples; else st[ST_DROP] += (unsigned)n_samples;
+        const unsigned r = atomicAdd(&E.cnt[1], 1u);
+        if (r < (unsigned)E.cfg.max_out_results) {
+            xq_game_result res;
+            res.slot = (uint32_t)s.slot; res.game_seq = (uint32_t)s.game_seq; res.winner = (int8_t)winner;
+            res.reason = (uint8_t)reason; res.steps = (uint16_t)s.mc; res.n_samples = (uint16_t)n_samples;
+            res.reserved = 0;
+            *(xq_game_result *)(E.outr + (size_t)r * XQ_RESULT_BYTES) = res;
+        }
+        st[ST_GAMES] += 1;
+        st[winner == 1 ? ST_RED : (winner == -1 ? ST_BLACK : ST_DRAW)] += 1;
+        st[ST_PLIES] += (unsigned)s.mc;
+        if (reason == 3) st[ST_RESIGN] += 1;
+    }
+}
+
+// PH_NEWGAME: new game + random opening (parallel_selfplay.py:58-72).  False when the games quota is used up: the slot idles.
+__device__ __forceinline__ bool slot_new_game(const Dev &E, Slot &s, SelectLds &L, bool arena) {
+    const int lane = s.lane, slot = s.slot;
+    unsigned long long idx = 0;
+    if (lane == 0) idx = atomicAdd(E.started, 1ull);
+    idx = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(idx >> 32)) << 32) |
+          (unsigned)__builtin_amdgcn_readfirstlane((unsigned)idx);
+    if (E.cfg.games_target > 0 && idx >= (unsigned long long)E.cfg.games_target) return false;
+    s.game_seq += 1;
+    s.n_samples = 0;
+    init_board_lds(L.root);
+    s.side = 1; s.mc = 0; s.nocap = 0;
+    if (lane == 0) { s.gi[GI_RESIGN_N] = 0; s.st[ST_STARTED] += 1; }
+    wave_sync();
+    const int R = arena ? 0 : E.cfg.random_opening_moves;
+    const int k = R > 0 ? (int)(draw_u64(E, slot, RNG_RANDINT, s.rng_ctr[RNG_RANDINT], s.st) % (uint64_t)(R + 1)) : 0;
+    if (!arena) s.rng_ctr[RNG_RANDINT] += 1;   // random.randint is called even when R == 0
+    for (int i = 0; i < k; ++i) {
+        const int cnt = wave_movegen(L.root, s.side, L.mg, L.moves, &s.ovf);
+        if (cnt == 0) break;
+        const int pick = (int)(draw_u64(E, slot, RNG_CHOICE, s.rng_ctr[RNG_CHOICE], s.st) % (uint64_t)cnt);
+        s.rng_ctr[RNG_CHOICE] += 1;
+        const int action = L.moves[pick];
+        wave_make_move(L.root, L.rhist, action, s.side, s.mc, s.nocap);
+        int c2, w2;
+        if (wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, L.mg, L.moves, &c2, &w2, &s.ovf)) {
+            init_board_lds(L.root);
+            s.side = 1; s.mc = 0; s.nocap = 0;
+            wave_sync();
+            break;
+        }
+    }
+    s.dirty = true;
+    return true;
+}
+
+// PH_NEWPOS, the root request: terminal status of the real position (0: to be searched), its planes to x and its ordered
+// legal moves to pmoves (the slot's first request row), and a fresh tree root.  Returns the number of legal moves.
+__device__ __forceinline__ int slot_root_request(const Dev &E, Slot &s, SelectLds &L, bool manual, bool arena, float *x,
+                                                 uint16_t *pmoves, int &status) {
+    const Tree &T = s.T;
+    int cnt, winner;
+    status = 0;
+    const bool done = wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, L.mg, L.moves, &cnt, &winner, &s.ovf);
+    if (done) status = 1;
+    else if (arena && s.mc >= E.cfg.max_game_length) {     // train.py:477,494-496: not over after max plies => draw
+        winner = 0;
+        status = 2;
+    } else if (!manual && !arena && s.mc >= E.cfg.max_game_length) {   // parallel_selfplay.py:79-89
+        int red, black;
+        wave_material(L.root, red, black);
+        const int diff = red - black;
+        winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
+        status = 2;
+    }
+    wave_encode(L.root, s.side, x);
+    for (int j = s.lane; j < cnt; j += 64) pmoves[j] = L.moves[j];
+    if (s.lane == 0) {
+        s.gi[GI_PCOUNT] = cnt; s.gi[GI_RSTATUS] = status; s.gi[GI_RWINNER] = winner;
+        s.gi[GI_ALLOC] = 1;
+        T.N[0] = 0; T.W[0] = 0.0; T.C[0] = -1; T.M[0] = 0; T.A[0] = 0; T.P[0] = 0.0f;
+    }
+    s.sims_done = 0;
+    return cnt;
+}
+
+// first maximum of n[0 .. nch): its index (lowest on ties) and value, wave-uniform
+__device__ __forceinline__ int wave_first_max(const int32_t *n, int nch, int &max) {
+    int bn = -1, bi = 0x7FFFFFFF;
+    for (int i = lane_id(); i < nch; i += 64) {
+        const int v = n[i];
+        if (v > bn) { bn = v; bi = i; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
+        if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+    }
+    max = __builtin_amdgcn_readfirstlane(bn);
+    return __builtin_amdgcn_readfirstlane(bi);
+}
+
+// the real game advances by one move
+__device__ __forceinline__ void slot_play(Slot &s, SelectLds &L, int action) {
+    wave_make_move(L.root, L.rhist, action, s.side, s.mc, s.nocap);
+    s.d_moves += 1;
+    s.dirty = true;
+}
+
+// arena move, MCTS.get_action(temperature=0) (mcts.py:166-174, 197-200): first maximum of the visit counts, move order
+__device__ __forceinline__ void slot_arena_move(Slot &s, SelectLds &L, int nch, int first) {
+    int bn;
+    const int bi = wave_first_max(s.T.N + first, nch, bn);
+    slot_play(s, L, __builtin_amdgcn_readfirstlane((int)s.T.A[first + bi]));
+}
+
+// FORCED: policy target pruning at a kind-1 root.  c* = first maximum of N; P* its PUCT score at the root's final
+// count, in the kind-1 float64 arithmetic of the descent; every other visited child gives back, one at a time and
+// at most while (d + 1)^2 < f_i, the visits after which its score (q held constant) would still be below P*.
+// The pruned counts go to L.w_tmp (slot_end_move's lanes read back only what they wrote here).
+__device__ __forceinline__ void wave_prune_visits(const Dev &E, Slot &s, SelectLds &L, const double *rootP, float fp_k, int nch,
+                                                  int first) {
+    const Tree &T = s.T;
+    const int lane = s.lane;
+    int bn;
+    const int p_star_i = wave_first_max(T.N + first, nch, bn);
+    const int nr = __builtin_amdgcn_readfirstlane(T.N[0]);
+    const double p_nr = (double)nr, p_sqrt = E.sqrt_tab[nr];
+    double p_star;
+    {
+        const double w = T.W[first + p_star_i];
+        double t = E.cfg.c_puct * rootP[p_star_i];
+        t = t * p_sqrt;
+        t = t / (double)(1 + bn);
+        p_star = (bn ? w / (double)bn : 0.0) + t;
+    }
+    int l_prunedv = 0, l_prunedc = 0;
+    for (int i = lane; i < nch; i += 64) {
+        int n = T.N[first + i];
+        if (i != p_star_i && n > 0) {
+            const int n0 = n;
+            const double p = rootP[i];
+            const double f = ((double)fp_k * p) * p_nr;
+            const double q = T.W[first + i] / (double)n0;
+            double e = E.cfg.c_puct * p;
+            e = e * p_sqrt;
+            int d = 0;
+            while (n > 1 && (double)(d + 1) * (double)(d + 1) < f && q + e / (double)n < p_star) { n -= 1; d += 1; }
+            if (d > 0 && n == 1) n = 0;               // reduced to a single playout: removed
+            l_prunedv += n0 - n;
+            l_prunedc += n == 0 ? 1 : 0;
+        }
+        L.w_tmp[i] = (double)n;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { l_prunedv += __shfl_xor(l_prunedv, off); l_prunedc += __shfl_xor(l_prunedc, off); }
+    s.d_prunedv += (unsigned)l_prunedv; s.d_prunedc += (unsigned)l_prunedc;
+}
+
+// End of a move: the sample (parallel_selfplay.py:97-107) and the sampled action, pi from visit counts (mcts.py:190-206).
+// full_move false (a fast move of the playout cap) stages no sample; pruned: the visits are wave_prune_visits' counts in
+// L.w_tmp.  Leaves child i's action in L.a_tmp[i]; the caller plays the returned action.
+__device__ __forceinline__ int slot_end_move(const Dev &E, Slot &s, SelectLds &L, bool full_move, bool pruned, int nch, int first) {
+    const Tree &T = s.T;
+    const int lane = s.lane;
+    const bool late = s.mc >= E.cfg.temperature_threshold;
+    const double inv_t = 1.0 / E.cfg.late_temperature;
+    uint8_t *rec = E.stage + ((size_t)s.slot * E.stage_cap + (s.n_samples < E.stage_cap ? s.n_samples : E.stage_cap - 1)) * XQ_SAMPLE_BYTES;
+    if (full_move) {
+        if (s.n_samples >= E.stage_cap) s.ovf |= 4;
+        for (int i = lane; i < XQ_SAMPLE_BYTES / 4; i += 64) ((uint32_t *)rec)[i] = 0u;
+        wave_sync_mem();
+        for (int i = lane; i < 90; i += 64) rec[i] = (uint8_t)L.root[i];
+        if (lane == 0) {
+            xq_sample *r = (xq_sample *)rec;
+            r->side = (int8_t)s.side; r->z = 0; r->n_moves = (uint8_t)nch; r->late_temp = late ? 1 : 0;
+            r->ply = (uint16_t)s.mc; r->slot = (uint32_t)s.slot; r->game_seq = (uint32_t)s.game_seq;
+        }
+    }
+    for (int i = lane; i < nch; i += 64) {
+        const int a = T.A[first + i];
+        const int n = pruned ? (int)L.w_tmp[i] : T.N[first + i];
+        if (full_move) {
+            ((xq_sample *)rec)->actions[i] = (uint16_t)a;
+            ((xq_sample *)rec)->visits[i] = (uint16_t)(n > 65535 ? 65535 : n);
+        }
+        L.a_tmp[i] = (uint16_t)a;
+        L.w_tmp[i] = late ? (n > 0 ? pow((double)n, inv_t) : 0.0) : (double)n;
+    }
+    wave_sync();
+    // np.random.choice walks the dense pi in ACTION-ID order: sort the (action, weight) pairs by id
+    for (int i = lane; i < nch; i += 64) {
+        const int a = L.a_tmp[i];
+        int rank = 0;
+        for (int j = 0; j < nch; ++j) rank += (L.a_tmp[j] < a) ? 1 : 0;
+        L.sa[rank] = (uint16_t)a;
+        L.sw[rank] = L.w_tmp[i];
+    }
+    wave_sync();
+    const double u = u64_to_unit(draw_u64(E, s.slot, RNG_UNIFORM, s.rng_ctr[RNG_UNIFORM], s.st));
+    s.rng_ctr[RNG_UNIFORM] += 1;
+    // every lane runs the same short sequential scan (LDS broadcast reads); result is wave-uniform
+    double total = 0.0;
+    for (int i = 0; i < nch; ++i) total += L.sw[i];
+    double run = 0.0;
+    for (int i = 0; i < nch; ++i) run += L.sw[i] / total;
+    const double last = run;
+    run = 0.0;
+    int pick = nch - 1;
+    for (int i = 0; i < nch; ++i) {
+        run += L.sw[i] / total;
+        if (run / last > u) { pick = i; break; }
+    }
+    if (full_move) s.n_samples += 1;
+    return __builtin_amdgcn_readfirstlane((int)L.sa[pick]);
+}
+
+// The leaf a descent ends on, and the simulated position there (its board and ring are SelectLds.board / .hist)
+struct Leaf {
+    int node, depth, side, mc, nocap;
+};
+
+// One PUCT descent (mcts.py:126-153) from the root, replaying moves on the LDS board; the nodes passed go to path[0 .. depth].
+// VL (leaf batching): each in-flight descent through a node counts as a visit and as a loss for the side choosing there (W is
+// from the chooser's view): n = N + vl in q and in 1 + n, w = W - vl, parent count N + vl; vl = 0 gives the plain values exactly.
+// FORCED: at a root of prior kind 1 a visited child below its minimum share of the root's visits scores +infinity.
+//
+// One dependent round trip to memory per level: every lane reads, with its candidate child's N / W / P, that child's own
+// node words (children count + kind, first child, action) as well, so the winner's are already in a register when the arg-max
+// is known -- the next level starts from a lane read instead of three more dependent loads (tM -> tC/tN -> ... -> tA).  The
+// winner's N, read here, IS the next level's parent count.
+template <bool VL, bool FORCED>
+__device__ __forceinline__ Leaf wave_descend(const Dev &E, Slot &s, SelectLds &L, const int32_t *vl, const double *rootP, float fp_k,
+                                             int32_t *path) {
+    const Tree &T = s.T;
+    const int lane = s.lane;
+    lds_copy_dwords(L.board, L.root, XQ_BS / 4);
+    lds_copy_dwords(L.hist, L.rhist, XQ_HIST * XQ_BS / 4);
+    wave_sync();
+    int side = s.side, mc = s.mc, nocap = s.nocap, node = 0, depth = 0;
+    if (lane == 0) path[0] = 0;
+    int m = __builtin_amdgcn_readfirstlane((int)T.M[0]);
+    int first = __builtin_amdgcn_readfirstlane(T.C[0]);
+    int pn = __builtin_amdgcn_readfirstlane(VL ? T.N[0] + vl[0] : T.N[0]);
+    for (;;) {
+        const int nch = m & 0x3FFF, kind = m >> 14;
+        if (nch == 0) break;
+        const double sqrtp = E.sqrt_tab[pn];
+        const float sqrtp_f = (float)sqrtp, c_f = (float)E.cfg.c_puct;
+        const double uni = 1.0 / (double)nch;
+        double best = -INFINITY;
+        int best_i = 0x7FFFFFFF;
+        int c_m = 0, c_first = 0, c_n = 0, c_a = 0;              // node words of this lane's best candidate
+        for (int base = 0; base < nch; base += 64) {
+            const int i = base + lane;
+            if (i < nch) {
+                int n = T.N[first + i];
+                double w = T.W[first + i];
+                if (VL) { const int v = vl[first + i]; n += v; w -= (double)v; }
+                const int cm = (int)T.M[first + i], cf = T.C[first + i], ca = (int)T.A[first + i];
+                const double q = n ? w / (double)n : 0.0;
+                double ucb;
+                if (kind == 0) {
+                    float t = c_f * T.P[first + i];
+                    t = t * sqrtp_f;
+                    t = t / (float)(1 + n);
+                    t = (float)q + t;
+                    ucb = (double)t;
+                } else {
+                    const double p = kind == 1 ? rootP[i] : uni;
+                    double t = E.cfg.c_puct * p;
+                    t = t * sqrtp;
+                    t = t / (double)(1 + n);
+                    ucb = q + t;
+                    if (FORCED && kind == 1 && n > 0 && (double)n * (double)n < ((double)fp_k * p) * (double)pn) ucb = INFINITY;
+                }
+                if (ucb > best) { best = ucb; best_i = i; c_m = cm; c_first = cf; c_n = n; c_a = ca; }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ov = __shfl_xor(best, off);
+            const int oi = __shfl_xor(best_i, off);
+            if (ov > best || (ov == best && oi < best_i)) { best = ov; best_i = oi; }
+        }
+        best_i = __builtin_amdgcn_readfirstlane(best_i);
+        if (FORCED && kind == 1 && best == INFINITY) s.d_forced += 1;   // wave-uniform after the reduction
+        s.d_scan += (unsigned)nch;
+        int action, child;
+        if (best_i == 0x7FFFFFFF) {                              // all-NaN scores: the reference would raise
+            s.ovf |= 8;
+            child = first;
+            m = __builtin_amdgcn_readfirstlane((int)T.M[child]);
+            pn = __builtin_amdgcn_readfirstlane(VL ? T.N[child] + vl[child] : T.N[child]);
+            action = __builtin_amdgcn_readfirstlane((int)T.A[child]);
+            first = __builtin_amdgcn_readfirstlane(T.C[child]);
+        } else {
+            child = first + best_i;
+            const int src = best_i & 63;                         // child i was lane i % 64's candidate, and its best (it won)
+            action = __builtin_amdgcn_readlane(c_a, src);
+            m = __builtin_amdgcn_readlane(c_m, src);
+            pn = __builtin_amdgcn_readlane(c_n, src);
+            first = __builtin_amdgcn_readlane(c_first, src);
+        }
+        wave_make_move(L.board, L.hist, action, side, mc, nocap);
+        depth += 1;
+        if (depth >= E.path_cap) { s.ovf |= 16; depth = E.path_cap - 1; }
+        if (lane == 0) path[depth] = child;
+        node = child;
+    }
+    return Leaf{node, depth, side, mc, nocap};
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -258,21 +656,21 @@ constexpr int WAVES_PER_WG = 4;
 #if XQ_SELECT_WAVES_PER_EU > 0
 #define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu(XQ_SELECT_WAVES_PER_EU, XQ_SELECT_WAVES_PER_EU)))
 #else
-// Nothing for the instances without forced playouts (0, 0 emits no attribute: they compile as they always did).  The FORCED
-// instances are held to the same two waves per SIMD: left alone, the two with CAP take 256 VGPRs plus a few AGPRs and halve
-// their occupancy.
+// Nothing for the instances without forced playouts (0, 0 emits no attribute).  The FORCED instances are held to the same two
+// waves per SIMD: left alone, the two with CAP take 256 VGPRs plus a few AGPRs and halve their occupancy.  Headroom of the
+// unpinned instances: <0,1,0> and <1,1,0> stand at 255 of the 256 VGPRs that two waves allow, the others at 244 / 245, so a
+// change to a shared helper wants the resource table regenerated (profiles/r11_shared_search_phases_kernel_resource_usage.txt).
 #define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu(FORCED ? 2 : 0, FORCED ? 2 : 0)))
 #endif
 // REUSE (tree reuse): at the end of a move the chosen child and the old allocation mark are handed to k_reroot and
-// k_expand<true> of the same step (GI_RR_NODE / GI_RR_MARK); k_select<false> is k_select as it always was.
+// k_expand<true> of the same step (GI_RR_NODE / GI_RR_MARK).
 // CAP (playout cap randomization, xq_engine_init_cap): every searched position takes one draw of the slot's uniform stream when
-// its root request is issued; u < p makes the move FULL (today's move), otherwise FAST: budget S_fast, no root noise
+// its root request is issued; u < p makes the move FULL (the move without the cap), otherwise FAST: budget S_fast, no root noise
 // (k_expand), no sample.  The kind and the budget live in GI_CAP_FULL / GI_CAP_BUDGET from the root request to the move's end.
-// k_select<.., false> is k_select as it always was.
 // FORCED (forced playouts and policy target pruning, xq_engine_init_fp): at a root of prior kind 1 -- the noisy root of a full
 // move, always node 0 -- a visited child i with N_i^2 < (k rootP[i]) N_root scores +infinity in the descent (the first maximum
 // then takes the lowest-index forced child), and at the move's end the sample's visits and the move-choice weights are the
-// PRUNED counts v_i (include/xq_hip.h); the tree keeps its N and W.  k_select<.., .., false> is k_select as it always was.
+// PRUNED counts v_i (include/xq_hip.h); the tree keeps its N and W.
 template <bool REUSE, bool CAP = false, bool FORCED = false>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev E, float *__restrict__ nn_in) {
     __shared__ SelectLds Ls[WAVES_PER_WG];
@@ -280,15 +678,13 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
     const int slot = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
     if (slot >= E.cfg.n_games) return;
     const int lane = lane_id();
-    int32_t *gi = E.gi + (size_t)slot * GI_N;
-    unsigned long long *st = E.stats + (size_t)slot * ST_N;
-    const size_t nb = (size_t)slot * E.node_cap;
-    int32_t *tN = E.tN + nb; double *tW = E.tW + nb; float *tP = E.tP + nb;
-    uint16_t *tA = E.tA + nb; int32_t *tC = E.tC + nb; uint16_t *tM = E.tM + nb;
+    Slot s;
+    s.slot = slot; s.lane = lane; s.gi = E.gi + (size_t)slot * GI_N; s.st = E.stats + (size_t)slot * ST_N; s.T = slot_tree(E, slot);
+    int32_t *gi = s.gi;
+    const Tree &T = s.T;
     int32_t *path = E.path + (size_t)slot * E.path_cap;
-    int8_t *g_board = E.board + (size_t)slot * XQ_BS;
-    int8_t *g_hist = E.hist + (size_t)slot * XQ_HIST * XQ_BS;
     uint16_t *pmoves = E.pmoves + (size_t)slot * XQ_MAXM;
+    float *x = nn_in + (size_t)slot * XQ_STATE_FLOATS;
     const double *rootP = E.rootP + (size_t)slot * XQ_MAXM;
     const int S = E.cfg.num_simulations;
     const bool manual = E.cfg.manual_moves == 1;     // search only (MCTS.search parity / serving)
@@ -303,137 +699,40 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
         return;
     }
     int req_cnt = 0;
-
-    int g_side = __builtin_amdgcn_readfirstlane(gi[GI_SIDE]);
-    int g_mc = __builtin_amdgcn_readfirstlane(gi[GI_MC]);
-    int g_nocap = __builtin_amdgcn_readfirstlane(gi[GI_NOCAP]);
-    int sims_done = __builtin_amdgcn_readfirstlane(gi[GI_SIMS]);
-    int n_samples = __builtin_amdgcn_readfirstlane(gi[GI_NSAMP]);
-    int game_seq = __builtin_amdgcn_readfirstlane(gi[GI_GSEQ]);
-    int rng_ctr[4] = {__builtin_amdgcn_readfirstlane(gi[GI_RNG0]), __builtin_amdgcn_readfirstlane(gi[GI_RNG1]),
-                      __builtin_amdgcn_readfirstlane(gi[GI_RNG2]), __builtin_amdgcn_readfirstlane(gi[GI_RNG3])};
-    int ovf = 0;
-    // per-lane stat deltas are kept wave-uniform and written by lane 0 at the end
-    unsigned long long d_sims = 0, d_term = 0, d_moves = 0, d_depth = 0, d_scan = 0;
+    slot_load(s);
     int term_run = 0;
     // CAP: the kind and budget of the move being searched.  A launch never searches a move whose root request it issued
     // itself (PH_NEWPOS ends the launch), so the words read here hold for the whole launch.
     const bool full_move = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_FULL]) != 0 : true;
     const int budget = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_BUDGET]) : S;
     unsigned long long d_fast_moves = 0, d_fast_sims = 0;
-    // FORCED: k, a float32 widened at every use; the counters of this launch (one launch runs fewer than 2^31 simulations)
+    // FORCED: k, a float32 widened at every use
     const float fp_k = FORCED ? __int_as_float(__builtin_amdgcn_readfirstlane(gi[GI_FP_K])) : 0.0f;
-    unsigned d_forced = 0, d_prunedv = 0, d_prunedc = 0;
 
-    lds_copy_dwords(L.root, g_board, XQ_BS / 4);
-    lds_copy_dwords(L.rhist, g_hist, XQ_HIST * XQ_BS / 4);
+    lds_copy_dwords(L.root, E.board + (size_t)slot * XQ_BS, XQ_BS / 4);
+    lds_copy_dwords(L.rhist, E.hist + (size_t)slot * XQ_HIST * XQ_BS, XQ_HIST * XQ_BS / 4);
     wave_sync();
 
-    bool state_dirty = false;  // real game state changed -> write back
     for (int guard = 0; guard < 4 * S + 64; ++guard) {
         if (phase == PH_FINISHED) {
-            // ---- flush the finished game's samples with z (parallel_selfplay.py:123-132) and its result
-            const int winner = __builtin_amdgcn_readfirstlane(gi[GI_FWINNER]);
-            const int reason = __builtin_amdgcn_readfirstlane(gi[GI_FREASON]);
-            unsigned base = 0;
-            bool fits = true;
-            if (n_samples > 0) {
-                if (lane == 0) base = atomicAdd(&E.cnt[0], (unsigned)n_samples);
-                base = __builtin_amdgcn_readfirstlane(base);
-                fits = (unsigned long long)base + (unsigned)n_samples <= (unsigned)E.cfg.max_out_samples;
-                if (fits) {
-                    const uint8_t *src = E.stage + (size_t)slot * E.stage_cap * XQ_SAMPLE_BYTES;
-                    uint8_t *dst = E.outs + (size_t)base * XQ_SAMPLE_BYTES;
-                    const int ndw = n_samples * (XQ_SAMPLE_BYTES / 4);
-                    for (int i = lane; i < ndw; i += 64) ((uint32_t *)dst)[i] = ((const uint32_t *)src)[i];
-                    for (int i = lane; i < n_samples; i += 64) {
-                        const int sside = ((const int8_t *)src)[(size_t)i * XQ_SAMPLE_BYTES + 90];
-                        ((int8_t *)dst)[(size_t)i * XQ_SAMPLE_BYTES + 91] = (int8_t)(winner == 0 ? 0 : (winner == sside ? 1 : -1));
-                    }
-                }
-            }
-            if (lane == 0) {
-                if (fits) st[ST_SAMP] += (unsigned)n_samples; else st[ST_DROP] += (unsigned)n_samples;
-                const unsigned r = atomicAdd(&E.cnt[1], 1u);
-                if (r < (unsigned)E.cfg.max_out_results) {
-                    xq_game_result res;
-                    res.slot = (uint32_t)slot; res.game_seq = (uint32_t)game_seq; res.winner = (int8_t)winner;
-                    res.reason = (uint8_t)reason; res.steps = (uint16_t)g_mc; res.n_samples = (uint16_t)n_samples;
-                    res.reserved = 0;
-                    *(xq_game_result *)(E.outr + (size_t)r * XQ_RESULT_BYTES) = res;
-                }
-                st[ST_GAMES] += 1;
-                st[winner == 1 ? ST_RED : (winner == -1 ? ST_BLACK : ST_DRAW)] += 1;
-                st[ST_PLIES] += (unsigned)g_mc;
-                if (reason == 3) st[ST_RESIGN] += 1;
-            }
+            slot_flush_finished(E, s);
             phase = PH_NEWGAME;
         }
         if (phase == PH_NEWGAME) {
-            // ---- new game + random opening (parallel_selfplay.py:58-72)
-            unsigned long long idx = 0;
-            if (lane == 0) idx = atomicAdd(E.started, 1ull);
-            idx = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(idx >> 32)) << 32) |
-                  (unsigned)__builtin_amdgcn_readfirstlane((unsigned)idx);
-            if (E.cfg.games_target > 0 && idx >= (unsigned long long)E.cfg.games_target) { phase = PH_IDLE; break; }
-            game_seq += 1;
-            n_samples = 0;
-            init_board_lds(L.root);
-            g_side = 1; g_mc = 0; g_nocap = 0;
-            if (lane == 0) { gi[GI_RESIGN_N] = 0; st[ST_STARTED] += 1; }
+            if (!slot_new_game(E, s, L, arena)) { phase = PH_IDLE; break; }
             if (REUSE && lane == 0) gi[GI_RR_NODE] = 0;     // a new game never sees a hand-off
-            wave_sync();
-            const int R = arena ? 0 : E.cfg.random_opening_moves;
-            const int k = R > 0 ? (int)(draw_u64(E, slot, RNG_RANDINT, rng_ctr[RNG_RANDINT], st) % (uint64_t)(R + 1)) : 0;
-            if (!arena) rng_ctr[RNG_RANDINT] += 1;   // random.randint is called even when R == 0
-            for (int i = 0; i < k; ++i) {
-                const int cnt = wave_movegen(L.root, g_side, L.mg, L.moves, &ovf);
-                if (cnt == 0) break;
-                const int pick = (int)(draw_u64(E, slot, RNG_CHOICE, rng_ctr[RNG_CHOICE], st) % (uint64_t)cnt);
-                rng_ctr[RNG_CHOICE] += 1;
-                const int action = L.moves[pick];
-                wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
-                int c2, w2;
-                if (wave_game_over(L.root, L.rhist, g_side, g_mc, g_nocap, L.mg, L.moves, &c2, &w2, &ovf)) {
-                    init_board_lds(L.root);
-                    g_side = 1; g_mc = 0; g_nocap = 0;
-                    wave_sync();
-                    break;
-                }
-            }
-            state_dirty = true;
             phase = PH_NEWPOS;
         }
         if (phase == PH_NEWPOS) {
-            // ---- root request: terminal status of the real position + its planes + its ordered legal moves
-            int cnt, winner;
-            int status = 0;
-            const bool done = wave_game_over(L.root, L.rhist, g_side, g_mc, g_nocap, L.mg, L.moves, &cnt, &winner, &ovf);
-            if (done) status = 1;
-            else if (arena && g_mc >= E.cfg.max_game_length) {     // train.py:477,494-496: not over after max plies => draw
-                winner = 0;
-                status = 2;
-            } else if (!manual && !arena && g_mc >= E.cfg.max_game_length) {   // parallel_selfplay.py:79-89
-                int red, black;
-                wave_material(L.root, red, black);
-                const int diff = red - black;
-                winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
-                status = 2;
-            }
-            wave_encode(L.root, g_side, nn_in + (size_t)slot * XQ_STATE_FLOATS);
-            for (int j = lane; j < cnt; j += 64) pmoves[j] = L.moves[j];
-            if (lane == 0) {
-                gi[GI_PCOUNT] = cnt; gi[GI_RSTATUS] = status; gi[GI_RWINNER] = winner;
-                gi[GI_ALLOC] = 1;
-                tN[0] = 0; tW[0] = 0.0; tC[0] = -1; tM[0] = 0; tA[0] = 0; tP[0] = 0.0f;
-            }
+            int status;
+            req_cnt = slot_root_request(E, s, L, manual, arena, x, pmoves, status);
             if (REUSE && lane == 0) gi[GI_RR_DROP] = 0;      // this move's tree is grown under the current weights
             if (CAP) {
                 // the cap draw: one uniform per position that will be searched, ahead of that move's move-choice draw
                 bool full = true;
                 if (status == 0) {
-                    const double u = u64_to_unit(draw_u64(E, slot, RNG_UNIFORM, rng_ctr[RNG_UNIFORM], st));
-                    rng_ctr[RNG_UNIFORM] += 1;
+                    const double u = u64_to_unit(draw_u64(E, slot, RNG_UNIFORM, s.rng_ctr[RNG_UNIFORM], s.st));
+                    s.rng_ctr[RNG_UNIFORM] += 1;
                     const unsigned long long pb = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(gi[GI_CAP_PHI]) << 32) |
                                                   (unsigned)__builtin_amdgcn_readfirstlane(gi[GI_CAP_PLO]);
                     full = u < __longlong_as_double((long long)pb);
@@ -441,142 +740,19 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                 const int sfast = __builtin_amdgcn_readfirstlane(gi[GI_CAP_SFAST]);
                 if (lane == 0) { gi[GI_CAP_FULL] = full ? 1 : 0; gi[GI_CAP_BUDGET] = full ? S : sfast; }
             }
-            sims_done = 0;
-            req_cnt = cnt;
             phase = PH_WAIT_ROOT;
             break;
         }
         // ---- phase == PH_SEARCH
-        if (sims_done >= budget) {
+        if (s.sims_done >= budget) {
             if (manual) { phase = PH_HOLD; break; }
-            const int nch = __builtin_amdgcn_readfirstlane((int)(tM[0] & 0x3FFF));
-            const int first = __builtin_amdgcn_readfirstlane(tC[0]);
-            if (arena) {
-                // MCTS.get_action(temperature=0) (mcts.py:166-174, 197-200): first maximum of the visit counts, move order
-                int bn = -1, bi = 0x7FFFFFFF;
-                for (int i = lane; i < nch; i += 64) {
-                    const int n = tN[first + i];
-                    if (n > bn) { bn = n; bi = i; }
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
-                    if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
-                }
-                bi = __builtin_amdgcn_readfirstlane(bi);
-                const int action = __builtin_amdgcn_readfirstlane((int)tA[first + bi]);
-                wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
-                d_moves += 1;
-                state_dirty = true;
-                phase = PH_NEWPOS;
-                continue;
-            }
-            // ---- end of move: sample (parallel_selfplay.py:97-107), pi from visit counts (mcts.py:190-206)
-            const bool late = g_mc >= E.cfg.temperature_threshold;
-            const double inv_t = 1.0 / E.cfg.late_temperature;
-            uint8_t *rec = E.stage + ((size_t)slot * E.stage_cap + (n_samples < E.stage_cap ? n_samples : E.stage_cap - 1)) * XQ_SAMPLE_BYTES;
-            if (full_move) {                                  // a fast move stages no sample
-                if (n_samples >= E.stage_cap) ovf |= 4;
-                for (int i = lane; i < XQ_SAMPLE_BYTES / 4; i += 64) ((uint32_t *)rec)[i] = 0u;
-                wave_sync_mem();
-                for (int i = lane; i < 90; i += 64) rec[i] = (uint8_t)L.root[i];
-                if (lane == 0) {
-                    xq_sample *s = (xq_sample *)rec;
-                    s->side = (int8_t)g_side; s->z = 0; s->n_moves = (uint8_t)nch; s->late_temp = late ? 1 : 0;
-                    s->ply = (uint16_t)g_mc; s->slot = (uint32_t)slot; s->game_seq = (uint32_t)game_seq;
-                }
-            }
-            // FORCED: policy target pruning at a kind-1 root.  c* = first maximum of N; P* its PUCT score at the root's final
-            // count, in the kind-1 float64 arithmetic of the descent; every other visited child gives back, one at a time and
-            // at most while (d + 1)^2 < f_i, the visits after which its score (q held constant) would still be below P*.
-            // The pruned counts go through L.w_tmp (every lane reads back only what it wrote), so that nothing of this block is
-            // live in the staging loop below.
-            bool prune = false;
-            if (FORCED && (__builtin_amdgcn_readfirstlane((int)tM[0]) >> 14) == 1) {
-                prune = true;
-                int bn = -1, bi = 0x7FFFFFFF;
-                for (int i = lane; i < nch; i += 64) {
-                    const int n = tN[first + i];
-                    if (n > bn) { bn = n; bi = i; }
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
-                    if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
-                }
-                const int p_star_i = __builtin_amdgcn_readfirstlane(bi);
-                bn = __builtin_amdgcn_readfirstlane(bn);
-                const int nr = __builtin_amdgcn_readfirstlane(tN[0]);
-                const double p_nr = (double)nr, p_sqrt = E.sqrt_tab[nr];
-                double p_star;
-                {
-                    const double w = tW[first + p_star_i];
-                    double t = E.cfg.c_puct * rootP[p_star_i];
-                    t = t * p_sqrt;
-                    t = t / (double)(1 + bn);
-                    p_star = (bn ? w / (double)bn : 0.0) + t;
-                }
-                int l_prunedv = 0, l_prunedc = 0;
-                for (int i = lane; i < nch; i += 64) {
-                    int n = tN[first + i];
-                    if (i != p_star_i && n > 0) {
-                        const int n0 = n;
-                        const double p = rootP[i];
-                        const double f = ((double)fp_k * p) * p_nr;
-                        const double q = tW[first + i] / (double)n0;
-                        double e = E.cfg.c_puct * p;
-                        e = e * p_sqrt;
-                        int d = 0;
-                        while (n > 1 && (double)(d + 1) * (double)(d + 1) < f && q + e / (double)n < p_star) { n -= 1; d += 1; }
-                        if (d > 0 && n == 1) n = 0;               // reduced to a single playout: removed
-                        l_prunedv += n0 - n;
-                        l_prunedc += n == 0 ? 1 : 0;
-                    }
-                    L.w_tmp[i] = (double)n;
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) { l_prunedv += __shfl_xor(l_prunedv, off); l_prunedc += __shfl_xor(l_prunedc, off); }
-                d_prunedv += (unsigned)l_prunedv; d_prunedc += (unsigned)l_prunedc;
-            }
-            for (int i = lane; i < nch; i += 64) {
-                const int a = tA[first + i];
-                const int n = (FORCED && prune) ? (int)L.w_tmp[i] : tN[first + i];
-                if (full_move) {
-                    ((xq_sample *)rec)->actions[i] = (uint16_t)a;
-                    ((xq_sample *)rec)->visits[i] = (uint16_t)(n > 65535 ? 65535 : n);
-                }
-                L.a_tmp[i] = (uint16_t)a;
-                L.w_tmp[i] = late ? (n > 0 ? pow((double)n, inv_t) : 0.0) : (double)n;
-            }
-            wave_sync();
-            // np.random.choice walks the dense pi in ACTION-ID order: sort the (action, weight) pairs by id
-            for (int i = lane; i < nch; i += 64) {
-                const int a = L.a_tmp[i];
-                int rank = 0;
-                for (int j = 0; j < nch; ++j) rank += (L.a_tmp[j] < a) ? 1 : 0;
-                L.sa[rank] = (uint16_t)a;
-                L.sw[rank] = L.w_tmp[i];
-            }
-            wave_sync();
-            const double u = u64_to_unit(draw_u64(E, slot, RNG_UNIFORM, rng_ctr[RNG_UNIFORM], st));
-            rng_ctr[RNG_UNIFORM] += 1;
-            int action = 0;
-            {
-                // every lane runs the same short sequential scan (LDS broadcast reads); result is wave-uniform
-                double total = 0.0;
-                for (int i = 0; i < nch; ++i) total += L.sw[i];
-                double run = 0.0;
-                for (int i = 0; i < nch; ++i) run += L.sw[i] / total;
-                const double last = run;
-                run = 0.0;
-                int pick = nch - 1;
-                for (int i = 0; i < nch; ++i) {
-                    run += L.sw[i] / total;
-                    if (run / last > u) { pick = i; break; }
-                }
-                action = L.sa[pick];
-            }
-            action = __builtin_amdgcn_readfirstlane(action);
+            const int nch = __builtin_amdgcn_readfirstlane((int)(T.M[0] & 0x3FFF));
+            const int first = __builtin_amdgcn_readfirstlane(T.C[0]);
+            phase = PH_NEWPOS;
+            if (arena) { slot_arena_move(s, L, nch, first); continue; }
+            const bool pruned = FORCED && (__builtin_amdgcn_readfirstlane((int)T.M[0]) >> 14) == 1;
+            if (pruned) wave_prune_visits(E, s, L, rootP, fp_k, nch, first);
+            const int action = slot_end_move(E, s, L, full_move, pruned, nch, first);
             if (REUSE) {
                 // hand the chosen child c to k_reroot / k_expand<true> of this step when it was expanded and no drop
                 // (xq_engine_drop_reroots) ran since this move began; L.a_tmp[i] is child i's action
@@ -586,111 +762,23 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                     if (b) { c = first + base + (int)__builtin_ctzll(b); break; }
                 }
                 c = __builtin_amdgcn_readfirstlane(c);
-                const bool keep = c > 0 && __builtin_amdgcn_readfirstlane(tC[c]) >= 0 &&
+                const bool keep = c > 0 && __builtin_amdgcn_readfirstlane(T.C[c]) >= 0 &&
                                   __builtin_amdgcn_readfirstlane(gi[GI_RR_DROP]) == 0;
                 if (lane == 0) { gi[GI_RR_NODE] = keep ? c : 0; gi[GI_RR_MARK] = keep ? gi[GI_ALLOC] : 0; }
             }
-            wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
-            if (full_move) n_samples += 1; else d_fast_moves += 1;
-            d_moves += 1;
-            state_dirty = true;
-            phase = PH_NEWPOS;
+            slot_play(s, L, action);
+            if (CAP && !full_move) d_fast_moves += 1;
             continue;
         }
-        // ---- one simulation (mcts.py:126-153): descend from the root replaying moves on the LDS board
-        lds_copy_dwords(L.board, L.root, XQ_BS / 4);
-        lds_copy_dwords(L.hist, L.rhist, XQ_HIST * XQ_BS / 4);
-        wave_sync();
-        int side = g_side, mc = g_mc, nocap = g_nocap, node = 0, depth = 0;
-        if (lane == 0) path[0] = 0;
-        // One dependent round trip to memory per level: every lane reads, with its candidate child's N / W / P, that child's own
-        // node words (children count + kind, first child, action) as well, so the winner's are already in a register when the arg-max
-        // is known -- the next level starts from a lane read instead of three more dependent loads (tM -> tC/tN -> ... -> tA).  The
-        // winner's N, read here, IS the next level's parent count.  Same values, same arithmetic, same order as before.
-        int m = __builtin_amdgcn_readfirstlane((int)tM[0]);
-        int first = __builtin_amdgcn_readfirstlane(tC[0]);
-        int pn = __builtin_amdgcn_readfirstlane(tN[0]);
-        for (;;) {
-            const int nch = m & 0x3FFF, kind = m >> 14;
-            if (nch == 0) break;
-            const double sqrtp = E.sqrt_tab[pn];
-            const float sqrtp_f = (float)sqrtp, c_f = (float)E.cfg.c_puct;
-            const double uni = 1.0 / (double)nch;
-            double best = -INFINITY;
-            int best_i = 0x7FFFFFFF;
-            int c_m = 0, c_first = 0, c_n = 0, c_a = 0;              // node words of this lane's best candidate
-            for (int base = 0; base < nch; base += 64) {
-                const int i = base + lane;
-                if (i < nch) {
-                    const int n = tN[first + i];
-                    const double w = tW[first + i];
-                    const int cm = (int)tM[first + i], cf = tC[first + i], ca = (int)tA[first + i];
-                    const double q = n ? w / (double)n : 0.0;
-                    double ucb;
-                    if (kind == 0) {
-                        float t = c_f * tP[first + i];
-                        t = t * sqrtp_f;
-                        t = t / (float)(1 + n);
-                        t = (float)q + t;
-                        ucb = (double)t;
-                    } else {
-                        const double p = kind == 1 ? rootP[i] : uni;
-                        double t = E.cfg.c_puct * p;
-                        t = t * sqrtp;
-                        t = t / (double)(1 + n);
-                        ucb = q + t;
-                        // forced playout: a visited child of the noisy root below its minimum share of the root's visits
-                        if (FORCED && kind == 1 && n > 0 && (double)n * (double)n < ((double)fp_k * p) * (double)pn) ucb = INFINITY;
-                    }
-                    if (ucb > best) { best = ucb; best_i = i; c_m = cm; c_first = cf; c_n = n; c_a = ca; }
-                }
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const double ov = __shfl_xor(best, off);
-                const int oi = __shfl_xor(best_i, off);
-                if (ov > best || (ov == best && oi < best_i)) { best = ov; best_i = oi; }
-            }
-            best_i = __builtin_amdgcn_readfirstlane(best_i);
-            if (FORCED && kind == 1 && best == INFINITY) d_forced += 1;   // wave-uniform after the reduction
-            int action;
-            if (best_i == 0x7FFFFFFF) {                              // all-NaN scores: the reference would raise
-                ovf |= 8; best_i = 0;
-                m = __builtin_amdgcn_readfirstlane((int)tM[first]);
-                pn = __builtin_amdgcn_readfirstlane(tN[first]);
-                action = __builtin_amdgcn_readfirstlane((int)tA[first]);
-                const int nf = __builtin_amdgcn_readfirstlane(tC[first]);
-                d_scan += (unsigned)nch;
-                const int child0 = first;
-                first = nf;
-                wave_make_move(L.board, L.hist, action, side, mc, nocap);
-                depth += 1;
-                if (depth >= E.path_cap) { ovf |= 16; depth = E.path_cap - 1; }
-                if (lane == 0) path[depth] = child0;
-                node = child0;
-                continue;
-            }
-            d_scan += (unsigned)nch;
-            const int child = first + best_i;
-            const int src = best_i & 63;                              // child i was lane i % 64's candidate, and its best (it won)
-            action = __builtin_amdgcn_readlane(c_a, src);
-            m = __builtin_amdgcn_readlane(c_m, src);
-            pn = __builtin_amdgcn_readlane(c_n, src);
-            first = __builtin_amdgcn_readlane(c_first, src);
-            wave_make_move(L.board, L.hist, action, side, mc, nocap);
-            depth += 1;
-            if (depth >= E.path_cap) { ovf |= 16; depth = E.path_cap - 1; }
-            if (lane == 0) path[depth] = child;
-            node = child;
-        }
-        d_depth += (unsigned)depth;
+        const Leaf lf = wave_descend<false, FORCED>(E, s, L, nullptr, rootP, fp_k, path);
+        s.d_depth += (unsigned)lf.depth;
         int cnt, winner;
-        const bool term = wave_game_over(L.board, L.hist, side, mc, nocap, L.mg, L.moves, &cnt, &winner, &ovf);
+        const bool term = wave_game_over(L.board, L.hist, lf.side, lf.mc, lf.nocap, L.mg, L.moves, &cnt, &winner, &s.ovf);
         if (term) {
             wave_sync_mem();   // path[] stores of lane 0 must be visible to the other lanes
-            wave_backup(tN, tW, path, depth, winner == 0 ? 0.0 : 1.0);   // mcts.py:137-140
+            wave_backup<false>(T, nullptr, path, lf.depth, winner == 0 ? 0.0 : 1.0);   // mcts.py:137-140
             wave_sync_mem();   // the next descent reads N/W written here by other lanes
-            sims_done += 1; d_sims += 1; d_term += 1;
+            s.sims_done += 1; s.d_sims += 1; s.d_term += 1;
             if (CAP && !full_move) d_fast_sims += 1;
             // A root with a mating reply re-tests that terminal child on every visit (as mcts.py does); bound how
             // many such simulations one launch runs so a single slot cannot stretch the step (it resumes next step
@@ -698,114 +786,69 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
             if (++term_run >= 48) break;
             continue;
         }
-        wave_encode(L.board, side, nn_in + (size_t)slot * XQ_STATE_FLOATS);
+        wave_encode(L.board, lf.side, x);
         for (int j = lane; j < cnt; j += 64) pmoves[j] = L.moves[j];
-        if (lane == 0) { gi[GI_PLEAF] = node; gi[GI_PDEPTH] = depth; gi[GI_PCOUNT] = cnt; }
+        if (lane == 0) { gi[GI_PLEAF] = lf.node; gi[GI_PDEPTH] = lf.depth; gi[GI_PCOUNT] = cnt; }
         req_cnt = cnt;
         phase = PH_WAIT_LEAF;
         break;
     }
 
-    if (state_dirty) {
-        lds_copy_dwords(g_board, L.root, XQ_BS / 4);
-        lds_copy_dwords(g_hist, L.rhist, XQ_HIST * XQ_BS / 4);
-    }
+    slot_store(E, s, L, phase);
     if (lane == 0) {
         E.req[slot] = (phase == PH_WAIT_ROOT || phase == PH_WAIT_LEAF) ? req_cnt : 0;
-        gi[GI_SIDE] = g_side; gi[GI_MC] = g_mc; gi[GI_NOCAP] = g_nocap; gi[GI_PHASE] = phase; gi[GI_SIMS] = sims_done;
-        gi[GI_NSAMP] = n_samples; gi[GI_GSEQ] = game_seq;
-        gi[GI_RNG0] = rng_ctr[0]; gi[GI_RNG1] = rng_ctr[1]; gi[GI_RNG2] = rng_ctr[2]; gi[GI_RNG3] = rng_ctr[3];
-        st[ST_SIMS] += d_sims; st[ST_TERM] += d_term; st[ST_MOVES] += d_moves; st[ST_DEPTH] += d_depth; st[ST_SCAN] += d_scan;
-        if (CAP) { st[ST_FASTM] += d_fast_moves; st[ST_FASTS] += d_fast_sims; }
-        if (FORCED) { st[ST_FORCED] += d_forced; st[ST_PRUNEDV] += d_prunedv; st[ST_PRUNEDC] += d_prunedc; }
-        if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8;
+        if (CAP) { s.st[ST_FASTM] += d_fast_moves; s.st[ST_FASTS] += d_fast_sims; }
+        if (FORCED) { s.st[ST_FORCED] += s.d_forced; s.st[ST_PRUNEDV] += s.d_prunedv; s.st[ST_PRUNEDC] += s.d_prunedc; }
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The pieces of the expand kernels (k_expand<REUSE, CAP> and k_expand_multi), one copy each.
 struct ExpandLds {
     float p[XQ_MAXM];
     double eta[XQ_MAXM];
     uint16_t act[XQ_MAXM];
 };
 
-// one game per 64-thread workgroup: this kernel streams 32 KB of logits per game and measured faster with more,
-// smaller workgroups in flight (0.111 vs 0.132 ms at G = 8192) than with four games per workgroup
-// REUSE (k_expand<true>): a root request of a slot that k_select<true> handed a chosen child to (GI_RR_NODE; k_reroot has moved
-// that child's subtree to the front of the arena) keeps the children, their N, W, first-child and meta words, rewrites their
-// float32 priors, draws fresh noise into rootP and starts the search at sims_done = root N = the sum of their visits.
-// CAP (k_expand<.., true>): the root of a fast move (GI_CAP_FULL == 0) takes the no-noise path: no Dirichlet draw, rootP unused,
-// prior kind 0 (or 2), also when it is a reused root; a leaf backed up under a fast move counts in ST_FASTS.
-template <bool REUSE, bool CAP = false>
-__global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ policy, const float *__restrict__ value,
-                                               int is_probs) {
-    __shared__ ExpandLds L;
-    const int slot = blockIdx.x;
-    if (slot >= E.cfg.n_games) return;
+// A root's evaluation has arrived: the resign probe on the position after the move (parallel_selfplay.py:110-121), then the
+// position's own terminal status.  True: the game (a manual search: the slot) ends here and the root is not expanded.
+__device__ __forceinline__ bool expand_root_finish(const Dev &E, int32_t *gi, unsigned long long *st, int slot, double v_net) {
     const int lane = lane_id();
-    int32_t *gi = E.gi + (size_t)slot * GI_N;
-    unsigned long long *st = E.stats + (size_t)slot * ST_N;
-    int phase = __builtin_amdgcn_readfirstlane(gi[GI_PHASE]);
-    if (phase != PH_WAIT_ROOT && phase != PH_WAIT_LEAF) return;
-    const size_t nb = (size_t)slot * E.node_cap;
-    int32_t *tN = E.tN + nb; double *tW = E.tW + nb; float *tP = E.tP + nb;
-    uint16_t *tA = E.tA + nb; int32_t *tC = E.tC + nb; uint16_t *tM = E.tM + nb;
-    const int32_t *path = E.path + (size_t)slot * E.path_cap;
-    const uint16_t *pmoves = E.pmoves + (size_t)slot * XQ_MAXM;
-    double *rootP = E.rootP + (size_t)slot * XQ_MAXM;
-    const bool manual = E.cfg.manual_moves == 1;
-    const bool arena = E.cfg.manual_moves == 2;
-    const bool is_root = phase == PH_WAIT_ROOT;
-    const double v_net = (double)value[slot];        // tensor.item(): float32 widened
-    const int cnt = __builtin_amdgcn_readfirstlane(gi[GI_PCOUNT]);
-    int sims_done = __builtin_amdgcn_readfirstlane(gi[GI_SIMS]);
-    int ovf = 0;
-    int rr = 0;                                       // REUSE: the re-rooted child of this step's hand-off (0: none)
-
-    if (is_root) {
-        if (REUSE) {
-            rr = __builtin_amdgcn_readfirstlane(gi[GI_RR_NODE]);
-            // consumed: a hand-off lives for one step.  The store depends on rr: the word is read by a scalar load, and a
-            // vector store issued before that load returns could overtake it (the load would then see the cleared word)
-            if (rr != 0 && lane == 0) gi[GI_RR_NODE] = 0;
+    const bool manual = E.cfg.manual_moves == 1, arena = E.cfg.manual_moves == 2;
+    if (lane == 0) st[ST_ROOT] += 1;
+    const int side = gi[GI_SIDE];
+    int fin = 0, fwinner = 0, freason = 0;
+    if (!manual && !arena && E.cfg.enable_resign && gi[GI_NSAMP] > 10) {
+        const int K = E.cfg.resign_check_steps;
+        double *rh = E.resign + (size_t)slot * 16;
+        int rn = gi[GI_RESIGN_N];
+        wave_sync_mem();
+        if (lane == 0) { rh[rn % 16] = v_net; gi[GI_RESIGN_N] = rn + 1; }
+        wave_sync_mem();
+        rn += 1;
+        if (rn >= K) {
+            bool all_low = true;
+            for (int i = rn - K; i < rn; ++i) all_low = all_low && (rh[i % 16] < E.cfg.resign_threshold);
+            if (all_low) { fin = 1; fwinner = -side; freason = 3; }
         }
-        if (lane == 0) st[ST_ROOT] += 1;
-        const int side = gi[GI_SIDE];
-        int fin = 0, fwinner = 0, freason = 0;
-        // resign probe on the position after the move (parallel_selfplay.py:110-121)
-        if (!manual && !arena && E.cfg.enable_resign && gi[GI_NSAMP] > 10) {
-            const int K = E.cfg.resign_check_steps;
-            double *rh = E.resign + (size_t)slot * 16;
-            int rn = gi[GI_RESIGN_N];
-            wave_sync_mem();
-            if (lane == 0) { rh[rn % 16] = v_net; gi[GI_RESIGN_N] = rn + 1; }
-            wave_sync_mem();
-            rn += 1;
-            if (rn >= K) {
-                bool all_low = true;
-                for (int i = rn - K; i < rn; ++i) all_low = all_low && (rh[i % 16] < E.cfg.resign_threshold);
-                if (all_low) { fin = 1; fwinner = -side; freason = 3; }
-            }
-        }
-        const int rstatus = gi[GI_RSTATUS];
-        if (!fin && rstatus != 0) { fin = 1; fwinner = gi[GI_RWINNER]; freason = rstatus; }
-        fin = __builtin_amdgcn_readfirstlane(fin);
-        if (fin) {
-            if (lane == 0) {
-                gi[GI_FWINNER] = fwinner; gi[GI_FREASON] = freason;
-                gi[GI_PHASE] = manual ? PH_HOLD : PH_FINISHED;
-            }
-            return;
-        }
-    } else {
-        if (lane == 0) st[ST_LEAF] += 1;
     }
+    const int rstatus = gi[GI_RSTATUS];
+    if (!fin && rstatus != 0) { fin = 1; fwinner = gi[GI_RWINNER]; freason = rstatus; }
+    fin = __builtin_amdgcn_readfirstlane(fin);
+    if (fin && lane == 0) {
+        gi[GI_FWINNER] = fwinner; gi[GI_FREASON] = freason;
+        gi[GI_PHASE] = manual ? PH_HOLD : PH_FINISHED;
+    }
+    return fin != 0;
+}
 
-    // ---- priors of the legal moves: softmax over ALL 8100 logits (model.py:122), then mcts.py:176-188
-    // is_probs: 0 logits over all 8100 actions, 1 probabilities over all 8100, 2 logits of the legal moves only
-    // ([G][XQ_MAXM], move order): softmax over the legal logits -- the common factor of the full softmax cancels in
-    // mcts.py:176-188's renormalisation
-    const float *pol = policy + (size_t)slot * (is_probs == 2 ? XQ_MAXM : XQ_ACTION_SPACE);
+// Unnormalised priors of the cnt legal moves into L.p (their actions into L.act): softmax over ALL 8100 logits (model.py:122),
+// to be normalised as mcts.py:176-188 by the returned builtin sum() (sequential float32, move order).
+// is_probs: 0 logits over all 8100 actions, 1 probabilities over all 8100, 2 logits of the legal moves only
+// ([XQ_MAXM], move order): softmax over the legal logits -- the common factor of the full softmax cancels in
+// mcts.py:176-188's renormalisation
+__device__ __forceinline__ float wave_priors(ExpandLds &L, const float *pol, const uint16_t *pmoves, int cnt, int is_probs) {
+    const int lane = lane_id();
     float mx = 0.0f, den = 1.0f;
     if (is_probs == 2) {
         float m = -INFINITY;
@@ -839,36 +882,120 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
     }
     wave_sync();
     float sum = 0.0f;
-    for (int i = 0; i < cnt; ++i) sum = sum + L.p[i];      // builtin sum(): sequential float32, move order
+    for (int i = 0; i < cnt; ++i) sum = sum + L.p[i];
+    return sum;
+}
 
-    const bool full_move = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_FULL]) != 0 : true;
-    const bool noisy = is_root && full_move && (E.cfg.add_noise != 0 || gi[GI_MANNOISE] != 0);
-    if (noisy) {
-        // eta ~ Dirichlet(alpha) over the legal moves, in move order
-        if (gi[GI_MANNOISE] != 0) {
-            const double *mn = E.mnoise + (size_t)slot * XQ_MAXM;
-            for (int i = lane; i < cnt; i += 64) L.eta[i] = mn[i];
-        } else {
-            const int ctr0 = gi[GI_RNG0 + RNG_DIRICHLET];
-            for (int i = lane; i < cnt; i += 64) {
-                double g;
-                if (E.cfg.inject_len > 0) {           // tests/draws.py Draws.dirichlet: w = (1 + (u>>40)%4096)^3
-                    const double w = (double)(1 + (int)((draw_u64(E, slot, RNG_DIRICHLET, ctr0 + i, st) >> 40) % 4096ull));
-                    g = w * w * w;
-                } else {
-                    g = gamma_variate(E, slot, ctr0 + i, E.cfg.dirichlet_alpha);
-                }
-                L.eta[i] = g;
+// eta ~ Dirichlet(alpha) over the legal moves, in move order, into L.eta (mcts.py:117-121); or the noise set by hand
+__device__ __forceinline__ void wave_root_noise(const Dev &E, ExpandLds &L, int32_t *gi, unsigned long long *st, int slot, int cnt) {
+    const int lane = lane_id();
+    if (gi[GI_MANNOISE] != 0) {
+        const double *mn = E.mnoise + (size_t)slot * XQ_MAXM;
+        for (int i = lane; i < cnt; i += 64) L.eta[i] = mn[i];
+    } else {
+        const int ctr0 = gi[GI_RNG0 + RNG_DIRICHLET];
+        for (int i = lane; i < cnt; i += 64) {
+            double g;
+            if (E.cfg.inject_len > 0) {           // tests/draws.py Draws.dirichlet: w = (1 + (u>>40)%4096)^3
+                const double w = (double)(1 + (int)((draw_u64(E, slot, RNG_DIRICHLET, ctr0 + i, st) >> 40) % 4096ull));
+                g = w * w * w;
+            } else {
+                g = gamma_variate(E, slot, ctr0 + i, E.cfg.dirichlet_alpha);
             }
-            wave_sync();
-            double tot = 0.0;
-            for (int i = 0; i < cnt; ++i) tot += L.eta[i];
-            wave_sync();
-            for (int i = lane; i < cnt; i += 64) L.eta[i] = L.eta[i] / tot;
-            if (lane == 0) gi[GI_RNG0 + RNG_DIRICHLET] = ctr0 + cnt;
+            L.eta[i] = g;
         }
         wave_sync();
+        double tot = 0.0;
+        for (int i = 0; i < cnt; ++i) tot += L.eta[i];
+        wave_sync();
+        for (int i = lane; i < cnt; i += 64) L.eta[i] = L.eta[i] / tot;
+        if (lane == 0) gi[GI_RNG0 + RNG_DIRICHLET] = ctr0 + cnt;
     }
+    wave_sync();
+}
+
+// The float32 priors of the children at tP[0 .. cnt) and, at a noisy root, the float64 mixed priors in rootP.  Returns the
+// node's prior kind: 0 float32 priors, 1 rootP, 2 uniform (the network gave the legal moves no mass).
+__device__ __forceinline__ int wave_write_priors(const Dev &E, const ExpandLds &L, float *tP, double *rootP, int cnt, float sum,
+                                                 bool noisy) {
+    const int lane = lane_id();
+    const double eps = E.cfg.noise_eps;
+    const float keep_f = (float)(1.0 - eps);
+    if (sum > 0.0f) {
+        for (int i = lane; i < cnt; i += 64) {
+            const float pr = L.p[i] / sum;
+            if (noisy) { const float sc = keep_f * pr; rootP[i] = (double)sc + eps * L.eta[i]; }
+            tP[i] = pr;
+        }
+        return noisy ? 1 : 0;
+    }
+    const double uni = 1.0 / (double)cnt;
+    for (int i = lane; i < cnt; i += 64) {
+        if (noisy) rootP[i] = (1.0 - eps) * uni + eps * L.eta[i];
+        tP[i] = (float)uni;
+    }
+    return noisy ? 1 : 2;
+}
+
+// fresh children of `node` at [first, first + cnt), in move order
+__device__ __forceinline__ void wave_new_children(const Tree &T, const ExpandLds &L, unsigned long long *st, int node, int first,
+                                                  int cnt, int kind) {
+    const int lane = lane_id();
+    for (int i = lane; i < cnt; i += 64) {
+        T.N[first + i] = 0; T.W[first + i] = 0.0; T.A[first + i] = L.act[i]; T.C[first + i] = -1; T.M[first + i] = 0;
+    }
+    if (lane == 0) {
+        T.C[node] = first; T.M[node] = (uint16_t)(cnt | (kind << 14));
+        st[ST_NODES] += (unsigned)cnt;
+    }
+}
+
+// one game per 64-thread workgroup: this kernel streams 32 KB of logits per game and measured faster with more,
+// smaller workgroups in flight (0.111 vs 0.132 ms at G = 8192) than with four games per workgroup
+// REUSE (k_expand<true>): a root request of a slot that k_select<true> handed a chosen child to (GI_RR_NODE; k_reroot has moved
+// that child's subtree to the front of the arena) keeps the children, their N, W, first-child and meta words, rewrites their
+// float32 priors, draws fresh noise into rootP and starts the search at sims_done = root N = the sum of their visits.
+// CAP (k_expand<.., true>): the root of a fast move (GI_CAP_FULL == 0) takes the no-noise path: no Dirichlet draw, rootP unused,
+// prior kind 0 (or 2), also when it is a reused root; a leaf backed up under a fast move counts in ST_FASTS.
+template <bool REUSE, bool CAP = false>
+__global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ policy, const float *__restrict__ value,
+                                               int is_probs) {
+    __shared__ ExpandLds L;
+    const int slot = blockIdx.x;
+    if (slot >= E.cfg.n_games) return;
+    const int lane = lane_id();
+    int32_t *gi = E.gi + (size_t)slot * GI_N;
+    unsigned long long *st = E.stats + (size_t)slot * ST_N;
+    int phase = __builtin_amdgcn_readfirstlane(gi[GI_PHASE]);
+    if (phase != PH_WAIT_ROOT && phase != PH_WAIT_LEAF) return;
+    const Tree T = slot_tree(E, slot);
+    const int32_t *path = E.path + (size_t)slot * E.path_cap;
+    const uint16_t *pmoves = E.pmoves + (size_t)slot * XQ_MAXM;
+    double *rootP = E.rootP + (size_t)slot * XQ_MAXM;
+    const bool manual = E.cfg.manual_moves == 1;
+    const bool is_root = phase == PH_WAIT_ROOT;
+    const double v_net = (double)value[slot];        // tensor.item(): float32 widened
+    const int cnt = __builtin_amdgcn_readfirstlane(gi[GI_PCOUNT]);
+    int sims_done = __builtin_amdgcn_readfirstlane(gi[GI_SIMS]);
+    int ovf = 0;
+    int rr = 0;                                       // REUSE: the re-rooted child of this step's hand-off (0: none)
+
+    if (is_root) {
+        if (REUSE) {
+            rr = __builtin_amdgcn_readfirstlane(gi[GI_RR_NODE]);
+            // consumed: a hand-off lives for one step.  The store depends on rr: the word is read by a scalar load, and a
+            // vector store issued before that load returns could overtake it (the load would then see the cleared word)
+            if (rr != 0 && lane == 0) gi[GI_RR_NODE] = 0;
+        }
+        if (expand_root_finish(E, gi, st, slot, v_net)) return;
+    } else {
+        if (lane == 0) st[ST_LEAF] += 1;
+    }
+
+    const float sum = wave_priors(L, policy + (size_t)slot * (is_probs == 2 ? XQ_MAXM : XQ_ACTION_SPACE), pmoves, cnt, is_probs);
+    const bool full_move = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_FULL]) != 0 : true;
+    const bool noisy = is_root && full_move && (E.cfg.add_noise != 0 || gi[GI_MANNOISE] != 0);
+    if (noisy) wave_root_noise(E, L, gi, st, slot, cnt);
 
     const int node = is_root ? 0 : __builtin_amdgcn_readfirstlane(gi[GI_PLEAF]);
     int first = __builtin_amdgcn_readfirstlane(gi[GI_ALLOC]);
@@ -876,61 +1003,38 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
     int root_sims = 0;                                // the search's first sims_done: 0, or the reused root's visits
     if (REUSE && rr > 0) {
         // node 0 holds the chosen child's words (k_reroot); its children must be this position's legal moves
-        const int m0 = __builtin_amdgcn_readfirstlane((int)tM[0]), f0 = __builtin_amdgcn_readfirstlane(tC[0]);
+        const int m0 = __builtin_amdgcn_readfirstlane((int)T.M[0]), f0 = __builtin_amdgcn_readfirstlane(T.C[0]);
         reused = cnt > 0 && (m0 & 0x3FFF) == cnt && f0 >= 1 && f0 + cnt <= E.node_cap;
         if (reused) {
             first = f0;
         } else {                                      // a defect: reported, and the root is expanded afresh
             ovf |= 64;
-            if (lane == 0) { tN[0] = 0; tW[0] = 0.0; }
+            if (lane == 0) { T.N[0] = 0; T.W[0] = 0.0; }
         }
     }
     if (cnt > 0) {
         if (first + cnt > E.node_cap) {
             ovf |= 32;
         } else {
-            int kind;
-            const double eps = E.cfg.noise_eps;
-            const float keep_f = (float)(1.0 - eps);
-            if (sum > 0.0f) {
-                kind = noisy ? 1 : 0;
-                for (int i = lane; i < cnt; i += 64) {
-                    const float pr = L.p[i] / sum;
-                    if (noisy) { const float sc = keep_f * pr; rootP[i] = (double)sc + eps * L.eta[i]; }
-                    tP[first + i] = pr;
-                }
-            } else {
-                kind = noisy ? 1 : 2;
-                const double uni = 1.0 / (double)cnt;
-                for (int i = lane; i < cnt; i += 64) {
-                    if (noisy) rootP[i] = (1.0 - eps) * uni + eps * L.eta[i];
-                    tP[first + i] = (float)uni;
-                }
-            }
+            const int kind = wave_write_priors(E, L, T.P + first, rootP, cnt, sum, noisy);
             if (REUSE && reused) {
                 // the kept children keep N, W, action, first child and meta; the budget is visits: sims_done = root N = sum N
                 int vis = 0, bad = 0;
                 for (int i = lane; i < cnt; i += 64) {
-                    vis += tN[first + i];
-                    bad |= tA[first + i] != L.act[i];
+                    vis += T.N[first + i];
+                    bad |= T.A[first + i] != L.act[i];
                 }
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) { vis += __shfl_xor(vis, off); bad |= __shfl_xor(bad, off); }
                 root_sims = __builtin_amdgcn_readfirstlane(vis);
                 if (__builtin_amdgcn_readfirstlane(bad)) ovf |= 64;
                 if (lane == 0) {
-                    tM[0] = (uint16_t)(cnt | (kind << 14)); tN[0] = root_sims;
+                    T.M[0] = (uint16_t)(cnt | (kind << 14)); T.N[0] = root_sims;
                     st[ST_REUSED] += (unsigned)root_sims; st[ST_REROOTS] += 1;
                 }
             } else {
-                for (int i = lane; i < cnt; i += 64) {
-                    tN[first + i] = 0; tW[first + i] = 0.0; tA[first + i] = L.act[i]; tC[first + i] = -1; tM[first + i] = 0;
-                }
-                if (lane == 0) {
-                    tC[node] = first; tM[node] = (uint16_t)(cnt | (kind << 14));
-                    gi[GI_ALLOC] = first + cnt;
-                    st[ST_NODES] += (unsigned)cnt;
-                }
+                wave_new_children(T, L, st, node, first, cnt, kind);
+                if (lane == 0) gi[GI_ALLOC] = first + cnt;
             }
         }
     }
@@ -941,7 +1045,7 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
     // ---- leaf: value = -v (mcts.py:150), backup
     const int depth = __builtin_amdgcn_readfirstlane(gi[GI_PDEPTH]);
     wave_sync_mem();
-    wave_backup(tN, tW, path, depth, -v_net);
+    wave_backup<false>(T, nullptr, path, depth, -v_net);
     sims_done += 1;
     if (lane == 0) {
         gi[GI_SIMS] = sims_done;
@@ -1090,14 +1194,12 @@ __global__ void k_drop_reroots(Dev E) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Leaf batching (xq_engine_init_leaves, K > 1): k_select_multi / k_expand_multi replace k_select / k_expand; k_select,
-// k_expand and the K = 1 step are untouched.  Per step a searching slot runs up to K descents under virtual loss (a
-// separate int32 counter per node, never folded into N / W): child i of parent p is scored with n = N_i + vl_i (in q and in
-// 1 + n), w = W_i - vl_i (fp64) and sqrt_tab[N_p + vl_p], otherwise the arithmetic of k_select term by term.  A descent
-// that chooses a non-terminal leaf adds 1 to vl along its path (the root included) and hands the leaf to the evaluator in
-// row slot K + j; a terminal leaf is backed up at once; a descent that ends on a leaf already pending in this step (a
-// collision) is dropped and ends the slot's collection.  k_expand_multi expands and backs up the pending leaves in
-// descent order and removes each one's virtual loss: every vl is 0 again after every step.
+// Leaf batching (xq_engine_init_leaves, K > 1): k_select_multi / k_expand_multi replace k_select / k_expand.  Per step a
+// searching slot runs up to K descents under virtual loss (a separate int32 counter per node, never folded into N / W):
+// wave_descend<true, ..>.  A descent that chooses a non-terminal leaf adds 1 to vl along its path (the root included) and
+// hands the leaf to the evaluator in row slot K + j; a terminal leaf is backed up at once; a descent that ends on a leaf
+// already pending in this step (a collision) is dropped and ends the slot's collection.  k_expand_multi expands and backs
+// up the pending leaves in descent order and removes each one's virtual loss: every vl is 0 again after every step.
 struct Mx {
     int K;                          // leaves per step (2..64)
     int32_t *vl;                    // [G][node_cap] in-flight descents through each node
@@ -1111,22 +1213,20 @@ __global__ __launch_bounds__(64) void k_select_multi(Dev E, Mx X, float *__restr
     const int slot = blockIdx.x;
     if (slot >= E.cfg.n_games) return;
     const int lane = lane_id();
-    int32_t *gi = E.gi + (size_t)slot * GI_N;
-    unsigned long long *st = E.stats + (size_t)slot * ST_N;
-    const size_t nb = (size_t)slot * E.node_cap;
-    int32_t *tN = E.tN + nb; double *tW = E.tW + nb; float *tP = E.tP + nb;
-    uint16_t *tA = E.tA + nb; int32_t *tC = E.tC + nb; uint16_t *tM = E.tM + nb;
+    Slot s;
+    s.slot = slot; s.lane = lane; s.gi = E.gi + (size_t)slot * GI_N; s.st = E.stats + (size_t)slot * ST_N; s.T = slot_tree(E, slot);
+    int32_t *gi = s.gi;
+    unsigned long long *st = s.st;
+    const Tree &T = s.T;
     const int K = X.K;
     const size_t row0 = (size_t)slot * K;                // the slot's first request row; descent j uses row row0 + j
-    int32_t *vl = X.vl + nb;
+    int32_t *vl = X.vl + (size_t)slot * E.node_cap;
     int32_t *path = E.path + row0 * E.path_cap;
-    int8_t *g_board = E.board + (size_t)slot * XQ_BS;
-    int8_t *g_hist = E.hist + (size_t)slot * XQ_HIST * XQ_BS;
     uint16_t *pmoves = E.pmoves + row0 * XQ_MAXM;
     const double *rootP = E.rootP + (size_t)slot * XQ_MAXM;
     const int S = E.cfg.num_simulations;
     const bool manual = E.cfg.manual_moves == 1;     // search only (MCTS.search parity / serving)
-    const bool arena = E.cfg.manual_moves == 2;      // evaluation games (train.py:453-535): T = 0, no opening, no samples
+    const bool arena = E.cfg.manual_moves == 2;      // evaluation games: not with K > 1 (leaves_ok)
 
     int phase = __builtin_amdgcn_readfirstlane(gi[GI_PHASE]);
     if (phase == PH_WAIT_ROOT || phase == PH_WAIT_LEAF) return;        // still waiting: the request stands
@@ -1137,359 +1237,85 @@ __global__ __launch_bounds__(64) void k_select_multi(Dev E, Mx X, float *__restr
         for (int j = lane; j < K; j += 64) E.req[row0 + j] = 0;
         return;
     }
-
-    int g_side = __builtin_amdgcn_readfirstlane(gi[GI_SIDE]);
-    int g_mc = __builtin_amdgcn_readfirstlane(gi[GI_MC]);
-    int g_nocap = __builtin_amdgcn_readfirstlane(gi[GI_NOCAP]);
-    int sims_done = __builtin_amdgcn_readfirstlane(gi[GI_SIMS]);
-    int n_samples = __builtin_amdgcn_readfirstlane(gi[GI_NSAMP]);
-    int game_seq = __builtin_amdgcn_readfirstlane(gi[GI_GSEQ]);
-    int rng_ctr[4] = {__builtin_amdgcn_readfirstlane(gi[GI_RNG0]), __builtin_amdgcn_readfirstlane(gi[GI_RNG1]),
-                      __builtin_amdgcn_readfirstlane(gi[GI_RNG2]), __builtin_amdgcn_readfirstlane(gi[GI_RNG3])};
-    int ovf = 0;
-    // per-lane stat deltas are kept wave-uniform and written by lane 0 at the end
-    unsigned long long d_sims = 0, d_term = 0, d_moves = 0, d_depth = 0, d_scan = 0;
+    slot_load(s);
     int term_run = 0;
     // pending leaves of this step: lane j holds leaf j's node and legal-move count (K <= 64)
     int npend = 0, my_node = -1, my_cnt = 0;
     unsigned long long d_coll = 0;
 
-    lds_copy_dwords(L.root, g_board, XQ_BS / 4);
-    lds_copy_dwords(L.rhist, g_hist, XQ_HIST * XQ_BS / 4);
+    lds_copy_dwords(L.root, E.board + (size_t)slot * XQ_BS, XQ_BS / 4);
+    lds_copy_dwords(L.rhist, E.hist + (size_t)slot * XQ_HIST * XQ_BS, XQ_HIST * XQ_BS / 4);
     wave_sync();
 
-    bool state_dirty = false;  // real game state changed -> write back
     for (int guard = 0; guard < 4 * S + 64; ++guard) {
         if (phase == PH_FINISHED) {
-            // ---- flush the finished game's samples with z (parallel_selfplay.py:123-132) and its result
-            const int winner = __builtin_amdgcn_readfirstlane(gi[GI_FWINNER]);
-            const int reason = __builtin_amdgcn_readfirstlane(gi[GI_FREASON]);
-            unsigned base = 0;
-            bool fits = true;
-            if (n_samples > 0) {
-                if (lane == 0) base = atomicAdd(&E.cnt[0], (unsigned)n_samples);
-                base = __builtin_amdgcn_readfirstlane(base);
-                fits = (unsigned long long)base + (unsigned)n_samples <= (unsigned)E.cfg.max_out_samples;
-                if (fits) {
-                    const uint8_t *src = E.stage + (size_t)slot * E.stage_cap * XQ_SAMPLE_BYTES;
-                    uint8_t *dst = E.outs + (size_t)base * XQ_SAMPLE_BYTES;
-                    const int ndw = n_samples * (XQ_SAMPLE_BYTES / 4);
-                    for (int i = lane; i < ndw; i += 64) ((uint32_t *)dst)[i] = ((const uint32_t *)src)[i];
-                    for (int i = lane; i < n_samples; i += 64) {
-                        const int sside = ((const int8_t *)src)[(size_t)i * XQ_SAMPLE_BYTES + 90];
-                        ((int8_t *)dst)[(size_t)i * XQ_SAMPLE_BYTES + 91] = (int8_t)(winner == 0 ? 0 : (winner == sside ? 1 : -1));
-                    }
-                }
-            }
-            if (lane == 0) {
-                if (fits) st[ST_SAMP] += (unsigned)n_samples; else st[ST_DROP] += (unsigned)n_samples;
-                const unsigned r = atomicAdd(&E.cnt[1], 1u);
-                if (r < (unsigned)E.cfg.max_out_results) {
-                    xq_game_result res;
-                    res.slot = (uint32_t)slot; res.game_seq = (uint32_t)game_seq; res.winner = (int8_t)winner;
-                    res.reason = (uint8_t)reason; res.steps = (uint16_t)g_mc; res.n_samples = (uint16_t)n_samples;
-                    res.reserved = 0;
-                    *(xq_game_result *)(E.outr + (size_t)r * XQ_RESULT_BYTES) = res;
-                }
-                st[ST_GAMES] += 1;
-                st[winner == 1 ? ST_RED : (winner == -1 ? ST_BLACK : ST_DRAW)] += 1;
-                st[ST_PLIES] += (unsigned)g_mc;
-                if (reason == 3) st[ST_RESIGN] += 1;
-            }
+            slot_flush_finished(E, s);
             phase = PH_NEWGAME;
         }
         if (phase == PH_NEWGAME) {
-            // ---- new game + random opening (parallel_selfplay.py:58-72)
-            unsigned long long idx = 0;
-            if (lane == 0) idx = atomicAdd(E.started, 1ull);
-            idx = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(idx >> 32)) << 32) |
-                  (unsigned)__builtin_amdgcn_readfirstlane((unsigned)idx);
-            if (E.cfg.games_target > 0 && idx >= (unsigned long long)E.cfg.games_target) { phase = PH_IDLE; break; }
-            game_seq += 1;
-            n_samples = 0;
-            init_board_lds(L.root);
-            g_side = 1; g_mc = 0; g_nocap = 0;
-            if (lane == 0) { gi[GI_RESIGN_N] = 0; st[ST_STARTED] += 1; }
-            wave_sync();
-            const int R = arena ? 0 : E.cfg.random_opening_moves;
-            const int k = R > 0 ? (int)(draw_u64(E, slot, RNG_RANDINT, rng_ctr[RNG_RANDINT], st) % (uint64_t)(R + 1)) : 0;
-            if (!arena) rng_ctr[RNG_RANDINT] += 1;   // random.randint is called even when R == 0
-            for (int i = 0; i < k; ++i) {
-                const int cnt = wave_movegen(L.root, g_side, L.mg, L.moves, &ovf);
-                if (cnt == 0) break;
-                const int pick = (int)(draw_u64(E, slot, RNG_CHOICE, rng_ctr[RNG_CHOICE], st) % (uint64_t)cnt);
-                rng_ctr[RNG_CHOICE] += 1;
-                const int action = L.moves[pick];
-                wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
-                int c2, w2;
-                if (wave_game_over(L.root, L.rhist, g_side, g_mc, g_nocap, L.mg, L.moves, &c2, &w2, &ovf)) {
-                    init_board_lds(L.root);
-                    g_side = 1; g_mc = 0; g_nocap = 0;
-                    wave_sync();
-                    break;
-                }
-            }
-            state_dirty = true;
+            if (!slot_new_game(E, s, L, arena)) { phase = PH_IDLE; break; }
             phase = PH_NEWPOS;
         }
         if (phase == PH_NEWPOS) {
-            // ---- root request: terminal status of the real position + its planes + its ordered legal moves
-            int cnt, winner;
-            int status = 0;
-            const bool done = wave_game_over(L.root, L.rhist, g_side, g_mc, g_nocap, L.mg, L.moves, &cnt, &winner, &ovf);
-            if (done) status = 1;
-            else if (arena && g_mc >= E.cfg.max_game_length) {     // train.py:477,494-496: not over after max plies => draw
-                winner = 0;
-                status = 2;
-            } else if (!manual && !arena && g_mc >= E.cfg.max_game_length) {   // parallel_selfplay.py:79-89
-                int red, black;
-                wave_material(L.root, red, black);
-                const int diff = red - black;
-                winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
-                status = 2;
-            }
-            wave_encode(L.root, g_side, nn_in + row0 * XQ_STATE_FLOATS);
-            for (int j = lane; j < cnt; j += 64) pmoves[j] = L.moves[j];
+            int status;
+            const int cnt = slot_root_request(E, s, L, manual, arena, nn_in + row0 * XQ_STATE_FLOATS, pmoves, status);
             my_cnt = lane == 0 ? cnt : 0;
-            if (lane == 0) {
-                gi[GI_PCOUNT] = cnt; gi[GI_RSTATUS] = status; gi[GI_RWINNER] = winner;
-                gi[GI_ALLOC] = 1;
-                tN[0] = 0; tW[0] = 0.0; tC[0] = -1; tM[0] = 0; tA[0] = 0; tP[0] = 0.0f;
-            }
-            sims_done = 0;
             phase = PH_WAIT_ROOT;
             break;
         }
         // ---- phase == PH_SEARCH
         // stop collecting: K leaves pending, or the pending leaves complete the move's S simulations
-        if (npend > 0 && (npend >= K || sims_done + npend >= S)) { phase = PH_WAIT_LEAF; break; }
-        if (sims_done >= S) {
+        if (npend > 0 && (npend >= K || s.sims_done + npend >= S)) { phase = PH_WAIT_LEAF; break; }
+        if (s.sims_done >= S) {
             if (manual) { phase = PH_HOLD; break; }
-            const int nch = __builtin_amdgcn_readfirstlane((int)(tM[0] & 0x3FFF));
-            const int first = __builtin_amdgcn_readfirstlane(tC[0]);
-            if (arena) {
-                // MCTS.get_action(temperature=0) (mcts.py:166-174, 197-200): first maximum of the visit counts, move order
-                int bn = -1, bi = 0x7FFFFFFF;
-                for (int i = lane; i < nch; i += 64) {
-                    const int n = tN[first + i];
-                    if (n > bn) { bn = n; bi = i; }
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const int on = __shfl_xor(bn, off), oi = __shfl_xor(bi, off);
-                    if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
-                }
-                bi = __builtin_amdgcn_readfirstlane(bi);
-                const int action = __builtin_amdgcn_readfirstlane((int)tA[first + bi]);
-                wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
-                d_moves += 1;
-                state_dirty = true;
-                phase = PH_NEWPOS;
-                continue;
-            }
-            // ---- end of move: sample (parallel_selfplay.py:97-107), pi from visit counts (mcts.py:190-206)
-            const bool late = g_mc >= E.cfg.temperature_threshold;
-            const double inv_t = 1.0 / E.cfg.late_temperature;
-            uint8_t *rec = E.stage + ((size_t)slot * E.stage_cap + (n_samples < E.stage_cap ? n_samples : E.stage_cap - 1)) * XQ_SAMPLE_BYTES;
-            if (n_samples >= E.stage_cap) ovf |= 4;
-            for (int i = lane; i < XQ_SAMPLE_BYTES / 4; i += 64) ((uint32_t *)rec)[i] = 0u;
-            wave_sync_mem();
-            for (int i = lane; i < 90; i += 64) rec[i] = (uint8_t)L.root[i];
-            if (lane == 0) {
-                xq_sample *s = (xq_sample *)rec;
-                s->side = (int8_t)g_side; s->z = 0; s->n_moves = (uint8_t)nch; s->late_temp = late ? 1 : 0;
-                s->ply = (uint16_t)g_mc; s->slot = (uint32_t)slot; s->game_seq = (uint32_t)game_seq;
-            }
-            for (int i = lane; i < nch; i += 64) {
-                const int a = tA[first + i], n = tN[first + i];
-                ((xq_sample *)rec)->actions[i] = (uint16_t)a;
-                ((xq_sample *)rec)->visits[i] = (uint16_t)(n > 65535 ? 65535 : n);
-                L.a_tmp[i] = (uint16_t)a;
-                L.w_tmp[i] = late ? (n > 0 ? pow((double)n, inv_t) : 0.0) : (double)n;
-            }
-            wave_sync();
-            // np.random.choice walks the dense pi in ACTION-ID order: sort the (action, weight) pairs by id
-            for (int i = lane; i < nch; i += 64) {
-                const int a = L.a_tmp[i];
-                int rank = 0;
-                for (int j = 0; j < nch; ++j) rank += (L.a_tmp[j] < a) ? 1 : 0;
-                L.sa[rank] = (uint16_t)a;
-                L.sw[rank] = L.w_tmp[i];
-            }
-            wave_sync();
-            const double u = u64_to_unit(draw_u64(E, slot, RNG_UNIFORM, rng_ctr[RNG_UNIFORM], st));
-            rng_ctr[RNG_UNIFORM] += 1;
-            int action = 0;
-            {
-                // every lane runs the same short sequential scan (LDS broadcast reads); result is wave-uniform
-                double total = 0.0;
-                for (int i = 0; i < nch; ++i) total += L.sw[i];
-                double run = 0.0;
-                for (int i = 0; i < nch; ++i) run += L.sw[i] / total;
-                const double last = run;
-                run = 0.0;
-                int pick = nch - 1;
-                for (int i = 0; i < nch; ++i) {
-                    run += L.sw[i] / total;
-                    if (run / last > u) { pick = i; break; }
-                }
-                action = L.sa[pick];
-            }
-            action = __builtin_amdgcn_readfirstlane(action);
-            wave_make_move(L.root, L.rhist, action, g_side, g_mc, g_nocap);
-            n_samples += 1;
-            d_moves += 1;
-            state_dirty = true;
+            const int nch = __builtin_amdgcn_readfirstlane((int)(T.M[0] & 0x3FFF));
+            const int first = __builtin_amdgcn_readfirstlane(T.C[0]);
+            if (arena) slot_arena_move(s, L, nch, first);
+            else slot_play(s, L, slot_end_move(E, s, L, true, false, nch, first));
             phase = PH_NEWPOS;
             continue;
         }
-        // ---- one simulation (mcts.py:126-153): descend from the root replaying moves on the LDS board
-        lds_copy_dwords(L.board, L.root, XQ_BS / 4);
-        lds_copy_dwords(L.hist, L.rhist, XQ_HIST * XQ_BS / 4);
-        wave_sync();
-        int side = g_side, mc = g_mc, nocap = g_nocap, node = 0, depth = 0;
         int32_t *pathj = path + (size_t)npend * E.path_cap;   // this descent's row (reused after a terminal leaf / collision)
-        if (lane == 0) pathj[0] = 0;
-        // One dependent round trip to memory per level: every lane reads, with its candidate child's N / W / P, that child's own
-        // node words (children count + kind, first child, action) as well, so the winner's are already in a register when the arg-max
-        // is known -- the next level starts from a lane read instead of three more dependent loads (tM -> tC/tN -> ... -> tA).  The
-        // winner's N, read here, IS the next level's parent count.  Same values, same arithmetic, same order as before.
-        int m = __builtin_amdgcn_readfirstlane((int)tM[0]);
-        int first = __builtin_amdgcn_readfirstlane(tC[0]);
-        int pn = __builtin_amdgcn_readfirstlane(tN[0] + vl[0]);     // visits + in-flight descents
-        for (;;) {
-            const int nch = m & 0x3FFF, kind = m >> 14;
-            if (nch == 0) break;
-            const double sqrtp = E.sqrt_tab[pn];
-            const float sqrtp_f = (float)sqrtp, c_f = (float)E.cfg.c_puct;
-            const double uni = 1.0 / (double)nch;
-            double best = -INFINITY;
-            int best_i = 0x7FFFFFFF;
-            int c_m = 0, c_first = 0, c_n = 0, c_a = 0;              // node words of this lane's best candidate
-            for (int base = 0; base < nch; base += 64) {
-                const int i = base + lane;
-                if (i < nch) {
-                    // virtual loss: each in-flight descent through child i counts as a visit and as a loss for the
-                    // side choosing here (W is from the chooser's view); vl = 0 gives today's values exactly
-                    const int v = vl[first + i];
-                    const int n = tN[first + i] + v;
-                    const double w = tW[first + i] - (double)v;
-                    const int cm = (int)tM[first + i], cf = tC[first + i], ca = (int)tA[first + i];
-                    const double q = n ? w / (double)n : 0.0;
-                    double ucb;
-                    if (kind == 0) {
-                        float t = c_f * tP[first + i];
-                        t = t * sqrtp_f;
-                        t = t / (float)(1 + n);
-                        t = (float)q + t;
-                        ucb = (double)t;
-                    } else {
-                        const double p = kind == 1 ? rootP[i] : uni;
-                        double t = E.cfg.c_puct * p;
-                        t = t * sqrtp;
-                        t = t / (double)(1 + n);
-                        ucb = q + t;
-                    }
-                    if (ucb > best) { best = ucb; best_i = i; c_m = cm; c_first = cf; c_n = n; c_a = ca; }
-                }
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const double ov = __shfl_xor(best, off);
-                const int oi = __shfl_xor(best_i, off);
-                if (ov > best || (ov == best && oi < best_i)) { best = ov; best_i = oi; }
-            }
-            best_i = __builtin_amdgcn_readfirstlane(best_i);
-            int action;
-            if (best_i == 0x7FFFFFFF) {                              // all-NaN scores: the reference would raise
-                ovf |= 8; best_i = 0;
-                m = __builtin_amdgcn_readfirstlane((int)tM[first]);
-                pn = __builtin_amdgcn_readfirstlane(tN[first] + vl[first]);
-                action = __builtin_amdgcn_readfirstlane((int)tA[first]);
-                const int nf = __builtin_amdgcn_readfirstlane(tC[first]);
-                d_scan += (unsigned)nch;
-                const int child0 = first;
-                first = nf;
-                wave_make_move(L.board, L.hist, action, side, mc, nocap);
-                depth += 1;
-                if (depth >= E.path_cap) { ovf |= 16; depth = E.path_cap - 1; }
-                if (lane == 0) pathj[depth] = child0;
-                node = child0;
-                continue;
-            }
-            d_scan += (unsigned)nch;
-            const int child = first + best_i;
-            const int src = best_i & 63;                              // child i was lane i % 64's candidate, and its best (it won)
-            action = __builtin_amdgcn_readlane(c_a, src);
-            m = __builtin_amdgcn_readlane(c_m, src);
-            pn = __builtin_amdgcn_readlane(c_n, src);
-            first = __builtin_amdgcn_readlane(c_first, src);
-            wave_make_move(L.board, L.hist, action, side, mc, nocap);
-            depth += 1;
-            if (depth >= E.path_cap) { ovf |= 16; depth = E.path_cap - 1; }
-            if (lane == 0) pathj[depth] = child;
-            node = child;
-        }
+        const Leaf lf = wave_descend<true, false>(E, s, L, vl, rootP, 0.0f, pathj);
         // collision: the descent ended on a leaf an earlier descent of this step already waits on -- it is not a simulation
         // (it added no virtual loss yet) and ends this step's collection
-        if (__ballot(lane < npend && my_node == node) != 0ull) { d_coll += 1; phase = PH_WAIT_LEAF; break; }
-        d_depth += (unsigned)depth;
+        if (__ballot(lane < npend && my_node == lf.node) != 0ull) { d_coll += 1; phase = PH_WAIT_LEAF; break; }
+        s.d_depth += (unsigned)lf.depth;
         int cnt, winner;
-        const bool term = wave_game_over(L.board, L.hist, side, mc, nocap, L.mg, L.moves, &cnt, &winner, &ovf);
+        const bool term = wave_game_over(L.board, L.hist, lf.side, lf.mc, lf.nocap, L.mg, L.moves, &cnt, &winner, &s.ovf);
         if (term) {
             wave_sync_mem();   // path[] stores of lane 0 must be visible to the other lanes
-            wave_backup(tN, tW, pathj, depth, winner == 0 ? 0.0 : 1.0);   // mcts.py:137-140
+            wave_backup<false>(T, nullptr, pathj, lf.depth, winner == 0 ? 0.0 : 1.0);   // mcts.py:137-140
             wave_sync_mem();   // the next descent reads N/W written here by other lanes
-            sims_done += 1; d_sims += 1; d_term += 1;
-            // A root with a mating reply re-tests that terminal child on every visit (as mcts.py does); bound how
-            // many such simulations one launch runs so a single slot cannot stretch the step (it resumes next step
-            // and hands the evaluator no position this time).
+            s.sims_done += 1; s.d_sims += 1; s.d_term += 1;
+            // the bound on terminal simulations per launch, for k_select's reason
             if (++term_run >= 48) { if (npend > 0) phase = PH_WAIT_LEAF; break; }
             continue;
         }
         // ---- pending leaf j = npend: its request goes to row row0 + j; virtual loss along its path, the root included
-        wave_encode(L.board, side, nn_in + (row0 + npend) * XQ_STATE_FLOATS);
+        wave_encode(L.board, lf.side, nn_in + (row0 + npend) * XQ_STATE_FLOATS);
         uint16_t *pm = pmoves + (size_t)npend * XQ_MAXM;
         for (int j = lane; j < cnt; j += 64) pm[j] = L.moves[j];
-        if (lane == npend) { my_node = node; my_cnt = cnt; }
-        if (lane == 0) { int32_t *lf = X.leaf + (row0 + npend) * 4; lf[0] = node; lf[1] = depth; lf[2] = cnt; }
+        if (lane == npend) { my_node = lf.node; my_cnt = cnt; }
+        if (lane == 0) { int32_t *rec = X.leaf + (row0 + npend) * 4; rec[0] = lf.node; rec[1] = lf.depth; rec[2] = cnt; }
         wave_sync_mem();   // pathj[] stores of lane 0 must be visible to the other lanes
-        for (int j = lane; j <= depth; j += 64) vl[pathj[j]] += 1;
+        for (int j = lane; j <= lf.depth; j += 64) vl[pathj[j]] += 1;
         wave_sync_mem();   // the next descent reads vl written here by other lanes
         npend += 1;
     }
 
-    if (state_dirty) {
-        lds_copy_dwords(g_board, L.root, XQ_BS / 4);
-        lds_copy_dwords(g_hist, L.rhist, XQ_HIST * XQ_BS / 4);
-    }
+    slot_store(E, s, L, phase);
     const int nrows = phase == PH_WAIT_ROOT ? 1 : (phase == PH_WAIT_LEAF ? npend : 0);
     for (int j = lane; j < K; j += 64) E.req[row0 + j] = j < nrows ? my_cnt : 0;
     if (lane == 0) {
         gi[GI_NPEND] = nrows;
         if (phase == PH_WAIT_LEAF) { st[ST_LPS] += (unsigned)npend; st[ST_LSTEPS] += 1; }
         st[ST_COLL] += d_coll;
-        gi[GI_SIDE] = g_side; gi[GI_MC] = g_mc; gi[GI_NOCAP] = g_nocap; gi[GI_PHASE] = phase; gi[GI_SIMS] = sims_done;
-        gi[GI_NSAMP] = n_samples; gi[GI_GSEQ] = game_seq;
-        gi[GI_RNG0] = rng_ctr[0]; gi[GI_RNG1] = rng_ctr[1]; gi[GI_RNG2] = rng_ctr[2]; gi[GI_RNG3] = rng_ctr[3];
-        st[ST_SIMS] += d_sims; st[ST_TERM] += d_term; st[ST_MOVES] += d_moves; st[ST_DEPTH] += d_depth; st[ST_SCAN] += d_scan;
-        if (ovf) st[ST_OVF] |= (unsigned long long)ovf << 8;
     }
 }
 
-// mcts.py:66-73 along path[0..depth] of one pending descent, removing its virtual loss
-__device__ __forceinline__ void wave_backup_vl(int32_t *tN, double *tW, int32_t *vl, const int32_t *path, int depth, double v) {
-    for (int j = lane_id(); j <= depth; j += 64) {
-        const int nd = path[j];
-        const double s = ((depth - j) & 1) ? -v : v;
-        tN[nd] += 1;
-        tW[nd] += s;
-        vl[nd] -= 1;
-    }
-}
-
-// k_expand for request rows slot K + j: the root (one row, j = 0) exactly as k_expand; the pending leaves j = 0 .. npend-1
-// expanded (children bump-allocated in j order) and backed up in j order
+// k_expand for request rows slot K + j: the root (one row, j = 0); the pending leaves j = 0 .. npend-1 expanded (children
+// bump-allocated in j order) and backed up in j order
 __global__ __launch_bounds__(64) void k_expand_multi(Dev E, Mx X, const float *__restrict__ policy, const float *__restrict__ value,
                                                      int is_probs) {
     __shared__ ExpandLds L;
@@ -1502,10 +1328,8 @@ __global__ __launch_bounds__(64) void k_expand_multi(Dev E, Mx X, const float *_
     if (phase != PH_WAIT_ROOT && phase != PH_WAIT_LEAF) return;
     const int K = X.K;
     const size_t row0 = (size_t)slot * K;
-    const size_t nb = (size_t)slot * E.node_cap;
-    int32_t *tN = E.tN + nb; double *tW = E.tW + nb; float *tP = E.tP + nb;
-    uint16_t *tA = E.tA + nb; int32_t *tC = E.tC + nb; uint16_t *tM = E.tM + nb;
-    int32_t *vl = X.vl + nb;
+    const Tree T = slot_tree(E, slot);
+    int32_t *vl = X.vl + (size_t)slot * E.node_cap;
     double *rootP = E.rootP + (size_t)slot * XQ_MAXM;
     const bool manual = E.cfg.manual_moves == 1;
     const bool is_root = phase == PH_WAIT_ROOT;
@@ -1514,107 +1338,17 @@ __global__ __launch_bounds__(64) void k_expand_multi(Dev E, Mx X, const float *_
     int alloc = __builtin_amdgcn_readfirstlane(gi[GI_ALLOC]);
     int ovf = 0;
 
-    if (is_root) {
-        const double v_net = (double)value[row0];
-        if (lane == 0) st[ST_ROOT] += 1;
-        const int side = gi[GI_SIDE];
-        int fin = 0, fwinner = 0, freason = 0;
-        // resign probe on the position after the move (parallel_selfplay.py:110-121)
-        if (!manual && E.cfg.enable_resign && gi[GI_NSAMP] > 10) {
-            const int RK = E.cfg.resign_check_steps;
-            double *rh = E.resign + (size_t)slot * 16;
-            int rn = gi[GI_RESIGN_N];
-            wave_sync_mem();
-            if (lane == 0) { rh[rn % 16] = v_net; gi[GI_RESIGN_N] = rn + 1; }
-            wave_sync_mem();
-            rn += 1;
-            if (rn >= RK) {
-                bool all_low = true;
-                for (int i = rn - RK; i < rn; ++i) all_low = all_low && (rh[i % 16] < E.cfg.resign_threshold);
-                if (all_low) { fin = 1; fwinner = -side; freason = 3; }
-            }
-        }
-        const int rstatus = gi[GI_RSTATUS];
-        if (!fin && rstatus != 0) { fin = 1; fwinner = gi[GI_RWINNER]; freason = rstatus; }
-        fin = __builtin_amdgcn_readfirstlane(fin);
-        if (fin) {
-            if (lane == 0) {
-                gi[GI_FWINNER] = fwinner; gi[GI_FREASON] = freason;
-                gi[GI_PHASE] = manual ? PH_HOLD : PH_FINISHED;
-            }
-            return;
-        }
-    }
+    if (is_root && expand_root_finish(E, gi, st, slot, (double)value[row0])) return;
 
     for (int j = 0; j < nrows; ++j) {
         const size_t row = row0 + j;
         const int32_t *lf = X.leaf + row * 4;
-        const uint16_t *pmoves = E.pmoves + row * XQ_MAXM;
         const int cnt = is_root ? __builtin_amdgcn_readfirstlane(gi[GI_PCOUNT]) : __builtin_amdgcn_readfirstlane(lf[2]);
-        // ---- priors of the legal moves, as k_expand (is_probs: 0 logits over 8100, 1 probabilities over 8100, 2 legal logits)
-        const float *pol = policy + row * (is_probs == 2 ? XQ_MAXM : XQ_ACTION_SPACE);
-        float mx = 0.0f, den = 1.0f;
-        if (is_probs == 2) {
-            float m = -INFINITY;
-            for (int i = lane; i < cnt; i += 64) m = fmaxf(m, pol[i]);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-            mx = m;
-        } else if (!is_probs) {
-            const float4 *p4 = (const float4 *)pol;
-            float m = -INFINITY;
-            for (int i = lane; i < XQ_ACTION_SPACE / 4; i += 64) {
-                const float4 x = p4[i];
-                m = fmaxf(fmaxf(m, fmaxf(x.x, x.y)), fmaxf(x.z, x.w));
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-            float s = 0.0f;
-            for (int i = lane; i < XQ_ACTION_SPACE / 4; i += 64) {
-                const float4 x = p4[i];
-                s += expf(x.x - m) + expf(x.y - m) + expf(x.z - m) + expf(x.w - m);
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            mx = m; den = s;
-        }
         wave_sync();       // the previous row's readers of L are done
-        for (int i = lane; i < cnt; i += 64) {
-            const int a = pmoves[i];
-            const float x = pol[is_probs == 2 ? i : a];
-            L.p[i] = is_probs == 1 ? x : expf(x - mx) / den;
-            L.act[i] = (uint16_t)a;
-        }
-        wave_sync();
-        float sum = 0.0f;
-        for (int i = 0; i < cnt; ++i) sum = sum + L.p[i];      // builtin sum(): sequential float32, move order
-
+        const float sum = wave_priors(L, policy + row * (is_probs == 2 ? XQ_MAXM : XQ_ACTION_SPACE), E.pmoves + row * XQ_MAXM, cnt,
+                                      is_probs);
         const bool noisy = is_root && (E.cfg.add_noise != 0 || gi[GI_MANNOISE] != 0);
-        if (noisy) {
-            if (gi[GI_MANNOISE] != 0) {
-                const double *mn = E.mnoise + (size_t)slot * XQ_MAXM;
-                for (int i = lane; i < cnt; i += 64) L.eta[i] = mn[i];
-            } else {
-                const int ctr0 = gi[GI_RNG0 + RNG_DIRICHLET];
-                for (int i = lane; i < cnt; i += 64) {
-                    double g;
-                    if (E.cfg.inject_len > 0) {
-                        const double w = (double)(1 + (int)((draw_u64(E, slot, RNG_DIRICHLET, ctr0 + i, st) >> 40) % 4096ull));
-                        g = w * w * w;
-                    } else {
-                        g = gamma_variate(E, slot, ctr0 + i, E.cfg.dirichlet_alpha);
-                    }
-                    L.eta[i] = g;
-                }
-                wave_sync();
-                double tot = 0.0;
-                for (int i = 0; i < cnt; ++i) tot += L.eta[i];
-                wave_sync();
-                for (int i = lane; i < cnt; i += 64) L.eta[i] = L.eta[i] / tot;
-                if (lane == 0) gi[GI_RNG0 + RNG_DIRICHLET] = ctr0 + cnt;
-            }
-            wave_sync();
-        }
+        if (noisy) wave_root_noise(E, L, gi, st, slot, cnt);
 
         const int node = is_root ? 0 : __builtin_amdgcn_readfirstlane(lf[0]);
         const int first = alloc;
@@ -1622,31 +1356,8 @@ __global__ __launch_bounds__(64) void k_expand_multi(Dev E, Mx X, const float *_
             if (first + cnt > E.node_cap) {
                 ovf |= 32;
             } else {
-                int kind;
-                const double eps = E.cfg.noise_eps;
-                const float keep_f = (float)(1.0 - eps);
-                if (sum > 0.0f) {
-                    kind = noisy ? 1 : 0;
-                    for (int i = lane; i < cnt; i += 64) {
-                        const float pr = L.p[i] / sum;
-                        if (noisy) { const float sc = keep_f * pr; rootP[i] = (double)sc + eps * L.eta[i]; }
-                        tP[first + i] = pr;
-                    }
-                } else {
-                    kind = noisy ? 1 : 2;
-                    const double uni = 1.0 / (double)cnt;
-                    for (int i = lane; i < cnt; i += 64) {
-                        if (noisy) rootP[i] = (1.0 - eps) * uni + eps * L.eta[i];
-                        tP[first + i] = (float)uni;
-                    }
-                }
-                for (int i = lane; i < cnt; i += 64) {
-                    tN[first + i] = 0; tW[first + i] = 0.0; tA[first + i] = L.act[i]; tC[first + i] = -1; tM[first + i] = 0;
-                }
-                if (lane == 0) {
-                    tC[node] = first; tM[node] = (uint16_t)(cnt | (kind << 14));
-                    st[ST_NODES] += (unsigned)cnt;
-                }
+                const int kind = wave_write_priors(E, L, T.P + first, rootP, cnt, sum, noisy);
+                wave_new_children(T, L, st, node, first, cnt, kind);
                 alloc = first + cnt;
             }
         }
@@ -1655,7 +1366,7 @@ __global__ __launch_bounds__(64) void k_expand_multi(Dev E, Mx X, const float *_
         const double v_net = (double)value[row];
         const int depth = __builtin_amdgcn_readfirstlane(lf[1]);
         wave_sync_mem();
-        wave_backup_vl(tN, tW, vl, E.path + row * E.path_cap, depth, -v_net);
+        wave_backup<true>(T, vl, E.path + row * E.path_cap, depth, -v_net);
         wave_sync_mem();   // the next leaf's backup updates nodes of this path from other lanes
     }
     if (lane == 0) gi[GI_ALLOC] = alloc;
@@ -1731,20 +1442,24 @@ __global__ __launch_bounds__(256) void k_reduce_stats(Dev E, unsigned long long 
 // evaluation, packed to the front of engine-owned buffers in slot order.  The predicate is k_expand's own (phase
 // WAIT_ROOT / WAIT_LEAF after select), so the two kernels cannot disagree about which slots need output.
 
-// Stable compaction by ONE workgroup for any G: thread t owns the contiguous slots [t K, t K + K), K = ceil(G / 1024); it
-// counts its waiting slots, a block-wide exclusive scan of the counts gives its first packed row, and it writes rows[] in
-// slot order.  G = 8192: eight strided 4-byte reads per thread, a few microseconds.
+// waiting for an evaluation: k_expand's own predicate
+__device__ __forceinline__ bool slot_waits(const Dev &E, int slot) {
+    const int ph = E.gi[(size_t)slot * GI_N + GI_PHASE];
+    return ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF;
+}
+
+// Stable compaction by ONE workgroup of the rows r < R with live(r), for any R: thread t owns the contiguous rows
+// [t K, t K + K), K = ceil(R / 1024); it counts its live rows, a block-wide exclusive scan of the counts gives its first packed
+// row, and it writes rows[] in row order.  R = 8192: eight strided 4-byte reads per thread, a few microseconds.
 constexpr int CPT = 1024;
-__global__ __launch_bounds__(CPT) void k_compact(Dev E, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
+template <class Live>
+__device__ __forceinline__ void block_compact(const Dev &E, int R, Live live, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
     __shared__ int wsum[CPT / 64];
-    const int G = E.cfg.n_games, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int K = (G + CPT - 1) / CPT;
-    const int s0 = t * K, s1 = min(s0 + K, G);
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int K = (R + CPT - 1) / CPT;
+    const int r0 = t * K, r1 = min(r0 + K, R);
     int cnt = 0;
-    for (int s = s0; s < s1; ++s) {
-        const int ph = E.gi[(size_t)s * GI_N + GI_PHASE];
-        cnt += (ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF);
-    }
+    for (int r = r0; r < r1; ++r) cnt += live(r);
     int inc = cnt;                                    // inclusive scan within the wave
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -1760,15 +1475,17 @@ __global__ __launch_bounds__(CPT) void k_compact(Dev E, int32_t *__restrict__ n_
         base += w < wave ? v : 0;
         total += v;
     }
-    int r = base + inc - cnt;
-    for (int s = s0; s < s1; ++s) {
-        const int ph = E.gi[(size_t)s * GI_N + GI_PHASE];
-        if (ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF) rows[r++] = s;
-    }
+    int o = base + inc - cnt;
+    for (int r = r0; r < r1; ++r)
+        if (live(r)) rows[o++] = r;
     if (t == 0) {
         *n_live = total;
         E.stats[ST_ROWS] += (unsigned long long)total;   // slot 0's counter row: k_reduce_stats sums the column
     }
+}
+
+__global__ __launch_bounds__(CPT) void k_compact(Dev E, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
+    block_compact(E, E.cfg.n_games, [&](int s) { return slot_waits(E, s); }, n_live, rows);
 }
 
 // Gather of the packed rows: one workgroup per row of the capacity, rows past *n_live exit.  Per row the 5 400-byte
@@ -1803,41 +1520,8 @@ __global__ __launch_bounds__(256) void k_scatter_rows(const int32_t *__restrict_
 // j < its request-row count (1 for a root, the pending leaves for a leaf step); rows[r] is then that ROW's index, so
 // k_gather_rows / k_scatter_rows serve it unchanged over the row-indexed request buffers.
 __global__ __launch_bounds__(CPT) void k_compact_multi(Dev E, int K, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
-    __shared__ int wsum[CPT / 64];
-    const int R = E.cfg.n_games * K, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int RPT = (R + CPT - 1) / CPT;
-    const int r0 = t * RPT, r1 = min(r0 + RPT, R);
-    int cnt = 0;
-    for (int r = r0; r < r1; ++r) {
-        const int32_t *g = E.gi + (size_t)(r / K) * GI_N;
-        const int ph = g[GI_PHASE];
-        cnt += (ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF) && (r % K) < g[GI_NPEND];
-    }
-    int inc = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(inc, off);
-        if (lane >= off) inc += v;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < CPT / 64; ++w) {
-        const int v = wsum[w];
-        base += w < wave ? v : 0;
-        total += v;
-    }
-    int o = base + inc - cnt;
-    for (int r = r0; r < r1; ++r) {
-        const int32_t *g = E.gi + (size_t)(r / K) * GI_N;
-        const int ph = g[GI_PHASE];
-        if ((ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF) && (r % K) < g[GI_NPEND]) rows[o++] = r;
-    }
-    if (t == 0) {
-        *n_live = total;
-        E.stats[ST_ROWS] += (unsigned long long)total;
-    }
+    block_compact(E, E.cfg.n_games * K, [&](int r) { return slot_waits(E, r / K) && (r % K) < E.gi[(size_t)(r / K) * GI_N + GI_NPEND]; },
+                  n_live, rows);
 }
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1963,43 +1647,10 @@ __global__ __launch_bounds__(256) void k_evcache_probe(Dev E, EvDev C, const flo
     }
 }
 
-// Stable compaction of the misses (xq_engine_compact_misses): k_compact with the predicate "waiting and not a hit".  A copy,
-// not a shared template, so k_compact's code stays exactly what it was.
+// Stable compaction of the misses (xq_engine_compact_misses): k_compact with the predicate "waiting and not a hit".
 __global__ __launch_bounds__(CPT) void k_compact_misses(Dev E, const int32_t *__restrict__ hit, int32_t *__restrict__ n_live,
                                                         int32_t *__restrict__ rows) {
-    __shared__ int wsum[CPT / 64];
-    const int G = E.cfg.n_games, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int K = (G + CPT - 1) / CPT;
-    const int s0 = t * K, s1 = min(s0 + K, G);
-    int cnt = 0;
-    for (int s = s0; s < s1; ++s) {
-        const int ph = E.gi[(size_t)s * GI_N + GI_PHASE];
-        cnt += (ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF) && hit[s] == 0;
-    }
-    int inc = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(inc, off);
-        if (lane >= off) inc += v;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < CPT / 64; ++w) {
-        const int v = wsum[w];
-        base += w < wave ? v : 0;
-        total += v;
-    }
-    int r = base + inc - cnt;
-    for (int s = s0; s < s1; ++s) {
-        const int ph = E.gi[(size_t)s * GI_N + GI_PHASE];
-        if ((ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF) && hit[s] == 0) rows[r++] = s;
-    }
-    if (t == 0) {
-        *n_live = total;
-        E.stats[ST_ROWS] += (unsigned long long)total;   // rows the network really runs on
-    }
+    block_compact(E, E.cfg.n_games, [&](int s) { return slot_waits(E, s) && hit[s] == 0; }, n_live, rows);
 }
 
 // Commit: one wave per evaluated (packed) row r < n_live; the row's slot inserts the key it probed with this step.  One
@@ -2170,28 +1821,19 @@ bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE
 bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
 bool forced_of(const xq_engine *e) { return (e->pad0 & PAD0_FORCED) != 0; }
 
-// the K = 1 step's two kernels, by the engine's options
+// the K = 1 step's two kernels, by the engine's options: instance [FORCED][CAP][REUSE]
 void launch_select(const xq_engine *eng, const Dev &d, float *nn_in, hipStream_t s) {
+    static void (*const k[2][2][2])(Dev, float *) = {
+        {{k_select<false, false, false>, k_select<true, false, false>}, {k_select<false, true, false>, k_select<true, true, false>}},
+        {{k_select<false, false, true>, k_select<true, false, true>}, {k_select<false, true, true>, k_select<true, true, true>}}};
     const dim3 grid((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), block(64 * WAVES_PER_WG);
-    const bool reuse = reuse_of(eng), cap = cap_of(eng);
-    if (forced_of(eng)) {
-        if (reuse && cap) hipLaunchKernelGGL((k_select<true, true, true>), grid, block, 0, s, d, nn_in);
-        else if (reuse) hipLaunchKernelGGL((k_select<true, false, true>), grid, block, 0, s, d, nn_in);
-        else if (cap) hipLaunchKernelGGL((k_select<false, true, true>), grid, block, 0, s, d, nn_in);
-        else hipLaunchKernelGGL((k_select<false, false, true>), grid, block, 0, s, d, nn_in);
-    } else if (reuse && cap) hipLaunchKernelGGL((k_select<true, true>), grid, block, 0, s, d, nn_in);
-    else if (reuse) hipLaunchKernelGGL((k_select<true, false>), grid, block, 0, s, d, nn_in);
-    else if (cap) hipLaunchKernelGGL((k_select<false, true>), grid, block, 0, s, d, nn_in);
-    else hipLaunchKernelGGL((k_select<false, false>), grid, block, 0, s, d, nn_in);
+    hipLaunchKernelGGL(k[forced_of(eng)][cap_of(eng)][reuse_of(eng)], grid, block, 0, s, d, nn_in);
 }
 
 void launch_expand(const xq_engine *eng, const Dev &d, const float *policy, const float *value, int is_probs, hipStream_t s) {
-    const dim3 grid(eng->cfg.n_games), block(64);
-    const bool reuse = reuse_of(eng), cap = cap_of(eng);
-    if (reuse && cap) hipLaunchKernelGGL((k_expand<true, true>), grid, block, 0, s, d, policy, value, is_probs);
-    else if (reuse) hipLaunchKernelGGL((k_expand<true, false>), grid, block, 0, s, d, policy, value, is_probs);
-    else if (cap) hipLaunchKernelGGL((k_expand<false, true>), grid, block, 0, s, d, policy, value, is_probs);
-    else hipLaunchKernelGGL((k_expand<false, false>), grid, block, 0, s, d, policy, value, is_probs);
+    static void (*const k[2][2])(Dev, const float *, const float *, int) = {{k_expand<false, false>, k_expand<true, false>},
+                                                                            {k_expand<false, true>, k_expand<true, true>}};
+    hipLaunchKernelGGL(k[cap_of(eng)][reuse_of(eng)], dim3(eng->cfg.n_games), dim3(64), 0, s, d, policy, value, is_probs);
 }
 
 Mx make_mx(const xq_engine *e) {
