@@ -157,7 +157,9 @@ typedef struct xq_engine_stats {
                                  [XQ_STAT_REUSED_VISITS], [XQ_STAT_REROOTS]: the tree-reuse counters (xq_engine_init_ex);
                                  [XQ_STAT_FAST_MOVES], [XQ_STAT_FAST_SIMS]: the playout-cap counters (xq_engine_init_cap);
                                  [XQ_STAT_FORCED_SIMS], [XQ_STAT_PRUNED_VISITS], [XQ_STAT_PRUNED_CHILDREN]: forced playouts
-                                 (xq_engine_init_fp) */
+                                 (xq_engine_init_fp);
+                                 [XQ_STAT_GUMBEL_MOVES], [XQ_STAT_GUMBEL_CONSIDERED], [XQ_STAT_GUMBEL_OFFPRIOR]: Gumbel root search
+                                 (xq_engine_init_gz) */
 
 } xq_engine_stats;
 /* Leaf-batching counters (xq_engine_init_leaves), kept in the reserved words so the struct's layout is unchanged:
@@ -311,6 +313,69 @@ size_t xq_engine_workspace_bytes_fp(const xq_engine_config *cfg, int leaves_per_
 int xq_engine_init_fp(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
                       const xq_forced_playouts *forced, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream);
 
+/* Gumbel root search with sequential halving (opt-in; gumbel == NULL is xq_engine_init_fp exactly, and xq_engine_init_fp is that
+ * call).  The root rule of Gumbel AlphaZero (Danihelka et al., "Policy improvement by planning with Gumbel", ICLR 2022; the usual
+ * formulation is DeepMind's mctx): at the root, m moves are sampled without replacement by the Gumbel-top-k trick and the budget is
+ * spent on them by sequential halving; the training target is the completed-Q improved policy, not the visit counts.  Interior
+ * nodes keep PUCT.  Outside the reference-parity contract, like the other opt-in options.
+ * Parameters: considered = m, 1 <= m <= 128; c_visit >= 0 (mctx: 50); c_scale > 0 (mctx: 1.0 for two-player games here, values
+ * bounded by +-1); reserved = 0.  c_visit and c_scale are rounded to float32 ONCE at init and widened to double at every use.
+ * ROOT EXPANSION (every root of a Gumbel engine, self-play and manual_moves = 1).  The root has its float32 priors tP[i] over the cnt
+ * ordered legal moves exactly as without the option (uniform 1 / cnt when the network gave the legal moves no mass).
+ *     l_i = log((double)max(tP[i], FLT_MIN))
+ *     g_i = one Gumbel(0, 1) draw per legal move from the slot's Dirichlet stream (stream 2), whose counter advances by cnt:
+ *           device RNG  g = -log(-log(u)), u = ((x >> 11) + 0.5) * 2^-53 for the raw 64-bit draw x;
+ *           inject_len > 0  g = ((double)((x >> 40) % 4096) - 1024.0) / 512.0 (exact, no transcendental);
+ *           manual_moves = 1 with a non-null host_noise in xq_engine_set_position: the handed values ARE the g_i, no draw is taken.
+ *     rootP[i] = g_i + l_i  (float64), the root's prior kind is 3 (xq_engine_read_root: prior = rootP, *prior_kind = 3).
+ * The root never takes Dirichlet noise, whatever add_noise says.  The root's network value v_hat (the float32 widened) is kept for
+ * the end of the move.  The resign probe, terminal status and adjudication are unchanged.
+ * CONSIDERED VISITS.  considered_visits(k, S) is mctx's get_sequence_of_considered_visits, a sequence of length S:
+ *     k <= 1: t -> t.   Otherwise: L = ceil(log2(k)); c = k; base = 0; until S entries exist:
+ *       e = max(1, S / (L * c)) (integer division); append base, c times; base + 1, c times; ... base + e - 1, c times;
+ *       base += e; c = max(2, c / 2).
+ * xq_gumbel_considered_visits_host writes it for 1 <= k <= 128, 1 <= S <= 65535 (tests pin the table with it).
+ * ROOT SELECTION, in the descent at a node of kind 3 (always node 0); every other level is unchanged.  k = min(m, cnt); t = the
+ * root's visit count before this simulation; cv = considered_visits(k, S)[t].  The CANDIDATES are the children with N_i == cv.
+ *     cv == 0: the winner is the first maximum over the candidates of rootP[i];
+ *     cv  > 0: the first maximum over the candidates of rootP[i] + sigma(q_i),
+ *     sigma(q) = ((c_visit + maxN) * c_scale) * ((q + 1) * 0.5),  q_i = W_i / N_i,  maxN = the maximum of the children's N,
+ * all in float64, products and sums in the order written, no fused multiply-add.  No considered set is stored: the equal-visit
+ * rule is the sequential halving (the first k simulations take the k largest g + l in order, every later phase revisits the best
+ * of the children that reached the phase's count).  The fixed map (q + 1) / 2 replaces mctx's min-max rescaling of q: values here
+ * are bounded by +-1.  No candidate (never observed) sets overflow bit 8 << 8 like an all-NaN level.
+ * END OF A MOVE (self-play, root of kind 3).  maxN = max N_i, sumN = sum N_i, both over the children in move order.
+ *     played child = the first maximum, over the children with N_i == maxN, of rootP[i] + sigma(q_i).
+ * No temperature is applied and NO draw of the uniform stream (stream 3) is consumed.  The sample's visits[] hold the improved
+ * policy quantised to 16 bits:
+ *     v_mix = (v_hat + sumN * (sum_{N_b>0} tP[b] q_b / sum_{N_b>0} tP[b])) / (1 + sumN), the two sums float64, sequential in move
+ *             order over the float32 priors widened (a zero denominator takes v_hat for the quotient);
+ *     completed q_i = q_i if N_i > 0, else v_mix;
+ *     pi'_i = softmax_i(l_i + sigma(completed q_i)) in float64: x_i - max x, exp, the denominator summed sequentially in move order;
+ *     visits[i] = (uint16_t)floor(pi'_i * 65535 + 0.5).
+ * late_temp = 0 and reserved0 = 1 ("visits are a quantised improved policy"; 0 in every other sample).  The record size and every
+ * consumer stay as they are: they normalise visits by their sum, which lies within cnt / 2 of 65535.  The tree keeps its real N
+ * and W.  A search-only engine (manual_moves = 1) holds after S simulations as always.
+ * Counters, 0 without the option:
+ *   reserved[XQ_STAT_GUMBEL_MOVES]       moves chosen by a Gumbel search
+ *   reserved[XQ_STAT_GUMBEL_CONSIDERED]  the sum of k = min(m, cnt) over those moves
+ *   reserved[XQ_STAT_GUMBEL_OFFPRIOR]    those moves whose played child is not the first maximum of tP
+ * XQ_ERR_ARG before any launch (xq_engine_workspace_bytes_gz: 0): gumbel with manual_moves = 2 (arena), XQ_ENGINE_TREE_REUSE, a
+ * playout cap, forced playouts or leaves_per_step > 1; m outside [1, 128]; c_visit or c_scale not finite (as float32), c_visit < 0,
+ * c_scale <= 0; reserved != 0; and whatever xq_engine_init_fp refuses.  The evaluation cache and manual_moves = 1 are allowed.
+ * Workspace: the parameters, one double per slot and the tables for k = 1 .. m (2 m S bytes) lie behind the engine's square-root
+ * table; only Gumbel engines grow, "gumbel on" lives in the handle (pad0, above the public flag bits). */
+typedef struct xq_gumbel { int32_t considered; int32_t reserved; double c_visit; double c_scale; } xq_gumbel;
+#define XQ_STAT_GUMBEL_MOVES 10
+#define XQ_STAT_GUMBEL_CONSIDERED 11
+#define XQ_STAT_GUMBEL_OFFPRIOR 12
+size_t xq_engine_workspace_bytes_gz(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel);
+int xq_engine_init_gz(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, void *ws, size_t ws_bytes,
+                      const uint64_t *dev_inject, void *stream);
+int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out);
+
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 
 /* dev_policy[slot] = float32[8100]: network LOGITS (policy_is_probs = 0; softmax over all 8100 as
@@ -425,7 +490,8 @@ int xq_engine_set_position(const xq_engine *eng, int slot, const int8_t *host_bo
                            int no_capture, const int8_t *host_hist12 /* int8[12][90], oldest first, last
                            min(12,move_count) valid */, const double *host_noise /* eta per legal move or NULL */,
                            void *stream);
-/* Root children of `slot` after a search: returns n; arrays sized XQ_MAXM. prior_kind: 0 float32, 1 float64. */
+/* Root children of `slot` after a search: returns n; arrays sized XQ_MAXM. prior_kind: 0 float32, 1 float64, 3 float64 g + l of a
+ * Gumbel root (xq_engine_init_gz). */
 int xq_engine_read_root(const xq_engine *eng, int slot, uint16_t *actions, int32_t *visits, double *total_value,
                         double *prior, int *prior_kind, int32_t *root_visits, int32_t *sims_done, void *stream);
 

@@ -18,6 +18,7 @@
 // PUCT evaluated in float32 as f32(q) + ((f32(c)*P)*f32(sqrt(N_parent)))/f32(1+N); at a noisy root (and for the
 // uniform fallback) priors and PUCT are float64; W accumulates in float64; first maximum wins.
 // Floating-point contraction is OFF for this file.
+#include <float.h>
 #include <math.h>
 #include <string.h>
 
@@ -48,7 +49,8 @@ static_assert(GI_FP_K == 31, "the forced-playout parameter takes the last free s
 
 enum St : int { ST_SIMS = 0, ST_TERM, ST_LEAF, ST_ROOT, ST_MOVES, ST_GAMES, ST_RED, ST_BLACK, ST_DRAW, ST_PLIES, ST_NODES,
                 ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_COLL, ST_LPS, ST_LSTEPS, ST_REUSED,
-                ST_REROOTS, ST_FASTM, ST_FASTS, ST_FORCED, ST_PRUNEDV, ST_PRUNEDC, ST_N = 32 };
+                ST_REROOTS, ST_FASTM, ST_FASTS, ST_FORCED, ST_PRUNEDV, ST_PRUNEDC, ST_GZ_MOVES, ST_GZ_CONS, ST_GZ_OFF, ST_N = 32 };
+static_assert(ST_GZ_OFF == 31, "the Gumbel counters take the last free statistics words");
 
 enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_TW, P_TP, P_TA, P_TC, P_TM, P_ROOTP,
                  P_STAGE, P_OUTS, P_OUTR, P_CNT, P_STATS, P_INJECT, P_SQRT, P_MNOISE, P_STATSUM, P_REQ,
@@ -91,6 +93,39 @@ Dev make_dev(const xq_engine *e) {
     d.stats = (unsigned long long *)e->p[P_STATS]; d.inject = (const uint64_t *)e->p[P_INJECT];
     d.sqrt_tab = (const double *)e->p[P_SQRT]; d.mnoise = (double *)e->p[P_MNOISE]; d.req = (int32_t *)e->p[P_REQ];
     return d;
+}
+
+// Gumbel root search (xq_engine_init_gz): its words live behind the square-root table, in that table's workspace region (the handle,
+// the config struct and the per-slot state words are full): the parameters, the root's network value of every slot, and the
+// considered-visit tables, row k - 1 for k considered moves.  K = 1 always, so the square-root table has S + 2 entries.
+struct GzHead {
+    int32_t m;                      // considered moves at most
+    float c_visit, c_scale;         // rounded to float32 once, widened at every use
+    int32_t pad;
+};
+static_assert(sizeof(GzHead) == 16, "GzHead layout");
+
+size_t gz_bytes(size_t G, size_t S, size_t m) { return sizeof(GzHead) + G * 8 + m * S * 2; }
+
+__device__ __forceinline__ const GzHead *gz_head(const Dev &E) { return (const GzHead *)(E.sqrt_tab + E.cfg.num_simulations + 2); }
+__device__ __forceinline__ double *gz_vhat(const Dev &E) { return (double *)(gz_head(E) + 1); }
+__device__ __forceinline__ const uint16_t *gz_table(const Dev &E) { return (const uint16_t *)(gz_vhat(E) + E.cfg.n_games); }
+
+// get_sequence_of_considered_visits(k, S) of include/xq_hip.h: out[t] = the visit count a root child must have to be a
+// candidate of simulation t
+__host__ void gz_considered_visits(int k, int S, uint16_t *out) {
+    if (k <= 1) { for (int t = 0; t < S; ++t) out[t] = (uint16_t)t; return; }
+    int log2max = 0;
+    while ((1 << log2max) < k) ++log2max;
+    int n = 0, considered = k, base = 0;           // every considered move has `base` visits when a phase starts
+    while (n < S) {
+        int extra = S / (log2max * considered);
+        if (extra < 1) extra = 1;
+        for (int e = 0; e < extra; ++e)
+            for (int i = 0; i < considered && n < S; ++i) out[n++] = (uint16_t)(base + e);
+        base += extra;
+        considered = considered / 2 > 2 ? considered / 2 : 2;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -543,6 +578,88 @@ __device__ __forceinline__ int slot_end_move(const Dev &E, Slot &s, SelectLds &L
     return __builtin_amdgcn_readfirstlane((int)L.sa[pick]);
 }
 
+// GUMBEL: the end of a self-play move at a root of prior kind 3 (include/xq_hip.h).  The played child is the first maximum, over
+// the children with N_i == maxN, of rootP[i] + sigma(q_i): no temperature and no draw.  The sample's visits[] are the completed-Q
+// improved policy softmax(l_i + sigma(completed q_i)) quantised to 16 bits (reserved0 = 1 says so).  maxN, sumN and the two
+// prior-weighted sums run sequentially in move order over LDS (every lane the same scan), so the host model can repeat them bit
+// for bit; the maxima are wave reductions.  `considered` / `offprior` take the move's k and whether the played child is not the
+// first maximum of the float32 priors.
+__device__ __forceinline__ int slot_end_move_gumbel(const Dev &E, Slot &s, SelectLds &L, const double *rootP, int nch, int first,
+                                                    unsigned &considered, unsigned &offprior) {
+    const Tree &T = s.T;
+    const int lane = s.lane;
+    uint8_t *rec = E.stage + ((size_t)s.slot * E.stage_cap + (s.n_samples < E.stage_cap ? s.n_samples : E.stage_cap - 1)) * XQ_SAMPLE_BYTES;
+    if (s.n_samples >= E.stage_cap) s.ovf |= 4;
+    for (int i = lane; i < XQ_SAMPLE_BYTES / 4; i += 64) ((uint32_t *)rec)[i] = 0u;
+    wave_sync_mem();
+    for (int i = lane; i < 90; i += 64) rec[i] = (uint8_t)L.root[i];
+    if (lane == 0) {
+        xq_sample *r = (xq_sample *)rec;
+        r->side = (int8_t)s.side; r->z = 0; r->n_moves = (uint8_t)nch; r->late_temp = 0;
+        r->ply = (uint16_t)s.mc; r->reserved0 = 1; r->slot = (uint32_t)s.slot; r->game_seq = (uint32_t)s.game_seq;
+    }
+    for (int i = lane; i < nch; i += 64) {
+        const int n = T.N[first + i];
+        L.a_tmp[i] = (uint16_t)n;                                 // n <= S < 16000
+        L.sw[i] = n ? T.W[first + i] / (double)n : 0.0;           // q_i
+        L.cdf[i] = (double)T.P[first + i];
+    }
+    wave_sync();
+    int max_n = 0, sum_n = 0;
+    double num = 0.0, den = 0.0;
+    for (int i = 0; i < nch; ++i) {
+        const int n = L.a_tmp[i];
+        max_n = n > max_n ? n : max_n;
+        sum_n += n;
+        if (n > 0) { const double p = L.cdf[i]; num += p * L.sw[i]; den += p; }
+    }
+    const GzHead *h = gz_head(E);
+    const double v_hat = gz_vhat(E)[s.slot];
+    const double scale = ((double)h->c_visit + (double)max_n) * (double)h->c_scale;
+    const double v_mix = (v_hat + (double)sum_n * (den > 0.0 ? num / den : v_hat)) / (1.0 + (double)sum_n);
+    // per child: the logit of the improved policy, and the move-choice score of the most-visited children
+    double bx = -INFINITY, bs = -INFINITY;
+    float bp = -INFINITY;
+    int bs_i = 0x7FFFFFFF, bp_i = 0x7FFFFFFF;
+    for (int i = lane; i < nch; i += 64) {
+        const int n = L.a_tmp[i];
+        const double q = L.sw[i];
+        const float p = T.P[first + i];
+        const double x = log((double)fmaxf(p, FLT_MIN)) + scale * (((n ? q : v_mix) + 1.0) * 0.5);
+        L.w_tmp[i] = x;
+        bx = x > bx ? x : bx;
+        if (n == max_n) {
+            const double sc = rootP[i] + scale * ((q + 1.0) * 0.5);
+            if (sc > bs) { bs = sc; bs_i = i; }
+        }
+        if (p > bp) { bp = p; bp_i = i; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ox = __shfl_xor(bx, off), os = __shfl_xor(bs, off);
+        const float op = __shfl_xor(bp, off);
+        const int osi = __shfl_xor(bs_i, off), opi = __shfl_xor(bp_i, off);
+        bx = ox > bx ? ox : bx;
+        if (os > bs || (os == bs && osi < bs_i)) { bs = os; bs_i = osi; }
+        if (op > bp || (op == bp && opi < bp_i)) { bp = op; bp_i = opi; }
+    }
+    bs_i = __builtin_amdgcn_readfirstlane(bs_i);
+    bp_i = __builtin_amdgcn_readfirstlane(bp_i);
+    if (bs_i == 0x7FFFFFFF) { s.ovf |= 8; bs_i = 0; }             // all-NaN scores
+    for (int i = lane; i < nch; i += 64) L.w_tmp[i] = exp(L.w_tmp[i] - bx);
+    wave_sync();
+    double total = 0.0;
+    for (int i = 0; i < nch; ++i) total += L.w_tmp[i];
+    for (int i = lane; i < nch; i += 64) {
+        ((xq_sample *)rec)->actions[i] = T.A[first + i];
+        ((xq_sample *)rec)->visits[i] = (uint16_t)floor((L.w_tmp[i] / total) * 65535.0 + 0.5);
+    }
+    considered = (unsigned)min((int)h->m, nch);
+    offprior = bs_i != bp_i ? 1u : 0u;
+    s.n_samples += 1;
+    return __builtin_amdgcn_readfirstlane((int)T.A[first + bs_i]);
+}
+
 // The leaf a descent ends on, and the simulated position there (its board and ring are SelectLds.board / .hist)
 struct Leaf {
     int node, depth, side, mc, nocap;
@@ -552,12 +669,15 @@ struct Leaf {
 // VL (leaf batching): each in-flight descent through a node counts as a visit and as a loss for the side choosing there (W is
 // from the chooser's view): n = N + vl in q and in 1 + n, w = W - vl, parent count N + vl; vl = 0 gives the plain values exactly.
 // FORCED: at a root of prior kind 1 a visited child below its minimum share of the root's visits scores +infinity.
+// GUMBEL: at a root of prior kind 3 the candidates are the children whose N equals this simulation's considered-visit count
+// (the sequential halving); they score rootP[i] = g_i + l_i plus, once visited, sigma(q_i), everyone else -infinity.  sigma needs
+// the maximum of the children's N first: one more pass over the (at most 128) counts and one more wave reduction, at that level only.
 //
 // One dependent round trip to memory per level: every lane reads, with its candidate child's N / W / P, that child's own
 // node words (children count + kind, first child, action) as well, so the winner's are already in a register when the arg-max
 // is known -- the next level starts from a lane read instead of three more dependent loads (tM -> tC/tN -> ... -> tA).  The
 // winner's N, read here, IS the next level's parent count.
-template <bool VL, bool FORCED>
+template <bool VL, bool FORCED, bool GUMBEL = false>
 __device__ __forceinline__ Leaf wave_descend(const Dev &E, Slot &s, SelectLds &L, const int32_t *vl, const double *rootP, float fp_k,
                                              int32_t *path) {
     const Tree &T = s.T;
@@ -579,6 +699,18 @@ __device__ __forceinline__ Leaf wave_descend(const Dev &E, Slot &s, SelectLds &L
         double best = -INFINITY;
         int best_i = 0x7FFFFFFF;
         int c_m = 0, c_first = 0, c_n = 0, c_a = 0;              // node words of this lane's best candidate
+        double gz_scale = 0.0;                                   // GUMBEL, kind 3: (c_visit + maxN) * c_scale
+        int gz_cv = 0;                                           //                 the considered-visit count of this simulation
+        if (GUMBEL && kind == 3) {
+            int mx = 0;
+            for (int i = lane; i < nch; i += 64) mx = max(mx, T.N[first + i]);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off));
+            const GzHead *h = gz_head(E);
+            const int S = E.cfg.num_simulations, k = min(h->m, nch);
+            gz_scale = ((double)h->c_visit + (double)mx) * (double)h->c_scale;
+            gz_cv = (int)gz_table(E)[(size_t)(k - 1) * S + min(pn, S - 1)];
+        }
         for (int base = 0; base < nch; base += 64) {
             const int i = base + lane;
             if (i < nch) {
@@ -588,7 +720,9 @@ __device__ __forceinline__ Leaf wave_descend(const Dev &E, Slot &s, SelectLds &L
                 const int cm = (int)T.M[first + i], cf = T.C[first + i], ca = (int)T.A[first + i];
                 const double q = n ? w / (double)n : 0.0;
                 double ucb;
-                if (kind == 0) {
+                if (GUMBEL && kind == 3) {
+                    ucb = n != gz_cv ? -INFINITY : (gz_cv > 0 ? rootP[i] + gz_scale * ((q + 1.0) * 0.5) : rootP[i]);
+                } else if (kind == 0) {
                     float t = c_f * T.P[first + i];
                     t = t * sqrtp_f;
                     t = t / (float)(1 + n);
@@ -659,8 +793,9 @@ constexpr int WAVES_PER_WG = 4;
 // Nothing for the instances without forced playouts (0, 0 emits no attribute).  The FORCED instances are held to the same two
 // waves per SIMD: left alone, the two with CAP take 256 VGPRs plus a few AGPRs and halve their occupancy.  Headroom of the
 // unpinned instances: <0,1,0> and <1,1,0> stand at 255 of the 256 VGPRs that two waves allow, the others at 244 / 245, so a
-// change to a shared helper wants the resource table regenerated (profiles/r11_shared_search_phases_kernel_resource_usage.txt).
-#define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu(FORCED ? 2 : 0, FORCED ? 2 : 0)))
+// change to a shared helper wants the resource table regenerated (profiles/r12_gumbel_kernel_resource_usage.txt).  The GUMBEL
+// instance is held to two waves like the FORCED ones.
+#define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu((FORCED || GUMBEL) ? 2 : 0, (FORCED || GUMBEL) ? 2 : 0)))
 #endif
 // REUSE (tree reuse): at the end of a move the chosen child and the old allocation mark are handed to k_reroot and
 // k_expand<true> of the same step (GI_RR_NODE / GI_RR_MARK).
@@ -671,7 +806,11 @@ constexpr int WAVES_PER_WG = 4;
 // move, always node 0 -- a visited child i with N_i^2 < (k rootP[i]) N_root scores +infinity in the descent (the first maximum
 // then takes the lowest-index forced child), and at the move's end the sample's visits and the move-choice weights are the
 // PRUNED counts v_i (include/xq_hip.h); the tree keeps its N and W.
-template <bool REUSE, bool CAP = false, bool FORCED = false>
+// GUMBEL (Gumbel root search with sequential halving, xq_engine_init_gz; one instance, <false, false, false, true>): the root of
+// every searched position has prior kind 3 (k_expand<.., .., true>); the descent picks among its equal-visit candidates
+// (wave_descend), and a self-play move ends in slot_end_move_gumbel: no temperature, no uniform draw, the improved policy as the
+// sample's target.  Every other level is the PUCT of the other instances.
+template <bool REUSE, bool CAP = false, bool FORCED = false, bool GUMBEL = false>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev E, float *__restrict__ nn_in) {
     __shared__ SelectLds Ls[WAVES_PER_WG];
     SelectLds &L = Ls[threadIdx.x >> 6];
@@ -708,6 +847,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
     unsigned long long d_fast_moves = 0, d_fast_sims = 0;
     // FORCED: k, a float32 widened at every use
     const float fp_k = FORCED ? __int_as_float(__builtin_amdgcn_readfirstlane(gi[GI_FP_K])) : 0.0f;
+    unsigned d_gz_moves = 0, d_gz_cons = 0, d_gz_off = 0;      // GUMBEL only
 
     lds_copy_dwords(L.root, E.board + (size_t)slot * XQ_BS, XQ_BS / 4);
     lds_copy_dwords(L.rhist, E.hist + (size_t)slot * XQ_HIST * XQ_BS, XQ_HIST * XQ_BS / 4);
@@ -750,6 +890,13 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
             const int first = __builtin_amdgcn_readfirstlane(T.C[0]);
             phase = PH_NEWPOS;
             if (arena) { slot_arena_move(s, L, nch, first); continue; }
+            if (GUMBEL && (__builtin_amdgcn_readfirstlane((int)T.M[0]) >> 14) == 3) {
+                unsigned cons, off;
+                const int action = slot_end_move_gumbel(E, s, L, rootP, nch, first, cons, off);
+                d_gz_moves += 1; d_gz_cons += cons; d_gz_off += off;
+                slot_play(s, L, action);
+                continue;
+            }
             const bool pruned = FORCED && (__builtin_amdgcn_readfirstlane((int)T.M[0]) >> 14) == 1;
             if (pruned) wave_prune_visits(E, s, L, rootP, fp_k, nch, first);
             const int action = slot_end_move(E, s, L, full_move, pruned, nch, first);
@@ -770,7 +917,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
             if (CAP && !full_move) d_fast_moves += 1;
             continue;
         }
-        const Leaf lf = wave_descend<false, FORCED>(E, s, L, nullptr, rootP, fp_k, path);
+        const Leaf lf = wave_descend<false, FORCED, GUMBEL>(E, s, L, nullptr, rootP, fp_k, path);
         s.d_depth += (unsigned)lf.depth;
         int cnt, winner;
         const bool term = wave_game_over(L.board, L.hist, lf.side, lf.mc, lf.nocap, L.mg, L.moves, &cnt, &winner, &s.ovf);
@@ -799,6 +946,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
         E.req[slot] = (phase == PH_WAIT_ROOT || phase == PH_WAIT_LEAF) ? req_cnt : 0;
         if (CAP) { s.st[ST_FASTM] += d_fast_moves; s.st[ST_FASTS] += d_fast_sims; }
         if (FORCED) { s.st[ST_FORCED] += s.d_forced; s.st[ST_PRUNEDV] += s.d_prunedv; s.st[ST_PRUNEDC] += s.d_prunedc; }
+        if (GUMBEL) { s.st[ST_GZ_MOVES] += d_gz_moves; s.st[ST_GZ_CONS] += d_gz_cons; s.st[ST_GZ_OFF] += d_gz_off; }
     }
 }
 
@@ -937,6 +1085,32 @@ __device__ __forceinline__ int wave_write_priors(const Dev &E, const ExpandLds &
     return noisy ? 1 : 2;
 }
 
+// GUMBEL root: rootP[i] = g_i + l_i over the float32 priors this lane wrote to tP just before (wave_write_priors, the same
+// lane-to-child map), l_i = log((double)max(tP[i], FLT_MIN)), g_i one Gumbel(0, 1) draw per legal move from the slot's Dirichlet
+// stream (or the values set by hand).  The root's network value is kept for the end of the move.
+__device__ __forceinline__ void wave_gumbel_root(const Dev &E, int32_t *gi, unsigned long long *st, int slot, const float *tP,
+                                                 double *rootP, int cnt, double v_net) {
+    const int lane = lane_id();
+    const bool by_hand = gi[GI_MANNOISE] != 0;
+    const double *mn = E.mnoise + (size_t)slot * XQ_MAXM;
+    const int ctr0 = gi[GI_RNG0 + RNG_DIRICHLET];
+    for (int i = lane; i < cnt; i += 64) {
+        double g;
+        if (by_hand) {
+            g = mn[i];
+        } else {
+            const uint64_t x = draw_u64(E, slot, RNG_DIRICHLET, ctr0 + i, st);
+            if (E.cfg.inject_len > 0) g = ((double)(int)((x >> 40) % 4096ull) - 1024.0) / 512.0;   // exact: no transcendental
+            else g = -log(-log(((double)(x >> 11) + 0.5) * (1.0 / 9007199254740992.0)));
+        }
+        rootP[i] = g + log((double)fmaxf(tP[i], FLT_MIN));
+    }
+    if (lane == 0) {
+        if (!by_hand) gi[GI_RNG0 + RNG_DIRICHLET] = ctr0 + cnt;
+        gz_vhat(E)[slot] = v_net;
+    }
+}
+
 // fresh children of `node` at [first, first + cnt), in move order
 __device__ __forceinline__ void wave_new_children(const Tree &T, const ExpandLds &L, unsigned long long *st, int node, int first,
                                                   int cnt, int kind) {
@@ -957,7 +1131,8 @@ __device__ __forceinline__ void wave_new_children(const Tree &T, const ExpandLds
 // float32 priors, draws fresh noise into rootP and starts the search at sims_done = root N = the sum of their visits.
 // CAP (k_expand<.., true>): the root of a fast move (GI_CAP_FULL == 0) takes the no-noise path: no Dirichlet draw, rootP unused,
 // prior kind 0 (or 2), also when it is a reused root; a leaf backed up under a fast move counts in ST_FASTS.
-template <bool REUSE, bool CAP = false>
+// GUMBEL (k_expand<false, false, true>): a root never takes Dirichlet noise; it gets prior kind 3 and rootP = g + l.
+template <bool REUSE, bool CAP = false, bool GUMBEL = false>
 __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ policy, const float *__restrict__ value,
                                                int is_probs) {
     __shared__ ExpandLds L;
@@ -994,7 +1169,7 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
 
     const float sum = wave_priors(L, policy + (size_t)slot * (is_probs == 2 ? XQ_MAXM : XQ_ACTION_SPACE), pmoves, cnt, is_probs);
     const bool full_move = CAP ? __builtin_amdgcn_readfirstlane(gi[GI_CAP_FULL]) != 0 : true;
-    const bool noisy = is_root && full_move && (E.cfg.add_noise != 0 || gi[GI_MANNOISE] != 0);
+    const bool noisy = !GUMBEL && is_root && full_move && (E.cfg.add_noise != 0 || gi[GI_MANNOISE] != 0);
     if (noisy) wave_root_noise(E, L, gi, st, slot, cnt);
 
     const int node = is_root ? 0 : __builtin_amdgcn_readfirstlane(gi[GI_PLEAF]);
@@ -1016,7 +1191,11 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
         if (first + cnt > E.node_cap) {
             ovf |= 32;
         } else {
-            const int kind = wave_write_priors(E, L, T.P + first, rootP, cnt, sum, noisy);
+            int kind = wave_write_priors(E, L, T.P + first, rootP, cnt, sum, noisy);
+            if (GUMBEL && is_root) {
+                wave_gumbel_root(E, gi, st, slot, T.P + first, rootP, cnt, v_net);
+                kind = 3;
+            }
             if (REUSE && reused) {
                 // the kept children keep N, W, action, first child and meta; the budget is visits: sims_done = root N = sum N
                 int vis = 0, bad = 0;
@@ -1736,8 +1915,9 @@ struct Layout {
 };
 
 // K > 1 (leaf batching): the request rows (moves, counts, paths, packed buffers) are G K, slot-major; the virtual-loss
-// counters and the pending-leaf records follow the K = 1 layout, which is unchanged.
-Layout make_layout(const xq_engine_config *c, int K = 1) {
+// counters and the pending-leaf records follow the K = 1 layout, which is unchanged.  gz_m > 0 (Gumbel root search, K = 1): the
+// square-root table's region also holds the Gumbel words (gz_bytes); every other engine has the layout it had.
+Layout make_layout(const xq_engine_config *c, int K = 1, int gz_m = 0) {
     Layout l;
     memset(&l, 0, sizeof(l));
     const size_t G = (size_t)c->n_games, S = (size_t)c->num_simulations, GK = G * (size_t)K;
@@ -1766,7 +1946,7 @@ Layout make_layout(const xq_engine_config *c, int K = 1) {
     put(P_OUTR, (size_t)(c->max_out_results > 0 ? c->max_out_results : 1) * XQ_RESULT_BYTES);
     put(P_CNT, 64);
     put(P_STATS, G * ST_N * 8);
-    put(P_SQRT, (S + 2 + (K > 1 ? (size_t)K : 0)) * 8);
+    put(P_SQRT, (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0));
     put(P_MNOISE, G * XQ_MAXM * 8);
     put(P_STATSUM, ST_N * 8);
     put(P_REQ, GK * 4);
@@ -1812,27 +1992,48 @@ bool forced_ok(const xq_engine_config *c, int K, const xq_forced_playouts *fp) {
     return fp->k > 0.0 && fp->k <= 16.0;
 }
 
+// Gumbel root search: self-play or search only, one leaf per step, none of tree reuse, playout cap and forced playouts;
+// 1 <= m <= XQ_MAXM, c_visit >= 0 and c_scale > 0, finite as the float32 values the kernels use (a NaN fails the comparisons)
+bool gumbel_ok(const xq_engine_config *c, int K, unsigned flags, const xq_playout_cap *cap, const xq_forced_playouts *forced,
+               const xq_gumbel *gz) {
+    if (c->manual_moves == 2 || K != 1 || (flags & XQ_ENGINE_TREE_REUSE) || cap || forced || gz->reserved != 0) return false;
+    if (!(gz->c_visit >= 0.0 && gz->c_visit <= (double)FLT_MAX && gz->c_scale > 0.0 && gz->c_scale <= (double)FLT_MAX)) return false;
+    return gz->considered >= 1 && gz->considered <= XQ_MAXM && (float)gz->c_scale > 0.0f;
+}
+
 // pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
-// flag bits "playout cap on" (xq_engine_init_cap) and "forced playouts on" (xq_engine_init_fp)
+// flag bits "playout cap on" (xq_engine_init_cap), "forced playouts on" (xq_engine_init_fp) and "Gumbel root search on"
+// (xq_engine_init_gz)
 constexpr int PAD0_CAP = 1 << 30;
 constexpr int PAD0_FORCED = 1 << 29;
+constexpr int PAD0_GUMBEL = 1 << 28;
 int leaves_of(const xq_engine *e) { return (e->pad0 & 0xFFFF) > 1 ? (e->pad0 & 0xFFFF) : 1; }
 bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE_TREE_REUSE; }
 bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
 bool forced_of(const xq_engine *e) { return (e->pad0 & PAD0_FORCED) != 0; }
+bool gumbel_of(const xq_engine *e) { return (e->pad0 & PAD0_GUMBEL) != 0; }
 
-// the K = 1 step's two kernels, by the engine's options: instance [FORCED][CAP][REUSE]
+// the K = 1 step's two kernels, by the engine's options: instance [FORCED][CAP][REUSE]; a Gumbel engine has none of the three
+// and its own instance of each kernel
 void launch_select(const xq_engine *eng, const Dev &d, float *nn_in, hipStream_t s) {
     static void (*const k[2][2][2])(Dev, float *) = {
         {{k_select<false, false, false>, k_select<true, false, false>}, {k_select<false, true, false>, k_select<true, true, false>}},
         {{k_select<false, false, true>, k_select<true, false, true>}, {k_select<false, true, true>, k_select<true, true, true>}}};
     const dim3 grid((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), block(64 * WAVES_PER_WG);
+    if (gumbel_of(eng)) {
+        hipLaunchKernelGGL((k_select<false, false, false, true>), grid, block, 0, s, d, nn_in);
+        return;
+    }
     hipLaunchKernelGGL(k[forced_of(eng)][cap_of(eng)][reuse_of(eng)], grid, block, 0, s, d, nn_in);
 }
 
 void launch_expand(const xq_engine *eng, const Dev &d, const float *policy, const float *value, int is_probs, hipStream_t s) {
     static void (*const k[2][2])(Dev, const float *, const float *, int) = {{k_expand<false, false>, k_expand<true, false>},
                                                                             {k_expand<false, true>, k_expand<true, true>}};
+    if (gumbel_of(eng)) {
+        hipLaunchKernelGGL((k_expand<false, false, true>), dim3(eng->cfg.n_games), dim3(64), 0, s, d, policy, value, is_probs);
+        return;
+    }
     hipLaunchKernelGGL(k[cap_of(eng)][reuse_of(eng)], dim3(eng->cfg.n_games), dim3(64), 0, s, d, policy, value, is_probs);
 }
 
@@ -1873,6 +2074,20 @@ size_t xq_engine_workspace_bytes_fp(const xq_engine_config *cfg, int leaves_per_
     return make_layout(cfg, leaves_per_step).total;   // tree reuse, the playout cap and forced playouts need no workspace of their own
 }
 
+size_t xq_engine_workspace_bytes_gz(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel) {
+    if (!gumbel) return xq_engine_workspace_bytes_fp(cfg, leaves_per_step, flags, cap, forced);
+    if (!config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags)) return 0;
+    if (!gumbel_ok(cfg, leaves_per_step, flags, cap, forced, gumbel)) return 0;
+    return make_layout(cfg, 1, gumbel->considered).total;
+}
+
+int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out) {
+    if (k < 1 || k > XQ_MAXM || num_simulations < 1 || num_simulations > 65535 || !host_out) return XQ_ERR_ARG;
+    gz_considered_visits(k, num_simulations, host_out);
+    return XQ_OK;
+}
+
 int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t ws_bytes, const uint64_t *dev_inject,
                    void *stream) {
     return xq_engine_init_ex(eng, cfg, 1, 0u, ws, ws_bytes, dev_inject, stream);
@@ -1895,19 +2110,26 @@ int xq_engine_init_cap(xq_engine *eng, const xq_engine_config *cfg, int leaves_p
 
 int xq_engine_init_fp(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
                       const xq_forced_playouts *forced, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
+    return xq_engine_init_gz(eng, cfg, leaves_per_step, flags, cap, forced, nullptr, ws, ws_bytes, dev_inject, stream);
+}
+
+int xq_engine_init_gz(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, void *ws, size_t ws_bytes,
+                      const uint64_t *dev_inject, void *stream) {
     if (!eng || !config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags) || !ws ||
         ((uintptr_t)ws & 255))
         return XQ_ERR_ARG;
     if (cap && !cap_ok(cfg, leaves_per_step, cap)) return XQ_ERR_ARG;
     if (forced && !forced_ok(cfg, leaves_per_step, forced)) return XQ_ERR_ARG;
+    if (gumbel && !gumbel_ok(cfg, leaves_per_step, flags, cap, forced, gumbel)) return XQ_ERR_ARG;
     if (cfg->inject_len > 0 && !dev_inject) return XQ_ERR_ARG;
     const int K = leaves_per_step;
-    const Layout l = make_layout(cfg, K);
+    const Layout l = make_layout(cfg, K, gumbel ? gumbel->considered : 0);
     if (ws_bytes < l.total) return XQ_ERR_WORKSPACE;
     memset(eng, 0, sizeof(*eng));
     eng->cfg = *cfg;
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
-    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16) | (cap ? PAD0_CAP : 0) | (forced ? PAD0_FORCED : 0);
+    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16) | (cap ? PAD0_CAP : 0) | (forced ? PAD0_FORCED : 0) | (gumbel ? PAD0_GUMBEL : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -1922,10 +2144,19 @@ int xq_engine_init_fp(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
     XQ_TRY(hipMemsetAsync(eng->p[P_PK_MOVES], 0, l.total - l.off[P_PK_MOVES], s));
     {
         const int n = cfg->num_simulations + 2 + (K > 1 ? K : 0);   // K > 1: N_parent + vl_parent < S + K
-        double *tab = (double *)malloc(sizeof(double) * n);
+        // Gumbel root search: the parameters, a zeroed v_hat per slot and the considered-visit tables for k = 1 .. m follow the table
+        const size_t S = (size_t)cfg->num_simulations, G = (size_t)cfg->n_games;
+        const size_t bytes = sizeof(double) * n + (gumbel ? gz_bytes(G, S, (size_t)gumbel->considered) : 0);
+        double *tab = (double *)calloc(bytes, 1);
         if (!tab) return XQ_ERR_ARG;
         for (int i = 0; i < n; ++i) tab[i] = sqrt((double)i);   // math.sqrt(visit_count), mcts.py:49
-        const int rc = xq::check(hipMemcpyAsync(eng->p[P_SQRT], tab, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        if (gumbel) {
+            GzHead *h = (GzHead *)(tab + n);
+            h->m = gumbel->considered; h->c_visit = (float)gumbel->c_visit; h->c_scale = (float)gumbel->c_scale;
+            uint16_t *vis = (uint16_t *)((char *)(h + 1) + G * 8);
+            for (int k = 1; k <= gumbel->considered; ++k) gz_considered_visits(k, (int)S, vis + (size_t)(k - 1) * S);
+        }
+        const int rc = xq::check(hipMemcpyAsync(eng->p[P_SQRT], tab, bytes, hipMemcpyHostToDevice, s));
         if (rc == XQ_OK) (void)hipStreamSynchronize(s);
         free(tab);
         if (rc != XQ_OK) return rc;
@@ -2069,6 +2300,8 @@ int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *
     host_out->reserved[XQ_STAT_FAST_MOVES] = h[ST_FASTM]; host_out->reserved[XQ_STAT_FAST_SIMS] = h[ST_FASTS];
     host_out->reserved[XQ_STAT_FORCED_SIMS] = h[ST_FORCED]; host_out->reserved[XQ_STAT_PRUNED_VISITS] = h[ST_PRUNEDV];
     host_out->reserved[XQ_STAT_PRUNED_CHILDREN] = h[ST_PRUNEDC];
+    host_out->reserved[XQ_STAT_GUMBEL_MOVES] = h[ST_GZ_MOVES]; host_out->reserved[XQ_STAT_GUMBEL_CONSIDERED] = h[ST_GZ_CONS];
+    host_out->reserved[XQ_STAT_GUMBEL_OFFPRIOR] = h[ST_GZ_OFF];
     return h[ST_OVF] ? XQ_ERR_OVERFLOW : XQ_OK;
 }
 
@@ -2152,13 +2385,13 @@ int xq_engine_read_root(const xq_engine *eng, int slot, uint16_t *actions, int32
     const int n = m & 0x3FFF, kind = m >> 14;
     if (root_visits) *root_visits = rn;
     if (sims_done) *sims_done = gi[GI_SIMS];
-    if (prior_kind) *prior_kind = kind == 0 ? 0 : 1;
+    if (prior_kind) *prior_kind = kind == 0 ? 0 : (kind == 3 ? 3 : 1);
     if (n == 0) return 0;
     float pf[XQ_MAXM];
     XQ_TRY(hipMemcpy(actions, (uint16_t *)eng->p[P_TA] + nb + first, (size_t)n * 2, hipMemcpyDeviceToHost));
     XQ_TRY(hipMemcpy(visits, (int32_t *)eng->p[P_TN] + nb + first, (size_t)n * 4, hipMemcpyDeviceToHost));
     XQ_TRY(hipMemcpy(total_value, (double *)eng->p[P_TW] + nb + first, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (kind == 1) {
+    if (kind == 1 || kind == 3) {
         XQ_TRY(hipMemcpy(prior, (double *)eng->p[P_ROOTP] + (size_t)slot * XQ_MAXM, (size_t)n * 8, hipMemcpyDeviceToHost));
     } else if (kind == 2) {
         for (int i = 0; i < n; ++i) prior[i] = 1.0 / (double)n;

@@ -53,6 +53,13 @@ spent by itself are subtracted again before the visit counts become the sample's
 sample's visits sum to at most S.  The tree keeps its real counts.  `stats()` adds `forced_sims`, `pruned_visits` and
 `pruned_children`.  Self-play with root noise only, K = 1; it combines with tree reuse, the playout cap (full moves only) and
 the evaluation cache.
+
+With `gumbel=(m, c_visit, c_scale)` (opt-in, 1 <= m <= 128, mctx uses c_visit = 50 and c_scale = 1; xq_engine_init_gz, DESIGN.md
+section 4.9) the root rule is Gumbel AlphaZero's: m moves sampled without replacement by the Gumbel-top-k trick, the budget spent
+on them by sequential halving, the move with the best g + log prior + sigma(q) among the most visited played without temperature,
+and the sample's `visits` hold the completed-Q improved policy quantised to 16 bits (`reserved0` = 1) instead of visit counts.
+Interior nodes keep PUCT.  `stats()` adds `gumbel_moves`, `gumbel_considered` and `gumbel_offprior`.  Self-play and search only
+(manual_moves 0 or 1), K = 1; it combines with the evaluation cache and with nothing else.
 """
 from __future__ import annotations
 
@@ -105,7 +112,7 @@ def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
 class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
-                 tree_reuse: bool = False, playout_cap=None, forced_playouts=None):
+                 tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None):
         K = int(leaves_per_step)
         if not 1 <= K <= 64:
             raise hip.XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
@@ -146,6 +153,26 @@ class SelfPlayEngine:
             if not 0.0 < fk <= 16.0:                       # a NaN fails both comparisons
                 raise hip.XqError(f"forced_playouts: k must be in (0, 16], got {fk}")
             forced = hip.ForcedPlayouts(fk)
+        gz = None
+        if gumbel is not None:
+            try:
+                gm, gcv, gcs = int(gumbel[0]), float(gumbel[1]), float(gumbel[2])
+                if len(gumbel) != 3 or gm != gumbel[0]:
+                    raise ValueError
+            except (TypeError, ValueError, IndexError, OverflowError):
+                raise hip.XqError("gumbel must be (considered_moves, c_visit, c_scale)")
+            if int(cfg.manual_moves) == 2:
+                raise hip.XqError("gumbel is a self-play and search option: not available for arena games (manual_moves = 2)")
+            if tree_reuse or cap is not None or forced is not None:
+                raise hip.XqError("gumbel cannot be combined with tree_reuse, playout_cap or forced_playouts")
+            if K > 1:
+                raise hip.XqError("gumbel cannot be combined with leaves_per_step > 1")
+            if not 1 <= gm <= hip.MAXM:
+                raise hip.XqError(f"gumbel: considered moves must be in [1, {hip.MAXM}], got {gm}")
+            f32_max = float(np.finfo(np.float32).max)
+            if not (0.0 <= gcv <= f32_max) or not (0.0 < gcs <= f32_max) or not float(np.float32(gcs)) > 0.0:   # a NaN fails them
+                raise hip.XqError(f"gumbel: c_visit >= 0 and c_scale > 0, finite as float32, required; got {gcv}, {gcs}")
+            gz = hip.Gumbel(gm, 0, gcv, gcs)
         if K > 1 and eval_cache_entries:
             raise hip.XqError("leaves_per_step > 1 cannot be combined with an evaluation cache (eval_cache_entries > 0)")
         if K > 1 and int(cfg.manual_moves) == 2:
@@ -160,11 +187,14 @@ class SelfPlayEngine:
         self.tree_reuse = tree_reuse
         self.playout_cap = None if cap is None else (cap.full_search_prob, cap.fast_simulations)
         self.forced_playouts = None if forced is None else float(np.float32(forced.k))   # k as the kernels use it
+        self.gumbel = None if gz is None else (gz.considered, float(np.float32(gz.c_visit)), float(np.float32(gz.c_scale)))
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         flags = hip.ENGINE_TREE_REUSE if tree_reuse else 0
         cap_ref = None if cap is None else C.byref(cap)
-        if forced is not None:
+        if gz is not None:
+            nbytes = self.lib.xq_engine_workspace_bytes_gz(C.byref(cfg), K, flags, None, None, C.byref(gz))
+        elif forced is not None:
             nbytes = self.lib.xq_engine_workspace_bytes_fp(C.byref(cfg), K, flags, cap_ref, C.byref(forced))
         elif cap is not None:
             nbytes = self.lib.xq_engine_workspace_bytes_cap(C.byref(cfg), K, flags, C.byref(cap))
@@ -188,7 +218,11 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            if forced is not None:
+            if gz is not None:
+                hip.check(self.lib.xq_engine_init_gz(C.byref(self.h), C.byref(cfg), K, flags, None, None, C.byref(gz), base,
+                                                     self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
+                          "xq_engine_init_gz")
+            elif forced is not None:
                 hip.check(self.lib.xq_engine_init_fp(C.byref(self.h), C.byref(cfg), K, flags, cap_ref, C.byref(forced), base,
                                                      self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
                           "xq_engine_init_fp")
@@ -491,9 +525,18 @@ class SelfPlayEngine:
     def slot_counters(self) -> torch.Tensor:
         """Zero-copy int64 [G, 32] view of the per-slot counters that xq_engine_stats_read sums (column 19: collisions, 20:
         pending leaves handed out, 21: slot-steps that handed leaves, 22: reused visits, 23: re-rooted searches, 24: fast moves,
-        25: simulations of fast searches, 26: forced simulations, 27: pruned visits, 28: pruned children).  For tests."""
+        25: simulations of fast searches, 26: forced simulations, 27: pruned visits, 28: pruned children, 29: Gumbel moves, 30: the sum
+        of their considered moves, 31: Gumbel moves off the prior's first maximum).  For tests."""
         off = int(self.h.p[17]) - int(self.ws.data_ptr())
         return self.ws[off:off + self.G * 32 * 8].view(torch.int64).view(self.G, 32)
+
+    def gumbel_root_values(self) -> torch.Tensor:
+        """Gumbel engines: zero-copy float64 [G] view of v_hat, the root's network value every slot keeps for the end of its
+        move (behind the square-root table and the 16 bytes of parameters, include/xq_hip.h).  For tools and tests."""
+        if self.gumbel is None:
+            raise hip.XqError("gumbel_root_values needs an engine with gumbel=")
+        off = int(self.h.p[19]) - int(self.ws.data_ptr()) + (int(self.cfg.num_simulations) + 2) * 8 + 16
+        return self.ws[off:off + self.G * 8].view(torch.float64)
 
     def held(self) -> bool:
         """Search-only engines: every slot holds its finished search (phase HOLD).  Synchronises."""
@@ -529,7 +572,7 @@ class SelfPlayEngine:
         if n < 0:
             hip.check(n, "xq_engine_read_root")
         return dict(actions=a[:n], visits=v[:n], total_value=w[:n], prior=p[:n], prior_is_f64=bool(kind.value),
-                    root_visits=rv.value, sims_done=sd.value)
+                    prior_kind=int(kind.value), root_visits=rv.value, sims_done=sd.value)
 
 
 action_probs_dense = dense_pi   # the reference's dense pi (mcts.py:190-206) from compact (action, visit) pairs

@@ -62,8 +62,13 @@ class EngineStats(C.Structure):
                  "leaves_per_step_sum", "leaf_steps", "reused_visits", "reroots", "fast_moves", "fast_sims", "forced_sims",
                  "pruned_visits", "pruned_children")] + [("reserved", C.c_uint64 * 3)]
 
+    # the Gumbel root search's counters (xq_engine_init_gz) are the struct's last three words, kept under `reserved`
+    GUMBEL_KEYS = ("gumbel_moves", "gumbel_considered", "gumbel_offprior")
+
     def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+        out = {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+        out.update({n: int(self.reserved[i]) for i, n in enumerate(self.GUMBEL_KEYS)})
+        return out
 
 
 class PlayoutCap(C.Structure):
@@ -74,6 +79,11 @@ class PlayoutCap(C.Structure):
 class ForcedPlayouts(C.Structure):
     """xq_forced_playouts: forced playouts and policy target pruning (xq_engine_init_fp): the parameter k."""
     _fields_ = [("k", C.c_double), ("reserved", C.c_uint32 * 2)]
+
+
+class Gumbel(C.Structure):
+    """xq_gumbel: Gumbel root search with sequential halving (xq_engine_init_gz): considered moves m, c_visit, c_scale."""
+    _fields_ = [("considered", C.c_int32), ("reserved", C.c_int32), ("c_visit", C.c_double), ("c_scale", C.c_double)]
 
 
 class PackedBuffers(C.Structure):
@@ -135,6 +145,12 @@ def lib():
     L.xq_engine_workspace_bytes_fp.restype = C.c_size_t
     L.xq_engine_init_fp.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap),
                                     C.POINTER(ForcedPlayouts), vp, C.c_size_t, vp, vp]
+    L.xq_engine_workspace_bytes_gz.argtypes = [C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap),
+                                               C.POINTER(ForcedPlayouts), C.POINTER(Gumbel)]
+    L.xq_engine_workspace_bytes_gz.restype = C.c_size_t
+    L.xq_engine_init_gz.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap),
+                                    C.POINTER(ForcedPlayouts), C.POINTER(Gumbel), vp, C.c_size_t, vp, vp]
+    L.xq_gumbel_considered_visits_host.argtypes = [i32, i32, vp]
     L.xq_engine_select.argtypes = [C.POINTER(Engine), vp, vp]
     L.xq_engine_expand.argtypes = [C.POINTER(Engine), vp, vp, i32, vp]
     L.xq_engine_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(EngineStats), vp]
@@ -209,7 +225,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_compact_misses", "xq_evcache_commit", "xq_evcache_invalidate", "xq_evcache_stats_read",
            "xq_evcache_key_host", "xq_engine_workspace_bytes_leaves", "xq_engine_init_leaves", "xq_engine_workspace_bytes_ex",
            "xq_engine_init_ex", "xq_engine_drop_reroots", "xq_engine_workspace_bytes_cap", "xq_engine_init_cap",
-           "xq_engine_workspace_bytes_fp", "xq_engine_init_fp"]
+           "xq_engine_workspace_bytes_fp", "xq_engine_init_fp", "xq_engine_workspace_bytes_gz", "xq_engine_init_gz",
+           "xq_gumbel_considered_visits_host"]
 
 
 def check(rc: int, what: str):

@@ -25,7 +25,7 @@ _CFG_KEYS = ("num_simulations", "c_puct", "temperature_threshold", "max_game_len
 def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[int] = None, seed: int = 0, rank: int = 0,
               evaluator_kind: str = "hip", poll_every: int = 64, device_records: bool = False, use_graph: bool = True,
               eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None,
-              tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None):
+              tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -40,7 +40,11 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     `playout_cap`).  Games finish sooner and carry fewer samples each; it needs K = 1.
     `forced_playouts` = k (None: `config.forced_playouts_k`, absent or 0 = off) forces visited children of a noisy root up to
     sqrt(k * prior * root visits) visits and prunes those visits from the samples' targets and the move distribution again
-    (stats `forced_sims`, `pruned_visits`, `pruned_children`, `forced_playouts`); it needs K = 1."""
+    (stats `forced_sims`, `pruned_visits`, `pruned_children`, `forced_playouts`); it needs K = 1.
+    `gumbel` = (m, c_visit, c_scale) (None: `config.gumbel_considered`, absent or 0 = off, with `config.gumbel_c_visit`, default
+    50, and `config.gumbel_c_scale`, default 1.0) replaces the root rule by Gumbel top-m sampling with sequential halving and
+    the samples' visit counts by the quantised improved policy (stats `gumbel_moves`, `gumbel_considered`, `gumbel_offprior`,
+    `gumbel`); it needs K = 1 and none of tree reuse, playout cap and forced playouts."""
     if eval_cache_entries is None:
         eval_cache_entries = int(getattr(config, "eval_cache_entries", 0) or 0)
     if leaves_per_step is None:
@@ -56,6 +60,11 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
             playout_cap = (float(p_full), int(s_fast))
     if forced_playouts is None:
         forced_playouts = float(getattr(config, "forced_playouts_k", 0) or 0) or None
+    if gumbel is None:
+        gm = int(getattr(config, "gumbel_considered", 0) or 0)
+        if gm:
+            gcv, gcs = getattr(config, "gumbel_c_visit", None), getattr(config, "gumbel_c_scale", None)
+            gumbel = (gm, 50.0 if gcv is None else float(gcv), 1.0 if gcs is None else float(gcs))
     slots = int(n_slots or min(num_games, 8192))
     slots = max(1, min(slots, num_games))
     ev, ev_name = evaluator.make_evaluator(model, device, evaluator_kind)
@@ -68,7 +77,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
         max_out_samples=num_games * 201, max_out_results=num_games + 8)
     eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries,
                                 leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
-                                forced_playouts=forced_playouts)
+                                forced_playouts=forced_playouts, gumbel=gumbel)
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -88,6 +97,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     st["tree_reuse"] = eng.tree_reuse
     st["playout_cap"] = eng.playout_cap                # None, or (full_search_prob, fast_simulations)
     st["forced_playouts"] = eng.forced_playouts        # None, or k
+    st["gumbel"] = eng.gumbel                          # None, or (m, c_visit, c_scale)
     st.setdefault("eval_cache_probes", 0)              # the cache's keys are present (0) when it is off
     st.setdefault("eval_cache_hits", 0)
     if eng.capture_error:
@@ -100,7 +110,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
                        return_compact: bool = False, eval_cache_entries: Optional[int] = None,
                        leaves_per_step: Optional[int] = None,
                        tree_reuse: Optional[bool] = None, playout_cap=None,
-                       forced_playouts: Optional[float] = None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
+                       forced_playouts: Optional[float] = None, gumbel=None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
     for k in _CFG_KEYS + ("num_games_per_iter",):
         if not hasattr(config, k):
             raise AttributeError(f"config lacks '{k}' (see training/train.py:55-111)")
@@ -110,7 +120,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
     samples, results, st, elapsed = run_games(model, config, num_games, gpu_device, n_slots, seed,
                                               eval_cache_entries=eval_cache_entries, leaves_per_step=leaves_per_step,
                                               tree_reuse=tree_reuse, playout_cap=playout_cap,
-                                              forced_playouts=forced_playouts)
+                                              forced_playouts=forced_playouts, gumbel=gumbel)
     all_data, per_game = to_reference_tuples(samples, results, augment=True)
     wins = {1: 0, -1: 0, 0: 0}
     total_steps = 0
@@ -128,6 +138,8 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
         "fast_moves": st["fast_moves"], "fast_sims": st["fast_sims"], "playout_cap": st["playout_cap"],
         "forced_sims": st["forced_sims"], "pruned_visits": st["pruned_visits"], "pruned_children": st["pruned_children"],
         "forced_playouts": st["forced_playouts"],
+        "gumbel_moves": st["gumbel_moves"], "gumbel_considered": st["gumbel_considered"],
+        "gumbel_offprior": st["gumbel_offprior"], "gumbel": st["gumbel"],
     }
     if return_compact:
         stats["compact_samples"], stats["compact_results"] = samples, results

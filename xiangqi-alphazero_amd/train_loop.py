@@ -82,6 +82,8 @@ class AlphaZeroLoop:
                                                     # forced playouts too (config.forced_playouts_k; absent or 0: off): the
                                                     # arena (arena.py) never takes it
                                                     forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None)
+        # the Gumbel root search (config.gumbel_considered, gumbel_c_visit, gumbel_c_scale; absent or 0: off) reaches the engine
+        # through run_games, which reads those keys from the config it is handed; the arena never takes it either
         return samples, results
 
     def self_play(self) -> dict:
