@@ -376,6 +376,65 @@ int xq_engine_init_gz(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       const uint64_t *dev_inject, void *stream);
 int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out);
 
+/* Arena options (opt-in; arena == NULL is xq_engine_init_gz exactly, and xq_engine_init_gz is that call): paired random openings
+ * and a per-model packed step for the arena games (manual_moves = 2), so a gate can play hundreds of DISTINCT games whose
+ * evaluator cost follows each model's own live requests.  Without the options an arena plays two distinct games however many it
+ * is asked for (no opening, no noise, first maximum of the visits); that stays the default.  Outside the reference-parity
+ * contract, like the other opt-in options; with opening_plies = 0 the games are the reference's.
+ * Parameters: opening_plies = R, 0 <= R <= XQ_ARENA_MAX_OPENING; first_game >= 0, the arena game index of slot 0 (a shard of a
+ * larger arena starts on any index); reserved = 0.
+ * PAIRED OPENINGS, when a slot starts its game and R > 0.  Slot s plays arena game g = first_game + s (slot == game); its pair is
+ * p = g / 2 (integer division).  The new model is red in even games, as in every arena.
+ *     The game starts with exactly R uniformly random legal plies: ply i (0-based) plays move x_i % cnt of the cnt ORDERED legal
+ *     moves of the position, the mechanics of the self-play opening.
+ *     The raw 64-bit draw x_i is a function of the PAIR, never of the slot, the rank or the shard:
+ *           device RNG      x_i = philox_u64(cfg.seed, 0, p, 8, i, 0): rank word 0, the slot word holds p, kind 8 (no other draw
+ *                           uses it; 7 is the start stagger's), counter i, sub 0;
+ *           inject_len > 0  x_i = entry i of the slot's own stream 1 (choice); a test gives both slots of a pair the same stream.
+ *                           i >= inject_len sets overflow bit 2 and takes x_i = 0.  The stream's counter is not advanced.
+ *     If an opening ply ends the game (xq_game_over_batch's rule on the position after it), the game restarts from the initial
+ *     position with NO opening, as self-play does; its recorded count is 0.
+ *     So games 2p and 2p + 1 start from the same position with colours swapped, and a shard that starts on any game index plays
+ *     the same games as the unsharded arena.
+ * The opening plies count in move_count (the result's steps); they are not counted in moves_played.  Everything after the
+ * opening is the arena move rule: S simulations without noise, the first maximum of the visit counts, a draw when the game is
+ * not over at max_game_length plies.
+ * xq_engine_arena_openings: *dev_actions = uint16[G][XQ_ARENA_MAX_OPENING], row s = the actions slot s played as its opening,
+ * zero past *dev_counts[s]; *dev_counts = int32[G], R for a played opening, 0 before the slot's game started, after the restart
+ * rule and with R = 0.  Workspace pointers valid for the engine's lifetime.
+ * PER-MODEL PACKED STEP.  Slot s belongs to the NEW model iff ((first_game + s) even) == (red is to move in the slot's REAL game):
+ * the model that is searching evaluates every node of its search, root and leaves at any depth.  On one stream:
+ *     xq_engine_select(eng, nn_input)                       as before
+ *     xq_engine_compact_arena(eng, nn_input)                stable, slot-ordered compaction of the waiting slots (phase WAIT_ROOT /
+ *                                                           WAIT_LEAF: exactly k_expand's test) into TWO buffer sets, set 0 the new
+ *                                                           model's slots and set 1 the old model's; each set has its own n_live,
+ *                                                           rows, x, moves, counts as xq_engine_compact fills them.  Every waiting
+ *                                                           slot is in exactly one set; rows_evaluated grows by n_live0 + n_live1
+ *     <new model over set 0, old model over set 1>          the *_live entry points, capacity = n_games, dev_n = the set's n_live;
+ *                                                           the two evaluations are independent and may run concurrently
+ *     xq_engine_expand_packed_arena(eng, logits_new, value_new, logits_old, value_old)
+ *                                                           scatters packed row r of set 0 from the new model's outputs and of
+ *                                                           set 1 from the old model's back to slot rows[r] of slot_logits /
+ *                                                           slot_value (shared by both sets) and runs xq_engine_expand_legal
+ * xq_engine_packed_arena writes the two sets' addresses to out[0] (new) and out[1] (old); slot_logits / slot_value are the
+ * engine's one pair.  No count leaves the device and every grid is sized by n_games, so the step records into one replayable
+ * graph; n_live = 0 in either set, or both, is a valid step.  The games are those of the full-width step with the other model's
+ * requests masked: a row's arithmetic in every evaluator kernel does not depend on its position in the batch.
+ * XQ_ERR_ARG before any launch (xq_engine_workspace_bytes_ar: 0): arena options with manual_moves != 2; opening_plies outside
+ * [0, 16]; first_game < 0 (or first_game + n_games beyond int32); reserved != 0; and whatever xq_engine_init_gz refuses -- so
+ * with arena options leaves_per_step = 1 and none of tree reuse, playout cap, forced playouts and Gumbel root search.  The three
+ * xq_engine_*_arena calls and xq_engine_arena_openings return XQ_ERR_ARG on an engine without arena options.
+ * Workspace: the parameters, the openings record and the two buffer sets (about 5.7 KB per slot and set) lie behind the engine's
+ * square-root table; only arena-option engines grow, "arena options on" lives in the handle (pad0, above the public flag bits). */
+#define XQ_ARENA_MAX_OPENING 16
+typedef struct xq_arena_opts { int32_t opening_plies; int32_t first_game; uint32_t reserved[2]; } xq_arena_opts;
+size_t xq_engine_workspace_bytes_ar(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena);
+int xq_engine_init_ar(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena, void *ws,
+                      size_t ws_bytes, const uint64_t *dev_inject, void *stream);
+int xq_engine_arena_openings(const xq_engine *eng, const uint16_t **dev_actions /* [G][16] */, const int32_t **dev_counts /* [G] */);
+
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 
 /* dev_policy[slot] = float32[8100]: network LOGITS (policy_is_probs = 0; softmax over all 8100 as
@@ -423,6 +482,11 @@ typedef struct xq_engine_packed_buffers {
 int xq_engine_compact(const xq_engine *eng, const float *dev_nn_input, void *stream);
 int xq_engine_packed(const xq_engine *eng, xq_engine_packed_buffers *out);
 int xq_engine_expand_packed(const xq_engine *eng, const float *dev_packed_logits, const float *dev_packed_value, void *stream);
+/* the per-model packed step of an engine with arena options (rules: xq_engine_init_ar above) */
+int xq_engine_compact_arena(const xq_engine *eng, const float *dev_nn_input, void *stream);
+int xq_engine_packed_arena(const xq_engine *eng, xq_engine_packed_buffers out[2]);
+int xq_engine_expand_packed_arena(const xq_engine *eng, const float *dev_logits_new, const float *dev_value_new,
+                                  const float *dev_logits_old, const float *dev_value_old, void *stream);
 
 /* Evaluation cache (opt-in): a table private to each slot that remembers the legal-move logits and value the network
  * returned for a position, so the next search, which revisits most of the previous move's subtree, does not ask again.

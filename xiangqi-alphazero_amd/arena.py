@@ -11,6 +11,15 @@ the cost) with the other model's requests masked out, and the merge happens on t
 Dense-protocol evaluators (the stubs of the fixtures) are run on their own slots only.  With a process group the games are sharded over the
 ranks like self-play games (`distributed.shard_games`); the per-game results are all-gathered and every rank derives the
 same verdict from the same gathered table.
+
+Opt-in, for a gate with statistical power (rules in include/xq_hip.h, xq_engine_init_ar).  The default gate
+above plays two distinct games however many it is asked for: every even game is one game, every odd game the other.
+`opening_plies = R > 0` starts game g with R random legal plies drawn for the PAIR g // 2, so games 2p and 2p + 1 share an opening
+with colours swapped and the games of different pairs differ; a shard plays the same games as the unsharded arena.  `packed`
+(the default with openings, when both evaluators take a device-side live row count) replaces the masked step by the per-model
+packed one: the waiting slots are compacted into the new model's and the old model's buffer sets on the device and each network
+runs over its own live rows only.  Same games as the masked step.  `evaluate_models` reads `config.arena_opening_plies` and
+`config.arena_seed` and reports the standard error of the win rate over the pairs (`pair_statistics`).
 """
 from __future__ import annotations
 
@@ -40,15 +49,26 @@ def _evaluate_subset(eng, ev, x, idx, policy_is_probs, dense, legal, value):
 
 
 def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_simulations: int, max_game_length: int,
-               c_puct: float = 1.5, device="cuda", policy_is_probs: bool = False, first_game: int = 0):
+               c_puct: float = 1.5, device="cuda", policy_is_probs: bool = False, first_game: int = 0,
+               opening_plies: int = 0, seed: int = 0, packed: Optional[bool] = None, inject=None, info: Optional[dict] = None):
     """eval_*: evaluators in either protocol (`evaluate_legal`, or a callable float32[n,15,10,9] -> (policy
     float32[n,8100], value float32[n])); both must use the same one.  Plays games first_game .. first_game+eval_games-1
     of the arena (the new model is red in even games) and returns the results array ordered by game (slot == game -
-    first_game)."""
+    first_game).
+    Opt-in: `opening_plies` > 0 and `seed` give every pair of games its random opening; `packed` (None: yes with openings when
+    both evaluators offer `live_rows`) takes the per-model packed step; `inject` (uint64 [games, 4, n], tests only) replaces the
+    device draws; `info` (a dict) receives `openings`, `opening_counts`, `steps` (engine steps run) and the engine's `stats`."""
     cfg = engine.make_config(eval_games, eval_simulations, c_puct=c_puct, max_game_length=max_game_length,
                              random_opening_moves=0, enable_resign=False, add_noise=False, games_target=eval_games,
                              manual_moves=2)
-    eng = engine.SelfPlayEngine(cfg, device)
+    opts = int(opening_plies) > 0 or bool(packed) or inject is not None or info is not None
+    if not opts:
+        eng = engine.SelfPlayEngine(cfg, device)
+    else:
+        if inject is not None:
+            cfg.inject_len = int(np.asarray(inject).shape[-1])
+        cfg.seed = int(seed)
+        eng = engine.arena_engine(cfg, device, opening_plies, first_game, inject)
     dev = eng.device
     new_is_red = ((torch.arange(eval_games, device=dev) + first_game) % 2 == 0)
     sparse = hasattr(eval_new, "evaluate_legal") and hasattr(eval_old, "evaluate_legal") and not policy_is_probs
@@ -58,8 +78,37 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
     zero = torch.zeros_like(eng.req_counts)
     # XQ_ARENA_STREAMS=0: both networks on the one stream (A/B runs and the equality test)
     side = torch.cuda.Stream(device=dev) if sparse and os.environ.get("XQ_ARENA_STREAMS", "1") != "0" else None
+    can_pack = sparse and bool(getattr(eval_new, "live_rows", False)) and bool(getattr(eval_old, "live_rows", False))
+    if packed and not can_pack:
+        raise hip.XqError("packed arena step: both evaluators must offer evaluate_legal with live_rows (the HIP evaluators)")
+    packed = (can_pack and int(opening_plies) > 0) if packed is None else bool(packed)
+    if opts and eval_old is eval_new:
+        side = None                                        # one evaluator's buffers serve one branch at a time
+
+    def packed_step():
+        # select -> two slot-ordered compactions by searching model -> each network over its own live rows -> scatter + expand.
+        # The counts stay on the device and every grid is sized by the slot count: the step records into one graph, the old
+        # network on the side stream as a parallel branch like the masked step's.
+        eng.select()
+        eng.compact_arena()
+        s_new, s_old = eng.arena_packed
+        if side is not None:
+            main = torch.cuda.current_stream(dev)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                ll_old, v_old = eval_old.evaluate_legal(s_old["x"], s_old["moves"], s_old["counts"], n_live=s_old["n_live"])
+            ll_new, v_new = eval_new.evaluate_legal(s_new["x"], s_new["moves"], s_new["counts"], n_live=s_new["n_live"])
+            main.wait_stream(side)
+        else:
+            ll_new, v_new = eval_new.evaluate_legal(s_new["x"], s_new["moves"], s_new["counts"], n_live=s_new["n_live"])
+            if eval_old is eval_new:
+                ll_new, v_new = ll_new.clone(), v_new.clone()   # the second call reuses the evaluator's output buffers
+            ll_old, v_old = eval_old.evaluate_legal(s_old["x"], s_old["moves"], s_old["counts"], n_live=s_old["n_live"])
+        eng.expand_packed_arena(ll_new, v_new, ll_old, v_old)
 
     def step():
+        if packed:
+            return packed_step()
         x = eng.select()
         # the model that is SEARCHING evaluates every node of its search (root and leaves at any depth), so the
         # choice follows the side to move of the real game, not of the evaluated position (train.py:479-483)
@@ -111,26 +160,58 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
             if not any(k in msg for k in ("captur", "hiperrorstreamcapture", "cudaerrorstreamcapture", "operation not permitted")):
                 raise
             torch.cuda.synchronize(dev)
+    n_steps = 2 if graph is not None else 0               # the two warm-up steps are steps of the games (the recording runs nothing)
     while True:
         for _ in range(64):
             if graph is not None:
                 graph.replay()
             else:
                 step()
+        n_steps += 64
         st = eng.stats()
         if st["games_finished"] >= eval_games:
             break
     _, results = eng.drain()
+    if info is not None:
+        info["openings"], info["opening_counts"] = eng.arena_openings()
+        info["steps"], info["stats"], info["packed"] = n_steps, st, bool(packed)
     return results[results["slot"].argsort()]
 
 
-def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind: str = "hip", group=None) -> Dict[str, object]:
+def pair_statistics(winners) -> Dict[str, object]:
+    """Win rate of the new model with its standard error over PAIRS.  `winners[g]` is game g's winner (1 red, -1 black, 0 draw),
+    the new model red in even games; games 2p and 2p + 1 share an opening, so they are not independent and the pair is the
+    sample: s_p = the mean of the new model's scores (1 / 0.5 / 0) in the pair's two games, win_rate = mean(s_p),
+    se = std(s_p, ddof=1) / sqrt(P) (0 for a single pair), ci95 = win_rate -+ 1.96 se."""
+    w = np.asarray(winners, dtype=np.int64).reshape(-1)
+    if w.size == 0 or w.size % 2:
+        raise ValueError("pair_statistics needs an even, positive number of games")
+    red_score = np.where(w == 1, 1.0, np.where(w == 0, 0.5, 0.0))
+    score = np.where(np.arange(w.size) % 2 == 0, red_score, 1.0 - red_score)
+    s = score.reshape(-1, 2).mean(axis=1)
+    pairs = int(s.size)
+    rate = float(s.mean())
+    se = float(s.std(ddof=1) / np.sqrt(pairs)) if pairs > 1 else 0.0
+    return {"pairs": pairs, "win_rate": rate, "win_rate_se": se, "win_rate_ci95": (rate - 1.96 * se, rate + 1.96 * se)}
+
+
+def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind: str = "hip", group=None,
+                    seed: Optional[int] = None) -> Dict[str, object]:
     """Same stats dict as the reference (`new_wins, old_wins, draws, win_rate, model_updated`); reads
     `eval_games, eval_simulations, c_puct, max_game_length, eval_win_rate` from `config` (train.py:97-100).
-    Under torch.distributed the games are split over the ranks and the winners all-gathered."""
+    Under torch.distributed the games are split over the ranks and the winners all-gathered.
+    `config.arena_opening_plies` = R > 0 (absent or 0: off) plays paired random openings (module docstring) under the seed
+    `seed` (None: `config.arena_seed`, absent: 0); `eval_games` must then be even, and the result adds `opening_plies`, `pairs`,
+    `openings` (uint16 [games, R]), `win_rate_se` and `win_rate_ci95`.  The promotion rule is unchanged."""
     import torch.distributed as dist
     from . import distributed as xdist
     total = int(config.eval_games)
+    plies = int(getattr(config, "arena_opening_plies", 0) or 0)
+    if plies > 0 and total % 2:
+        raise ValueError(f"arena_opening_plies needs an even eval_games (games come in colour-swapped pairs), got {total}")
+    if seed is None:
+        seed = int(getattr(config, "arena_seed", 0) or 0)
+    openings = np.zeros((total, max(plies, 0)), dtype=np.int64)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     mine = xdist.shard_games(total, world, rank)
@@ -140,8 +221,14 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
     if mine > 0:
         en, _ = ev_mod.make_evaluator(new_model, device, evaluator_kind)
         eo, _ = ev_mod.make_evaluator(old_model, device, evaluator_kind)
-        res = play_arena(en, eo, mine, int(config.eval_simulations), int(config.max_game_length), float(config.c_puct),
-                         device, first_game=first)
+        if plies > 0:
+            info = {}
+            res = play_arena(en, eo, mine, int(config.eval_simulations), int(config.max_game_length), float(config.c_puct),
+                             device, first_game=first, opening_plies=plies, seed=int(seed), info=info)
+            openings[first:first + mine] = info["openings"][:, :plies]
+        else:
+            res = play_arena(en, eo, mine, int(config.eval_simulations), int(config.max_game_length), float(config.c_puct),
+                             device, first_game=first)
         winners[first:first + mine] = res["winner"].astype(np.int64)
         steps[first:first + mine] = res["steps"].astype(np.int64)
     if dist.is_initialized():         # disjoint shards: a sum gathers them; every rank ends with the same table (a group of
@@ -149,6 +236,10 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
         t = torch.from_numpy(np.stack([winners, steps])).to(device if dist.get_backend(group) == "nccl" else "cpu")
         dist.all_reduce(t, group=group)
         winners, steps = t[0].cpu().numpy(), t[1].cpu().numpy()
+        if plies > 0:
+            t = torch.from_numpy(openings).to(device if dist.get_backend(group) == "nccl" else "cpu")
+            dist.all_reduce(t, group=group)
+            openings = t.cpu().numpy()
     new_wins = old_wins = draws = 0
     for game in range(total):
         w, new_is_red = int(winners[game]), game % 2 == 0
@@ -161,5 +252,10 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
     win_rate = (new_wins + 0.5 * draws) / total
     games = np.zeros(total, dtype=RESULT_DTYPE)
     games["slot"], games["winner"], games["steps"] = np.arange(total), winners, steps
-    return {"new_wins": new_wins, "old_wins": old_wins, "draws": draws, "win_rate": win_rate,
-            "model_updated": win_rate >= float(config.eval_win_rate), "games": games}
+    out = {"new_wins": new_wins, "old_wins": old_wins, "draws": draws, "win_rate": win_rate,
+           "model_updated": win_rate >= float(config.eval_win_rate), "games": games}
+    if plies > 0:
+        ps = pair_statistics(winners)
+        out.update({"opening_plies": plies, "pairs": ps["pairs"], "openings": openings.astype(np.uint16),
+                    "win_rate_se": ps["win_rate_se"], "win_rate_ci95": ps["win_rate_ci95"]})
+    return out

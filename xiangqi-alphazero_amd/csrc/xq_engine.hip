@@ -57,6 +57,7 @@ enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_
                  P_PK_N, P_PK_ROWS, P_PK_X, P_PK_MOVES, P_PK_COUNTS, P_PK_LOGITS, P_PK_VALUE, P_VL, P_LEAF };
 
 enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM = 3 };
+constexpr uint32_t RNG_ARENA_OPENING = 8u;  // xq_engine_init_ar: keyed by the PAIR and rank 0, never by the slot (7 is k_init's stagger)
 
 // Device view of the engine (passed by value to kernels)
 struct Dev {
@@ -110,6 +111,37 @@ size_t gz_bytes(size_t G, size_t S, size_t m) { return sizeof(GzHead) + G * 8 + 
 __device__ __forceinline__ const GzHead *gz_head(const Dev &E) { return (const GzHead *)(E.sqrt_tab + E.cfg.num_simulations + 2); }
 __device__ __forceinline__ double *gz_vhat(const Dev &E) { return (double *)(gz_head(E) + 1); }
 __device__ __forceinline__ const uint16_t *gz_table(const Dev &E) { return (const uint16_t *)(gz_vhat(E) + E.cfg.n_games); }
+
+// Arena options (xq_engine_init_ar; manual_moves = 2, so never a Gumbel engine): their words lie behind the square-root table as
+// well, from the next 256-byte boundary on: the parameters, what every slot played as its opening, and the two buffer sets of the
+// per-model packed step (set 0: the new model's slots, set 1: the old model's).  Offsets from the table's first byte.
+struct ArHead {
+    int32_t opening_plies, first_game, pad[2];
+};
+static_assert(sizeof(ArHead) == 16, "ArHead layout");
+
+struct ArOff {
+    size_t head, op_counts, op_actions, n_live, rows[2], x[2], moves[2], counts[2], end;
+};
+
+__host__ __device__ inline size_t ar_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+__host__ __device__ inline ArOff ar_off(size_t G, size_t S) {
+    ArOff a;
+    size_t o = ar_align((S + 2) * 8);
+    a.head = o; o = ar_align(o + sizeof(ArHead));
+    a.op_counts = o; o = ar_align(o + G * 4);
+    a.op_actions = o; o = ar_align(o + G * XQ_ARENA_MAX_OPENING * 2);
+    a.n_live = o; o = ar_align(o + 2 * 4);
+    for (int m = 0; m < 2; ++m) {
+        a.rows[m] = o; o = ar_align(o + G * 4);
+        a.x[m] = o; o = ar_align(o + G * XQ_STATE_FLOATS * 4);
+        a.moves[m] = o; o = ar_align(o + G * XQ_MAXM * 2);
+        a.counts[m] = o; o = ar_align(o + G * 4);
+    }
+    a.end = o;
+    return a;
+}
 
 // get_sequence_of_considered_visits(k, S) of include/xq_hip.h: out[t] = the visit count a root child must have to be a
 // candidate of simulation t
@@ -415,6 +447,49 @@ __device__ __forceinline__ bool slot_new_game(const Dev &E, Slot &s, SelectLds &
     }
     s.dirty = true;
     return true;
+}
+
+// AROPEN (arena options, xq_engine_init_ar), after slot_new_game: the paired random opening of arena game g = first_game + slot.
+// Exactly R uniformly random legal plies, ply i the move x_i % cnt of the ordered legal moves; x_i belongs to the PAIR g / 2
+// (philox_u64(seed, 0, g / 2, 8, i, 0)) or, with injected draws, is entry i of the slot's own choice stream.  A ply that ends the
+// game restarts it from the initial position without an opening (recorded count 0), as self-play does.  The plies count in
+// move_count.  What was played goes to the engine's record (xq_engine_arena_openings).
+__device__ __forceinline__ void slot_arena_opening(const Dev &E, Slot &s, SelectLds &L) {
+    const ArOff o = ar_off((size_t)E.cfg.n_games, (size_t)E.cfg.num_simulations);
+    char *base = (char *)E.sqrt_tab;
+    const ArHead *h = (const ArHead *)(base + o.head);
+    const int R = __builtin_amdgcn_readfirstlane(h->opening_plies);
+    const int pair = (__builtin_amdgcn_readfirstlane(h->first_game) + s.slot) >> 1;
+    uint16_t *rec = (uint16_t *)(base + o.op_actions) + (size_t)s.slot * XQ_ARENA_MAX_OPENING;
+    int played = 0;
+    for (int i = 0; i < R; ++i) {
+        const int cnt = wave_movegen(L.root, s.side, L.mg, L.moves, &s.ovf);
+        if (cnt == 0) break;
+        uint64_t x = 0;
+        if (E.cfg.inject_len > 0) {
+            if (i < E.cfg.inject_len) x = E.inject[((size_t)s.slot * 4 + RNG_CHOICE) * E.cfg.inject_len + i];
+            else s.st[ST_OVF] |= 2ull;
+        } else {
+            x = philox_u64(E.cfg.seed, 0u, (uint32_t)pair, RNG_ARENA_OPENING, (uint32_t)i, 0u);
+        }
+        const int action = L.moves[(int)(x % (uint64_t)cnt)];
+        wave_make_move(L.root, L.rhist, action, s.side, s.mc, s.nocap);
+        if (s.lane == 0) rec[i] = (uint16_t)action;
+        played = i + 1;
+        int c2, w2;
+        if (wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, L.mg, L.moves, &c2, &w2, &s.ovf)) {
+            init_board_lds(L.root);
+            s.side = 1; s.mc = 0; s.nocap = 0;
+            wave_sync();
+            played = 0;
+            break;
+        }
+    }
+    if (s.lane == 0) {
+        for (int i = played; i < XQ_ARENA_MAX_OPENING; ++i) rec[i] = 0;
+        ((int32_t *)(base + o.op_counts))[s.slot] = played;
+    }
+    s.dirty = true;
 }
 
 // PH_NEWPOS, the root request: terminal status of the real position (0: to be searched), its planes to x and its ordered
@@ -810,7 +885,9 @@ constexpr int WAVES_PER_WG = 4;
 // every searched position has prior kind 3 (k_expand<.., .., true>); the descent picks among its equal-visit candidates
 // (wave_descend), and a self-play move ends in slot_end_move_gumbel: no temperature, no uniform draw, the improved policy as the
 // sample's target.  Every other level is the PUCT of the other instances.
-template <bool REUSE, bool CAP = false, bool FORCED = false, bool GUMBEL = false>
+// AROPEN (arena options, xq_engine_init_ar; one instance, <false, false, false, false, true>): a new game starts with its pair's
+// random opening (slot_arena_opening).  Everything after it is the arena game of the plain instance.
+template <bool REUSE, bool CAP = false, bool FORCED = false, bool GUMBEL = false, bool AROPEN = false>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev E, float *__restrict__ nn_in) {
     __shared__ SelectLds Ls[WAVES_PER_WG];
     SelectLds &L = Ls[threadIdx.x >> 6];
@@ -860,6 +937,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
         }
         if (phase == PH_NEWGAME) {
             if (!slot_new_game(E, s, L, arena)) { phase = PH_IDLE; break; }
+            if (AROPEN) slot_arena_opening(E, s, L);
             if (REUSE && lane == 0) gi[GI_RR_NODE] = 0;     // a new game never sees a hand-off
             phase = PH_NEWPOS;
         }
@@ -1703,6 +1781,31 @@ __global__ __launch_bounds__(CPT) void k_compact_multi(Dev E, int K, int32_t *__
                   n_live, rows);
 }
 
+// Per-model packed step of an arena-options engine (xq_engine_compact_arena): ONE pass of one workgroup compacts the waiting slots
+// twice, into set 0 (the slots the NEW model searches for) and set 1 (the OLD model's).  Slot s is the new model's iff
+// ((first_game + s) even) == (red is to move in the slot's real game).  Every waiting slot is in exactly one set.
+struct ArSets {
+    const ArHead *head;             // first_game is read on the device: the handle has no word left for it
+    int32_t *n_live;                // [2]
+    int32_t *rows[2];
+    float *x[2];
+    uint16_t *moves[2];
+    int32_t *counts[2];
+};
+
+__device__ __forceinline__ bool slot_is_new_models(const Dev &E, int first_game, int slot) {
+    return (((first_game + slot) & 1) == 0) == (E.gi[(size_t)slot * GI_N + GI_SIDE] == 1);
+}
+
+__global__ __launch_bounds__(CPT) void k_compact_arena(Dev E, ArSets A) {
+    const int first_game = A.head->first_game;
+    block_compact(E, E.cfg.n_games, [&](int s) { return slot_waits(E, s) && slot_is_new_models(E, first_game, s); }, A.n_live,
+                  A.rows[0]);
+    __syncthreads();                                  // block_compact's scan scratch is read by every thread before it is reused
+    block_compact(E, E.cfg.n_games, [&](int s) { return slot_waits(E, s) && !slot_is_new_models(E, first_game, s); }, A.n_live + 1,
+                  A.rows[1]);
+}
+
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1917,7 +2020,8 @@ struct Layout {
 // K > 1 (leaf batching): the request rows (moves, counts, paths, packed buffers) are G K, slot-major; the virtual-loss
 // counters and the pending-leaf records follow the K = 1 layout, which is unchanged.  gz_m > 0 (Gumbel root search, K = 1): the
 // square-root table's region also holds the Gumbel words (gz_bytes); every other engine has the layout it had.
-Layout make_layout(const xq_engine_config *c, int K = 1, int gz_m = 0) {
+// arena (arena options, K = 1, never Gumbel): that region holds the arena words instead (ar_off).
+Layout make_layout(const xq_engine_config *c, int K = 1, int gz_m = 0, bool arena = false) {
     Layout l;
     memset(&l, 0, sizeof(l));
     const size_t G = (size_t)c->n_games, S = (size_t)c->num_simulations, GK = G * (size_t)K;
@@ -1946,7 +2050,7 @@ Layout make_layout(const xq_engine_config *c, int K = 1, int gz_m = 0) {
     put(P_OUTR, (size_t)(c->max_out_results > 0 ? c->max_out_results : 1) * XQ_RESULT_BYTES);
     put(P_CNT, 64);
     put(P_STATS, G * ST_N * 8);
-    put(P_SQRT, (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0));
+    put(P_SQRT, arena ? ar_off(G, S).end : (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0));
     put(P_MNOISE, G * XQ_MAXM * 8);
     put(P_STATSUM, ST_N * 8);
     put(P_REQ, GK * 4);
@@ -2001,17 +2105,40 @@ bool gumbel_ok(const xq_engine_config *c, int K, unsigned flags, const xq_playou
     return gz->considered >= 1 && gz->considered <= XQ_MAXM && (float)gz->c_scale > 0.0f;
 }
 
+// arena options: arena games only (so K = 1 and none of tree reuse, playout cap, forced playouts, Gumbel: each refuses
+// manual_moves = 2 itself), 0 <= opening_plies <= XQ_ARENA_MAX_OPENING, first_game >= 0 with first_game + n_games an int32
+bool arena_ok(const xq_engine_config *c, const xq_arena_opts *ar) {
+    if (c->manual_moves != 2 || ar->reserved[0] != 0 || ar->reserved[1] != 0) return false;
+    if (ar->opening_plies < 0 || ar->opening_plies > XQ_ARENA_MAX_OPENING) return false;
+    return ar->first_game >= 0 && ar->first_game <= 0x7FFFFFFF - c->n_games;
+}
+
 // pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
 // flag bits "playout cap on" (xq_engine_init_cap), "forced playouts on" (xq_engine_init_fp) and "Gumbel root search on"
-// (xq_engine_init_gz)
+// (xq_engine_init_gz) and "arena options on" (xq_engine_init_ar)
 constexpr int PAD0_CAP = 1 << 30;
 constexpr int PAD0_FORCED = 1 << 29;
 constexpr int PAD0_GUMBEL = 1 << 28;
+constexpr int PAD0_ARENA = 1 << 27;
 int leaves_of(const xq_engine *e) { return (e->pad0 & 0xFFFF) > 1 ? (e->pad0 & 0xFFFF) : 1; }
 bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE_TREE_REUSE; }
 bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
 bool forced_of(const xq_engine *e) { return (e->pad0 & PAD0_FORCED) != 0; }
 bool gumbel_of(const xq_engine *e) { return (e->pad0 & PAD0_GUMBEL) != 0; }
+bool arena_of(const xq_engine *e) { return e && (e->pad0 & PAD0_ARENA) != 0 && e->cfg.n_games > 0 && e->p[P_SQRT]; }
+
+ArSets make_ar_sets(const xq_engine *e) {
+    const ArOff o = ar_off((size_t)e->cfg.n_games, (size_t)e->cfg.num_simulations);
+    char *base = (char *)e->p[P_SQRT];
+    ArSets a;
+    a.head = (const ArHead *)(base + o.head);
+    a.n_live = (int32_t *)(base + o.n_live);
+    for (int m = 0; m < 2; ++m) {
+        a.rows[m] = (int32_t *)(base + o.rows[m]); a.x[m] = (float *)(base + o.x[m]);
+        a.moves[m] = (uint16_t *)(base + o.moves[m]); a.counts[m] = (int32_t *)(base + o.counts[m]);
+    }
+    return a;
+}
 
 // the K = 1 step's two kernels, by the engine's options: instance [FORCED][CAP][REUSE]; a Gumbel engine has none of the three
 // and its own instance of each kernel
@@ -2022,6 +2149,10 @@ void launch_select(const xq_engine *eng, const Dev &d, float *nn_in, hipStream_t
     const dim3 grid((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), block(64 * WAVES_PER_WG);
     if (gumbel_of(eng)) {
         hipLaunchKernelGGL((k_select<false, false, false, true>), grid, block, 0, s, d, nn_in);
+        return;
+    }
+    if (arena_of(eng)) {
+        hipLaunchKernelGGL((k_select<false, false, false, false, true>), grid, block, 0, s, d, nn_in);
         return;
     }
     hipLaunchKernelGGL(k[forced_of(eng)][cap_of(eng)][reuse_of(eng)], grid, block, 0, s, d, nn_in);
@@ -2082,6 +2213,14 @@ size_t xq_engine_workspace_bytes_gz(const xq_engine_config *cfg, int leaves_per_
     return make_layout(cfg, 1, gumbel->considered).total;
 }
 
+size_t xq_engine_workspace_bytes_ar(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena) {
+    const size_t plain = xq_engine_workspace_bytes_gz(cfg, leaves_per_step, flags, cap, forced, gumbel);
+    if (!arena || plain == 0) return plain;
+    if (!arena_ok(cfg, arena)) return 0;
+    return make_layout(cfg, 1, 0, true).total;
+}
+
 int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out) {
     if (k < 1 || k > XQ_MAXM || num_simulations < 1 || num_simulations > 65535 || !host_out) return XQ_ERR_ARG;
     gz_considered_visits(k, num_simulations, host_out);
@@ -2116,20 +2255,28 @@ int xq_engine_init_fp(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
 int xq_engine_init_gz(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
                       const xq_forced_playouts *forced, const xq_gumbel *gumbel, void *ws, size_t ws_bytes,
                       const uint64_t *dev_inject, void *stream) {
+    return xq_engine_init_ar(eng, cfg, leaves_per_step, flags, cap, forced, gumbel, nullptr, ws, ws_bytes, dev_inject, stream);
+}
+
+int xq_engine_init_ar(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena, void *ws,
+                      size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
     if (!eng || !config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags) || !ws ||
         ((uintptr_t)ws & 255))
         return XQ_ERR_ARG;
     if (cap && !cap_ok(cfg, leaves_per_step, cap)) return XQ_ERR_ARG;
     if (forced && !forced_ok(cfg, leaves_per_step, forced)) return XQ_ERR_ARG;
     if (gumbel && !gumbel_ok(cfg, leaves_per_step, flags, cap, forced, gumbel)) return XQ_ERR_ARG;
+    if (arena && !arena_ok(cfg, arena)) return XQ_ERR_ARG;
     if (cfg->inject_len > 0 && !dev_inject) return XQ_ERR_ARG;
     const int K = leaves_per_step;
-    const Layout l = make_layout(cfg, K, gumbel ? gumbel->considered : 0);
+    const Layout l = make_layout(cfg, K, gumbel ? gumbel->considered : 0, arena != nullptr);
     if (ws_bytes < l.total) return XQ_ERR_WORKSPACE;
     memset(eng, 0, sizeof(*eng));
     eng->cfg = *cfg;
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
-    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16) | (cap ? PAD0_CAP : 0) | (forced ? PAD0_FORCED : 0) | (gumbel ? PAD0_GUMBEL : 0);
+    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16) | (cap ? PAD0_CAP : 0) | (forced ? PAD0_FORCED : 0) | (gumbel ? PAD0_GUMBEL : 0) |
+                (arena ? PAD0_ARENA : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -2146,7 +2293,10 @@ int xq_engine_init_gz(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
         const int n = cfg->num_simulations + 2 + (K > 1 ? K : 0);   // K > 1: N_parent + vl_parent < S + K
         // Gumbel root search: the parameters, a zeroed v_hat per slot and the considered-visit tables for k = 1 .. m follow the table
         const size_t S = (size_t)cfg->num_simulations, G = (size_t)cfg->n_games;
-        const size_t bytes = sizeof(double) * n + (gumbel ? gz_bytes(G, S, (size_t)gumbel->considered) : 0);
+        // arena options: the whole region zeroed (openings record, both sets' counts and rows), then the table and the parameters
+        const ArOff ao = ar_off(G, S);
+        if (arena) XQ_TRY(hipMemsetAsync(eng->p[P_SQRT], 0, ao.end, s));
+        const size_t bytes = arena ? ao.head + sizeof(ArHead) : sizeof(double) * n + (gumbel ? gz_bytes(G, S, (size_t)gumbel->considered) : 0);
         double *tab = (double *)calloc(bytes, 1);
         if (!tab) return XQ_ERR_ARG;
         for (int i = 0; i < n; ++i) tab[i] = sqrt((double)i);   // math.sqrt(visit_count), mcts.py:49
@@ -2155,6 +2305,10 @@ int xq_engine_init_gz(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
             h->m = gumbel->considered; h->c_visit = (float)gumbel->c_visit; h->c_scale = (float)gumbel->c_scale;
             uint16_t *vis = (uint16_t *)((char *)(h + 1) + G * 8);
             for (int k = 1; k <= gumbel->considered; ++k) gz_considered_visits(k, (int)S, vis + (size_t)(k - 1) * S);
+        }
+        if (arena) {
+            ArHead *h = (ArHead *)((char *)tab + ao.head);
+            h->opening_plies = arena->opening_plies; h->first_game = arena->first_game;
         }
         const int rc = xq::check(hipMemcpyAsync(eng->p[P_SQRT], tab, bytes, hipMemcpyHostToDevice, s));
         if (rc == XQ_OK) (void)hipStreamSynchronize(s);
@@ -2269,6 +2423,57 @@ int xq_engine_expand_packed(const xq_engine *eng, const float *dev_packed_logits
                        (const int32_t *)eng->p[P_PK_ROWS], dev_packed_logits, dev_packed_value, slot_logits, slot_value, G);
     const int rc = launch_status();
     if (rc != XQ_OK) return rc;
+    return xq_engine_expand_legal(eng, slot_logits, slot_value, stream);
+}
+
+int xq_engine_arena_openings(const xq_engine *eng, const uint16_t **dev_actions, const int32_t **dev_counts) {
+    if (!arena_of(eng) || !dev_actions || !dev_counts) return XQ_ERR_ARG;
+    const ArOff o = ar_off((size_t)eng->cfg.n_games, (size_t)eng->cfg.num_simulations);
+    *dev_actions = (const uint16_t *)((char *)eng->p[P_SQRT] + o.op_actions);
+    *dev_counts = (const int32_t *)((char *)eng->p[P_SQRT] + o.op_counts);
+    return XQ_OK;
+}
+
+int xq_engine_compact_arena(const xq_engine *eng, const float *dev_nn_input, void *stream) {
+    if (!arena_of(eng) || !dev_nn_input) return XQ_ERR_ARG;
+    const Dev d = make_dev(eng);
+    const ArSets a = make_ar_sets(eng);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_compact_arena, dim3(1), dim3(CPT), 0, s, d, a);
+    for (int m = 0; m < 2; ++m) {
+        const int rc = launch_status();
+        if (rc != XQ_OK) return rc;
+        hipLaunchKernelGGL(k_gather_rows, dim3(eng->cfg.n_games), dim3(256), 0, s, d, (const int32_t *)(a.n_live + m),
+                           (const int32_t *)a.rows[m], dev_nn_input, a.x[m], a.moves[m], a.counts[m]);
+    }
+    return launch_status();
+}
+
+int xq_engine_packed_arena(const xq_engine *eng, xq_engine_packed_buffers out[2]) {
+    if (!arena_of(eng) || !out) return XQ_ERR_ARG;
+    const ArSets a = make_ar_sets(eng);
+    for (int m = 0; m < 2; ++m) {
+        out[m].n_live = a.n_live + m; out[m].rows = a.rows[m]; out[m].x = a.x[m]; out[m].moves = a.moves[m];
+        out[m].counts = a.counts[m];
+        out[m].slot_logits = (const float *)eng->p[P_PK_LOGITS]; out[m].slot_value = (const float *)eng->p[P_PK_VALUE];
+    }
+    return XQ_OK;
+}
+
+int xq_engine_expand_packed_arena(const xq_engine *eng, const float *dev_logits_new, const float *dev_value_new,
+                                  const float *dev_logits_old, const float *dev_value_old, void *stream) {
+    if (!arena_of(eng) || !dev_logits_new || !dev_value_new || !dev_logits_old || !dev_value_old) return XQ_ERR_ARG;
+    if ((((uintptr_t)dev_logits_new) | ((uintptr_t)dev_logits_old)) & 7) return XQ_ERR_ARG;
+    const int G = eng->cfg.n_games;
+    const ArSets a = make_ar_sets(eng);
+    float *slot_logits = (float *)eng->p[P_PK_LOGITS], *slot_value = (float *)eng->p[P_PK_VALUE];
+    const float *logits[2] = {dev_logits_new, dev_logits_old}, *value[2] = {dev_value_new, dev_value_old};
+    for (int m = 0; m < 2; ++m) {
+        hipLaunchKernelGGL(k_scatter_rows, dim3((G + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const int32_t *)(a.n_live + m),
+                           (const int32_t *)a.rows[m], logits[m], value[m], slot_logits, slot_value, G);
+        const int rc = launch_status();
+        if (rc != XQ_OK) return rc;
+    }
     return xq_engine_expand_legal(eng, slot_logits, slot_value, stream);
 }
 

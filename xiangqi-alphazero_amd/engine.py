@@ -60,6 +60,12 @@ on them by sequential halving, the move with the best g + log prior + sigma(q) a
 and the sample's `visits` hold the completed-Q improved policy quantised to 16 bits (`reserved0` = 1) instead of visit counts.
 Interior nodes keep PUCT.  `stats()` adds `gumbel_moves`, `gumbel_considered` and `gumbel_offprior`.  Self-play and search only
 (manual_moves 0 or 1), K = 1; it combines with the evaluation cache and with nothing else.
+
+With `arena_opts=(opening_plies, first_game)` (opt-in; xq_engine_init_ar) an arena engine (manual_moves = 2)
+starts game `first_game + slot` with `opening_plies` random legal plies drawn for the game's PAIR, so games 2p and 2p + 1 share an
+opening with colours swapped, and offers the per-model packed step: `compact_arena()` packs the waiting slots into two buffer sets
+(`arena_packed[0]`: the new model's slots, `arena_packed[1]`: the old model's), `expand_packed_arena()` scatters both models'
+outputs back.  `arena_openings()` reads what was played.  K = 1, none of the other options.
 """
 from __future__ import annotations
 
@@ -112,7 +118,7 @@ def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
 class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
-                 tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None):
+                 tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None):
         K = int(leaves_per_step)
         if not 1 <= K <= 64:
             raise hip.XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
@@ -173,6 +179,23 @@ class SelfPlayEngine:
             if not (0.0 <= gcv <= f32_max) or not (0.0 < gcs <= f32_max) or not float(np.float32(gcs)) > 0.0:   # a NaN fails them
                 raise hip.XqError(f"gumbel: c_visit >= 0 and c_scale > 0, finite as float32, required; got {gcv}, {gcs}")
             gz = hip.Gumbel(gm, 0, gcv, gcs)
+        ar = None
+        if arena_opts is not None:
+            try:
+                ar_plies, ar_first = int(arena_opts[0]), int(arena_opts[1])
+                if len(arena_opts) != 2 or ar_plies != arena_opts[0] or ar_first != arena_opts[1]:
+                    raise ValueError
+            except (TypeError, ValueError, IndexError, OverflowError):
+                raise hip.XqError("arena_opts must be (opening_plies, first_game)")
+            if int(cfg.manual_moves) != 2:
+                raise hip.XqError("arena_opts needs an arena engine (manual_moves = 2)")
+            if K > 1 or tree_reuse or cap is not None or forced is not None or gz is not None or eval_cache_entries:
+                raise hip.XqError("arena_opts cannot be combined with another engine option")
+            if not 0 <= ar_plies <= hip.ARENA_MAX_OPENING:
+                raise hip.XqError(f"arena_opts: opening_plies must be in [0, {hip.ARENA_MAX_OPENING}], got {ar_plies}")
+            if not 0 <= ar_first <= 2 ** 31 - 1 - int(cfg.n_games):
+                raise hip.XqError(f"arena_opts: first_game must be a non-negative int32 game index, got {ar_first}")
+            ar = hip.ArenaOpts(ar_plies, ar_first)
         if K > 1 and eval_cache_entries:
             raise hip.XqError("leaves_per_step > 1 cannot be combined with an evaluation cache (eval_cache_entries > 0)")
         if K > 1 and int(cfg.manual_moves) == 2:
@@ -188,11 +211,14 @@ class SelfPlayEngine:
         self.playout_cap = None if cap is None else (cap.full_search_prob, cap.fast_simulations)
         self.forced_playouts = None if forced is None else float(np.float32(forced.k))   # k as the kernels use it
         self.gumbel = None if gz is None else (gz.considered, float(np.float32(gz.c_visit)), float(np.float32(gz.c_scale)))
+        self.arena_opts = None if ar is None else (ar.opening_plies, ar.first_game)
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         flags = hip.ENGINE_TREE_REUSE if tree_reuse else 0
         cap_ref = None if cap is None else C.byref(cap)
-        if gz is not None:
+        if ar is not None:
+            nbytes = self.lib.xq_engine_workspace_bytes_ar(C.byref(cfg), K, flags, None, None, None, C.byref(ar))
+        elif gz is not None:
             nbytes = self.lib.xq_engine_workspace_bytes_gz(C.byref(cfg), K, flags, None, None, C.byref(gz))
         elif forced is not None:
             nbytes = self.lib.xq_engine_workspace_bytes_fp(C.byref(cfg), K, flags, cap_ref, C.byref(forced))
@@ -218,7 +244,11 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            if gz is not None:
+            if ar is not None:
+                hip.check(self.lib.xq_engine_init_ar(C.byref(self.h), C.byref(cfg), K, flags, None, None, None, C.byref(ar), base,
+                                                     self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
+                          "xq_engine_init_ar")
+            elif gz is not None:
                 hip.check(self.lib.xq_engine_init_gz(C.byref(self.h), C.byref(cfg), K, flags, None, None, C.byref(gz), base,
                                                      self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
                           "xq_engine_init_gz")
@@ -265,6 +295,20 @@ class SelfPlayEngine:
         self.packed_counts = ws_view(pb.counts, G * 4, torch.int32)
         self.slot_logits = ws_view(pb.slot_logits, G * hip.MAXM * 4, torch.float32).view(G, hip.MAXM)
         self.slot_value = ws_view(pb.slot_value, G * 4, torch.float32)
+        self.arena_packed = None
+        if ar is not None:
+            # the per-model packed step's two buffer sets (xq_engine_packed_arena) and the openings record
+            pbs = (hip.PackedBuffers * 2)()
+            hip.check(self.lib.xq_engine_packed_arena(C.byref(self.h), pbs), "xq_engine_packed_arena")
+            self.arena_packed = tuple(dict(
+                n_live=ws_view(b.n_live, 4, torch.int32), rows=ws_view(b.rows, G * 4, torch.int32),
+                x=ws_view(b.x, G * hip.STATE_FLOATS * 4, torch.float32).view(G, 15, 10, 9),
+                moves=ws_view(b.moves, G * hip.MAXM * 2, torch.int16).view(G, hip.MAXM),
+                counts=ws_view(b.counts, G * 4, torch.int32)) for b in pbs)
+            pa, pc = C.c_void_p(), C.c_void_p()
+            hip.check(self.lib.xq_engine_arena_openings(C.byref(self.h), C.byref(pa), C.byref(pc)), "xq_engine_arena_openings")
+            self._opening_actions = ws_view(pa.value, G * hip.ARENA_MAX_OPENING * 2, torch.int16).view(G, hip.ARENA_MAX_OPENING)
+            self._opening_counts = ws_view(pc.value, G * 4, torch.int32)
         self.cache = None
         if eval_cache_entries:
             self._init_cache(int(eval_cache_entries))
@@ -375,6 +419,43 @@ class SelfPlayEngine:
                                                    hip.stream_ptr(self.device)), "xq_engine_expand_packed")
         self._keep = (self.slot_logits, self.slot_value)    # slot-ordered, as the full-width step's (bench.py --dump-outputs)
         self._keep_packed = (legal_logits, value)          # keep alive until the stream has consumed them
+
+    # ---- arena options (xq_engine_init_ar) -----------------------------------------------------------------
+    def _need_arena_opts(self, what: str):
+        if self.arena_packed is None:
+            raise hip.XqError(f"{what} needs an engine with arena_opts=")
+
+    def compact_arena(self):
+        """After `select`: pack the waiting slots into the two sets of `arena_packed` (xq_engine_compact_arena): [0] the slots the
+        new model searches for, [1] the old model's; per set `n_live`, `rows`, `x`, `moves`, `counts`.  Asynchronous."""
+        self._need_arena_opts("compact_arena")
+        hip.check(self.lib.xq_engine_compact_arena(C.byref(self.h), self.nn_input.data_ptr(), hip.stream_ptr(self.device)),
+                  "xq_engine_compact_arena")
+
+    def expand_packed_arena(self, logits_new: torch.Tensor, value_new: torch.Tensor, logits_old: torch.Tensor,
+                            value_old: torch.Tensor):
+        """Expansion from the two models' PACKED outputs (rows [0, n_live) of float32[G, 128] / [G] each, over set 0 and set 1):
+        scattered back to `slot_logits` / `slot_value`, then xq_engine_expand_legal (xq_engine_expand_packed_arena)."""
+        self._need_arena_opts("expand_packed_arena")
+        keep = []
+        for ll, v in ((logits_new, value_new), (logits_old, value_old)):
+            if ll.dtype != torch.float32 or v.dtype != torch.float32:
+                raise hip.XqError("legal_logits/value must be float32")
+            ll, v = ll.contiguous(), v.contiguous().view(-1)
+            if ll.shape != (self.rows, hip.MAXM) or v.shape != (self.rows,):
+                raise hip.XqError(f"bad evaluator output shapes {tuple(ll.shape)} {tuple(v.shape)}")
+            keep += [ll, v]
+        hip.check(self.lib.xq_engine_expand_packed_arena(C.byref(self.h), keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(),
+                                                         keep[3].data_ptr(), hip.stream_ptr(self.device)),
+                  "xq_engine_expand_packed_arena")
+        self._keep = (self.slot_logits, self.slot_value)
+        self._keep_packed = tuple(keep)                    # keep alive until the stream has consumed them
+
+    def arena_openings(self):
+        """-> (actions uint16 [G, 16], counts int32 [G]) on the host: what every slot played as its opening (zero past its count;
+        count 0 before the game started, after the restart rule and with opening_plies = 0).  Synchronises."""
+        self._need_arena_opts("arena_openings")
+        return self._opening_actions.cpu().numpy().view(np.uint16).copy(), self._opening_counts.cpu().numpy().copy()
 
     @property
     def path(self) -> str:
@@ -573,6 +654,11 @@ class SelfPlayEngine:
             hip.check(n, "xq_engine_read_root")
         return dict(actions=a[:n], visits=v[:n], total_value=w[:n], prior=p[:n], prior_is_f64=bool(kind.value),
                     prior_kind=int(kind.value), root_visits=rv.value, sims_done=sd.value)
+
+
+def arena_engine(cfg: hip.EngineConfig, device, opening_plies: int, first_game: int, inject=None) -> SelfPlayEngine:
+    """The arena's engine with arena options (paired openings from game index `first_game`, the per-model packed step)."""
+    return SelfPlayEngine(cfg, device, inject=inject, arena_opts=(int(opening_plies), int(first_game)))
 
 
 action_probs_dense = dense_pi   # the reference's dense pi (mcts.py:190-206) from compact (action, visit) pairs

@@ -21,6 +21,7 @@ RESULT_BYTES = 16
 ACTION_SPACE = 8100
 STATE_FLOATS = 1350
 ENGINE_TREE_REUSE = 1          # XQ_ENGINE_TREE_REUSE
+ARENA_MAX_OPENING = 16         # XQ_ARENA_MAX_OPENING
 REUSE_MAX_SIMS = 1600          # XQ_REUSE_MAX_SIMS
 
 
@@ -84,6 +85,11 @@ class ForcedPlayouts(C.Structure):
 class Gumbel(C.Structure):
     """xq_gumbel: Gumbel root search with sequential halving (xq_engine_init_gz): considered moves m, c_visit, c_scale."""
     _fields_ = [("considered", C.c_int32), ("reserved", C.c_int32), ("c_visit", C.c_double), ("c_scale", C.c_double)]
+
+
+class ArenaOpts(C.Structure):
+    """xq_arena_opts: arena options (xq_engine_init_ar): opening plies R of the paired random openings, game index of slot 0."""
+    _fields_ = [("opening_plies", C.c_int32), ("first_game", C.c_int32), ("reserved", C.c_uint32 * 2)]
 
 
 class PackedBuffers(C.Structure):
@@ -151,6 +157,15 @@ def lib():
     L.xq_engine_init_gz.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap),
                                     C.POINTER(ForcedPlayouts), C.POINTER(Gumbel), vp, C.c_size_t, vp, vp]
     L.xq_gumbel_considered_visits_host.argtypes = [i32, i32, vp]
+    L.xq_engine_workspace_bytes_ar.argtypes = [C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap),
+                                               C.POINTER(ForcedPlayouts), C.POINTER(Gumbel), C.POINTER(ArenaOpts)]
+    L.xq_engine_workspace_bytes_ar.restype = C.c_size_t
+    L.xq_engine_init_ar.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap),
+                                    C.POINTER(ForcedPlayouts), C.POINTER(Gumbel), C.POINTER(ArenaOpts), vp, C.c_size_t, vp, vp]
+    L.xq_engine_arena_openings.argtypes = [C.POINTER(Engine), C.POINTER(vp), C.POINTER(vp)]
+    L.xq_engine_compact_arena.argtypes = [C.POINTER(Engine), vp, vp]
+    L.xq_engine_packed_arena.argtypes = [C.POINTER(Engine), C.POINTER(PackedBuffers)]
+    L.xq_engine_expand_packed_arena.argtypes = [C.POINTER(Engine), vp, vp, vp, vp, vp]
     L.xq_engine_select.argtypes = [C.POINTER(Engine), vp, vp]
     L.xq_engine_expand.argtypes = [C.POINTER(Engine), vp, vp, i32, vp]
     L.xq_engine_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(EngineStats), vp]
@@ -226,7 +241,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_evcache_key_host", "xq_engine_workspace_bytes_leaves", "xq_engine_init_leaves", "xq_engine_workspace_bytes_ex",
            "xq_engine_init_ex", "xq_engine_drop_reroots", "xq_engine_workspace_bytes_cap", "xq_engine_init_cap",
            "xq_engine_workspace_bytes_fp", "xq_engine_init_fp", "xq_engine_workspace_bytes_gz", "xq_engine_init_gz",
-           "xq_gumbel_considered_visits_host"]
+           "xq_gumbel_considered_visits_host", "xq_engine_workspace_bytes_ar", "xq_engine_init_ar", "xq_engine_arena_openings",
+           "xq_engine_compact_arena", "xq_engine_packed_arena", "xq_engine_expand_packed_arena"]
 
 
 def check(rc: int, what: str):

@@ -121,6 +121,11 @@ class AlphaZeroLoop:
         return stats
 
     def _arena(self) -> dict:
+        if int(getattr(self.config, "arena_opening_plies", 0) or 0) > 0:
+            # paired random openings (opt-in): another seed every iteration, so successive gates see different openings
+            seed = int(getattr(self.config, "arena_seed", 0) or 0) + self.iteration
+            return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind,
+                                         seed=seed)
         return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind)
 
     def evaluate(self) -> dict:
