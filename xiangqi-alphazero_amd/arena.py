@@ -112,7 +112,7 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
         x = eng.select()
         # the model that is SEARCHING evaluates every node of its search (root and leaves at any depth), so the
         # choice follows the side to move of the real game, not of the evaluated position (train.py:479-483)
-        red_to_move = eng.slot_ints[:, 0] == 1
+        red_to_move = eng.slot_ints[:, hip.GI_SIDE] == 1
         use_new = new_is_red == red_to_move
         if sparse:
             # No host round trip in a step: each model runs over the whole (small) slot batch with the OTHER model's

@@ -1,5 +1,15 @@
 // xq_engine.hip -- device-resident self-play engine (B3): SoA MCTS trees in HBM, one wavefront per game.
 //
+// The engine's source, file by file:
+//   xq_engine_state.cuh  : shared by the four units below -- enums (Phase, Gi, St, Ptr, Rng), the device view Dev, the Gumbel and
+//                          arena words behind the square-root table, the pad0 encoding, Philox, block_compact.  No kernel.
+//   xq_engine.hip        : the search (this file) -- k_select, k_expand, k_reroot, k_drop_reroots, k_select_multi, k_expand_multi and
+//                          xq_engine_select / _expand / _expand_legal / _requests / _drop_reroots.
+//   xq_engine_setup.hip  : the workspace layout, the option checks (Opts, opts_ok), every xq_engine_workspace_bytes* and
+//                          xq_engine_init*, and the host-side readers (stats, drain, set_position, read_root).
+//   xq_engine_packed.hip : the packed steps -- compaction, gather, scatter, and the arena's two-set variant.
+//   xq_evcache.hip       : the evaluation cache (xq_evcache_*, xq_engine_compact_misses).
+//
 //   k_select : per game, advance the game/search state machine until ONE network evaluation is needed:
 //                finish games (flush samples with z), start games (random opening), finish moves (visit
 //                counts -> sample -> sampled action -> make_move), run simulations: PUCT descent with lanes over
@@ -18,166 +28,16 @@
 // PUCT evaluated in float32 as f32(q) + ((f32(c)*P)*f32(sqrt(N_parent)))/f32(1+N); at a noisy root (and for the
 // uniform fallback) priors and PUCT are float64; W accumulates in float64; first maximum wins.
 // Floating-point contraction is OFF for this file.
-#include <float.h>
-#include <math.h>
-#include <string.h>
-
-#include "xq_common.h"
-#include "xq_rules.cuh"
+#include "xq_engine_state.cuh"
 
 #pragma clang fp contract(off)
-
-using namespace xq;
 
 static_assert(sizeof(xq_sample) == XQ_SAMPLE_BYTES, "xq_sample layout");
 static_assert(sizeof(xq_game_result) == XQ_RESULT_BYTES, "xq_game_result layout");
 
 namespace {
 
-enum Phase : int { PH_NEWGAME = 0, PH_NEWPOS = 1, PH_WAIT_ROOT = 2, PH_SEARCH = 3, PH_WAIT_LEAF = 4, PH_FINISHED = 5,
-                   PH_IDLE = 6, PH_HOLD = 7 };
-
-enum Gi : int { GI_SIDE = 0, GI_MC, GI_NOCAP, GI_PHASE, GI_SIMS, GI_NSAMP, GI_GSEQ, GI_ALLOC, GI_PLEAF, GI_PDEPTH,
-                GI_PCOUNT, GI_RSTATUS, GI_RWINNER, GI_RESIGN_N, GI_RNG0, GI_RNG1, GI_RNG2, GI_RNG3, GI_FWINNER,
-                GI_FREASON, GI_MANNOISE, GI_DELAY, GI_NPEND, GI_RR_NODE, GI_RR_MARK, GI_RR_DROP,
-                // playout cap (xq_engine_init_cap): this move's kind (1 full, 0 fast) and budget, written by k_select<.., true> at
-                // PH_NEWPOS; S_fast and the two halves of the float64 threshold p, written once by k_init_cap
-                GI_CAP_FULL, GI_CAP_BUDGET, GI_CAP_SFAST, GI_CAP_PLO, GI_CAP_PHI,
-                // forced playouts (xq_engine_init_fp): k as float32 bits, written once by k_init_fp
-                GI_FP_K, GI_N = 32 };
-static_assert(GI_FP_K == 31, "the forced-playout parameter takes the last free state word");
-
-enum St : int { ST_SIMS = 0, ST_TERM, ST_LEAF, ST_ROOT, ST_MOVES, ST_GAMES, ST_RED, ST_BLACK, ST_DRAW, ST_PLIES, ST_NODES,
-                ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_COLL, ST_LPS, ST_LSTEPS, ST_REUSED,
-                ST_REROOTS, ST_FASTM, ST_FASTS, ST_FORCED, ST_PRUNEDV, ST_PRUNEDC, ST_GZ_MOVES, ST_GZ_CONS, ST_GZ_OFF, ST_N = 32 };
-static_assert(ST_GZ_OFF == 31, "the Gumbel counters take the last free statistics words");
-
-enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_TW, P_TP, P_TA, P_TC, P_TM, P_ROOTP,
-                 P_STAGE, P_OUTS, P_OUTR, P_CNT, P_STATS, P_INJECT, P_SQRT, P_MNOISE, P_STATSUM, P_REQ,
-                 P_PK_N, P_PK_ROWS, P_PK_X, P_PK_MOVES, P_PK_COUNTS, P_PK_LOGITS, P_PK_VALUE, P_VL, P_LEAF };
-
-enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM = 3 };
 constexpr uint32_t RNG_ARENA_OPENING = 8u;  // xq_engine_init_ar: keyed by the PAIR and rank 0, never by the slot (7 is k_init's stagger)
-
-// Device view of the engine (passed by value to kernels)
-struct Dev {
-    xq_engine_config cfg;
-    int node_cap, path_cap, stage_cap;
-    int8_t *board, *hist;
-    int32_t *gi;
-    double *resign;
-    uint16_t *pmoves;
-    int32_t *path;
-    int32_t *tN; double *tW; float *tP; uint16_t *tA; int32_t *tC; uint16_t *tM;
-    double *rootP;
-    uint8_t *stage, *outs, *outr;
-    unsigned int *cnt;              // [0] out samples, [1] out results
-    unsigned long long *started;    // games started (quota)
-    unsigned long long *stats;      // [G][ST_N]
-    const uint64_t *inject;
-    const double *sqrt_tab;
-    double *mnoise;
-    int32_t *req;                   // [G] legal moves of the evaluation each slot asked for this step (0: none)
-};
-
-Dev make_dev(const xq_engine *e) {
-    Dev d;
-    d.cfg = e->cfg;
-    d.node_cap = e->node_cap; d.path_cap = e->path_cap; d.stage_cap = e->stage_cap;
-    d.board = (int8_t *)e->p[P_BOARD]; d.hist = (int8_t *)e->p[P_HIST]; d.gi = (int32_t *)e->p[P_GI];
-    d.resign = (double *)e->p[P_RESIGN]; d.pmoves = (uint16_t *)e->p[P_PMOVES]; d.path = (int32_t *)e->p[P_PATH];
-    d.tN = (int32_t *)e->p[P_TN]; d.tW = (double *)e->p[P_TW]; d.tP = (float *)e->p[P_TP];
-    d.tA = (uint16_t *)e->p[P_TA]; d.tC = (int32_t *)e->p[P_TC]; d.tM = (uint16_t *)e->p[P_TM];
-    d.rootP = (double *)e->p[P_ROOTP]; d.stage = (uint8_t *)e->p[P_STAGE]; d.outs = (uint8_t *)e->p[P_OUTS];
-    d.outr = (uint8_t *)e->p[P_OUTR]; d.cnt = (unsigned int *)e->p[P_CNT];
-    d.started = (unsigned long long *)((char *)e->p[P_CNT] + 16);
-    d.stats = (unsigned long long *)e->p[P_STATS]; d.inject = (const uint64_t *)e->p[P_INJECT];
-    d.sqrt_tab = (const double *)e->p[P_SQRT]; d.mnoise = (double *)e->p[P_MNOISE]; d.req = (int32_t *)e->p[P_REQ];
-    return d;
-}
-
-// Gumbel root search (xq_engine_init_gz): its words live behind the square-root table, in that table's workspace region (the handle,
-// the config struct and the per-slot state words are full): the parameters, the root's network value of every slot, and the
-// considered-visit tables, row k - 1 for k considered moves.  K = 1 always, so the square-root table has S + 2 entries.
-struct GzHead {
-    int32_t m;                      // considered moves at most
-    float c_visit, c_scale;         // rounded to float32 once, widened at every use
-    int32_t pad;
-};
-static_assert(sizeof(GzHead) == 16, "GzHead layout");
-
-size_t gz_bytes(size_t G, size_t S, size_t m) { return sizeof(GzHead) + G * 8 + m * S * 2; }
-
-__device__ __forceinline__ const GzHead *gz_head(const Dev &E) { return (const GzHead *)(E.sqrt_tab + E.cfg.num_simulations + 2); }
-__device__ __forceinline__ double *gz_vhat(const Dev &E) { return (double *)(gz_head(E) + 1); }
-__device__ __forceinline__ const uint16_t *gz_table(const Dev &E) { return (const uint16_t *)(gz_vhat(E) + E.cfg.n_games); }
-
-// Arena options (xq_engine_init_ar; manual_moves = 2, so never a Gumbel engine): their words lie behind the square-root table as
-// well, from the next 256-byte boundary on: the parameters, what every slot played as its opening, and the two buffer sets of the
-// per-model packed step (set 0: the new model's slots, set 1: the old model's).  Offsets from the table's first byte.
-struct ArHead {
-    int32_t opening_plies, first_game, pad[2];
-};
-static_assert(sizeof(ArHead) == 16, "ArHead layout");
-
-struct ArOff {
-    size_t head, op_counts, op_actions, n_live, rows[2], x[2], moves[2], counts[2], end;
-};
-
-__host__ __device__ inline size_t ar_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-__host__ __device__ inline ArOff ar_off(size_t G, size_t S) {
-    ArOff a;
-    size_t o = ar_align((S + 2) * 8);
-    a.head = o; o = ar_align(o + sizeof(ArHead));
-    a.op_counts = o; o = ar_align(o + G * 4);
-    a.op_actions = o; o = ar_align(o + G * XQ_ARENA_MAX_OPENING * 2);
-    a.n_live = o; o = ar_align(o + 2 * 4);
-    for (int m = 0; m < 2; ++m) {
-        a.rows[m] = o; o = ar_align(o + G * 4);
-        a.x[m] = o; o = ar_align(o + G * XQ_STATE_FLOATS * 4);
-        a.moves[m] = o; o = ar_align(o + G * XQ_MAXM * 2);
-        a.counts[m] = o; o = ar_align(o + G * 4);
-    }
-    a.end = o;
-    return a;
-}
-
-// get_sequence_of_considered_visits(k, S) of include/xq_hip.h: out[t] = the visit count a root child must have to be a
-// candidate of simulation t
-__host__ void gz_considered_visits(int k, int S, uint16_t *out) {
-    if (k <= 1) { for (int t = 0; t < S; ++t) out[t] = (uint16_t)t; return; }
-    int log2max = 0;
-    while ((1 << log2max) < k) ++log2max;
-    int n = 0, considered = k, base = 0;           // every considered move has `base` visits when a phase starts
-    while (n < S) {
-        int extra = S / (log2max * considered);
-        if (extra < 1) extra = 1;
-        for (int e = 0; e < extra; ++e)
-            for (int i = 0; i < considered && n < S; ++i) out[n++] = (uint16_t)(base + e);
-        base += extra;
-        considered = considered / 2 > 2 ? considered / 2 : 2;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// RNG: Philox4x32-10 keyed by (seed, rank), counter (slot, kind, ctr, sub); or injected raw draws (tests).
-__device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-
-__device__ inline uint64_t philox_u64(uint64_t seed, uint32_t rank, uint32_t slot, uint32_t kind, uint32_t ctr, uint32_t sub) {
-    uint32_t c0 = slot, c1 = kind | (sub << 8), c2 = ctr, c3 = rank;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return ((uint64_t)c0 << 32) | c1;
-}
 
 // raw 64-bit draw number `ctr` (0-based) of stream `kind` of this slot
 __device__ inline uint64_t draw_u64(const Dev &E, int slot, int kind, int ctr, unsigned long long *st) {
@@ -1642,504 +1502,6 @@ __global__ __launch_bounds__(64) void k_expand_multi(Dev E, Mx X, const float *_
     }
 }
 
-__global__ void k_init(Dev E) {
-    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= E.cfg.n_games) return;
-    int32_t *gi = E.gi + (size_t)slot * GI_N;
-    for (int i = 0; i < GI_N; ++i) gi[i] = 0;
-    gi[GI_PHASE] = E.cfg.manual_moves == 1 ? PH_HOLD : PH_NEWGAME;
-    gi[GI_SIDE] = 1;
-    if (E.cfg.start_stagger && E.cfg.manual_moves == 0)
-        gi[GI_DELAY] = (int)(philox_u64(E.cfg.seed, (uint32_t)E.cfg.rank, (uint32_t)slot, 7u, 0u, 0u) % (uint64_t)(E.cfg.num_simulations + 1));
-    unsigned long long *st = E.stats + (size_t)slot * ST_N;
-    for (int i = 0; i < ST_N; ++i) st[i] = 0;
-    if (slot == 0) { E.cnt[0] = 0; E.cnt[1] = 0; *E.started = 0; }
-}
-
-// xq_engine_init_cap: the playout cap's parameters, after k_init, in free state words of every slot (the handle and the config
-// struct are full): S_fast and the float64 threshold p as two words.  The kernels read them with their other scalar loads.
-__global__ void k_init_cap(Dev E, int fast_simulations, double full_search_prob) {
-    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= E.cfg.n_games) return;
-    int32_t *gi = E.gi + (size_t)slot * GI_N;
-    const unsigned long long pb = (unsigned long long)__double_as_longlong(full_search_prob);
-    gi[GI_CAP_FULL] = 1; gi[GI_CAP_BUDGET] = E.cfg.num_simulations;
-    gi[GI_CAP_SFAST] = fast_simulations; gi[GI_CAP_PLO] = (int32_t)(uint32_t)pb; gi[GI_CAP_PHI] = (int32_t)(uint32_t)(pb >> 32);
-}
-
-// xq_engine_init_fp: the forced-playout parameter k, rounded to float32 by the host, in the last free state word of every slot.
-__global__ void k_init_fp(Dev E, float k) {
-    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= E.cfg.n_games) return;
-    E.gi[(size_t)slot * GI_N + GI_FP_K] = __float_as_int(k);
-}
-
-// Column sums of the per-slot counters [G][ST_N] (OR for the overflow word): each 256-thread block sweeps slot rows
-// (8 rows x 32 columns per pass, 256 contiguous bytes per row), folds its eight partial rows through LDS and adds the
-// result to the zeroed output with one atomic per column.
-__global__ __launch_bounds__(256) void k_reduce_stats(Dev E, unsigned long long *out) {
-    __shared__ unsigned long long part[8][ST_N];
-    const int col = threadIdx.x & (ST_N - 1), row = threadIdx.x >> 5;
-    unsigned long long acc = 0;
-    for (int s = blockIdx.x * 8 + row; s < E.cfg.n_games; s += gridDim.x * 8) {
-        const unsigned long long v = E.stats[(size_t)s * ST_N + col];
-        acc = (col == ST_OVF) ? (acc | v) : (acc + v);
-    }
-    part[row][col] = acc;
-    __syncthreads();
-    if (row == 0) {
-#pragma unroll
-        for (int r = 1; r < 8; ++r) acc = (col == ST_OVF) ? (acc | part[r][col]) : (acc + part[r][col]);
-        if (col == ST_OVF) atomicOr(&out[col], acc); else atomicAdd(&out[col], acc);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Packed step (xq_engine_compact / xq_engine_expand_packed): the evaluator sees only the slots that asked for an
-// evaluation, packed to the front of engine-owned buffers in slot order.  The predicate is k_expand's own (phase
-// WAIT_ROOT / WAIT_LEAF after select), so the two kernels cannot disagree about which slots need output.
-
-// waiting for an evaluation: k_expand's own predicate
-__device__ __forceinline__ bool slot_waits(const Dev &E, int slot) {
-    const int ph = E.gi[(size_t)slot * GI_N + GI_PHASE];
-    return ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF;
-}
-
-// Stable compaction by ONE workgroup of the rows r < R with live(r), for any R: thread t owns the contiguous rows
-// [t K, t K + K), K = ceil(R / 1024); it counts its live rows, a block-wide exclusive scan of the counts gives its first packed
-// row, and it writes rows[] in row order.  R = 8192: eight strided 4-byte reads per thread, a few microseconds.
-constexpr int CPT = 1024;
-template <class Live>
-__device__ __forceinline__ void block_compact(const Dev &E, int R, Live live, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
-    __shared__ int wsum[CPT / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int K = (R + CPT - 1) / CPT;
-    const int r0 = t * K, r1 = min(r0 + K, R);
-    int cnt = 0;
-    for (int r = r0; r < r1; ++r) cnt += live(r);
-    int inc = cnt;                                    // inclusive scan within the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(inc, off);
-        if (lane >= off) inc += v;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < CPT / 64; ++w) {
-        const int v = wsum[w];
-        base += w < wave ? v : 0;
-        total += v;
-    }
-    int o = base + inc - cnt;
-    for (int r = r0; r < r1; ++r)
-        if (live(r)) rows[o++] = r;
-    if (t == 0) {
-        *n_live = total;
-        E.stats[ST_ROWS] += (unsigned long long)total;   // slot 0's counter row: k_reduce_stats sums the column
-    }
-}
-
-__global__ __launch_bounds__(CPT) void k_compact(Dev E, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
-    block_compact(E, E.cfg.n_games, [&](int s) { return slot_waits(E, s); }, n_live, rows);
-}
-
-// Gather of the packed rows: one workgroup per row of the capacity, rows past *n_live exit.  Per row the 5 400-byte
-// planes (8-byte aligned: float2), the 256-byte ordered move list and its count.
-__global__ __launch_bounds__(256) void k_gather_rows(Dev E, const int32_t *__restrict__ n_live, const int32_t *__restrict__ rows,
-                                                     const float *__restrict__ nn_in, float *__restrict__ x, uint16_t *__restrict__ moves,
-                                                     int32_t *__restrict__ counts) {
-    const int r = blockIdx.x;
-    if (r >= *n_live) return;
-    const int slot = rows[r], t = threadIdx.x;
-    const float2 *src = (const float2 *)(nn_in + (size_t)slot * XQ_STATE_FLOATS);
-    float2 *dst = (float2 *)(x + (size_t)r * XQ_STATE_FLOATS);
-    for (int i = t; i < XQ_STATE_FLOATS / 2; i += 256) dst[i] = src[i];
-    if (t < XQ_MAXM / 2)
-        ((uint32_t *)(moves + (size_t)r * XQ_MAXM))[t] = ((const uint32_t *)(E.pmoves + (size_t)slot * XQ_MAXM))[t];
-    if (t == 0) counts[r] = E.req[slot];
-}
-
-// Hand-back: packed row r's legal-move logits and value go to slot rows[r] of the slot-ordered buffers k_expand reads.
-// One wave per row (two floats per lane), four rows per workgroup.
-__global__ __launch_bounds__(256) void k_scatter_rows(const int32_t *__restrict__ n_live, const int32_t *__restrict__ rows,
-                                                      const float *__restrict__ logits, const float *__restrict__ value,
-                                                      float *__restrict__ slot_logits, float *__restrict__ slot_value, int G) {
-    const int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= G || r >= *n_live) return;
-    const int slot = rows[r];
-    ((float2 *)(slot_logits + (size_t)slot * XQ_MAXM))[lane] = ((const float2 *)(logits + (size_t)r * XQ_MAXM))[lane];
-    if (lane == 0) slot_value[slot] = value[r];
-}
-
-// Leaf batching (K > 1): k_compact over the G K request rows, slot-major.  Row slot K + j is live when the slot waits and
-// j < its request-row count (1 for a root, the pending leaves for a leaf step); rows[r] is then that ROW's index, so
-// k_gather_rows / k_scatter_rows serve it unchanged over the row-indexed request buffers.
-__global__ __launch_bounds__(CPT) void k_compact_multi(Dev E, int K, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
-    block_compact(E, E.cfg.n_games * K, [&](int r) { return slot_waits(E, r / K) && (r % K) < E.gi[(size_t)(r / K) * GI_N + GI_NPEND]; },
-                  n_live, rows);
-}
-
-// Per-model packed step of an arena-options engine (xq_engine_compact_arena): ONE pass of one workgroup compacts the waiting slots
-// twice, into set 0 (the slots the NEW model searches for) and set 1 (the OLD model's).  Slot s is the new model's iff
-// ((first_game + s) even) == (red is to move in the slot's real game).  Every waiting slot is in exactly one set.
-struct ArSets {
-    const ArHead *head;             // first_game is read on the device: the handle has no word left for it
-    int32_t *n_live;                // [2]
-    int32_t *rows[2];
-    float *x[2];
-    uint16_t *moves[2];
-    int32_t *counts[2];
-};
-
-__device__ __forceinline__ bool slot_is_new_models(const Dev &E, int first_game, int slot) {
-    return (((first_game + slot) & 1) == 0) == (E.gi[(size_t)slot * GI_N + GI_SIDE] == 1);
-}
-
-__global__ __launch_bounds__(CPT) void k_compact_arena(Dev E, ArSets A) {
-    const int first_game = A.head->first_game;
-    block_compact(E, E.cfg.n_games, [&](int s) { return slot_waits(E, s) && slot_is_new_models(E, first_game, s); }, A.n_live,
-                  A.rows[0]);
-    __syncthreads();                                  // block_compact's scan scratch is read by every thread before it is reused
-    block_compact(E, E.cfg.n_games, [&](int s) { return slot_waits(E, s) && !slot_is_new_models(E, first_game, s); }, A.n_live + 1,
-                  A.rows[1]);
-}
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// ---------------------------------------------------------------------------------------------------------
-// Evaluation cache (xq_evcache_*, opt-in): per slot K entries in W-way sets (W = min(4, K)) holding the legal-move logits and
-// value the network returned for a position.  A request's output depends only on its 15 input planes (board + side to move;
-// the ordered legal moves are a function of them) and each evaluator kernel's arithmetic for a row is independent of its
-// batch position, so a cached row is bit-identical to a recomputed one.  Private to a slot: no sharing, no atomics.
-//
-//   key   : 90 squares x 4 bits (1 + the plane 0..13 that holds the square's piece, 0 = empty) and the side to move (plane
-//           14) as nibble 90; nibble i sits at bits 4 (i mod 8) of word i / 8 -- 12 words, injective over k_select's planes.
-//   set   : a hash of the key picks the set; a hit needs all 12 key words, the current generation and the count to match.
-//   stamp : the slot's probe clock at insert / last hit; the victim is an entry of an older generation, else the oldest stamp
-//           (lowest way on ties).
-
-enum Ec : int { EC_GEN = 0, EC_CLOCK, EC_HIT, EC_SKEY, EC_STATS, EC_EGEN, EC_STAMP, EC_COUNT, EC_VALUE, EC_KEY, EC_LOGITS, EC_N };
-enum EcSt : int { ECS_PROBES = 0, ECS_HITS, ECS_INSERTS, ECS_EVICTIONS, ECS_MISMATCHES, ECS_N = 8 };
-constexpr int EC_KEYW = 12;
-
-struct EvDev {
-    int K, W, sets;
-    uint32_t *gen;                    // the current generation (device word: no host value is recorded into a graph)
-    uint32_t *clock;                  // [G] probes of the slot so far
-    int32_t *hit;                     // [G] 1: this step's request was answered by the cache
-    uint32_t *skey;                   // [G][12] the key probed this step (commit's input)
-    unsigned long long *stats;        // [G][ECS_N]
-    uint32_t *egen, *stamp;           // [G K]
-    int32_t *count;                   // [G K]
-    float *value;                     // [G K]
-    uint32_t *key;                    // [G K][12]
-    float *logits;                    // [G K][XQ_MAXM]
-};
-
-EvDev make_evdev(const xq_evcache *c) {
-    EvDev d;
-    d.K = c->entries; d.W = c->ways; d.sets = c->sets;
-    d.gen = (uint32_t *)c->p[EC_GEN]; d.clock = (uint32_t *)c->p[EC_CLOCK]; d.hit = (int32_t *)c->p[EC_HIT];
-    d.skey = (uint32_t *)c->p[EC_SKEY]; d.stats = (unsigned long long *)c->p[EC_STATS];
-    d.egen = (uint32_t *)c->p[EC_EGEN]; d.stamp = (uint32_t *)c->p[EC_STAMP]; d.count = (int32_t *)c->p[EC_COUNT];
-    d.value = (float *)c->p[EC_VALUE]; d.key = (uint32_t *)c->p[EC_KEY]; d.logits = (float *)c->p[EC_LOGITS];
-    return d;
-}
-
-// nibble of square sq (sq < 90): 1 + the piece plane that is set there, 0 when none is
-__host__ __device__ inline uint32_t evkey_nibble(const float *planes, int sq) {
-    uint32_t n = 0;
-    for (int p = 0; p < 14; ++p) n = planes[p * 90 + sq] != 0.0f ? (uint32_t)(p + 1) : n;
-    return n;
-}
-
-__host__ __device__ inline uint32_t evkey_side(const float *planes) { return planes[14 * 90] != 0.0f ? 1u : 0u; }
-
-__host__ __device__ inline uint32_t evkey_hash(const uint32_t *k) {
-    uint32_t h = 0x811C9DC5u;
-    for (int i = 0; i < EC_KEYW; ++i) h = (h ^ k[i]) * 0x01000193u;
-    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15;
-    return h;
-}
-
-// the 12 key words of one slot's planes, built by one wave: lane l decodes squares l and 64 + l (or the side at 90), groups
-// of eight lanes OR their shifted nibbles into one word, and every lane receives all 12 words
-__device__ inline void wave_evkey(const float *__restrict__ x, uint32_t key[EC_KEYW]) {
-    const int lane = lane_id(), sq1 = 64 + lane;
-    uint32_t lo = evkey_nibble(x, lane) << (4 * (lane & 7));
-    const uint32_t n1 = sq1 < 90 ? evkey_nibble(x, sq1) : (sq1 == 90 ? evkey_side(x) : 0u);
-    uint32_t hi = n1 << (4 * (lane & 7));
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        lo |= (uint32_t)__shfl_xor((int)lo, o);
-        hi |= (uint32_t)__shfl_xor((int)hi, o);
-    }
-#pragma unroll
-    for (int w = 0; w < 8; ++w) key[w] = (uint32_t)__shfl((int)lo, 8 * w);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) key[8 + w] = (uint32_t)__shfl((int)hi, 8 * w);
-}
-
-__device__ __forceinline__ bool key_eq(const uint32_t *__restrict__ e, const uint32_t key[EC_KEYW]) {
-    const uint4 a = ((const uint4 *)e)[0], b = ((const uint4 *)e)[1], c = ((const uint4 *)e)[2];
-    return a.x == key[0] && a.y == key[1] && a.z == key[2] && a.w == key[3] && b.x == key[4] && b.y == key[5] &&
-           b.z == key[6] && b.w == key[7] && c.x == key[8] && c.y == key[9] && c.z == key[10] && c.w == key[11];
-}
-
-// Probe: one wave per slot, four per workgroup; slots that are not waiting exit.  Lane w < W tests way w of the key's set.
-// A hit writes the entry's logits / value into the slot-ordered hand-back rows k_expand reads (as k_scatter_rows does for
-// evaluated rows) and refreshes its stamp; every probe records its key for k_evcache_commit.
-__global__ __launch_bounds__(256) void k_evcache_probe(Dev E, EvDev C, const float *__restrict__ nn_in,
-                                                       float *__restrict__ slot_logits, float *__restrict__ slot_value) {
-    const int slot = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (slot >= E.cfg.n_games) return;
-    const int ph = E.gi[(size_t)slot * GI_N + GI_PHASE];
-    if (ph != PH_WAIT_ROOT && ph != PH_WAIT_LEAF) return;
-    uint32_t key[EC_KEYW];
-    wave_evkey(nn_in + (size_t)slot * XQ_STATE_FLOATS, key);
-    const int count = E.req[slot];
-    const uint32_t gen = *C.gen, clock = C.clock[slot] + 1u;
-    const size_t e0 = (size_t)slot * C.K + (size_t)(evkey_hash(key) & (uint32_t)(C.sets - 1)) * C.W;
-    bool kmatch = false, same = false;
-    if (lane < C.W) {
-        const size_t e = e0 + lane;
-        kmatch = C.egen[e] == gen && key_eq(C.key + e * EC_KEYW, key);
-        same = kmatch && C.count[e] == count;
-    }
-    const unsigned long long km = __ballot(kmatch), sm = __ballot(same);
-    const int way = sm ? __ffsll((long long)sm) - 1 : -1;
-    if (way >= 0) {
-        const size_t e = e0 + way;
-        ((float2 *)(slot_logits + (size_t)slot * XQ_MAXM))[lane] = ((const float2 *)(C.logits + e * XQ_MAXM))[lane];
-        if (lane == 0) { slot_value[slot] = C.value[e]; C.stamp[e] = clock; }
-    }
-    if (lane == 0) {
-        uint4 *sk = (uint4 *)(C.skey + (size_t)slot * EC_KEYW);
-        sk[0] = make_uint4(key[0], key[1], key[2], key[3]);
-        sk[1] = make_uint4(key[4], key[5], key[6], key[7]);
-        sk[2] = make_uint4(key[8], key[9], key[10], key[11]);
-        C.hit[slot] = way >= 0 ? 1 : 0;
-        C.clock[slot] = clock;
-        unsigned long long *st = C.stats + (size_t)slot * ECS_N;
-        st[ECS_PROBES] += 1;
-        st[ECS_HITS] += way >= 0 ? 1 : 0;
-        st[ECS_MISMATCHES] += (way < 0 && km) ? 1 : 0;     // key and generation match, count differs: never expected
-    }
-}
-
-// Stable compaction of the misses (xq_engine_compact_misses): k_compact with the predicate "waiting and not a hit".
-__global__ __launch_bounds__(CPT) void k_compact_misses(Dev E, const int32_t *__restrict__ hit, int32_t *__restrict__ n_live,
-                                                        int32_t *__restrict__ rows) {
-    block_compact(E, E.cfg.n_games, [&](int s) { return slot_waits(E, s) && hit[s] == 0; }, n_live, rows);
-}
-
-// Commit: one wave per evaluated (packed) row r < n_live; the row's slot inserts the key it probed with this step.  One
-// insert per slot and step, so the victim choice is deterministic without atomics.
-__global__ __launch_bounds__(256) void k_evcache_commit(EvDev C, int G, const int32_t *__restrict__ n_live,
-                                                        const int32_t *__restrict__ rows, const int32_t *__restrict__ counts,
-                                                        const float *__restrict__ logits, const float *__restrict__ value) {
-    const int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= G || r >= *n_live) return;
-    const int slot = rows[r];
-    const uint4 *sk = (const uint4 *)(C.skey + (size_t)slot * EC_KEYW);
-    const uint4 k0 = sk[0], k1 = sk[1], k2 = sk[2];
-    const uint32_t key[EC_KEYW] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w, k2.x, k2.y, k2.z, k2.w};
-    const uint32_t gen = *C.gen, clock = C.clock[slot];
-    const size_t e0 = (size_t)slot * C.K + (size_t)(evkey_hash(key) & (uint32_t)(C.sets - 1)) * C.W;
-    int victim = 0;
-    bool evict = true;
-    uint32_t oldest = 0xFFFFFFFFu;
-    for (int w = 0; w < C.W; ++w) {
-        const size_t e = e0 + w;
-        if (C.egen[e] != gen) { victim = w; evict = false; break; }
-        const uint32_t st = C.stamp[e];
-        if (st < oldest) { oldest = st; victim = w; }
-    }
-    const size_t e = e0 + victim;
-    ((float2 *)(C.logits + e * XQ_MAXM))[lane] = ((const float2 *)(logits + (size_t)r * XQ_MAXM))[lane];
-    if (lane == 0) {
-        uint4 *ek = (uint4 *)(C.key + e * EC_KEYW);
-        ek[0] = k0; ek[1] = k1; ek[2] = k2;
-        C.value[e] = value[r];
-        C.count[e] = counts[r];
-        C.egen[e] = gen;
-        C.stamp[e] = clock;
-        unsigned long long *st = C.stats + (size_t)slot * ECS_N;
-        st[ECS_INSERTS] += 1;
-        st[ECS_EVICTIONS] += evict ? 1 : 0;
-    }
-}
-
-// Invalidation: a new generation; entries of older ones never hit and are the first victims.
-__global__ void k_evcache_invalidate(uint32_t *gen) {
-    if (threadIdx.x == 0) *gen += 1u;
-}
-
-struct EcLayout {
-    size_t off[EC_N];
-    size_t total;
-};
-
-bool evcache_args_ok(long long n_slots, long long k) { return n_slots > 0 && k > 0 && (k & (k - 1)) == 0 && k <= (1 << 20); }
-
-EcLayout make_ec_layout(size_t G, size_t K) {
-    EcLayout l;
-    memset(&l, 0, sizeof(l));
-    const size_t GK = G * K;
-    size_t o = 0;
-    auto put = [&](int id, size_t bytes) { l.off[id] = o; o = align_up(o + bytes); };
-    put(EC_GEN, 4);
-    put(EC_CLOCK, G * 4);
-    put(EC_HIT, G * 4);
-    put(EC_SKEY, G * EC_KEYW * 4);
-    put(EC_STATS, G * ECS_N * 8);
-    put(EC_EGEN, GK * 4);            // everything up to here is zeroed by xq_evcache_init
-    put(EC_STAMP, GK * 4);
-    put(EC_COUNT, GK * 4);
-    put(EC_VALUE, GK * 4);
-    put(EC_KEY, GK * EC_KEYW * 4);
-    put(EC_LOGITS, GK * XQ_MAXM * 4);
-    l.total = o;
-    return l;
-}
-
-bool evcache_ok(const xq_evcache *c) {
-    return c && evcache_args_ok(c->n_slots, c->entries) && c->ways > 0 && c->sets > 0 && c->ways * c->sets == c->entries &&
-           c->p[EC_GEN] && c->p[EC_LOGITS];
-}
-
-
-struct Layout {
-    size_t off[32];
-    size_t total;
-    int node_cap, path_cap, stage_cap;
-};
-
-// K > 1 (leaf batching): the request rows (moves, counts, paths, packed buffers) are G K, slot-major; the virtual-loss
-// counters and the pending-leaf records follow the K = 1 layout, which is unchanged.  gz_m > 0 (Gumbel root search, K = 1): the
-// square-root table's region also holds the Gumbel words (gz_bytes); every other engine has the layout it had.
-// arena (arena options, K = 1, never Gumbel): that region holds the arena words instead (ar_off).
-Layout make_layout(const xq_engine_config *c, int K = 1, int gz_m = 0, bool arena = false) {
-    Layout l;
-    memset(&l, 0, sizeof(l));
-    const size_t G = (size_t)c->n_games, S = (size_t)c->num_simulations, GK = G * (size_t)K;
-    l.node_cap = (int)(1 + (S + 1) * XQ_MAXM);
-    l.path_cap = (int)(S + 2);
-    int sc = c->max_game_length < 200 ? c->max_game_length : 200;
-    if (sc < 1) sc = 1;
-    l.stage_cap = c->manual_moves ? 1 : sc + 1;
-    size_t o = 0;
-    auto put = [&](int id, size_t bytes) { l.off[id] = o; o = align_up(o + bytes); };
-    put(P_BOARD, G * XQ_BS);
-    put(P_HIST, G * XQ_HIST * XQ_BS);
-    put(P_GI, G * GI_N * 4);
-    put(P_RESIGN, G * 16 * 8);
-    put(P_PMOVES, GK * XQ_MAXM * 2);
-    put(P_PATH, GK * (size_t)l.path_cap * 4);
-    put(P_TN, G * (size_t)l.node_cap * 4);
-    put(P_TW, G * (size_t)l.node_cap * 8);
-    put(P_TP, G * (size_t)l.node_cap * 4);
-    put(P_TA, G * (size_t)l.node_cap * 2);
-    put(P_TC, G * (size_t)l.node_cap * 4);
-    put(P_TM, G * (size_t)l.node_cap * 2);
-    put(P_ROOTP, G * XQ_MAXM * 8);
-    put(P_STAGE, G * (size_t)l.stage_cap * XQ_SAMPLE_BYTES);
-    put(P_OUTS, (size_t)(c->max_out_samples > 0 ? c->max_out_samples : 1) * XQ_SAMPLE_BYTES);
-    put(P_OUTR, (size_t)(c->max_out_results > 0 ? c->max_out_results : 1) * XQ_RESULT_BYTES);
-    put(P_CNT, 64);
-    put(P_STATS, G * ST_N * 8);
-    put(P_SQRT, arena ? ar_off(G, S).end : (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0));
-    put(P_MNOISE, G * XQ_MAXM * 8);
-    put(P_STATSUM, ST_N * 8);
-    put(P_REQ, GK * 4);
-    put(P_PK_N, 4);
-    put(P_PK_ROWS, GK * 4);
-    put(P_PK_X, GK * XQ_STATE_FLOATS * 4);
-    put(P_PK_MOVES, GK * XQ_MAXM * 2);
-    put(P_PK_COUNTS, GK * 4);
-    put(P_PK_LOGITS, GK * XQ_MAXM * 4);
-    put(P_PK_VALUE, GK * 4);
-    if (K > 1) {
-        put(P_VL, G * (size_t)l.node_cap * 4);
-        put(P_LEAF, GK * 4 * 4);
-    }
-    l.total = o;
-    return l;
-}
-
-bool config_ok(const xq_engine_config *c) {
-    return c && c->n_games > 0 && c->num_simulations > 0 && c->num_simulations < 16000 && c->resign_check_steps >= 1 &&
-           c->resign_check_steps <= 16 && c->random_opening_moves >= 0 && c->late_temperature > 0.0 && c->inject_len >= 0;
-}
-
-bool leaves_ok(const xq_engine_config *c, int K) { return K >= 1 && K <= 64 && !(K > 1 && c->manual_moves == 2); }
-
-// tree reuse: self-play only, one leaf per step, S within k_reroot's LDS (64 KiB at S = XQ_REUSE_MAX_SIMS)
-bool flags_ok(const xq_engine_config *c, int K, unsigned flags) {
-    if (flags & ~(unsigned)XQ_ENGINE_TREE_REUSE) return false;
-    if (!(flags & XQ_ENGINE_TREE_REUSE)) return true;
-    return c->manual_moves == 0 && K == 1 && c->num_simulations <= XQ_REUSE_MAX_SIMS;
-}
-
-// playout cap: self-play only, one leaf per step, 1 <= S_fast < S, 0 < p <= 1 (a NaN fails both comparisons)
-bool cap_ok(const xq_engine_config *c, int K, const xq_playout_cap *cap) {
-    return c->manual_moves == 0 && K == 1 && cap->reserved == 0 && cap->fast_simulations >= 1 &&
-           cap->fast_simulations < c->num_simulations && cap->full_search_prob > 0.0 && cap->full_search_prob <= 1.0;
-}
-
-// forced playouts: self-play with root noise only, one leaf per step, 0 < k <= 16 (a NaN fails both comparisons)
-bool forced_ok(const xq_engine_config *c, int K, const xq_forced_playouts *fp) {
-    if (c->manual_moves != 0 || c->add_noise == 0 || K != 1) return false;
-    for (uint32_t r : fp->reserved) if (r != 0) return false;
-    return fp->k > 0.0 && fp->k <= 16.0;
-}
-
-// Gumbel root search: self-play or search only, one leaf per step, none of tree reuse, playout cap and forced playouts;
-// 1 <= m <= XQ_MAXM, c_visit >= 0 and c_scale > 0, finite as the float32 values the kernels use (a NaN fails the comparisons)
-bool gumbel_ok(const xq_engine_config *c, int K, unsigned flags, const xq_playout_cap *cap, const xq_forced_playouts *forced,
-               const xq_gumbel *gz) {
-    if (c->manual_moves == 2 || K != 1 || (flags & XQ_ENGINE_TREE_REUSE) || cap || forced || gz->reserved != 0) return false;
-    if (!(gz->c_visit >= 0.0 && gz->c_visit <= (double)FLT_MAX && gz->c_scale > 0.0 && gz->c_scale <= (double)FLT_MAX)) return false;
-    return gz->considered >= 1 && gz->considered <= XQ_MAXM && (float)gz->c_scale > 0.0f;
-}
-
-// arena options: arena games only (so K = 1 and none of tree reuse, playout cap, forced playouts, Gumbel: each refuses
-// manual_moves = 2 itself), 0 <= opening_plies <= XQ_ARENA_MAX_OPENING, first_game >= 0 with first_game + n_games an int32
-bool arena_ok(const xq_engine_config *c, const xq_arena_opts *ar) {
-    if (c->manual_moves != 2 || ar->reserved[0] != 0 || ar->reserved[1] != 0) return false;
-    if (ar->opening_plies < 0 || ar->opening_plies > XQ_ARENA_MAX_OPENING) return false;
-    return ar->first_game >= 0 && ar->first_game <= 0x7FFFFFFF - c->n_games;
-}
-
-// pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
-// flag bits "playout cap on" (xq_engine_init_cap), "forced playouts on" (xq_engine_init_fp) and "Gumbel root search on"
-// (xq_engine_init_gz) and "arena options on" (xq_engine_init_ar)
-constexpr int PAD0_CAP = 1 << 30;
-constexpr int PAD0_FORCED = 1 << 29;
-constexpr int PAD0_GUMBEL = 1 << 28;
-constexpr int PAD0_ARENA = 1 << 27;
-int leaves_of(const xq_engine *e) { return (e->pad0 & 0xFFFF) > 1 ? (e->pad0 & 0xFFFF) : 1; }
-bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE_TREE_REUSE; }
-bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
-bool forced_of(const xq_engine *e) { return (e->pad0 & PAD0_FORCED) != 0; }
-bool gumbel_of(const xq_engine *e) { return (e->pad0 & PAD0_GUMBEL) != 0; }
-bool arena_of(const xq_engine *e) { return e && (e->pad0 & PAD0_ARENA) != 0 && e->cfg.n_games > 0 && e->p[P_SQRT]; }
-
-ArSets make_ar_sets(const xq_engine *e) {
-    const ArOff o = ar_off((size_t)e->cfg.n_games, (size_t)e->cfg.num_simulations);
-    char *base = (char *)e->p[P_SQRT];
-    ArSets a;
-    a.head = (const ArHead *)(base + o.head);
-    a.n_live = (int32_t *)(base + o.n_live);
-    for (int m = 0; m < 2; ++m) {
-        a.rows[m] = (int32_t *)(base + o.rows[m]); a.x[m] = (float *)(base + o.x[m]);
-        a.moves[m] = (uint16_t *)(base + o.moves[m]); a.counts[m] = (int32_t *)(base + o.counts[m]);
-    }
-    return a;
-}
-
 // the K = 1 step's two kernels, by the engine's options: instance [FORCED][CAP][REUSE]; a Gumbel engine has none of the three
 // and its own instance of each kernel
 void launch_select(const xq_engine *eng, const Dev &d, float *nn_in, hipStream_t s) {
@@ -2179,157 +1541,6 @@ Mx make_mx(const xq_engine *e) {
 }  // namespace
 
 extern "C" {
-
-size_t xq_engine_workspace_bytes(const xq_engine_config *cfg) {
-    if (!config_ok(cfg)) return 0;
-    return make_layout(cfg).total;
-}
-
-size_t xq_engine_workspace_bytes_leaves(const xq_engine_config *cfg, int leaves_per_step) {
-    return xq_engine_workspace_bytes_ex(cfg, leaves_per_step, 0u);
-}
-
-size_t xq_engine_workspace_bytes_ex(const xq_engine_config *cfg, int leaves_per_step, unsigned flags) {
-    return xq_engine_workspace_bytes_cap(cfg, leaves_per_step, flags, nullptr);
-}
-
-size_t xq_engine_workspace_bytes_cap(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap) {
-    return xq_engine_workspace_bytes_fp(cfg, leaves_per_step, flags, cap, nullptr);
-}
-
-size_t xq_engine_workspace_bytes_fp(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
-                                    const xq_forced_playouts *forced) {
-    if (!config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags)) return 0;
-    if (cap && !cap_ok(cfg, leaves_per_step, cap)) return 0;
-    if (forced && !forced_ok(cfg, leaves_per_step, forced)) return 0;
-    return make_layout(cfg, leaves_per_step).total;   // tree reuse, the playout cap and forced playouts need no workspace of their own
-}
-
-size_t xq_engine_workspace_bytes_gz(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
-                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel) {
-    if (!gumbel) return xq_engine_workspace_bytes_fp(cfg, leaves_per_step, flags, cap, forced);
-    if (!config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags)) return 0;
-    if (!gumbel_ok(cfg, leaves_per_step, flags, cap, forced, gumbel)) return 0;
-    return make_layout(cfg, 1, gumbel->considered).total;
-}
-
-size_t xq_engine_workspace_bytes_ar(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
-                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena) {
-    const size_t plain = xq_engine_workspace_bytes_gz(cfg, leaves_per_step, flags, cap, forced, gumbel);
-    if (!arena || plain == 0) return plain;
-    if (!arena_ok(cfg, arena)) return 0;
-    return make_layout(cfg, 1, 0, true).total;
-}
-
-int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out) {
-    if (k < 1 || k > XQ_MAXM || num_simulations < 1 || num_simulations > 65535 || !host_out) return XQ_ERR_ARG;
-    gz_considered_visits(k, num_simulations, host_out);
-    return XQ_OK;
-}
-
-int xq_engine_init(xq_engine *eng, const xq_engine_config *cfg, void *ws, size_t ws_bytes, const uint64_t *dev_inject,
-                   void *stream) {
-    return xq_engine_init_ex(eng, cfg, 1, 0u, ws, ws_bytes, dev_inject, stream);
-}
-
-int xq_engine_init_leaves(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, void *ws, size_t ws_bytes,
-                          const uint64_t *dev_inject, void *stream) {
-    return xq_engine_init_ex(eng, cfg, leaves_per_step, 0u, ws, ws_bytes, dev_inject, stream);
-}
-
-int xq_engine_init_ex(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, void *ws,
-                      size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
-    return xq_engine_init_cap(eng, cfg, leaves_per_step, flags, nullptr, ws, ws_bytes, dev_inject, stream);
-}
-
-int xq_engine_init_cap(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
-                       void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
-    return xq_engine_init_fp(eng, cfg, leaves_per_step, flags, cap, nullptr, ws, ws_bytes, dev_inject, stream);
-}
-
-int xq_engine_init_fp(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
-                      const xq_forced_playouts *forced, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
-    return xq_engine_init_gz(eng, cfg, leaves_per_step, flags, cap, forced, nullptr, ws, ws_bytes, dev_inject, stream);
-}
-
-int xq_engine_init_gz(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
-                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, void *ws, size_t ws_bytes,
-                      const uint64_t *dev_inject, void *stream) {
-    return xq_engine_init_ar(eng, cfg, leaves_per_step, flags, cap, forced, gumbel, nullptr, ws, ws_bytes, dev_inject, stream);
-}
-
-int xq_engine_init_ar(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
-                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena, void *ws,
-                      size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
-    if (!eng || !config_ok(cfg) || !leaves_ok(cfg, leaves_per_step) || !flags_ok(cfg, leaves_per_step, flags) || !ws ||
-        ((uintptr_t)ws & 255))
-        return XQ_ERR_ARG;
-    if (cap && !cap_ok(cfg, leaves_per_step, cap)) return XQ_ERR_ARG;
-    if (forced && !forced_ok(cfg, leaves_per_step, forced)) return XQ_ERR_ARG;
-    if (gumbel && !gumbel_ok(cfg, leaves_per_step, flags, cap, forced, gumbel)) return XQ_ERR_ARG;
-    if (arena && !arena_ok(cfg, arena)) return XQ_ERR_ARG;
-    if (cfg->inject_len > 0 && !dev_inject) return XQ_ERR_ARG;
-    const int K = leaves_per_step;
-    const Layout l = make_layout(cfg, K, gumbel ? gumbel->considered : 0, arena != nullptr);
-    if (ws_bytes < l.total) return XQ_ERR_WORKSPACE;
-    memset(eng, 0, sizeof(*eng));
-    eng->cfg = *cfg;
-    eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
-    eng->pad0 = (K > 1 ? K : 0) | (int)(flags << 16) | (cap ? PAD0_CAP : 0) | (forced ? PAD0_FORCED : 0) | (gumbel ? PAD0_GUMBEL : 0) |
-                (arena ? PAD0_ARENA : 0);
-    for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
-    eng->p[P_INJECT] = (void *)dev_inject;
-    hipStream_t s = (hipStream_t)stream;
-    // small state is zeroed; tree arenas need no clearing (nodes are initialised when created)
-    XQ_TRY(hipMemsetAsync(eng->p[P_BOARD], 0, l.off[P_PATH] - l.off[P_BOARD], s));
-    XQ_TRY(hipMemsetAsync(eng->p[P_ROOTP], 0, (size_t)cfg->n_games * XQ_MAXM * 8, s));
-    XQ_TRY(hipMemsetAsync(eng->p[P_MNOISE], 0, (size_t)cfg->n_games * XQ_MAXM * 8, s));
-    XQ_TRY(hipMemsetAsync(eng->p[P_REQ], 0, (size_t)cfg->n_games * K * 4, s));
-    // packed-step buffers: zero count, rows, requests, hand-back (the packed planes are written before they are read);
-    // with K > 1 the virtual-loss counters and pending-leaf records behind them as well
-    XQ_TRY(hipMemsetAsync(eng->p[P_PK_N], 0, l.off[P_PK_X] - l.off[P_PK_N], s));
-    XQ_TRY(hipMemsetAsync(eng->p[P_PK_MOVES], 0, l.total - l.off[P_PK_MOVES], s));
-    {
-        const int n = cfg->num_simulations + 2 + (K > 1 ? K : 0);   // K > 1: N_parent + vl_parent < S + K
-        // Gumbel root search: the parameters, a zeroed v_hat per slot and the considered-visit tables for k = 1 .. m follow the table
-        const size_t S = (size_t)cfg->num_simulations, G = (size_t)cfg->n_games;
-        // arena options: the whole region zeroed (openings record, both sets' counts and rows), then the table and the parameters
-        const ArOff ao = ar_off(G, S);
-        if (arena) XQ_TRY(hipMemsetAsync(eng->p[P_SQRT], 0, ao.end, s));
-        const size_t bytes = arena ? ao.head + sizeof(ArHead) : sizeof(double) * n + (gumbel ? gz_bytes(G, S, (size_t)gumbel->considered) : 0);
-        double *tab = (double *)calloc(bytes, 1);
-        if (!tab) return XQ_ERR_ARG;
-        for (int i = 0; i < n; ++i) tab[i] = sqrt((double)i);   // math.sqrt(visit_count), mcts.py:49
-        if (gumbel) {
-            GzHead *h = (GzHead *)(tab + n);
-            h->m = gumbel->considered; h->c_visit = (float)gumbel->c_visit; h->c_scale = (float)gumbel->c_scale;
-            uint16_t *vis = (uint16_t *)((char *)(h + 1) + G * 8);
-            for (int k = 1; k <= gumbel->considered; ++k) gz_considered_visits(k, (int)S, vis + (size_t)(k - 1) * S);
-        }
-        if (arena) {
-            ArHead *h = (ArHead *)((char *)tab + ao.head);
-            h->opening_plies = arena->opening_plies; h->first_game = arena->first_game;
-        }
-        const int rc = xq::check(hipMemcpyAsync(eng->p[P_SQRT], tab, bytes, hipMemcpyHostToDevice, s));
-        if (rc == XQ_OK) (void)hipStreamSynchronize(s);
-        free(tab);
-        if (rc != XQ_OK) return rc;
-    }
-    const Dev d = make_dev(eng);
-    hipLaunchKernelGGL(k_init, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d);
-    if (cap) {
-        const int rc = launch_status();
-        if (rc != XQ_OK) return rc;
-        hipLaunchKernelGGL(k_init_cap, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d, (int)cap->fast_simulations,
-                           cap->full_search_prob);
-    }
-    if (forced) {
-        const int rc = launch_status();
-        if (rc != XQ_OK) return rc;
-        hipLaunchKernelGGL(k_init_fp, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d, (float)forced->k);
-    }
-    return launch_status();
-}
 
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input, void *stream) {
     if (!eng || !dev_nn_input) return XQ_ERR_ARG;
@@ -2385,323 +1596,6 @@ int xq_engine_expand_legal(const xq_engine *eng, const float *dev_legal_logits, 
     }
     launch_expand(eng, d, dev_legal_logits, dev_value, 2, (hipStream_t)stream);
     return launch_status();
-}
-
-int xq_engine_compact(const xq_engine *eng, const float *dev_nn_input, void *stream) {
-    if (!eng || !dev_nn_input || eng->cfg.n_games <= 0) return XQ_ERR_ARG;
-    const Dev d = make_dev(eng);
-    hipStream_t s = (hipStream_t)stream;
-    int32_t *n_live = (int32_t *)eng->p[P_PK_N], *rows = (int32_t *)eng->p[P_PK_ROWS];
-    const int K = leaves_of(eng);
-    if (K > 1) hipLaunchKernelGGL(k_compact_multi, dim3(1), dim3(CPT), 0, s, d, K, n_live, rows);
-    else hipLaunchKernelGGL(k_compact, dim3(1), dim3(CPT), 0, s, d, n_live, rows);
-    int rc = launch_status();
-    if (rc != XQ_OK) return rc;
-    hipLaunchKernelGGL(k_gather_rows, dim3(eng->cfg.n_games * K), dim3(256), 0, s, d, (const int32_t *)n_live, (const int32_t *)rows,
-                       dev_nn_input, (float *)eng->p[P_PK_X], (uint16_t *)eng->p[P_PK_MOVES], (int32_t *)eng->p[P_PK_COUNTS]);
-    return launch_status();
-}
-
-int xq_engine_packed(const xq_engine *eng, xq_engine_packed_buffers *out) {
-    if (!eng || !out) return XQ_ERR_ARG;
-    out->n_live = (const int32_t *)eng->p[P_PK_N];
-    out->rows = (const int32_t *)eng->p[P_PK_ROWS];
-    out->x = (const float *)eng->p[P_PK_X];
-    out->moves = (const uint16_t *)eng->p[P_PK_MOVES];
-    out->counts = (const int32_t *)eng->p[P_PK_COUNTS];
-    out->slot_logits = (const float *)eng->p[P_PK_LOGITS];
-    out->slot_value = (const float *)eng->p[P_PK_VALUE];
-    return XQ_OK;
-}
-
-int xq_engine_expand_packed(const xq_engine *eng, const float *dev_packed_logits, const float *dev_packed_value, void *stream) {
-    if (!eng || !dev_packed_logits || !dev_packed_value || eng->cfg.n_games <= 0) return XQ_ERR_ARG;
-    if (((uintptr_t)dev_packed_logits) & 7) return XQ_ERR_ARG;
-    const int G = eng->cfg.n_games * leaves_of(eng);   // request rows
-    float *slot_logits = (float *)eng->p[P_PK_LOGITS], *slot_value = (float *)eng->p[P_PK_VALUE];
-    hipLaunchKernelGGL(k_scatter_rows, dim3((G + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const int32_t *)eng->p[P_PK_N],
-                       (const int32_t *)eng->p[P_PK_ROWS], dev_packed_logits, dev_packed_value, slot_logits, slot_value, G);
-    const int rc = launch_status();
-    if (rc != XQ_OK) return rc;
-    return xq_engine_expand_legal(eng, slot_logits, slot_value, stream);
-}
-
-int xq_engine_arena_openings(const xq_engine *eng, const uint16_t **dev_actions, const int32_t **dev_counts) {
-    if (!arena_of(eng) || !dev_actions || !dev_counts) return XQ_ERR_ARG;
-    const ArOff o = ar_off((size_t)eng->cfg.n_games, (size_t)eng->cfg.num_simulations);
-    *dev_actions = (const uint16_t *)((char *)eng->p[P_SQRT] + o.op_actions);
-    *dev_counts = (const int32_t *)((char *)eng->p[P_SQRT] + o.op_counts);
-    return XQ_OK;
-}
-
-int xq_engine_compact_arena(const xq_engine *eng, const float *dev_nn_input, void *stream) {
-    if (!arena_of(eng) || !dev_nn_input) return XQ_ERR_ARG;
-    const Dev d = make_dev(eng);
-    const ArSets a = make_ar_sets(eng);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_compact_arena, dim3(1), dim3(CPT), 0, s, d, a);
-    for (int m = 0; m < 2; ++m) {
-        const int rc = launch_status();
-        if (rc != XQ_OK) return rc;
-        hipLaunchKernelGGL(k_gather_rows, dim3(eng->cfg.n_games), dim3(256), 0, s, d, (const int32_t *)(a.n_live + m),
-                           (const int32_t *)a.rows[m], dev_nn_input, a.x[m], a.moves[m], a.counts[m]);
-    }
-    return launch_status();
-}
-
-int xq_engine_packed_arena(const xq_engine *eng, xq_engine_packed_buffers out[2]) {
-    if (!arena_of(eng) || !out) return XQ_ERR_ARG;
-    const ArSets a = make_ar_sets(eng);
-    for (int m = 0; m < 2; ++m) {
-        out[m].n_live = a.n_live + m; out[m].rows = a.rows[m]; out[m].x = a.x[m]; out[m].moves = a.moves[m];
-        out[m].counts = a.counts[m];
-        out[m].slot_logits = (const float *)eng->p[P_PK_LOGITS]; out[m].slot_value = (const float *)eng->p[P_PK_VALUE];
-    }
-    return XQ_OK;
-}
-
-int xq_engine_expand_packed_arena(const xq_engine *eng, const float *dev_logits_new, const float *dev_value_new,
-                                  const float *dev_logits_old, const float *dev_value_old, void *stream) {
-    if (!arena_of(eng) || !dev_logits_new || !dev_value_new || !dev_logits_old || !dev_value_old) return XQ_ERR_ARG;
-    if ((((uintptr_t)dev_logits_new) | ((uintptr_t)dev_logits_old)) & 7) return XQ_ERR_ARG;
-    const int G = eng->cfg.n_games;
-    const ArSets a = make_ar_sets(eng);
-    float *slot_logits = (float *)eng->p[P_PK_LOGITS], *slot_value = (float *)eng->p[P_PK_VALUE];
-    const float *logits[2] = {dev_logits_new, dev_logits_old}, *value[2] = {dev_value_new, dev_value_old};
-    for (int m = 0; m < 2; ++m) {
-        hipLaunchKernelGGL(k_scatter_rows, dim3((G + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const int32_t *)(a.n_live + m),
-                           (const int32_t *)a.rows[m], logits[m], value[m], slot_logits, slot_value, G);
-        const int rc = launch_status();
-        if (rc != XQ_OK) return rc;
-    }
-    return xq_engine_expand_legal(eng, slot_logits, slot_value, stream);
-}
-
-int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *stream) {
-    if (!eng || !host_out) return XQ_ERR_ARG;
-    const Dev d = make_dev(eng);
-    hipStream_t s = (hipStream_t)stream;
-    unsigned long long *sum = (unsigned long long *)eng->p[P_STATSUM];
-    XQ_TRY(hipMemsetAsync(sum, 0, ST_N * sizeof(unsigned long long), s));
-    int blocks = (eng->cfg.n_games + 63) / 64;
-    if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(k_reduce_stats, dim3(blocks), dim3(256), 0, s, d, sum);
-    int rc = launch_status();
-    if (rc != XQ_OK) return rc;
-    unsigned long long h[ST_N];
-    XQ_TRY(hipMemcpyAsync(h, sum, sizeof(h), hipMemcpyDeviceToHost, s));
-    XQ_TRY(hipStreamSynchronize(s));
-    memset(host_out, 0, sizeof(*host_out));
-    host_out->sims = h[ST_SIMS]; host_out->terminal_sims = h[ST_TERM]; host_out->leaf_evals = h[ST_LEAF];
-    host_out->root_evals = h[ST_ROOT]; host_out->moves_played = h[ST_MOVES]; host_out->games_finished = h[ST_GAMES];
-    host_out->red_wins = h[ST_RED]; host_out->black_wins = h[ST_BLACK]; host_out->draws = h[ST_DRAW];
-    host_out->plies_finished = h[ST_PLIES]; host_out->nodes_created = h[ST_NODES]; host_out->depth_sum = h[ST_DEPTH];
-    host_out->children_scanned = h[ST_SCAN]; host_out->resigns = h[ST_RESIGN]; host_out->samples_written = h[ST_SAMP];
-    host_out->samples_dropped = h[ST_DROP]; host_out->overflow = h[ST_OVF]; host_out->games_started = h[ST_STARTED];
-    host_out->rows_evaluated = h[ST_ROWS];
-    host_out->reserved[XQ_STAT_COLLISIONS] = h[ST_COLL]; host_out->reserved[XQ_STAT_LEAVES_SUM] = h[ST_LPS];
-    host_out->reserved[XQ_STAT_LEAF_STEPS] = h[ST_LSTEPS];
-    host_out->reserved[XQ_STAT_REUSED_VISITS] = h[ST_REUSED]; host_out->reserved[XQ_STAT_REROOTS] = h[ST_REROOTS];
-    host_out->reserved[XQ_STAT_FAST_MOVES] = h[ST_FASTM]; host_out->reserved[XQ_STAT_FAST_SIMS] = h[ST_FASTS];
-    host_out->reserved[XQ_STAT_FORCED_SIMS] = h[ST_FORCED]; host_out->reserved[XQ_STAT_PRUNED_VISITS] = h[ST_PRUNEDV];
-    host_out->reserved[XQ_STAT_PRUNED_CHILDREN] = h[ST_PRUNEDC];
-    host_out->reserved[XQ_STAT_GUMBEL_MOVES] = h[ST_GZ_MOVES]; host_out->reserved[XQ_STAT_GUMBEL_CONSIDERED] = h[ST_GZ_CONS];
-    host_out->reserved[XQ_STAT_GUMBEL_OFFPRIOR] = h[ST_GZ_OFF];
-    return h[ST_OVF] ? XQ_ERR_OVERFLOW : XQ_OK;
-}
-
-int xq_engine_drain(const xq_engine *eng, void *host_samples, int max_samples, int *n_samples, void *host_results,
-                    int max_results, int *n_results, void *stream) {
-    if (!eng || !n_samples || !n_results) return XQ_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned cnt[2];
-    XQ_TRY(hipStreamSynchronize(s));
-    XQ_TRY(hipMemcpy(cnt, eng->p[P_CNT], sizeof(cnt), hipMemcpyDeviceToHost));
-    unsigned ns = cnt[0] < (unsigned)eng->cfg.max_out_samples ? cnt[0] : (unsigned)eng->cfg.max_out_samples;
-    unsigned nr = cnt[1] < (unsigned)eng->cfg.max_out_results ? cnt[1] : (unsigned)eng->cfg.max_out_results;
-    if ((int)ns > max_samples || (int)nr > max_results) {   // caller's buffers too small: report sizes, keep the data
-        *n_samples = (int)ns; *n_results = (int)nr;
-        return XQ_ERR_ARG;
-    }
-    if (ns && host_samples) XQ_TRY(hipMemcpy(host_samples, eng->p[P_OUTS], (size_t)ns * XQ_SAMPLE_BYTES, hipMemcpyDeviceToHost));
-    if (nr && host_results) XQ_TRY(hipMemcpy(host_results, eng->p[P_OUTR], (size_t)nr * XQ_RESULT_BYTES, hipMemcpyDeviceToHost));
-    XQ_TRY(hipMemset(eng->p[P_CNT], 0, 8));
-    *n_samples = (int)ns; *n_results = (int)nr;
-    return XQ_OK;
-}
-
-int xq_engine_drain_device(const xq_engine *eng, void *dev_samples, int max_samples, int *n_samples, void *dev_results,
-                           int max_results, int *n_results, void *stream) {
-    if (!eng || !n_samples || !n_results) return XQ_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned cnt[2];
-    XQ_TRY(hipStreamSynchronize(s));
-    XQ_TRY(hipMemcpy(cnt, eng->p[P_CNT], sizeof(cnt), hipMemcpyDeviceToHost));
-    const unsigned ns = cnt[0] < (unsigned)eng->cfg.max_out_samples ? cnt[0] : (unsigned)eng->cfg.max_out_samples;
-    const unsigned nr = cnt[1] < (unsigned)eng->cfg.max_out_results ? cnt[1] : (unsigned)eng->cfg.max_out_results;
-    *n_samples = (int)ns; *n_results = (int)nr;
-    if (!dev_samples && !dev_results) return XQ_OK;          // size query: nothing is consumed
-    if ((int)ns > max_samples || (int)nr > max_results || (ns && !dev_samples) || (nr && !dev_results)) return XQ_ERR_ARG;
-    if (ns) XQ_TRY(hipMemcpyAsync(dev_samples, eng->p[P_OUTS], (size_t)ns * XQ_SAMPLE_BYTES, hipMemcpyDeviceToDevice, s));
-    if (nr) XQ_TRY(hipMemcpyAsync(dev_results, eng->p[P_OUTR], (size_t)nr * XQ_RESULT_BYTES, hipMemcpyDeviceToDevice, s));
-    XQ_TRY(hipMemsetAsync(eng->p[P_CNT], 0, 8, s));
-    XQ_TRY(hipStreamSynchronize(s));
-    return XQ_OK;
-}
-
-int xq_engine_set_position(const xq_engine *eng, int slot, const int8_t *host_board, int side, int move_count,
-                           int no_capture, const int8_t *host_hist12, const double *host_noise, void *stream) {
-    if (!eng || !host_board || slot < 0 || slot >= eng->cfg.n_games || (side != 1 && side != -1) || move_count < 0)
-        return XQ_ERR_ARG;
-    XQ_TRY(hipStreamSynchronize((hipStream_t)stream));
-    int8_t b[XQ_BS];
-    memset(b, 0, sizeof(b));
-    memcpy(b, host_board, 90);
-    XQ_TRY(hipMemcpy((char *)eng->p[P_BOARD] + (size_t)slot * XQ_BS, b, XQ_BS, hipMemcpyHostToDevice));
-    int8_t ring[XQ_HIST][XQ_BS];
-    memset(ring, 0, sizeof(ring));
-    const int k = move_count < XQ_HIST ? move_count : XQ_HIST;
-    if (k > 0 && !host_hist12) return XQ_ERR_ARG;
-    for (int e = 0; e < k; ++e) {               // entry e (oldest first) is the pre-move board of ply mc-k+e
-        const int ply = move_count - k + e;
-        memcpy(ring[ply % XQ_HIST], host_hist12 + (size_t)e * 90, 90);
-    }
-    XQ_TRY(hipMemcpy((char *)eng->p[P_HIST] + (size_t)slot * XQ_HIST * XQ_BS, ring, sizeof(ring), hipMemcpyHostToDevice));
-    int32_t gi[GI_N];
-    memset(gi, 0, sizeof(gi));
-    gi[GI_SIDE] = side; gi[GI_MC] = move_count; gi[GI_NOCAP] = no_capture; gi[GI_PHASE] = PH_NEWPOS;
-    gi[GI_MANNOISE] = host_noise ? 1 : 0;
-    XQ_TRY(hipMemcpy((char *)eng->p[P_GI] + (size_t)slot * GI_N * 4, gi, sizeof(gi), hipMemcpyHostToDevice));
-    if (host_noise)
-        XQ_TRY(hipMemcpy((char *)eng->p[P_MNOISE] + (size_t)slot * XQ_MAXM * 8, host_noise, XQ_MAXM * 8, hipMemcpyHostToDevice));
-    return XQ_OK;
-}
-
-int xq_engine_read_root(const xq_engine *eng, int slot, uint16_t *actions, int32_t *visits, double *total_value,
-                        double *prior, int *prior_kind, int32_t *root_visits, int32_t *sims_done, void *stream) {
-    if (!eng || slot < 0 || slot >= eng->cfg.n_games || !actions || !visits || !total_value || !prior) return XQ_ERR_ARG;
-    XQ_TRY(hipStreamSynchronize((hipStream_t)stream));
-    const size_t nb = (size_t)slot * eng->node_cap;
-    uint16_t m; int32_t first, rn; int32_t gi[GI_N];
-    XQ_TRY(hipMemcpy(&m, (uint16_t *)eng->p[P_TM] + nb, 2, hipMemcpyDeviceToHost));
-    XQ_TRY(hipMemcpy(&first, (int32_t *)eng->p[P_TC] + nb, 4, hipMemcpyDeviceToHost));
-    XQ_TRY(hipMemcpy(&rn, (int32_t *)eng->p[P_TN] + nb, 4, hipMemcpyDeviceToHost));
-    XQ_TRY(hipMemcpy(gi, (char *)eng->p[P_GI] + (size_t)slot * GI_N * 4, sizeof(gi), hipMemcpyDeviceToHost));
-    const int n = m & 0x3FFF, kind = m >> 14;
-    if (root_visits) *root_visits = rn;
-    if (sims_done) *sims_done = gi[GI_SIMS];
-    if (prior_kind) *prior_kind = kind == 0 ? 0 : (kind == 3 ? 3 : 1);
-    if (n == 0) return 0;
-    float pf[XQ_MAXM];
-    XQ_TRY(hipMemcpy(actions, (uint16_t *)eng->p[P_TA] + nb + first, (size_t)n * 2, hipMemcpyDeviceToHost));
-    XQ_TRY(hipMemcpy(visits, (int32_t *)eng->p[P_TN] + nb + first, (size_t)n * 4, hipMemcpyDeviceToHost));
-    XQ_TRY(hipMemcpy(total_value, (double *)eng->p[P_TW] + nb + first, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (kind == 1 || kind == 3) {
-        XQ_TRY(hipMemcpy(prior, (double *)eng->p[P_ROOTP] + (size_t)slot * XQ_MAXM, (size_t)n * 8, hipMemcpyDeviceToHost));
-    } else if (kind == 2) {
-        for (int i = 0; i < n; ++i) prior[i] = 1.0 / (double)n;
-    } else {
-        XQ_TRY(hipMemcpy(pf, (float *)eng->p[P_TP] + nb + first, (size_t)n * 4, hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i) prior[i] = (double)pf[i];
-    }
-    return n;
-}
-
-
-// ---- evaluation cache --------------------------------------------------------------------------------------------------
-size_t xq_evcache_bytes(int n_slots, int entries_per_slot) {
-    if (!evcache_args_ok(n_slots, entries_per_slot)) return 0;
-    return make_ec_layout((size_t)n_slots, (size_t)entries_per_slot).total;
-}
-
-int xq_evcache_init(xq_evcache *cache, int n_slots, int entries_per_slot, void *dev_mem, size_t bytes, void *stream) {
-    if (!cache || !evcache_args_ok(n_slots, entries_per_slot) || !dev_mem || ((uintptr_t)dev_mem & 255)) return XQ_ERR_ARG;
-    const EcLayout l = make_ec_layout((size_t)n_slots, (size_t)entries_per_slot);
-    if (bytes < l.total) return XQ_ERR_WORKSPACE;
-    memset(cache, 0, sizeof(*cache));
-    cache->n_slots = n_slots;
-    cache->entries = entries_per_slot;
-    cache->ways = entries_per_slot < 4 ? entries_per_slot : 4;
-    cache->sets = entries_per_slot / cache->ways;
-    for (int i = 0; i < EC_N; ++i) cache->p[i] = (char *)dev_mem + l.off[i];
-    hipStream_t s = (hipStream_t)stream;
-    XQ_TRY(hipMemsetAsync(dev_mem, 0, l.off[EC_COUNT], s));   // generation 0, clocks, flags, counters, entry generations, stamps
-    hipLaunchKernelGGL(k_evcache_invalidate, dim3(1), dim3(64), 0, s, (uint32_t *)cache->p[EC_GEN]);   // generation 1
-    return launch_status();
-}
-
-int xq_evcache_hit_flags(const xq_evcache *cache, const int32_t **dev_hit) {
-    if (!evcache_ok(cache) || !dev_hit) return XQ_ERR_ARG;
-    *dev_hit = (const int32_t *)cache->p[EC_HIT];
-    return XQ_OK;
-}
-
-int xq_evcache_probe(const xq_evcache *cache, const xq_engine *eng, const float *dev_nn_input, void *stream) {
-    if (!eng || leaves_of(eng) > 1) return XQ_ERR_ARG;            // the cache serves one request row per slot
-    if (!evcache_ok(cache) || !dev_nn_input || eng->cfg.n_games <= 0 || cache->n_slots != eng->cfg.n_games)
-        return XQ_ERR_ARG;
-    const int G = eng->cfg.n_games;
-    hipLaunchKernelGGL(k_evcache_probe, dim3((G + 3) / 4), dim3(256), 0, (hipStream_t)stream, make_dev(eng), make_evdev(cache),
-                       dev_nn_input, (float *)eng->p[P_PK_LOGITS], (float *)eng->p[P_PK_VALUE]);
-    return launch_status();
-}
-
-int xq_engine_compact_misses(const xq_engine *eng, const float *dev_nn_input, const int32_t *dev_hit_flags, void *stream) {
-    if (!eng || !dev_nn_input || !dev_hit_flags || eng->cfg.n_games <= 0 || leaves_of(eng) > 1) return XQ_ERR_ARG;
-    const Dev d = make_dev(eng);
-    hipStream_t s = (hipStream_t)stream;
-    int32_t *n_live = (int32_t *)eng->p[P_PK_N], *rows = (int32_t *)eng->p[P_PK_ROWS];
-    hipLaunchKernelGGL(k_compact_misses, dim3(1), dim3(CPT), 0, s, d, dev_hit_flags, n_live, rows);
-    int rc = launch_status();
-    if (rc != XQ_OK) return rc;
-    hipLaunchKernelGGL(k_gather_rows, dim3(eng->cfg.n_games), dim3(256), 0, s, d, (const int32_t *)n_live, (const int32_t *)rows,
-                       dev_nn_input, (float *)eng->p[P_PK_X], (uint16_t *)eng->p[P_PK_MOVES], (int32_t *)eng->p[P_PK_COUNTS]);
-    return launch_status();
-}
-
-int xq_evcache_commit(const xq_evcache *cache, const xq_engine *eng, const float *dev_packed_logits,
-                      const float *dev_packed_value, void *stream) {
-    if (!evcache_ok(cache) || !eng || leaves_of(eng) > 1 || !dev_packed_logits || !dev_packed_value || eng->cfg.n_games <= 0 ||
-        cache->n_slots != eng->cfg.n_games || (((uintptr_t)dev_packed_logits) & 7))
-        return XQ_ERR_ARG;
-    const int G = eng->cfg.n_games;
-    hipLaunchKernelGGL(k_evcache_commit, dim3((G + 3) / 4), dim3(256), 0, (hipStream_t)stream, make_evdev(cache), G,
-                       (const int32_t *)eng->p[P_PK_N], (const int32_t *)eng->p[P_PK_ROWS], (const int32_t *)eng->p[P_PK_COUNTS],
-                       dev_packed_logits, dev_packed_value);
-    return launch_status();
-}
-
-int xq_evcache_invalidate(const xq_evcache *cache, void *stream) {
-    if (!evcache_ok(cache)) return XQ_ERR_ARG;
-    hipLaunchKernelGGL(k_evcache_invalidate, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t *)cache->p[EC_GEN]);
-    return launch_status();
-}
-
-int xq_evcache_stats_read(const xq_evcache *cache, xq_evcache_stats *host_out, void *stream) {
-    if (!evcache_ok(cache) || !host_out) return XQ_ERR_ARG;
-    const size_t n = (size_t)cache->n_slots * ECS_N;
-    unsigned long long *h = (unsigned long long *)malloc(n * sizeof(unsigned long long));
-    if (!h) return XQ_ERR_ARG;
-    int rc = xq::check(hipMemcpyAsync(h, cache->p[EC_STATS], n * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                      (hipStream_t)stream));
-    if (rc == XQ_OK) rc = xq::check(hipStreamSynchronize((hipStream_t)stream));
-    if (rc == XQ_OK) {
-        unsigned long long sum[ECS_N] = {0};
-        for (size_t i = 0; i < n; ++i) sum[i % ECS_N] += h[i];
-        memset(host_out, 0, sizeof(*host_out));
-        host_out->probes = sum[ECS_PROBES]; host_out->hits = sum[ECS_HITS]; host_out->inserts = sum[ECS_INSERTS];
-        host_out->evictions = sum[ECS_EVICTIONS]; host_out->mismatches = sum[ECS_MISMATCHES];
-    }
-    free(h);
-    return rc;
-}
-
-int xq_evcache_key_host(const float *host_planes, uint32_t *host_out12) {
-    if (!host_planes || !host_out12) return XQ_ERR_ARG;
-    for (int w = 0; w < EC_KEYW; ++w) host_out12[w] = 0;
-    for (int sq = 0; sq < 90; ++sq) host_out12[sq >> 3] |= evkey_nibble(host_planes, sq) << (4 * (sq & 7));
-    host_out12[90 >> 3] |= evkey_side(host_planes) << (4 * (90 & 7));
-    return XQ_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,215 @@
+// xq_engine_state.cuh -- what more than one of the engine's translation units needs (map: xq_engine.hip): the numbering of the
+// phases, state words, counters and workspace regions, the device view of the handle, the words behind the square-root table,
+// the pad0 encoding, Philox, and the one-workgroup compaction.  Device and host helpers only: every kernel lives in one unit.
+//
+// include/xq_hip.h pins the handle; tests pin the Gi / St / Ptr numbering and the workspace layout, and
+// xiangqi-alphazero_amd/hip.py mirrors the entries Python reads (P_*, GI_*, PH_HOLD).  A change here changes both.
+#pragma once
+
+#include <float.h>
+#include <math.h>
+#include <string.h>
+
+#include "xq_common.h"
+#include "xq_rules.cuh"
+
+#pragma clang fp contract(off)
+
+using namespace xq;
+
+namespace xq {
+
+// k_gather_rows over the engine's own packed buffers, for the first `rows` request rows (xq_engine_packed.hip).  The one call
+// that crosses units: the evaluation cache's miss compaction gathers as the packed step does.  Not exported.
+__attribute__((visibility("hidden"))) int gather_packed_rows(const xq_engine *eng, const float *dev_nn_input, int rows, hipStream_t s);
+
+}  // namespace xq
+
+namespace {
+
+enum Phase : int { PH_NEWGAME = 0, PH_NEWPOS = 1, PH_WAIT_ROOT = 2, PH_SEARCH = 3, PH_WAIT_LEAF = 4, PH_FINISHED = 5,
+                   PH_IDLE = 6, PH_HOLD = 7 };
+
+enum Gi : int { GI_SIDE = 0, GI_MC, GI_NOCAP, GI_PHASE, GI_SIMS, GI_NSAMP, GI_GSEQ, GI_ALLOC, GI_PLEAF, GI_PDEPTH,
+                GI_PCOUNT, GI_RSTATUS, GI_RWINNER, GI_RESIGN_N, GI_RNG0, GI_RNG1, GI_RNG2, GI_RNG3, GI_FWINNER,
+                GI_FREASON, GI_MANNOISE, GI_DELAY, GI_NPEND, GI_RR_NODE, GI_RR_MARK, GI_RR_DROP,
+                // playout cap (xq_engine_init_cap): this move's kind (1 full, 0 fast) and budget, written by k_select<.., true> at
+                // PH_NEWPOS; S_fast and the two halves of the float64 threshold p, written once by k_init_cap
+                GI_CAP_FULL, GI_CAP_BUDGET, GI_CAP_SFAST, GI_CAP_PLO, GI_CAP_PHI,
+                // forced playouts (xq_engine_init_fp): k as float32 bits, written once by k_init_fp
+                GI_FP_K, GI_N = 32 };
+static_assert(GI_FP_K == 31, "the forced-playout parameter takes the last free state word");
+
+enum St : int { ST_SIMS = 0, ST_TERM, ST_LEAF, ST_ROOT, ST_MOVES, ST_GAMES, ST_RED, ST_BLACK, ST_DRAW, ST_PLIES, ST_NODES,
+                ST_DEPTH, ST_SCAN, ST_RESIGN, ST_SAMP, ST_DROP, ST_OVF, ST_STARTED, ST_ROWS, ST_COLL, ST_LPS, ST_LSTEPS, ST_REUSED,
+                ST_REROOTS, ST_FASTM, ST_FASTS, ST_FORCED, ST_PRUNEDV, ST_PRUNEDC, ST_GZ_MOVES, ST_GZ_CONS, ST_GZ_OFF, ST_N = 32 };
+static_assert(ST_GZ_OFF == 31, "the Gumbel counters take the last free statistics words");
+
+enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_TW, P_TP, P_TA, P_TC, P_TM, P_ROOTP,
+                 P_STAGE, P_OUTS, P_OUTR, P_CNT, P_STATS, P_INJECT, P_SQRT, P_MNOISE, P_STATSUM, P_REQ,
+                 P_PK_N, P_PK_ROWS, P_PK_X, P_PK_MOVES, P_PK_COUNTS, P_PK_LOGITS, P_PK_VALUE, P_VL, P_LEAF };
+
+enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM = 3 };
+
+// Device view of the engine (passed by value to kernels)
+struct Dev {
+    xq_engine_config cfg;
+    int node_cap, path_cap, stage_cap;
+    int8_t *board, *hist;
+    int32_t *gi;
+    double *resign;
+    uint16_t *pmoves;
+    int32_t *path;
+    int32_t *tN; double *tW; float *tP; uint16_t *tA; int32_t *tC; uint16_t *tM;
+    double *rootP;
+    uint8_t *stage, *outs, *outr;
+    unsigned int *cnt;              // [0] out samples, [1] out results
+    unsigned long long *started;    // games started (quota)
+    unsigned long long *stats;      // [G][ST_N]
+    const uint64_t *inject;
+    const double *sqrt_tab;
+    double *mnoise;
+    int32_t *req;                   // [G] legal moves of the evaluation each slot asked for this step (0: none)
+};
+
+Dev make_dev(const xq_engine *e) {
+    Dev d;
+    d.cfg = e->cfg;
+    d.node_cap = e->node_cap; d.path_cap = e->path_cap; d.stage_cap = e->stage_cap;
+    d.board = (int8_t *)e->p[P_BOARD]; d.hist = (int8_t *)e->p[P_HIST]; d.gi = (int32_t *)e->p[P_GI];
+    d.resign = (double *)e->p[P_RESIGN]; d.pmoves = (uint16_t *)e->p[P_PMOVES]; d.path = (int32_t *)e->p[P_PATH];
+    d.tN = (int32_t *)e->p[P_TN]; d.tW = (double *)e->p[P_TW]; d.tP = (float *)e->p[P_TP];
+    d.tA = (uint16_t *)e->p[P_TA]; d.tC = (int32_t *)e->p[P_TC]; d.tM = (uint16_t *)e->p[P_TM];
+    d.rootP = (double *)e->p[P_ROOTP]; d.stage = (uint8_t *)e->p[P_STAGE]; d.outs = (uint8_t *)e->p[P_OUTS];
+    d.outr = (uint8_t *)e->p[P_OUTR]; d.cnt = (unsigned int *)e->p[P_CNT];
+    d.started = (unsigned long long *)((char *)e->p[P_CNT] + 16);
+    d.stats = (unsigned long long *)e->p[P_STATS]; d.inject = (const uint64_t *)e->p[P_INJECT];
+    d.sqrt_tab = (const double *)e->p[P_SQRT]; d.mnoise = (double *)e->p[P_MNOISE]; d.req = (int32_t *)e->p[P_REQ];
+    return d;
+}
+
+// Gumbel root search (xq_engine_init_gz): its words live behind the square-root table, in that table's workspace region (the handle,
+// the config struct and the per-slot state words are full): the parameters, the root's network value of every slot, and the
+// considered-visit tables, row k - 1 for k considered moves.  K = 1 always, so the square-root table has S + 2 entries.
+struct GzHead {
+    int32_t m;                      // considered moves at most
+    float c_visit, c_scale;         // rounded to float32 once, widened at every use
+    int32_t pad;
+};
+static_assert(sizeof(GzHead) == 16, "GzHead layout");
+
+size_t gz_bytes(size_t G, size_t S, size_t m) { return sizeof(GzHead) + G * 8 + m * S * 2; }
+
+__device__ __forceinline__ const GzHead *gz_head(const Dev &E) { return (const GzHead *)(E.sqrt_tab + E.cfg.num_simulations + 2); }
+__device__ __forceinline__ double *gz_vhat(const Dev &E) { return (double *)(gz_head(E) + 1); }
+__device__ __forceinline__ const uint16_t *gz_table(const Dev &E) { return (const uint16_t *)(gz_vhat(E) + E.cfg.n_games); }
+
+// Arena options (xq_engine_init_ar; manual_moves = 2, so never a Gumbel engine): their words lie behind the square-root table as
+// well, from the next 256-byte boundary on: the parameters, what every slot played as its opening, and the two buffer sets of the
+// per-model packed step (set 0: the new model's slots, set 1: the old model's).  Offsets from the table's first byte.
+struct ArHead {
+    int32_t opening_plies, first_game, pad[2];
+};
+static_assert(sizeof(ArHead) == 16, "ArHead layout");
+
+struct ArOff {
+    size_t head, op_counts, op_actions, n_live, rows[2], x[2], moves[2], counts[2], end;
+};
+
+__host__ __device__ inline size_t ar_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+__host__ __device__ inline ArOff ar_off(size_t G, size_t S) {
+    ArOff a;
+    size_t o = ar_align((S + 2) * 8);
+    a.head = o; o = ar_align(o + sizeof(ArHead));
+    a.op_counts = o; o = ar_align(o + G * 4);
+    a.op_actions = o; o = ar_align(o + G * XQ_ARENA_MAX_OPENING * 2);
+    a.n_live = o; o = ar_align(o + 2 * 4);
+    for (int m = 0; m < 2; ++m) {
+        a.rows[m] = o; o = ar_align(o + G * 4);
+        a.x[m] = o; o = ar_align(o + G * XQ_STATE_FLOATS * 4);
+        a.moves[m] = o; o = ar_align(o + G * XQ_MAXM * 2);
+        a.counts[m] = o; o = ar_align(o + G * 4);
+    }
+    a.end = o;
+    return a;
+}
+
+// pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
+// flag bits "playout cap on" (xq_engine_init_cap), "forced playouts on" (xq_engine_init_fp) and "Gumbel root search on"
+// (xq_engine_init_gz) and "arena options on" (xq_engine_init_ar)
+constexpr int PAD0_CAP = 1 << 30;
+constexpr int PAD0_FORCED = 1 << 29;
+constexpr int PAD0_GUMBEL = 1 << 28;
+constexpr int PAD0_ARENA = 1 << 27;
+int leaves_of(const xq_engine *e) { return (e->pad0 & 0xFFFF) > 1 ? (e->pad0 & 0xFFFF) : 1; }
+bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE_TREE_REUSE; }
+bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
+bool forced_of(const xq_engine *e) { return (e->pad0 & PAD0_FORCED) != 0; }
+bool gumbel_of(const xq_engine *e) { return (e->pad0 & PAD0_GUMBEL) != 0; }
+bool arena_of(const xq_engine *e) { return e && (e->pad0 & PAD0_ARENA) != 0 && e->cfg.n_games > 0 && e->p[P_SQRT]; }
+
+// ---------------------------------------------------------------------------------------------------------
+// RNG: Philox4x32-10 keyed by (seed, rank), counter (slot, kind, ctr, sub); or injected raw draws (tests).
+__device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0, uint32_t k1) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+}
+
+__device__ inline uint64_t philox_u64(uint64_t seed, uint32_t rank, uint32_t slot, uint32_t kind, uint32_t ctr, uint32_t sub) {
+    uint32_t c0 = slot, c1 = kind | (sub << 8), c2 = ctr, c3 = rank;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        philox_round(c0, c1, c2, c3, k0, k1);
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return ((uint64_t)c0 << 32) | c1;
+}
+
+// waiting for an evaluation: k_expand's own predicate
+__device__ __forceinline__ bool slot_waits(const Dev &E, int slot) {
+    const int ph = E.gi[(size_t)slot * GI_N + GI_PHASE];
+    return ph == PH_WAIT_ROOT || ph == PH_WAIT_LEAF;
+}
+
+// Stable compaction by ONE workgroup of the rows r < R with live(r), for any R: thread t owns the contiguous rows
+// [t K, t K + K), K = ceil(R / 1024); it counts its live rows, a block-wide exclusive scan of the counts gives its first packed
+// row, and it writes rows[] in row order.  R = 8192: eight strided 4-byte reads per thread, a few microseconds.
+constexpr int CPT = 1024;
+template <class Live>
+__device__ __forceinline__ void block_compact(const Dev &E, int R, Live live, int32_t *__restrict__ n_live, int32_t *__restrict__ rows) {
+    __shared__ int wsum[CPT / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int K = (R + CPT - 1) / CPT;
+    const int r0 = t * K, r1 = min(r0 + K, R);
+    int cnt = 0;
+    for (int r = r0; r < r1; ++r) cnt += live(r);
+    int inc = cnt;                                    // inclusive scan within the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(inc, off);
+        if (lane >= off) inc += v;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < CPT / 64; ++w) {
+        const int v = wsum[w];
+        base += w < wave ? v : 0;
+        total += v;
+    }
+    int o = base + inc - cnt;
+    for (int r = r0; r < r1; ++r)
+        if (live(r)) rows[o++] = r;
+    if (t == 0) {
+        *n_live = total;
+        E.stats[ST_ROWS] += (unsigned long long)total;   // slot 0's counter row: k_reduce_stats sums the column
+    }
+}
+
+size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+}  // namespace

@@ -69,6 +69,7 @@ outputs back.  `arena_openings()` reads what was played.  K = 1, none of the oth
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 from typing import Callable, Optional
 
@@ -115,91 +116,107 @@ def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
     return int(hip.lib().xq_evcache_bytes(int(n_slots), int(entries_per_slot)))
 
 
+# What `parse_engine_options` returns: the arguments every xq_engine_workspace_bytes_* / xq_engine_init_* call takes after the
+# config, the four structs as ctypes structures or None (the C side's NULL)
+EngineOptions = collections.namedtuple("EngineOptions", "K flags cap forced gumbel arena")
+
+
+def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
+                         forced_playouts=None, gumbel=None, arena_opts=None, eval_cache_entries: int = 0) -> EngineOptions:
+    """The engine options of `SelfPlayEngine` checked and turned into the C structs; needs no GPU.  Every rule of the header's
+    refusal lists (include/xq_hip.h; opts_ok in csrc/xq_engine_setup.hip) is refused here first, with a message that names the
+    option; tests/test_engine_options.py holds the two side by side."""
+    K = int(leaves_per_step)
+    if not 1 <= K <= 64:
+        raise hip.XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
+    tree_reuse = bool(tree_reuse)
+    if tree_reuse and int(cfg.manual_moves) != 0:
+        raise hip.XqError("tree_reuse is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
+    if tree_reuse and K > 1:
+        raise hip.XqError("tree_reuse cannot be combined with leaves_per_step > 1")
+    if tree_reuse and int(cfg.num_simulations) > hip.REUSE_MAX_SIMS:
+        raise hip.XqError(f"tree_reuse supports num_simulations <= {hip.REUSE_MAX_SIMS}, got {cfg.num_simulations}")
+    cap = None
+    if playout_cap is not None:
+        try:
+            p_full, s_fast = float(playout_cap[0]), int(playout_cap[1])
+        except (TypeError, ValueError, IndexError):
+            raise hip.XqError("playout_cap must be (full_search_prob, fast_simulations)")
+        if int(cfg.manual_moves) != 0:
+            raise hip.XqError("playout_cap is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
+        if K > 1:
+            raise hip.XqError("playout_cap cannot be combined with leaves_per_step > 1")
+        if not 1 <= s_fast < int(cfg.num_simulations):
+            raise hip.XqError(f"playout_cap: fast_simulations must be in [1, num_simulations), got {s_fast}")
+        if not 0.0 < p_full <= 1.0:                    # a NaN fails both comparisons
+            raise hip.XqError(f"playout_cap: full_search_prob must be in (0, 1], got {p_full}")
+        cap = hip.PlayoutCap(s_fast, 0, p_full)
+    forced = None
+    if forced_playouts is not None:
+        try:
+            fk = float(forced_playouts)
+        except (TypeError, ValueError):
+            raise hip.XqError("forced_playouts must be a number k with 0 < k <= 16")
+        if int(cfg.manual_moves) != 0:
+            raise hip.XqError("forced_playouts is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
+        if not int(cfg.add_noise):
+            raise hip.XqError("forced_playouts acts at noisy roots only: not available with add_noise = 0")
+        if K > 1:
+            raise hip.XqError("forced_playouts cannot be combined with leaves_per_step > 1")
+        if not 0.0 < fk <= 16.0:                       # a NaN fails both comparisons
+            raise hip.XqError(f"forced_playouts: k must be in (0, 16], got {fk}")
+        forced = hip.ForcedPlayouts(fk)
+    gz = None
+    if gumbel is not None:
+        try:
+            gm, gcv, gcs = int(gumbel[0]), float(gumbel[1]), float(gumbel[2])
+            if len(gumbel) != 3 or gm != gumbel[0]:
+                raise ValueError
+        except (TypeError, ValueError, IndexError, OverflowError):
+            raise hip.XqError("gumbel must be (considered_moves, c_visit, c_scale)")
+        if int(cfg.manual_moves) == 2:
+            raise hip.XqError("gumbel is a self-play and search option: not available for arena games (manual_moves = 2)")
+        if tree_reuse or cap is not None or forced is not None:
+            raise hip.XqError("gumbel cannot be combined with tree_reuse, playout_cap or forced_playouts")
+        if K > 1:
+            raise hip.XqError("gumbel cannot be combined with leaves_per_step > 1")
+        if not 1 <= gm <= hip.MAXM:
+            raise hip.XqError(f"gumbel: considered moves must be in [1, {hip.MAXM}], got {gm}")
+        f32_max = float(np.finfo(np.float32).max)
+        if not (0.0 <= gcv <= f32_max) or not (0.0 < gcs <= f32_max) or not float(np.float32(gcs)) > 0.0:   # a NaN fails them
+            raise hip.XqError(f"gumbel: c_visit >= 0 and c_scale > 0, finite as float32, required; got {gcv}, {gcs}")
+        gz = hip.Gumbel(gm, 0, gcv, gcs)
+    ar = None
+    if arena_opts is not None:
+        try:
+            ar_plies, ar_first = int(arena_opts[0]), int(arena_opts[1])
+            if len(arena_opts) != 2 or ar_plies != arena_opts[0] or ar_first != arena_opts[1]:
+                raise ValueError
+        except (TypeError, ValueError, IndexError, OverflowError):
+            raise hip.XqError("arena_opts must be (opening_plies, first_game)")
+        if int(cfg.manual_moves) != 2:
+            raise hip.XqError("arena_opts needs an arena engine (manual_moves = 2)")
+        if K > 1 or tree_reuse or cap is not None or forced is not None or gz is not None or eval_cache_entries:
+            raise hip.XqError("arena_opts cannot be combined with another engine option")
+        if not 0 <= ar_plies <= hip.ARENA_MAX_OPENING:
+            raise hip.XqError(f"arena_opts: opening_plies must be in [0, {hip.ARENA_MAX_OPENING}], got {ar_plies}")
+        if not 0 <= ar_first <= 2 ** 31 - 1 - int(cfg.n_games):
+            raise hip.XqError(f"arena_opts: first_game must be a non-negative int32 game index, got {ar_first}")
+        ar = hip.ArenaOpts(ar_plies, ar_first)
+    if K > 1 and eval_cache_entries:
+        raise hip.XqError("leaves_per_step > 1 cannot be combined with an evaluation cache (eval_cache_entries > 0)")
+    if K > 1 and int(cfg.manual_moves) == 2:
+        raise hip.XqError("leaves_per_step > 1 is not available for arena games (manual_moves = 2)")
+    return EngineOptions(K, hip.ENGINE_TREE_REUSE if tree_reuse else 0, cap, forced, gz, ar)
+
+
 class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None):
-        K = int(leaves_per_step)
-        if not 1 <= K <= 64:
-            raise hip.XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
-        tree_reuse = bool(tree_reuse)
-        if tree_reuse and int(cfg.manual_moves) != 0:
-            raise hip.XqError("tree_reuse is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
-        if tree_reuse and K > 1:
-            raise hip.XqError("tree_reuse cannot be combined with leaves_per_step > 1")
-        if tree_reuse and int(cfg.num_simulations) > hip.REUSE_MAX_SIMS:
-            raise hip.XqError(f"tree_reuse supports num_simulations <= {hip.REUSE_MAX_SIMS}, got {cfg.num_simulations}")
-        cap = None
-        if playout_cap is not None:
-            try:
-                p_full, s_fast = float(playout_cap[0]), int(playout_cap[1])
-            except (TypeError, ValueError, IndexError):
-                raise hip.XqError("playout_cap must be (full_search_prob, fast_simulations)")
-            if int(cfg.manual_moves) != 0:
-                raise hip.XqError("playout_cap is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
-            if K > 1:
-                raise hip.XqError("playout_cap cannot be combined with leaves_per_step > 1")
-            if not 1 <= s_fast < int(cfg.num_simulations):
-                raise hip.XqError(f"playout_cap: fast_simulations must be in [1, num_simulations), got {s_fast}")
-            if not 0.0 < p_full <= 1.0:                    # a NaN fails both comparisons
-                raise hip.XqError(f"playout_cap: full_search_prob must be in (0, 1], got {p_full}")
-            cap = hip.PlayoutCap(s_fast, 0, p_full)
-        forced = None
-        if forced_playouts is not None:
-            try:
-                fk = float(forced_playouts)
-            except (TypeError, ValueError):
-                raise hip.XqError("forced_playouts must be a number k with 0 < k <= 16")
-            if int(cfg.manual_moves) != 0:
-                raise hip.XqError("forced_playouts is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
-            if not int(cfg.add_noise):
-                raise hip.XqError("forced_playouts acts at noisy roots only: not available with add_noise = 0")
-            if K > 1:
-                raise hip.XqError("forced_playouts cannot be combined with leaves_per_step > 1")
-            if not 0.0 < fk <= 16.0:                       # a NaN fails both comparisons
-                raise hip.XqError(f"forced_playouts: k must be in (0, 16], got {fk}")
-            forced = hip.ForcedPlayouts(fk)
-        gz = None
-        if gumbel is not None:
-            try:
-                gm, gcv, gcs = int(gumbel[0]), float(gumbel[1]), float(gumbel[2])
-                if len(gumbel) != 3 or gm != gumbel[0]:
-                    raise ValueError
-            except (TypeError, ValueError, IndexError, OverflowError):
-                raise hip.XqError("gumbel must be (considered_moves, c_visit, c_scale)")
-            if int(cfg.manual_moves) == 2:
-                raise hip.XqError("gumbel is a self-play and search option: not available for arena games (manual_moves = 2)")
-            if tree_reuse or cap is not None or forced is not None:
-                raise hip.XqError("gumbel cannot be combined with tree_reuse, playout_cap or forced_playouts")
-            if K > 1:
-                raise hip.XqError("gumbel cannot be combined with leaves_per_step > 1")
-            if not 1 <= gm <= hip.MAXM:
-                raise hip.XqError(f"gumbel: considered moves must be in [1, {hip.MAXM}], got {gm}")
-            f32_max = float(np.finfo(np.float32).max)
-            if not (0.0 <= gcv <= f32_max) or not (0.0 < gcs <= f32_max) or not float(np.float32(gcs)) > 0.0:   # a NaN fails them
-                raise hip.XqError(f"gumbel: c_visit >= 0 and c_scale > 0, finite as float32, required; got {gcv}, {gcs}")
-            gz = hip.Gumbel(gm, 0, gcv, gcs)
-        ar = None
-        if arena_opts is not None:
-            try:
-                ar_plies, ar_first = int(arena_opts[0]), int(arena_opts[1])
-                if len(arena_opts) != 2 or ar_plies != arena_opts[0] or ar_first != arena_opts[1]:
-                    raise ValueError
-            except (TypeError, ValueError, IndexError, OverflowError):
-                raise hip.XqError("arena_opts must be (opening_plies, first_game)")
-            if int(cfg.manual_moves) != 2:
-                raise hip.XqError("arena_opts needs an arena engine (manual_moves = 2)")
-            if K > 1 or tree_reuse or cap is not None or forced is not None or gz is not None or eval_cache_entries:
-                raise hip.XqError("arena_opts cannot be combined with another engine option")
-            if not 0 <= ar_plies <= hip.ARENA_MAX_OPENING:
-                raise hip.XqError(f"arena_opts: opening_plies must be in [0, {hip.ARENA_MAX_OPENING}], got {ar_plies}")
-            if not 0 <= ar_first <= 2 ** 31 - 1 - int(cfg.n_games):
-                raise hip.XqError(f"arena_opts: first_game must be a non-negative int32 game index, got {ar_first}")
-            ar = hip.ArenaOpts(ar_plies, ar_first)
-        if K > 1 and eval_cache_entries:
-            raise hip.XqError("leaves_per_step > 1 cannot be combined with an evaluation cache (eval_cache_entries > 0)")
-        if K > 1 and int(cfg.manual_moves) == 2:
-            raise hip.XqError("leaves_per_step > 1 is not available for arena games (manual_moves = 2)")
+        K, flags, cap, forced, gz, ar = parse_engine_options(
+            cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
+            gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries)
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
@@ -207,28 +224,16 @@ class SelfPlayEngine:
         self.cfg = cfg
         self.G = cfg.n_games
         self.K = K
-        self.tree_reuse = tree_reuse
+        self.tree_reuse = bool(flags & hip.ENGINE_TREE_REUSE)
         self.playout_cap = None if cap is None else (cap.full_search_prob, cap.fast_simulations)
         self.forced_playouts = None if forced is None else float(np.float32(forced.k))   # k as the kernels use it
         self.gumbel = None if gz is None else (gz.considered, float(np.float32(gz.c_visit)), float(np.float32(gz.c_scale)))
         self.arena_opts = None if ar is None else (ar.opening_plies, ar.first_game)
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
-        flags = hip.ENGINE_TREE_REUSE if tree_reuse else 0
-        cap_ref = None if cap is None else C.byref(cap)
-        if ar is not None:
-            nbytes = self.lib.xq_engine_workspace_bytes_ar(C.byref(cfg), K, flags, None, None, None, C.byref(ar))
-        elif gz is not None:
-            nbytes = self.lib.xq_engine_workspace_bytes_gz(C.byref(cfg), K, flags, None, None, C.byref(gz))
-        elif forced is not None:
-            nbytes = self.lib.xq_engine_workspace_bytes_fp(C.byref(cfg), K, flags, cap_ref, C.byref(forced))
-        elif cap is not None:
-            nbytes = self.lib.xq_engine_workspace_bytes_cap(C.byref(cfg), K, flags, C.byref(cap))
-        elif tree_reuse:
-            nbytes = self.lib.xq_engine_workspace_bytes_ex(C.byref(cfg), K, flags)
-        else:
-            nbytes = (self.lib.xq_engine_workspace_bytes(C.byref(cfg)) if K == 1 else
-                      self.lib.xq_engine_workspace_bytes_leaves(C.byref(cfg), K))
+        # every entry point is the widest one with NULL for the options it does not take (include/xq_hip.h)
+        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar)]
+        nbytes = self.lib.xq_engine_workspace_bytes_ar(C.byref(cfg), K, flags, *refs)
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
@@ -244,34 +249,11 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            if ar is not None:
-                hip.check(self.lib.xq_engine_init_ar(C.byref(self.h), C.byref(cfg), K, flags, None, None, None, C.byref(ar), base,
-                                                     self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
-                          "xq_engine_init_ar")
-            elif gz is not None:
-                hip.check(self.lib.xq_engine_init_gz(C.byref(self.h), C.byref(cfg), K, flags, None, None, C.byref(gz), base,
-                                                     self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
-                          "xq_engine_init_gz")
-            elif forced is not None:
-                hip.check(self.lib.xq_engine_init_fp(C.byref(self.h), C.byref(cfg), K, flags, cap_ref, C.byref(forced), base,
-                                                     self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
-                          "xq_engine_init_fp")
-            elif cap is not None:
-                hip.check(self.lib.xq_engine_init_cap(C.byref(self.h), C.byref(cfg), K, flags, C.byref(cap), base,
-                                                      self.workspace_bytes, inj_ptr, hip.stream_ptr(self.device)),
-                          "xq_engine_init_cap")
-            elif tree_reuse:
-                hip.check(self.lib.xq_engine_init_ex(C.byref(self.h), C.byref(cfg), K, flags, base, self.workspace_bytes, inj_ptr,
-                                                     hip.stream_ptr(self.device)), "xq_engine_init_ex")
-            elif K == 1:
-                hip.check(self.lib.xq_engine_init(C.byref(self.h), C.byref(cfg), base, self.workspace_bytes, inj_ptr,
-                                                  hip.stream_ptr(self.device)), "xq_engine_init")
-            else:
-                hip.check(self.lib.xq_engine_init_leaves(C.byref(self.h), C.byref(cfg), K, base, self.workspace_bytes, inj_ptr,
-                                                         hip.stream_ptr(self.device)), "xq_engine_init_leaves")
-        # zero-copy int32 view of the per-slot state words (side to move of the REAL game in column 0, move_count 1,
-        # phase 3, simulations done 4): host-side policies such as the arena's model choice read it between stages
-        gi_off = int(self.h.p[2]) - int(self.ws.data_ptr())
+            hip.check(self.lib.xq_engine_init_ar(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
+                                                 hip.stream_ptr(self.device)), "xq_engine_init_ar")
+        # zero-copy int32 view of the per-slot state words (columns hip.GI_*: side to move of the REAL game, move_count, phase,
+        # simulations done): host-side policies such as the arena's model choice read it between stages
+        gi_off = int(self.h.p[hip.P_GI]) - int(self.ws.data_ptr())
         self.slot_ints = self.ws[gi_off:gi_off + self.G * 32 * 4].view(torch.int32).view(self.G, 32)
         # sparse hand-off to the evaluator (xq_engine_requests): ordered legal moves + their number per pending evaluation
         pm, pc = C.c_void_p(), C.c_void_p()
@@ -596,11 +578,11 @@ class SelfPlayEngine:
             nbytes = self.G * cols * torch.empty(0, dtype=dtype).element_size()
             return self.ws[off:off + nbytes].view(dtype).view(self.G, cols)
 
-        out = dict(N=view(6, torch.int32, cap), W=view(7, torch.float64, cap), P=view(8, torch.float32, cap),
-                   action=view(9, torch.int16, cap), first=view(10, torch.int32, cap), meta=view(11, torch.int16, cap),
-                   board=view(0, torch.int8, 96), node_cap=cap)
+        out = dict(N=view(hip.P_TN, torch.int32, cap), W=view(hip.P_TW, torch.float64, cap), P=view(hip.P_TP, torch.float32, cap),
+                   action=view(hip.P_TA, torch.int16, cap), first=view(hip.P_TC, torch.int32, cap),
+                   meta=view(hip.P_TM, torch.int16, cap), board=view(hip.P_BOARD, torch.int8, 96), node_cap=cap)
         if self.K > 1:
-            out["vl"] = view(30, torch.int32, cap)     # virtual-loss counters: all 0 between steps
+            out["vl"] = view(hip.P_VL, torch.int32, cap)     # virtual-loss counters: all 0 between steps
         return out
 
     def slot_counters(self) -> torch.Tensor:
@@ -608,7 +590,7 @@ class SelfPlayEngine:
         pending leaves handed out, 21: slot-steps that handed leaves, 22: reused visits, 23: re-rooted searches, 24: fast moves,
         25: simulations of fast searches, 26: forced simulations, 27: pruned visits, 28: pruned children, 29: Gumbel moves, 30: the sum
         of their considered moves, 31: Gumbel moves off the prior's first maximum).  For tests."""
-        off = int(self.h.p[17]) - int(self.ws.data_ptr())
+        off = int(self.h.p[hip.P_STATS]) - int(self.ws.data_ptr())
         return self.ws[off:off + self.G * 32 * 8].view(torch.int64).view(self.G, 32)
 
     def gumbel_root_values(self) -> torch.Tensor:
@@ -616,12 +598,12 @@ class SelfPlayEngine:
         move (behind the square-root table and the 16 bytes of parameters, include/xq_hip.h).  For tools and tests."""
         if self.gumbel is None:
             raise hip.XqError("gumbel_root_values needs an engine with gumbel=")
-        off = int(self.h.p[19]) - int(self.ws.data_ptr()) + (int(self.cfg.num_simulations) + 2) * 8 + 16
+        off = int(self.h.p[hip.P_SQRT]) - int(self.ws.data_ptr()) + (int(self.cfg.num_simulations) + 2) * 8 + 16
         return self.ws[off:off + self.G * 8].view(torch.float64)
 
     def held(self) -> bool:
         """Search-only engines: every slot holds its finished search (phase HOLD).  Synchronises."""
-        return bool((self.slot_ints[:, 3] == 7).all().item())
+        return bool((self.slot_ints[:, hip.GI_PHASE] == hip.PH_HOLD).all().item())
 
     # ---- MCTS.search for a given position (manual_moves engines; mcts.py:94-155) ---------------------------
     def set_position(self, slot: int, board, side: int, move_count: int = 0, no_capture: int = 0, hist12=None,

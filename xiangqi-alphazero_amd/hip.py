@@ -55,6 +55,23 @@ class Engine(C.Structure):
                 ("stage_cap", C.c_int32), ("pad0", C.c_int32), ("p", C.c_void_p * 32)]
 
 
+# Where Python looks into the workspace: indices into Engine.p, columns of a slot's 32 state words, one phase value.
+P_BOARD = 0        # mirrors P_BOARD of enum Ptr in csrc/xq_engine_state.cuh: the real games' boards
+P_GI = 2           # mirrors P_GI of enum Ptr: the per-slot state words
+P_TN, P_TW, P_TP, P_TA, P_TC, P_TM = 6, 7, 8, 9, 10, 11   # mirror P_TN .. P_TM of enum Ptr: the six tree arrays
+P_ROOTP = 12       # mirrors P_ROOTP of enum Ptr: the float64 root priors
+P_STATS = 17       # mirrors P_STATS of enum Ptr: the per-slot counters
+P_SQRT = 19        # mirrors P_SQRT of enum Ptr: the square-root table and the Gumbel / arena words behind it
+P_VL = 30          # mirrors P_VL of enum Ptr: the virtual-loss counters (leaves_per_step > 1)
+GI_SIDE = 0        # mirrors GI_SIDE of enum Gi in csrc/xq_engine_state.cuh: side to move of the real game
+GI_MC = 1          # mirrors GI_MC of enum Gi: its move count
+GI_PHASE = 3       # mirrors GI_PHASE of enum Gi
+GI_SIMS = 4        # mirrors GI_SIMS of enum Gi: simulations done
+GI_ALLOC = 7       # mirrors GI_ALLOC of enum Gi: the tree's allocation mark
+GI_RNG0 = 14       # mirrors GI_RNG0 of enum Gi: the first of the four stream counters
+PH_HOLD = 7        # mirrors PH_HOLD of enum Phase in csrc/xq_engine_state.cuh
+
+
 class EngineStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in
                 ("sims", "terminal_sims", "leaf_evals", "root_evals", "moves_played", "games_finished", "red_wins",
