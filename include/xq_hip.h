@@ -82,6 +82,31 @@ int xq_game_over_batch(const int8_t *dev_boards, const int8_t *dev_side, const i
                        const int32_t *dev_no_capture, const int8_t *dev_hist, int n, int8_t *dev_out,
                        void *stream);
 
+/* Rules options (opt-in; NULL everywhere is the reference's rules).  perpetual_check = 1: the side that checks through a repetition
+ * loses.  The reference calls every repetition a draw (game.py:606-614); under every real Xiangqi rule set the side that repeats
+ * the position by checking on every move loses, and a network trained on the draw learns to escape lost positions into a
+ * perpetual check no opponent will grant it.  Outside the reference-parity contract, like the other opt-in options.
+ * THE RULE.  The trigger is the reference's and does not move: the repetition test is reached exactly as before (after king
+ * capture, no legal move, 120 no-capture plies and the ply-200 material rule) and counts the boards of the 12-board window that
+ * equal the current one; nothing changes below three matches.  With three or more, and the option on:
+ *     s = the side to move now; entry e = 0, 1, ... = the board e + 1 plies ago (entry 0 is the newest pre-move board);
+ *     E = the oldest entry of the window that equals the current board: the start of the repetition span;
+ *     by ply parity -s is to move in the even entries and s in the odd ones (boards carry no side, none is stored);
+ *     chk(-s) = the side to move is in check now and in every odd entry e <= E: every move -s made in the span gave check;
+ *     chk(s)  = the side to move is in check in every even entry e <= E;
+ *     exactly one of the two holds: that side loses, the winner is the other; both or neither: a draw, as before.
+ * "In check" is xq_movegen_batch's in_check (a missing king counts as in check).  In practice only a 4-ply cycle played three times
+ * reaches three matches in twelve boards (distances 4, 8, 12, E = 11).  Chase rules (perpetual attack on an unprotected piece) are
+ * out of scope.
+ * xq_game_over_batch_ex: xq_game_over_batch with the options; dev_kind (or NULL) = uint8[n], what ended the game: 0 not over,
+ * 1 king missing, 2 no legal move, 3 no-capture, 4 ply-200, 5 repetition draw, 6 perpetual-check loss.  rules == NULL gives
+ * xq_game_over_batch's dev_out byte for byte, and xq_game_over_batch is that call.  XQ_ERR_ARG before any launch: perpetual_check
+ * outside {0, 1} or a non-zero reserved word. */
+typedef struct xq_rules_opts { int32_t perpetual_check; int32_t reserved[3]; } xq_rules_opts;
+int xq_game_over_batch_ex(const int8_t *dev_boards, const int8_t *dev_side, const int32_t *dev_move_count,
+                          const int32_t *dev_no_capture, const int8_t *dev_hist, int n, const xq_rules_opts *rules,
+                          int8_t *dev_out, uint8_t *dev_kind, void *stream);
+
 /* =====================================================================================
  * B3 -- self-play operator.  Replaces the search + game loop that the reference fans out over
  * processes: training/mcts.py:21-206 (MCTSNode, MCTS.search), training/parallel_selfplay.py:42-134
@@ -435,6 +460,24 @@ int xq_engine_init_ar(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       size_t ws_bytes, const uint64_t *dev_inject, void *stream);
 int xq_engine_arena_openings(const xq_engine *eng, const uint16_t **dev_actions /* [G][16] */, const int32_t **dev_counts /* [G] */);
 
+/* Rules options of an engine (opt-in; rules == NULL or perpetual_check = 0 is xq_engine_init_ar exactly, and xq_engine_init_ar is
+ * that call): the perpetual-check rule of xq_rules_opts above at every terminal test of the engine -- the root's status, the real
+ * game (openings included) and the leaves of the descent in k_select and k_select_multi.  It changes a terminal verdict and nothing
+ * else, so it goes with every mode (self-play, search only, arena) and every other option, and refuses only perpetual_check
+ * outside {0, 1} and a non-zero reserved word (XQ_ERR_ARG before any launch; xq_engine_workspace_bytes_ru: 0).
+ * A game the rule decides carries reason 4 in its xq_game_result and its root's status word is 4; reason 1 stays for every other
+ * rules ending, a repetition that stays a draw under the option included.  A leaf the rule decides backs up 1 for the side that
+ * moved into it when that side wins (the usual case: the checked side completes the repetition), like a mate, and -1 when that
+ * side loses (its own check completed its perpetual); every other decided leaf keeps the reference's 1 (mcts.py:137-140).
+ * No workspace, no state word, no counter: "rule on" lives in the handle (pad0, above the public flag bits) and reaches the
+ * kernels as a kernel argument. */
+size_t xq_engine_workspace_bytes_ru(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules);
+int xq_engine_init_ru(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream);
+
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 
 /* dev_policy[slot] = float32[8100]: network LOGITS (policy_is_probs = 0; softmax over all 8100 as
@@ -751,7 +794,8 @@ typedef struct xq_sample {
 typedef struct xq_game_result {
     uint32_t slot, game_seq;
     int8_t winner;      /* +1 / -1 / 0 */
-    uint8_t reason;     /* 1 rules (is_game_over), 2 max_game_length adjudication, 3 resign */
+    uint8_t reason;     /* 1 rules (is_game_over), 2 max_game_length adjudication, 3 resign, 4 rules: repetition, perpetual check
+                         * (xq_engine_init_ru only) */
     uint16_t steps;     /* game.move_count */
     uint16_t n_samples;
     uint16_t reserved;

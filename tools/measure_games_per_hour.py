@@ -160,7 +160,7 @@ def main():
         "rows_evaluated_share": round(st["rows_evaluated"] / (st["steps"] * min(args.slots, args.games)), 4),
         "plies_per_game": {"mean": round(float(steps.mean()), 2), "p10": int(np.percentile(steps, 10)),
                            "p50": int(np.percentile(steps, 50)), "p90": int(np.percentile(steps, 90)), "max": int(steps.max())},
-        "endings": {"rules": int((reasons == 1).sum()), "max_length": int((reasons == 2).sum()), "resign": int((reasons == 3).sum())},
+        "endings": {"rules": int(np.isin(reasons, (1, 4)).sum()), "max_length": int((reasons == 2).sum()), "resign": int((reasons == 3).sum())},
         "winners": {"red": st["red_wins"], "black": st["black_wins"], "draw": st["draws"]},
         "samples": int(len(samples)), "records_sha256_16": digest, "root_evals": st["root_evals"], "leaf_evals": st["leaf_evals"],
         "terminal_sims": st["terminal_sims"], "note": "games_target == games: the tail of the run has idle slots, so this "

@@ -20,6 +20,11 @@ with colours swapped and the games of different pairs differ; a shard plays the 
 packed one: the waiting slots are compacted into the new model's and the old model's buffer sets on the device and each network
 runs over its own live rows only.  Same games as the masked step.  `evaluate_models` reads `config.arena_opening_plies` and
 `config.arena_seed` and reports the standard error of the win rate over the pairs (`pair_statistics`).
+
+Opt-in as well: `perpetual_check` (`config.perpetual_check_loses` for `evaluate_models`) plays the gate under the perpetual-check
+rule: a game one side forces into a repetition by checking on every move is that side's loss, not half a
+point.  A loop that trains under the rule gates under it (`AlphaZeroLoop` passes one value to both); off, the gate is the
+reference's.
 """
 from __future__ import annotations
 
@@ -50,25 +55,27 @@ def _evaluate_subset(eng, ev, x, idx, policy_is_probs, dense, legal, value):
 
 def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_simulations: int, max_game_length: int,
                c_puct: float = 1.5, device="cuda", policy_is_probs: bool = False, first_game: int = 0,
-               opening_plies: int = 0, seed: int = 0, packed: Optional[bool] = None, inject=None, info: Optional[dict] = None):
+               opening_plies: int = 0, seed: int = 0, packed: Optional[bool] = None, inject=None, info: Optional[dict] = None,
+               perpetual_check: bool = False):
     """eval_*: evaluators in either protocol (`evaluate_legal`, or a callable float32[n,15,10,9] -> (policy
     float32[n,8100], value float32[n])); both must use the same one.  Plays games first_game .. first_game+eval_games-1
     of the arena (the new model is red in even games) and returns the results array ordered by game (slot == game -
     first_game).
     Opt-in: `opening_plies` > 0 and `seed` give every pair of games its random opening; `packed` (None: yes with openings when
     both evaluators offer `live_rows`) takes the per-model packed step; `inject` (uint64 [games, 4, n], tests only) replaces the
-    device draws; `info` (a dict) receives `openings`, `opening_counts`, `steps` (engine steps run) and the engine's `stats`."""
+    device draws; `info` (a dict) receives `openings`, `opening_counts`, `steps` (engine steps run) and the engine's `stats`;
+    `perpetual_check` builds the engine with the perpetual-check rule (results then may carry reason 4)."""
     cfg = engine.make_config(eval_games, eval_simulations, c_puct=c_puct, max_game_length=max_game_length,
                              random_opening_moves=0, enable_resign=False, add_noise=False, games_target=eval_games,
                              manual_moves=2)
     opts = int(opening_plies) > 0 or bool(packed) or inject is not None or info is not None
     if not opts:
-        eng = engine.SelfPlayEngine(cfg, device)
+        eng = engine.SelfPlayEngine(cfg, device, perpetual_check=perpetual_check)
     else:
         if inject is not None:
             cfg.inject_len = int(np.asarray(inject).shape[-1])
         cfg.seed = int(seed)
-        eng = engine.arena_engine(cfg, device, opening_plies, first_game, inject)
+        eng = engine.arena_engine(cfg, device, opening_plies, first_game, inject, perpetual_check=perpetual_check)
     dev = eng.device
     new_is_red = ((torch.arange(eval_games, device=dev) + first_game) % 2 == 0)
     sparse = hasattr(eval_new, "evaluate_legal") and hasattr(eval_old, "evaluate_legal") and not policy_is_probs
@@ -196,13 +203,15 @@ def pair_statistics(winners) -> Dict[str, object]:
 
 
 def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind: str = "hip", group=None,
-                    seed: Optional[int] = None) -> Dict[str, object]:
+                    seed: Optional[int] = None, perpetual_check: Optional[bool] = None) -> Dict[str, object]:
     """Same stats dict as the reference (`new_wins, old_wins, draws, win_rate, model_updated`); reads
     `eval_games, eval_simulations, c_puct, max_game_length, eval_win_rate` from `config` (train.py:97-100).
     Under torch.distributed the games are split over the ranks and the winners all-gathered.
     `config.arena_opening_plies` = R > 0 (absent or 0: off) plays paired random openings (module docstring) under the seed
     `seed` (None: `config.arena_seed`, absent: 0); `eval_games` must then be even, and the result adds `opening_plies`, `pairs`,
-    `openings` (uint16 [games, R]), `win_rate_se` and `win_rate_ci95`.  The promotion rule is unchanged."""
+    `openings` (uint16 [games, R]), `win_rate_se` and `win_rate_ci95`.  The promotion rule is unchanged.
+    `perpetual_check` (None: `config.perpetual_check_loses`, absent: off) plays the games under the perpetual-check rule; the
+    result then adds `perpetual_check` = True.  Off, `play_arena` is called as before."""
     import torch.distributed as dist
     from . import distributed as xdist
     total = int(config.eval_games)
@@ -211,6 +220,9 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
         raise ValueError(f"arena_opening_plies needs an even eval_games (games come in colour-swapped pairs), got {total}")
     if seed is None:
         seed = int(getattr(config, "arena_seed", 0) or 0)
+    if perpetual_check is None:
+        perpetual_check = bool(getattr(config, "perpetual_check_loses", False))
+    rule = {"perpetual_check": True} if perpetual_check else {}
     openings = np.zeros((total, max(plies, 0)), dtype=np.int64)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -224,11 +236,11 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
         if plies > 0:
             info = {}
             res = play_arena(en, eo, mine, int(config.eval_simulations), int(config.max_game_length), float(config.c_puct),
-                             device, first_game=first, opening_plies=plies, seed=int(seed), info=info)
+                             device, first_game=first, opening_plies=plies, seed=int(seed), info=info, **rule)
             openings[first:first + mine] = info["openings"][:, :plies]
         else:
             res = play_arena(en, eo, mine, int(config.eval_simulations), int(config.max_game_length), float(config.c_puct),
-                             device, first_game=first)
+                             device, first_game=first, **rule)
         winners[first:first + mine] = res["winner"].astype(np.int64)
         steps[first:first + mine] = res["steps"].astype(np.int64)
     if dist.is_initialized():         # disjoint shards: a sum gathers them; every rank ends with the same table (a group of
@@ -253,7 +265,7 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
     games = np.zeros(total, dtype=RESULT_DTYPE)
     games["slot"], games["winner"], games["steps"] = np.arange(total), winners, steps
     out = {"new_wins": new_wins, "old_wins": old_wins, "draws": draws, "win_rate": win_rate,
-           "model_updated": win_rate >= float(config.eval_win_rate), "games": games}
+           "model_updated": win_rate >= float(config.eval_win_rate), "games": games, **rule}
     if plies > 0:
         ps = pair_statistics(winners)
         out.update({"opening_plies": plies, "pairs": ps["pairs"], "openings": openings.astype(np.uint16),

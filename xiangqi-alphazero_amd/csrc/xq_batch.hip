@@ -109,11 +109,12 @@ __global__ void k_apply_moves(const int8_t *__restrict__ boards, const int8_t *_
     out_boards[(size_t)j * 90 + b] = v;
 }
 
-// game.py:565-616 for independent states; hist = last min(12,mc) pre-move boards, oldest first
+// game.py:565-616 for independent states; hist = last min(12,mc) pre-move boards, oldest first.  `perpetual`: the opt-in
+// perpetual-check rule (xq_rules_opts); `kind` (or NULL): which test ended the game (XQ_OVER_*).
 __global__ __launch_bounds__(64 * WPW) void k_game_over(const int8_t *__restrict__ boards, const int8_t *__restrict__ side,
                                                   const int32_t *__restrict__ move_count,
                                                   const int32_t *__restrict__ no_capture, const int8_t *__restrict__ hist,
-                                                  int n, int8_t *__restrict__ out) {
+                                                  int n, int perpetual, int8_t *__restrict__ out, uint8_t *__restrict__ kind) {
     __shared__ __attribute__((aligned(16))) int8_t s_boards[WPW][XQ_BS];
     __shared__ MoveGenLds s_mgs[WPW];
     __shared__ uint16_t s_outs[WPW][XQ_MAXM];
@@ -124,32 +125,41 @@ __global__ __launch_bounds__(64 * WPW) void k_game_over(const int8_t *__restrict
     wave_sync();
     const int player = side[i], mc = move_count[i], nc = no_capture[i];
     const VMove none{-1, -1, 0};
-    int done = 0, winner = 2;
-    if (find_king(s_board, none, 1) < 0) { done = 1; winner = -1; }
-    else if (find_king(s_board, none, -1) < 0) { done = 1; winner = 1; }
+    int over = XQ_OVER_NONE, winner = 2;
+    if (find_king(s_board, none, 1) < 0) { over = XQ_OVER_KING; winner = -1; }
+    else if (find_king(s_board, none, -1) < 0) { over = XQ_OVER_KING; winner = 1; }
     else {
         int ovf = 0;
         const int cnt = wave_movegen(s_board, player, s_mgs[wv], s_outs[wv], &ovf);
-        if (cnt == 0) { done = 1; winner = -player; }
-        else if (nc >= 120) { done = 1; winner = 0; }
+        if (cnt == 0) { over = XQ_OVER_NO_MOVE; winner = -player; }
+        else if (nc >= 120) { over = XQ_OVER_NO_CAPTURE; winner = 0; }
         else if (mc >= 200) {
             int red, black;
             wave_material(s_board, red, black);
             const int diff = red - black;
-            done = 1; winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
+            over = XQ_OVER_PLY200; winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
         } else if (mc >= 6) {
             const int k = mc < XQ_HIST ? mc : XQ_HIST;
+            const int8_t *hk = hist + (size_t)i * XQ_HIST * 90;
             int rep = 0;
             for (int e = 0; e < k; ++e) {
-                const int8_t *h = hist + ((size_t)i * XQ_HIST + e) * 90;
+                const int8_t *h = hk + (size_t)e * 90;
                 bool diff = h[lane] != s_board[lane];
                 if (lane + 64 < 90) diff = diff || (h[lane + 64] != s_board[lane + 64]);
                 if (__ballot(diff) == 0ull) ++rep;
             }
-            if (rep >= 3) { done = 1; winner = 0; }
+            if (rep >= 3) {
+                // the board e + 1 plies ago is row k - 1 - e of the oldest-first history
+                winner = perpetual ? wave_perpetual_winner(s_board, hk, 90, k - 1, k, player) : 0;
+                over = winner != 0 ? XQ_OVER_PERPETUAL : XQ_OVER_REPETITION;
+            }
         }
     }
-    if (lane == 0) { out[(size_t)i * 2] = (int8_t)done; out[(size_t)i * 2 + 1] = (int8_t)winner; }
+    const int done = over != XQ_OVER_NONE;
+    if (lane == 0) {
+        out[(size_t)i * 2] = (int8_t)done; out[(size_t)i * 2 + 1] = (int8_t)winner;
+        if (kind) kind[i] = (uint8_t)over;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -208,14 +218,26 @@ int xq_apply_moves_batch(const int8_t *dev_boards, const int8_t *dev_side, const
     return launch_status();
 }
 
-int xq_game_over_batch(const int8_t *dev_boards, const int8_t *dev_side, const int32_t *dev_move_count,
-                       const int32_t *dev_no_capture, const int8_t *dev_hist, int n, int8_t *dev_out, void *stream) {
+// xq_rules_opts as the entry points accept it: perpetual_check 0 or 1, reserved words zero
+static bool rules_ok(const xq_rules_opts *r) {
+    return (r->perpetual_check == 0 || r->perpetual_check == 1) && r->reserved[0] == 0 && r->reserved[1] == 0 && r->reserved[2] == 0;
+}
+
+int xq_game_over_batch_ex(const int8_t *dev_boards, const int8_t *dev_side, const int32_t *dev_move_count,
+                          const int32_t *dev_no_capture, const int8_t *dev_hist, int n, const xq_rules_opts *rules,
+                          int8_t *dev_out, uint8_t *dev_kind, void *stream) {
     if (n < 0 || (n > 0 && (!dev_boards || !dev_side || !dev_move_count || !dev_no_capture || !dev_hist || !dev_out)))
         return XQ_ERR_ARG;
+    if (rules && !rules_ok(rules)) return XQ_ERR_ARG;
     if (n == 0) return XQ_OK;
     hipLaunchKernelGGL(k_game_over, dim3((n + WPW - 1) / WPW), dim3(64 * WPW), 0, (hipStream_t)stream, dev_boards, dev_side, dev_move_count,
-                       dev_no_capture, dev_hist, n, dev_out);
+                       dev_no_capture, dev_hist, n, rules ? (int)rules->perpetual_check : 0, dev_out, dev_kind);
     return launch_status();
+}
+
+int xq_game_over_batch(const int8_t *dev_boards, const int8_t *dev_side, const int32_t *dev_move_count,
+                       const int32_t *dev_no_capture, const int8_t *dev_hist, int n, int8_t *dev_out, void *stream) {
+    return xq_game_over_batch_ex(dev_boards, dev_side, dev_move_count, dev_no_capture, dev_hist, n, nullptr, dev_out, nullptr, stream);
 }
 
 }  // extern "C"

@@ -112,24 +112,25 @@ __device__ __forceinline__ void init_board_lds(int8_t *b) {
 }
 
 // game.py:565-616 on an LDS position.  Leaves the ordered legal moves in `moves` (count in *cnt) whenever both
-// kings stand.  Wave-uniform result.
-__device__ inline bool wave_game_over(const int8_t *b, const int8_t (*ring)[XQ_BS], int side, int mc, int nocap,
-                                      MoveGenLds &mg, uint16_t *moves, int *cnt, int *winner, int *ovf) {
+// kings stand.  Wave-uniform result: 0 not over, 1 over, 4 over by the perpetual-check rule (`perpetual`: the engine's
+// xq_rules_opts flag) -- the values of a root's status word and a result's reason.
+__device__ inline int wave_game_over(const int8_t *b, const int8_t (*ring)[XQ_BS], int side, int mc, int nocap, bool perpetual,
+                                     MoveGenLds &mg, uint16_t *moves, int *cnt, int *winner, int *ovf) {
     const VMove none{-1, -1, 0};
     const int lane = lane_id();
     *cnt = 0;
-    if (find_king(b, none, 1) < 0) { *winner = -1; return true; }
-    if (find_king(b, none, -1) < 0) { *winner = 1; return true; }
+    if (find_king(b, none, 1) < 0) { *winner = -1; return 1; }
+    if (find_king(b, none, -1) < 0) { *winner = 1; return 1; }
     const int n = wave_movegen(b, side, mg, moves, ovf);
     *cnt = n;
-    if (n == 0) { *winner = -side; return true; }
-    if (nocap >= 120) { *winner = 0; return true; }
+    if (n == 0) { *winner = -side; return 1; }
+    if (nocap >= 120) { *winner = 0; return 1; }
     if (mc >= 200) {
         int red, black;
         wave_material(b, red, black);
         const int diff = red - black;
         *winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
-        return true;
+        return 1;
     }
     if (mc >= 6) {
         const int k = mc < XQ_HIST ? mc : XQ_HIST;
@@ -139,10 +140,21 @@ __device__ inline bool wave_game_over(const int8_t *b, const int8_t (*ring)[XQ_B
             const uint32_t x = lane < 23 ? (((const uint32_t *)h)[lane] ^ ((const uint32_t *)b)[lane]) : 0u;
             if (__ballot(x != 0u) == 0ull) ++rep;
         }
-        if (rep >= 3) { *winner = 0; return true; }
+        if (rep >= 3) {
+            const int w = perpetual ? wave_perpetual_winner(b, ring[0], XQ_BS, (mc - 1) % XQ_HIST, k, side) : 0;
+            *winner = w;
+            return w != 0 ? 4 : 1;
+        }
     }
     *winner = 2;
-    return false;
+    return 0;
+}
+
+// mcts.py:137-140: the value a terminal leaf backs up, from the view of the side that moved into it -- 0 for a draw, else 1: the
+// reference takes every decided leaf for a win of the mover.  Only the perpetual-check verdict (`over` == 4) can name the side
+// to move the winner (the mover's check completed its own perpetual): that leaf is the mover's loss.
+__device__ __forceinline__ double terminal_leaf_value(int over, int winner, int side) {
+    return winner == 0 ? 0.0 : (over == 4 && winner == side ? -1.0 : 1.0);
 }
 
 // game.py:528-550 on an LDS position + ring.  Wave-uniform scalars updated by reference.
@@ -298,7 +310,7 @@ __device__ __forceinline__ bool slot_new_game(const Dev &E, Slot &s, SelectLds &
         const int action = L.moves[pick];
         wave_make_move(L.root, L.rhist, action, s.side, s.mc, s.nocap);
         int c2, w2;
-        if (wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, L.mg, L.moves, &c2, &w2, &s.ovf)) {
+        if (wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, E.perpetual != 0, L.mg, L.moves, &c2, &w2, &s.ovf)) {
             init_board_lds(L.root);
             s.side = 1; s.mc = 0; s.nocap = 0;
             wave_sync();
@@ -337,7 +349,7 @@ __device__ __forceinline__ void slot_arena_opening(const Dev &E, Slot &s, Select
         if (s.lane == 0) rec[i] = (uint16_t)action;
         played = i + 1;
         int c2, w2;
-        if (wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, L.mg, L.moves, &c2, &w2, &s.ovf)) {
+        if (wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, E.perpetual != 0, L.mg, L.moves, &c2, &w2, &s.ovf)) {
             init_board_lds(L.root);
             s.side = 1; s.mc = 0; s.nocap = 0;
             wave_sync();
@@ -359,8 +371,8 @@ __device__ __forceinline__ int slot_root_request(const Dev &E, Slot &s, SelectLd
     const Tree &T = s.T;
     int cnt, winner;
     status = 0;
-    const bool done = wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, L.mg, L.moves, &cnt, &winner, &s.ovf);
-    if (done) status = 1;
+    const int done = wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, E.perpetual != 0, L.mg, L.moves, &cnt, &winner, &s.ovf);
+    if (done) status = done;                               // 1, or 4: decided by the perpetual-check rule
     else if (arena && s.mc >= E.cfg.max_game_length) {     // train.py:477,494-496: not over after max plies => draw
         winner = 0;
         status = 2;
@@ -729,8 +741,10 @@ constexpr int WAVES_PER_WG = 4;
 // waves per SIMD: left alone, the two with CAP take 256 VGPRs plus a few AGPRs and halve their occupancy.  Headroom of the
 // unpinned instances: <0,1,0> and <1,1,0> stand at 255 of the 256 VGPRs that two waves allow, the others at 244 / 245, so a
 // change to a shared helper wants the resource table regenerated (profiles/r12_gumbel_kernel_resource_usage.txt).  The GUMBEL
-// instance is held to two waves like the FORCED ones.
-#define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu((FORCED || GUMBEL) ? 2 : 0, (FORCED || GUMBEL) ? 2 : 0)))
+// instance is held to two waves like the FORCED ones, and so is the AROPEN one since the perpetual-check rule joined
+// wave_game_over: left alone it took 255 VGPRs plus 2 AGPRs and one wave; held, 255 VGPRs, no spill, no scratch
+// (profiles/r14_perpetual_check_kernel_resource_usage.txt; the unpinned instances now stand at 253 to 256).
+#define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu((FORCED || GUMBEL || AROPEN) ? 2 : 0, (FORCED || GUMBEL || AROPEN) ? 2 : 0)))
 #endif
 // REUSE (tree reuse): at the end of a move the chosen child and the old allocation mark are handed to k_reroot and
 // k_expand<true> of the same step (GI_RR_NODE / GI_RR_MARK).
@@ -858,10 +872,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
         const Leaf lf = wave_descend<false, FORCED, GUMBEL>(E, s, L, nullptr, rootP, fp_k, path);
         s.d_depth += (unsigned)lf.depth;
         int cnt, winner;
-        const bool term = wave_game_over(L.board, L.hist, lf.side, lf.mc, lf.nocap, L.mg, L.moves, &cnt, &winner, &s.ovf);
+        const int term = wave_game_over(L.board, L.hist, lf.side, lf.mc, lf.nocap, E.perpetual != 0, L.mg, L.moves, &cnt, &winner, &s.ovf);
         if (term) {
             wave_sync_mem();   // path[] stores of lane 0 must be visible to the other lanes
-            wave_backup<false>(T, nullptr, path, lf.depth, winner == 0 ? 0.0 : 1.0);   // mcts.py:137-140
+            wave_backup<false>(T, nullptr, path, lf.depth, terminal_leaf_value(term, winner, lf.side));   // mcts.py:137-140
             wave_sync_mem();   // the next descent reads N/W written here by other lanes
             s.sims_done += 1; s.d_sims += 1; s.d_term += 1;
             if (CAP && !full_move) d_fast_sims += 1;
@@ -1399,10 +1413,10 @@ __global__ __launch_bounds__(64) void k_select_multi(Dev E, Mx X, float *__restr
         if (__ballot(lane < npend && my_node == lf.node) != 0ull) { d_coll += 1; phase = PH_WAIT_LEAF; break; }
         s.d_depth += (unsigned)lf.depth;
         int cnt, winner;
-        const bool term = wave_game_over(L.board, L.hist, lf.side, lf.mc, lf.nocap, L.mg, L.moves, &cnt, &winner, &s.ovf);
+        const int term = wave_game_over(L.board, L.hist, lf.side, lf.mc, lf.nocap, E.perpetual != 0, L.mg, L.moves, &cnt, &winner, &s.ovf);
         if (term) {
             wave_sync_mem();   // path[] stores of lane 0 must be visible to the other lanes
-            wave_backup<false>(T, nullptr, pathj, lf.depth, winner == 0 ? 0.0 : 1.0);   // mcts.py:137-140
+            wave_backup<false>(T, nullptr, pathj, lf.depth, terminal_leaf_value(term, winner, lf.side));   // mcts.py:137-140
             wave_sync_mem();   // the next descent reads N/W written here by other lanes
             s.sims_done += 1; s.d_sims += 1; s.d_term += 1;
             // the bound on terminal simulations per launch, for k_select's reason

@@ -15,6 +15,7 @@ struct Opts {
     const xq_forced_playouts *forced;
     const xq_gumbel *gumbel;
     const xq_arena_opts *arena;
+    const xq_rules_opts *rules;     // absent from an initialiser: NULL, the reference's rules
 };
 
 struct Layout {
@@ -121,8 +122,14 @@ bool arena_ok(const xq_engine_config *c, const xq_arena_opts *ar) {
     return ar->first_game >= 0 && ar->first_game <= 0x7FFFFFFF - c->n_games;
 }
 
+// rules options: perpetual_check 0 or 1, reserved words zero; they go with every mode and every other option
+bool rules_ok(const xq_rules_opts *r) {
+    return (r->perpetual_check == 0 || r->perpetual_check == 1) && r->reserved[0] == 0 && r->reserved[1] == 0 && r->reserved[2] == 0;
+}
+
 // every option check, in the order the entry points have always refused in; an absent option passes
 bool opts_ok(const xq_engine_config *c, const Opts &o) {
+    if (o.rules && !rules_ok(o.rules)) return false;
     if (!config_ok(c) || !leaves_ok(c, o.K) || !flags_ok(c, o.K, o.flags)) return false;
     if (o.cap && !cap_ok(c, o.K, o.cap)) return false;
     if (o.forced && !forced_ok(c, o.K, o.forced)) return false;
@@ -214,7 +221,8 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
     eng->cfg = *cfg;
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
     eng->pad0 = (K > 1 ? K : 0) | (int)(o.flags << 16) | (o.cap ? PAD0_CAP : 0) | (o.forced ? PAD0_FORCED : 0) |
-                (o.gumbel ? PAD0_GUMBEL : 0) | (o.arena ? PAD0_ARENA : 0);
+                (o.gumbel ? PAD0_GUMBEL : 0) | (o.arena ? PAD0_ARENA : 0) |
+                (o.rules && o.rules->perpetual_check ? PAD0_PERPETUAL : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -302,6 +310,12 @@ size_t xq_engine_workspace_bytes_ar(const xq_engine_config *cfg, int leaves_per_
     return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena});
 }
 
+size_t xq_engine_workspace_bytes_ru(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules) {
+    return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules});
+}
+
 int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out) {
     if (k < 1 || k > XQ_MAXM || num_simulations < 1 || num_simulations > 65535 || !host_out) return XQ_ERR_ARG;
     gz_considered_visits(k, num_simulations, host_out);
@@ -343,6 +357,12 @@ int xq_engine_init_ar(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena, void *ws,
                       size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
     return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena}, ws, ws_bytes, dev_inject, stream);
+}
+
+int xq_engine_init_ru(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
+    return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules}, ws, ws_bytes, dev_inject, stream);
 }
 
 int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *stream) {

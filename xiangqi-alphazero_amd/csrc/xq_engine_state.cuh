@@ -51,6 +51,8 @@ enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_
 
 enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM = 3 };
 
+constexpr int PAD0_PERPETUAL = 1 << 26;     // pad0 of the handle (encoding below): "perpetual-check rule on"
+
 // Device view of the engine (passed by value to kernels)
 struct Dev {
     xq_engine_config cfg;
@@ -70,6 +72,7 @@ struct Dev {
     const double *sqrt_tab;
     double *mnoise;
     int32_t *req;                   // [G] legal moves of the evaluation each slot asked for this step (0: none)
+    int perpetual;                  // xq_rules_opts.perpetual_check of xq_engine_init_ru (wave-uniform: a kernel argument)
 };
 
 Dev make_dev(const xq_engine *e) {
@@ -85,6 +88,7 @@ Dev make_dev(const xq_engine *e) {
     d.started = (unsigned long long *)((char *)e->p[P_CNT] + 16);
     d.stats = (unsigned long long *)e->p[P_STATS]; d.inject = (const uint64_t *)e->p[P_INJECT];
     d.sqrt_tab = (const double *)e->p[P_SQRT]; d.mnoise = (double *)e->p[P_MNOISE]; d.req = (int32_t *)e->p[P_REQ];
+    d.perpetual = (e->pad0 & PAD0_PERPETUAL) != 0;
     return d;
 }
 
@@ -137,7 +141,7 @@ __host__ __device__ inline ArOff ar_off(size_t G, size_t S) {
 
 // pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
 // flag bits "playout cap on" (xq_engine_init_cap), "forced playouts on" (xq_engine_init_fp) and "Gumbel root search on"
-// (xq_engine_init_gz) and "arena options on" (xq_engine_init_ar)
+// (xq_engine_init_gz), "arena options on" (xq_engine_init_ar) and "perpetual-check rule on" (xq_engine_init_ru)
 constexpr int PAD0_CAP = 1 << 30;
 constexpr int PAD0_FORCED = 1 << 29;
 constexpr int PAD0_GUMBEL = 1 << 28;

@@ -371,6 +371,37 @@ __device__ __forceinline__ void wave_material(const int8_t *b, int &red, int &bl
     black = wave_sum(k);
 }
 
+// What ended a game, in the order is_game_over tests (game.py:565-616); 6 only under the perpetual-check rule
+enum : int { XQ_OVER_NONE = 0, XQ_OVER_KING = 1, XQ_OVER_NO_MOVE = 2, XQ_OVER_NO_CAPTURE = 3, XQ_OVER_PLY200 = 4,
+             XQ_OVER_REPETITION = 5, XQ_OVER_PERPETUAL = 6 };
+
+// The opt-in perpetual-check rule (include/xq_hip.h, xq_rules_opts) for a position whose repetition test has fired (three or
+// more of the last k <= XQ_HIST pre-move boards equal the current board `b`); one copy for wave_game_over (xq_engine.hip) and
+// k_game_over (xq_batch.hip).  Entry e, the board e + 1 plies ago, is row (newest - e) mod XQ_HIST of `hist` (rows `stride`
+// bytes apart, LDS or global); `side` is to move in `b`, so by ply parity -side is to move in the even entries and side in the
+// odd ones.  Returns the winner: the side that did NOT check on every one of its moves of the span (entries 0 .. E, E the
+// oldest entry equal to b) when exactly one side did, else 0.  Wave-uniform; all 64 lanes call it together.
+// At most 13 wave_in_check calls, in a branch almost no position enters.  Inlined: as a __noinline__ function the call's
+// register convention cost the select kernels more than the body does (three instances lost a wave, two began to spill).
+__device__ __forceinline__ int wave_perpetual_winner(const int8_t *b, const int8_t *hist, int stride, int newest, int k,
+                                                         int side) {
+    const int lane = lane_id();
+    bool other_checks = wave_in_check(b, side);      // every move of -side in the span gave check
+    bool side_checks = true;                         // every move of side did
+    bool other_span = other_checks, side_span = true;    // the same up to the oldest match so far
+    for (int e = 0; e < k; ++e) {
+        const int8_t *h = hist + ((newest - e + XQ_HIST) % XQ_HIST) * stride;
+        const bool c = wave_in_check(h, (e & 1) ? side : -side);
+        if (e & 1) other_checks = other_checks && c;
+        else side_checks = side_checks && c;
+        bool diff = h[lane] != b[lane];
+        if (lane + 64 < 90) diff = diff || (h[lane + 64] != b[lane + 64]);
+        if (__ballot(diff) == 0ull) { other_span = other_checks; side_span = side_checks; }
+    }
+    if (other_span == side_span) return 0;
+    return other_span ? side : -side;
+}
+
 // game.py:618-640 -- 15 planes, absolute orientation, plane 14 = all ones iff red to move
 __device__ __forceinline__ void wave_encode(const int8_t *b, int player, float *out) {
     const int lane = lane_id();

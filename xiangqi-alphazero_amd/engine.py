@@ -66,6 +66,12 @@ starts game `first_game + slot` with `opening_plies` random legal plies drawn fo
 opening with colours swapped, and offers the per-model packed step: `compact_arena()` packs the waiting slots into two buffer sets
 (`arena_packed[0]`: the new model's slots, `arena_packed[1]`: the old model's), `expand_packed_arena()` scatters both models'
 outputs back.  `arena_openings()` reads what was played.  K = 1, none of the other options.
+
+With `perpetual_check=True` (opt-in; xq_engine_init_ru) the side that checks through a repetition loses:
+where the reference calls three repetitions in the 12-board window a draw, the side whose every move of the repetition span gave
+check loses when the other side's did not.  The verdict holds at the root, in the real game and at the leaves of the search; a
+game it decides has `reason` 4 in its result (1 rules, 2 max_game_length adjudication, 3 resign, 4 rules: repetition, perpetual
+check).  Every mode, every other option.
 """
 from __future__ import annotations
 
@@ -118,11 +124,17 @@ def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
 
 # What `parse_engine_options` returns: the arguments every xq_engine_workspace_bytes_* / xq_engine_init_* call takes after the
 # config, the four structs as ctypes structures or None (the C side's NULL)
-EngineOptions = collections.namedtuple("EngineOptions", "K flags cap forced gumbel arena")
+class EngineOptions(collections.namedtuple("EngineOptions", "K flags cap forced gumbel arena")):
+    # the tuple is the argument list of xq_engine_*_ar; `rules` (hip.RulesOpts or None) is what xq_engine_*_ru take after it
+    rules = None
+
+
+RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_game_over, and its perpetual-check verdict
 
 
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
-                         forced_playouts=None, gumbel=None, arena_opts=None, eval_cache_entries: int = 0) -> EngineOptions:
+                         forced_playouts=None, gumbel=None, arena_opts=None, eval_cache_entries: int = 0,
+                         perpetual_check: bool = False) -> EngineOptions:
     """The engine options of `SelfPlayEngine` checked and turned into the C structs; needs no GPU.  Every rule of the header's
     refusal lists (include/xq_hip.h; opts_ok in csrc/xq_engine_setup.hip) is refused here first, with a message that names the
     option; tests/test_engine_options.py holds the two side by side."""
@@ -207,16 +219,24 @@ def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tre
         raise hip.XqError("leaves_per_step > 1 cannot be combined with an evaluation cache (eval_cache_entries > 0)")
     if K > 1 and int(cfg.manual_moves) == 2:
         raise hip.XqError("leaves_per_step > 1 is not available for arena games (manual_moves = 2)")
-    return EngineOptions(K, hip.ENGINE_TREE_REUSE if tree_reuse else 0, cap, forced, gz, ar)
+    if perpetual_check not in (False, True, 0, 1):
+        raise hip.XqError(f"perpetual_check must be a bool, got {perpetual_check!r}")
+    opts = EngineOptions(K, hip.ENGINE_TREE_REUSE if tree_reuse else 0, cap, forced, gz, ar)
+    if perpetual_check:                                # a verdict, not a search option: it goes with every mode and option
+        opts.rules = hip.RulesOpts(1)
+    return opts
 
 
 class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
-                 tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None):
-        K, flags, cap, forced, gz, ar = parse_engine_options(
+                 tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
+                 perpetual_check: bool = False):
+        opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
-            gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries)
+            gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check)
+        K, flags, cap, forced, gz, ar = opts
+        rules = opts.rules
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
@@ -229,11 +249,12 @@ class SelfPlayEngine:
         self.forced_playouts = None if forced is None else float(np.float32(forced.k))   # k as the kernels use it
         self.gumbel = None if gz is None else (gz.considered, float(np.float32(gz.c_visit)), float(np.float32(gz.c_scale)))
         self.arena_opts = None if ar is None else (ar.opening_plies, ar.first_game)
+        self.perpetual_check = rules is not None
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         # every entry point is the widest one with NULL for the options it does not take (include/xq_hip.h)
-        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar)]
-        nbytes = self.lib.xq_engine_workspace_bytes_ar(C.byref(cfg), K, flags, *refs)
+        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules)]
+        nbytes = self.lib.xq_engine_workspace_bytes_ru(C.byref(cfg), K, flags, *refs)
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
@@ -249,8 +270,8 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            hip.check(self.lib.xq_engine_init_ar(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
-                                                 hip.stream_ptr(self.device)), "xq_engine_init_ar")
+            hip.check(self.lib.xq_engine_init_ru(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
+                                                 hip.stream_ptr(self.device)), "xq_engine_init_ru")
         # zero-copy int32 view of the per-slot state words (columns hip.GI_*: side to move of the REAL game, move_count, phase,
         # simulations done): host-side policies such as the arena's model choice read it between stages
         gi_off = int(self.h.p[hip.P_GI]) - int(self.ws.data_ptr())
@@ -638,9 +659,11 @@ class SelfPlayEngine:
                     prior_kind=int(kind.value), root_visits=rv.value, sims_done=sd.value)
 
 
-def arena_engine(cfg: hip.EngineConfig, device, opening_plies: int, first_game: int, inject=None) -> SelfPlayEngine:
+def arena_engine(cfg: hip.EngineConfig, device, opening_plies: int, first_game: int, inject=None,
+                 perpetual_check: bool = False) -> SelfPlayEngine:
     """The arena's engine with arena options (paired openings from game index `first_game`, the per-model packed step)."""
-    return SelfPlayEngine(cfg, device, inject=inject, arena_opts=(int(opening_plies), int(first_game)))
+    return SelfPlayEngine(cfg, device, inject=inject, arena_opts=(int(opening_plies), int(first_game)),
+                          perpetual_check=perpetual_check)
 
 
 action_probs_dense = dense_pi   # the reference's dense pi (mcts.py:190-206) from compact (action, visit) pairs

@@ -68,6 +68,8 @@ GI_MC = 1          # mirrors GI_MC of enum Gi: its move count
 GI_PHASE = 3       # mirrors GI_PHASE of enum Gi
 GI_SIMS = 4        # mirrors GI_SIMS of enum Gi: simulations done
 GI_ALLOC = 7       # mirrors GI_ALLOC of enum Gi: the tree's allocation mark
+GI_RSTATUS = 11    # mirrors GI_RSTATUS of enum Gi: the root's terminal status (0 searched, 1 rules, 2 max length, 4 perpetual check)
+GI_RWINNER = 12    # mirrors GI_RWINNER of enum Gi: the winner that goes with a non-zero status
 GI_RNG0 = 14       # mirrors GI_RNG0 of enum Gi: the first of the four stream counters
 PH_HOLD = 7        # mirrors PH_HOLD of enum Phase in csrc/xq_engine_state.cuh
 
@@ -107,6 +109,15 @@ class Gumbel(C.Structure):
 class ArenaOpts(C.Structure):
     """xq_arena_opts: arena options (xq_engine_init_ar): opening plies R of the paired random openings, game index of slot 0."""
     _fields_ = [("opening_plies", C.c_int32), ("first_game", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class RulesOpts(C.Structure):
+    """xq_rules_opts: rules options (xq_engine_init_ru, xq_game_over_batch_ex): the side that checks through a repetition loses."""
+    _fields_ = [("perpetual_check", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+# what ended a game, xq_game_over_batch_ex's dev_kind
+OVER_KINDS = ("not_over", "king_missing", "no_legal_move", "no_capture", "ply_200", "repetition_draw", "perpetual_check")
 
 
 class PackedBuffers(C.Structure):
@@ -149,6 +160,7 @@ def lib():
     L.xq_material_batch.argtypes = [vp, i32, vp, vp]
     L.xq_apply_moves_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
     L.xq_game_over_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
+    L.xq_game_over_batch_ex.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(RulesOpts), vp, vp, vp]
     L.xq_engine_workspace_bytes.argtypes = [C.POINTER(EngineConfig)]
     L.xq_engine_workspace_bytes.restype = C.c_size_t
     L.xq_engine_init.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), vp, C.c_size_t, vp, vp]
@@ -179,6 +191,9 @@ def lib():
     L.xq_engine_workspace_bytes_ar.restype = C.c_size_t
     L.xq_engine_init_ar.argtypes = [C.POINTER(Engine), C.POINTER(EngineConfig), i32, C.c_uint, C.POINTER(PlayoutCap),
                                     C.POINTER(ForcedPlayouts), C.POINTER(Gumbel), C.POINTER(ArenaOpts), vp, C.c_size_t, vp, vp]
+    L.xq_engine_workspace_bytes_ru.argtypes = L.xq_engine_workspace_bytes_ar.argtypes + [C.POINTER(RulesOpts)]
+    L.xq_engine_workspace_bytes_ru.restype = C.c_size_t
+    L.xq_engine_init_ru.argtypes = L.xq_engine_init_ar.argtypes[:8] + [C.POINTER(RulesOpts)] + L.xq_engine_init_ar.argtypes[8:]
     L.xq_engine_arena_openings.argtypes = [C.POINTER(Engine), C.POINTER(vp), C.POINTER(vp)]
     L.xq_engine_compact_arena.argtypes = [C.POINTER(Engine), vp, vp]
     L.xq_engine_packed_arena.argtypes = [C.POINTER(Engine), C.POINTER(PackedBuffers)]
@@ -259,7 +274,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_init_ex", "xq_engine_drop_reroots", "xq_engine_workspace_bytes_cap", "xq_engine_init_cap",
            "xq_engine_workspace_bytes_fp", "xq_engine_init_fp", "xq_engine_workspace_bytes_gz", "xq_engine_init_gz",
            "xq_gumbel_considered_visits_host", "xq_engine_workspace_bytes_ar", "xq_engine_init_ar", "xq_engine_arena_openings",
-           "xq_engine_compact_arena", "xq_engine_packed_arena", "xq_engine_expand_packed_arena"]
+           "xq_engine_compact_arena", "xq_engine_packed_arena", "xq_engine_expand_packed_arena",
+           "xq_engine_workspace_bytes_ru", "xq_engine_init_ru", "xq_game_over_batch_ex"]
 
 
 def check(rc: int, what: str):
@@ -344,6 +360,21 @@ def game_over(boards, side, move_count, no_capture, hist):
         check(lib().xq_game_over_batch(_dev(boards), _dev(side), _dev(move_count), _dev(no_capture), _dev(hist), n,
                                        _dev(out), stream_ptr(boards.device)), "xq_game_over_batch")
     return out
+
+
+def game_over_batch(boards, side, move_count, no_capture, hist, perpetual_check: bool = False, return_kind: bool = False):
+    """`game_over` through xq_game_over_batch_ex: `perpetual_check` turns the perpetual-check rule on (xq_rules_opts; off: NULL
+    rules, `game_over`'s bytes); `return_kind` adds uint8[n], what ended each game (index into OVER_KINDS)."""
+    n = boards.shape[0]
+    out = torch.zeros((n, 2), dtype=torch.int8, device=boards.device)
+    kind = torch.zeros(n, dtype=torch.uint8, device=boards.device) if return_kind else None
+    rules = RulesOpts(1) if perpetual_check else None
+    if n:
+        check(lib().xq_game_over_batch_ex(_dev(boards), _dev(side), _dev(move_count), _dev(no_capture), _dev(hist), n,
+                                          None if rules is None else C.byref(rules), _dev(out),
+                                          None if kind is None else _dev(kind), stream_ptr(boards.device)),
+              "xq_game_over_batch_ex")
+    return (out, kind) if return_kind else out
 
 
 def bias_act_(y: torch.Tensor, bias: torch.Tensor, residual=None, relu: bool = True) -> torch.Tensor:

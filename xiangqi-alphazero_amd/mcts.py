@@ -13,6 +13,9 @@ is evaluated on the GPU.  With `add_noise=True` the root noise comes from the de
 `leaves_per_step = K > 1` (opt-in, K <= 64) batches up to K leaves per position and step under virtual loss
 (engine.SelfPlayEngine): a search of S simulations takes about S / K + 1 steps instead of S + 1.  It is knowingly not the
 reference's sequential search (the visit counts differ); K = 1 is.
+
+`perpetual_check=True` (opt-in) searches under the perpetual-check rule (engine.SelfPlayEngine): a
+repetition one side forced by checking on every move is that side's loss at the root and at every leaf, not a draw.
 """
 from __future__ import annotations
 
@@ -26,11 +29,12 @@ from .sample_format import ACTION_SPACE, dense_pi
 
 class MCTS:
     def __init__(self, model, num_simulations: int = 200, c_puct: float = 1.5, device: str = "cuda",
-                 evaluator_kind: str = "auto", seed: int = 0, leaves_per_step: int = 1):
+                 evaluator_kind: str = "auto", seed: int = 0, leaves_per_step: int = 1, perpetual_check: bool = False):
         if not 1 <= int(leaves_per_step) <= 64:
             from .hip import XqError
             raise XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
         self.leaves_per_step = int(leaves_per_step)
+        self.perpetual_check = bool(perpetual_check)
         self.model = model
         self.num_simulations = num_simulations
         self.c_puct = c_puct
@@ -55,7 +59,8 @@ class MCTS:
             cfg = engine.make_config(n, self.num_simulations, c_puct=self.c_puct, add_noise=add_noise, manual_moves=1,
                                      seed=self.seed)
             self._engines[key] = engine.SelfPlayEngine(cfg, self.device, evaluator=self.evaluator,
-                                                       leaves_per_step=self.leaves_per_step)
+                                                       leaves_per_step=self.leaves_per_step,
+                                                       perpetual_check=self.perpetual_check)
         return self._engines[key]
 
     def search_many(self, games: Sequence, temperature: float = 1.0, add_noise: bool = True) -> List[np.ndarray]:

@@ -25,7 +25,8 @@ _CFG_KEYS = ("num_simulations", "c_puct", "temperature_threshold", "max_game_len
 def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[int] = None, seed: int = 0, rank: int = 0,
               evaluator_kind: str = "hip", poll_every: int = 64, device_records: bool = False, use_graph: bool = True,
               eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None,
-              tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None):
+              tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None,
+              perpetual_check: Optional[bool] = None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -44,7 +45,10 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     `gumbel` = (m, c_visit, c_scale) (None: `config.gumbel_considered`, absent or 0 = off, with `config.gumbel_c_visit`, default
     50, and `config.gumbel_c_scale`, default 1.0) replaces the root rule by Gumbel top-m sampling with sequential halving and
     the samples' visit counts by the quantised improved policy (stats `gumbel_moves`, `gumbel_considered`, `gumbel_offprior`,
-    `gumbel`); it needs K = 1 and none of tree reuse, playout cap and forced playouts."""
+    `gumbel`); it needs K = 1 and none of tree reuse, playout cap and forced playouts.
+    `perpetual_check` (None: `config.perpetual_check_loses`, absent = off) plays under the perpetual-check rule: the side that
+    checks through a repetition loses instead of drawing (stats `perpetual_check`, `perpetual_check_games`: the finished games
+    with reason 4).  It goes with every other option; gate under the same rule (arena.evaluate_models)."""
     if eval_cache_entries is None:
         eval_cache_entries = int(getattr(config, "eval_cache_entries", 0) or 0)
     if leaves_per_step is None:
@@ -65,6 +69,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
         if gm:
             gcv, gcs = getattr(config, "gumbel_c_visit", None), getattr(config, "gumbel_c_scale", None)
             gumbel = (gm, 50.0 if gcv is None else float(gcv), 1.0 if gcs is None else float(gcs))
+    if perpetual_check is None:
+        perpetual_check = bool(getattr(config, "perpetual_check_loses", False))
     slots = int(n_slots or min(num_games, 8192))
     slots = max(1, min(slots, num_games))
     ev, ev_name = evaluator.make_evaluator(model, device, evaluator_kind)
@@ -77,7 +83,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
         max_out_samples=num_games * 201, max_out_results=num_games + 8)
     eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries,
                                 leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
-                                forced_playouts=forced_playouts, gumbel=gumbel)
+                                forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check)
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -98,6 +104,11 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     st["playout_cap"] = eng.playout_cap                # None, or (full_search_prob, fast_simulations)
     st["forced_playouts"] = eng.forced_playouts        # None, or k
     st["gumbel"] = eng.gumbel                          # None, or (m, c_visit, c_scale)
+    st["perpetual_check"] = eng.perpetual_check
+    if device_records:
+        st["perpetual_check_games"] = int((results[:, 9] == 4).sum().item()) if len(results) else 0   # byte 9: reason
+    else:
+        st["perpetual_check_games"] = int((results["reason"] == 4).sum())
     st.setdefault("eval_cache_probes", 0)              # the cache's keys are present (0) when it is off
     st.setdefault("eval_cache_hits", 0)
     if eng.capture_error:
@@ -110,17 +121,20 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
                        return_compact: bool = False, eval_cache_entries: Optional[int] = None,
                        leaves_per_step: Optional[int] = None,
                        tree_reuse: Optional[bool] = None, playout_cap=None,
-                       forced_playouts: Optional[float] = None, gumbel=None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
+                       forced_playouts: Optional[float] = None, gumbel=None,
+                       perpetual_check: Optional[bool] = None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
     for k in _CFG_KEYS + ("num_games_per_iter",):
         if not hasattr(config, k):
             raise AttributeError(f"config lacks '{k}' (see training/train.py:55-111)")
     num_games = int(config.num_games_per_iter)
     if leaves_per_step is None:
         leaves_per_step = int(getattr(config, "leaves_per_step", 1) or 1)   # a reference TrainingConfig has no such key
+    if perpetual_check is None:                        # read once, here: a reference TrainingConfig has no such key
+        perpetual_check = bool(getattr(config, "perpetual_check_loses", False))
     samples, results, st, elapsed = run_games(model, config, num_games, gpu_device, n_slots, seed,
                                               eval_cache_entries=eval_cache_entries, leaves_per_step=leaves_per_step,
                                               tree_reuse=tree_reuse, playout_cap=playout_cap,
-                                              forced_playouts=forced_playouts, gumbel=gumbel)
+                                              forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check)
     all_data, per_game = to_reference_tuples(samples, results, augment=True)
     wins = {1: 0, -1: 0, 0: 0}
     total_steps = 0
@@ -140,6 +154,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
         "forced_playouts": st["forced_playouts"],
         "gumbel_moves": st["gumbel_moves"], "gumbel_considered": st["gumbel_considered"],
         "gumbel_offprior": st["gumbel_offprior"], "gumbel": st["gumbel"],
+        "perpetual_check": st["perpetual_check"], "perpetual_check_games": st["perpetual_check_games"],
     }
     if return_compact:
         stats["compact_samples"], stats["compact_results"] = samples, results

@@ -49,6 +49,9 @@ class AlphaZeroLoop:
         self.rank = dist.get_rank() if self.grouped else 0
         self.seed = seed
         self.evaluator_kind = evaluator_kind
+        # the perpetual-check rule (config.perpetual_check_loses; absent: off), read once: self-play and the arena gate get this
+        # one value, so a loop never trains under one rule and gates under the other
+        self.perpetual_check = bool(getattr(config, "perpetual_check_loses", False))
         torch.manual_seed(seed)                        # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -81,7 +84,8 @@ class AlphaZeroLoop:
                                                     leaves_per_step=int(getattr(self.config, "leaves_per_step", 1) or 1),
                                                     # forced playouts too (config.forced_playouts_k; absent or 0: off): the
                                                     # arena (arena.py) never takes it
-                                                    forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None)
+                                                    forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None,
+                                                    perpetual_check=self.perpetual_check)
         # the Gumbel root search (config.gumbel_considered, gumbel_c_visit, gumbel_c_scale; absent or 0: off) reaches the engine
         # through run_games, which reads those keys from the config it is handed; the arena never takes it either
         return samples, results
@@ -125,8 +129,9 @@ class AlphaZeroLoop:
             # paired random openings (opt-in): another seed every iteration, so successive gates see different openings
             seed = int(getattr(self.config, "arena_seed", 0) or 0) + self.iteration
             return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind,
-                                         seed=seed)
-        return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind)
+                                         seed=seed, perpetual_check=self.perpetual_check)
+        return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind,
+                                     perpetual_check=self.perpetual_check)
 
     def evaluate(self) -> dict:
         stats = self._arena()
