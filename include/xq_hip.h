@@ -478,6 +478,73 @@ int xq_engine_init_ru(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
                       const xq_rules_opts *rules, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream);
 
+/* Proven-result search (MCTS-solver; opt-in; solver == NULL or enabled = 0 is xq_engine_init_ru exactly, and xq_engine_init_ru is
+ * that call).  Exact result propagation as chess-like engines ship it (Winands et al., "Monte-Carlo Tree Search Solver", 2008;
+ * lc0's "sticky endgames"): the search learns that a position is decided, stops re-testing it, never prefers a move it has shown
+ * to lose and plays a move it has shown to win at once.  Outside the reference-parity contract, like the other opt-in options;
+ * off, every byte is as before.
+ * THE RULE.  Every tree node carries a state in {UNKNOWN, WIN, DRAW, LOSS}, seen from the side that MOVED INTO the node -- the view
+ * of its W.  New nodes are UNKNOWN.  A tree node has one path from the root, so the history-dependent verdicts (repetition,
+ * no-capture count, ply 200) are properties of the node.
+ * 1. TERMINAL LEAF.  When a descent ends on a node that the terminal test (xq_game_over_batch's rule, with the engine's rules
+ *    options) decides, the node's state is set from the TRUE result: DRAW if winner == 0, WIN if the winner is the side that moved
+ *    into the leaf, LOSS otherwise (ply 200's material rule and the perpetual-check rule can name the side to move the winner).
+ *    The value backed up is the state's exact value, +1 / 0 / -1.  This is NOT the reference's "every decided leaf is the mover's
+ *    win" (mcts.py:137-140), which an engine without the option keeps.
+ * 2. PROPAGATION, in xq_engine_select right after that backup, up the recorded path while a state changes.  For the parent p, if
+ *    UNKNOWN, of the node c whose state just changed: c WIN makes p LOSS; otherwise, if no child of p is UNKNOWN, p becomes DRAW
+ *    when some child is DRAW and WIN when every child is LOSS; otherwise propagation stops.  It also stops at a parent that is
+ *    already decided.  All of p's children exist from its expansion on.  The root takes part.
+ * 3. DESCENT.  A descent stops at the first NON-ROOT node whose state is not UNKNOWN: no terminal test, no evaluator request, the
+ *    node's exact value is backed up; it counts as a simulation and as a terminal simulation (also towards the bound of 48 per
+ *    launch).  At every level a child of state LOSS scores -infinity, unless the parent's own state is WIN (then every child is
+ *    LOSS; reachable only at the root; plain PUCT).  Everything else in the score, the first-maximum rule included, is unchanged.
+ * 4. EARLY END OF A MOVE.  Whenever a search looks at its root -- before every simulation, the first one after the root's expansion
+ *    or a re-root included, and AHEAD of the test of the budget, so a reused root that inherits its whole budget in visits, or a
+ *    win proven by the budget's last simulation, is covered too -- if some root child is WIN (equivalently: the root is LOSS), the
+ *    move ends at once.  c = the first such child in move order is played: no temperature and no draw of the uniform stream (a
+ *    playout cap's cap draw has already happened).  unspent = max(0, budget - sims_done); the unspent simulations are not run and
+ *    not counted in `sims`.  Search only (manual_moves = 1): the slot holds, with sims_done < num_simulations when unspent > 0.
+ * 5. THE COUNTS A MOVE ENDS WITH (self-play full and fast moves, arena moves).  v_i = 0 for a LOSS child when some child is not
+ *    LOSS, otherwise v_i = N_i; on an early end v_c += unspent; if every v_i is 0, v = N (nothing is taken away).  The sample's
+ *    visits[] and the move-choice weights use v: self-play takes its one uniform draw as always unless rule 4 applied; the arena
+ *    takes the first maximum of v.  A sample whose move rule 4 chose carries reserved1 = 1 (0 in every other sample).  A sample's
+ *    visits sum to AT MOST the budget.  The tree keeps its real N and W.
+ * 6. TREE REUSE.  Kept nodes keep their state through the re-root, the new root included (its other meta bits are rewritten).  A
+ *    reused root may already be decided; rules 3-5 cover it: a WIN root (the side to move has lost) is searched by plain PUCT over
+ *    its LOSS children, every simulation a stop.
+ * 7. UNCHANGED: the root request and its status, resignation, max_game_length adjudication, the z of samples, the evaluation cache
+ *    (decided nodes never ask), the perpetual-check rule (it only changes what rule 1 sees).
+ * The state lives in bits 12-13 of the node meta word (child count: bits 0-11, prior kind: bits 14-15); they are 0 on every engine
+ * without the option.  Counters (xq_engine_solver_stats_read; the engine's own statistics words are all taken), all 0 on a game
+ * where nothing is ever decided:
+ *   proven_nodes    states set, by rules 1 and 2          proven_stops    simulations that ended by rule 3
+ *   proven_moves    moves (search only: searches) ended by rule 4          unspent_sims    the sum of their unspent
+ *   removed_visits  the sum of N_i - v_i over rule 5's zeroed children
+ * Allowed: self-play with tree reuse, the playout cap and the evaluation cache in every combination; search only; arena games with
+ * and without arena options; the perpetual-check rule.  XQ_ERR_ARG before any launch (xq_engine_workspace_bytes_sv: 0): enabled
+ * outside {0, 1}, a non-zero reserved word; with enabled = 1: leaves_per_step > 1, Gumbel root search (its equal-visit candidates
+ * cannot skip a child), forced playouts; and whatever xq_engine_init_ru refuses.  A LOSS root without a WIN child (a defect) sets
+ * overflow bit 128 << 8.  Workspace: 64 bytes of counters per slot behind the engine's square-root table (behind the arena words
+ * with arena options); only solver engines grow, "solver on" lives in the handle (pad0, above the public flag bits).
+ * xq_engine_read_root_states: the states at the root of `slot` from the view of the SIDE TO MOVE there: child_state[i] (move order,
+ * XQ_MAXM entries, zero past the count) +1 this move wins, -1 it loses, 2 draw, 0 unknown; *root_state in the same code.  Returns
+ * the child count; XQ_ERR_ARG on an engine without the option.  Synchronises, as xq_engine_solver_stats_read does. */
+typedef struct xq_solver_opts { int32_t enabled; int32_t reserved[3]; } xq_solver_opts;
+typedef struct xq_solver_stats {
+    uint64_t proven_nodes, proven_stops, proven_moves, unspent_sims, removed_visits;
+    uint64_t reserved[3];
+} xq_solver_stats;
+size_t xq_engine_workspace_bytes_sv(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver);
+int xq_engine_init_sv(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, void *ws, size_t ws_bytes, const uint64_t *dev_inject,
+                      void *stream);
+int xq_engine_read_root_states(const xq_engine *eng, int slot, int8_t *child_state /* [XQ_MAXM] */, int8_t *root_state, void *stream);
+int xq_engine_solver_stats_read(const xq_engine *eng, xq_solver_stats *host_out, void *stream);
+
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 
 /* dev_policy[slot] = float32[8100]: network LOGITS (policy_is_probs = 0; softmax over all 8100 as

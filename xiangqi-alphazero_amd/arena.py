@@ -56,7 +56,7 @@ def _evaluate_subset(eng, ev, x, idx, policy_is_probs, dense, legal, value):
 def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_simulations: int, max_game_length: int,
                c_puct: float = 1.5, device="cuda", policy_is_probs: bool = False, first_game: int = 0,
                opening_plies: int = 0, seed: int = 0, packed: Optional[bool] = None, inject=None, info: Optional[dict] = None,
-               perpetual_check: bool = False):
+               perpetual_check: bool = False, solver: bool = False):
     """eval_*: evaluators in either protocol (`evaluate_legal`, or a callable float32[n,15,10,9] -> (policy
     float32[n,8100], value float32[n])); both must use the same one.  Plays games first_game .. first_game+eval_games-1
     of the arena (the new model is red in even games) and returns the results array ordered by game (slot == game -
@@ -64,18 +64,20 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
     Opt-in: `opening_plies` > 0 and `seed` give every pair of games its random opening; `packed` (None: yes with openings when
     both evaluators offer `live_rows`) takes the per-model packed step; `inject` (uint64 [games, 4, n], tests only) replaces the
     device draws; `info` (a dict) receives `openings`, `opening_counts`, `steps` (engine steps run) and the engine's `stats`;
-    `perpetual_check` builds the engine with the perpetual-check rule (results then may carry reason 4)."""
+    `perpetual_check` builds the engine with the perpetual-check rule (results then may carry reason 4); `solver` with the
+    proven-result search (a move shown to lose is not played while another is not, a move shown to win is
+    played at once; `info["stats"]` then carries the five solver counters)."""
     cfg = engine.make_config(eval_games, eval_simulations, c_puct=c_puct, max_game_length=max_game_length,
                              random_opening_moves=0, enable_resign=False, add_noise=False, games_target=eval_games,
                              manual_moves=2)
     opts = int(opening_plies) > 0 or bool(packed) or inject is not None or info is not None
     if not opts:
-        eng = engine.SelfPlayEngine(cfg, device, perpetual_check=perpetual_check)
+        eng = engine.SelfPlayEngine(cfg, device, perpetual_check=perpetual_check, solver=solver)
     else:
         if inject is not None:
             cfg.inject_len = int(np.asarray(inject).shape[-1])
         cfg.seed = int(seed)
-        eng = engine.arena_engine(cfg, device, opening_plies, first_game, inject, perpetual_check=perpetual_check)
+        eng = engine.arena_engine(cfg, device, opening_plies, first_game, inject, perpetual_check=perpetual_check, solver=solver)
     dev = eng.device
     new_is_red = ((torch.arange(eval_games, device=dev) + first_game) % 2 == 0)
     sparse = hasattr(eval_new, "evaluate_legal") and hasattr(eval_old, "evaluate_legal") and not policy_is_probs
@@ -203,7 +205,8 @@ def pair_statistics(winners) -> Dict[str, object]:
 
 
 def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind: str = "hip", group=None,
-                    seed: Optional[int] = None, perpetual_check: Optional[bool] = None) -> Dict[str, object]:
+                    seed: Optional[int] = None, perpetual_check: Optional[bool] = None,
+                    solver: Optional[bool] = None) -> Dict[str, object]:
     """Same stats dict as the reference (`new_wins, old_wins, draws, win_rate, model_updated`); reads
     `eval_games, eval_simulations, c_puct, max_game_length, eval_win_rate` from `config` (train.py:97-100).
     Under torch.distributed the games are split over the ranks and the winners all-gathered.
@@ -211,7 +214,8 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
     `seed` (None: `config.arena_seed`, absent: 0); `eval_games` must then be even, and the result adds `opening_plies`, `pairs`,
     `openings` (uint16 [games, R]), `win_rate_se` and `win_rate_ci95`.  The promotion rule is unchanged.
     `perpetual_check` (None: `config.perpetual_check_loses`, absent: off) plays the games under the perpetual-check rule; the
-    result then adds `perpetual_check` = True.  Off, `play_arena` is called as before."""
+    result then adds `perpetual_check` = True.  Off, `play_arena` is called as before.
+    `solver` (None: `config.mcts_solver`, absent: off) searches with proven results; the result then adds `solver` = True."""
     import torch.distributed as dist
     from . import distributed as xdist
     total = int(config.eval_games)
@@ -223,6 +227,10 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
     if perpetual_check is None:
         perpetual_check = bool(getattr(config, "perpetual_check_loses", False))
     rule = {"perpetual_check": True} if perpetual_check else {}
+    if solver is None:
+        solver = bool(getattr(config, "mcts_solver", False))
+    if solver:
+        rule["solver"] = True
     openings = np.zeros((total, max(plies, 0)), dtype=np.int64)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0

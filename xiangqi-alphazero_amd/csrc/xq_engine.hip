@@ -469,8 +469,10 @@ __device__ __forceinline__ void wave_prune_visits(const Dev &E, Slot &s, SelectL
 
 // End of a move: the sample (parallel_selfplay.py:97-107) and the sampled action, pi from visit counts (mcts.py:190-206).
 // full_move false (a fast move of the playout cap) stages no sample; pruned: the visits are wave_prune_visits' counts in
-// L.w_tmp.  Leaves child i's action in L.a_tmp[i]; the caller plays the returned action.
-__device__ __forceinline__ int slot_end_move(const Dev &E, Slot &s, SelectLds &L, bool full_move, bool pruned, int nch, int first) {
+// L.w_tmp (wave_prune_visits', or wave_solver_counts').  Leaves child i's action in L.a_tmp[i]; the caller plays the returned
+// action.  proven >= 0 (SOLVER, rule 4): child `proven` is played, no temperature, no uniform draw, the sample says reserved1 = 1.
+__device__ __forceinline__ int slot_end_move(const Dev &E, Slot &s, SelectLds &L, bool full_move, bool pruned, int nch, int first,
+                                             int proven = -1) {
     const Tree &T = s.T;
     const int lane = s.lane;
     const bool late = s.mc >= E.cfg.temperature_threshold;
@@ -485,6 +487,7 @@ __device__ __forceinline__ int slot_end_move(const Dev &E, Slot &s, SelectLds &L
             xq_sample *r = (xq_sample *)rec;
             r->side = (int8_t)s.side; r->z = 0; r->n_moves = (uint8_t)nch; r->late_temp = late ? 1 : 0;
             r->ply = (uint16_t)s.mc; r->slot = (uint32_t)s.slot; r->game_seq = (uint32_t)s.game_seq;
+            if (proven >= 0) r->reserved1 = 1;
         }
     }
     for (int i = lane; i < nch; i += 64) {
@@ -498,6 +501,10 @@ __device__ __forceinline__ int slot_end_move(const Dev &E, Slot &s, SelectLds &L
         L.w_tmp[i] = late ? (n > 0 ? pow((double)n, inv_t) : 0.0) : (double)n;
     }
     wave_sync();
+    if (proven >= 0) {
+        if (full_move) s.n_samples += 1;
+        return __builtin_amdgcn_readfirstlane((int)T.A[first + proven]);
+    }
     // np.random.choice walks the dense pi in ACTION-ID order: sort the (action, weight) pairs by id
     for (int i = lane; i < nch; i += 64) {
         const int a = L.a_tmp[i];
@@ -607,9 +614,82 @@ __device__ __forceinline__ int slot_end_move_gumbel(const Dev &E, Slot &s, Selec
     return __builtin_amdgcn_readfirstlane((int)T.A[first + bs_i]);
 }
 
+// SOLVER (proven-result search, xq_engine_init_sv; the rules are include/xq_hip.h's).  The exact value of a decided node, from
+// the view of the side that moved into it.
+__device__ __forceinline__ double state_value(int st) { return st == NS_WIN ? 1.0 : (st == NS_DRAW ? 0.0 : -1.0); }
+
+// Rule 2: the state of path[depth] has just become `cstate`; go up the recorded path while a state changes.  An UNKNOWN parent of
+// a WIN child is LOSS; otherwise, once no child is UNKNOWN, it is DRAW when some child is DRAW and WIN when every child is LOSS.
+// One wave pass over the parent's children (at most 128) per changed ancestor.  Returns the number of states set.
+__device__ __forceinline__ unsigned wave_propagate(const Tree &T, const int32_t *path, int depth, int cstate) {
+    const int lane = lane_id();
+    unsigned changed = 0;
+    for (int j = depth - 1; j >= 0; --j) {
+        const int p = __builtin_amdgcn_readfirstlane(path[j]);
+        const int pm = __builtin_amdgcn_readfirstlane((int)T.M[p]);
+        if (node_state(pm) != NS_UNKNOWN) break;
+        int ns = NS_LOSS;
+        if (cstate != NS_WIN) {
+            const int f = __builtin_amdgcn_readfirstlane(T.C[p]), nch = pm & XQ_CNT_MASK;
+            bool unk = false, drw = false;
+            for (int i = lane; i < nch; i += 64) {
+                const int st = node_state((int)T.M[f + i]);
+                unk = unk || st == NS_UNKNOWN;
+                drw = drw || st == NS_DRAW;
+            }
+            if (__ballot(unk) != 0ull) break;
+            ns = __ballot(drw) != 0ull ? NS_DRAW : NS_WIN;
+        }
+        if (lane == 0) T.M[p] = (uint16_t)(pm | (ns << XQ_STATE_SHIFT));
+        wave_sync_mem();   // the next level's pass reads this word from other lanes
+        changed += 1;
+        cstate = ns;
+    }
+    return changed;
+}
+
+// Rule 5: the counts a move ends with, into L.w_tmp (slot_end_move's lanes read back only what they wrote here): v_i = 0 for a
+// LOSS child when some child is not LOSS, else N_i; the proven child of an early end (or -1) gets the unspent simulations; if
+// every v_i would be 0, v = N.  Returns the visits taken away.
+__device__ __forceinline__ unsigned wave_solver_counts(const Tree &T, SelectLds &L, int nch, int first, int proven, int unspent) {
+    const int lane = lane_id();
+    int nonloss = 0, sum = 0, rem = 0;
+    for (int i = lane; i < nch; i += 64) {
+        const int n = T.N[first + i];
+        if (node_state((int)T.M[first + i]) == NS_LOSS) rem += n; else { nonloss = 1; sum += n; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { nonloss |= __shfl_xor(nonloss, off); sum += __shfl_xor(sum, off); rem += __shfl_xor(rem, off); }
+    const bool zero = nonloss != 0 && sum + unspent > 0;
+    for (int i = lane; i < nch; i += 64) {
+        int v = (zero && node_state((int)T.M[first + i]) == NS_LOSS) ? 0 : T.N[first + i];
+        if (i == proven) v += unspent;
+        L.w_tmp[i] = (double)v;
+    }
+    return zero ? (unsigned)__builtin_amdgcn_readfirstlane(rem) : 0u;
+}
+
+// REUSE: hand the chosen child c to k_reroot / k_expand<true> of this step when it was expanded and no drop
+// (xq_engine_drop_reroots) ran since this move began; L.a_tmp[i] is child i's action
+__device__ __forceinline__ void slot_hand_off(const Slot &s, const SelectLds &L, int nch, int first, int action) {
+    const Tree &T = s.T;
+    int32_t *gi = s.gi;
+    const int lane = s.lane;
+    int c = 0;
+    for (int base = 0; base < nch; base += 64) {
+        const unsigned long long b = __ballot(base + lane < nch && (int)L.a_tmp[base + lane] == action);
+        if (b) { c = first + base + (int)__builtin_ctzll(b); break; }
+    }
+    c = __builtin_amdgcn_readfirstlane(c);
+    const bool keep = c > 0 && __builtin_amdgcn_readfirstlane(T.C[c]) >= 0 &&
+                      __builtin_amdgcn_readfirstlane(gi[GI_RR_DROP]) == 0;
+    if (lane == 0) { gi[GI_RR_NODE] = keep ? c : 0; gi[GI_RR_MARK] = keep ? gi[GI_ALLOC] : 0; }
+}
+
 // The leaf a descent ends on, and the simulated position there (its board and ring are SelectLds.board / .hist)
 struct Leaf {
     int node, depth, side, mc, nocap;
+    int state;                              // SOLVER: the proven state of the node the descent stopped on (0: an ordinary leaf)
 };
 
 // One PUCT descent (mcts.py:126-153) from the root, replaying moves on the LDS board; the nodes passed go to path[0 .. depth].
@@ -620,11 +700,15 @@ struct Leaf {
 // (the sequential halving); they score rootP[i] = g_i + l_i plus, once visited, sigma(q_i), everyone else -infinity.  sigma needs
 // the maximum of the children's N first: one more pass over the (at most 128) counts and one more wave reduction, at that level only.
 //
+// SOLVER (proven-result search, xq_engine_init_sv): the descent stops at the first non-root node whose state is not UNKNOWN, and
+// a child of state LOSS scores -infinity unless the parent itself is WIN (every child LOSS: the root only, plain PUCT).  The
+// states ride in the meta words the descent reads anyway.
+//
 // One dependent round trip to memory per level: every lane reads, with its candidate child's N / W / P, that child's own
 // node words (children count + kind, first child, action) as well, so the winner's are already in a register when the arg-max
 // is known -- the next level starts from a lane read instead of three more dependent loads (tM -> tC/tN -> ... -> tA).  The
 // winner's N, read here, IS the next level's parent count.
-template <bool VL, bool FORCED, bool GUMBEL = false>
+template <bool VL, bool FORCED, bool GUMBEL = false, bool SOLVER = false>
 __device__ __forceinline__ Leaf wave_descend(const Dev &E, Slot &s, SelectLds &L, const int32_t *vl, const double *rootP, float fp_k,
                                              int32_t *path) {
     const Tree &T = s.T;
@@ -637,9 +721,12 @@ __device__ __forceinline__ Leaf wave_descend(const Dev &E, Slot &s, SelectLds &L
     int m = __builtin_amdgcn_readfirstlane((int)T.M[0]);
     int first = __builtin_amdgcn_readfirstlane(T.C[0]);
     int pn = __builtin_amdgcn_readfirstlane(VL ? T.N[0] + vl[0] : T.N[0]);
+    int stop = 0;
     for (;;) {
-        const int nch = m & 0x3FFF, kind = m >> 14;
+        const int nch = m & XQ_CNT_MASK, kind = m >> 14;
+        if (SOLVER && depth > 0 && node_state(m) != NS_UNKNOWN) { stop = node_state(m); break; }
         if (nch == 0) break;
+        const bool skip_loss = SOLVER && node_state(m) != NS_WIN;
         const double sqrtp = E.sqrt_tab[pn];
         const float sqrtp_f = (float)sqrtp, c_f = (float)E.cfg.c_puct;
         const double uni = 1.0 / (double)nch;
@@ -683,6 +770,7 @@ __device__ __forceinline__ Leaf wave_descend(const Dev &E, Slot &s, SelectLds &L
                     ucb = q + t;
                     if (FORCED && kind == 1 && n > 0 && (double)n * (double)n < ((double)fp_k * p) * (double)pn) ucb = INFINITY;
                 }
+                if (SOLVER && skip_loss && node_state(cm) == NS_LOSS) ucb = -INFINITY;
                 if (ucb > best) { best = ucb; best_i = i; c_m = cm; c_first = cf; c_n = n; c_a = ca; }
             }
         }
@@ -717,7 +805,7 @@ __device__ __forceinline__ Leaf wave_descend(const Dev &E, Slot &s, SelectLds &L
         if (lane == 0) path[depth] = child;
         node = child;
     }
-    return Leaf{node, depth, side, mc, nocap};
+    return Leaf{node, depth, side, mc, nocap, stop};
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -743,8 +831,10 @@ constexpr int WAVES_PER_WG = 4;
 // change to a shared helper wants the resource table regenerated (profiles/r12_gumbel_kernel_resource_usage.txt).  The GUMBEL
 // instance is held to two waves like the FORCED ones, and so is the AROPEN one since the perpetual-check rule joined
 // wave_game_over: left alone it took 255 VGPRs plus 2 AGPRs and one wave; held, 255 VGPRs, no spill, no scratch
-// (profiles/r14_perpetual_check_kernel_resource_usage.txt; the unpinned instances now stand at 253 to 256).
-#define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu((FORCED || GUMBEL || AROPEN) ? 2 : 0, (FORCED || GUMBEL || AROPEN) ? 2 : 0)))
+// (profiles/r14_perpetual_check_kernel_resource_usage.txt; the unpinned instances now stand at 253 to 256).  The SOLVER
+// instances are held to two waves as well (profiles/r15_solver_kernel_resource_usage.txt).
+#define XQ_SELECT_OCC \
+    __attribute__((amdgpu_waves_per_eu((FORCED || GUMBEL || AROPEN || SOLVER) ? 2 : 0, (FORCED || GUMBEL || AROPEN || SOLVER) ? 2 : 0)))
 #endif
 // REUSE (tree reuse): at the end of a move the chosen child and the old allocation mark are handed to k_reroot and
 // k_expand<true> of the same step (GI_RR_NODE / GI_RR_MARK).
@@ -761,7 +851,11 @@ constexpr int WAVES_PER_WG = 4;
 // sample's target.  Every other level is the PUCT of the other instances.
 // AROPEN (arena options, xq_engine_init_ar; one instance, <false, false, false, false, true>): a new game starts with its pair's
 // random opening (slot_arena_opening).  Everything after it is the arena game of the plain instance.
-template <bool REUSE, bool CAP = false, bool FORCED = false, bool GUMBEL = false, bool AROPEN = false>
+// SOLVER (proven-result search, xq_engine_init_sv; instances {REUSE} x {CAP}, the plain one for search only and arena games, and
+// one with AROPEN): tree nodes carry a proven state in their meta word (rules: include/xq_hip.h).  A terminal leaf sets its state
+// from the true result and backs up the exact value, wave_propagate carries it up the path, a descent stops at a decided node,
+// LOSS children are skipped, a root with a WIN child ends the move at once, and a move ends on the counts of wave_solver_counts.
+template <bool REUSE, bool CAP = false, bool FORCED = false, bool GUMBEL = false, bool AROPEN = false, bool SOLVER = false>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev E, float *__restrict__ nn_in) {
     __shared__ SelectLds Ls[WAVES_PER_WG];
     SelectLds &L = Ls[threadIdx.x >> 6];
@@ -799,6 +893,12 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
     // FORCED: k, a float32 widened at every use
     const float fp_k = FORCED ? __int_as_float(__builtin_amdgcn_readfirstlane(gi[GI_FP_K])) : 0.0f;
     unsigned d_gz_moves = 0, d_gz_cons = 0, d_gz_off = 0;      // GUMBEL only
+    // SOLVER: its counters are bumped in memory where the (rare) events happen -- five more wave-uniform words kept live across
+    // the loop cost the AROPEN instance a spilled VGPR
+    auto sv_add = [&](int word, unsigned v) {
+        if (lane == 0)
+            ((unsigned long long *)((char *)E.sqrt_tab + sv_off((size_t)E.cfg.n_games, (size_t)S, AROPEN)))[(size_t)slot * SV_WORDS + word] += v;
+    };
 
     lds_copy_dwords(L.root, E.board + (size_t)slot * XQ_BS, XQ_BS / 4);
     lds_copy_dwords(L.rhist, E.hist + (size_t)slot * XQ_HIST * XQ_BS, XQ_HIST * XQ_BS / 4);
@@ -836,11 +936,46 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
             break;
         }
         // ---- phase == PH_SEARCH
+        if (SOLVER && node_state(__builtin_amdgcn_readfirstlane((int)T.M[0])) == NS_LOSS) {
+            // rule 4, whenever a search looks at its root -- before every simulation, and before the test of the budget, so a
+            // reused root that inherits its whole budget plays its proven win too: some root child is WIN (what makes a root LOSS),
+            // the move ends at once on the first such child in move order; the unspent simulations are not run and not counted
+            const int nch = __builtin_amdgcn_readfirstlane((int)(T.M[0] & XQ_CNT_MASK));
+            const int first = __builtin_amdgcn_readfirstlane(T.C[0]);
+            int c = -1;
+            for (int base = 0; base < nch; base += 64) {
+                const unsigned long long b = __ballot(base + lane < nch && node_state((int)T.M[first + base + lane]) == NS_WIN);
+                if (b) { c = base + (int)__builtin_ctzll(b); break; }
+            }
+            c = __builtin_amdgcn_readfirstlane(c);
+            if (c < 0) { s.ovf |= 128; c = 0; }              // a LOSS root without a WIN child: a defect
+            const int unspent = budget > s.sims_done ? budget - s.sims_done : 0;
+            sv_add(SV_MOVES, 1u); sv_add(SV_UNSPENT, (unsigned)unspent);
+            if (manual) { phase = PH_HOLD; break; }
+            phase = PH_NEWPOS;
+            sv_add(SV_REMOVED, wave_solver_counts(T, L, nch, first, c, unspent));     // rule 5, arena moves included
+            if (arena) { slot_play(s, L, __builtin_amdgcn_readfirstlane((int)T.A[first + c])); continue; }
+            const int action = slot_end_move(E, s, L, full_move, true, nch, first, c);
+            if (REUSE) slot_hand_off(s, L, nch, first, action);
+            slot_play(s, L, action);
+            if (CAP && !full_move) d_fast_moves += 1;
+            continue;
+        }
         if (s.sims_done >= budget) {
             if (manual) { phase = PH_HOLD; break; }
-            const int nch = __builtin_amdgcn_readfirstlane((int)(T.M[0] & 0x3FFF));
+            const int nch = __builtin_amdgcn_readfirstlane((int)(T.M[0] & XQ_CNT_MASK));
             const int first = __builtin_amdgcn_readfirstlane(T.C[0]);
             phase = PH_NEWPOS;
+            if (SOLVER && arena) {                   // rule 5: the first maximum of v
+                sv_add(SV_REMOVED, wave_solver_counts(T, L, nch, first, -1, 0));
+                int32_t *v = (int32_t *)L.cdf;
+                for (int i = lane; i < nch; i += 64) v[i] = (int)L.w_tmp[i];
+                wave_sync();
+                int bn;
+                const int bi = wave_first_max(v, nch, bn);
+                slot_play(s, L, __builtin_amdgcn_readfirstlane((int)T.A[first + bi]));
+                continue;
+            }
             if (arena) { slot_arena_move(s, L, nch, first); continue; }
             if (GUMBEL && (__builtin_amdgcn_readfirstlane((int)T.M[0]) >> 14) == 3) {
                 unsigned cons, off;
@@ -849,33 +984,42 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                 slot_play(s, L, action);
                 continue;
             }
-            const bool pruned = FORCED && (__builtin_amdgcn_readfirstlane((int)T.M[0]) >> 14) == 1;
-            if (pruned) wave_prune_visits(E, s, L, rootP, fp_k, nch, first);
+            const bool pruned = SOLVER || (FORCED && (__builtin_amdgcn_readfirstlane((int)T.M[0]) >> 14) == 1);
+            if (SOLVER) sv_add(SV_REMOVED, wave_solver_counts(T, L, nch, first, -1, 0));
+            else if (pruned) wave_prune_visits(E, s, L, rootP, fp_k, nch, first);
             const int action = slot_end_move(E, s, L, full_move, pruned, nch, first);
-            if (REUSE) {
-                // hand the chosen child c to k_reroot / k_expand<true> of this step when it was expanded and no drop
-                // (xq_engine_drop_reroots) ran since this move began; L.a_tmp[i] is child i's action
-                int c = 0;
-                for (int base = 0; base < nch; base += 64) {
-                    const unsigned long long b = __ballot(base + lane < nch && (int)L.a_tmp[base + lane] == action);
-                    if (b) { c = first + base + (int)__builtin_ctzll(b); break; }
-                }
-                c = __builtin_amdgcn_readfirstlane(c);
-                const bool keep = c > 0 && __builtin_amdgcn_readfirstlane(T.C[c]) >= 0 &&
-                                  __builtin_amdgcn_readfirstlane(gi[GI_RR_DROP]) == 0;
-                if (lane == 0) { gi[GI_RR_NODE] = keep ? c : 0; gi[GI_RR_MARK] = keep ? gi[GI_ALLOC] : 0; }
-            }
+            if (REUSE) slot_hand_off(s, L, nch, first, action);
             slot_play(s, L, action);
             if (CAP && !full_move) d_fast_moves += 1;
             continue;
         }
-        const Leaf lf = wave_descend<false, FORCED, GUMBEL>(E, s, L, nullptr, rootP, fp_k, path);
+        const Leaf lf = wave_descend<false, FORCED, GUMBEL, SOLVER>(E, s, L, nullptr, rootP, fp_k, path);
         s.d_depth += (unsigned)lf.depth;
+        if (SOLVER && lf.state != NS_UNKNOWN) {
+            // rule 3: the descent stopped on a decided node -- no terminal test, no request, its exact value backed up
+            wave_sync_mem();
+            wave_backup<false>(T, nullptr, path, lf.depth, state_value(lf.state));
+            wave_sync_mem();
+            s.sims_done += 1; s.d_sims += 1; s.d_term += 1; sv_add(SV_STOPS, 1u);
+            if (CAP && !full_move) d_fast_sims += 1;
+            if (++term_run >= 48) break;
+            continue;
+        }
         int cnt, winner;
         const int term = wave_game_over(L.board, L.hist, lf.side, lf.mc, lf.nocap, E.perpetual != 0, L.mg, L.moves, &cnt, &winner, &s.ovf);
         if (term) {
             wave_sync_mem();   // path[] stores of lane 0 must be visible to the other lanes
-            wave_backup<false>(T, nullptr, path, lf.depth, terminal_leaf_value(term, winner, lf.side));   // mcts.py:137-140
+            if (SOLVER) {
+                // rule 1: the leaf's state from the TRUE result, seen from the side that moved into it (-lf.side), its exact value
+                // backed up (not the reference's "every decided leaf is the mover's win"), then rule 2 up the path
+                const int st = winner == 0 ? NS_DRAW : (winner == -lf.side ? NS_WIN : NS_LOSS);
+                if (lane == 0 && lf.depth > 0) T.M[lf.node] = (uint16_t)(st << XQ_STATE_SHIFT);
+                wave_backup<false>(T, nullptr, path, lf.depth, state_value(st));
+                wave_sync_mem();
+                sv_add(SV_NODES, 1u + wave_propagate(T, path, lf.depth, st));
+            } else {
+                wave_backup<false>(T, nullptr, path, lf.depth, terminal_leaf_value(term, winner, lf.side));   // mcts.py:137-140
+            }
             wave_sync_mem();   // the next descent reads N/W written here by other lanes
             s.sims_done += 1; s.d_sims += 1; s.d_term += 1;
             if (CAP && !full_move) d_fast_sims += 1;
@@ -1128,10 +1272,12 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
     int first = __builtin_amdgcn_readfirstlane(gi[GI_ALLOC]);
     bool reused = false;
     int root_sims = 0;                                // the search's first sims_done: 0, or the reused root's visits
+    int root_state = 0;                               // REUSE: the kept root's proven-state bits (0 without xq_engine_init_sv)
     if (REUSE && rr > 0) {
         // node 0 holds the chosen child's words (k_reroot); its children must be this position's legal moves
         const int m0 = __builtin_amdgcn_readfirstlane((int)T.M[0]), f0 = __builtin_amdgcn_readfirstlane(T.C[0]);
-        reused = cnt > 0 && (m0 & 0x3FFF) == cnt && f0 >= 1 && f0 + cnt <= E.node_cap;
+        reused = cnt > 0 && (m0 & XQ_CNT_MASK) == cnt && f0 >= 1 && f0 + cnt <= E.node_cap;
+        root_state = m0 & (3 << XQ_STATE_SHIFT);
         if (reused) {
             first = f0;
         } else {                                      // a defect: reported, and the root is expanded afresh
@@ -1160,7 +1306,8 @@ __global__ __launch_bounds__(64) void k_expand(Dev E, const float *__restrict__ 
                 root_sims = __builtin_amdgcn_readfirstlane(vis);
                 if (__builtin_amdgcn_readfirstlane(bad)) ovf |= 64;
                 if (lane == 0) {
-                    T.M[0] = (uint16_t)(cnt | (kind << 14)); T.N[0] = root_sims;
+                    // the kept root keeps its proven state (bits 12-13: always 0 without xq_engine_init_sv)
+                    T.M[0] = (uint16_t)(cnt | root_state | (kind << 14)); T.N[0] = root_sims;
                     st[ST_REUSED] += (unsigned)root_sims; st[ST_REROOTS] += 1;
                 }
             } else {
@@ -1231,7 +1378,7 @@ __global__ __launch_bounds__(RR_THREADS) void k_reroot(Dev E) {
     const double cW = c_in ? tW[c] : 0.0;
     const float cP = c_in ? tP[c] : 0.0f;
     const uint16_t cA = c_in ? tA[c] : 0;
-    if (!(c_in && cF > c && (cM & 0x3FFF) > 0 && cF + (cM & 0x3FFF) <= mark)) {
+    if (!(c_in && cF > c && (cM & XQ_CNT_MASK) > 0 && cF + (cM & XQ_CNT_MASK) <= mark)) {
         if (t == 0) { gi[GI_RR_NODE] = 0; st[ST_OVF] |= 64ull << 8; }
         return;
     }
@@ -1244,7 +1391,7 @@ __global__ __launch_bounds__(RR_THREADS) void k_reroot(Dev E) {
     while (lo < hi) {
         for (int e = lo + wave; e < hi; e += RR_THREADS / 64) {
             const int x = q[e];
-            const int f = tC[x], n = tM[x] & 0x3FFF;
+            const int f = tC[x], n = tM[x] & XQ_CNT_MASK;
             if (!(f > x && n > 0 && f + n <= mark)) { s_bad = 1; continue; }
             for (int i = lane; i < n; i += 64) {
                 const int y = f + i;
@@ -1399,7 +1546,7 @@ __global__ __launch_bounds__(64) void k_select_multi(Dev E, Mx X, float *__restr
         if (npend > 0 && (npend >= K || s.sims_done + npend >= S)) { phase = PH_WAIT_LEAF; break; }
         if (s.sims_done >= S) {
             if (manual) { phase = PH_HOLD; break; }
-            const int nch = __builtin_amdgcn_readfirstlane((int)(T.M[0] & 0x3FFF));
+            const int nch = __builtin_amdgcn_readfirstlane((int)(T.M[0] & XQ_CNT_MASK));
             const int first = __builtin_amdgcn_readfirstlane(T.C[0]);
             if (arena) slot_arena_move(s, L, nch, first);
             else slot_play(s, L, slot_end_move(E, s, L, true, false, nch, first));
@@ -1525,6 +1672,14 @@ void launch_select(const xq_engine *eng, const Dev &d, float *nn_in, hipStream_t
     const dim3 grid((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), block(64 * WAVES_PER_WG);
     if (gumbel_of(eng)) {
         hipLaunchKernelGGL((k_select<false, false, false, true>), grid, block, 0, s, d, nn_in);
+        return;
+    }
+    if (solver_of(eng)) {                              // never Gumbel or forced playouts: instance [CAP][REUSE], or the AROPEN one
+        static void (*const ksv[2][2])(Dev, float *) = {
+            {k_select<false, false, false, false, false, true>, k_select<true, false, false, false, false, true>},
+            {k_select<false, true, false, false, false, true>, k_select<true, true, false, false, false, true>}};
+        if (arena_of(eng)) hipLaunchKernelGGL((k_select<false, false, false, false, true, true>), grid, block, 0, s, d, nn_in);
+        else hipLaunchKernelGGL(ksv[cap_of(eng)][reuse_of(eng)], grid, block, 0, s, d, nn_in);
         return;
     }
     if (arena_of(eng)) {

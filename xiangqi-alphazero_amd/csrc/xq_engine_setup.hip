@@ -16,6 +16,8 @@ struct Opts {
     const xq_gumbel *gumbel;
     const xq_arena_opts *arena;
     const xq_rules_opts *rules;     // absent from an initialiser: NULL, the reference's rules
+    const xq_solver_opts *solver;   // absent, NULL or enabled = 0: no proven-result search
+    bool solver_on() const { return solver && solver->enabled != 0; }
 };
 
 struct Layout {
@@ -27,7 +29,8 @@ struct Layout {
 // K > 1 (leaf batching): the request rows (moves, counts, paths, packed buffers) are G K, slot-major; the virtual-loss
 // counters and the pending-leaf records follow the K = 1 layout, which is unchanged.  Gumbel root search (K = 1): the
 // square-root table's region also holds the Gumbel words (gz_bytes); every other engine has the layout it had.
-// Arena options (K = 1, never Gumbel): that region holds the arena words instead (ar_off).
+// Arena options (K = 1, never Gumbel): that region holds the arena words instead (ar_off).  Proven-result search (K = 1, never
+// Gumbel): its counters follow in the same region (sv_off, sv_bytes).
 Layout make_layout(const xq_engine_config *c, const Opts &opts) {
     const int K = opts.K, gz_m = opts.gumbel ? opts.gumbel->considered : 0;
     const bool arena = opts.arena != nullptr;
@@ -59,7 +62,9 @@ Layout make_layout(const xq_engine_config *c, const Opts &opts) {
     put(P_OUTR, (size_t)(c->max_out_results > 0 ? c->max_out_results : 1) * XQ_RESULT_BYTES);
     put(P_CNT, 64);
     put(P_STATS, G * ST_N * 8);
-    put(P_SQRT, arena ? ar_off(G, S).end : (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0));
+    put(P_SQRT, opts.solver_on() ? sv_off(G, S, arena) + sv_bytes(G)
+                : arena        ? ar_off(G, S).end
+                               : (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0));
     put(P_MNOISE, G * XQ_MAXM * 8);
     put(P_STATSUM, ST_N * 8);
     put(P_REQ, GK * 4);
@@ -127,9 +132,18 @@ bool rules_ok(const xq_rules_opts *r) {
     return (r->perpetual_check == 0 || r->perpetual_check == 1) && r->reserved[0] == 0 && r->reserved[1] == 0 && r->reserved[2] == 0;
 }
 
+// proven-result search: enabled 0 or 1, reserved words zero; on, it needs one leaf per step and goes with neither Gumbel root
+// search (its equal-visit candidates cannot skip a child) nor forced playouts
+bool solver_ok(const Opts &o) {
+    const xq_solver_opts *sv = o.solver;
+    if ((sv->enabled != 0 && sv->enabled != 1) || sv->reserved[0] != 0 || sv->reserved[1] != 0 || sv->reserved[2] != 0) return false;
+    return sv->enabled == 0 || (o.K == 1 && !o.gumbel && !o.forced);
+}
+
 // every option check, in the order the entry points have always refused in; an absent option passes
 bool opts_ok(const xq_engine_config *c, const Opts &o) {
     if (o.rules && !rules_ok(o.rules)) return false;
+    if (o.solver && !solver_ok(o)) return false;
     if (!config_ok(c) || !leaves_ok(c, o.K) || !flags_ok(c, o.K, o.flags)) return false;
     if (o.cap && !cap_ok(c, o.K, o.cap)) return false;
     if (o.forced && !forced_ok(c, o.K, o.forced)) return false;
@@ -222,7 +236,7 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
     eng->pad0 = (K > 1 ? K : 0) | (int)(o.flags << 16) | (o.cap ? PAD0_CAP : 0) | (o.forced ? PAD0_FORCED : 0) |
                 (o.gumbel ? PAD0_GUMBEL : 0) | (o.arena ? PAD0_ARENA : 0) |
-                (o.rules && o.rules->perpetual_check ? PAD0_PERPETUAL : 0);
+                (o.rules && o.rules->perpetual_check ? PAD0_PERPETUAL : 0) | (o.solver_on() ? PAD0_SOLVER : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -242,6 +256,7 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
         // arena options: the whole region zeroed (openings record, both sets' counts and rows), then the table and the parameters
         const ArOff ao = ar_off(G, S);
         if (o.arena) XQ_TRY(hipMemsetAsync(eng->p[P_SQRT], 0, ao.end, s));
+        if (o.solver_on()) XQ_TRY(hipMemsetAsync((char *)eng->p[P_SQRT] + sv_off(G, S, o.arena != nullptr), 0, sv_bytes(G), s));
         const size_t bytes = o.arena ? ao.head + sizeof(ArHead) : sizeof(double) * n + (o.gumbel ? gz_bytes(G, S, (size_t)o.gumbel->considered) : 0);
         double *tab = (double *)calloc(bytes, 1);
         if (!tab) return XQ_ERR_ARG;
@@ -316,6 +331,12 @@ size_t xq_engine_workspace_bytes_ru(const xq_engine_config *cfg, int leaves_per_
     return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules});
 }
 
+size_t xq_engine_workspace_bytes_sv(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver) {
+    return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver});
+}
+
 int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out) {
     if (k < 1 || k > XQ_MAXM || num_simulations < 1 || num_simulations > 65535 || !host_out) return XQ_ERR_ARG;
     gz_considered_visits(k, num_simulations, host_out);
@@ -363,6 +384,51 @@ int xq_engine_init_ru(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
                       const xq_rules_opts *rules, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
     return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules}, ws, ws_bytes, dev_inject, stream);
+}
+
+int xq_engine_init_sv(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, void *ws, size_t ws_bytes, const uint64_t *dev_inject,
+                      void *stream) {
+    return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver}, ws, ws_bytes, dev_inject,
+                       stream);
+}
+
+int xq_engine_solver_stats_read(const xq_engine *eng, xq_solver_stats *host_out, void *stream) {
+    if (!eng || !host_out || !solver_of(eng) || eng->cfg.n_games <= 0 || !eng->p[P_SQRT]) return XQ_ERR_ARG;
+    const size_t G = (size_t)eng->cfg.n_games, S = (size_t)eng->cfg.num_simulations;
+    XQ_TRY(hipStreamSynchronize((hipStream_t)stream));
+    unsigned long long *h = (unsigned long long *)malloc(sv_bytes(G));
+    if (!h) return XQ_ERR_ARG;
+    const int rc = xq::check(hipMemcpy(h, (char *)eng->p[P_SQRT] + sv_off(G, S, arena_of(eng)), sv_bytes(G), hipMemcpyDeviceToHost));
+    memset(host_out, 0, sizeof(*host_out));
+    if (rc == XQ_OK)
+        for (size_t g = 0; g < G; ++g) {
+            const unsigned long long *r = h + g * SV_WORDS;
+            host_out->proven_nodes += r[SV_NODES]; host_out->proven_stops += r[SV_STOPS]; host_out->proven_moves += r[SV_MOVES];
+            host_out->unspent_sims += r[SV_UNSPENT]; host_out->removed_visits += r[SV_REMOVED];
+        }
+    free(h);
+    return rc;
+}
+
+int xq_engine_read_root_states(const xq_engine *eng, int slot, int8_t *child_state, int8_t *root_state, void *stream) {
+    if (!eng || !solver_of(eng) || slot < 0 || slot >= eng->cfg.n_games || !child_state || !root_state) return XQ_ERR_ARG;
+    XQ_TRY(hipStreamSynchronize((hipStream_t)stream));
+    const size_t nb = (size_t)slot * eng->node_cap;
+    uint16_t m; int32_t first;
+    XQ_TRY(hipMemcpy(&m, (uint16_t *)eng->p[P_TM] + nb, 2, hipMemcpyDeviceToHost));
+    XQ_TRY(hipMemcpy(&first, (int32_t *)eng->p[P_TC] + nb, 4, hipMemcpyDeviceToHost));
+    // node states are seen from the side that moved into the node: a child's is the root mover's own view, the root's the opponent's
+    static const int8_t of_child[4] = {0, 1, 2, -1}, of_root[4] = {0, -1, 2, 1};
+    *root_state = of_root[node_state(m)];
+    const int n = m & XQ_CNT_MASK;
+    memset(child_state, 0, XQ_MAXM);
+    if (n == 0 || n > XQ_MAXM || first < 0) return 0;
+    uint16_t cm[XQ_MAXM];
+    XQ_TRY(hipMemcpy(cm, (uint16_t *)eng->p[P_TM] + nb + first, (size_t)n * 2, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) child_state[i] = of_child[node_state(cm[i])];
+    return n;
 }
 
 int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *stream) {
@@ -475,7 +541,7 @@ int xq_engine_read_root(const xq_engine *eng, int slot, uint16_t *actions, int32
     XQ_TRY(hipMemcpy(&first, (int32_t *)eng->p[P_TC] + nb, 4, hipMemcpyDeviceToHost));
     XQ_TRY(hipMemcpy(&rn, (int32_t *)eng->p[P_TN] + nb, 4, hipMemcpyDeviceToHost));
     XQ_TRY(hipMemcpy(gi, (char *)eng->p[P_GI] + (size_t)slot * GI_N * 4, sizeof(gi), hipMemcpyDeviceToHost));
-    const int n = m & 0x3FFF, kind = m >> 14;
+    const int n = m & XQ_CNT_MASK, kind = m >> 14;
     if (root_visits) *root_visits = rn;
     if (sims_done) *sims_done = gi[GI_SIMS];
     if (prior_kind) *prior_kind = kind == 0 ? 0 : (kind == 3 ? 3 : 1);

@@ -53,6 +53,14 @@ enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM
 
 constexpr int PAD0_PERPETUAL = 1 << 26;     // pad0 of the handle (encoding below): "perpetual-check rule on"
 
+// The node meta word tM: the child count in bits 0-11 (at most XQ_MAXM = 128), the node's proven state in bits 12-13 (always 0
+// without xq_engine_init_sv: every reader masks the count, and an engine without the solver stays byte-identical), the prior
+// kind in bits 14-15.  States are seen from the side that moved into the node, the view of its W.
+constexpr int XQ_CNT_MASK = 0x0FFF;
+constexpr int XQ_STATE_SHIFT = 12;
+enum NodeState : int { NS_UNKNOWN = 0, NS_WIN = 1, NS_DRAW = 2, NS_LOSS = 3 };
+__host__ __device__ inline int node_state(int m) { return (m >> XQ_STATE_SHIFT) & 3; }
+
 // Device view of the engine (passed by value to kernels)
 struct Dev {
     xq_engine_config cfg;
@@ -139,18 +147,29 @@ __host__ __device__ inline ArOff ar_off(size_t G, size_t S) {
     return a;
 }
 
+// Proven-result search (xq_engine_init_sv): its counters lie behind the square-root table too -- never a Gumbel engine, K = 1 --
+// from the next 256-byte boundary behind the table, or behind the arena words of an engine with arena options: SV_WORDS uint64
+// per slot (proven_nodes, proven_stops, proven_moves, unspent_sims, removed_visits, 3 spare).  Only solver engines grow.
+constexpr int SV_WORDS = 8;
+enum Sv : int { SV_NODES = 0, SV_STOPS, SV_MOVES, SV_UNSPENT, SV_REMOVED };
+__host__ __device__ inline size_t sv_off(size_t G, size_t S, bool arena_opts) { return arena_opts ? ar_off(G, S).end : ar_align((S + 2) * 8); }
+__host__ __device__ inline size_t sv_bytes(size_t G) { return G * SV_WORDS * 8; }
+
 // pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
 // flag bits "playout cap on" (xq_engine_init_cap), "forced playouts on" (xq_engine_init_fp) and "Gumbel root search on"
-// (xq_engine_init_gz), "arena options on" (xq_engine_init_ar) and "perpetual-check rule on" (xq_engine_init_ru)
+// (xq_engine_init_gz), "arena options on" (xq_engine_init_ar), "perpetual-check rule on" (xq_engine_init_ru) and "proven-result
+// search on" (xq_engine_init_sv)
 constexpr int PAD0_CAP = 1 << 30;
 constexpr int PAD0_FORCED = 1 << 29;
 constexpr int PAD0_GUMBEL = 1 << 28;
 constexpr int PAD0_ARENA = 1 << 27;
+constexpr int PAD0_SOLVER = 1 << 25;
 int leaves_of(const xq_engine *e) { return (e->pad0 & 0xFFFF) > 1 ? (e->pad0 & 0xFFFF) : 1; }
 bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE_TREE_REUSE; }
 bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
 bool forced_of(const xq_engine *e) { return (e->pad0 & PAD0_FORCED) != 0; }
 bool gumbel_of(const xq_engine *e) { return (e->pad0 & PAD0_GUMBEL) != 0; }
+bool solver_of(const xq_engine *e) { return (e->pad0 & PAD0_SOLVER) != 0; }
 bool arena_of(const xq_engine *e) { return e && (e->pad0 & PAD0_ARENA) != 0 && e->cfg.n_games > 0 && e->p[P_SQRT]; }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -72,6 +72,14 @@ where the reference calls three repetitions in the 12-board window a draw, the s
 check loses when the other side's did not.  The verdict holds at the root, in the real game and at the leaves of the search; a
 game it decides has `reason` 4 in its result (1 rules, 2 max_game_length adjudication, 3 resign, 4 rules: repetition, perpetual
 check).  Every mode, every other option.
+
+With `solver=True` (opt-in; xq_engine_init_sv) the search keeps exact results (MCTS-solver): a terminal leaf
+sets its node's proven state and backs up the true +1 / 0 / -1, states propagate up the path, a descent stops at a decided node, a
+child shown to lose is never chosen while a sibling is not, a root with a winning child ends the move at once on that child (the
+sample then carries `reserved1` = 1), and a losing child's visits leave the sample and the move distribution.  `read_root_states`
+reads the states at a root, `solver_stats` (merged into `stats()`) the five counters.  Self-play with tree reuse, the playout cap
+and the evaluation cache, search only, arena games, the perpetual-check rule; not with leaves_per_step > 1, gumbel or
+forced_playouts.
 """
 from __future__ import annotations
 
@@ -127,6 +135,7 @@ def eval_cache_bytes(n_slots: int, entries_per_slot: int) -> int:
 class EngineOptions(collections.namedtuple("EngineOptions", "K flags cap forced gumbel arena")):
     # the tuple is the argument list of xq_engine_*_ar; `rules` (hip.RulesOpts or None) is what xq_engine_*_ru take after it
     rules = None
+    solver = None              # hip.SolverOpts or None: what xq_engine_*_sv take after `rules`
 
 
 RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_game_over, and its perpetual-check verdict
@@ -134,7 +143,7 @@ RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_
 
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
                          forced_playouts=None, gumbel=None, arena_opts=None, eval_cache_entries: int = 0,
-                         perpetual_check: bool = False) -> EngineOptions:
+                         perpetual_check: bool = False, solver: bool = False) -> EngineOptions:
     """The engine options of `SelfPlayEngine` checked and turned into the C structs; needs no GPU.  Every rule of the header's
     refusal lists (include/xq_hip.h; opts_ok in csrc/xq_engine_setup.hip) is refused here first, with a message that names the
     option; tests/test_engine_options.py holds the two side by side."""
@@ -221,7 +230,17 @@ def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tre
         raise hip.XqError("leaves_per_step > 1 is not available for arena games (manual_moves = 2)")
     if perpetual_check not in (False, True, 0, 1):
         raise hip.XqError(f"perpetual_check must be a bool, got {perpetual_check!r}")
+    if solver not in (False, True, 0, 1):
+        raise hip.XqError(f"solver must be a bool, got {solver!r}")
+    if solver and K > 1:
+        raise hip.XqError("solver cannot be combined with leaves_per_step > 1")
+    if solver and gz is not None:
+        raise hip.XqError("solver cannot be combined with gumbel: its equal-visit candidates cannot skip a child")
+    if solver and forced is not None:
+        raise hip.XqError("solver cannot be combined with forced_playouts")
     opts = EngineOptions(K, hip.ENGINE_TREE_REUSE if tree_reuse else 0, cap, forced, gz, ar)
+    if solver:
+        opts.solver = hip.SolverOpts(1)
     if perpetual_check:                                # a verdict, not a search option: it goes with every mode and option
         opts.rules = hip.RulesOpts(1)
     return opts
@@ -231,12 +250,13 @@ class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
-                 perpetual_check: bool = False):
+                 perpetual_check: bool = False, solver: bool = False):
         opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
-            gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check)
+            gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check,
+            solver=solver)
         K, flags, cap, forced, gz, ar = opts
-        rules = opts.rules
+        rules, sv = opts.rules, opts.solver
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
@@ -250,11 +270,12 @@ class SelfPlayEngine:
         self.gumbel = None if gz is None else (gz.considered, float(np.float32(gz.c_visit)), float(np.float32(gz.c_scale)))
         self.arena_opts = None if ar is None else (ar.opening_plies, ar.first_game)
         self.perpetual_check = rules is not None
+        self.solver = sv is not None
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         # every entry point is the widest one with NULL for the options it does not take (include/xq_hip.h)
-        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules)]
-        nbytes = self.lib.xq_engine_workspace_bytes_ru(C.byref(cfg), K, flags, *refs)
+        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules, sv)]
+        nbytes = self.lib.xq_engine_workspace_bytes_sv(C.byref(cfg), K, flags, *refs)
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
@@ -270,8 +291,8 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            hip.check(self.lib.xq_engine_init_ru(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
-                                                 hip.stream_ptr(self.device)), "xq_engine_init_ru")
+            hip.check(self.lib.xq_engine_init_sv(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
+                                                 hip.stream_ptr(self.device)), "xq_engine_init_sv")
         # zero-copy int32 view of the per-slot state words (columns hip.GI_*: side to move of the REAL game, move_count, phase,
         # simulations done): host-side policies such as the arena's model choice read it between stages
         gi_off = int(self.h.p[hip.P_GI]) - int(self.ws.data_ptr())
@@ -554,6 +575,8 @@ class SelfPlayEngine:
         if rc != 0 and (check or rc != -4):
             hip.check(rc, "xq_engine_stats_read")
         out = s.as_dict()
+        if self.solver:
+            out.update(self.solver_stats())
         if self.cache is not None:
             cs = hip.EvCacheStats()
             hip.check(self.lib.xq_evcache_stats_read(C.byref(self.cache), C.byref(cs), hip.stream_ptr(self.device)),
@@ -562,6 +585,30 @@ class SelfPlayEngine:
             out["eval_cache_entries"] = self.cache_entries
             out["eval_cache_bytes"] = self.cache_bytes
         return out
+
+    def solver_stats(self) -> dict:
+        """The proven-result search's counters (xq_engine_solver_stats_read): proven_nodes, proven_stops, proven_moves,
+        unspent_sims, removed_visits.  Synchronises."""
+        if not self.solver:
+            raise hip.XqError("solver_stats needs an engine with solver=True")
+        s = hip.SolverStats()
+        hip.check(self.lib.xq_engine_solver_stats_read(C.byref(self.h), C.byref(s), hip.stream_ptr(self.device)),
+                  "xq_engine_solver_stats_read")
+        return s.as_dict()
+
+    def read_root_states(self, slot: int) -> dict:
+        """The proven states at the root of `slot`, from the view of the side to move there (xq_engine_read_root_states):
+        `children` int8 per legal move in move order (+1 the move wins, -1 it loses, 2 draw, 0 unknown) and `root` in the same
+        code.  Synchronises."""
+        if not self.solver:
+            raise hip.XqError("read_root_states needs an engine with solver=True")
+        cs = np.zeros(hip.MAXM, dtype=np.int8)
+        rs = np.zeros(1, dtype=np.int8)
+        n = self.lib.xq_engine_read_root_states(C.byref(self.h), int(slot), cs.ctypes.data, rs.ctypes.data,
+                                                hip.stream_ptr(self.device))
+        if n < 0:
+            hip.check(n, "xq_engine_read_root_states")
+        return dict(children=cs[:n].copy(), root=int(rs[0]))
 
     def drain(self):
         """-> (samples structured array, results structured array); empties the device rings."""
@@ -590,7 +637,7 @@ class SelfPlayEngine:
     def arena_views(self) -> dict:
         """Zero-copy torch views of the SoA tree arenas in the workspace, [G, node_cap] each:
         N int32, W float64, P float32, action int16 (uint16 bits), first int32 (first child, -1 = none), meta int16
-        (uint16 bits: child count | kind << 14), plus the root boards int8 [G, 96] (90 squares + pad).  For inspection and tests."""
+        (uint16 bits: child count, mask hip.META_COUNT_MASK | proven state << 12 (solver=True only) | kind << 14), plus the root boards int8 [G, 96] (90 squares + pad).  For inspection and tests."""
         base = int(self.ws.data_ptr())
         cap = int(self.h.node_cap)
 
@@ -660,10 +707,10 @@ class SelfPlayEngine:
 
 
 def arena_engine(cfg: hip.EngineConfig, device, opening_plies: int, first_game: int, inject=None,
-                 perpetual_check: bool = False) -> SelfPlayEngine:
+                 perpetual_check: bool = False, solver: bool = False) -> SelfPlayEngine:
     """The arena's engine with arena options (paired openings from game index `first_game`, the per-model packed step)."""
     return SelfPlayEngine(cfg, device, inject=inject, arena_opts=(int(opening_plies), int(first_game)),
-                          perpetual_check=perpetual_check)
+                          perpetual_check=perpetual_check, solver=solver)
 
 
 action_probs_dense = dense_pi   # the reference's dense pi (mcts.py:190-206) from compact (action, visit) pairs

@@ -116,6 +116,24 @@ class RulesOpts(C.Structure):
     _fields_ = [("perpetual_check", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class SolverOpts(C.Structure):
+    """xq_solver_opts: proven-result search (xq_engine_init_sv): enabled 0 / 1."""
+    _fields_ = [("enabled", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class SolverStats(C.Structure):
+    """xq_solver_stats: the proven-result search's counters (xq_engine_solver_stats_read)."""
+    _fields_ = [(n, C.c_uint64) for n in ("proven_nodes", "proven_stops", "proven_moves", "unspent_sims", "removed_visits")] + \
+               [("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+SOLVER_KEYS = ("proven_nodes", "proven_stops", "proven_moves", "unspent_sims", "removed_visits")
+META_COUNT_MASK = 0x0FFF       # XQ_CNT_MASK of csrc/xq_engine_state.cuh: the child count in a node's meta word (bits 12-13: its
+                               # proven state, 14-15: the prior kind)
+
 # what ended a game, xq_game_over_batch_ex's dev_kind
 OVER_KINDS = ("not_over", "king_missing", "no_legal_move", "no_capture", "ply_200", "repetition_draw", "perpetual_check")
 
@@ -194,6 +212,11 @@ def lib():
     L.xq_engine_workspace_bytes_ru.argtypes = L.xq_engine_workspace_bytes_ar.argtypes + [C.POINTER(RulesOpts)]
     L.xq_engine_workspace_bytes_ru.restype = C.c_size_t
     L.xq_engine_init_ru.argtypes = L.xq_engine_init_ar.argtypes[:8] + [C.POINTER(RulesOpts)] + L.xq_engine_init_ar.argtypes[8:]
+    L.xq_engine_workspace_bytes_sv.argtypes = L.xq_engine_workspace_bytes_ru.argtypes + [C.POINTER(SolverOpts)]
+    L.xq_engine_workspace_bytes_sv.restype = C.c_size_t
+    L.xq_engine_init_sv.argtypes = L.xq_engine_init_ru.argtypes[:9] + [C.POINTER(SolverOpts)] + L.xq_engine_init_ru.argtypes[9:]
+    L.xq_engine_read_root_states.argtypes = [C.POINTER(Engine), i32, vp, vp, vp]
+    L.xq_engine_solver_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(SolverStats), vp]
     L.xq_engine_arena_openings.argtypes = [C.POINTER(Engine), C.POINTER(vp), C.POINTER(vp)]
     L.xq_engine_compact_arena.argtypes = [C.POINTER(Engine), vp, vp]
     L.xq_engine_packed_arena.argtypes = [C.POINTER(Engine), C.POINTER(PackedBuffers)]
@@ -275,7 +298,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_workspace_bytes_fp", "xq_engine_init_fp", "xq_engine_workspace_bytes_gz", "xq_engine_init_gz",
            "xq_gumbel_considered_visits_host", "xq_engine_workspace_bytes_ar", "xq_engine_init_ar", "xq_engine_arena_openings",
            "xq_engine_compact_arena", "xq_engine_packed_arena", "xq_engine_expand_packed_arena",
-           "xq_engine_workspace_bytes_ru", "xq_engine_init_ru", "xq_game_over_batch_ex"]
+           "xq_engine_workspace_bytes_ru", "xq_engine_init_ru", "xq_game_over_batch_ex",
+           "xq_engine_workspace_bytes_sv", "xq_engine_init_sv", "xq_engine_read_root_states", "xq_engine_solver_stats_read"]
 
 
 def check(rc: int, what: str):

@@ -16,6 +16,10 @@ reference's sequential search (the visit counts differ); K = 1 is.
 
 `perpetual_check=True` (opt-in) searches under the perpetual-check rule (engine.SelfPlayEngine): a
 repetition one side forced by checking on every move is that side's loss at the root and at every leaf, not a draw.
+
+`solver=True` (opt-in) searches with proven results (engine.SelfPlayEngine): `get_action` at temperature 0
+returns the proven winning move when the search found one, and never a move shown to lose while another is not (`solver_choice`
+over the root's visits and `read_root_states`); `search`'s pi stays the visit counts'.
 """
 from __future__ import annotations
 
@@ -27,14 +31,29 @@ from . import engine, evaluator as ev_mod
 from .sample_format import ACTION_SPACE, dense_pi
 
 
+def solver_choice(actions, visits, child_states) -> int:
+    """The move a solver engine's root gives at temperature 0 (`child_states`: engine.read_root_states' code, +1 wins, -1 loses):
+    the first proven win; else the first maximum of the visits over the moves not shown to lose; else, every move lost, the
+    first maximum of the visits."""
+    st, v = np.asarray(child_states), np.asarray(visits, dtype=np.int64)
+    wins = np.nonzero(st == 1)[0]
+    if len(wins):
+        return int(actions[wins[0]])
+    if (st != -1).any():
+        v = np.where(st == -1, -1, v)
+    return int(actions[int(np.argmax(v))])
+
+
 class MCTS:
     def __init__(self, model, num_simulations: int = 200, c_puct: float = 1.5, device: str = "cuda",
-                 evaluator_kind: str = "auto", seed: int = 0, leaves_per_step: int = 1, perpetual_check: bool = False):
+                 evaluator_kind: str = "auto", seed: int = 0, leaves_per_step: int = 1, perpetual_check: bool = False,
+                 solver: bool = False):
         if not 1 <= int(leaves_per_step) <= 64:
             from .hip import XqError
             raise XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
         self.leaves_per_step = int(leaves_per_step)
         self.perpetual_check = bool(perpetual_check)
+        self.solver = bool(solver)
         self.model = model
         self.num_simulations = num_simulations
         self.c_puct = c_puct
@@ -60,7 +79,7 @@ class MCTS:
                                      seed=self.seed)
             self._engines[key] = engine.SelfPlayEngine(cfg, self.device, evaluator=self.evaluator,
                                                        leaves_per_step=self.leaves_per_step,
-                                                       perpetual_check=self.perpetual_check)
+                                                       perpetual_check=self.perpetual_check, solver=self.solver)
         return self._engines[key]
 
     def search_many(self, games: Sequence, temperature: float = 1.0, add_noise: bool = True) -> List[np.ndarray]:
@@ -96,6 +115,11 @@ class MCTS:
     def get_action(self, game, temperature: float = 0.0, add_noise: bool = False) -> int:
         """mcts.py:166-174"""
         probs = self.search(game, temperature, add_noise)
+        if temperature == 0 and self.solver:
+            eng = self._engine(1, add_noise)           # the engine `search` just used: slot 0 holds the finished search
+            r = eng.read_root(0)
+            if len(r["actions"]):
+                return solver_choice(r["actions"], r["visits"], eng.read_root_states(0)["children"])
         if temperature == 0:
             return int(np.argmax(probs))
         return int(np.random.choice(len(probs), p=probs))

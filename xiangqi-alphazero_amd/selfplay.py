@@ -15,7 +15,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import engine, evaluator
+from . import engine, evaluator, hip
 from .sample_format import to_reference_tuples
 
 _CFG_KEYS = ("num_simulations", "c_puct", "temperature_threshold", "max_game_length", "random_opening_moves",
@@ -26,7 +26,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
               evaluator_kind: str = "hip", poll_every: int = 64, device_records: bool = False, use_graph: bool = True,
               eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None,
               tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None,
-              perpetual_check: Optional[bool] = None):
+              perpetual_check: Optional[bool] = None, solver: Optional[bool] = None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -48,7 +48,10 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     `gumbel`); it needs K = 1 and none of tree reuse, playout cap and forced playouts.
     `perpetual_check` (None: `config.perpetual_check_loses`, absent = off) plays under the perpetual-check rule: the side that
     checks through a repetition loses instead of drawing (stats `perpetual_check`, `perpetual_check_games`: the finished games
-    with reason 4).  It goes with every other option; gate under the same rule (arena.evaluate_models)."""
+    with reason 4).  It goes with every other option; gate under the same rule (arena.evaluate_models).
+    `solver` (None: `config.mcts_solver`, absent = off) searches with proven results (stats `solver`, `proven_nodes`,
+    `proven_stops`, `proven_moves`, `unspent_sims`, `removed_visits`, all 0 when off); it needs K = 1 and
+    neither Gumbel root search nor forced playouts."""
     if eval_cache_entries is None:
         eval_cache_entries = int(getattr(config, "eval_cache_entries", 0) or 0)
     if leaves_per_step is None:
@@ -71,6 +74,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
             gumbel = (gm, 50.0 if gcv is None else float(gcv), 1.0 if gcs is None else float(gcs))
     if perpetual_check is None:
         perpetual_check = bool(getattr(config, "perpetual_check_loses", False))
+    if solver is None:
+        solver = bool(getattr(config, "mcts_solver", False))
     slots = int(n_slots or min(num_games, 8192))
     slots = max(1, min(slots, num_games))
     ev, ev_name = evaluator.make_evaluator(model, device, evaluator_kind)
@@ -83,7 +88,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
         max_out_samples=num_games * 201, max_out_results=num_games + 8)
     eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries,
                                 leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
-                                forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check)
+                                forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check, solver=solver)
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -105,6 +110,9 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     st["forced_playouts"] = eng.forced_playouts        # None, or k
     st["gumbel"] = eng.gumbel                          # None, or (m, c_visit, c_scale)
     st["perpetual_check"] = eng.perpetual_check
+    st["solver"] = eng.solver
+    for k in hip.SOLVER_KEYS:                          # the solver's keys are present (0) when it is off
+        st.setdefault(k, 0)
     if device_records:
         st["perpetual_check_games"] = int((results[:, 9] == 4).sum().item()) if len(results) else 0   # byte 9: reason
     else:
@@ -122,7 +130,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
                        leaves_per_step: Optional[int] = None,
                        tree_reuse: Optional[bool] = None, playout_cap=None,
                        forced_playouts: Optional[float] = None, gumbel=None,
-                       perpetual_check: Optional[bool] = None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
+                       perpetual_check: Optional[bool] = None, solver: Optional[bool] = None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
     for k in _CFG_KEYS + ("num_games_per_iter",):
         if not hasattr(config, k):
             raise AttributeError(f"config lacks '{k}' (see training/train.py:55-111)")
@@ -134,7 +142,8 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
     samples, results, st, elapsed = run_games(model, config, num_games, gpu_device, n_slots, seed,
                                               eval_cache_entries=eval_cache_entries, leaves_per_step=leaves_per_step,
                                               tree_reuse=tree_reuse, playout_cap=playout_cap,
-                                              forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check)
+                                              forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check,
+                                              solver=solver)
     all_data, per_game = to_reference_tuples(samples, results, augment=True)
     wins = {1: 0, -1: 0, 0: 0}
     total_steps = 0
@@ -155,6 +164,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
         "gumbel_moves": st["gumbel_moves"], "gumbel_considered": st["gumbel_considered"],
         "gumbel_offprior": st["gumbel_offprior"], "gumbel": st["gumbel"],
         "perpetual_check": st["perpetual_check"], "perpetual_check_games": st["perpetual_check_games"],
+        "solver": st["solver"], **{k: st[k] for k in hip.SOLVER_KEYS},
     }
     if return_compact:
         stats["compact_samples"], stats["compact_results"] = samples, results

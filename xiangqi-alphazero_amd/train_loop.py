@@ -52,6 +52,8 @@ class AlphaZeroLoop:
         # the perpetual-check rule (config.perpetual_check_loses; absent: off), read once: self-play and the arena gate get this
         # one value, so a loop never trains under one rule and gates under the other
         self.perpetual_check = bool(getattr(config, "perpetual_check_loses", False))
+        # the proven-result search (config.mcts_solver; absent: off), read once as well, for self-play and the gate alike
+        self.solver = bool(getattr(config, "mcts_solver", False))
         torch.manual_seed(seed)                        # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -85,7 +87,7 @@ class AlphaZeroLoop:
                                                     # forced playouts too (config.forced_playouts_k; absent or 0: off): the
                                                     # arena (arena.py) never takes it
                                                     forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None,
-                                                    perpetual_check=self.perpetual_check)
+                                                    perpetual_check=self.perpetual_check, solver=self.solver)
         # the Gumbel root search (config.gumbel_considered, gumbel_c_visit, gumbel_c_scale; absent or 0: off) reaches the engine
         # through run_games, which reads those keys from the config it is handed; the arena never takes it either
         return samples, results
@@ -129,9 +131,9 @@ class AlphaZeroLoop:
             # paired random openings (opt-in): another seed every iteration, so successive gates see different openings
             seed = int(getattr(self.config, "arena_seed", 0) or 0) + self.iteration
             return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind,
-                                         seed=seed, perpetual_check=self.perpetual_check)
+                                         seed=seed, perpetual_check=self.perpetual_check, solver=self.solver)
         return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind,
-                                     perpetual_check=self.perpetual_check)
+                                     perpetual_check=self.perpetual_check, solver=self.solver)
 
     def evaluate(self) -> dict:
         stats = self._arena()
