@@ -2,8 +2,8 @@
 xq_engine_init_gz).  TEST INFRASTRUCTURE ONLY: it judges k_select<false, false, false, true> / k_expand<false, false, true>.
 Written from the header's text, not from the kernels.
 
-It is tests/tree_reuse_model.py's game loop and search (imported, not edited; tests/playout_cap_model.py is that loop plus the
-cap, and is what the model is when the option is off) with the header's rules:
+The game loop is tests/selfplay_model.py's, the one loop of every self-play model, the search tests/tree_reuse_model.py's, with
+the header's rules:
   * root expansion: l_i = log(max(tP[i], FLT_MIN)) in float64, g_i from the raw Dirichlet stream of tests/draws.py (injected
     draws: ((x >> 40) % 4096 - 1024) / 512), rootP = g + l, prior kind 3, no Dirichlet noise;
   * root selection: the candidates are the children with N_i == considered_visits(min(m, cnt), S)[root visits]; the first
@@ -22,12 +22,7 @@ import math
 
 import numpy as np
 
-import leaf_batch_model as LB
-import playout_cap_model as PC
 import tree_reuse_model as M
-from draws import Draws
-from oracle import xq_oracle as O
-from stub_eval import predict_from_key, state_key
 
 FLT_MIN = float(np.finfo(np.float32).tiny)
 
@@ -103,31 +98,6 @@ class GumbelSearch(M.ReuseSearch):
         self.min_gap = min(self.min_gap, _gap(score, cand, win))
         return f + win
 
-    def run(self):
-        g = self.game
-        legal = g.legal_actions()
-        pri, kind, value = self.priors(g.state_for_nn(), legal)
-        if len(legal) == 0:
-            return self
-        self._expand_root(legal, pri, kind, value)
-        while self.sims < self.S:
-            sim = g.clone()
-            node, path = 0, [0]
-            while self.nch[node] > 0:
-                node = self._select(node)
-                sim.make_action(int(self.action[node]))
-                path.append(node)
-            over, winner = sim.is_game_over()
-            if over:
-                self._backup(path, 0.0 if winner == 0 else 1.0)
-            else:
-                lg = sim.legal_actions()
-                p, k, value = self.priors(sim.state_for_nn(), lg)
-                self._expand(node, lg, p, k, False)
-                self._backup(path, -float(np.float32(value)))
-            self.sims += 1
-        return self
-
     def root(self) -> dict:
         r = super().root()
         r["prior_kind"] = int(self.kind[0])
@@ -167,64 +137,21 @@ class GumbelSearch(M.ReuseSearch):
                     unvisited_mass=float(sum(p for p, c in zip(pi, N) if c == 0)),
                     unvisited_with_target=int(((N == 0) & (target > 0)).sum()))
 
+    def move_end(self, stats):
+        r, fin = self.root(), self.finish()
+        assert fin["sum_n"] == self.S == int(self.N[0])
+        stats["gumbel_moves"] += 1
+        stats["gumbel_considered"] += fin["considered"]
+        stats["gumbel_offprior"] += fin["offprior"]
+        stats["min_gap"] = min(stats["min_gap"], self.min_gap)
+        fin["visits"] = r["visits"].copy()
+        return fin["target"], fin["played"], fin        # no temperature, no uniform draw
+
 
 def search(game, num_simulations, priors, g, gumbel, c_puct=1.5) -> GumbelSearch:
     return GumbelSearch(game, num_simulations, priors, g, gumbel, c_puct).run()
 
 
 def play_game(cfg: dict, peaked: bool, seed, gumbel=None):
-    """One self-play game on Draws(seed) -> (samples, winner, plies, stats).  gumbel = (m, c_visit, c_scale) or None (the game
-    of playout_cap_model.play_game).  stats: sims, gumbel_moves, gumbel_considered, gumbel_offprior, min_gap (the smallest gap
-    between winner and runner-up over every root arg-max of the game) and `moves`, one finish() dict per move."""
-    if gumbel is None:
-        samples, winner, plies, stats = PC.play_game(cfg, peaked, seed)
-        stats.update(gumbel_moves=0, gumbel_considered=0, gumbel_offprior=0, min_gap=math.inf)
-        return samples, winner, plies, stats
-    d = Draws(seed) if isinstance(seed, int) else seed
-    priors = LB.stub_priors(peaked)
-    S = int(cfg["num_simulations"])
-    g = O.Game()
-    k = d.randint(0, int(cfg["random_opening_moves"]))
-    for _ in range(k):
-        legal = g.legal_actions()
-        if len(legal) == 0:
-            break
-        g.make_action(int(legal[d.choice_index(len(legal))]))
-        if g.is_game_over()[0]:
-            g = O.Game()
-            break
-    samples, resign_hist = [], []
-    stats = dict(sims=0, gumbel_moves=0, gumbel_considered=0, gumbel_offprior=0, min_gap=math.inf, moves=[])
-    while True:
-        over, w = g.is_game_over()
-        if over:
-            winner = w
-            break
-        if g.move_count >= int(cfg["max_game_length"]):
-            diff = O.material(g.board, 1) - O.material(g.board, -1)
-            winner = 1 if diff > 30 else (-1 if diff < -30 else 0)
-            break
-        gs = injected_gumbels(d.s_dirichlet, len(g.legal_actions()))
-        s = search(g, S, priors, gs, gumbel, float(cfg["c_puct"]))
-        r, fin = s.root(), s.finish()
-        assert fin["sum_n"] == S == int(s.N[0])
-        stats["sims"] += S
-        stats["gumbel_moves"] += 1
-        stats["gumbel_considered"] += fin["considered"]
-        stats["gumbel_offprior"] += fin["offprior"]
-        stats["min_gap"] = min(stats["min_gap"], s.min_gap)
-        fin["visits"] = r["visits"].copy()
-        stats["moves"].append(fin)
-        samples.append(dict(board=g.board.reshape(90).copy(), player=g.current_player, actions=r["actions"].copy(),
-                            visits=fin["target"].copy(), late=False))
-        g.make_action(int(r["actions"][fin["played"]]))        # no temperature, no uniform draw
-        if cfg["enable_resign"] and len(samples) > 10:
-            _, v = predict_from_key(state_key(g.state_for_nn()), peaked)
-            resign_hist.append(v)
-            K = int(cfg["resign_check_steps"])
-            if len(resign_hist) >= K and all(x < float(cfg["resign_threshold"]) for x in resign_hist[-K:]):
-                winner = -g.current_player
-                break
-    for smp in samples:
-        smp["z"] = 0 if winner == 0 else (1 if winner == smp["player"] else -1)
-    return samples, winner, g.move_count, stats
+    import selfplay_model                              # it imports this module
+    return selfplay_model.play_game(cfg, peaked, seed, gumbel=gumbel)

@@ -70,6 +70,13 @@ class LeafBatchSearch:
         self.noise, self.eps = noise, float(noise_eps)
 
     # ---- tree ------------------------------------------------------------------------------------------------------------
+    def _noisy(self, pri, kind, n):
+        """The float64 priors of a noisy root (kind 1) over priors of `kind`."""
+        eta = np.asarray(self.noise, dtype=np.float64)[:n]
+        if kind == 0:
+            return (np.float32(1.0 - self.eps) * pri).astype(np.float32).astype(np.float64) + self.eps * eta
+        return (1.0 - self.eps) * (1.0 / n) + self.eps * eta
+
     def _expand(self, node, legal, pri, kind, noisy):
         n = len(legal)
         f = self.alloc
@@ -77,12 +84,7 @@ class LeafBatchSearch:
         self.first[node], self.nch[node] = f, n
         self.action[f:f + n] = legal
         if noisy:
-            eta = np.asarray(self.noise, dtype=np.float64)[:n]
-            if kind == 0:
-                keep = np.float32(1.0 - self.eps)
-                self.P64[f:f + n] = (keep * pri).astype(np.float32).astype(np.float64) + self.eps * eta
-            else:
-                self.P64[f:f + n] = (1.0 - self.eps) * (1.0 / n) + self.eps * eta
+            self.P64[f:f + n] = self._noisy(pri, kind, n)
             self.kind[node] = 1
         elif kind == 0:
             self.P32[f:f + n] = pri
@@ -91,7 +93,8 @@ class LeafBatchSearch:
             self.P64[f:f + n] = 1.0 / n
             self.kind[node] = 2
 
-    def _select(self, p):
+    def _scores(self, p):
+        """The PUCT score of every child of p: float32 arithmetic over float32 priors (kind 0), float64 otherwise."""
         f, n = self.first[p], self.nch[p]
         v = self.vl[f:f + n]
         nn = self.N[f:f + n] + v
@@ -109,7 +112,29 @@ class LeafBatchSearch:
             t = t * sq
             t = t / (1 + nn).astype(np.float64)
             ucb = q + t
-        return int(f + int(np.argmax(ucb)))             # first maximum
+        return ucb
+
+    def _select(self, p):
+        return int(self.first[p] + int(np.argmax(self._scores(p))))     # first maximum
+
+    def _descend(self, sim):
+        """One descent from the root to a leaf (or to a node `_decided` stops it at), played on `sim` -> the path."""
+        node, path = 0, [0]
+        while self.nch[node] > 0 and not self._decided(node):
+            node = self._select(node)
+            sim.make_action(int(self.action[node]))
+            path.append(node)
+        return path
+
+    def _decided(self, node):
+        """A node whose value is known without looking below it (none here: the solver's rule 3)."""
+        return False
+
+    def _terminal(self, sim, path):
+        """The value a descent that ended on a finished game backs up, from the view of the side that moved into the leaf, or
+        None when the leaf is to be evaluated."""
+        over, winner = sim.is_game_over()
+        return (0.0 if winner == 0 else 1.0) if over else None
 
     def _backup(self, path, v, vl=0):
         for k, nd in enumerate(reversed(path)):
@@ -136,17 +161,13 @@ class LeafBatchSearch:
                 if self.sims >= self.S:
                     break
                 sim = g.clone()
-                node, path = 0, [0]
-                while self.nch[node] > 0:
-                    node = self._select(node)
-                    sim.make_action(int(self.action[node]))
-                    path.append(node)
-                if any(p[0][-1] == node for p in pend):
+                path = self._descend(sim)
+                if any(p[0][-1] == path[-1] for p in pend):
                     self.collisions += 1
                     break
-                over, winner = sim.is_game_over()
-                if over:
-                    self._backup(path, 0.0 if winner == 0 else 1.0)
+                v = self._terminal(sim, path)
+                if v is not None:
+                    self._backup(path, v)
                     self.sims += 1
                     self.terminal_sims += 1
                     term_run += 1

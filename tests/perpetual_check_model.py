@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from leaf_batch_model import TERMINAL_RUN, LeafBatchSearch
+from leaf_batch_model import LeafBatchSearch
 from oracle import xq_oracle as O
 
 KINDS = ("not_over", "king_missing", "no_legal_move", "no_capture", "ply_200", "repetition_draw", "perpetual_check")
@@ -90,60 +90,16 @@ def terminal_value(kind, winner, side_to_move):
 
 
 class PerpetualSearch(LeafBatchSearch):
-    """`LeafBatchSearch` with the rule's verdict at the root and the leaves (`perpetual`; off: the parent class, which
+    """`LeafBatchSearch` with the rule's verdict at the leaves (`perpetual`; off: the parent class, which
     tests/test_perpetual_check_model.py pins)."""
 
     def __init__(self, game, num_simulations, leaves_per_step, priors, perpetual, c_puct=1.5, noise=None):
         super().__init__(game, num_simulations, leaves_per_step, priors, c_puct, noise)
         self.perpetual = bool(perpetual)
 
-    def run(self):
-        g = self.game
-        legal = g.legal_actions()
-        self.current = g
-        pri, kind, _ = self.priors(g.state_for_nn(), legal)
-        if len(legal) == 0:
-            return self
-        self._expand(0, legal, pri, kind, self.noise is not None)
-        while self.sims < self.S:
-            self.steps += 1
-            pend = []
-            term_run = 0
-            while True:
-                if pend and (len(pend) >= self.K or self.sims + len(pend) >= self.S):
-                    break
-                if self.sims >= self.S:
-                    break
-                sim = g.clone()
-                node, path = 0, [0]
-                while self.nch[node] > 0:
-                    node = self._select(node)
-                    sim.make_action(int(self.action[node]))
-                    path.append(node)
-                if any(p[0][-1] == node for p in pend):
-                    self.collisions += 1
-                    break
-                over, winner = game_verdict(sim, self.perpetual)
-                if over != NOT_OVER:
-                    self._backup(path, terminal_value(over, winner, sim.current_player))
-                    self.sims += 1
-                    self.terminal_sims += 1
-                    term_run += 1
-                    if term_run >= TERMINAL_RUN:
-                        break
-                    continue
-                pend.append((path, sim.state_for_nn(), sim.legal_actions(), sim))
-                self.vl[path] += 1
-            if pend:
-                self.leaves_per_step.append(len(pend))
-            for path, state, lg, sim in pend:
-                self.current = sim
-                pri, kind, value = self.priors(state, lg)
-                self._expand(path[-1], lg, pri, kind, False)
-                self._backup(path, -float(np.float32(value)), vl=1)
-                self.sims += 1
-        assert not self.vl.any()
-        return self
+    def _terminal(self, sim, path):
+        kind, winner = game_verdict(sim, self.perpetual)
+        return None if kind == NOT_OVER else terminal_value(kind, winner, sim.current_player)
 
 
 def search(game, num_simulations, leaves_per_step, priors, perpetual, c_puct=1.5, noise=None) -> dict:

@@ -52,7 +52,7 @@ def test_model_with_reuse_keeps_the_chosen_subtree(idx):
     S = int(t["cfg"]["num_simulations"])
     moves = []
     got, winner, steps, stats = M.play_game(t["cfg"], t["stub"] == "peaked", t["seed"], tree_reuse=True,
-                                            on_move=lambda s, c, kept: moves.append((s, c, kept)))
+                                            on_move=lambda s, c, kept, g: moves.append((s, c, kept)))
     assert all(int(s["visits"].sum()) == S for s in got)
     checked = 0
     for (prev, c, kept), (nxt, _, _) in zip(moves, moves[1:]):

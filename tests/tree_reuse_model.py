@@ -1,10 +1,11 @@
 """Host model of a self-play game with tree reuse across moves (include/xq_hip.h, XQ_ENGINE_TREE_REUSE).  TEST INFRASTRUCTURE
 ONLY: it judges k_select<true> / k_reroot / k_expand<true>.
 
-The game loop is the oracle's (oracle/xq_oracle.c, xqo_play_one_game: random opening, adjudication, Dirichlet noise per move,
-sample, move from the visit counts, resign probe) with the draws injected (tests/draws.py).  The search is the K = 1 search of
-tests/leaf_batch_model.py (oracle rules, the oracle's PUCT arithmetic), which test_leaf_batch_model.py pins against the
-reference.  With reuse off the model is the oracle's game (tests/test_tree_reuse_model.py checks that on every recorded game).
+The game loop is tests/selfplay_model.py's, the one loop of every self-play model (the oracle's, with the draws injected).  The
+search, `ReuseSearch`, is the one sequential search of a move: the K = 1 search of tests/leaf_batch_model.py (oracle rules, the
+oracle's PUCT arithmetic, its descent and its terminal test), which test_leaf_batch_model.py pins against the reference; the
+searches of the other options subclass it.  With reuse off the model is the oracle's game (tests/test_tree_reuse_model.py checks
+that on every recorded game).
 
 With reuse on, when a move ends the chosen child c, if it was expanded, becomes the next search's root with its subtree:
   * the arena is compacted as k_reroot does it -- c at node 0, its descendants in their old order from node 1 on;
@@ -17,9 +18,6 @@ from __future__ import annotations
 import numpy as np
 
 import leaf_batch_model as LB
-from draws import Draws
-from oracle import xq_oracle as O
-from stub_eval import predict_from_key, state_key
 
 ARRAYS = ("N", "W", "P32", "P64", "first", "nch", "kind", "action")
 
@@ -48,55 +46,71 @@ def remap_first(first_old, order):
 
 
 class ReuseSearch(LB.LeafBatchSearch):
-    """The K = 1 search of one move; `kept` (from `reroot`) starts it from the previous move's subtree."""
+    """The K = 1 search of one move.  `kept` (from `reroot`) starts it from the previous move's subtree; `noise` None is a root
+    without noise (a fast move, an arena move); it runs until sims >= `budget` <= num_simulations (which sizes the arrays, so
+    that a tree inherited from a full search fits)."""
 
-    def __init__(self, game, num_simulations, priors, noise, kept=None, c_puct: float = 1.5, noise_eps: float = 0.25):
+    ARRAYS = ARRAYS                                    # what `reroot` hands to the next search
+
+    def __init__(self, game, num_simulations, priors, noise, kept=None, c_puct: float = 1.5, noise_eps: float = 0.25,
+                 budget=None):
         super().__init__(game, num_simulations, 1, priors, c_puct, noise, noise_eps)
         self.kept = kept
+        self.budget = self.S if budget is None else int(budget)
         self.reused = 0
 
-    def run(self):
-        g = self.game
-        legal = g.legal_actions()
-        pri, kind, _ = self.priors(g.state_for_nn(), legal)
+    def _expand_root(self, legal, pri, kind, value):
+        self._expand(0, legal, pri, kind, self.noise is not None)
+
+    def _root_setup(self):
+        """Expands a fresh root, or takes `kept` over and redoes what the root request does to it -> False without a legal move."""
+        legal = self.game.legal_actions()
+        pri, kind, value = self.priors(self.game.state_for_nn(), legal)
         if len(legal) == 0:
-            return self
+            return False
         if self.kept is None:
-            self._expand(0, legal, pri, kind, True)
-        else:
-            n_nodes = len(self.kept["N"])
-            for k in ARRAYS:
-                getattr(self, k)[:n_nodes] = self.kept[k]
-            self.alloc = n_nodes
-            f, n = int(self.first[0]), int(self.nch[0])
-            assert n == len(legal) and list(self.action[f:f + n]) == list(legal)
-            eta = np.asarray(self.noise, dtype=np.float64)[:n]
-            if kind == 0:
-                assert self.P32[f:f + n].tobytes() == np.asarray(pri, np.float32).tobytes()   # same position, same priors
-                self.P32[f:f + n] = pri
-                self.P64[f:f + n] = (np.float32(1.0 - self.eps) * pri).astype(np.float32).astype(np.float64) + self.eps * eta
-            else:
-                self.P64[f:f + n] = (1.0 - self.eps) * (1.0 / n) + self.eps * eta
+            self._expand_root(legal, pri, kind, value)
+            return True
+        n_nodes = len(self.kept["N"])
+        for k in self.ARRAYS:
+            getattr(self, k)[:n_nodes] = self.kept[k]
+        self.alloc = n_nodes
+        f, n = int(self.first[0]), int(self.nch[0])
+        assert n == len(legal) and list(self.action[f:f + n]) == list(legal)
+        if kind == 0:
+            assert self.P32[f:f + n].tobytes() == np.asarray(pri, np.float32).tobytes()   # same position, same priors
+            self.P32[f:f + n] = pri
+        if self.noise is not None:
+            self.P64[f:f + n] = self._noisy(pri, kind, n)
             self.kind[0] = 1
-            self.reused = int(self.N[f:f + n].sum())
-            self.N[0] = self.reused
-            self.sims = self.reused
-        self.start = {k: getattr(self, k)[:self.alloc].copy() for k in ARRAYS}    # the first search state of this move
-        while self.sims < self.S:
-            sim = g.clone()
-            node, path = 0, [0]
-            while self.nch[node] > 0:
-                node = self._select(node)
-                sim.make_action(int(self.action[node]))
-                path.append(node)
-            over, winner = sim.is_game_over()
-            if over:
-                self._backup(path, 0.0 if winner == 0 else 1.0)
-            else:
+        else:
+            assert int(self.kind[0]) == kind               # the kind it had as an inner node: same position, same evaluation
+            if kind != 0:
+                self.P64[f:f + n] = 1.0 / n
+        self.reused = int(self.N[f:f + n].sum())
+        self.N[0] = self.reused
+        self.sims = self.reused
+        return True
+
+    def _finished(self):
+        return self.sims >= self.budget
+
+    def run(self):
+        if not self._root_setup():
+            return self
+        self.start = {k: getattr(self, k)[:self.alloc].copy() for k in self.ARRAYS}    # the first search state of this move
+        while not self._finished():
+            sim = self.game.clone()
+            path = self._descend(sim)
+            v = self._terminal(sim, path)
+            if v is None:
                 lg = sim.legal_actions()
                 p, k, value = self.priors(sim.state_for_nn(), lg)
-                self._expand(node, lg, p, k, False)
-                self._backup(path, -float(np.float32(value)))
+                self._expand(path[-1], lg, p, k, False)
+                v = -float(np.float32(value))
+            else:
+                self.terminal_sims += 1
+            self._backup(path, v)
             self.sims += 1
         return self
 
@@ -105,10 +119,15 @@ class ReuseSearch(LB.LeafBatchSearch):
         if self.first[c] < 0:
             return None
         order = compaction_order(self.first, self.nch, c, self.alloc)
-        out = {k: getattr(self, k)[order].copy() for k in ARRAYS}
+        out = {k: getattr(self, k)[order].copy() for k in self.ARRAYS}
         out["first"] = remap_first(self.first, order)
         out["old_index"] = order
         return out
+
+    def move_end(self, stats):
+        """The end of a self-play move: adds this search's own counters to `stats` -> (the visit counts the sample records and the
+        move is drawn from, the child the move is already decided on or None, what the search adds to the move's record)."""
+        return self.root()["visits"], None, {}
 
 
 def choose(actions, visits, late: bool, u: float, late_temperature: float = 0.3) -> int:
@@ -131,55 +150,6 @@ def choose(actions, visits, late: bool, u: float, late_temperature: float = 0.3)
     return int(order[-1])
 
 
-def play_game(cfg: dict, peaked: bool, seed: int, tree_reuse: bool = False, on_move=None):
-    """One self-play game with Draws(seed) -> (samples, winner, plies, stats).  samples: dicts with board, player, actions,
-    visits, late, z.  `on_move(search, chosen_child, next_kept)` is called after every search (tests)."""
-    d = Draws(seed)
-    priors = LB.stub_priors(peaked)
-    S = int(cfg["num_simulations"])
-    g = O.Game()
-    k = d.randint(0, int(cfg["random_opening_moves"]))
-    for _ in range(k):
-        legal = g.legal_actions()
-        if len(legal) == 0:
-            break
-        g.make_action(int(legal[d.choice_index(len(legal))]))
-        if g.is_game_over()[0]:
-            g = O.Game()
-            break
-    samples, resign_hist, kept = [], [], None
-    stats = dict(sims=0, reused_visits=0, reroots=0)
-    while True:
-        over, w = g.is_game_over()
-        if over:
-            winner = w
-            break
-        if g.move_count >= int(cfg["max_game_length"]):
-            diff = O.material(g.board, 1) - O.material(g.board, -1)
-            winner = 1 if diff > 30 else (-1 if diff < -30 else 0)
-            break
-        late = g.move_count >= int(cfg["temperature_threshold"])
-        noise = d.dirichlet(len(g.legal_actions()))
-        s = ReuseSearch(g, S, priors, noise, kept).run()
-        stats["sims"] += S - s.reused
-        stats["reused_visits"] += s.reused
-        stats["reroots"] += kept is not None
-        r = s.root()
-        samples.append(dict(board=g.board.reshape(90).copy(), player=g.current_player, actions=r["actions"].copy(),
-                            visits=r["visits"].copy(), late=late))
-        i = choose(r["actions"], r["visits"], late, d.uniform())
-        c = int(s.first[0]) + i
-        kept = s.reroot(c) if tree_reuse else None
-        if on_move is not None:
-            on_move(s, c, kept)
-        g.make_action(int(r["actions"][i]))
-        if cfg["enable_resign"] and len(samples) > 10:
-            _, v = predict_from_key(state_key(g.state_for_nn()), peaked)
-            resign_hist.append(v)
-            K = int(cfg["resign_check_steps"])
-            if len(resign_hist) >= K and all(x < float(cfg["resign_threshold"]) for x in resign_hist[-K:]):
-                winner = -g.current_player                 # a pending re-root is not counted: no search follows
-                break
-    for smp in samples:
-        smp["z"] = 0 if winner == 0 else (1 if winner == smp["player"] else -1)
-    return samples, winner, g.move_count, stats
+def play_game(cfg: dict, peaked: bool, seed, tree_reuse: bool = False, on_move=None):
+    import selfplay_model                              # it imports this module
+    return selfplay_model.play_game(cfg, peaked, seed, tree_reuse=tree_reuse, on_move=on_move)
