@@ -545,6 +545,46 @@ int xq_engine_init_sv(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
 int xq_engine_read_root_states(const xq_engine *eng, int slot, int8_t *child_state /* [XQ_MAXM] */, int8_t *root_state, void *stream);
 int xq_engine_solver_stats_read(const xq_engine *eng, xq_solver_stats *host_out, void *stream);
 
+/* Root statistics per sample (opt-in; root_stats == NULL or enabled = 0 is xq_engine_init_sv exactly -- same workspace bytes, same
+ * handle, same bytes out -- and xq_engine_init_sv is that call).  The search's own value of the root is kept with every sample a
+ * self-play move stages, so a trainer can regress the value head on a mix of the game's result z and the search value q
+ * (xq_samples_to_batch_ex below; lc0's q-ratio, KataGo).  Outside the reference-parity contract, like the other opt-in options.
+ * WHAT IS WRITTEN.  At the end of every move that stages a sample (k_select and k_select_multi; a fast move of the playout cap
+ * stages none and writes nothing), into the sample's `pad` bytes, the layout of xq_sample_root_stats at byte
+ * XQ_SAMPLE_ROOT_STATS_OFFSET = 108 of the record:
+ *     root_q          float32  the search value of the position from the view of the side to move
+ *     root_visits     uint32   the sum of N_i over the root's children
+ *     has_root_stats  uint8    1
+ *     the other 11 bytes zero.
+ * ARITHMETIC, over the RAW tree arrays at the end of the move -- before forced-playout pruning and before the solver's rule-5
+ * counts -- so that a host model repeats it bit for bit:
+ *     sumW = 0.0 (double), sumN = 0
+ *     for i = 0 .. nch-1 in move order:  sumW += W[first+i];  sumN += N[first+i]     (one sequential scan)
+ *     root_q = proven >= 0 ? 1.0f : (sumN > 0 ? (float)(sumW / (double)sumN) : 0.0f)  (round to nearest even)
+ * proven >= 0 is the solver's rule 4 (the side to move has a proven win); root_visits is the raw sumN in that case too.
+ * Without the option the pad bytes stay the zeros the move end fills in.  No draw, visit, move or record changes with the option
+ * on or off, outside those 20 bytes.  It goes with leaf batching, tree reuse, the playout cap, forced playouts, the solver, the
+ * perpetual-check rule and the evaluation cache.
+ * XQ_ERR_ARG before any launch (xq_engine_workspace_bytes_rs: 0): enabled outside {0, 1}; a non-zero reserved word; enabled = 1
+ * with manual_moves != 0 (search-only and arena engines record no samples) or with Gumbel root search (its root value is its own
+ * v_mix; left for later); and whatever xq_engine_init_sv refuses.  No workspace, no state word, no counter: "root statistics on"
+ * lives in the handle (pad0, above the public flag bits) and reaches the kernels as a kernel argument. */
+typedef struct xq_root_stats_opts { int32_t enabled; int32_t reserved[3]; } xq_root_stats_opts;
+#define XQ_SAMPLE_ROOT_STATS_OFFSET 108
+typedef struct xq_sample_root_stats {
+    float root_q;
+    uint32_t root_visits;
+    uint8_t has_root_stats;
+    uint8_t zero[11];
+} xq_sample_root_stats;
+size_t xq_engine_workspace_bytes_rs(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats);
+int xq_engine_init_rs(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats, void *ws,
+                      size_t ws_bytes, const uint64_t *dev_inject, void *stream);
+
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 
 /* dev_policy[slot] = float32[8100]: network LOGITS (policy_is_probs = 0; softmax over all 8100 as
@@ -841,6 +881,18 @@ int xq_wino_conv3x3_bf16_live(const float *dev_x, const void *dev_u_bf16, const 
  * ===================================================================================== */
 int xq_samples_to_batch(const void *dev_samples, const int32_t *dev_index, const uint8_t *dev_flip, int n,
                         double late_temperature, float *dev_states, float *dev_pi, float *dev_z, void *stream);
+
+/* The same with a q-mixed value target (opt-in; opts == NULL or q_mix = 0.0 gives xq_samples_to_batch's three outputs byte for
+ * byte, and xq_samples_to_batch is that call).  For a record whose has_root_stats is 1 (xq_engine_init_rs), in float64, products
+ * and the sum in the order written, no fused multiply-add:
+ *     dev_z[j] = (float)((1.0 - q_mix) * (double)z + q_mix * (double)root_q)
+ * A record without the mark gets (float)z.  The mirror flag does not touch the value; planes and pi do not depend on the option.
+ * XQ_ERR_ARG before any launch: q_mix outside [0, 1] or NaN, a non-zero reserved word, and xq_samples_to_batch's argument rules.
+ * n = 0 is a no-op. */
+typedef struct xq_batch_opts { double q_mix; int32_t reserved[2]; } xq_batch_opts;
+int xq_samples_to_batch_ex(const void *dev_samples, const int32_t *dev_index, const uint8_t *dev_flip, int n,
+                           double late_temperature, const xq_batch_opts *opts, float *dev_states, float *dev_pi, float *dev_z,
+                           void *stream);
 
 /* Finished training sample (compact form of the reference's (state, pi, z) tuple,
  * parallel_selfplay.py:97-99,123-132; dense pi / planes / flip augmentation materialise on the consumer). */

@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""Root statistics per sample (engine.SelfPlayEngine(root_stats=True)): what recording them costs, and
+how the recorded value relates to the game's result.
+
+    python tools/measure_root_stats.py --parent-tree <dir> --out profiles/r16_root_stats_cfg1.json
+
+`--parent-tree` is a built checkout of the PARENT commit (its libxq_hip.so in place).  The "off" runs are taken there, the "on"
+runs on this tree, alternated parent, this, parent, this ... in one call, every run in a fresh child process under `timeout -k`;
+the first failing run ends the measurement.  A child is this file run with the tree it measures first on sys.path; it uses only
+what both trees have.
+
+Per run (preset cfg1 = BASELINE configs[1]: 1024 slots x 400 simulations x 128x6, peaked weights, games_target 1024):
+  (a) complete games through run_games: games/hour; and k_select's time per launch over `--select-steps` eager steps from a
+      staggered start, device events around xq_engine_select alone (the evaluator and the expansion run full width between them).
+      The margin of each figure is the spread (max - min) the PARENT's own repeated runs show in this call.
+  (b) over the samples of the "on" games: the mean of |root_q - z| and the share with sign(root_q) != z per ply bucket.
+      Descriptive only.
+
+Two limits of what this reports.  The `k_select` figure is the time of the whole `eng.select()` call between two device events:
+that is `k_select` alone only because the measured engine has neither tree reuse (which adds `k_reroot` to the call) nor leaf
+batching (which launches `k_select_multi`), so xq_engine_select launches exactly one kernel; the figure includes the events'
+own overhead, equally on both trees.  And the margin is the spread of the parent's runs in this one call: with the default
+`--repeats 2` that is the distance of two runs, a weak margin -- use `--repeats 3` or more where the GPU time allows, and read
+"within_margin" as "not distinguishable here", not as "no cost".
+
+Whether a network trained on the mixed target is stronger is NOT measured here: that takes arena matches over trained networks.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PEAKED_GAIN = 8.0
+PRESETS = {
+    "cfg1": dict(slots=1024, games=1024, sims=400, channels=128, blocks=6, temperature_threshold=20, max_game_length=400,
+                 random_opening_moves=8),
+    "small": dict(slots=256, games=256, sims=64, channels=64, blocks=2, temperature_threshold=20, max_game_length=120,
+                  random_opening_moves=6),
+}
+BUCKETS = ((0, 20), (20, 40), (40, 80), (80, 120), (120, 1 << 16))
+
+
+def _net(channels, blocks, seed=0):
+    from xiangqi_alphazero_amd import model, weights
+    net = model.XiangqiNet(channels, blocks)
+    net.load_state_dict(weights.make_state_dict(channels, blocks, seed=seed, policy_gain=PEAKED_GAIN))
+    return net
+
+
+def _ply_buckets(samples):
+    import numpy as np
+    pad = np.ascontiguousarray(samples["pad"])
+    q = pad[:, 0:4].copy().view(np.float32).reshape(-1)
+    mark = pad[:, 8] == 1
+    z, ply = samples["z"].astype(np.float64), samples["ply"].astype(np.int64)
+    out = []
+    for lo, hi in BUCKETS:
+        m = mark & (ply >= lo) & (ply < hi)
+        n = int(m.sum())
+        out.append({"plies": [lo, None if hi >= 1 << 16 else hi - 1], "samples": n,
+                    "mean_abs_q_minus_z": round(float(np.abs(q[m] - z[m]).mean()), 4) if n else None,
+                    "share_sign_differs": round(float((np.sign(q[m]) != z[m]).mean()), 4) if n else None})
+    return {"marked": int(mark.sum()), "samples": int(len(samples)), "buckets": out}
+
+
+def child(job):
+    import torch
+    from xiangqi_alphazero_amd import engine, evaluator, selfplay
+    p = PRESETS[job["preset"]]
+    on = job["root_stats"] == "on"
+    net = _net(p["channels"], p["blocks"])
+    cfg = types.SimpleNamespace(num_simulations=p["sims"], c_puct=1.5, temperature_threshold=p["temperature_threshold"],
+                                max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
+                                enable_resign=True, resign_threshold=-0.9, resign_check_steps=5)
+    if on:
+        cfg.record_root_stats = True                   # through the config key, as a training loop sets it
+    samples, results, st, elapsed = selfplay.run_games(net, cfg, p["games"], "cuda", n_slots=p["slots"], seed=11, poll_every=256)
+    torch.cuda.synchronize()
+    assert bool(st.get("root_stats", False)) == on and int(st["overflow"]) == 0
+    row = {"preset": job["preset"], "tree": job["tree"], "root_stats": on, "path": st["path"], "launch": st["launch"],
+           "games": int(len(results)), "samples": int(len(samples)), "wall_s": round(elapsed, 2),
+           "games_per_hour": round(len(results) * 3600.0 / elapsed, 1), "mean_plies": round(float(results["steps"].mean()), 2),
+           "moves": int(st["moves_played"]), "sims": int(st["sims"])}
+    if on:
+        row["root_q_against_z"] = _ply_buckets(samples)
+    # k_select alone: eager steps from a staggered start, the stages called one by one, events around the select launch
+    ev = evaluator.make_evaluator(net, "cuda", "hip")[0]
+    ecfg = engine.make_config(p["slots"], p["sims"], seed=5, start_stagger=True, max_out_samples=p["slots"] * 16)
+    eng = engine.SelfPlayEngine(ecfg, evaluator=ev, **({"root_stats": True} if on else {}))
+    steps, warm = int(job["select_steps"]), 32
+    pairs = []
+    for i in range(warm + steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        x = eng.select()
+        b.record()
+        eng.evaluate_and_expand(x)
+        if i >= warm:
+            pairs.append((a, b))
+        if i % 256 == 255:
+            eng.drain_device()
+    torch.cuda.synchronize()
+    ms = sorted(a.elapsed_time(b) for a, b in pairs)
+    est = eng.stats()
+    assert int(est["overflow"]) == 0
+    row.update(k_select_us_mean=round(1000.0 * sum(ms) / len(ms), 3), k_select_us_median=round(1000.0 * ms[len(ms) // 2], 3),
+               select_steps=steps, select_moves=int(est["moves_played"]))
+    return row
+
+
+def _group(rows, key):
+    v = [r[key] for r in rows]
+    return {"runs": v, "min": min(v), "max": max(v), "mean": round(sum(v) / len(v), 3), "spread": round(max(v) - min(v), 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--preset", choices=sorted(PRESETS), default="cfg1")
+    ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit: the `off` runs are taken there")
+    ap.add_argument("--repeats", type=int, default=2, help="parent/this pairs")
+    ap.add_argument("--select-steps", type=int, default=600)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
+    ap.add_argument("--child", default=None)
+    args = ap.parse_args()
+    if args.child:
+        job = json.loads(args.child)
+        sys.path.insert(0, job["tree_path"])
+        print("RESULT " + json.dumps(child(job)), flush=True)
+        return
+    if not args.parent_tree or not os.path.isdir(os.path.join(args.parent_tree, "xiangqi-alphazero_amd")):
+        sys.exit("--parent-tree: a built checkout of the parent commit is required (the `off` runs are taken on it)")
+    trees = {"parent": os.path.abspath(args.parent_tree), "this": ROOT}
+    out = {"tool": "tools/measure_root_stats.py", "preset": dict(PRESETS[args.preset], name=args.preset), "weights": "peaked",
+           "order": [], "runs": []}
+    for _ in range(args.repeats):
+        for tree, rs in (("parent", "off"), ("this", "on")):
+            job = dict(preset=args.preset, tree=tree, tree_path=trees[tree], root_stats=rs, select_steps=args.select_steps)
+            t0 = time.time()
+            cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", json.dumps(job)]
+            r = subprocess.run(cmd, cwd=trees[tree], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
+            if r.returncode != 0 or line is None:
+                print(r.stdout[-3000:], file=sys.stderr)
+                print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
+                out["failed"] = dict(job=job, exit=r.returncode)
+                break
+            row = json.loads(line[7:])
+            row["child_wall_s"] = round(time.time() - t0, 1)
+            print(json.dumps(row), flush=True)
+            out["order"].append(tree)
+            out["runs"].append(row)
+        if "failed" in out:
+            break
+    par, this = [r for r in out["runs"] if r["tree"] == "parent"], [r for r in out["runs"] if r["tree"] == "this"]
+    if par and this:
+        out["summary"] = {}
+        for key in ("games_per_hour", "k_select_us_mean", "k_select_us_median"):
+            p, t = _group(par, key), _group(this, key)
+            out["summary"][key] = {"parent_off": p, "this_on": t, "delta_of_means": round(t["mean"] - p["mean"], 3),
+                                   "margin_parent_spread": p["spread"],
+                                   "within_margin": abs(t["mean"] - p["mean"]) <= p["spread"]}
+        out["summary"]["root_q_against_z"] = this[-1].get("root_q_against_z")
+        print(json.dumps(out["summary"], indent=1))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+    sys.exit(1 if "failed" in out else 0)
+
+
+if __name__ == "__main__":
+    main()

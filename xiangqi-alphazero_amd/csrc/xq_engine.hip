@@ -34,6 +34,8 @@
 
 static_assert(sizeof(xq_sample) == XQ_SAMPLE_BYTES, "xq_sample layout");
 static_assert(sizeof(xq_game_result) == XQ_RESULT_BYTES, "xq_game_result layout");
+static_assert(sizeof(xq_sample_root_stats) == 20 && offsetof(xq_sample, pad) == XQ_SAMPLE_ROOT_STATS_OFFSET &&
+                  sizeof(((xq_sample *)0)->pad) == sizeof(xq_sample_root_stats), "xq_sample_root_stats overlays xq_sample.pad");
 
 namespace {
 
@@ -471,6 +473,7 @@ __device__ __forceinline__ void wave_prune_visits(const Dev &E, Slot &s, SelectL
 // full_move false (a fast move of the playout cap) stages no sample; pruned: the visits are wave_prune_visits' counts in
 // L.w_tmp (wave_prune_visits', or wave_solver_counts').  Leaves child i's action in L.a_tmp[i]; the caller plays the returned
 // action.  proven >= 0 (SOLVER, rule 4): child `proven` is played, no temperature, no uniform draw, the sample says reserved1 = 1.
+// E.root_stats (xq_engine_init_rs): a staged sample also takes the root's search value, visits and mark into its pad bytes.
 __device__ __forceinline__ int slot_end_move(const Dev &E, Slot &s, SelectLds &L, bool full_move, bool pruned, int nch, int first,
                                              int proven = -1) {
     const Tree &T = s.T;
@@ -488,6 +491,24 @@ __device__ __forceinline__ int slot_end_move(const Dev &E, Slot &s, SelectLds &L
             r->side = (int8_t)s.side; r->z = 0; r->n_moves = (uint8_t)nch; r->late_temp = late ? 1 : 0;
             r->ply = (uint16_t)s.mc; r->slot = (uint32_t)s.slot; r->game_seq = (uint32_t)s.game_seq;
             if (proven >= 0) r->reserved1 = 1;
+        }
+        if (E.root_stats) {
+            // xq_engine_init_rs: the root's search value over the RAW tree arrays (before pruning and rule 5's counts).  sumN is
+            // an exact integer reduction; sumW is one sequential float64 scan in move order over LDS, the same in every lane, so a
+            // host model repeats it bit for bit.  L.sw is free here: the action-id sort below rewrites it after the next wave_sync.
+            int sum_n = 0;
+            for (int i = lane; i < nch; i += 64) { L.sw[i] = T.W[first + i]; sum_n += T.N[first + i]; }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) sum_n += __shfl_xor(sum_n, off);
+            wave_sync();
+            double sum_w = 0.0;
+            for (int i = 0; i < nch; ++i) sum_w += L.sw[i];
+            if (lane == 0) {
+                xq_sample_root_stats *rs = (xq_sample_root_stats *)(rec + XQ_SAMPLE_ROOT_STATS_OFFSET);
+                rs->root_q = proven >= 0 ? 1.0f : (sum_n > 0 ? (float)(sum_w / (double)sum_n) : 0.0f);
+                rs->root_visits = (uint32_t)sum_n;
+                rs->has_root_stats = 1;
+            }
         }
     }
     for (int i = lane; i < nch; i += 64) {

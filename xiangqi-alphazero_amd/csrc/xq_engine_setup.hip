@@ -17,7 +17,9 @@ struct Opts {
     const xq_arena_opts *arena;
     const xq_rules_opts *rules;     // absent from an initialiser: NULL, the reference's rules
     const xq_solver_opts *solver;   // absent, NULL or enabled = 0: no proven-result search
+    const xq_root_stats_opts *root_stats;   // absent, NULL or enabled = 0: the samples' pad bytes stay zero
     bool solver_on() const { return solver && solver->enabled != 0; }
+    bool root_stats_on() const { return root_stats && root_stats->enabled != 0; }
 };
 
 struct Layout {
@@ -140,10 +142,19 @@ bool solver_ok(const Opts &o) {
     return sv->enabled == 0 || (o.K == 1 && !o.gumbel && !o.forced);
 }
 
+// root statistics per sample: enabled 0 or 1, reserved words zero; on, it needs an engine that records samples (self-play) and
+// goes with everything but Gumbel root search, whose root value is its own v_mix
+bool root_stats_ok(const xq_engine_config *c, const Opts &o) {
+    const xq_root_stats_opts *rs = o.root_stats;
+    if ((rs->enabled != 0 && rs->enabled != 1) || rs->reserved[0] != 0 || rs->reserved[1] != 0 || rs->reserved[2] != 0) return false;
+    return rs->enabled == 0 || (c && c->manual_moves == 0 && !o.gumbel);
+}
+
 // every option check, in the order the entry points have always refused in; an absent option passes
 bool opts_ok(const xq_engine_config *c, const Opts &o) {
     if (o.rules && !rules_ok(o.rules)) return false;
     if (o.solver && !solver_ok(o)) return false;
+    if (o.root_stats && !root_stats_ok(c, o)) return false;
     if (!config_ok(c) || !leaves_ok(c, o.K) || !flags_ok(c, o.K, o.flags)) return false;
     if (o.cap && !cap_ok(c, o.K, o.cap)) return false;
     if (o.forced && !forced_ok(c, o.K, o.forced)) return false;
@@ -236,7 +247,8 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
     eng->pad0 = (K > 1 ? K : 0) | (int)(o.flags << 16) | (o.cap ? PAD0_CAP : 0) | (o.forced ? PAD0_FORCED : 0) |
                 (o.gumbel ? PAD0_GUMBEL : 0) | (o.arena ? PAD0_ARENA : 0) |
-                (o.rules && o.rules->perpetual_check ? PAD0_PERPETUAL : 0) | (o.solver_on() ? PAD0_SOLVER : 0);
+                (o.rules && o.rules->perpetual_check ? PAD0_PERPETUAL : 0) | (o.solver_on() ? PAD0_SOLVER : 0) |
+                (o.root_stats_on() ? PAD0_ROOT_STATS : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -337,6 +349,12 @@ size_t xq_engine_workspace_bytes_sv(const xq_engine_config *cfg, int leaves_per_
     return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver});
 }
 
+size_t xq_engine_workspace_bytes_rs(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats) {
+    return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats});
+}
+
 int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out) {
     if (k < 1 || k > XQ_MAXM || num_simulations < 1 || num_simulations > 65535 || !host_out) return XQ_ERR_ARG;
     gz_considered_visits(k, num_simulations, host_out);
@@ -392,6 +410,14 @@ int xq_engine_init_sv(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       void *stream) {
     return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver}, ws, ws_bytes, dev_inject,
                        stream);
+}
+
+int xq_engine_init_rs(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats, void *ws,
+                      size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
+    return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats}, ws, ws_bytes,
+                       dev_inject, stream);
 }
 
 int xq_engine_solver_stats_read(const xq_engine *eng, xq_solver_stats *host_out, void *stream) {

@@ -52,6 +52,7 @@ enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_
 enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM = 3 };
 
 constexpr int PAD0_PERPETUAL = 1 << 26;     // pad0 of the handle (encoding below): "perpetual-check rule on"
+constexpr int PAD0_ROOT_STATS = 1 << 24;    // "root statistics per sample on" (xq_engine_init_rs)
 
 // The node meta word tM: the child count in bits 0-11 (at most XQ_MAXM = 128), the node's proven state in bits 12-13 (always 0
 // without xq_engine_init_sv: every reader masks the count, and an engine without the solver stays byte-identical), the prior
@@ -81,6 +82,7 @@ struct Dev {
     double *mnoise;
     int32_t *req;                   // [G] legal moves of the evaluation each slot asked for this step (0: none)
     int perpetual;                  // xq_rules_opts.perpetual_check of xq_engine_init_ru (wave-uniform: a kernel argument)
+    int root_stats;                 // xq_root_stats_opts.enabled of xq_engine_init_rs (wave-uniform, like perpetual)
 };
 
 Dev make_dev(const xq_engine *e) {
@@ -97,6 +99,7 @@ Dev make_dev(const xq_engine *e) {
     d.stats = (unsigned long long *)e->p[P_STATS]; d.inject = (const uint64_t *)e->p[P_INJECT];
     d.sqrt_tab = (const double *)e->p[P_SQRT]; d.mnoise = (double *)e->p[P_MNOISE]; d.req = (int32_t *)e->p[P_REQ];
     d.perpetual = (e->pad0 & PAD0_PERPETUAL) != 0;
+    d.root_stats = (e->pad0 & PAD0_ROOT_STATS) != 0;
     return d;
 }
 
@@ -157,8 +160,8 @@ __host__ __device__ inline size_t sv_bytes(size_t G) { return G * SV_WORDS * 8; 
 
 // pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
 // flag bits "playout cap on" (xq_engine_init_cap), "forced playouts on" (xq_engine_init_fp) and "Gumbel root search on"
-// (xq_engine_init_gz), "arena options on" (xq_engine_init_ar), "perpetual-check rule on" (xq_engine_init_ru) and "proven-result
-// search on" (xq_engine_init_sv)
+// (xq_engine_init_gz), "arena options on" (xq_engine_init_ar), "perpetual-check rule on" (xq_engine_init_ru), "proven-result
+// search on" (xq_engine_init_sv) and "root statistics per sample on" (xq_engine_init_rs, PAD0_ROOT_STATS above)
 constexpr int PAD0_CAP = 1 << 30;
 constexpr int PAD0_FORCED = 1 << 29;
 constexpr int PAD0_GUMBEL = 1 << 28;

@@ -11,9 +11,11 @@ namespace {
 // compact 640-byte samples -> dense float32 planes [15][10][9], dense float32 pi[8100] (visits^(1/T) normalised in
 // float64, then cast, as torch.FloatTensor(policy) does) and z; `flip` mirrors the columns of the board and of both
 // squares of every action.  One wavefront per output sample; HBM-bound (37.8 KB written per sample).
+// q_mix != 0 (xq_samples_to_batch_ex): a record that carries root statistics (xq_engine_init_rs) gets the mixed value target
+// (1 - q_mix) z + q_mix root_q, float64, products and sum in that order, uncontracted, cast once; every other record keeps z.
 __global__ __launch_bounds__(64) void k_samples_to_batch(const xq_sample *__restrict__ rec, const int32_t *__restrict__ idx,
                                                          const uint8_t *__restrict__ flip, int n, double late_temperature,
-                                                         float *__restrict__ states, float *__restrict__ pi,
+                                                         double q_mix, float *__restrict__ states, float *__restrict__ pi,
                                                          float *__restrict__ z) {
     const int o = blockIdx.x;
     if (o >= n) return;
@@ -56,7 +58,15 @@ __global__ __launch_bounds__(64) void k_samples_to_batch(const xq_sample *__rest
         }
         pi[(size_t)o * XQ_ACTION_SPACE + a] = total > 0.0 ? (float)(w / total) : 0.0f;
     }
-    if (lane == 0) z[o] = (float)s->z;
+    if (lane == 0) {
+        const xq_sample_root_stats *rs = (const xq_sample_root_stats *)((const uint8_t *)s + XQ_SAMPLE_ROOT_STATS_OFFSET);
+        float zv = (float)s->z;
+        if (q_mix != 0.0 && rs->has_root_stats == 1) {
+            const double a = (1.0 - q_mix) * (double)s->z, b = q_mix * (double)rs->root_q;
+            zv = (float)(a + b);
+        }
+        z[o] = zv;
+    }
 }
 
 __global__ __launch_bounds__(256) void k_bias_act(float4 *__restrict__ y, const float4 *__restrict__ bias,
@@ -300,14 +310,21 @@ extern "C" int xq_bias_act(float *dev_y, const float *dev_bias, const float *dev
     return xq::launch_status();
 }
 
-extern "C" int xq_samples_to_batch(const void *dev_samples, const int32_t *dev_index, const uint8_t *dev_flip, int n,
-                                   double late_temperature, float *dev_states, float *dev_pi, float *dev_z, void *stream) {
+extern "C" int xq_samples_to_batch_ex(const void *dev_samples, const int32_t *dev_index, const uint8_t *dev_flip, int n,
+                                      double late_temperature, const xq_batch_opts *opts, float *dev_states, float *dev_pi,
+                                      float *dev_z, void *stream) {
+    if (opts && (!(opts->q_mix >= 0.0 && opts->q_mix <= 1.0) || opts->reserved[0] != 0 || opts->reserved[1] != 0)) return XQ_ERR_ARG;
     if (n < 0 || (n > 0 && (!dev_samples || !dev_index || !dev_flip || !dev_states || !dev_pi || !dev_z))) return XQ_ERR_ARG;
     if (late_temperature <= 0.0 || ((uintptr_t)dev_pi & 15)) return XQ_ERR_ARG;
     if (n == 0) return XQ_OK;
     hipLaunchKernelGGL(k_samples_to_batch, dim3(n), dim3(64), 0, (hipStream_t)stream, (const xq_sample *)dev_samples, dev_index,
-                       dev_flip, n, late_temperature, dev_states, dev_pi, dev_z);
+                       dev_flip, n, late_temperature, opts ? opts->q_mix : 0.0, dev_states, dev_pi, dev_z);
     return xq::launch_status();
+}
+
+extern "C" int xq_samples_to_batch(const void *dev_samples, const int32_t *dev_index, const uint8_t *dev_flip, int n,
+                                   double late_temperature, float *dev_states, float *dev_pi, float *dev_z, void *stream) {
+    return xq_samples_to_batch_ex(dev_samples, dev_index, dev_flip, n, late_temperature, nullptr, dev_states, dev_pi, dev_z, stream);
 }
 
 static int heads_1x1(const float *dev_h, const float *dev_w, const float *dev_bias, float *dev_p, float *dev_v, long long rows,

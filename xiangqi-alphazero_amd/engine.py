@@ -80,6 +80,11 @@ sample then carries `reserved1` = 1), and a losing child's visits leave the samp
 reads the states at a root, `solver_stats` (merged into `stats()`) the five counters.  Self-play with tree reuse, the playout cap
 and the evaluation cache, search only, arena games, the perpetual-check rule; not with leaves_per_step > 1, gumbel or
 forced_playouts.
+
+With `root_stats=True` (opt-in; xq_engine_init_rs) every sample carries the search's own value of its
+position in its 20 spare bytes (`sample_format.root_stats`): `root_q` from the view of the side to move, `root_visits`, and the
+mark `has_root_stats`.  `ReplayBuffer.batch(..., q_mix=...)` mixes it into the value target.  Nothing else about the games
+changes.  Self-play only; every other option but gumbel.
 """
 from __future__ import annotations
 
@@ -136,6 +141,7 @@ class EngineOptions(collections.namedtuple("EngineOptions", "K flags cap forced 
     # the tuple is the argument list of xq_engine_*_ar; `rules` (hip.RulesOpts or None) is what xq_engine_*_ru take after it
     rules = None
     solver = None              # hip.SolverOpts or None: what xq_engine_*_sv take after `rules`
+    root_stats = None          # hip.RootStatsOpts or None: what xq_engine_*_rs take after `solver`
 
 
 RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_game_over, and its perpetual-check verdict
@@ -143,7 +149,7 @@ RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_
 
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
                          forced_playouts=None, gumbel=None, arena_opts=None, eval_cache_entries: int = 0,
-                         perpetual_check: bool = False, solver: bool = False) -> EngineOptions:
+                         perpetual_check: bool = False, solver: bool = False, root_stats: bool = False) -> EngineOptions:
     """The engine options of `SelfPlayEngine` checked and turned into the C structs; needs no GPU.  Every rule of the header's
     refusal lists (include/xq_hip.h; opts_ok in csrc/xq_engine_setup.hip) is refused here first, with a message that names the
     option; tests/test_engine_options.py holds the two side by side."""
@@ -238,9 +244,17 @@ def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tre
         raise hip.XqError("solver cannot be combined with gumbel: its equal-visit candidates cannot skip a child")
     if solver and forced is not None:
         raise hip.XqError("solver cannot be combined with forced_playouts")
+    if root_stats not in (False, True, 0, 1):
+        raise hip.XqError(f"root_stats must be a bool, got {root_stats!r}")
+    if root_stats and int(cfg.manual_moves) != 0:
+        raise hip.XqError("root_stats is a self-play option: search-only (manual_moves = 1) and arena (2) engines record no samples")
+    if root_stats and gz is not None:
+        raise hip.XqError("root_stats cannot be combined with gumbel: a Gumbel root's value is its own v_mix")
     opts = EngineOptions(K, hip.ENGINE_TREE_REUSE if tree_reuse else 0, cap, forced, gz, ar)
     if solver:
         opts.solver = hip.SolverOpts(1)
+    if root_stats:
+        opts.root_stats = hip.RootStatsOpts(1)
     if perpetual_check:                                # a verdict, not a search option: it goes with every mode and option
         opts.rules = hip.RulesOpts(1)
     return opts
@@ -250,13 +264,13 @@ class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
-                 perpetual_check: bool = False, solver: bool = False):
+                 perpetual_check: bool = False, solver: bool = False, root_stats: bool = False):
         opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
             gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check,
-            solver=solver)
+            solver=solver, root_stats=root_stats)
         K, flags, cap, forced, gz, ar = opts
-        rules, sv = opts.rules, opts.solver
+        rules, sv, rs = opts.rules, opts.solver, opts.root_stats
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
@@ -271,11 +285,12 @@ class SelfPlayEngine:
         self.arena_opts = None if ar is None else (ar.opening_plies, ar.first_game)
         self.perpetual_check = rules is not None
         self.solver = sv is not None
+        self.root_stats = rs is not None
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         # every entry point is the widest one with NULL for the options it does not take (include/xq_hip.h)
-        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules, sv)]
-        nbytes = self.lib.xq_engine_workspace_bytes_sv(C.byref(cfg), K, flags, *refs)
+        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules, sv, rs)]
+        nbytes = self.lib.xq_engine_workspace_bytes_rs(C.byref(cfg), K, flags, *refs)
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
@@ -291,8 +306,8 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            hip.check(self.lib.xq_engine_init_sv(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
-                                                 hip.stream_ptr(self.device)), "xq_engine_init_sv")
+            hip.check(self.lib.xq_engine_init_rs(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
+                                                 hip.stream_ptr(self.device)), "xq_engine_init_rs")
         # zero-copy int32 view of the per-slot state words (columns hip.GI_*: side to move of the REAL game, move_count, phase,
         # simulations done): host-side policies such as the arena's model choice read it between stages
         gi_off = int(self.h.p[hip.P_GI]) - int(self.ws.data_ptr())

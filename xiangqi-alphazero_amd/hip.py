@@ -121,6 +121,16 @@ class SolverOpts(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class RootStatsOpts(C.Structure):
+    """xq_root_stats_opts: the root's search value per sample (xq_engine_init_rs): enabled 0 / 1."""
+    _fields_ = [("enabled", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class BatchOpts(C.Structure):
+    """xq_batch_opts: the q-mixed value target of xq_samples_to_batch_ex: q_mix in [0, 1]."""
+    _fields_ = [("q_mix", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
 class SolverStats(C.Structure):
     """xq_solver_stats: the proven-result search's counters (xq_engine_solver_stats_read)."""
     _fields_ = [(n, C.c_uint64) for n in ("proven_nodes", "proven_stops", "proven_moves", "unspent_sims", "removed_visits")] + \
@@ -215,6 +225,9 @@ def lib():
     L.xq_engine_workspace_bytes_sv.argtypes = L.xq_engine_workspace_bytes_ru.argtypes + [C.POINTER(SolverOpts)]
     L.xq_engine_workspace_bytes_sv.restype = C.c_size_t
     L.xq_engine_init_sv.argtypes = L.xq_engine_init_ru.argtypes[:9] + [C.POINTER(SolverOpts)] + L.xq_engine_init_ru.argtypes[9:]
+    L.xq_engine_workspace_bytes_rs.argtypes = L.xq_engine_workspace_bytes_sv.argtypes + [C.POINTER(RootStatsOpts)]
+    L.xq_engine_workspace_bytes_rs.restype = C.c_size_t
+    L.xq_engine_init_rs.argtypes = L.xq_engine_init_sv.argtypes[:10] + [C.POINTER(RootStatsOpts)] + L.xq_engine_init_sv.argtypes[10:]
     L.xq_engine_read_root_states.argtypes = [C.POINTER(Engine), i32, vp, vp, vp]
     L.xq_engine_solver_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(SolverStats), vp]
     L.xq_engine_arena_openings.argtypes = [C.POINTER(Engine), C.POINTER(vp), C.POINTER(vp)]
@@ -233,6 +246,7 @@ def lib():
     L.xq_heads_1x1.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, i32, vp]
     L.xq_stem_conv.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.xq_samples_to_batch.argtypes = [vp, vp, vp, i32, C.c_double, vp, vp, vp, vp]
+    L.xq_samples_to_batch_ex.argtypes = [vp, vp, vp, i32, C.c_double, C.POINTER(BatchOpts), vp, vp, vp, vp]
     L.xq_wino_weight_bytes.argtypes = [i32]
     L.xq_wino_weight_bytes.restype = C.c_size_t
     L.xq_wino_conv3x3.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
@@ -299,7 +313,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_gumbel_considered_visits_host", "xq_engine_workspace_bytes_ar", "xq_engine_init_ar", "xq_engine_arena_openings",
            "xq_engine_compact_arena", "xq_engine_packed_arena", "xq_engine_expand_packed_arena",
            "xq_engine_workspace_bytes_ru", "xq_engine_init_ru", "xq_game_over_batch_ex",
-           "xq_engine_workspace_bytes_sv", "xq_engine_init_sv", "xq_engine_read_root_states", "xq_engine_solver_stats_read"]
+           "xq_engine_workspace_bytes_sv", "xq_engine_init_sv", "xq_engine_read_root_states", "xq_engine_solver_stats_read",
+           "xq_engine_workspace_bytes_rs", "xq_engine_init_rs", "xq_samples_to_batch_ex"]
 
 
 def check(rc: int, what: str):

@@ -20,6 +20,10 @@ repetition one side forced by checking on every move is that side's loss at the 
 `solver=True` (opt-in) searches with proven results (engine.SelfPlayEngine): `get_action` at temperature 0
 returns the proven winning move when the search found one, and never a move shown to lose while another is not (`solver_choice`
 over the root's visits and `read_root_states`); `search`'s pi stays the visit counts'.
+
+`search_many(..., return_values=True)` also returns the search's value of every position, from the view of its side to move
+(`root_value`: the engine's root_q arithmetic of DESIGN.md section 4.13 over `read_root`'s arrays); `root_values` keeps the last
+search's.
 """
 from __future__ import annotations
 
@@ -44,6 +48,17 @@ def solver_choice(actions, visits, child_states) -> int:
     return int(actions[int(np.argmax(v))])
 
 
+def root_value(visits, total_value) -> np.float32:
+    """The root's search value from the view of the side to move, as an engine with root_stats=True records it
+    (include/xq_hip.h, xq_engine_init_rs): one sequential float64 sum of the children's W in move order over the sum of their N,
+    cast to float32 once; 0.0 for a position without legal moves or without visits."""
+    sum_w, sum_n = 0.0, 0
+    for w, n in zip(np.asarray(total_value, dtype=np.float64).tolist(), np.asarray(visits).tolist()):
+        sum_w += w
+        sum_n += int(n)
+    return np.float32(sum_w / float(sum_n)) if sum_n > 0 else np.float32(0.0)
+
+
 class MCTS:
     def __init__(self, model, num_simulations: int = 200, c_puct: float = 1.5, device: str = "cuda",
                  evaluator_kind: str = "auto", seed: int = 0, leaves_per_step: int = 1, perpetual_check: bool = False,
@@ -62,6 +77,7 @@ class MCTS:
         self.evaluator = model if callable(model) and not hasattr(model, "state_dict") else \
             ev_mod.make_evaluator(model, device, evaluator_kind)[0]
         self._engines = {}
+        self.root_values = np.zeros(0, dtype=np.float32)      # the last search's root value per position
 
     def refresh(self, model=None):
         """Re-fold the weights after the caller changed its model in place (or hand over a new one).  The reference's
@@ -82,7 +98,9 @@ class MCTS:
                                                        perpetual_check=self.perpetual_check, solver=self.solver)
         return self._engines[key]
 
-    def search_many(self, games: Sequence, temperature: float = 1.0, add_noise: bool = True) -> List[np.ndarray]:
+    def search_many(self, games: Sequence, temperature: float = 1.0, add_noise: bool = True, return_values: bool = False):
+        """pi float64[8100] per position; with `return_values` (pis, float32[len(games)]): the search's value of every position
+        as well (`root_value`), which `root_values` holds after any search."""
         eng = self._engine(len(games), add_noise)
         for slot, g in enumerate(games):
             hist = [np.frombuffer(h, dtype=np.int8) for h in list(g.history)[-12:]]
@@ -101,13 +119,16 @@ class MCTS:
             if extra > 4 * self.num_simulations + 64:
                 raise RuntimeError("search did not finish")
         out = []
+        values = np.zeros(len(games), dtype=np.float32)
         for slot in range(len(games)):
             r = eng.read_root(slot)
+            values[slot] = root_value(r["visits"], r["total_value"])
             if len(r["actions"]) == 0:
                 out.append(np.zeros(ACTION_SPACE))                       # mcts.py:111-112
             else:
                 out.append(dense_pi(r["actions"], r["visits"].astype(np.float64), temperature))
-        return out
+        self.root_values = values
+        return (out, values) if return_values else out
 
     def search(self, game, temperature: float = 1.0, add_noise: bool = True) -> np.ndarray:
         return self.search_many([game], temperature, add_noise)[0]

@@ -22,6 +22,32 @@ SAMPLE_DTYPE = np.dtype([("board", np.int8, 90), ("side", np.int8), ("z", np.int
 RESULT_DTYPE = np.dtype([("slot", np.uint32), ("game_seq", np.uint32), ("winner", np.int8), ("reason", np.uint8),
                          ("steps", np.uint16), ("n_samples", np.uint16), ("reserved", np.uint16)])
 assert SAMPLE_DTYPE.itemsize == 640 and RESULT_DTYPE.itemsize == 16
+# xq_sample_root_stats: what an engine with root_stats=True (xq_engine_init_rs) writes into a sample's `pad` bytes
+ROOT_STATS_DTYPE = np.dtype([("root_q", np.float32), ("root_visits", np.uint32), ("has_root_stats", np.uint8),
+                             ("zero", np.uint8, 11)])
+assert ROOT_STATS_DTYPE.itemsize == SAMPLE_DTYPE["pad"].itemsize == 20 and SAMPLE_DTYPE.fields["pad"][1] == 108
+
+
+def root_stats(samples: np.ndarray) -> np.ndarray:
+    """The samples' `pad` bytes as ROOT_STATS_DTYPE records, one per sample (a copy when `pad` is not contiguous)."""
+    pad = np.ascontiguousarray(np.asarray(samples)["pad"])
+    return pad.view(ROOT_STATS_DTYPE).reshape(pad.shape[:-1])
+
+
+def mixed_z(samples: np.ndarray, q_mix: float) -> np.ndarray:
+    """The value target of xq_samples_to_batch_ex, float32 per sample: (1 - q_mix) z + q_mix root_q in float64 for a sample
+    that carries root statistics, z for every other sample (and for all of them at q_mix = 0)."""
+    q_mix = float(q_mix)
+    if not 0.0 <= q_mix <= 1.0:
+        raise ValueError(f"q_mix must be in [0, 1], got {q_mix}")
+    samples = np.asarray(samples)
+    z = samples["z"].astype(np.float64)
+    if q_mix == 0.0:
+        return z.astype(np.float32)
+    rs = root_stats(samples)
+    a = (1.0 - q_mix) * z
+    b = q_mix * rs["root_q"].astype(np.float64)
+    return np.where(rs["has_root_stats"] == 1, a + b, z).astype(np.float32)
 
 
 def encode_planes(board: np.ndarray, side: int) -> np.ndarray:
@@ -69,9 +95,10 @@ def flip_sample(state: np.ndarray, pi: np.ndarray) -> Tuple[np.ndarray, np.ndarr
 
 
 def to_reference_tuples(samples: np.ndarray, results: np.ndarray, late_temperature: float = 0.3,
-                        augment: bool = True):
+                        augment: bool = True, q_mix: float = 0.0):
     """-> (all_data, per_game) where all_data is the reference's list of (state, pi, z) with each sample followed by
-    its mirror image, games in result order, plies in order; per_game = [(winner, steps, n_samples)]."""
+    its mirror image, games in result order, plies in order; per_game = [(winner, steps, n_samples)].  q_mix > 0: z is the
+    mixed value target `mixed_z`, as the batch kernel materialises it."""
     all_data: List[tuple] = []
     per_game = []
     key = samples["slot"].astype(np.int64) << 32 | samples["game_seq"].astype(np.int64)
@@ -79,12 +106,13 @@ def to_reference_tuples(samples: np.ndarray, results: np.ndarray, late_temperatu
         k = int(r["slot"]) << 32 | int(r["game_seq"])
         mine = samples[key == k]
         mine = mine[np.argsort(mine["ply"], kind="stable")]
-        for s in mine:
+        zs = mixed_z(mine, q_mix)
+        for s, zq in zip(mine, zs):
             n = int(s["n_moves"])
             t = late_temperature if s["late_temp"] else 1.0
             state = encode_planes(s["board"], int(s["side"]))
             pi = dense_pi(s["actions"][:n], s["visits"][:n].astype(np.float64), t)
-            z = float(s["z"])
+            z = float(zq)
             all_data.append((state, pi, z))
             if augment:
                 fs, fp = flip_sample(state, pi)

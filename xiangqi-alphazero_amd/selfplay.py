@@ -22,11 +22,23 @@ _CFG_KEYS = ("num_simulations", "c_puct", "temperature_threshold", "max_game_len
              "enable_resign", "resign_threshold", "resign_check_steps")     # parallel_selfplay.py:184-187
 
 
+def root_stats_q_mix(config) -> float:
+    """`config.value_target_q_mix` (a reference TrainingConfig has no such key: 0), checked: the share of the search's root value
+    in the value target.  Above 0 it turns the recording of root statistics on and excludes Gumbel root search."""
+    q_mix = float(getattr(config, "value_target_q_mix", 0.0) or 0.0)
+    if not 0.0 <= q_mix <= 1.0:
+        raise hip.XqError(f"config.value_target_q_mix must be in [0, 1], got {q_mix}")
+    if q_mix > 0.0 and int(getattr(config, "gumbel_considered", 0) or 0):
+        raise hip.XqError("config.value_target_q_mix > 0 needs root_stats, which cannot be combined with gumbel "
+                          "(config.gumbel_considered): a Gumbel root's value is its own v_mix")
+    return q_mix
+
+
 def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[int] = None, seed: int = 0, rank: int = 0,
               evaluator_kind: str = "hip", poll_every: int = 64, device_records: bool = False, use_graph: bool = True,
               eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None,
               tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None,
-              perpetual_check: Optional[bool] = None, solver: Optional[bool] = None):
+              perpetual_check: Optional[bool] = None, solver: Optional[bool] = None, root_stats: Optional[bool] = None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -51,7 +63,12 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     with reason 4).  It goes with every other option; gate under the same rule (arena.evaluate_models).
     `solver` (None: `config.mcts_solver`, absent = off) searches with proven results (stats `solver`, `proven_nodes`,
     `proven_stops`, `proven_moves`, `unspent_sims`, `removed_visits`, all 0 when off); it needs K = 1 and
-    neither Gumbel root search nor forced playouts."""
+    neither Gumbel root search nor forced playouts.
+    `root_stats` (None: `config.record_root_stats`, absent = off, or a `config.value_target_q_mix` above 0, which needs them)
+    records the search's value of every sampled position in the sample's spare bytes (`sample_format.root_stats`; stats
+    `root_stats`); the games do not change.  It goes with every option but Gumbel root search."""
+    if root_stats is None:
+        root_stats = bool(getattr(config, "record_root_stats", False)) or root_stats_q_mix(config) > 0.0
     if eval_cache_entries is None:
         eval_cache_entries = int(getattr(config, "eval_cache_entries", 0) or 0)
     if leaves_per_step is None:
@@ -88,7 +105,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
         max_out_samples=num_games * 201, max_out_results=num_games + 8)
     eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries,
                                 leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
-                                forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check, solver=solver)
+                                forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check, solver=solver,
+                                root_stats=root_stats)
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -111,6 +129,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     st["gumbel"] = eng.gumbel                          # None, or (m, c_visit, c_scale)
     st["perpetual_check"] = eng.perpetual_check
     st["solver"] = eng.solver
+    st["root_stats"] = eng.root_stats
     for k in hip.SOLVER_KEYS:                          # the solver's keys are present (0) when it is off
         st.setdefault(k, 0)
     if device_records:
@@ -144,7 +163,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
                                               tree_reuse=tree_reuse, playout_cap=playout_cap,
                                               forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check,
                                               solver=solver)
-    all_data, per_game = to_reference_tuples(samples, results, augment=True)
+    all_data, per_game = to_reference_tuples(samples, results, augment=True, q_mix=root_stats_q_mix(config))
     wins = {1: 0, -1: 0, 0: 0}
     total_steps = 0
     for winner, steps, _n in per_game:
@@ -164,7 +183,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
         "gumbel_moves": st["gumbel_moves"], "gumbel_considered": st["gumbel_considered"],
         "gumbel_offprior": st["gumbel_offprior"], "gumbel": st["gumbel"],
         "perpetual_check": st["perpetual_check"], "perpetual_check_games": st["perpetual_check_games"],
-        "solver": st["solver"], **{k: st[k] for k in hip.SOLVER_KEYS},
+        "solver": st["solver"], **{k: st[k] for k in hip.SOLVER_KEYS}, "root_stats": st["root_stats"],
     }
     if return_compact:
         stats["compact_samples"], stats["compact_results"] = samples, results

@@ -54,6 +54,11 @@ class AlphaZeroLoop:
         self.perpetual_check = bool(getattr(config, "perpetual_check_loses", False))
         # the proven-result search (config.mcts_solver; absent: off), read once as well, for self-play and the gate alike
         self.solver = bool(getattr(config, "mcts_solver", False))
+        # the q-mixed value target (config.value_target_q_mix = lambda, absent: 0; config.record_root_stats): checked here, so a
+        # lambda outside [0, 1] or one with Gumbel root search fails at construction; lambda > 0 turns the recording on.  Read
+        # once: self-play and the train step below are handed these two values and do not read the keys again
+        self.q_mix = selfplay.root_stats_q_mix(config)
+        self.record_root_stats = bool(getattr(config, "record_root_stats", False)) or self.q_mix > 0.0
         torch.manual_seed(seed)                        # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -87,7 +92,8 @@ class AlphaZeroLoop:
                                                     # forced playouts too (config.forced_playouts_k; absent or 0: off): the
                                                     # arena (arena.py) never takes it
                                                     forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None,
-                                                    perpetual_check=self.perpetual_check, solver=self.solver)
+                                                    perpetual_check=self.perpetual_check, solver=self.solver,
+                                                    root_stats=self.record_root_stats)
         # the Gumbel root search (config.gumbel_considered, gumbel_c_visit, gumbel_c_scale; absent or 0: off) reaches the engine
         # through run_games, which reads those keys from the config it is handed; the arena never takes it either
         return samples, results
@@ -121,7 +127,8 @@ class AlphaZeroLoop:
         gen = torch.Generator().manual_seed(self.seed * 1000003 + 7919 * self.iteration + 17)
         if ddp or self.rank == 0:
             stats = training.train_network(self.current_model, self.optimizer, self.scheduler, self.buffer, self.config,
-                                           generator=gen, ddp=ddp, native_bn=bool(getattr(self.config, "native_sync_bn", False)))
+                                           generator=gen, ddp=ddp, native_bn=bool(getattr(self.config, "native_sync_bn", False)),
+                                           q_mix=self.q_mix)
         if self.grouped:
             xdist.broadcast_weights(self.current_model, src=0, device=self.device)
         return stats

@@ -13,6 +13,7 @@ and `best_model.pt` with the same keys, so runs can move between the reference a
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 from typing import Dict, Optional
 
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import hip
+from . import hip, selfplay
 from .sample_format import SAMPLE_DTYPE
 
 
@@ -63,17 +64,28 @@ class ReplayBuffer:
         oldest = (self.head - self.count) % self.cap
         return ((rec + oldest) % self.cap).to(torch.int32), (logical % 2).to(torch.uint8)
 
-    def batch(self, logical: torch.Tensor):
-        """-> states f32[B,15,10,9], pi f32[B,8100], z f32[B,1] for the given logical indices (device int64)."""
+    def root_stats_coverage(self) -> float:
+        """The share of the held records that carry root statistics (has_root_stats, byte 116 of a record: an engine with
+        root_stats=True wrote it); 0.0 for an empty buffer.  Counted on the device over the ring's live records."""
+        if self.count == 0:
+            return 0.0
+        # a ring that has not wrapped holds its records at [0, count); a wrapped one is full
+        mark = self.store[:self.count, 116] == 1
+        return float(mark.sum().item()) / float(self.count)
+
+    def batch(self, logical: torch.Tensor, q_mix: float = 0.0):
+        """-> states f32[B,15,10,9], pi f32[B,8100], z f32[B,1] for the given logical indices (device int64).  q_mix > 0: z is
+        the q-mixed value target of xq_samples_to_batch_ex for the records that carry root statistics."""
         idx, flip = self._record_of(logical.to(self.device))
         b = idx.shape[0]
         states = torch.empty((b, 15, 10, 9), dtype=torch.float32, device=self.device)
         pi = torch.empty((b, hip.ACTION_SPACE), dtype=torch.float32, device=self.device)
         z = torch.empty((b, 1), dtype=torch.float32, device=self.device)
-        hip.check(hip.lib().xq_samples_to_batch(self.store.data_ptr(), idx.contiguous().data_ptr(),
-                                                flip.contiguous().data_ptr(), b, float(self.late_temperature),
-                                                states.data_ptr(), pi.data_ptr(), z.data_ptr(),
-                                                hip.stream_ptr(self.device)), "xq_samples_to_batch")
+        opts = hip.BatchOpts(float(q_mix))
+        hip.check(hip.lib().xq_samples_to_batch_ex(self.store.data_ptr(), idx.contiguous().data_ptr(),
+                                                   flip.contiguous().data_ptr(), b, float(self.late_temperature),
+                                                   C.byref(opts), states.data_ptr(), pi.data_ptr(), z.data_ptr(),
+                                                   hip.stream_ptr(self.device)), "xq_samples_to_batch_ex")
         self._keep = (idx, flip)
         return states, pi, z
 
@@ -120,7 +132,7 @@ def revert_sync_batchnorm(model) -> None:
 
 def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shuffle: bool = True,
                   generator: Optional[torch.Generator] = None, ddp: bool = False, group=None,
-                  native_bn: bool = False) -> Dict[str, float]:
+                  native_bn: bool = False, q_mix: Optional[float] = None) -> Dict[str, float]:
     """One call of the reference's train_network (train.py:376-447) on the device-resident buffer.
 
     `ddp=True` under an initialised torch.distributed group (every rank holds the same buffer and the same weights, as
@@ -130,9 +142,22 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     replicas stay identical, and each GPU runs 1/world of the forward/backward work.  The conversion and the wrapper are
     made once per model (`prepare_ddp`, which documents the side effect on the caller's model).  The batch order comes
     from `generator` (or a generator seeded identically on every rank).  `native_bn=True` (ddp only; opt-in) runs the synchronised
-    BatchNorm of the tower and the stem on the hand-written kernels instead of torch's SyncBatchNorm (`prepare_ddp`)."""
+    BatchNorm of the tower and the stem on the hand-written kernels instead of torch's SyncBatchNorm (`prepare_ddp`).
+
+    `q_mix` (default: the config's `value_target_q_mix`, 0 when it has none): the value head regresses on
+    (1 - q_mix) z + q_mix root_q for the samples that carry root statistics (`ReplayBuffer.batch`), on both paths.  With
+    q_mix > 0 a buffer without a single such sample is refused: the option would silently do nothing.  With q_mix = 0 the
+    step is unchanged; the stats gain "value_target_q_mix"."""
     if len(buffer) < config.min_buffer_size:
         return {}
+    if q_mix is None:                                  # self-play's reader of the key: None, the range, the Gumbel refusal
+        q_mix = selfplay.root_stats_q_mix(config)
+    q_mix = float(q_mix)
+    if not 0.0 <= q_mix <= 1.0:
+        raise hip.XqError(f"value_target_q_mix must be in [0, 1], got {q_mix}")
+    if q_mix > 0.0 and buffer.root_stats_coverage() == 0.0:
+        raise hip.XqError("value_target_q_mix > 0 but no sample in the replay buffer carries root statistics: "
+                          "record them in self-play (record_root_stats / SelfPlayEngine(root_stats=True))")
     import torch.distributed as dist
     use_ddp = bool(ddp and dist.is_initialized())
     world = dist.get_world_size(group) if use_ddp else 1
@@ -162,7 +187,7 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
             if use_ddp and full >= world:                              # this rank's slice of the batch
                 idx = idx.tensor_split(world)[rank]
                 scale = float(world)                                   # DDP averages the ranks' gradients
-            states, target_pi, target_z = buffer.batch(idx)
+            states, target_pi, target_z = buffer.batch(idx, q_mix)
             logits, value = net(states)
             if use_ddp and full >= world:
                 # sums over the local slice, scaled so that DDP's average over ranks is the full-batch mean loss
@@ -185,7 +210,8 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     scheduler.step()
     total_p, total_v = totals.tolist() if totals is not None else (0.0, 0.0)
     return {"policy_loss": total_p / max(batches, 1), "value_loss": total_v / max(batches, 1),
-            "total_loss": (total_p + total_v) / max(batches, 1), "learning_rate": optimizer.param_groups[0]["lr"]}
+            "total_loss": (total_p + total_v) / max(batches, 1), "learning_rate": optimizer.param_groups[0]["lr"],
+            "value_target_q_mix": q_mix}
 
 
 def save_checkpoint(checkpoint_dir: str, iteration: int, current_model, best_model, optimizer, scheduler, total_games: int,
