@@ -585,6 +585,67 @@ int xq_engine_init_rs(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats, void *ws,
                       size_t ws_bytes, const uint64_t *dev_inject, void *stream);
 
+/* Evaluation mirror (opt-in; mirror == NULL or mode = 0 is xq_engine_init_rs exactly -- same workspace bytes, same handle, same
+ * kernels launched, same bytes out -- and xq_engine_init_rs is that call).  Xiangqi is left-right symmetric and the trainer doubles
+ * every sample by its mirror image, but a search evaluates every request in the orientation its game happens to be in, so whatever
+ * left/right asymmetry the network has is backed up into every W with one sign.  With the option each request of the PACKED step is
+ * evaluated under a randomly chosen symmetry (AlphaGo Zero; KataGo's self-play does the same): one random bit per request, and the
+ * values a search backs up average over the two orientations at no extra evaluator cost.  Outside the reference-parity contract,
+ * like the other opt-in options.  mode: 0 off, 1 random; reserved = 0.
+ * THE MIRRORED ROW (one device function; xq_mirror_requests_batch runs it over caller-owned rows):
+ *     planes  float[15][10][9]: out[p][r][c] = in[p][r][8 - c] in all 15 planes; the centre column maps to itself.
+ *     moves   uint16[XQ_MAXM], a = from * 90 + to: both squares' columns go to 8 - c, the arithmetic of xq_samples_to_batch's flip:
+ *                 mirror(a) = ((from / 9) * 9 + 8 - from % 9) * 90 + (to / 9) * 9 + 8 - to % 9
+ *             word i of the output is mirror(word i of the input): the list keeps its ORDER.  xq_policy_head_legal returns
+ *             out[i] for moves[i], so the evaluator's logits come back already un-mirrored and xq_engine_expand_packed does
+ *             not know of the option.  (The mirrored position's own move generation lists the same moves as a set, in another
+ *             order for most positions: the list must be mirrored in place, not regenerated.)
+ *     count   copied.
+ *     All XQ_MAXM words are written.  A word at or past the count, or a word that is no action id (>= 8100), is copied as it is:
+ *     no evaluator kernel reads past the count.
+ * THE BIT of a request is a pure function of (seed, rank, slot, game_seq, ply, is_root, sims_done, row):
+ *           h   = philox_u64(seed, rank, slot, 9, game_seq, ply & 0xFFFFFF)
+ *           r   = philox_u64(h,    rank, slot, 9, (is_root << 31) | (row << 16) | sims_done, 0)
+ *           bit = r >> 63
+ *     philox_u64(key, rank, slot, kind, ctr, sub) is the engine's Philox4x32-10: key words (key low, key high), counter words
+ *     (slot, kind | sub << 8, ctr, rank), the result is output word 0 in the high half and word 1 in the low half.  Kind 9: no other
+ *     draw uses it (0-3 are the four per-slot streams, 7 the start stagger, 8 the arena openings).  The first draw is the key of
+ *     the second, so the eight coordinates fit the 32-bit ctr and the 24-bit sub.
+ *     The mirrored gather reads the coordinates after xq_engine_select from the slot's state words: game_seq and ply (move_count)
+ *     of the real game, is_root = the slot waits for its root's evaluation, sims_done = the simulations done of the current
+ *     search (taken as 0 for a root request), row = the request's index among the slot's leaves_per_step rows (0 with K = 1).
+ *     No step counter and no state word: eager, graph-replayed and repeated runs agree, and the four per-slot draw streams do
+ *     not move -- games with the option on differ from games with it off only through the network's answers.
+ *     xq_eval_mirror_bit_host runs the same code on the host and returns 0 or 1; XQ_ERR_ARG for rank, slot or ply < 0, is_root
+ *     outside {0, 1}, sims_done outside [0, 16000), row outside [0, 64).
+ * WHERE IT ACTS: only in xq_engine_compact, whose gather is then a separate kernel that copies a row whose bit is 0 as before
+ * and writes the mirrored row when it is 1; it takes everything from device memory, so the step records into a graph as before.
+ * A full-width host (xq_engine_requests + xq_engine_expand_legal) gets NO mirroring: the requests it reads are the slots' own.
+ * xq_engine_compact_misses on a mirror engine returns XQ_ERR_ARG: an evaluation-cache hit would return whichever orientation was
+ * evaluated first, and the cache's promise of identical games would be false.
+ * Allowed: manual_moves 0 and 1, leaf batching, tree reuse, the playout cap, forced playouts, Gumbel root search, the solver, the
+ * perpetual-check rule and root statistics.  XQ_ERR_ARG before any launch (xq_engine_workspace_bytes_em: 0): mode outside {0, 1};
+ * a non-zero reserved word; mode = 1 with manual_moves = 2 (arena engines, with or without arena options: the gate stays
+ * deterministic, and xq_engine_compact_arena shares the plain gather and stays as it is); and whatever xq_engine_init_rs refuses.
+ * No workspace, no state word, no counter: "evaluation mirror on" lives in the handle (pad0, bit 31).
+ * xq_mirror_requests_batch: rows r < n of dev_x (float32[n][15][10][9], 8-byte aligned), dev_moves (uint16[n][XQ_MAXM]) and
+ * dev_counts go to dev_x_out / dev_moves_out, mirrored where dev_flags[r] != 0 (uint8[n]) and copied otherwise; nothing past row
+ * n is written.  n = 0 is a no-op; n < 0, a null pointer, a misaligned pointer or an output that is its input return XQ_ERR_ARG.
+ * xq_mirror_action_host: mirror(a) on the host, XQ_ERR_ARG outside [0, 8100). */
+typedef struct xq_eval_mirror_opts { int32_t mode; int32_t reserved[3]; } xq_eval_mirror_opts;
+size_t xq_engine_workspace_bytes_em(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                                    const xq_eval_mirror_opts *mirror);
+int xq_engine_init_em(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                      const xq_eval_mirror_opts *mirror, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream);
+int xq_eval_mirror_bit_host(uint64_t seed, int rank, int slot, uint32_t game_seq, int ply, int is_root, int sims_done, int row);
+int xq_mirror_action_host(int action);
+int xq_mirror_requests_batch(const float *dev_x, const uint16_t *dev_moves, const int32_t *dev_counts, const uint8_t *dev_flags, int n,
+                             float *dev_x_out, uint16_t *dev_moves_out, void *stream);
+
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input /* [G][15][90] */, void *stream);
 
 /* dev_policy[slot] = float32[8100]: network LOGITS (policy_is_probs = 0; softmax over all 8100 as

@@ -29,6 +29,90 @@ __global__ __launch_bounds__(256) void k_gather_rows(Dev E, const int32_t *__res
     if (t == 0) counts[r] = E.req[slot];
 }
 
+// Evaluation mirror (xq_engine_init_em, opt-in; rules in include/xq_hip.h).  The board is left-right symmetric, so a request may be
+// evaluated in either orientation; the gather below hands the evaluator the mirrored row when the request's bit is 1.  The move
+// list is mirrored IN PLACE -- word i stays word i -- so k_policy_legal's out[i] is the logit of the original move i and
+// k_scatter_rows / k_expand see nothing of it.
+
+// one action id under the mirror: both squares' columns c -> 8 - c (k_samples_to_batch's arithmetic); an involution over [0, 8100)
+__host__ __device__ inline int mirror_action(int a) {
+    const int from = a / 90, to = a - from * 90;
+    const int fr = from / 9, fc = from - fr * 9, tr = to / 9, tc = to - tr * 9;
+    return (fr * 9 + (8 - fc)) * 90 + tr * 9 + (8 - tc);
+}
+
+// The bit of one request: include/xq_hip.h writes the packing out.  Philox stream kind 9, two draws: the first keys the second.
+__host__ __device__ inline int eval_mirror_bit(uint64_t seed, uint32_t rank, uint32_t slot, uint32_t game_seq, uint32_t ply,
+                                               uint32_t is_root, uint32_t sims_done, uint32_t row) {
+    const uint64_t h = philox_u64(seed, rank, slot, 9u, game_seq, ply & 0xFFFFFFu);
+    const uint64_t r = philox_u64(h, rank, slot, 9u, (is_root << 31) | (row << 16) | sims_done, 0u);
+    return (int)(r >> 63);
+}
+
+// One request row, by the 256 threads of a workgroup (t = threadIdx.x): the 15 planes with column c -> 8 - c (the centre column
+// maps to itself) and the XQ_MAXM words of the move list.  Word i < count is mirrored when it is an action id (< 8100); a word at
+// or past the count, or one that is no action id, is copied as it is.  All 128 words are written either way.
+__device__ __forceinline__ void mirror_row(const float *__restrict__ src_x, const uint16_t *__restrict__ src_m, int count,
+                                           float *__restrict__ dst_x, uint16_t *__restrict__ dst_m, int t) {
+    for (int e = t; e < XQ_STATE_FLOATS; e += 256) {
+        const int c = e % 9;
+        dst_x[e] = src_x[e + 8 - 2 * c];
+    }
+    if (t < XQ_MAXM) {
+        const int a = src_m[t];
+        dst_m[t] = (uint16_t)((t < count && a < XQ_ACTION_SPACE) ? mirror_action(a) : a);
+    }
+}
+
+// k_gather_rows's copy of one row: the aligned float2 path over the planes, the move list as 64 words
+__device__ __forceinline__ void copy_row(const float *__restrict__ src_x, const uint16_t *__restrict__ src_m, float *__restrict__ dst_x,
+                                         uint16_t *__restrict__ dst_m, int t) {
+    const float2 *src = (const float2 *)src_x;
+    float2 *dst = (float2 *)dst_x;
+    for (int i = t; i < XQ_STATE_FLOATS / 2; i += 256) dst[i] = src[i];
+    if (t < XQ_MAXM / 2) ((uint32_t *)dst_m)[t] = ((const uint32_t *)src_m)[t];
+}
+
+// The mirrored gather: k_gather_rows with a decision per row.  rows[r] is a request ROW (slot K + j; the slot itself with K = 1);
+// the bit's coordinates are read from the slot's state words as k_select left them, so the kernel takes nothing from the host and
+// records into a graph.  A root request takes sims_done = 0 (GI_SIMS may hold the last move's count, or a reused root's visits).
+__global__ __launch_bounds__(256) void k_gather_rows_mirror(Dev E, int K, int mode, const int32_t *__restrict__ n_live,
+                                                            const int32_t *__restrict__ rows, const float *__restrict__ nn_in,
+                                                            float *__restrict__ x, uint16_t *__restrict__ moves,
+                                                            int32_t *__restrict__ counts) {
+    const int r = blockIdx.x;
+    if (r >= *n_live) return;
+    const int row = rows[r], t = threadIdx.x;
+    const int slot = row / K, j = row - slot * K;
+    const int32_t *gi = E.gi + (size_t)slot * GI_N;
+    const uint32_t is_root = gi[GI_PHASE] == PH_WAIT_ROOT ? 1u : 0u;
+    const int bit = mode == 1 ? eval_mirror_bit(E.cfg.seed, (uint32_t)E.cfg.rank, (uint32_t)slot, (uint32_t)gi[GI_GSEQ], (uint32_t)gi[GI_MC],
+                                                is_root, is_root ? 0u : (uint32_t)gi[GI_SIMS], (uint32_t)j)
+                              : 0;
+    const int count = E.req[row];
+    const float *src_x = nn_in + (size_t)row * XQ_STATE_FLOATS;
+    const uint16_t *src_m = E.pmoves + (size_t)row * XQ_MAXM;
+    float *dst_x = x + (size_t)r * XQ_STATE_FLOATS;
+    uint16_t *dst_m = moves + (size_t)r * XQ_MAXM;
+    if (bit) mirror_row(src_x, src_m, count, dst_x, dst_m, t);
+    else copy_row(src_x, src_m, dst_x, dst_m, t);
+    if (t == 0) counts[r] = count;
+}
+
+// xq_mirror_requests_batch: the same two row functions over n caller-owned rows, flags[r] != 0 mirrors
+__global__ __launch_bounds__(256) void k_mirror_rows(const float *__restrict__ x, const uint16_t *__restrict__ moves,
+                                                     const int32_t *__restrict__ counts, const uint8_t *__restrict__ flags, int n,
+                                                     float *__restrict__ x_out, uint16_t *__restrict__ moves_out) {
+    const int r = blockIdx.x, t = threadIdx.x;
+    if (r >= n) return;
+    const float *src_x = x + (size_t)r * XQ_STATE_FLOATS;
+    const uint16_t *src_m = moves + (size_t)r * XQ_MAXM;
+    float *dst_x = x_out + (size_t)r * XQ_STATE_FLOATS;
+    uint16_t *dst_m = moves_out + (size_t)r * XQ_MAXM;
+    if (flags[r] != 0) mirror_row(src_x, src_m, counts[r], dst_x, dst_m, t);
+    else copy_row(src_x, src_m, dst_x, dst_m, t);
+}
+
 // Hand-back: packed row r's legal-move logits and value go to slot rows[r] of the slot-ordered buffers k_expand reads.
 // One wave per row (two floats per lane), four rows per workgroup.
 __global__ __launch_bounds__(256) void k_scatter_rows(const int32_t *__restrict__ n_live, const int32_t *__restrict__ rows,
@@ -90,6 +174,12 @@ ArSets make_ar_sets(const xq_engine *e) {
 }  // namespace
 
 int xq::gather_packed_rows(const xq_engine *eng, const float *dev_nn_input, int rows, hipStream_t s) {
+    if (mirror_of(eng)) {                              // the kernel follows the handle; every other engine launches k_gather_rows
+        hipLaunchKernelGGL(k_gather_rows_mirror, dim3(rows), dim3(256), 0, s, make_dev(eng), leaves_of(eng), 1,
+                           (const int32_t *)eng->p[P_PK_N], (const int32_t *)eng->p[P_PK_ROWS], dev_nn_input, (float *)eng->p[P_PK_X],
+                           (uint16_t *)eng->p[P_PK_MOVES], (int32_t *)eng->p[P_PK_COUNTS]);
+        return launch_status();
+    }
     hipLaunchKernelGGL(k_gather_rows, dim3(rows), dim3(256), 0, s, make_dev(eng), (const int32_t *)eng->p[P_PK_N],
                        (const int32_t *)eng->p[P_PK_ROWS], dev_nn_input, (float *)eng->p[P_PK_X], (uint16_t *)eng->p[P_PK_MOVES],
                        (int32_t *)eng->p[P_PK_COUNTS]);
@@ -109,6 +199,28 @@ int xq_engine_compact(const xq_engine *eng, const float *dev_nn_input, void *str
     int rc = launch_status();
     if (rc != XQ_OK) return rc;
     return gather_packed_rows(eng, dev_nn_input, eng->cfg.n_games * K, s);
+}
+
+int xq_eval_mirror_bit_host(uint64_t seed, int rank, int slot, uint32_t game_seq, int ply, int is_root, int sims_done, int row) {
+    if (rank < 0 || slot < 0 || ply < 0 || (is_root != 0 && is_root != 1) || sims_done < 0 || sims_done >= 16000 || row < 0 || row >= 64)
+        return XQ_ERR_ARG;
+    return eval_mirror_bit(seed, (uint32_t)rank, (uint32_t)slot, game_seq, (uint32_t)ply, (uint32_t)is_root, (uint32_t)sims_done,
+                           (uint32_t)row);
+}
+
+int xq_mirror_action_host(int action) { return action < 0 || action >= XQ_ACTION_SPACE ? XQ_ERR_ARG : mirror_action(action); }
+
+int xq_mirror_requests_batch(const float *dev_x, const uint16_t *dev_moves, const int32_t *dev_counts, const uint8_t *dev_flags, int n,
+                             float *dev_x_out, uint16_t *dev_moves_out, void *stream) {
+    if (n < 0) return XQ_ERR_ARG;
+    if (n == 0) return XQ_OK;
+    if (!dev_x || !dev_moves || !dev_counts || !dev_flags || !dev_x_out || !dev_moves_out) return XQ_ERR_ARG;
+    if (dev_x_out == dev_x || dev_moves_out == dev_moves) return XQ_ERR_ARG;      // a mirrored row reads what it would overwrite
+    if ((((uintptr_t)dev_x) | ((uintptr_t)dev_x_out)) & 7 || (((uintptr_t)dev_moves) | ((uintptr_t)dev_moves_out)) & 3)
+        return XQ_ERR_ARG;                                                          // the copied rows take the aligned path
+    hipLaunchKernelGGL(k_mirror_rows, dim3(n), dim3(256), 0, (hipStream_t)stream, dev_x, dev_moves, dev_counts, dev_flags, n, dev_x_out,
+                       dev_moves_out);
+    return launch_status();
 }
 
 int xq_engine_packed(const xq_engine *eng, xq_engine_packed_buffers *out) {

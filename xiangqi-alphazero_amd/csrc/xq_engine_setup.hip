@@ -18,7 +18,9 @@ struct Opts {
     const xq_rules_opts *rules;     // absent from an initialiser: NULL, the reference's rules
     const xq_solver_opts *solver;   // absent, NULL or enabled = 0: no proven-result search
     const xq_root_stats_opts *root_stats;   // absent, NULL or enabled = 0: the samples' pad bytes stay zero
+    const xq_eval_mirror_opts *mirror;      // absent, NULL or mode = 0: every request is evaluated as it stands
     bool solver_on() const { return solver && solver->enabled != 0; }
+    bool mirror_on() const { return mirror && mirror->mode != 0; }
     bool root_stats_on() const { return root_stats && root_stats->enabled != 0; }
 };
 
@@ -150,11 +152,20 @@ bool root_stats_ok(const xq_engine_config *c, const Opts &o) {
     return rs->enabled == 0 || (c && c->manual_moves == 0 && !o.gumbel);
 }
 
+// evaluation mirror: mode 0 or 1, reserved words zero; on, it goes with everything but arena games, whose gate stays deterministic
+// and whose per-model packed step shares k_gather_rows
+bool mirror_ok(const xq_engine_config *c, const Opts &o) {
+    const xq_eval_mirror_opts *em = o.mirror;
+    if ((em->mode != 0 && em->mode != 1) || em->reserved[0] != 0 || em->reserved[1] != 0 || em->reserved[2] != 0) return false;
+    return em->mode == 0 || (c && c->manual_moves != 2);
+}
+
 // every option check, in the order the entry points have always refused in; an absent option passes
 bool opts_ok(const xq_engine_config *c, const Opts &o) {
     if (o.rules && !rules_ok(o.rules)) return false;
     if (o.solver && !solver_ok(o)) return false;
     if (o.root_stats && !root_stats_ok(c, o)) return false;
+    if (o.mirror && !mirror_ok(c, o)) return false;
     if (!config_ok(c) || !leaves_ok(c, o.K) || !flags_ok(c, o.K, o.flags)) return false;
     if (o.cap && !cap_ok(c, o.K, o.cap)) return false;
     if (o.forced && !forced_ok(c, o.K, o.forced)) return false;
@@ -162,7 +173,7 @@ bool opts_ok(const xq_engine_config *c, const Opts &o) {
     return !o.arena || arena_ok(c, o.arena);
 }
 
-// tree reuse, the playout cap and forced playouts need no workspace of their own
+// tree reuse, the playout cap, forced playouts and the evaluation mirror need no workspace of their own
 size_t workspace_bytes(const xq_engine_config *cfg, const Opts &o) { return opts_ok(cfg, o) ? make_layout(cfg, o).total : 0; }
 
 // get_sequence_of_considered_visits(k, S) of include/xq_hip.h: out[t] = the visit count a root child must have to be a
@@ -248,7 +259,7 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
     eng->pad0 = (K > 1 ? K : 0) | (int)(o.flags << 16) | (o.cap ? PAD0_CAP : 0) | (o.forced ? PAD0_FORCED : 0) |
                 (o.gumbel ? PAD0_GUMBEL : 0) | (o.arena ? PAD0_ARENA : 0) |
                 (o.rules && o.rules->perpetual_check ? PAD0_PERPETUAL : 0) | (o.solver_on() ? PAD0_SOLVER : 0) |
-                (o.root_stats_on() ? PAD0_ROOT_STATS : 0);
+                (o.root_stats_on() ? PAD0_ROOT_STATS : 0) | (o.mirror_on() ? PAD0_EVAL_MIRROR : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -355,6 +366,13 @@ size_t xq_engine_workspace_bytes_rs(const xq_engine_config *cfg, int leaves_per_
     return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats});
 }
 
+size_t xq_engine_workspace_bytes_em(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                                    const xq_eval_mirror_opts *mirror) {
+    return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror});
+}
+
 int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out) {
     if (k < 1 || k > XQ_MAXM || num_simulations < 1 || num_simulations > 65535 || !host_out) return XQ_ERR_ARG;
     gz_considered_visits(k, num_simulations, host_out);
@@ -418,6 +436,14 @@ int xq_engine_init_rs(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
     return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats}, ws, ws_bytes,
                        dev_inject, stream);
+}
+
+int xq_engine_init_em(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                      const xq_eval_mirror_opts *mirror, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
+    return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror}, ws,
+                       ws_bytes, dev_inject, stream);
 }
 
 int xq_engine_solver_stats_read(const xq_engine *eng, xq_solver_stats *host_out, void *stream) {

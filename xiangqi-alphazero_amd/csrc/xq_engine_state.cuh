@@ -53,6 +53,7 @@ enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM
 
 constexpr int PAD0_PERPETUAL = 1 << 26;     // pad0 of the handle (encoding below): "perpetual-check rule on"
 constexpr int PAD0_ROOT_STATS = 1 << 24;    // "root statistics per sample on" (xq_engine_init_rs)
+constexpr int PAD0_EVAL_MIRROR = (int)(1u << 31);   // "evaluation mirror on" (xq_engine_init_em): the last private bit, the sign
 
 // The node meta word tM: the child count in bits 0-11 (at most XQ_MAXM = 128), the node's proven state in bits 12-13 (always 0
 // without xq_engine_init_sv: every reader masks the count, and an engine without the solver stays byte-identical), the prior
@@ -161,7 +162,9 @@ __host__ __device__ inline size_t sv_bytes(size_t G) { return G * SV_WORDS * 8; 
 // pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
 // flag bits "playout cap on" (xq_engine_init_cap), "forced playouts on" (xq_engine_init_fp) and "Gumbel root search on"
 // (xq_engine_init_gz), "arena options on" (xq_engine_init_ar), "perpetual-check rule on" (xq_engine_init_ru), "proven-result
-// search on" (xq_engine_init_sv) and "root statistics per sample on" (xq_engine_init_rs, PAD0_ROOT_STATS above)
+// search on" (xq_engine_init_sv), "root statistics per sample on" (xq_engine_init_rs, PAD0_ROOT_STATS above) and, in bit 31,
+// "evaluation mirror on" (xq_engine_init_em, PAD0_EVAL_MIRROR above).  Bits 24-31 are now all taken; of the public flag byte
+// (bits 16-23) only bit 16 is.
 constexpr int PAD0_CAP = 1 << 30;
 constexpr int PAD0_FORCED = 1 << 29;
 constexpr int PAD0_GUMBEL = 1 << 28;
@@ -173,17 +176,19 @@ bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
 bool forced_of(const xq_engine *e) { return (e->pad0 & PAD0_FORCED) != 0; }
 bool gumbel_of(const xq_engine *e) { return (e->pad0 & PAD0_GUMBEL) != 0; }
 bool solver_of(const xq_engine *e) { return (e->pad0 & PAD0_SOLVER) != 0; }
+bool mirror_of(const xq_engine *e) { return (e->pad0 & PAD0_EVAL_MIRROR) != 0; }
 bool arena_of(const xq_engine *e) { return e && (e->pad0 & PAD0_ARENA) != 0 && e->cfg.n_games > 0 && e->p[P_SQRT]; }
 
 // ---------------------------------------------------------------------------------------------------------
-// RNG: Philox4x32-10 keyed by (seed, rank), counter (slot, kind, ctr, sub); or injected raw draws (tests).
-__device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0, uint32_t k1) {
+// RNG: Philox4x32-10 keyed by (seed, rank), counter (slot, kind, ctr, sub); or injected raw draws (tests).  Host-callable as
+// well: xq_eval_mirror_bit_host runs the device's own code.
+__host__ __device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0, uint32_t k1) {
     const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
     const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
     c0 = n0; c1 = n1; c2 = n2; c3 = n3;
 }
 
-__device__ inline uint64_t philox_u64(uint64_t seed, uint32_t rank, uint32_t slot, uint32_t kind, uint32_t ctr, uint32_t sub) {
+__host__ __device__ inline uint64_t philox_u64(uint64_t seed, uint32_t rank, uint32_t slot, uint32_t kind, uint32_t ctr, uint32_t sub) {
     uint32_t c0 = slot, c1 = kind | (sub << 8), c2 = ctr, c3 = rank;
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll

@@ -249,6 +249,7 @@ int xq_evcache_probe(const xq_evcache *cache, const xq_engine *eng, const float 
 
 int xq_engine_compact_misses(const xq_engine *eng, const float *dev_nn_input, const int32_t *dev_hit_flags, void *stream) {
     if (!eng || !dev_nn_input || !dev_hit_flags || eng->cfg.n_games <= 0 || leaves_of(eng) > 1) return XQ_ERR_ARG;
+    if (mirror_of(eng)) return XQ_ERR_ARG;            // a hit would return whichever orientation was evaluated first
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_compact_misses, dim3(1), dim3(CPT), 0, s, make_dev(eng), dev_hit_flags, (int32_t *)eng->p[P_PK_N],
                        (int32_t *)eng->p[P_PK_ROWS]);

@@ -85,6 +85,12 @@ With `root_stats=True` (opt-in; xq_engine_init_rs) every
 position in its 20 spare bytes (`sample_format.root_stats`): `root_q` from the view of the side to move, `root_visits`, and the
 mark `has_root_stats`.  `ReplayBuffer.batch(..., q_mix=...)` mixes it into the value target.  Nothing else about the games
 changes.  Self-play only; every other option but gumbel.
+
+With `eval_mirror=True` (opt-in; xq_engine_init_em) every request of the packed step is evaluated under a
+randomly chosen left-right orientation: `compact()` hands the evaluator the mirrored planes and the mirrored move list, in the
+original order, when the request's bit (`hip.eval_mirror_bit`, a function of seed, rank, slot, game, ply, root / leaf, simulations
+done and row) is 1, so the logits come back un-mirrored and the search averages the network's left/right asymmetry away.  It needs
+the packed step (an evaluator with `live_rows`); not with the evaluation cache and not for arena games; every other option.
 """
 from __future__ import annotations
 
@@ -142,6 +148,7 @@ class EngineOptions(collections.namedtuple("EngineOptions", "K flags cap forced 
     rules = None
     solver = None              # hip.SolverOpts or None: what xq_engine_*_sv take after `rules`
     root_stats = None          # hip.RootStatsOpts or None: what xq_engine_*_rs take after `solver`
+    eval_mirror = None         # hip.EvalMirrorOpts or None: what xq_engine_*_em take after `root_stats`
 
 
 RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_game_over, and its perpetual-check verdict
@@ -149,7 +156,8 @@ RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_
 
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
                          forced_playouts=None, gumbel=None, arena_opts=None, eval_cache_entries: int = 0,
-                         perpetual_check: bool = False, solver: bool = False, root_stats: bool = False) -> EngineOptions:
+                         perpetual_check: bool = False, solver: bool = False, root_stats: bool = False,
+                         eval_mirror: bool = False) -> EngineOptions:
     """The engine options of `SelfPlayEngine` checked and turned into the C structs; needs no GPU.  Every rule of the header's
     refusal lists (include/xq_hip.h; opts_ok in csrc/xq_engine_setup.hip) is refused here first, with a message that names the
     option; tests/test_engine_options.py holds the two side by side."""
@@ -250,7 +258,17 @@ def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tre
         raise hip.XqError("root_stats is a self-play option: search-only (manual_moves = 1) and arena (2) engines record no samples")
     if root_stats and gz is not None:
         raise hip.XqError("root_stats cannot be combined with gumbel: a Gumbel root's value is its own v_mix")
+    if eval_mirror not in (False, True, 0, 1):
+        raise hip.XqError(f"eval_mirror must be a bool, got {eval_mirror!r}")
+    if eval_mirror and int(cfg.manual_moves) == 2:
+        raise hip.XqError("eval_mirror is a self-play and search option: not available for arena games (manual_moves = 2), whose "
+                          "gate stays deterministic")
+    if eval_mirror and eval_cache_entries:
+        raise hip.XqError("eval_mirror cannot be combined with an evaluation cache (eval_cache_entries > 0): a hit would return "
+                          "whichever orientation was evaluated first")
     opts = EngineOptions(K, hip.ENGINE_TREE_REUSE if tree_reuse else 0, cap, forced, gz, ar)
+    if eval_mirror:
+        opts.eval_mirror = hip.EvalMirrorOpts(1)
     if solver:
         opts.solver = hip.SolverOpts(1)
     if root_stats:
@@ -264,13 +282,15 @@ class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
-                 perpetual_check: bool = False, solver: bool = False, root_stats: bool = False):
+                 perpetual_check: bool = False, solver: bool = False, root_stats: bool = False, eval_mirror: bool = False):
         opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
             gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check,
-            solver=solver, root_stats=root_stats)
+            solver=solver, root_stats=root_stats, eval_mirror=eval_mirror)
         K, flags, cap, forced, gz, ar = opts
-        rules, sv, rs = opts.rules, opts.solver, opts.root_stats
+        rules, sv, rs, em = opts.rules, opts.solver, opts.root_stats, opts.eval_mirror
+        if em is not None and not getattr(evaluator, "live_rows", False):
+            raise hip.XqError("eval_mirror acts in the packed step only: it needs an evaluator with live_rows (the HIP evaluators)")
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
@@ -286,11 +306,12 @@ class SelfPlayEngine:
         self.perpetual_check = rules is not None
         self.solver = sv is not None
         self.root_stats = rs is not None
+        self.eval_mirror = em is not None
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         # every entry point is the widest one with NULL for the options it does not take (include/xq_hip.h)
-        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules, sv, rs)]
-        nbytes = self.lib.xq_engine_workspace_bytes_rs(C.byref(cfg), K, flags, *refs)
+        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules, sv, rs, em)]
+        nbytes = self.lib.xq_engine_workspace_bytes_em(C.byref(cfg), K, flags, *refs)
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
@@ -306,8 +327,8 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            hip.check(self.lib.xq_engine_init_rs(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
-                                                 hip.stream_ptr(self.device)), "xq_engine_init_rs")
+            hip.check(self.lib.xq_engine_init_em(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
+                                                 hip.stream_ptr(self.device)), "xq_engine_init_em")
         # zero-copy int32 view of the per-slot state words (columns hip.GI_*: side to move of the REAL game, move_count, phase,
         # simulations done): host-side policies such as the arena's model choice read it between stages
         gi_off = int(self.h.p[hip.P_GI]) - int(self.ws.data_ptr())
@@ -522,6 +543,8 @@ class SelfPlayEngine:
             ll, value = self.evaluator.evaluate_legal(self.packed_x, self.packed_moves, self.packed_counts, n_live=self.n_live)
             self.expand_packed(ll, value)
         else:
+            if self.eval_mirror:                       # the full-width step never mirrors: an error, not a silent no-op
+                raise hip.XqError("eval_mirror needs the packed step: the evaluator has no live_rows")
             self.evaluate_and_expand(self.select())
 
     def step(self):

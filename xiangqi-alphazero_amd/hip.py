@@ -67,6 +67,7 @@ GI_SIDE = 0        # mirrors GI_SIDE of enum Gi in csrc/xq_engine_state.cuh: sid
 GI_MC = 1          # mirrors GI_MC of enum Gi: its move count
 GI_PHASE = 3       # mirrors GI_PHASE of enum Gi
 GI_SIMS = 4        # mirrors GI_SIMS of enum Gi: simulations done
+GI_GSEQ = 6        # mirrors GI_GSEQ of enum Gi: the slot's game sequence number
 GI_ALLOC = 7       # mirrors GI_ALLOC of enum Gi: the tree's allocation mark
 GI_RSTATUS = 11    # mirrors GI_RSTATUS of enum Gi: the root's terminal status (0 searched, 1 rules, 2 max length, 4 perpetual check)
 GI_RWINNER = 12    # mirrors GI_RWINNER of enum Gi: the winner that goes with a non-zero status
@@ -124,6 +125,11 @@ class SolverOpts(C.Structure):
 class RootStatsOpts(C.Structure):
     """xq_root_stats_opts: the root's search value per sample (xq_engine_init_rs): enabled 0 / 1."""
     _fields_ = [("enabled", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class EvalMirrorOpts(C.Structure):
+    """xq_eval_mirror_opts: random mirror of the packed step's evaluation requests (xq_engine_init_em): mode 0 off / 1 random."""
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class BatchOpts(C.Structure):
@@ -228,6 +234,12 @@ def lib():
     L.xq_engine_workspace_bytes_rs.argtypes = L.xq_engine_workspace_bytes_sv.argtypes + [C.POINTER(RootStatsOpts)]
     L.xq_engine_workspace_bytes_rs.restype = C.c_size_t
     L.xq_engine_init_rs.argtypes = L.xq_engine_init_sv.argtypes[:10] + [C.POINTER(RootStatsOpts)] + L.xq_engine_init_sv.argtypes[10:]
+    L.xq_engine_workspace_bytes_em.argtypes = L.xq_engine_workspace_bytes_rs.argtypes + [C.POINTER(EvalMirrorOpts)]
+    L.xq_engine_workspace_bytes_em.restype = C.c_size_t
+    L.xq_engine_init_em.argtypes = L.xq_engine_init_rs.argtypes[:11] + [C.POINTER(EvalMirrorOpts)] + L.xq_engine_init_rs.argtypes[11:]
+    L.xq_eval_mirror_bit_host.argtypes = [C.c_uint64, i32, i32, C.c_uint32, i32, i32, i32, i32]
+    L.xq_mirror_action_host.argtypes = [i32]
+    L.xq_mirror_requests_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
     L.xq_engine_read_root_states.argtypes = [C.POINTER(Engine), i32, vp, vp, vp]
     L.xq_engine_solver_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(SolverStats), vp]
     L.xq_engine_arena_openings.argtypes = [C.POINTER(Engine), C.POINTER(vp), C.POINTER(vp)]
@@ -314,7 +326,9 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_compact_arena", "xq_engine_packed_arena", "xq_engine_expand_packed_arena",
            "xq_engine_workspace_bytes_ru", "xq_engine_init_ru", "xq_game_over_batch_ex",
            "xq_engine_workspace_bytes_sv", "xq_engine_init_sv", "xq_engine_read_root_states", "xq_engine_solver_stats_read",
-           "xq_engine_workspace_bytes_rs", "xq_engine_init_rs", "xq_samples_to_batch_ex"]
+           "xq_engine_workspace_bytes_rs", "xq_engine_init_rs", "xq_samples_to_batch_ex",
+           "xq_engine_workspace_bytes_em", "xq_engine_init_em", "xq_eval_mirror_bit_host", "xq_mirror_action_host",
+           "xq_mirror_requests_batch"]
 
 
 def check(rc: int, what: str):
@@ -414,6 +428,38 @@ def game_over_batch(boards, side, move_count, no_capture, hist, perpetual_check:
                                           None if kind is None else _dev(kind), stream_ptr(boards.device)),
               "xq_game_over_batch_ex")
     return (out, kind) if return_kind else out
+
+
+def eval_mirror_bit(seed: int, rank: int, slot: int, game_seq: int, ply: int, is_root, sims_done: int, row: int = 0) -> int:
+    """The evaluation mirror's bit of one request (xq_eval_mirror_bit_host: the device's own code on the host; needs no GPU).
+    A root request is asked with sims_done = 0, as the mirrored gather does."""
+    if not (0 <= int(seed) < 2 ** 64 and 0 <= int(game_seq) < 2 ** 32):
+        raise XqError(f"eval_mirror_bit: seed must be a uint64 and game_seq a uint32, got {seed}, {game_seq}")
+    b = lib().xq_eval_mirror_bit_host(int(seed), int(rank), int(slot), int(game_seq), int(ply), int(is_root), int(sims_done), int(row))
+    if b not in (0, 1):
+        raise XqError(f"xq_eval_mirror_bit_host failed: code {b}")
+    return b
+
+
+def mirror_requests(x: torch.Tensor, moves: torch.Tensor, counts: torch.Tensor, flags: torch.Tensor, out=None):
+    """Rows of evaluation requests under the left-right mirror (xq_mirror_requests_batch): x float32[n,15,10,9], moves 16-bit
+    [n,128], counts int32[n], flags uint8[n] -> (x_out, moves_out); row r is mirrored where flags[r] != 0 and copied otherwise.
+    The move list keeps its order, so the evaluator's legal-move logits of a mirrored row are those of the original moves.
+    `out` = (x_out, moves_out) preallocated, holding at least n rows (rows past n are not written)."""
+    n = x.shape[0]
+    if x.shape[1:] != (15, 10, 9) or x.dtype != torch.float32 or moves.shape != (n, MAXM) or moves.element_size() != 2 \
+            or counts.shape != (n,) or counts.dtype != torch.int32 or flags.shape != (n,) or flags.dtype != torch.uint8:
+        raise XqError("mirror_requests: x float32[n,15,10,9], moves 16-bit [n,128], counts int32[n], flags uint8[n] required")
+    if out is None:
+        out = (torch.empty_like(x), torch.empty_like(moves))
+    xo, mo = out
+    if xo.shape[0] < n or xo.shape[1:] != x.shape[1:] or xo.dtype != x.dtype or mo.shape[0] < n or mo.shape[1:] != moves.shape[1:] \
+            or mo.dtype != moves.dtype:
+        raise XqError("mirror_requests: out = (float32[>=n,15,10,9], 16-bit [>=n,128]) required")
+    if n:
+        check(lib().xq_mirror_requests_batch(_dev(x), _dev(moves), _dev(counts), _dev(flags), n, _dev(xo), _dev(mo), stream_ptr(x.device)),
+              "xq_mirror_requests_batch")
+    return xo, mo
 
 
 def bias_act_(y: torch.Tensor, bias: torch.Tensor, residual=None, relu: bool = True) -> torch.Tensor:

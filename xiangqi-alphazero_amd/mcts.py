@@ -24,6 +24,10 @@ over the root's visits and `read_root_states`); `search`'s pi stays the visit co
 `search_many(..., return_values=True)` also returns the search's value of every position, from the view of its side to move
 (`root_value`: the engine's root_q arithmetic of DESIGN.md section 4.13 over `read_root`'s arrays); `root_values` keeps the last
 search's.
+
+`eval_mirror=True` (opt-in) evaluates every request of the search under a randomly chosen left-right orientation
+(engine.SelfPlayEngine).  The orientation is a function of the seed, the position's index in the call, its
+`move_count` and the request's place in the search, so the same call gives the same answer again: serving stays reproducible.
 """
 from __future__ import annotations
 
@@ -62,13 +66,14 @@ def root_value(visits, total_value) -> np.float32:
 class MCTS:
     def __init__(self, model, num_simulations: int = 200, c_puct: float = 1.5, device: str = "cuda",
                  evaluator_kind: str = "auto", seed: int = 0, leaves_per_step: int = 1, perpetual_check: bool = False,
-                 solver: bool = False):
+                 solver: bool = False, eval_mirror: bool = False):
         if not 1 <= int(leaves_per_step) <= 64:
             from .hip import XqError
             raise XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
         self.leaves_per_step = int(leaves_per_step)
         self.perpetual_check = bool(perpetual_check)
         self.solver = bool(solver)
+        self.eval_mirror = bool(eval_mirror)
         self.model = model
         self.num_simulations = num_simulations
         self.c_puct = c_puct
@@ -95,7 +100,8 @@ class MCTS:
                                      seed=self.seed)
             self._engines[key] = engine.SelfPlayEngine(cfg, self.device, evaluator=self.evaluator,
                                                        leaves_per_step=self.leaves_per_step,
-                                                       perpetual_check=self.perpetual_check, solver=self.solver)
+                                                       perpetual_check=self.perpetual_check, solver=self.solver,
+                                                       eval_mirror=self.eval_mirror)
         return self._engines[key]
 
     def search_many(self, games: Sequence, temperature: float = 1.0, add_noise: bool = True, return_values: bool = False):

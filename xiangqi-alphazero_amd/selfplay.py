@@ -38,7 +38,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
               evaluator_kind: str = "hip", poll_every: int = 64, device_records: bool = False, use_graph: bool = True,
               eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None,
               tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None,
-              perpetual_check: Optional[bool] = None, solver: Optional[bool] = None, root_stats: Optional[bool] = None):
+              perpetual_check: Optional[bool] = None, solver: Optional[bool] = None, root_stats: Optional[bool] = None,
+              eval_mirror: Optional[bool] = None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -66,7 +67,11 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     neither Gumbel root search nor forced playouts.
     `root_stats` (None: `config.record_root_stats`, absent = off, or a `config.value_target_q_mix` above 0, which needs them)
     records the search's value of every sampled position in the sample's spare bytes (`sample_format.root_stats`; stats
-    `root_stats`); the games do not change.  It goes with every option but Gumbel root search."""
+    `root_stats`); the games do not change.  It goes with every option but Gumbel root search.
+    `eval_mirror` (None: `config.eval_random_mirror`, absent = off) evaluates every request under a randomly chosen left-right
+    orientation (stats `eval_mirror`); it needs the packed step and excludes the evaluation cache."""
+    if eval_mirror is None:
+        eval_mirror = bool(getattr(config, "eval_random_mirror", False))
     if root_stats is None:
         root_stats = bool(getattr(config, "record_root_stats", False)) or root_stats_q_mix(config) > 0.0
     if eval_cache_entries is None:
@@ -106,7 +111,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries,
                                 leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
                                 forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check, solver=solver,
-                                root_stats=root_stats)
+                                root_stats=root_stats, eval_mirror=eval_mirror)
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -130,6 +135,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     st["perpetual_check"] = eng.perpetual_check
     st["solver"] = eng.solver
     st["root_stats"] = eng.root_stats
+    st["eval_mirror"] = eng.eval_mirror
     for k in hip.SOLVER_KEYS:                          # the solver's keys are present (0) when it is off
         st.setdefault(k, 0)
     if device_records:

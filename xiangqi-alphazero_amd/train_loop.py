@@ -59,6 +59,9 @@ class AlphaZeroLoop:
         # once: self-play and the train step below are handed these two values and do not read the keys again
         self.q_mix = selfplay.root_stats_q_mix(config)
         self.record_root_stats = bool(getattr(config, "record_root_stats", False)) or self.q_mix > 0.0
+        # the evaluation mirror (config.eval_random_mirror; absent: off), read once, for self-play ONLY: the arena gate never gets
+        # it, so a gate's games stay a function of the two models and the seed
+        self.eval_mirror = bool(getattr(config, "eval_random_mirror", False))
         torch.manual_seed(seed)                        # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -93,7 +96,7 @@ class AlphaZeroLoop:
                                                     # arena (arena.py) never takes it
                                                     forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None,
                                                     perpetual_check=self.perpetual_check, solver=self.solver,
-                                                    root_stats=self.record_root_stats)
+                                                    root_stats=self.record_root_stats, eval_mirror=self.eval_mirror)
         # the Gumbel root search (config.gumbel_considered, gumbel_c_visit, gumbel_c_scale; absent or 0: off) reaches the engine
         # through run_games, which reads those keys from the config it is handed; the arena never takes it either
         return samples, results
