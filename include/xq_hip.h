@@ -750,13 +750,24 @@ int xq_evcache_key_host(const float *host_planes, uint32_t *host_out12);
 /* Synchronises `stream`, copies the counters to host. */
 int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *stream);
 
-/* Synchronises; copies up to max_samples finished samples (XQ_SAMPLE_BYTES each, layout xq_sample) and
- * up to max_results game results (xq_game_result) to host buffers and resets the rings. */
+/* Synchronises; copies the finished samples (XQ_SAMPLE_BYTES each, layout xq_sample) and the game results (xq_game_result)
+ * that are pending in the rings to host buffers and resets the rings.
+ * What a drain returns, full rings included:
+ *   - samples: every row was written since the last drain, by a finished game that is there whole (all n_samples rows of its
+ *     result, contiguous) or not at all.  A game finds room only while its rows fit under cfg.max_out_samples: one that does not
+ *     fit is dropped whole, counted in samples_dropped and leaves the ring as it was, so a later, shorter game may still fit.
+ *     The rows of all drains add up to samples_written; samples_written + samples_dropped is the n_samples of all finished games.
+ *   - results: the first min(games finished since the last drain, cfg.max_out_results) of them, in the order they finished;
+ *     a result is returned whether or not its game's samples were dropped.
+ *   - a full ring is no capacity error: overflow stays 0, the games go on unchanged.
+ * max_samples / max_results smaller than what is pending: XQ_ERR_ARG, *n_samples / *n_results report the pending sizes and
+ * nothing is consumed. */
 int xq_engine_drain(const xq_engine *eng, void *host_samples, int max_samples, int *n_samples,
                     void *host_results, int max_results, int *n_results, void *stream);
 
 /* The same into DEVICE buffers (the samples stay on the GPU for the replay buffer / the RCCL all-gather; nothing crosses
- * PCIe).  With both buffers NULL it only reports the pending counts and consumes nothing.  Synchronises. */
+ * PCIe); the same rows under the same contract.  With both buffers NULL it only reports the pending counts and consumes
+ * nothing; so does a call whose buffers are too small (XQ_ERR_ARG).  Synchronises. */
 int xq_engine_drain_device(const xq_engine *eng, void *dev_samples, int max_samples, int *n_samples,
                            void *dev_results, int max_results, int *n_results, void *stream);
 

@@ -256,9 +256,20 @@ __device__ __forceinline__ void slot_flush_finished(const Dev &E, const Slot &s)
     unsigned base = 0;
     bool fits = true;
     if (n_samples > 0) {
-        if (lane == 0) base = atomicAdd(&E.cnt[0], (unsigned)n_samples);
+        // The cursor advances only for a game that fits: it never passes max_out_samples, and every row below it has been
+        // written since the last drain.  A game that does not fit is dropped whole; a shorter one may still fit after it.
+        if (lane == 0) {
+            const unsigned cap = (unsigned)E.cfg.max_out_samples;
+            unsigned seen = atomicAdd(&E.cnt[0], 0u);
+            for (;;) {
+                if ((unsigned long long)seen + (unsigned)n_samples > cap) { base = 0xFFFFFFFFu; break; }
+                const unsigned prev = atomicCAS(&E.cnt[0], seen, seen + (unsigned)n_samples);
+                if (prev == seen) { base = seen; break; }
+                seen = prev;
+            }
+        }
         base = __builtin_amdgcn_readfirstlane(base);
-        fits = (unsigned long long)base + (unsigned)n_samples <= (unsigned)E.cfg.max_out_samples;
+        fits = base != 0xFFFFFFFFu;
         if (fits) {
             const uint8_t *src = E.stage + (size_t)s.slot * E.stage_cap * XQ_SAMPLE_BYTES;
             uint8_t *dst = E.outs + (size_t)base * XQ_SAMPLE_BYTES;

@@ -60,6 +60,7 @@ P_BOARD = 0        # mirrors P_BOARD of enum Ptr in csrc/xq_engine_state.cuh: th
 P_GI = 2           # mirrors P_GI of enum Ptr: the per-slot state words
 P_TN, P_TW, P_TP, P_TA, P_TC, P_TM = 6, 7, 8, 9, 10, 11   # mirror P_TN .. P_TM of enum Ptr: the six tree arrays
 P_ROOTP = 12       # mirrors P_ROOTP of enum Ptr: the float64 root priors
+P_OUTS, P_OUTR = 14, 15   # mirror P_OUTS, P_OUTR of enum Ptr: the sample ring and the result ring that the drains read
 P_STATS = 17       # mirrors P_STATS of enum Ptr: the per-slot counters
 P_SQRT = 19        # mirrors P_SQRT of enum Ptr: the square-root table and the Gumbel / arena words behind it
 P_VL = 30          # mirrors P_VL of enum Ptr: the virtual-loss counters (leaves_per_step > 1)
