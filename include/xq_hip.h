@@ -992,6 +992,80 @@ typedef struct xq_game_result {
     uint16_t reserved;
 } xq_game_result;
 
+/* Game records (opt-in, xq_engine_init_gr): every finished game's moves, and a batched device replay of records.
+ * THE RECORD: 1024 bytes, no implicit padding.  slot and game_seq join it with the game's xq_game_result and xq_sample rows;
+ * winner, reason and n_samples are the result's; n_moves is the result's steps.  moves[i] is the action (from * 90 + to) of ply i
+ * of the real game, in ply order, whoever chose it: a random opening ply, an arena opening ply or a searched move (fast moves of
+ * the playout cap and arena moves included); the entries at and after n_moves are 0.  opening_plies counts the leading plies no
+ * search chose: the random opening of a self-play game, the paired opening of an arena game; an opening whose plies ended the
+ * game restarted it from the initial position at ply 0, and opening_plies is then 0, as the arena's own opening record has it.
+ * THE ENGINE: xq_engine_workspace_bytes_gr / xq_engine_init_gr are the widest pair: everything the _em pair takes, then the
+ * options.  NULL or enabled = 0 is exactly the _em pair: the same workspace size, the same bytes, the same launches.  XQ_ERR_ARG
+ * before any launch (xq_engine_workspace_bytes_gr: 0): a non-zero reserved word; enabled outside {0, 1}; and, with enabled = 1,
+ * max_out_games < 1, manual_moves = 1 (a search-only engine plays no games), max_game_length > XQ_RECORD_MAX_PLIES or
+ * random_opening_moves > XQ_RECORD_MAX_PLIES; and whatever xq_engine_init_em refuses.  Every other option goes with it, leaf
+ * batching included.  Workspace: behind the engine's square-root table (behind every other option's words there), a ring of
+ * max_out_games records, a move log uint16[G][XQ_RECORD_MAX_PLIES], the opening count of every slot, and 256 bytes holding the
+ * ring's counter and the two statistics; "game records on" lives in the handle (pad0, bit 23).  The handle's layout and size do
+ * not change.
+ * Every real move writes log[slot][move_count before the move] = action with one 2-byte store of lane 0; an index at or above
+ * XQ_RECORD_MAX_PLIES is never written and sets overflow bit 256 << 8 (it cannot happen within the refusals above: rules end a
+ * game at ply 200).  A finished game's record is written by xq_engine_select, in a kernel of its own ahead of the select kernel
+ * that flushes the game's samples and result and starts the slot's next game (one more launch per step, on a records engine
+ * only): the game takes the next ring index r; r < max_out_games copies the header and the n_moves entries to row r, zeroes the
+ * rest of the row and counts in `recorded`; otherwise the game counts in `dropped`.  Games that finish in one step take their
+ * rows in an order of their own, which need not be that of their results: join on (slot, game_seq).  A full ring is no capacity
+ * error: overflow stays 0, and games, samples and results go on unchanged.
+ * xq_engine_drain_games / _device: independent of xq_engine_drain, under its contract: they synchronise, return the first
+ * min(games finished since the last drain of this ring, max_out_games) records in the order the games finished and reset this
+ * ring only.  max_records smaller than what is pending: XQ_ERR_ARG, *n_records reports the pending count and nothing is
+ * consumed.  A NULL buffer reports the count and consumes nothing.  XQ_ERR_ARG on an engine without the option.
+ * xq_engine_game_records_stats_read: synchronises; recorded + dropped = the games finished.  XQ_ERR_ARG without the option.
+ * THE REPLAY: xq_replay_games_batch, one wavefront per record, plays record i from the initial position for
+ * min(max(stop_ply[i], 0), n_moves) plies (all n_moves without dev_stop_ply): at each ply the ordered legal moves of the
+ * position are generated and the record's action must be one of them.
+ *   dev_status[i]   0: every requested ply was legal; k > 0: ply k - 1 is no legal move of its position, the replay stopped
+ *                   before it and every output describes the position before that ply; -1: n_moves > XQ_RECORD_MAX_PLIES, nothing
+ *                   is replayed and the outputs describe the initial position.
+ *   dev_boards[i], dev_side[i], dev_move_count[i], dev_no_capture[i]: the position reached.
+ *   dev_hist12[i]   int8[12][90]: the last min(12, move_count) pre-move boards, oldest first, zeros elsewhere --
+ *                   xq_engine_set_position's host_hist12.
+ *   dev_over_kind[i], dev_winner[i]: the rules' verdict at the position reached, as an engine's root status has it: 0 not over
+ *                   (winner 2), 1 over, 4 over by the perpetual-check rule (only with perpetual_check = 1); max_game_length is
+ *                   no rule and is not judged.
+ * Every output pointer but dev_status may be NULL.  n = 0 is a no-op; XQ_ERR_ARG before any launch: n < 0, with n > 0 a NULL
+ * dev_records or dev_status, perpetual_check outside {0, 1}. */
+#define XQ_RECORD_MAX_PLIES 504
+#define XQ_RECORD_BYTES 1024
+typedef struct xq_game_record {
+    uint32_t slot, game_seq;     /* join key with xq_game_result and xq_sample */
+    int8_t   winner;             /* as xq_game_result */
+    uint8_t  reason;             /* as xq_game_result */
+    uint16_t n_moves;            /* == the result's steps (game.move_count) */
+    uint16_t opening_plies;      /* leading plies no search chose: the random opening (self-play) or the paired arena opening */
+    uint16_t n_samples;          /* as xq_game_result */
+    uint16_t moves[XQ_RECORD_MAX_PLIES];   /* action codes in ply order; entries at and after n_moves are 0 */
+} xq_game_record;
+typedef struct xq_game_records_opts { int32_t enabled; int32_t max_out_games; int32_t reserved[2]; } xq_game_records_opts;
+typedef struct xq_game_records_stats { uint64_t recorded, dropped, reserved[2]; } xq_game_records_stats;
+size_t xq_engine_workspace_bytes_gr(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                                    const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records);
+int xq_engine_init_gr(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                      const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records, void *ws, size_t ws_bytes,
+                      const uint64_t *dev_inject, void *stream);
+int xq_engine_drain_games(const xq_engine *eng, void *host_records, int max_records, int *n_records, void *stream);
+int xq_engine_drain_games_device(const xq_engine *eng, void *dev_records, int max_records, int *n_records, void *stream);
+int xq_engine_game_records_stats_read(const xq_engine *eng, xq_game_records_stats *host_out, void *stream);
+int xq_replay_games_batch(const void *dev_records /* xq_game_record[n] */, const int32_t *dev_stop_ply /* [n] or NULL = all moves */,
+                          int n, int perpetual_check,
+                          int8_t *dev_boards /* [n][90] */, int8_t *dev_side, int32_t *dev_move_count, int32_t *dev_no_capture,
+                          int8_t *dev_hist12 /* [n][12][90], oldest first, xq_engine_set_position's layout */,
+                          int32_t *dev_status, int8_t *dev_over_kind, int8_t *dev_winner, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,10 @@ Opt-in as well: `perpetual_check` (`config.perpetual_check_loses` for `evaluate_
 rule: a game one side forces into a repetition by checking on every move is that side's loss, not half a
 point.  A loop that trains under the rule gates under it (`AlphaZeroLoop` passes one value to both); off, the gate is the
 reference's.
+
+Opt-in as well: `record_games` (`config.record_games` for `evaluate_models`) keeps every game's moves: an
+arena game writes no samples, so its record is all that is left of it besides winner and ply count.  `play_arena` then returns
+`(results, records)`, both ordered by game; `evaluate_models` adds `game_records` (this rank's games, `slot` = the game's index).
 """
 from __future__ import annotations
 
@@ -56,7 +60,7 @@ def _evaluate_subset(eng, ev, x, idx, policy_is_probs, dense, legal, value):
 def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_simulations: int, max_game_length: int,
                c_puct: float = 1.5, device="cuda", policy_is_probs: bool = False, first_game: int = 0,
                opening_plies: int = 0, seed: int = 0, packed: Optional[bool] = None, inject=None, info: Optional[dict] = None,
-               perpetual_check: bool = False, solver: bool = False):
+               perpetual_check: bool = False, solver: bool = False, record_games: bool = False):
     """eval_*: evaluators in either protocol (`evaluate_legal`, or a callable float32[n,15,10,9] -> (policy
     float32[n,8100], value float32[n])); both must use the same one.  Plays games first_game .. first_game+eval_games-1
     of the arena (the new model is red in even games) and returns the results array ordered by game (slot == game -
@@ -66,18 +70,20 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
     device draws; `info` (a dict) receives `openings`, `opening_counts`, `steps` (engine steps run) and the engine's `stats`;
     `perpetual_check` builds the engine with the perpetual-check rule (results then may carry reason 4); `solver` with the
     proven-result search (a move shown to lose is not played while another is not, a move shown to win is
-    played at once; `info["stats"]` then carries the five solver counters)."""
+    played at once; `info["stats"]` then carries the five solver counters); `record_games` with game records: the return value is
+    then `(results, records)`, the records (hip.GAME_RECORD_DTYPE) ordered by game like the results."""
     cfg = engine.make_config(eval_games, eval_simulations, c_puct=c_puct, max_game_length=max_game_length,
                              random_opening_moves=0, enable_resign=False, add_noise=False, games_target=eval_games,
                              manual_moves=2)
     opts = int(opening_plies) > 0 or bool(packed) or inject is not None or info is not None
     if not opts:
-        eng = engine.SelfPlayEngine(cfg, device, perpetual_check=perpetual_check, solver=solver)
+        eng = engine.SelfPlayEngine(cfg, device, perpetual_check=perpetual_check, solver=solver, record_games=record_games)
     else:
         if inject is not None:
             cfg.inject_len = int(np.asarray(inject).shape[-1])
         cfg.seed = int(seed)
-        eng = engine.arena_engine(cfg, device, opening_plies, first_game, inject, perpetual_check=perpetual_check, solver=solver)
+        eng = engine.arena_engine(cfg, device, opening_plies, first_game, inject, perpetual_check=perpetual_check, solver=solver,
+                                  record_games=record_games)
     dev = eng.device
     new_is_red = ((torch.arange(eval_games, device=dev) + first_game) % 2 == 0)
     sparse = hasattr(eval_new, "evaluate_legal") and hasattr(eval_old, "evaluate_legal") and not policy_is_probs
@@ -184,7 +190,11 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
     if info is not None:
         info["openings"], info["opening_counts"] = eng.arena_openings()
         info["steps"], info["stats"], info["packed"] = n_steps, st, bool(packed)
-    return results[results["slot"].argsort()]
+    results = results[results["slot"].argsort()]
+    if not record_games:
+        return results
+    records = eng.drain_games()
+    return results, records[records["slot"].argsort()]
 
 
 def pair_statistics(winners) -> Dict[str, object]:
@@ -206,7 +216,7 @@ def pair_statistics(winners) -> Dict[str, object]:
 
 def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind: str = "hip", group=None,
                     seed: Optional[int] = None, perpetual_check: Optional[bool] = None,
-                    solver: Optional[bool] = None) -> Dict[str, object]:
+                    solver: Optional[bool] = None, record_games: Optional[bool] = None) -> Dict[str, object]:
     """Same stats dict as the reference (`new_wins, old_wins, draws, win_rate, model_updated`); reads
     `eval_games, eval_simulations, c_puct, max_game_length, eval_win_rate` from `config` (train.py:97-100).
     Under torch.distributed the games are split over the ranks and the winners all-gathered.
@@ -215,7 +225,9 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
     `openings` (uint16 [games, R]), `win_rate_se` and `win_rate_ci95`.  The promotion rule is unchanged.
     `perpetual_check` (None: `config.perpetual_check_loses`, absent: off) plays the games under the perpetual-check rule; the
     result then adds `perpetual_check` = True.  Off, `play_arena` is called as before.
-    `solver` (None: `config.mcts_solver`, absent: off) searches with proven results; the result then adds `solver` = True."""
+    `solver` (None: `config.mcts_solver`, absent: off) searches with proven results; the result then adds `solver` = True.
+    `record_games` (None: `config.record_games`, absent: off) adds `game_records`: the records of the games THIS rank played
+    (hip.GAME_RECORD_DTYPE, `slot` = the game's index in the arena); records are not gathered across ranks."""
     import torch.distributed as dist
     from . import distributed as xdist
     total = int(config.eval_games)
@@ -231,6 +243,11 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
         solver = bool(getattr(config, "mcts_solver", False))
     if solver:
         rule["solver"] = True
+    if record_games is None:
+        record_games = bool(getattr(config, "record_games", False))
+    records = np.zeros(0, dtype=hip.GAME_RECORD_DTYPE)
+    if record_games:
+        rule["record_games"] = True
     openings = np.zeros((total, max(plies, 0)), dtype=np.int64)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -245,12 +262,17 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
             info = {}
             res = play_arena(en, eo, mine, int(config.eval_simulations), int(config.max_game_length), float(config.c_puct),
                              device, first_game=first, opening_plies=plies, seed=int(seed), info=info, **rule)
+            if record_games:
+                res, records = res
             openings[first:first + mine] = info["openings"][:, :plies]
         else:
             res = play_arena(en, eo, mine, int(config.eval_simulations), int(config.max_game_length), float(config.c_puct),
                              device, first_game=first, **rule)
+            if record_games:
+                res, records = res
         winners[first:first + mine] = res["winner"].astype(np.int64)
         steps[first:first + mine] = res["steps"].astype(np.int64)
+        records["slot"] += first
     if dist.is_initialized():         # disjoint shards: a sum gathers them; every rank ends with the same table (a group of
                                       # one rank runs the same collective)
         t = torch.from_numpy(np.stack([winners, steps])).to(device if dist.get_backend(group) == "nccl" else "cpu")
@@ -274,6 +296,8 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
     games["slot"], games["winner"], games["steps"] = np.arange(total), winners, steps
     out = {"new_wins": new_wins, "old_wins": old_wins, "draws": draws, "win_rate": win_rate,
            "model_updated": win_rate >= float(config.eval_win_rate), "games": games, **rule}
+    if record_games:
+        out["game_records"] = records
     if plies > 0:
         ps = pair_statistics(winners)
         out.update({"opening_plies": plies, "pairs": ps["pairs"], "openings": openings.astype(np.uint16),

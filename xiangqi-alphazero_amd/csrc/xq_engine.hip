@@ -21,6 +21,8 @@
 //                reference's sequential-float32 mask-and-normalise (mcts.py:176-188), children appended to the
 //                slot's bump arena, Dirichlet noise at the root (mcts.py:117-121), resign probe
 //                (parallel_selfplay.py:110-121), backup along the recorded path (mcts.py:66-73).
+//   k_flush_records : game records (opt-in, xq_engine_init_gr): the record of every finished game, ahead of the select kernel
+//                that starts the slot's next game; the moves themselves are logged by the select kernels (slot_log_move).
 //   k_reroot : tree reuse (opt-in, XQ_ENGINE_TREE_REUSE; k_select<true> / k_expand<true>): the chosen child's subtree moved to the
 //                front of the slot's arena, in place, between select and expand of the step that ends a move.
 //
@@ -88,88 +90,11 @@ struct SelectLds {
     double w_tmp[XQ_MAXM];
 };
 
-__device__ __forceinline__ void lds_copy_dwords(void *dst, const void *src, int ndw) {
-    const int lane = lane_id();
-    uint32_t *d = (uint32_t *)dst;
-    const uint32_t *s = (const uint32_t *)src;
-    for (int i = lane; i < ndw; i += 64) d[i] = s[i];
-}
-
-__device__ __forceinline__ void init_board_lds(int8_t *b) {
-    const int lane = lane_id();
-    for (int sq = lane; sq < XQ_BS; sq += 64) {
-        int v = 0;
-        if (sq < 90) {
-            const int r = sq / 9, c = sq % 9;
-            const int back = (c == 0 || c == 8) ? 5 : (c == 1 || c == 7) ? 4 : (c == 2 || c == 6) ? 3 : (c == 3 || c == 5) ? 2 : 1;
-            if (r == 0) v = back;
-            else if (r == 9) v = -back;
-            else if (r == 2 && (c == 1 || c == 7)) v = 6;
-            else if (r == 7 && (c == 1 || c == 7)) v = -6;
-            else if (r == 3 && (c % 2 == 0)) v = 7;
-            else if (r == 6 && (c % 2 == 0)) v = -7;
-        }
-        b[sq] = (int8_t)v;
-    }
-}
-
-// game.py:565-616 on an LDS position.  Leaves the ordered legal moves in `moves` (count in *cnt) whenever both
-// kings stand.  Wave-uniform result: 0 not over, 1 over, 4 over by the perpetual-check rule (`perpetual`: the engine's
-// xq_rules_opts flag) -- the values of a root's status word and a result's reason.
-__device__ inline int wave_game_over(const int8_t *b, const int8_t (*ring)[XQ_BS], int side, int mc, int nocap, bool perpetual,
-                                     MoveGenLds &mg, uint16_t *moves, int *cnt, int *winner, int *ovf) {
-    const VMove none{-1, -1, 0};
-    const int lane = lane_id();
-    *cnt = 0;
-    if (find_king(b, none, 1) < 0) { *winner = -1; return 1; }
-    if (find_king(b, none, -1) < 0) { *winner = 1; return 1; }
-    const int n = wave_movegen(b, side, mg, moves, ovf);
-    *cnt = n;
-    if (n == 0) { *winner = -side; return 1; }
-    if (nocap >= 120) { *winner = 0; return 1; }
-    if (mc >= 200) {
-        int red, black;
-        wave_material(b, red, black);
-        const int diff = red - black;
-        *winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
-        return 1;
-    }
-    if (mc >= 6) {
-        const int k = mc < XQ_HIST ? mc : XQ_HIST;
-        int rep = 0;
-        for (int e = 0; e < k; ++e) {
-            const int8_t *h = ring[(mc - 1 - e) % XQ_HIST];
-            const uint32_t x = lane < 23 ? (((const uint32_t *)h)[lane] ^ ((const uint32_t *)b)[lane]) : 0u;
-            if (__ballot(x != 0u) == 0ull) ++rep;
-        }
-        if (rep >= 3) {
-            const int w = perpetual ? wave_perpetual_winner(b, ring[0], XQ_BS, (mc - 1) % XQ_HIST, k, side) : 0;
-            *winner = w;
-            return w != 0 ? 4 : 1;
-        }
-    }
-    *winner = 2;
-    return 0;
-}
-
 // mcts.py:137-140: the value a terminal leaf backs up, from the view of the side that moved into it -- 0 for a draw, else 1: the
 // reference takes every decided leaf for a win of the mover.  Only the perpetual-check verdict (`over` == 4) can name the side
 // to move the winner (the mover's check completed its own perpetual): that leaf is the mover's loss.
 __device__ __forceinline__ double terminal_leaf_value(int over, int winner, int side) {
     return winner == 0 ? 0.0 : (over == 4 && winner == side ? -1.0 : 1.0);
-}
-
-// game.py:528-550 on an LDS position + ring.  Wave-uniform scalars updated by reference.
-__device__ __forceinline__ void wave_make_move(int8_t *b, int8_t (*ring)[XQ_BS], int action, int &side, int &mc, int &nocap) {
-    const int from = action / 90, to = action - from * 90;
-    lds_copy_dwords(ring[mc % XQ_HIST], b, XQ_BS / 4);
-    const int captured = b[to], mover = b[from];
-    wave_sync();
-    if (lane_id() == 0) { b[to] = (int8_t)mover; b[from] = 0; }
-    wave_sync();
-    nocap = captured != 0 ? 0 : nocap + 1;
-    side = -side;
-    mc += 1;
 }
 
 // One slot's tree: six arrays of node_cap entries (node 0 is the root)
@@ -247,6 +172,20 @@ __device__ __forceinline__ void slot_store(const Dev &E, const Slot &s, const Se
     }
 }
 
+// Game records (xq_engine_init_gr; E.gr_log is NULL without them, a wave-uniform test): a real move's action goes to the slot's
+// move log at the ply it is played at, before wave_make_move advances the count.  Indexing by the ply makes an opening that
+// ended its game right by construction: the game restarts at ply 0 and the next moves overwrite the log.
+__device__ __forceinline__ void slot_log_move(const Dev &E, Slot &s, int action) {
+    if (!E.gr_log) return;
+    if (s.mc >= XQ_RECORD_MAX_PLIES) { s.ovf |= 256; return; }
+    if (s.lane == 0) E.gr_log[(size_t)s.slot * XQ_RECORD_MAX_PLIES + s.mc] = (uint16_t)action;
+}
+
+// the plies of the game that no search chose, once its opening is played
+__device__ __forceinline__ void slot_log_opening(const Dev &E, const Slot &s) {
+    if (E.gr_log && s.lane == 0) gr_opening(E.gr_log, (size_t)E.cfg.n_games)[s.slot] = (uint16_t)s.mc;
+}
+
 // PH_FINISHED: flush the finished game's samples with z (parallel_selfplay.py:123-132) and its result
 __device__ __forceinline__ void slot_flush_finished(const Dev &E, const Slot &s) {
     const int lane = s.lane, n_samples = s.n_samples;
@@ -321,6 +260,7 @@ __device__ __forceinline__ bool slot_new_game(const Dev &E, Slot &s, SelectLds &
         const int pick = (int)(draw_u64(E, slot, RNG_CHOICE, s.rng_ctr[RNG_CHOICE], s.st) % (uint64_t)cnt);
         s.rng_ctr[RNG_CHOICE] += 1;
         const int action = L.moves[pick];
+        slot_log_move(E, s, action);
         wave_make_move(L.root, L.rhist, action, s.side, s.mc, s.nocap);
         int c2, w2;
         if (wave_game_over(L.root, L.rhist, s.side, s.mc, s.nocap, E.perpetual != 0, L.mg, L.moves, &c2, &w2, &s.ovf)) {
@@ -358,6 +298,7 @@ __device__ __forceinline__ void slot_arena_opening(const Dev &E, Slot &s, Select
             x = philox_u64(E.cfg.seed, 0u, (uint32_t)pair, RNG_ARENA_OPENING, (uint32_t)i, 0u);
         }
         const int action = L.moves[(int)(x % (uint64_t)cnt)];
+        slot_log_move(E, s, action);
         wave_make_move(L.root, L.rhist, action, s.side, s.mc, s.nocap);
         if (s.lane == 0) rec[i] = (uint16_t)action;
         played = i + 1;
@@ -424,17 +365,18 @@ __device__ __forceinline__ int wave_first_max(const int32_t *n, int nch, int &ma
 }
 
 // the real game advances by one move
-__device__ __forceinline__ void slot_play(Slot &s, SelectLds &L, int action) {
+__device__ __forceinline__ void slot_play(const Dev &E, Slot &s, SelectLds &L, int action) {
+    slot_log_move(E, s, action);
     wave_make_move(L.root, L.rhist, action, s.side, s.mc, s.nocap);
     s.d_moves += 1;
     s.dirty = true;
 }
 
 // arena move, MCTS.get_action(temperature=0) (mcts.py:166-174, 197-200): first maximum of the visit counts, move order
-__device__ __forceinline__ void slot_arena_move(Slot &s, SelectLds &L, int nch, int first) {
+__device__ __forceinline__ void slot_arena_move(const Dev &E, Slot &s, SelectLds &L, int nch, int first) {
     int bn;
     const int bi = wave_first_max(s.T.N + first, nch, bn);
-    slot_play(s, L, __builtin_amdgcn_readfirstlane((int)s.T.A[first + bi]));
+    slot_play(E, s, L, __builtin_amdgcn_readfirstlane((int)s.T.A[first + bi]));
 }
 
 // FORCED: policy target pruning at a kind-1 root.  c* = first maximum of N; P* its PUCT score at the root's final
@@ -857,16 +799,14 @@ constexpr int WAVES_PER_WG = 4;
 #if XQ_SELECT_WAVES_PER_EU > 0
 #define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu(XQ_SELECT_WAVES_PER_EU, XQ_SELECT_WAVES_PER_EU)))
 #else
-// Nothing for the instances without forced playouts (0, 0 emits no attribute).  The FORCED instances are held to the same two
-// waves per SIMD: left alone, the two with CAP take 256 VGPRs plus a few AGPRs and halve their occupancy.  Headroom of the
-// unpinned instances: <0,1,0> and <1,1,0> stand at 255 of the 256 VGPRs that two waves allow, the others at 244 / 245, so a
-// change to a shared helper wants the resource table regenerated (profiles/r12_gumbel_kernel_resource_usage.txt).  The GUMBEL
-// instance is held to two waves like the FORCED ones, and so is the AROPEN one since the perpetual-check rule joined
-// wave_game_over: left alone it took 255 VGPRs plus 2 AGPRs and one wave; held, 255 VGPRs, no spill, no scratch
-// (profiles/r14_perpetual_check_kernel_resource_usage.txt; the unpinned instances now stand at 253 to 256).  The SOLVER
-// instances are held to two waves as well (profiles/r15_solver_kernel_resource_usage.txt).
-#define XQ_SELECT_OCC \
-    __attribute__((amdgpu_waves_per_eu((FORCED || GUMBEL || AROPEN || SOLVER) ? 2 : 0, (FORCED || GUMBEL || AROPEN || SOLVER) ? 2 : 0)))
+// Every instance is held to two waves per SIMD.  The FORCED instances came first: left alone, the two with CAP took 256 VGPRs plus
+// a few AGPRs and halved their occupancy; then the GUMBEL one, the AROPEN one when the perpetual-check rule joined wave_game_over
+// (profiles/r14_perpetual_check_kernel_resource_usage.txt), and the SOLVER ones (profiles/r15_solver_kernel_resource_usage.txt).
+// The four plain instances <*, *, 0, 0, 0, 0> stood at 255 / 256 of the 256 VGPRs that two waves allow; the game records' one
+// store per real move (slot_log_move) tipped the two with CAP over into AGPRs and one wave, so they are held as well: 250 to 256
+// VGPRs, no spill, no scratch (profiles/r18_game_records_kernel_resource_usage.txt).  A change to a shared helper wants that table
+// regenerated.
+#define XQ_SELECT_OCC __attribute__((amdgpu_waves_per_eu(2, 2)))
 #endif
 // REUSE (tree reuse): at the end of a move the chosen child and the old allocation mark are handed to k_reroot and
 // k_expand<true> of the same step (GI_RR_NODE / GI_RR_MARK).
@@ -944,6 +884,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
         if (phase == PH_NEWGAME) {
             if (!slot_new_game(E, s, L, arena)) { phase = PH_IDLE; break; }
             if (AROPEN) slot_arena_opening(E, s, L);
+            slot_log_opening(E, s);
             if (REUSE && lane == 0) gi[GI_RR_NODE] = 0;     // a new game never sees a hand-off
             phase = PH_NEWPOS;
         }
@@ -986,10 +927,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
             if (manual) { phase = PH_HOLD; break; }
             phase = PH_NEWPOS;
             sv_add(SV_REMOVED, wave_solver_counts(T, L, nch, first, c, unspent));     // rule 5, arena moves included
-            if (arena) { slot_play(s, L, __builtin_amdgcn_readfirstlane((int)T.A[first + c])); continue; }
+            if (arena) { slot_play(E, s, L, __builtin_amdgcn_readfirstlane((int)T.A[first + c])); continue; }
             const int action = slot_end_move(E, s, L, full_move, true, nch, first, c);
             if (REUSE) slot_hand_off(s, L, nch, first, action);
-            slot_play(s, L, action);
+            slot_play(E, s, L, action);
             if (CAP && !full_move) d_fast_moves += 1;
             continue;
         }
@@ -1005,15 +946,15 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
                 wave_sync();
                 int bn;
                 const int bi = wave_first_max(v, nch, bn);
-                slot_play(s, L, __builtin_amdgcn_readfirstlane((int)T.A[first + bi]));
+                slot_play(E, s, L, __builtin_amdgcn_readfirstlane((int)T.A[first + bi]));
                 continue;
             }
-            if (arena) { slot_arena_move(s, L, nch, first); continue; }
+            if (arena) { slot_arena_move(E, s, L, nch, first); continue; }
             if (GUMBEL && (__builtin_amdgcn_readfirstlane((int)T.M[0]) >> 14) == 3) {
                 unsigned cons, off;
                 const int action = slot_end_move_gumbel(E, s, L, rootP, nch, first, cons, off);
                 d_gz_moves += 1; d_gz_cons += cons; d_gz_off += off;
-                slot_play(s, L, action);
+                slot_play(E, s, L, action);
                 continue;
             }
             const bool pruned = SOLVER || (FORCED && (__builtin_amdgcn_readfirstlane((int)T.M[0]) >> 14) == 1);
@@ -1021,7 +962,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) XQ_SELECT_OCC void k_select(Dev 
             else if (pruned) wave_prune_visits(E, s, L, rootP, fp_k, nch, first);
             const int action = slot_end_move(E, s, L, full_move, pruned, nch, first);
             if (REUSE) slot_hand_off(s, L, nch, first, action);
-            slot_play(s, L, action);
+            slot_play(E, s, L, action);
             if (CAP && !full_move) d_fast_moves += 1;
             continue;
         }
@@ -1564,6 +1505,7 @@ __global__ __launch_bounds__(64) void k_select_multi(Dev E, Mx X, float *__restr
         }
         if (phase == PH_NEWGAME) {
             if (!slot_new_game(E, s, L, arena)) { phase = PH_IDLE; break; }
+            slot_log_opening(E, s);
             phase = PH_NEWPOS;
         }
         if (phase == PH_NEWPOS) {
@@ -1580,8 +1522,8 @@ __global__ __launch_bounds__(64) void k_select_multi(Dev E, Mx X, float *__restr
             if (manual) { phase = PH_HOLD; break; }
             const int nch = __builtin_amdgcn_readfirstlane((int)(T.M[0] & XQ_CNT_MASK));
             const int first = __builtin_amdgcn_readfirstlane(T.C[0]);
-            if (arena) slot_arena_move(s, L, nch, first);
-            else slot_play(s, L, slot_end_move(E, s, L, true, false, nch, first));
+            if (arena) slot_arena_move(E, s, L, nch, first);
+            else slot_play(E, s, L, slot_end_move(E, s, L, true, false, nch, first));
             phase = PH_NEWPOS;
             continue;
         }
@@ -1731,6 +1673,40 @@ void launch_expand(const xq_engine *eng, const Dev &d, const float *policy, cons
     hipLaunchKernelGGL(k[cap_of(eng)][reuse_of(eng)], dim3(eng->cfg.n_games), dim3(64), 0, s, d, policy, value, is_probs);
 }
 
+// Game records (xq_engine_init_gr): the record of every game that stands at PH_FINISHED, one wavefront per slot, launched ahead of
+// the select kernel that flushes the game's samples and result and starts the slot's next game over the same log row.  A game is
+// finished by an expand kernel, so move count, game number, sample count, winner and reason are the slot's state words.  The
+// game takes the next row of the ring while there is one: header and moves copied, the rest of the row zeroed (a drained row
+// never shows an earlier game's tail); on a full ring it only counts as dropped.  Its own kernel: inside slot_flush_finished the
+// copy cost the select instances registers they do not have (profiles/r18_game_records_kernel_resource_usage.txt).
+__global__ __launch_bounds__(64 * WAVES_PER_WG) void k_flush_records(Dev E) {
+    const int slot = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
+    if (slot >= E.cfg.n_games) return;
+    const int lane = lane_id();
+    const int32_t *gi = E.gi + (size_t)slot * GI_N;
+    if (__builtin_amdgcn_readfirstlane(gi[GI_PHASE]) != PH_FINISHED) return;
+    const size_t G = (size_t)E.cfg.n_games;
+    GrHead *h = gr_head(E.gr_log, G);
+    const int cap = __builtin_amdgcn_readfirstlane(h->max_out_games);
+    unsigned r = 0;
+    if (lane == 0) {
+        r = atomicAdd(&h->count, 1u);
+        atomicAdd(r < (unsigned)cap ? &h->recorded : &h->dropped, 1ull);
+    }
+    r = __builtin_amdgcn_readfirstlane(r);
+    if (r >= (unsigned)cap) return;
+    const int mc = __builtin_amdgcn_readfirstlane(gi[GI_MC]);
+    const int n = mc < XQ_RECORD_MAX_PLIES ? mc : XQ_RECORD_MAX_PLIES;
+    xq_game_record *rec = gr_ring(E.gr_log, (size_t)cap) + r;            // r < cap: inside the ring
+    const uint16_t *log = E.gr_log + (size_t)slot * XQ_RECORD_MAX_PLIES;
+    for (int i = lane; i < XQ_RECORD_MAX_PLIES; i += 64) rec->moves[i] = i < n ? log[i] : (uint16_t)0;
+    if (lane == 0) {
+        rec->slot = (uint32_t)slot; rec->game_seq = (uint32_t)gi[GI_GSEQ]; rec->winner = (int8_t)gi[GI_FWINNER];
+        rec->reason = (uint8_t)gi[GI_FREASON]; rec->n_moves = (uint16_t)mc;
+        rec->opening_plies = gr_opening(E.gr_log, G)[slot]; rec->n_samples = (uint16_t)gi[GI_NSAMP];
+    }
+}
+
 Mx make_mx(const xq_engine *e) {
     Mx x;
     x.K = leaves_of(e);
@@ -1746,6 +1722,13 @@ extern "C" {
 int xq_engine_select(const xq_engine *eng, float *dev_nn_input, void *stream) {
     if (!eng || !dev_nn_input) return XQ_ERR_ARG;
     const Dev d = make_dev(eng);
+    if (d.gr_log) {
+        // game records: the finished games' records first, before the select kernel starts the slots' next games
+        hipLaunchKernelGGL(k_flush_records, dim3((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), dim3(64 * WAVES_PER_WG), 0,
+                           (hipStream_t)stream, d);
+        const int rc = launch_status();
+        if (rc != XQ_OK) return rc;
+    }
     if (leaves_of(eng) > 1) {
         hipLaunchKernelGGL(k_select_multi, dim3(eng->cfg.n_games), dim3(64), 0, (hipStream_t)stream, d, make_mx(eng), dev_nn_input);
         return launch_status();

@@ -19,9 +19,11 @@ struct Opts {
     const xq_solver_opts *solver;   // absent, NULL or enabled = 0: no proven-result search
     const xq_root_stats_opts *root_stats;   // absent, NULL or enabled = 0: the samples' pad bytes stay zero
     const xq_eval_mirror_opts *mirror;      // absent, NULL or mode = 0: every request is evaluated as it stands
+    const xq_game_records_opts *records;    // absent, NULL or enabled = 0: no game is recorded
     bool solver_on() const { return solver && solver->enabled != 0; }
     bool mirror_on() const { return mirror && mirror->mode != 0; }
     bool root_stats_on() const { return root_stats && root_stats->enabled != 0; }
+    bool records_on() const { return records && records->enabled != 0; }
 };
 
 struct Layout {
@@ -34,7 +36,8 @@ struct Layout {
 // counters and the pending-leaf records follow the K = 1 layout, which is unchanged.  Gumbel root search (K = 1): the
 // square-root table's region also holds the Gumbel words (gz_bytes); every other engine has the layout it had.
 // Arena options (K = 1, never Gumbel): that region holds the arena words instead (ar_off).  Proven-result search (K = 1, never
-// Gumbel): its counters follow in the same region (sv_off, sv_bytes).
+// Gumbel): its counters follow in the same region (sv_off, sv_bytes).  Game records (every engine that plays games): their words
+// close the region, from its next 256-byte boundary (gr_bytes).
 Layout make_layout(const xq_engine_config *c, const Opts &opts) {
     const int K = opts.K, gz_m = opts.gumbel ? opts.gumbel->considered : 0;
     const bool arena = opts.arena != nullptr;
@@ -66,9 +69,10 @@ Layout make_layout(const xq_engine_config *c, const Opts &opts) {
     put(P_OUTR, (size_t)(c->max_out_results > 0 ? c->max_out_results : 1) * XQ_RESULT_BYTES);
     put(P_CNT, 64);
     put(P_STATS, G * ST_N * 8);
-    put(P_SQRT, opts.solver_on() ? sv_off(G, S, arena) + sv_bytes(G)
-                : arena        ? ar_off(G, S).end
-                               : (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0));
+    const size_t sqrt_bytes = opts.solver_on() ? sv_off(G, S, arena) + sv_bytes(G)
+                              : arena          ? ar_off(G, S).end
+                                               : (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0);
+    put(P_SQRT, opts.records_on() ? gr_align(sqrt_bytes) + gr_bytes(G, (size_t)opts.records->max_out_games) : sqrt_bytes);
     put(P_MNOISE, G * XQ_MAXM * 8);
     put(P_STATSUM, ST_N * 8);
     put(P_REQ, GK * 4);
@@ -160,12 +164,23 @@ bool mirror_ok(const xq_engine_config *c, const Opts &o) {
     return em->mode == 0 || (c && c->manual_moves != 2);
 }
 
+// game records: enabled 0 or 1, reserved words zero; on, a ring of at least one record, an engine that plays games, and games
+// that fit a record
+bool records_ok(const xq_engine_config *c, const Opts &o) {
+    const xq_game_records_opts *gr = o.records;
+    if ((gr->enabled != 0 && gr->enabled != 1) || gr->reserved[0] != 0 || gr->reserved[1] != 0) return false;
+    if (gr->enabled == 0) return true;
+    return gr->max_out_games >= 1 && c && c->manual_moves != 1 && c->max_game_length <= XQ_RECORD_MAX_PLIES &&
+           c->random_opening_moves <= XQ_RECORD_MAX_PLIES;
+}
+
 // every option check, in the order the entry points have always refused in; an absent option passes
 bool opts_ok(const xq_engine_config *c, const Opts &o) {
     if (o.rules && !rules_ok(o.rules)) return false;
     if (o.solver && !solver_ok(o)) return false;
     if (o.root_stats && !root_stats_ok(c, o)) return false;
     if (o.mirror && !mirror_ok(c, o)) return false;
+    if (o.records && !records_ok(c, o)) return false;
     if (!config_ok(c) || !leaves_ok(c, o.K) || !flags_ok(c, o.K, o.flags)) return false;
     if (o.cap && !cap_ok(c, o.K, o.cap)) return false;
     if (o.forced && !forced_ok(c, o.K, o.forced)) return false;
@@ -259,7 +274,8 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
     eng->pad0 = (K > 1 ? K : 0) | (int)(o.flags << 16) | (o.cap ? PAD0_CAP : 0) | (o.forced ? PAD0_FORCED : 0) |
                 (o.gumbel ? PAD0_GUMBEL : 0) | (o.arena ? PAD0_ARENA : 0) |
                 (o.rules && o.rules->perpetual_check ? PAD0_PERPETUAL : 0) | (o.solver_on() ? PAD0_SOLVER : 0) |
-                (o.root_stats_on() ? PAD0_ROOT_STATS : 0) | (o.mirror_on() ? PAD0_EVAL_MIRROR : 0);
+                (o.root_stats_on() ? PAD0_ROOT_STATS : 0) | (o.mirror_on() ? PAD0_EVAL_MIRROR : 0) |
+                (o.records_on() ? PAD0_GAME_RECORDS : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -300,6 +316,13 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
         if (rc != XQ_OK) return rc;
     }
     const Dev d = make_dev(eng);
+    if (o.records_on()) {
+        // game records: the ring, the log, the opening counts and the head zeroed, then the ring's size
+        const size_t G = (size_t)cfg->n_games, M = (size_t)o.records->max_out_games;
+        XQ_TRY(hipMemsetAsync(gr_ring(d.gr_log, M), 0, gr_bytes(G, M), s));
+        XQ_TRY(hipMemcpyAsync(&gr_head(d.gr_log, G)->max_out_games, &o.records->max_out_games, 4, hipMemcpyHostToDevice, s));
+        XQ_TRY(hipStreamSynchronize(s));
+    }
     hipLaunchKernelGGL(k_init, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d);
     if (o.cap) {
         const int rc = launch_status();
@@ -373,6 +396,13 @@ size_t xq_engine_workspace_bytes_em(const xq_engine_config *cfg, int leaves_per_
     return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror});
 }
 
+size_t xq_engine_workspace_bytes_gr(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                                    const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records) {
+    return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror, records});
+}
+
 int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_out) {
     if (k < 1 || k > XQ_MAXM || num_simulations < 1 || num_simulations > 65535 || !host_out) return XQ_ERR_ARG;
     gz_considered_visits(k, num_simulations, host_out);
@@ -444,6 +474,59 @@ int xq_engine_init_em(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       const xq_eval_mirror_opts *mirror, void *ws, size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
     return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror}, ws,
                        ws_bytes, dev_inject, stream);
+}
+
+int xq_engine_init_gr(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                      const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records, void *ws, size_t ws_bytes,
+                      const uint64_t *dev_inject, void *stream) {
+    return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror, records},
+                       ws, ws_bytes, dev_inject, stream);
+}
+
+// the pending records of a game-records engine: the head read back after a synchronise
+static int gr_pending(const xq_engine *eng, hipStream_t s, GrHead *h, uint16_t **log) {
+    if (!records_of(eng)) return XQ_ERR_ARG;
+    *log = make_dev(eng).gr_log;
+    XQ_TRY(hipStreamSynchronize(s));
+    XQ_TRY(hipMemcpy(h, gr_head(*log, (size_t)eng->cfg.n_games), 32, hipMemcpyDeviceToHost));
+    return h->max_out_games >= 1 ? XQ_OK : XQ_ERR_ARG;
+}
+
+static int gr_drain(const xq_engine *eng, void *out, int max_records, int *n_records, hipStream_t s, hipMemcpyKind kind) {
+    if (!n_records) return XQ_ERR_ARG;
+    GrHead h;
+    uint16_t *log;
+    const int rc = gr_pending(eng, s, &h, &log);
+    if (rc != XQ_OK) return rc;
+    const unsigned n = h.count < (unsigned)h.max_out_games ? h.count : (unsigned)h.max_out_games;
+    *n_records = (int)n;
+    if (!out) return XQ_OK;                                  // size query: nothing is consumed
+    if ((int)n > max_records) return XQ_ERR_ARG;             // caller's buffer too small: report the size, keep the data
+    if (n) XQ_TRY(hipMemcpyAsync(out, gr_ring(log, (size_t)h.max_out_games), (size_t)n * XQ_RECORD_BYTES, kind, s));
+    XQ_TRY(hipMemsetAsync(&gr_head(log, (size_t)eng->cfg.n_games)->count, 0, 4, s));
+    XQ_TRY(hipStreamSynchronize(s));
+    return XQ_OK;
+}
+
+int xq_engine_drain_games(const xq_engine *eng, void *host_records, int max_records, int *n_records, void *stream) {
+    return gr_drain(eng, host_records, max_records, n_records, (hipStream_t)stream, hipMemcpyDeviceToHost);
+}
+
+int xq_engine_drain_games_device(const xq_engine *eng, void *dev_records, int max_records, int *n_records, void *stream) {
+    return gr_drain(eng, dev_records, max_records, n_records, (hipStream_t)stream, hipMemcpyDeviceToDevice);
+}
+
+int xq_engine_game_records_stats_read(const xq_engine *eng, xq_game_records_stats *host_out, void *stream) {
+    if (!host_out) return XQ_ERR_ARG;
+    GrHead h;
+    uint16_t *log;
+    const int rc = gr_pending(eng, (hipStream_t)stream, &h, &log);
+    if (rc != XQ_OK) return rc;
+    memset(host_out, 0, sizeof(*host_out));
+    host_out->recorded = h.recorded; host_out->dropped = h.dropped;
+    return XQ_OK;
 }
 
 int xq_engine_solver_stats_read(const xq_engine *eng, xq_solver_stats *host_out, void *stream) {

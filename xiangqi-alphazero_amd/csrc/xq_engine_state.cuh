@@ -54,6 +54,7 @@ enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM
 constexpr int PAD0_PERPETUAL = 1 << 26;     // pad0 of the handle (encoding below): "perpetual-check rule on"
 constexpr int PAD0_ROOT_STATS = 1 << 24;    // "root statistics per sample on" (xq_engine_init_rs)
 constexpr int PAD0_EVAL_MIRROR = (int)(1u << 31);   // "evaluation mirror on" (xq_engine_init_em): the last private bit, the sign
+constexpr int PAD0_GAME_RECORDS = 1 << 23;  // "game records on" (xq_engine_init_gr): the top bit of the public flag byte
 
 // The node meta word tM: the child count in bits 0-11 (at most XQ_MAXM = 128), the node's proven state in bits 12-13 (always 0
 // without xq_engine_init_sv: every reader masks the count, and an engine without the solver stays byte-identical), the prior
@@ -84,7 +85,31 @@ struct Dev {
     int32_t *req;                   // [G] legal moves of the evaluation each slot asked for this step (0: none)
     int perpetual;                  // xq_rules_opts.perpetual_check of xq_engine_init_ru (wave-uniform: a kernel argument)
     int root_stats;                 // xq_root_stats_opts.enabled of xq_engine_init_rs (wave-uniform, like perpetual)
+    uint16_t *gr_log;               // xq_engine_init_gr: the move log [G][XQ_RECORD_MAX_PLIES]; NULL without game records (wave-uniform)
 };
+
+// Game records (xq_engine_init_gr): their words are the LAST of the square-root table's region, behind whatever another option
+// keeps there, so the handle finds them from the region that follows (P_MNOISE) without knowing the ring's size:
+//   ring  xq_game_record[max_out_games] | log uint16[G][XQ_RECORD_MAX_PLIES] | opening uint16[G] | GrHead
+// each part rounded up to 256 bytes.  The ring's size is in the head.
+struct GrHead {
+    int32_t max_out_games;
+    unsigned int count;                 // games flushed since the last xq_engine_drain_games: the ring's cursor
+    unsigned long long recorded, dropped;
+    unsigned long long pad[29];
+};
+static_assert(sizeof(GrHead) == 256, "GrHead layout");
+static_assert(sizeof(xq_game_record) == XQ_RECORD_BYTES && offsetof(xq_game_record, moves) == 16, "xq_game_record layout");
+
+__host__ __device__ inline size_t gr_align(size_t x) { return (x + 255) & ~(size_t)255; }
+__host__ __device__ inline size_t gr_log_bytes(size_t G) { return gr_align(G * XQ_RECORD_MAX_PLIES * 2); }
+__host__ __device__ inline size_t gr_open_bytes(size_t G) { return gr_align(G * 2); }
+__host__ __device__ inline size_t gr_bytes(size_t G, size_t max_out_games) {
+    return max_out_games * XQ_RECORD_BYTES + gr_log_bytes(G) + gr_open_bytes(G) + sizeof(GrHead);
+}
+__host__ __device__ inline uint16_t *gr_opening(uint16_t *log, size_t G) { return (uint16_t *)((char *)log + gr_log_bytes(G)); }
+__host__ __device__ inline GrHead *gr_head(uint16_t *log, size_t G) { return (GrHead *)((char *)log + gr_log_bytes(G) + gr_open_bytes(G)); }
+__host__ __device__ inline xq_game_record *gr_ring(uint16_t *log, size_t max_out_games) { return (xq_game_record *)log - max_out_games; }
 
 Dev make_dev(const xq_engine *e) {
     Dev d;
@@ -101,6 +126,9 @@ Dev make_dev(const xq_engine *e) {
     d.sqrt_tab = (const double *)e->p[P_SQRT]; d.mnoise = (double *)e->p[P_MNOISE]; d.req = (int32_t *)e->p[P_REQ];
     d.perpetual = (e->pad0 & PAD0_PERPETUAL) != 0;
     d.root_stats = (e->pad0 & PAD0_ROOT_STATS) != 0;
+    d.gr_log = (e->pad0 & PAD0_GAME_RECORDS)
+                   ? (uint16_t *)((char *)e->p[P_MNOISE] - sizeof(GrHead) - gr_open_bytes((size_t)e->cfg.n_games) - gr_log_bytes((size_t)e->cfg.n_games))
+                   : nullptr;
     return d;
 }
 
@@ -164,7 +192,8 @@ __host__ __device__ inline size_t sv_bytes(size_t G) { return G * SV_WORDS * 8; 
 // (xq_engine_init_gz), "arena options on" (xq_engine_init_ar), "perpetual-check rule on" (xq_engine_init_ru), "proven-result
 // search on" (xq_engine_init_sv), "root statistics per sample on" (xq_engine_init_rs, PAD0_ROOT_STATS above) and, in bit 31,
 // "evaluation mirror on" (xq_engine_init_em, PAD0_EVAL_MIRROR above).  Bits 24-31 are now all taken; of the public flag byte
-// (bits 16-23) only bit 16 is.
+// (bits 16-23) bit 16 is, and bit 23 says "game records on" (xq_engine_init_gr, PAD0_GAME_RECORDS above): flags_ok lets no
+// caller's flag reach it.
 constexpr int PAD0_CAP = 1 << 30;
 constexpr int PAD0_FORCED = 1 << 29;
 constexpr int PAD0_GUMBEL = 1 << 28;
@@ -177,6 +206,7 @@ bool forced_of(const xq_engine *e) { return (e->pad0 & PAD0_FORCED) != 0; }
 bool gumbel_of(const xq_engine *e) { return (e->pad0 & PAD0_GUMBEL) != 0; }
 bool solver_of(const xq_engine *e) { return (e->pad0 & PAD0_SOLVER) != 0; }
 bool mirror_of(const xq_engine *e) { return (e->pad0 & PAD0_EVAL_MIRROR) != 0; }
+bool records_of(const xq_engine *e) { return e && (e->pad0 & PAD0_GAME_RECORDS) != 0 && e->cfg.n_games > 0 && e->p[P_MNOISE]; }
 bool arena_of(const xq_engine *e) { return e && (e->pad0 & PAD0_ARENA) != 0 && e->cfg.n_games > 0 && e->p[P_SQRT]; }
 
 // ---------------------------------------------------------------------------------------------------------

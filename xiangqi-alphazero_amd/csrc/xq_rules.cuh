@@ -376,7 +376,7 @@ enum : int { XQ_OVER_NONE = 0, XQ_OVER_KING = 1, XQ_OVER_NO_MOVE = 2, XQ_OVER_NO
              XQ_OVER_REPETITION = 5, XQ_OVER_PERPETUAL = 6 };
 
 // The opt-in perpetual-check rule (include/xq_hip.h, xq_rules_opts) for a position whose repetition test has fired (three or
-// more of the last k <= XQ_HIST pre-move boards equal the current board `b`); one copy for wave_game_over (xq_engine.hip) and
+// more of the last k <= XQ_HIST pre-move boards equal the current board `b`); one copy for wave_game_over (below) and
 // k_game_over (xq_batch.hip).  Entry e, the board e + 1 plies ago, is row (newest - e) mod XQ_HIST of `hist` (rows `stride`
 // bytes apart, LDS or global); `side` is to move in `b`, so by ply parity -side is to move in the even entries and side in the
 // odd ones.  Returns the winner: the side that did NOT check on every one of its moves of the span (entries 0 .. E, E the
@@ -424,6 +424,85 @@ __device__ __forceinline__ void wave_load_board(const int8_t *g, int8_t *s) {
     const int lane = lane_id();
     s[lane] = g[lane];
     if (lane < 32) s[lane + 64] = (lane + 64 < 90) ? g[lane + 64] : (int8_t)0;
+}
+
+// ---- one position with its 12-board repetition ring in LDS: the engine's real and simulated games (xq_engine.hip) and the
+// replay of game records (xq_replay.hip)
+__device__ __forceinline__ void lds_copy_dwords(void *dst, const void *src, int ndw) {
+    const int lane = lane_id();
+    uint32_t *d = (uint32_t *)dst;
+    const uint32_t *s = (const uint32_t *)src;
+    for (int i = lane; i < ndw; i += 64) d[i] = s[i];
+}
+
+__device__ __forceinline__ void init_board_lds(int8_t *b) {
+    const int lane = lane_id();
+    for (int sq = lane; sq < XQ_BS; sq += 64) {
+        int v = 0;
+        if (sq < 90) {
+            const int r = sq / 9, c = sq % 9;
+            const int back = (c == 0 || c == 8) ? 5 : (c == 1 || c == 7) ? 4 : (c == 2 || c == 6) ? 3 : (c == 3 || c == 5) ? 2 : 1;
+            if (r == 0) v = back;
+            else if (r == 9) v = -back;
+            else if (r == 2 && (c == 1 || c == 7)) v = 6;
+            else if (r == 7 && (c == 1 || c == 7)) v = -6;
+            else if (r == 3 && (c % 2 == 0)) v = 7;
+            else if (r == 6 && (c % 2 == 0)) v = -7;
+        }
+        b[sq] = (int8_t)v;
+    }
+}
+
+// game.py:565-616 on an LDS position.  Leaves the ordered legal moves in `moves` (count in *cnt) whenever both
+// kings stand.  Wave-uniform result: 0 not over, 1 over, 4 over by the perpetual-check rule (`perpetual`: the engine's
+// xq_rules_opts flag) -- the values of a root's status word and a result's reason.
+__device__ inline int wave_game_over(const int8_t *b, const int8_t (*ring)[XQ_BS], int side, int mc, int nocap, bool perpetual,
+                                     MoveGenLds &mg, uint16_t *moves, int *cnt, int *winner, int *ovf) {
+    const VMove none{-1, -1, 0};
+    const int lane = lane_id();
+    *cnt = 0;
+    if (find_king(b, none, 1) < 0) { *winner = -1; return 1; }
+    if (find_king(b, none, -1) < 0) { *winner = 1; return 1; }
+    const int n = wave_movegen(b, side, mg, moves, ovf);
+    *cnt = n;
+    if (n == 0) { *winner = -side; return 1; }
+    if (nocap >= 120) { *winner = 0; return 1; }
+    if (mc >= 200) {
+        int red, black;
+        wave_material(b, red, black);
+        const int diff = red - black;
+        *winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
+        return 1;
+    }
+    if (mc >= 6) {
+        const int k = mc < XQ_HIST ? mc : XQ_HIST;
+        int rep = 0;
+        for (int e = 0; e < k; ++e) {
+            const int8_t *h = ring[(mc - 1 - e) % XQ_HIST];
+            const uint32_t x = lane < 23 ? (((const uint32_t *)h)[lane] ^ ((const uint32_t *)b)[lane]) : 0u;
+            if (__ballot(x != 0u) == 0ull) ++rep;
+        }
+        if (rep >= 3) {
+            const int w = perpetual ? wave_perpetual_winner(b, ring[0], XQ_BS, (mc - 1) % XQ_HIST, k, side) : 0;
+            *winner = w;
+            return w != 0 ? 4 : 1;
+        }
+    }
+    *winner = 2;
+    return 0;
+}
+
+// game.py:528-550 on an LDS position + ring.  Wave-uniform scalars updated by reference.
+__device__ __forceinline__ void wave_make_move(int8_t *b, int8_t (*ring)[XQ_BS], int action, int &side, int &mc, int &nocap) {
+    const int from = action / 90, to = action - from * 90;
+    lds_copy_dwords(ring[mc % XQ_HIST], b, XQ_BS / 4);
+    const int captured = b[to], mover = b[from];
+    wave_sync();
+    if (lane_id() == 0) { b[to] = (int8_t)mover; b[from] = 0; }
+    wave_sync();
+    nocap = captured != 0 ? 0 : nocap + 1;
+    side = -side;
+    mc += 1;
 }
 
 }  // namespace xq

@@ -91,6 +91,14 @@ randomly chosen left-right orientation: `compact()` hands the evaluator the mirr
 original order, when the request's bit (`hip.eval_mirror_bit`, a function of seed, rank, slot, game, ply, root / leaf, simulations
 done and row) is 1, so the logits come back un-mirrored and the search averages the network's left/right asymmetry away.  It needs
 the packed step (an evaluator with `live_rows`); not with the evaluation cache and not for arena games; every other option.
+
+With `record_games=True` (opt-in; xq_engine_init_gr) every finished game leaves a 1024-byte record
+(`hip.GAME_RECORD_DTYPE`): slot and game_seq (the join key with its result and samples), winner, reason, n_moves, opening_plies,
+n_samples and the action of every ply, opening plies, fast moves and arena moves included.  `drain_games()` returns the records of
+the games finished since its last call (at most `max_out_games`, default the config's max_out_results; later games count in
+`game_records_stats()['dropped']`), `drain_games_device()` the same as a device tensor.  `replay_games` plays records on the
+device: legality of every move, the position at any ply in `set_position`'s form, and the rules' verdict there.  Games, samples,
+results and statistics are byte-identical with and without it.  Self-play and arena engines, every other option.
 """
 from __future__ import annotations
 
@@ -149,6 +157,7 @@ class EngineOptions(collections.namedtuple("EngineOptions", "K flags cap forced 
     solver = None              # hip.SolverOpts or None: what xq_engine_*_sv take after `rules`
     root_stats = None          # hip.RootStatsOpts or None: what xq_engine_*_rs take after `solver`
     eval_mirror = None         # hip.EvalMirrorOpts or None: what xq_engine_*_em take after `root_stats`
+    game_records = None        # hip.GameRecordsOpts or None: what xq_engine_*_gr take after `eval_mirror`
 
 
 RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_game_over, and its perpetual-check verdict
@@ -157,7 +166,7 @@ RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
                          forced_playouts=None, gumbel=None, arena_opts=None, eval_cache_entries: int = 0,
                          perpetual_check: bool = False, solver: bool = False, root_stats: bool = False,
-                         eval_mirror: bool = False) -> EngineOptions:
+                         eval_mirror: bool = False, record_games: bool = False, max_out_games=None) -> EngineOptions:
     """The engine options of `SelfPlayEngine` checked and turned into the C structs; needs no GPU.  Every rule of the header's
     refusal lists (include/xq_hip.h; opts_ok in csrc/xq_engine_setup.hip) is refused here first, with a message that names the
     option; tests/test_engine_options.py holds the two side by side."""
@@ -266,7 +275,28 @@ def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tre
     if eval_mirror and eval_cache_entries:
         raise hip.XqError("eval_mirror cannot be combined with an evaluation cache (eval_cache_entries > 0): a hit would return "
                           "whichever orientation was evaluated first")
+    if record_games not in (False, True, 0, 1):
+        raise hip.XqError(f"record_games must be a bool, got {record_games!r}")
+    if max_out_games is not None and not record_games:
+        raise hip.XqError("max_out_games is record_games' ring size: it needs record_games=True")
+    gr = None
+    if record_games:
+        if int(cfg.manual_moves) == 1:
+            raise hip.XqError("record_games needs an engine that plays games: not available with manual_moves = 1 (search only)")
+        if int(cfg.max_game_length) > hip.RECORD_MAX_PLIES or int(cfg.random_opening_moves) > hip.RECORD_MAX_PLIES:
+            raise hip.XqError(f"record_games: max_game_length and random_opening_moves must be <= {hip.RECORD_MAX_PLIES}, got "
+                              f"{cfg.max_game_length}, {cfg.random_opening_moves}")
+        try:
+            n_out = int(cfg.max_out_results) if max_out_games is None else int(max_out_games)
+            if max_out_games is not None and n_out != max_out_games:
+                raise ValueError
+        except (TypeError, ValueError, OverflowError):
+            raise hip.XqError(f"record_games: max_out_games must be an integer, got {max_out_games!r}")
+        if not 1 <= n_out <= 2 ** 31 - 1:
+            raise hip.XqError(f"record_games: max_out_games must be in [1, 2^31), got {n_out}")
+        gr = hip.GameRecordsOpts(1, n_out)
     opts = EngineOptions(K, hip.ENGINE_TREE_REUSE if tree_reuse else 0, cap, forced, gz, ar)
+    opts.game_records = gr
     if eval_mirror:
         opts.eval_mirror = hip.EvalMirrorOpts(1)
     if solver:
@@ -282,13 +312,14 @@ class SelfPlayEngine:
     def __init__(self, cfg: hip.EngineConfig, device="cuda", evaluator: Optional[Callable] = None,
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
-                 perpetual_check: bool = False, solver: bool = False, root_stats: bool = False, eval_mirror: bool = False):
+                 perpetual_check: bool = False, solver: bool = False, root_stats: bool = False, eval_mirror: bool = False,
+                 record_games: bool = False, max_out_games=None):
         opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
             gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check,
-            solver=solver, root_stats=root_stats, eval_mirror=eval_mirror)
+            solver=solver, root_stats=root_stats, eval_mirror=eval_mirror, record_games=record_games, max_out_games=max_out_games)
         K, flags, cap, forced, gz, ar = opts
-        rules, sv, rs, em = opts.rules, opts.solver, opts.root_stats, opts.eval_mirror
+        rules, sv, rs, em, gr = opts.rules, opts.solver, opts.root_stats, opts.eval_mirror, opts.game_records
         if em is not None and not getattr(evaluator, "live_rows", False):
             raise hip.XqError("eval_mirror acts in the packed step only: it needs an evaluator with live_rows (the HIP evaluators)")
         if not torch.cuda.is_available():
@@ -307,11 +338,13 @@ class SelfPlayEngine:
         self.solver = sv is not None
         self.root_stats = rs is not None
         self.eval_mirror = em is not None
+        self.record_games = gr is not None
+        self.max_out_games = 0 if gr is None else int(gr.max_out_games)
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         # every entry point is the widest one with NULL for the options it does not take (include/xq_hip.h)
-        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules, sv, rs, em)]
-        nbytes = self.lib.xq_engine_workspace_bytes_em(C.byref(cfg), K, flags, *refs)
+        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules, sv, rs, em, gr)]
+        nbytes = self.lib.xq_engine_workspace_bytes_gr(C.byref(cfg), K, flags, *refs)
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
@@ -327,8 +360,8 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            hip.check(self.lib.xq_engine_init_em(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
-                                                 hip.stream_ptr(self.device)), "xq_engine_init_em")
+            hip.check(self.lib.xq_engine_init_gr(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
+                                                 hip.stream_ptr(self.device)), "xq_engine_init_gr")
         # zero-copy int32 view of the per-slot state words (columns hip.GI_*: side to move of the REAL game, move_count, phase,
         # simulations done): host-side policies such as the arena's model choice read it between stages
         gi_off = int(self.h.p[hip.P_GI]) - int(self.ws.data_ptr())
@@ -672,6 +705,61 @@ class SelfPlayEngine:
                       "xq_engine_drain_device")
         return smp, res
 
+    def drain_games(self) -> np.ndarray:
+        """-> the records of the games finished since the last call (hip.GAME_RECORD_DTYPE, in the order they finished, at most
+        max_out_games); empties the record ring only (xq_engine_drain_games).  Needs record_games=True."""
+        if not self.record_games:
+            raise hip.XqError("drain_games needs an engine with record_games=True")
+        n = C.c_int()
+        sp = hip.stream_ptr(self.device)
+        hip.check(self.lib.xq_engine_drain_games(C.byref(self.h), None, 0, C.byref(n), sp), "xq_engine_drain_games")
+        rec = np.zeros(n.value, dtype=hip.GAME_RECORD_DTYPE)
+        if n.value:
+            hip.check(self.lib.xq_engine_drain_games(C.byref(self.h), rec.ctypes.data, len(rec), C.byref(n), sp),
+                      "xq_engine_drain_games")
+        return rec[:n.value]
+
+    def drain_games_device(self) -> torch.Tensor:
+        """-> the same records as a DEVICE tensor uint8[n, 1024] (xq_engine_drain_games_device), what `replay_games` takes."""
+        if not self.record_games:
+            raise hip.XqError("drain_games_device needs an engine with record_games=True")
+        n = C.c_int()
+        sp = hip.stream_ptr(self.device)
+        hip.check(self.lib.xq_engine_drain_games_device(C.byref(self.h), None, 0, C.byref(n), sp), "xq_engine_drain_games_device")
+        rec = torch.empty((n.value, hip.RECORD_BYTES), dtype=torch.uint8, device=self.device)
+        if n.value:
+            hip.check(self.lib.xq_engine_drain_games_device(C.byref(self.h), rec.data_ptr(), n.value, C.byref(n), sp),
+                      "xq_engine_drain_games_device")
+        return rec[:n.value]
+
+    def game_records_stats(self) -> dict:
+        """recorded: games whose record found a row of the ring; dropped: games that finished on a full ring."""
+        if not self.record_games:
+            raise hip.XqError("game_records_stats needs an engine with record_games=True")
+        s = hip.GameRecordsStats()
+        hip.check(self.lib.xq_engine_game_records_stats_read(C.byref(self.h), C.byref(s), hip.stream_ptr(self.device)),
+                  "xq_engine_game_records_stats_read")
+        return dict(recorded=int(s.recorded), dropped=int(s.dropped))
+
+    def game_record_views(self) -> dict:
+        """Zero-copy views of the game records' words in the workspace (csrc/xq_engine_state.cuh: the last words of the square-root
+        table's region, in front of P_MNOISE): `ring` int16 [max_out_games, 512] (uint16 bits: 8 header words, then the moves),
+        `log` int16 [G, 504] (the running games' moves so far) and `opening` int16 [G].  For tests and tools."""
+        if not self.record_games:
+            raise hip.XqError("game_record_views needs an engine with record_games=True")
+
+        def up(n):
+            return (n + 255) & ~255
+
+        G, M = self.G, self.max_out_games
+        head = int(self.h.p[hip.P_MNOISE]) - int(self.ws.data_ptr()) - 256
+        opening = head - up(G * 2)
+        log = opening - up(G * hip.RECORD_MAX_PLIES * 2)
+        ring = log - M * hip.RECORD_BYTES
+        return dict(ring=self.ws[ring:ring + M * hip.RECORD_BYTES].view(torch.int16).view(M, hip.RECORD_BYTES // 2),
+                    log=self.ws[log:log + G * hip.RECORD_MAX_PLIES * 2].view(torch.int16).view(G, hip.RECORD_MAX_PLIES),
+                    opening=self.ws[opening:opening + G * 2].view(torch.int16))
+
     def arena_views(self) -> dict:
         """Zero-copy torch views of the SoA tree arenas in the workspace, [G, node_cap] each:
         N int32, W float64, P float32, action int16 (uint16 bits), first int32 (first child, -1 = none), meta int16
@@ -745,10 +833,37 @@ class SelfPlayEngine:
 
 
 def arena_engine(cfg: hip.EngineConfig, device, opening_plies: int, first_game: int, inject=None,
-                 perpetual_check: bool = False, solver: bool = False) -> SelfPlayEngine:
+                 perpetual_check: bool = False, solver: bool = False, record_games: bool = False) -> SelfPlayEngine:
     """The arena's engine with arena options (paired openings from game index `first_game`, the per-model packed step)."""
     return SelfPlayEngine(cfg, device, inject=inject, arena_opts=(int(opening_plies), int(first_game)),
-                          perpetual_check=perpetual_check, solver=solver)
+                          perpetual_check=perpetual_check, solver=solver, record_games=record_games)
+
+
+def replay_games(records, stop_ply=None, perpetual_check: bool = False, device="cuda") -> dict:
+    """Replay game records on the device (xq_replay_games_batch, one wavefront per record).  `records`: a structured array of
+    hip.GAME_RECORD_DTYPE (as `drain_games` returns) or a uint8 tensor [n, 1024] (as `drain_games_device` does); `stop_ply`: None
+    (every move), one int for all records or one per record, clamped to [0, n_moves].  Returns a dict of device tensors:
+    `status` (0: every requested ply was legal; k > 0: ply k - 1 is illegal and the outputs describe the position before it; -1:
+    a malformed record), `board` int8[n, 90], `side`, `move_count`, `no_capture`, `hist12` int8[n, 12, 90] -- these five rows go
+    straight into `set_position` or `MCTS` -- and `over_kind` (0 not over, 1 over, 4 over by the perpetual-check rule) with
+    `winner` (2 while not over): the rules' verdict at the position reached."""
+    if isinstance(records, torch.Tensor):
+        rec = records.to(device)
+    else:
+        arr = np.ascontiguousarray(records)
+        if arr.dtype != hip.GAME_RECORD_DTYPE:
+            raise hip.XqError(f"replay_games: records must have hip.GAME_RECORD_DTYPE, got {arr.dtype}")
+        rec = torch.from_numpy(arr.reshape(-1).view(np.uint8).reshape(-1, hip.RECORD_BYTES).copy()).to(device)
+    rec = rec.contiguous()
+    n = rec.shape[0]
+    stop = None
+    if stop_ply is not None:
+        if isinstance(stop_ply, torch.Tensor):
+            stop = stop_ply.to(device=rec.device, dtype=torch.int32).contiguous()
+        else:
+            stop = torch.from_numpy(np.broadcast_to(np.asarray(stop_ply, dtype=np.int32), (n,)).copy()).to(rec.device)
+    with torch.cuda.device(rec.device):
+        return hip.replay_games(rec, stop, perpetual_check)
 
 
 action_probs_dense = dense_pi   # the reference's dense pi (mcts.py:190-206) from compact (action, visit) pairs

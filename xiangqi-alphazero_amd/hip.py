@@ -15,6 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("XQ_HIP_LIB", os.path.join(_HERE, "libxq_hip.so"))   # override: perf experiments only
 CSRC = os.path.join(_HERE, "csrc")
 
+from .sample_format import GAME_RECORD_DTYPE  # noqa: E402,F401  (numpy only: the record's layout lives with the other formats)
+
 MAXM = 128
 SAMPLE_BYTES = 640
 RESULT_BYTES = 16
@@ -23,6 +25,8 @@ STATE_FLOATS = 1350
 ENGINE_TREE_REUSE = 1          # XQ_ENGINE_TREE_REUSE
 ARENA_MAX_OPENING = 16         # XQ_ARENA_MAX_OPENING
 REUSE_MAX_SIMS = 1600          # XQ_REUSE_MAX_SIMS
+RECORD_MAX_PLIES = 504         # XQ_RECORD_MAX_PLIES
+RECORD_BYTES = 1024            # XQ_RECORD_BYTES
 
 
 class XqError(RuntimeError):
@@ -63,6 +67,7 @@ P_ROOTP = 12       # mirrors P_ROOTP of enum Ptr: the float64 root priors
 P_OUTS, P_OUTR = 14, 15   # mirror P_OUTS, P_OUTR of enum Ptr: the sample ring and the result ring that the drains read
 P_STATS = 17       # mirrors P_STATS of enum Ptr: the per-slot counters
 P_SQRT = 19        # mirrors P_SQRT of enum Ptr: the square-root table and the Gumbel / arena words behind it
+P_MNOISE = 20      # mirrors P_MNOISE of enum Ptr: the injected-noise table; the game records' words end where it begins
 P_VL = 30          # mirrors P_VL of enum Ptr: the virtual-loss counters (leaves_per_step > 1)
 GI_SIDE = 0        # mirrors GI_SIDE of enum Gi in csrc/xq_engine_state.cuh: side to move of the real game
 GI_MC = 1          # mirrors GI_MC of enum Gi: its move count
@@ -131,6 +136,27 @@ class RootStatsOpts(C.Structure):
 class EvalMirrorOpts(C.Structure):
     """xq_eval_mirror_opts: random mirror of the packed step's evaluation requests (xq_engine_init_em): mode 0 off / 1 random."""
     _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class GameRecordsOpts(C.Structure):
+    """xq_game_records_opts: game records (xq_engine_init_gr): enabled 0 / 1, rows of the ring of finished games."""
+    _fields_ = [("enabled", C.c_int32), ("max_out_games", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class GameRecordsStats(C.Structure):
+    """xq_game_records_stats: games whose record found a row of the ring, and games that did not (xq_engine_game_records_stats_read)."""
+    _fields_ = [("recorded", C.c_uint64), ("dropped", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+class GameRecord(C.Structure):
+    """xq_game_record: one finished game, 1024 bytes."""
+    _fields_ = [("slot", C.c_uint32), ("game_seq", C.c_uint32), ("winner", C.c_int8), ("reason", C.c_uint8),
+                ("n_moves", C.c_uint16), ("opening_plies", C.c_uint16), ("n_samples", C.c_uint16),
+                ("moves", C.c_uint16 * RECORD_MAX_PLIES)]
+
+
+# xq_game_record as a numpy record: what drain_games returns, what replay_games and sample_format.records_to_text take
+assert GAME_RECORD_DTYPE.itemsize == RECORD_BYTES == C.sizeof(GameRecord)
 
 
 class BatchOpts(C.Structure):
@@ -238,6 +264,13 @@ def lib():
     L.xq_engine_workspace_bytes_em.argtypes = L.xq_engine_workspace_bytes_rs.argtypes + [C.POINTER(EvalMirrorOpts)]
     L.xq_engine_workspace_bytes_em.restype = C.c_size_t
     L.xq_engine_init_em.argtypes = L.xq_engine_init_rs.argtypes[:11] + [C.POINTER(EvalMirrorOpts)] + L.xq_engine_init_rs.argtypes[11:]
+    L.xq_engine_workspace_bytes_gr.argtypes = L.xq_engine_workspace_bytes_em.argtypes + [C.POINTER(GameRecordsOpts)]
+    L.xq_engine_workspace_bytes_gr.restype = C.c_size_t
+    L.xq_engine_init_gr.argtypes = L.xq_engine_init_em.argtypes[:12] + [C.POINTER(GameRecordsOpts)] + L.xq_engine_init_em.argtypes[12:]
+    L.xq_engine_drain_games.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
+    L.xq_engine_drain_games_device.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
+    L.xq_engine_game_records_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(GameRecordsStats), vp]
+    L.xq_replay_games_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.xq_eval_mirror_bit_host.argtypes = [C.c_uint64, i32, i32, C.c_uint32, i32, i32, i32, i32]
     L.xq_mirror_action_host.argtypes = [i32]
     L.xq_mirror_requests_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
@@ -329,7 +362,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_workspace_bytes_sv", "xq_engine_init_sv", "xq_engine_read_root_states", "xq_engine_solver_stats_read",
            "xq_engine_workspace_bytes_rs", "xq_engine_init_rs", "xq_samples_to_batch_ex",
            "xq_engine_workspace_bytes_em", "xq_engine_init_em", "xq_eval_mirror_bit_host", "xq_mirror_action_host",
-           "xq_mirror_requests_batch"]
+           "xq_mirror_requests_batch", "xq_engine_workspace_bytes_gr", "xq_engine_init_gr", "xq_engine_drain_games",
+           "xq_engine_drain_games_device", "xq_engine_game_records_stats_read", "xq_replay_games_batch"]
 
 
 def check(rc: int, what: str):
@@ -429,6 +463,28 @@ def game_over_batch(boards, side, move_count, no_capture, hist, perpetual_check:
                                           None if kind is None else _dev(kind), stream_ptr(boards.device)),
               "xq_game_over_batch_ex")
     return (out, kind) if return_kind else out
+
+
+def replay_games(records: torch.Tensor, stop_ply=None, perpetual_check: bool = False):
+    """Replay of game records on the device (xq_replay_games_batch): records uint8[n, 1024] on the GPU, stop_ply int32[n] there or
+    None (all moves) -> dict of tensors: status int32[n], board int8[n,90], side int8[n], move_count / no_capture int32[n],
+    hist12 int8[n,12,90] (oldest first, set_position's layout), over_kind / winner int8[n]."""
+    if records.dtype != torch.uint8 or records.dim() != 2 or records.shape[1] != RECORD_BYTES:
+        raise XqError(f"replay_games: records must be uint8[n, {RECORD_BYTES}], got {records.dtype} {tuple(records.shape)}")
+    n, dev = records.shape[0], records.device
+    if stop_ply is not None and (stop_ply.dtype != torch.int32 or tuple(stop_ply.shape) != (n,)):
+        raise XqError(f"replay_games: stop_ply must be int32[{n}]")
+    out = {"status": torch.zeros(n, dtype=torch.int32, device=dev), "board": torch.zeros((n, 90), dtype=torch.int8, device=dev),
+           "side": torch.zeros(n, dtype=torch.int8, device=dev), "move_count": torch.zeros(n, dtype=torch.int32, device=dev),
+           "no_capture": torch.zeros(n, dtype=torch.int32, device=dev),
+           "hist12": torch.zeros((n, 12, 90), dtype=torch.int8, device=dev),
+           "over_kind": torch.zeros(n, dtype=torch.int8, device=dev), "winner": torch.zeros(n, dtype=torch.int8, device=dev)}
+    if n:
+        check(lib().xq_replay_games_batch(_dev(records), None if stop_ply is None else _dev(stop_ply), n, 1 if perpetual_check else 0,
+                                          _dev(out["board"]), _dev(out["side"]), _dev(out["move_count"]), _dev(out["no_capture"]),
+                                          _dev(out["hist12"]), _dev(out["status"]), _dev(out["over_kind"]), _dev(out["winner"]),
+                                          stream_ptr(dev)), "xq_replay_games_batch")
+    return out
 
 
 def eval_mirror_bit(seed: int, rank: int, slot: int, game_seq: int, ply: int, is_root, sims_done: int, row: int = 0) -> int:

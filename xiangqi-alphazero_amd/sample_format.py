@@ -22,6 +22,12 @@ SAMPLE_DTYPE = np.dtype([("board", np.int8, 90), ("side", np.int8), ("z", np.int
 RESULT_DTYPE = np.dtype([("slot", np.uint32), ("game_seq", np.uint32), ("winner", np.int8), ("reason", np.uint8),
                          ("steps", np.uint16), ("n_samples", np.uint16), ("reserved", np.uint16)])
 assert SAMPLE_DTYPE.itemsize == 640 and RESULT_DTYPE.itemsize == 16
+# xq_game_record: what an engine with record_games=True (xq_engine_init_gr) keeps of every finished game
+RECORD_MAX_PLIES = 504
+GAME_RECORD_DTYPE = np.dtype([("slot", np.uint32), ("game_seq", np.uint32), ("winner", np.int8), ("reason", np.uint8),
+                              ("n_moves", np.uint16), ("opening_plies", np.uint16), ("n_samples", np.uint16),
+                              ("moves", np.uint16, RECORD_MAX_PLIES)])
+assert GAME_RECORD_DTYPE.itemsize == 1024 and GAME_RECORD_DTYPE.fields["moves"][1] == 16
 # xq_sample_root_stats: what an engine with root_stats=True (xq_engine_init_rs) writes into a sample's `pad` bytes
 ROOT_STATS_DTYPE = np.dtype([("root_q", np.float32), ("root_visits", np.uint32), ("has_root_stats", np.uint8),
                              ("zero", np.uint8, 11)])
@@ -138,3 +144,65 @@ def reachable_actions() -> np.ndarray:
                     if dr == 0 or dc == 0 or (dr, dc) in ((1, 2), (2, 1), (1, 1), (2, 2)):
                         acts.append((fr * 9 + fc) * 90 + tr * 9 + tc)
     return np.array(sorted(acts), dtype=np.int64)
+
+
+# ---- game records as text: one game per line, ICCS coordinate moves ---------------------------------------------------------
+_RESULT_TEXT = {1: "1-0", -1: "0-1", 0: "1/2-1/2"}
+_RESULT_WINNER = {v: k for k, v in _RESULT_TEXT.items()}
+_RECORD_KEYS = ("reason", "opening_plies", "n_samples", "slot", "game_seq")
+
+
+def action_to_iccs(action: int) -> str:
+    """The project's action code (from * 90 + to, square = row * 9 + column, row 0 red's back rank) as an ICCS coordinate move:
+    files a-i for columns 0-8, ranks 0-9 for rows 0-9, e.g. 1732 -> 'b2e2'."""
+    a = int(action)
+    if not 0 <= a < ACTION_SPACE:
+        raise ValueError(f"no action code: {action}")
+    f, t = divmod(a, 90)
+    return "%s%d%s%d" % ("abcdefghi"[f % 9], f // 9, "abcdefghi"[t % 9], t // 9)
+
+
+def iccs_to_action(move: str) -> int:
+    if len(move) != 4 or move[0] not in "abcdefghi" or move[2] not in "abcdefghi" or not (move[1] + move[3]).isdigit():
+        raise ValueError(f"no ICCS coordinate move: {move!r}")
+    return (int(move[1]) * 9 + ord(move[0]) - 97) * 90 + int(move[3]) * 9 + ord(move[2]) - 97
+
+
+def records_to_text(records: np.ndarray) -> str:
+    """Game records (GAME_RECORD_DTYPE) as text, one game per line: the moves as ICCS coordinates in ply order, the result
+    ('1-0' red won, '0-1' black won, '1/2-1/2'), then reason, opening_plies, n_samples, slot and game_seq as key=value.
+    `records_from_text` reads it back exactly."""
+    lines = []
+    for r in np.asarray(records).reshape(-1):
+        n = int(r["n_moves"])
+        if n > RECORD_MAX_PLIES or int(r["winner"]) not in _RESULT_TEXT:
+            raise ValueError(f"malformed game record: n_moves {n}, winner {int(r['winner'])}")
+        words = [action_to_iccs(a) for a in r["moves"][:n]] + [_RESULT_TEXT[int(r["winner"])]]
+        words += ["%s=%d" % (k, int(r[k])) for k in _RECORD_KEYS]
+        lines.append(" ".join(words))
+    return "".join(line + "\n" for line in lines)
+
+
+def records_from_text(text: str) -> np.ndarray:
+    """The inverse of `records_to_text`; blank lines and lines starting with '#' are skipped."""
+    out = []
+    for line in text.splitlines():
+        words = line.split()
+        if not words or words[0].startswith("#"):
+            continue
+        at = [i for i, w in enumerate(words) if w in _RESULT_WINNER]
+        if len(at) != 1:
+            raise ValueError(f"a game line holds exactly one result: {line!r}")
+        rec = np.zeros((), dtype=GAME_RECORD_DTYPE)
+        moves = [iccs_to_action(w) for w in words[:at[0]]]
+        if len(moves) > RECORD_MAX_PLIES:
+            raise ValueError(f"a game record holds at most {RECORD_MAX_PLIES} moves, got {len(moves)}")
+        rec["n_moves"], rec["winner"] = len(moves), _RESULT_WINNER[words[at[0]]]
+        rec["moves"][:len(moves)] = moves
+        keys = dict(w.split("=", 1) for w in words[at[0] + 1:])
+        if sorted(keys) != sorted(_RECORD_KEYS):
+            raise ValueError(f"a game line carries the keys {_RECORD_KEYS}: {line!r}")
+        for k in _RECORD_KEYS:
+            rec[k] = int(keys[k])
+        out.append(rec)
+    return np.array(out, dtype=GAME_RECORD_DTYPE).reshape(-1)

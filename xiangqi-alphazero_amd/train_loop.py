@@ -37,7 +37,7 @@ import torch.distributed as dist
 
 from . import arena, distributed as xdist, selfplay, training
 from .model import XiangqiNet
-from .sample_format import RESULT_DTYPE
+from .sample_format import GAME_RECORD_DTYPE, RESULT_DTYPE, records_to_text
 
 
 class AlphaZeroLoop:
@@ -62,6 +62,10 @@ class AlphaZeroLoop:
         # the evaluation mirror (config.eval_random_mirror; absent: off), read once, for self-play ONLY: the arena gate never gets
         # it, so a gate's games stay a function of the two models and the seed
         self.eval_mirror = bool(getattr(config, "eval_random_mirror", False))
+        # game records (config.record_games; absent: off), read once, for self-play and the gate alike; with
+        # config.game_records_dir every iteration's games are written there as text (sample_format.records_to_text), per rank
+        self.record_games = bool(getattr(config, "record_games", False))
+        self.game_records_dir = getattr(config, "game_records_dir", None) if self.record_games else None
         torch.manual_seed(seed)                        # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -87,7 +91,7 @@ class AlphaZeroLoop:
         if n_games <= 0:
             return (torch.empty((0, 640), dtype=torch.uint8, device=self.device),
                     torch.empty((0, 16), dtype=torch.uint8, device=self.device))
-        samples, results, _, _ = selfplay.run_games(self.best_model, self.config, n_games, self.device,
+        samples, results, st, _ = selfplay.run_games(self.best_model, self.config, n_games, self.device,
                                                     seed=self.seed + 1000 * self.iteration, rank=self.rank,
                                                     evaluator_kind=self.evaluator_kind, device_records=True,
                                                     # leaf batching is a self-play option only: the arena stays sequential
@@ -96,10 +100,22 @@ class AlphaZeroLoop:
                                                     # arena (arena.py) never takes it
                                                     forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None,
                                                     perpetual_check=self.perpetual_check, solver=self.solver,
-                                                    root_stats=self.record_root_stats, eval_mirror=self.eval_mirror)
+                                                    root_stats=self.record_root_stats, eval_mirror=self.eval_mirror,
+                                                    record_games=self.record_games)
+        if self.record_games:
+            self._write_records("selfplay", st["game_records"].cpu().numpy().reshape(-1).view(GAME_RECORD_DTYPE))
         # the Gumbel root search (config.gumbel_considered, gumbel_c_visit, gumbel_c_scale; absent or 0: off) reaches the engine
         # through run_games, which reads those keys from the config it is handed; the arena never takes it either
         return samples, results
+
+    def _write_records(self, stage: str, records) -> None:
+        """This rank's game records of one stage of the current iteration, as text, when config.game_records_dir is set."""
+        if not self.game_records_dir:
+            return
+        os.makedirs(self.game_records_dir, exist_ok=True)
+        name = "iter%04d_%s_rank%d.txt" % (self.iteration, stage, self.rank)
+        with open(os.path.join(self.game_records_dir, name), "w") as f:
+            f.write(records_to_text(records))
 
     def self_play(self) -> dict:
         cfg = self.config
@@ -141,13 +157,17 @@ class AlphaZeroLoop:
             # paired random openings (opt-in): another seed every iteration, so successive gates see different openings
             seed = int(getattr(self.config, "arena_seed", 0) or 0) + self.iteration
             return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind,
-                                         seed=seed, perpetual_check=self.perpetual_check, solver=self.solver)
+                                         seed=seed, perpetual_check=self.perpetual_check, solver=self.solver,
+                                         record_games=self.record_games)
         return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind,
-                                     perpetual_check=self.perpetual_check, solver=self.solver)
+                                     perpetual_check=self.perpetual_check, solver=self.solver, record_games=self.record_games)
 
     def evaluate(self) -> dict:
         stats = self._arena()
         stats.pop("games", None)
+        records = stats.pop("game_records", None)
+        if records is not None:
+            self._write_records("arena", records)
         if self.grouped:                               # one verdict for all replicas: rank 0's
             flag = torch.tensor([1 if stats["model_updated"] else 0], dtype=torch.int64,
                                 device=self.device if dist.get_backend() == "nccl" else "cpu")
