@@ -1066,6 +1066,90 @@ int xq_replay_games_batch(const void *dev_records /* xq_game_record[n] */, const
                           int8_t *dev_hist12 /* [n][12][90], oldest first, xq_engine_set_position's layout */,
                           int32_t *dev_status, int8_t *dev_over_kind, int8_t *dev_winner, void *stream);
 
+/* Scoring samples against a network, and policy-surprise weighted training (opt-in; nothing in the engine knows of it, and no
+ * existing entry point, struct or byte changes).  A finished sample is turned back into an evaluation request, a network answers
+ * it, and the answer is compared with the sample's search target: how well does network X predict the samples in buffer Y, and
+ * which samples did the search change the most (KataGo's policy surprise)?  Self-play is played by one deterministic evaluator, so
+ * running an iteration's samples through the same evaluator once reproduces the search's raw, noise-free root prior.
+ * Both kernels run one wavefront per output row j, four rows per workgroup; row j is record dev_index[j] of dev_samples, or record
+ * j itself when dev_index is NULL.  The engine writes n_moves <= XQ_MAXM; a larger byte is read as XQ_MAXM.
+ *
+ * xq_samples_to_requests: compact records -> the three inputs of the evaluator's legal-move protocol (xq_policy_head_legal):
+ *     dev_planes[j]  float32[15][10][9], un-mirrored: the arithmetic of xq_samples_to_batch with flip = 0 (xq_encode_batch's planes)
+ *     dev_moves[j]   uint16[XQ_MAXM]: moves[j][i] = actions[i] for i < n_moves, 0 behind that (all XQ_MAXM words are written)
+ *     dev_counts[j]  int32: n_moves
+ *   About 640 bytes read and 5.7 KB written per row: HBM-bound.  dev_planes must be 8-byte and dev_moves 4-byte aligned.
+ *
+ * xq_score_samples: per row, with m = n_moves, the record's visits c_i, the evaluator's legal-move logits l_i =
+ * dev_legal_logits[j][i] (float32, i < m; entries at and behind m are never read) and T = late_temperature, in float64:
+ *     TARGET  w_i = late_temp ? (c_i > 0 ? pow(c_i, 1 / T) : 0) : c_i;  total = w_0 + w_1 + ... in move order;  t_i = w_i / total
+ *             -- w_i and total exactly as xq_samples_to_batch forms them; a Gumbel record's 16-bit improved policy (late_temp = 0)
+ *             is normalised the same way.
+ *     PRIOR   M = max_j l_j;  logp_i = l_i - M - log(sum_j exp(l_j - M))
+ *     SCORES  policy_ce = -sum_{t_i > 0} t_i * logp_i
+ *             policy_kl = max(0, sum_{t_i > 0} t_i * (log t_i - logp_i))
+ *             value     = dev_value[j]
+ *             top1      = (first index of the largest logit == first index of the largest visit count)
+ *   policy_kl and policy_ce are cast to float32 once.  The sums over the moves are wave reductions: their order is not the move
+ *   order, and they agree with a sequential float64 sum to about 1e-13.
+ *   INVALID rows -- m = 0, total = 0, a total that is not finite (a late record's powers overflow for a small T), or a logit
+ *   among the m that is not finite -- get valid = 0 and zeros in every other field, and nothing is written back.
+ *   write_back = 1 also writes 8 bytes into the RECORD (dev_samples is then written to): xq_sample_policy_stats at byte
+ *   XQ_SAMPLE_POLICY_STATS_OFFSET = 120, inside the 11 zero bytes of xq_sample_root_stats, whose own fields (root_q, root_visits,
+ *   has_root_stats at byte 116) are not touched:
+ *       policy_kl         float32 at 120   the score's policy_kl
+ *       has_policy_stats  uint8   at 124   1
+ *       prior_top1        uint8   at 125   the score's top1
+ *       two zero bytes
+ *   dev_scores may be NULL when write_back = 1.  Rows that name one record write the same bytes.
+ *   XQ_ERR_ARG before any launch: opts NULL, a non-zero reserved word, write_back outside {0, 1}, late_temperature not positive
+ *   and finite, n < 0, and with n > 0 a NULL dev_samples, dev_legal_logits or dev_value, or a NULL dev_scores with write_back = 0.
+ *   n = 0 is a no-op (the options are still checked).
+ *
+ * xq_surprise_counts: how often each of the n_records records of dev_samples is drawn in one epoch, dev_counts int32[n_records].
+ * A record without the mark (has_policy_stats != 1) counts 1.  Over the marked records the normaliser is integer, so that it does
+ * not depend on the order of summation (atomics and any tree give the same):
+ *     q_i = llrint(min(policy_kl_i, 64.0f) * 2^20) as uint64  (a policy_kl that is negative or NaN is taken as 0; the score kernel
+ *           writes neither);  S = sum q_i;  M = the number of marked records
+ *     S = 0: every count is 1.  Otherwise, in float64, uncontracted, in this order:
+ *     w_i = (1 - alpha) + alpha * (((double)q_i * (double)M) / (double)S)
+ *     u_i = (double)(philox_u64(seed, epoch, slot, 10, game_seq, ply) >> 11) * 2^-53
+ *     c_i = floor(w_i) + (u_i < w_i - floor(w_i))
+ *   so the counts of the marked records sum to M in expectation, alpha = 0 is the uniform epoch, and alpha = 1 draws in proportion
+ *   to the KL.  philox_u64(key, rank, slot, kind, ctr, sub) is the engine's Philox4x32-10 (see the evaluation mirror above): the
+ *   epoch takes the rank word, and kind 10 is used by no other draw (0-3, 7, 8 and 9 are taken).  The rounding decision is keyed by
+ *   the record's identity (slot, game_seq, ply), not by its place in the buffer.  There is no cap on w_i beyond the 64 nats.
+ *   dev_scratch: XQ_SURPRISE_SCRATCH_BYTES bytes of device memory, 8-byte aligned, zeroed and used by the call (S and M).
+ *   XQ_ERR_ARG before any launch: opts NULL, alpha outside [0, 1] or NaN, a non-zero reserved word, n_records < 0, and with
+ *   n_records > 0 a NULL pointer or a misaligned dev_scratch.  n_records = 0 is a no-op.
+ * xq_surprise_count_host: c_i of one record on the host, by the device's own code, bit for bit; -1 for alpha outside [0, 1]. */
+typedef struct xq_score_opts { double late_temperature; int32_t write_back; int32_t reserved; } xq_score_opts;
+typedef struct xq_sample_score {
+    float policy_kl, policy_ce, value;
+    uint8_t top1, valid;
+    uint8_t zero[2];
+} xq_sample_score;
+#define XQ_SAMPLE_POLICY_STATS_OFFSET 120
+typedef struct xq_sample_policy_stats {
+    float policy_kl;
+    uint8_t has_policy_stats;
+    uint8_t prior_top1;
+    uint8_t zero[2];
+} xq_sample_policy_stats;
+typedef struct xq_surprise_opts { double alpha; uint64_t seed; uint32_t epoch; uint32_t reserved; } xq_surprise_opts;
+#define XQ_SURPRISE_SCRATCH_BYTES 16
+#define XQ_RNG_KIND_SURPRISE 10
+int xq_samples_to_requests(const void *dev_samples, const int32_t *dev_index /* int32[n] or NULL = 0..n-1 */, int n,
+                           float *dev_planes /* [n][15][90] */, uint16_t *dev_moves /* [n][XQ_MAXM] */,
+                           int32_t *dev_counts /* [n] */, void *stream);
+int xq_score_samples(void *dev_samples, const int32_t *dev_index /* int32[n] or NULL = 0..n-1 */, int n,
+                     const float *dev_legal_logits /* [n][XQ_MAXM] */, const float *dev_value /* [n] */,
+                     const xq_score_opts *opts, xq_sample_score *dev_scores /* [n], or NULL with write_back = 1 */, void *stream);
+int xq_surprise_counts(const void *dev_samples, int n_records, const xq_surprise_opts *opts, int32_t *dev_counts /* [n_records] */,
+                       void *dev_scratch, void *stream);
+int xq_surprise_count_host(float policy_kl, int marked, uint64_t M, uint64_t S, double alpha, uint64_t seed, uint32_t epoch,
+                           uint32_t slot, uint32_t game_seq, uint32_t ply);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("XQ_HIP_LIB", os.path.join(_HERE, "libxq_hip.so"))   # override: perf experiments only
 CSRC = os.path.join(_HERE, "csrc")
 
-from .sample_format import GAME_RECORD_DTYPE  # noqa: E402,F401  (numpy only: the record's layout lives with the other formats)
+# numpy only: the records' layouts live with the other formats
+from .sample_format import GAME_RECORD_DTYPE, POLICY_STATS_DTYPE, SCORE_DTYPE  # noqa: E402,F401
 
 MAXM = 128
 SAMPLE_BYTES = 640
@@ -162,6 +163,35 @@ assert GAME_RECORD_DTYPE.itemsize == RECORD_BYTES == C.sizeof(GameRecord)
 class BatchOpts(C.Structure):
     """xq_batch_opts: the q-mixed value target of xq_samples_to_batch_ex: q_mix in [0, 1]."""
     _fields_ = [("q_mix", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+class ScoreOpts(C.Structure):
+    """xq_score_opts: scoring samples against a network (xq_score_samples): the samples' late temperature, write_back 0 / 1."""
+    _fields_ = [("late_temperature", C.c_double), ("write_back", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SampleScore(C.Structure):
+    """xq_sample_score: one sample against one network: KL and cross-entropy of the search target against the raw prior, the
+    network's value, whether the prior's first choice is the search's, and whether the row could be scored at all."""
+    _fields_ = [("policy_kl", C.c_float), ("policy_ce", C.c_float), ("value", C.c_float), ("top1", C.c_uint8),
+                ("valid", C.c_uint8), ("zero", C.c_uint8 * 2)]
+
+
+class SamplePolicyStats(C.Structure):
+    """xq_sample_policy_stats: what xq_score_samples writes back into a record, at byte POLICY_STATS_OFFSET."""
+    _fields_ = [("policy_kl", C.c_float), ("has_policy_stats", C.c_uint8), ("prior_top1", C.c_uint8), ("zero", C.c_uint8 * 2)]
+
+
+class SurpriseOpts(C.Structure):
+    """xq_surprise_opts: the epoch counts of policy-surprise weighted training (xq_surprise_counts): alpha in [0, 1]."""
+    _fields_ = [("alpha", C.c_double), ("seed", C.c_uint64), ("epoch", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SCORE_BYTES = 16                 # sizeof(xq_sample_score)
+POLICY_STATS_OFFSET = 120        # XQ_SAMPLE_POLICY_STATS_OFFSET
+SURPRISE_SCRATCH_BYTES = 16      # XQ_SURPRISE_SCRATCH_BYTES
+RNG_KIND_SURPRISE = 10           # XQ_RNG_KIND_SURPRISE
+assert C.sizeof(SampleScore) == SCORE_BYTES == SCORE_DTYPE.itemsize and C.sizeof(SamplePolicyStats) == POLICY_STATS_DTYPE.itemsize
 
 
 class SolverStats(C.Structure):
@@ -336,6 +366,11 @@ def lib():
     L.xq_evcache_invalidate.argtypes = [C.POINTER(EvCache), vp]
     L.xq_evcache_stats_read.argtypes = [C.POINTER(EvCache), C.POINTER(EvCacheStats), vp]
     L.xq_evcache_key_host.argtypes = [vp, vp]
+    L.xq_samples_to_requests.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.xq_score_samples.argtypes = [vp, vp, i32, vp, vp, C.POINTER(ScoreOpts), vp, vp]
+    L.xq_surprise_counts.argtypes = [vp, i32, C.POINTER(SurpriseOpts), vp, vp, vp]
+    L.xq_surprise_count_host.argtypes = [C.c_float, i32, C.c_uint64, C.c_uint64, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_uint32]
     _lib = L
     return L
 
@@ -363,7 +398,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_workspace_bytes_rs", "xq_engine_init_rs", "xq_samples_to_batch_ex",
            "xq_engine_workspace_bytes_em", "xq_engine_init_em", "xq_eval_mirror_bit_host", "xq_mirror_action_host",
            "xq_mirror_requests_batch", "xq_engine_workspace_bytes_gr", "xq_engine_init_gr", "xq_engine_drain_games",
-           "xq_engine_drain_games_device", "xq_engine_game_records_stats_read", "xq_replay_games_batch"]
+           "xq_engine_drain_games_device", "xq_engine_game_records_stats_read", "xq_replay_games_batch",
+           "xq_samples_to_requests", "xq_score_samples", "xq_surprise_counts", "xq_surprise_count_host"]
 
 
 def check(rc: int, what: str):
@@ -485,6 +521,84 @@ def replay_games(records: torch.Tensor, stop_ply=None, perpetual_check: bool = F
                                           _dev(out["hist12"]), _dev(out["status"]), _dev(out["over_kind"]), _dev(out["winner"]),
                                           stream_ptr(dev)), "xq_replay_games_batch")
     return out
+
+
+def _records_arg(samples: torch.Tensor, what: str):
+    if samples.dtype != torch.uint8 or samples.dim() != 2 or samples.shape[1] != SAMPLE_BYTES:
+        raise XqError(f"{what}: samples must be uint8[n, {SAMPLE_BYTES}], got {samples.dtype} {tuple(samples.shape)}")
+    return _dev(samples)
+
+
+def _index_arg(index, device, what: str):
+    if index is None:
+        return None
+    if index.dtype != torch.int32 or index.dim() != 1 or index.device != device:
+        raise XqError(f"{what}: index must be int32[n] on the samples' device")
+    return _dev(index)
+
+
+def samples_to_requests(samples: torch.Tensor, index=None, out=None):
+    """Compact records as evaluation requests (xq_samples_to_requests): samples uint8[r, 640] on the GPU, index int32[n] there or
+    None (the records in order) -> (planes float32[n,15,10,9], moves int16[n,128] holding uint16 action ids, counts int32[n]),
+    the three arguments of an evaluator's `evaluate_legal`.  `out` = such a triple, preallocated."""
+    p_s = _records_arg(samples, "samples_to_requests")
+    dev = samples.device
+    p_i = _index_arg(index, dev, "samples_to_requests")
+    n = samples.shape[0] if index is None else index.shape[0]
+    if out is None:
+        out = (torch.empty((n, 15, 10, 9), dtype=torch.float32, device=dev), torch.empty((n, MAXM), dtype=torch.int16, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev))
+    x, moves, counts = out
+    if x.shape != (n, 15, 10, 9) or x.dtype != torch.float32 or moves.shape != (n, MAXM) or moves.element_size() != 2 \
+            or counts.shape != (n,) or counts.dtype != torch.int32:
+        raise XqError("samples_to_requests: out = (float32[n,15,10,9], 16-bit [n,128], int32[n]) required")
+    if n:
+        check(lib().xq_samples_to_requests(p_s, p_i, n, _dev(x), _dev(moves), _dev(counts), stream_ptr(dev)), "xq_samples_to_requests")
+    return x, moves, counts
+
+
+def score_samples(samples: torch.Tensor, index, legal_logits: torch.Tensor, value: torch.Tensor, late_temperature: float = 0.3,
+                  write_back: bool = False, out=None) -> torch.Tensor:
+    """Samples against a network's answers (xq_score_samples): legal_logits float32[n,128] and value float32[n] as an evaluator's
+    `evaluate_legal` returns them for the requests of `samples_to_requests(samples, index)` -> scores uint8[n, 16]
+    (sample_format.SCORE_DTYPE).  `write_back` also marks the records themselves (sample_format.policy_stats)."""
+    p_s = _records_arg(samples, "score_samples")
+    dev = samples.device
+    p_i = _index_arg(index, dev, "score_samples")
+    n = samples.shape[0] if index is None else index.shape[0]
+    if legal_logits.shape != (n, MAXM) or legal_logits.dtype != torch.float32 or value.shape != (n,) or value.dtype != torch.float32:
+        raise XqError(f"score_samples: legal_logits float32[{n},{MAXM}] and value float32[{n}] required")
+    if out is None:
+        out = torch.zeros((n, SCORE_BYTES), dtype=torch.uint8, device=dev)
+    elif out.shape != (n, SCORE_BYTES) or out.dtype != torch.uint8:
+        raise XqError(f"score_samples: out uint8[{n},{SCORE_BYTES}] required")
+    opts = ScoreOpts(float(late_temperature), 1 if write_back else 0, 0)
+    check(lib().xq_score_samples(p_s, p_i, n, _dev(legal_logits) if n else None, _dev(value) if n else None, C.byref(opts),
+                                 _dev(out) if n else None, stream_ptr(dev)), "xq_score_samples")
+    return out
+
+
+def surprise_counts(samples: torch.Tensor, alpha: float, seed: int, epoch: int) -> torch.Tensor:
+    """How often each record is drawn in one epoch of policy-surprise weighted training (xq_surprise_counts): samples
+    uint8[n, 640] on the GPU -> int32[n]; sample_format.surprise_counts is the numpy reference."""
+    p_s = _records_arg(samples, "surprise_counts")
+    n, dev = samples.shape[0], samples.device
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    scratch = torch.empty(SURPRISE_SCRATCH_BYTES // 8, dtype=torch.int64, device=dev)
+    opts = SurpriseOpts(float(alpha), int(seed) & (2 ** 64 - 1), int(epoch) & 0xFFFFFFFF, 0)
+    check(lib().xq_surprise_counts(p_s if n else None, n, C.byref(opts), _dev(counts) if n else None, _dev(scratch),
+                                   stream_ptr(dev)), "xq_surprise_counts")
+    return counts
+
+
+def surprise_count_host(policy_kl: float, marked, M: int, S: int, alpha: float, seed: int, epoch: int, slot: int, game_seq: int,
+                        ply: int) -> int:
+    """One record's epoch count by the device's own code on the host (xq_surprise_count_host; needs no GPU)."""
+    c = lib().xq_surprise_count_host(float(policy_kl), 1 if marked else 0, int(M), int(S), float(alpha), int(seed) & (2 ** 64 - 1),
+                                     int(epoch) & 0xFFFFFFFF, int(slot), int(game_seq), int(ply))
+    if c < 0:
+        raise XqError(f"xq_surprise_count_host failed: code {c} (alpha must be in [0, 1], got {alpha})")
+    return c
 
 
 def eval_mirror_bit(seed: int, rank: int, slot: int, game_seq: int, ply: int, is_root, sims_done: int, row: int = 0) -> int:

@@ -32,6 +32,22 @@ assert GAME_RECORD_DTYPE.itemsize == 1024 and GAME_RECORD_DTYPE.fields["moves"][
 ROOT_STATS_DTYPE = np.dtype([("root_q", np.float32), ("root_visits", np.uint32), ("has_root_stats", np.uint8),
                              ("zero", np.uint8, 11)])
 assert ROOT_STATS_DTYPE.itemsize == SAMPLE_DTYPE["pad"].itemsize == 20 and SAMPLE_DTYPE.fields["pad"][1] == 108
+# xq_sample_policy_stats: what xq_score_samples(write_back = 1) writes into bytes 120..127 of a record, inside the zero bytes of
+# ROOT_STATS_DTYPE; xq_sample_score: one row of its output
+POLICY_STATS_OFFSET = 120
+POLICY_STATS_DTYPE = np.dtype([("policy_kl", np.float32), ("has_policy_stats", np.uint8), ("prior_top1", np.uint8),
+                               ("zero", np.uint8, 2)])
+SCORE_DTYPE = np.dtype([("policy_kl", np.float32), ("policy_ce", np.float32), ("value", np.float32), ("top1", np.uint8),
+                        ("valid", np.uint8), ("zero", np.uint8, 2)])
+# the float64 reference of a score row (sample_scores): the entropy of the target rides along, ce - kl
+SCORE_REF_DTYPE = np.dtype([("policy_kl", np.float64), ("policy_ce", np.float64), ("entropy", np.float64), ("value", np.float32),
+                            ("top1", np.uint8), ("valid", np.uint8)])
+assert POLICY_STATS_DTYPE.itemsize == 8 and SCORE_DTYPE.itemsize == 16
+assert SAMPLE_DTYPE.fields["pad"][1] + ROOT_STATS_DTYPE.fields["zero"][1] <= POLICY_STATS_OFFSET \
+    and POLICY_STATS_OFFSET + POLICY_STATS_DTYPE.itemsize <= SAMPLE_DTYPE.fields["pad"][1] + ROOT_STATS_DTYPE.itemsize
+SURPRISE_KL_CAP = 64.0            # nats: the only cap on a sample's weight
+SURPRISE_Q_SCALE = float(2 ** 20)
+RNG_KIND_SURPRISE = 10            # XQ_RNG_KIND_SURPRISE: the Philox stream kind of the epoch counts' rounding draws
 
 
 def root_stats(samples: np.ndarray) -> np.ndarray:
@@ -54,6 +70,103 @@ def mixed_z(samples: np.ndarray, q_mix: float) -> np.ndarray:
     a = (1.0 - q_mix) * z
     b = q_mix * rs["root_q"].astype(np.float64)
     return np.where(rs["has_root_stats"] == 1, a + b, z).astype(np.float32)
+
+
+def policy_stats(samples: np.ndarray) -> np.ndarray:
+    """Bytes 120..127 of the samples as POLICY_STATS_DTYPE records, one per sample (a copy): policy_kl, the mark
+    has_policy_stats (1 where xq_score_samples wrote the record back) and prior_top1."""
+    samples = np.asarray(samples)
+    raw = np.ascontiguousarray(samples).view(np.uint8).reshape(samples.shape + (SAMPLE_DTYPE.itemsize,))
+    ps = np.ascontiguousarray(raw[..., POLICY_STATS_OFFSET:POLICY_STATS_OFFSET + POLICY_STATS_DTYPE.itemsize])
+    return ps.view(POLICY_STATS_DTYPE).reshape(samples.shape)
+
+
+def sample_scores(samples: np.ndarray, legal_logits: np.ndarray, value: np.ndarray, late_temperature: float = 0.3) -> np.ndarray:
+    """The float64 reference of xq_score_samples, SCORE_REF_DTYPE per sample: legal_logits[j][:n_moves] are a network's logits of
+    the sample's moves, value[j] its value.  Target t = w / sum w with w = visits^(1/T) for late_temp records and the plain visits
+    otherwise; logp = log_softmax of the n_moves logits; ce = -sum t logp, kl = max(0, sum t (log t - logp)) over t > 0,
+    entropy = -sum t log t; top1 = the first largest logit is the first largest visit count.  A sample without moves, without
+    visits, with a total that is not finite or with a logit among its moves that is not finite is invalid: valid = 0 and zeros."""
+    samples = np.asarray(samples).reshape(-1)
+    legal_logits, value = np.asarray(legal_logits), np.asarray(value)
+    out = np.zeros(len(samples), dtype=SCORE_REF_DTYPE)
+    for j, s in enumerate(samples):
+        m = min(int(s["n_moves"]), 128)
+        c = s["visits"][:m].astype(np.float64)
+        lg = legal_logits[j][:m].astype(np.float64)
+        if s["late_temp"]:
+            with np.errstate(over="ignore"):            # a small T overflows the powers: the total is then not finite
+                w = np.where(c > 0.0, c ** (1.0 / float(late_temperature)), 0.0)
+        else:
+            w = c
+        total = 0.0
+        for x in w:                                     # the kernels' sequential sum in move order
+            total += float(x)
+        if m == 0 or not total > 0.0 or not np.isfinite(total) or not np.isfinite(lg).all():
+            continue
+        t = w / total
+        mx = lg.max()
+        logp = lg - mx - np.log(np.exp(lg - mx).sum())
+        nz = t > 0.0
+        ent = float(-(t[nz] * np.log(t[nz])).sum())
+        out[j] = (max(0.0, float((t[nz] * (np.log(t[nz]) - logp[nz])).sum())), float(-(t[nz] * logp[nz]).sum()), ent,
+                  np.float32(value[j]), int(np.argmax(lg)) == int(np.argmax(s["visits"][:m])), 1)
+    return out
+
+
+def _philox_u64(seed: int, rank, slot, kind: int, ctr, sub) -> np.ndarray:
+    """The engine's Philox4x32-10 (philox_u64 of csrc/xq_engine_state.cuh) over arrays: key = the two halves of `seed`, counter
+    words (slot, kind | sub << 8, ctr, rank); output word 0 in the high half, word 1 in the low half."""
+    m32 = np.uint64(0xFFFFFFFF)
+    slot, ctr, sub = (np.asarray(a).astype(np.uint64) for a in (slot, ctr, sub))
+    c0, c2 = slot & m32, ctr & m32
+    c1 = (np.uint64(kind) | (sub << np.uint64(8))) & m32
+    c3 = np.full_like(c0, np.uint64(int(rank) & 0xFFFFFFFF))
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0)) & m32, p1 & m32, \
+            ((p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1)) & m32, p0 & m32
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return (c0 << np.uint64(32)) | c1
+
+
+def surprise_q(policy_kl: np.ndarray) -> np.ndarray:
+    """q of xq_surprise_counts, uint64: the KL capped at 64 nats in units of 2^-20 nat, rounded to nearest even; a KL that is
+    negative or NaN counts 0."""
+    kl = np.asarray(policy_kl, dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        x = np.where(kl >= 0, np.minimum(kl, np.float32(SURPRISE_KL_CAP)), np.float32(0.0)).astype(np.float32)
+    return np.rint(x.astype(np.float64) * SURPRISE_Q_SCALE).astype(np.uint64)
+
+
+def surprise_weights(samples: np.ndarray, alpha: float):
+    """-> (w float64 per record, marked bool per record, M, S) of xq_surprise_counts: w = (1 - alpha) + alpha q M / S over the
+    marked records, 1.0 for an unmarked one and for all of them when S = 0."""
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must be in [0, 1], got {alpha}")
+    ps = policy_stats(np.asarray(samples).reshape(-1))
+    marked = ps["has_policy_stats"] == 1
+    q = np.where(marked, surprise_q(ps["policy_kl"]), np.uint64(0)).astype(np.uint64)
+    M, S = int(marked.sum()), int(sum(int(x) for x in q))
+    w = np.ones(len(ps), dtype=np.float64)
+    if S > 0:
+        ratio = (q.astype(np.float64) * float(M)) / float(S)
+        w = np.where(marked, (1.0 - alpha) + alpha * ratio, 1.0)
+    return w, marked, M, S
+
+
+def surprise_counts(samples: np.ndarray, alpha: float, seed: int, epoch: int) -> np.ndarray:
+    """The numpy reference of xq_surprise_counts, int32 per record: c = floor(w) + (u < w - floor(w)) with `surprise_weights`' w
+    and u = (philox_u64(seed, epoch, slot, 10, game_seq, ply) >> 11) * 2^-53 -- a draw keyed by the record's identity, so a record
+    keeps its rounding decision wherever it lies in a buffer.  It repeats the host twin xq_surprise_count_host."""
+    samples = np.asarray(samples).reshape(-1)
+    w, _, _, _ = surprise_weights(samples, alpha)
+    r = _philox_u64(seed, int(epoch), samples["slot"], RNG_KIND_SURPRISE, samples["game_seq"], samples["ply"])
+    u = (r >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    fl = np.floor(w)
+    return (fl + (u < w - fl)).astype(np.int32)
 
 
 def encode_planes(board: np.ndarray, side: int) -> np.ndarray:

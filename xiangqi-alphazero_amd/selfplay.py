@@ -34,6 +34,64 @@ def root_stats_q_mix(config) -> float:
     return q_mix
 
 
+def policy_surprise_weight(config) -> float:
+    """`config.policy_surprise_weight` (a reference TrainingConfig has no such key: 0; None is the absent key), checked: alpha of
+    the policy-surprise weighted epochs (training.train_network).  Above 0 it turns the scoring of the self-play samples on."""
+    alpha = float(getattr(config, "policy_surprise_weight", 0.0) or 0.0)
+    if not 0.0 <= alpha <= 1.0:
+        raise hip.XqError(f"config.policy_surprise_weight must be in [0, 1], got {alpha}")
+    return alpha
+
+
+def score_samples(evaluator, samples_dev, late_temperature: float = 0.3, write_back: bool = True, chunk: int = 2048):
+    """Score finished samples against a network: samples_dev uint8[n, 640] on the GPU (`SelfPlayEngine.drain_device`, a replay
+    buffer's store) go through the evaluator once, `chunk` records at a time -- `hip.samples_to_requests`, the evaluator's
+    `evaluate_legal`, `hip.score_samples` -- and come back as scores uint8[n, 16] on the device (sample_format.SCORE_DTYPE: KL and
+    cross-entropy of the search target against the network's raw prior over the legal moves, the network's value, top-1
+    agreement, valid).  `write_back` also marks the records in place (sample_format.policy_stats), which is what the
+    policy-surprise weighted epochs of `training.train_network` read.  The evaluator that played the games reproduces the
+    search's noise-free root prior; any other network answers "how well does it predict these samples".  `evaluate_legal`
+    returns views of buffers it reuses: every chunk is consumed, on the evaluator's stream, before the next is issued.  An
+    evaluator without `evaluate_legal` (the library comparison kinds) is refused."""
+    import torch
+    if not hasattr(evaluator, "evaluate_legal"):
+        raise hip.XqError("score_samples needs an evaluator with evaluate_legal (kinds 'hip' and 'bf16'), got %s" % type(evaluator).__name__)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise hip.XqError(f"score_samples: chunk must be at least 1, got {chunk}")
+    n, dev = samples_dev.shape[0], samples_dev.device
+    scores = torch.zeros((n, hip.SCORE_BYTES), dtype=torch.uint8, device=dev)
+    if n == 0:
+        return scores
+    width = min(chunk, n)
+    x = torch.empty((width, 15, 10, 9), dtype=torch.float32, device=dev)
+    moves = torch.empty((width, hip.MAXM), dtype=torch.int16, device=dev)
+    counts = torch.empty(width, dtype=torch.int32, device=dev)
+    for lo in range(0, n, width):
+        b = min(width, n - lo)
+        rows = samples_dev[lo:lo + b]
+        hip.samples_to_requests(rows, None, out=(x[:b], moves[:b], counts[:b]))
+        ll, v = evaluator.evaluate_legal(x[:b], moves[:b], counts[:b])
+        hip.score_samples(rows, None, ll[:b], v[:b], late_temperature, write_back, out=scores[lo:lo + b])
+    return scores
+
+
+def score_summary(scores_dev, samples_dev) -> Dict[str, float]:
+    """Means over the valid rows of `score_samples`' output: mean_policy_kl, mean_policy_ce, prior_top1_rate, and value_mse_vs_z,
+    the network's value against the game's result of the same records (byte 91: z).  One host read."""
+    import torch
+    if scores_dev.shape[0] == 0:
+        return {"mean_policy_kl": 0.0, "mean_policy_ce": 0.0, "prior_top1_rate": 0.0, "value_mse_vs_z": 0.0, "scored_samples": 0}
+    f = scores_dev[:, :12].contiguous().view(torch.float32).double()          # policy_kl, policy_ce, value
+    valid = (scores_dev[:, 13] == 1).double()
+    z = samples_dev[:, 91].view(torch.int8).double()
+    k = valid.sum().clamp(min=1.0)
+    out = torch.stack([(f[:, 0] * valid).sum() / k, (f[:, 1] * valid).sum() / k, (scores_dev[:, 12].double() * valid).sum() / k,
+                       (((f[:, 2] - z) ** 2) * valid).sum() / k, valid.sum()]).tolist()
+    return {"mean_policy_kl": out[0], "mean_policy_ce": out[1], "prior_top1_rate": out[2], "value_mse_vs_z": out[3],
+            "scored_samples": int(out[4])}
+
+
 def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[int] = None, seed: int = 0, rank: int = 0,
               evaluator_kind: str = "hip", poll_every: int = 64, device_records: bool = False, use_graph: bool = True,
               eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None,

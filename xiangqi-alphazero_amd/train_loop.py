@@ -66,6 +66,13 @@ class AlphaZeroLoop:
         # config.game_records_dir every iteration's games are written there as text (sample_format.records_to_text), per rank
         self.record_games = bool(getattr(config, "record_games", False))
         self.game_records_dir = getattr(config, "game_records_dir", None) if self.record_games else None
+        # policy-surprise weighting (config.policy_surprise_weight = alpha, absent: 0) and the scoring pass on its own
+        # (config.score_samples; absent: off), read once and checked here: either one has every shard of self-play scored against
+        # the network that played it, before the all-gather, so the marks travel inside the records
+        self.surprise_weight = selfplay.policy_surprise_weight(config)
+        self.score_samples = bool(getattr(config, "score_samples", False)) or self.surprise_weight > 0.0
+        self._shard_scores = None
+        self._score_ev = None
         torch.manual_seed(seed)                        # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -106,7 +113,20 @@ class AlphaZeroLoop:
             self._write_records("selfplay", st["game_records"].cpu().numpy().reshape(-1).view(GAME_RECORD_DTYPE))
         # the Gumbel root search (config.gumbel_considered, gumbel_c_visit, gumbel_c_scale; absent or 0: off) reaches the engine
         # through run_games, which reads those keys from the config it is handed; the arena never takes it either
+        if self.score_samples:
+            self._shard_scores = selfplay.score_samples(self._scoring_evaluator(), samples, self.buffer.late_temperature,
+                                                        write_back=True)     # the target the batch kernel trains on
         return samples, results
+
+    def _scoring_evaluator(self):
+        """The evaluator of `best_model` that scores the shards: built once and kept (its activation and logits buffers with it);
+        every iteration refreshes its weights in place, which is one more filter transform per iteration beside run_games' own."""
+        if self._score_ev is None:
+            from . import evaluator
+            self._score_ev = evaluator.make_evaluator(self.best_model, self.device, self.evaluator_kind)[0]
+        else:
+            self._score_ev.update(self.best_model)
+        return self._score_ev
 
     def _write_records(self, stage: str, records) -> None:
         """This rank's game records of one stage of the current iteration, as text, when config.game_records_dir is set."""
@@ -120,19 +140,30 @@ class AlphaZeroLoop:
     def self_play(self) -> dict:
         cfg = self.config
         t0 = time.time()
+        self._shard_scores = None
         samples, results = self._play_shard(xdist.shard_games(cfg.num_games_per_iter, self.world, self.rank))
+        scores = None
+        if self.score_samples:
+            # one score row per sample of this shard; a shard without games (or a _play_shard that does not score) has none, and
+            # still takes part in the gather below: every rank runs the same collectives
+            scores = self._shard_scores
+            if scores is None or scores.shape[0] != samples.shape[0]:
+                scores = torch.zeros((int(samples.shape[0]), 16), dtype=torch.uint8, device=samples.device)
         if self.grouped:
             samples = xdist.all_gather_records_device(samples)
             results = xdist.all_gather_records_device(results)
+            if scores is not None:
+                scores = xdist.all_gather_records_device(scores)
         self.buffer.extend(samples)
         res = results.cpu().numpy().reshape(-1).view(RESULT_DTYPE) if len(results) else np.zeros(0, RESULT_DTYPE)
         self.total_games += len(res)
         wins = {1: 0, -1: 0, 0: 0}
         for r in res:
             wins[int(r["winner"])] += 1
+        scored = selfplay.score_summary(scores, samples) if scores is not None else {}
         return {"games": len(res), "red_wins": wins[1], "black_wins": wins[-1], "draws": wins[0],
                 "avg_steps": float(res["steps"].mean()) if len(res) else 0.0, "new_samples": 2 * int(samples.shape[0]),
-                "total_time": time.time() - t0, "num_workers": self.world, "mode": "hip", "buffer_size": len(self.buffer)}
+                "total_time": time.time() - t0, "num_workers": self.world, "mode": "hip", "buffer_size": len(self.buffer), **scored}
 
     def train_network(self) -> dict:
         """World 1: the reference's step.  World > 1: the same full-batch update computed data-parallel -- every rank
@@ -147,7 +178,7 @@ class AlphaZeroLoop:
         if ddp or self.rank == 0:
             stats = training.train_network(self.current_model, self.optimizer, self.scheduler, self.buffer, self.config,
                                            generator=gen, ddp=ddp, native_bn=bool(getattr(self.config, "native_sync_bn", False)),
-                                           q_mix=self.q_mix)
+                                           q_mix=self.q_mix, surprise_weight=self.surprise_weight)
         if self.grouped:
             xdist.broadcast_weights(self.current_model, src=0, device=self.device)
         return stats

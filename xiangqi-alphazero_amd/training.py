@@ -73,6 +73,28 @@ class ReplayBuffer:
         mark = self.store[:self.count, 116] == 1
         return float(mark.sum().item()) / float(self.count)
 
+    def policy_stats_coverage(self) -> float:
+        """The share of the held records that carry policy statistics (has_policy_stats, byte 124 of a record:
+        `selfplay.score_samples(write_back=True)` wrote it); 0.0 for an empty buffer."""
+        if self.count == 0:
+            return 0.0
+        mark = self.store[:self.count, 124] == 1
+        return float(mark.sum().item()) / float(self.count)
+
+    def epoch_order(self, alpha: float, seed: int, epoch: int, generator=None, shuffle: bool = True) -> torch.Tensor:
+        """The logical indices of one policy-surprise weighted epoch (int64, on the host): record r of the live records, oldest
+        first, is drawn c_r times (xq_surprise_counts over the live records: uniform for alpha = 0, in proportion to the KL of the
+        search target against the raw prior for alpha = 1), so logical samples 2r and 2r + 1 -- the position and its mirror --
+        are each repeated c_r times; the list is then permuted by `torch.randperm(len, generator=generator)`."""
+        if self.count == 0:
+            return torch.zeros(0, dtype=torch.int64)
+        # a ring that has not wrapped holds its records at [0, count); a wrapped one is full: the live records, in ring order
+        counts = hip.surprise_counts(self.store[:self.count], alpha, seed, epoch)
+        oldest = (self.head - self.count) % self.cap
+        counts = torch.roll(counts, -oldest, 0).to("cpu", torch.int64)        # oldest first
+        order = torch.repeat_interleave(torch.arange(2 * self.count), torch.repeat_interleave(counts, 2))
+        return order[torch.randperm(order.numel(), generator=generator)] if shuffle else order
+
     def batch(self, logical: torch.Tensor, q_mix: float = 0.0):
         """-> states f32[B,15,10,9], pi f32[B,8100], z f32[B,1] for the given logical indices (device int64).  q_mix > 0: z is
         the q-mixed value target of xq_samples_to_batch_ex for the records that carry root statistics."""
@@ -132,7 +154,8 @@ def revert_sync_batchnorm(model) -> None:
 
 def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shuffle: bool = True,
                   generator: Optional[torch.Generator] = None, ddp: bool = False, group=None,
-                  native_bn: bool = False, q_mix: Optional[float] = None) -> Dict[str, float]:
+                  native_bn: bool = False, q_mix: Optional[float] = None,
+                  surprise_weight: Optional[float] = None) -> Dict[str, float]:
     """One call of the reference's train_network (train.py:376-447) on the device-resident buffer.
 
     `ddp=True` under an initialised torch.distributed group (every rank holds the same buffer and the same weights, as
@@ -147,7 +170,15 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     `q_mix` (default: the config's `value_target_q_mix`, 0 when it has none): the value head regresses on
     (1 - q_mix) z + q_mix root_q for the samples that carry root statistics (`ReplayBuffer.batch`), on both paths.  With
     q_mix > 0 a buffer without a single such sample is refused: the option would silently do nothing.  With q_mix = 0 the
-    step is unchanged; the stats gain "value_target_q_mix"."""
+    step is unchanged; the stats gain "value_target_q_mix".
+
+    `surprise_weight` (default: the config's `policy_surprise_weight`; None, absent and 0 mean off) = alpha in [0, 1]: every epoch
+    draws record r c_r times instead of once (`ReplayBuffer.epoch_order`), the counts growing with the KL of the record's
+    search target against the network's raw prior that `selfplay.score_samples` wrote into it (KataGo's policy-surprise
+    weighting); an epoch then has about as many samples as before, in expectation.  The seed of the counts' rounding draws is
+    one `torch.randint` draw from `generator` per call -- equal on every rank, so the data-parallel path needs nothing else.  With
+    alpha > 0 a buffer without a single scored record is refused.  Off, the epoch loop is unchanged.  The stats gain
+    "policy_surprise_weight", "policy_stats_coverage" (None when off: not measured) and "epoch_samples" (per epoch)."""
     if len(buffer) < config.min_buffer_size:
         return {}
     if q_mix is None:                                  # self-play's reader of the key: None, the range, the Gumbel refusal
@@ -158,6 +189,17 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     if q_mix > 0.0 and buffer.root_stats_coverage() == 0.0:
         raise hip.XqError("value_target_q_mix > 0 but no sample in the replay buffer carries root statistics: "
                           "record them in self-play (record_root_stats / SelfPlayEngine(root_stats=True))")
+    if surprise_weight is None:
+        surprise_weight = selfplay.policy_surprise_weight(config)
+    alpha = float(surprise_weight or 0.0)
+    if not 0.0 <= alpha <= 1.0:
+        raise hip.XqError(f"policy_surprise_weight must be in [0, 1], got {alpha}")
+    coverage = None
+    if alpha > 0.0:
+        coverage = buffer.policy_stats_coverage()
+        if coverage == 0.0:
+            raise hip.XqError("policy_surprise_weight > 0 but no sample in the replay buffer carries policy statistics: "
+                              "score the samples in self-play (score_samples / selfplay.score_samples(write_back=True))")
     import torch.distributed as dist
     use_ddp = bool(ddp and dist.is_initialized())
     world = dist.get_world_size(group) if use_ddp else 1
@@ -178,8 +220,16 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     # Python floats, train.py:421-423) and read once at the end: no host synchronisation inside the epoch loop
     totals = None                                                      # float64[2] on the losses' device
     batches = 0
-    for _ in range(config.num_epochs):
-        order = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
+    epoch_samples = []
+    if alpha > 0.0:                                                    # one draw per call keys every epoch's rounding decisions
+        surprise_seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator).item())
+    for epoch in range(config.num_epochs):
+        if alpha > 0.0:
+            order = buffer.epoch_order(alpha, surprise_seed, epoch, generator, shuffle)
+            n = order.numel()
+        else:
+            order = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
+        epoch_samples.append(int(n))
         for lo in range(0, n, config.batch_size):                     # drop_last=False
             idx = order[lo:lo + config.batch_size]
             full = idx.numel()
@@ -211,7 +261,8 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     total_p, total_v = totals.tolist() if totals is not None else (0.0, 0.0)
     return {"policy_loss": total_p / max(batches, 1), "value_loss": total_v / max(batches, 1),
             "total_loss": (total_p + total_v) / max(batches, 1), "learning_rate": optimizer.param_groups[0]["lr"],
-            "value_target_q_mix": q_mix}
+            "value_target_q_mix": q_mix, "policy_surprise_weight": alpha, "policy_stats_coverage": coverage,
+            "epoch_samples": epoch_samples}
 
 
 def save_checkpoint(checkpoint_dir: str, iteration: int, current_model, best_model, optimizer, scheduler, total_games: int,
