@@ -1150,6 +1150,72 @@ int xq_surprise_counts(const void *dev_samples, int n_records, const xq_surprise
 int xq_surprise_count_host(float policy_kl, int marked, uint64_t M, uint64_t S, double alpha, uint64_t seed, uint32_t epoch,
                            uint32_t slot, uint32_t game_seq, uint32_t ply);
 
+/* Merging the records of one position into one training sample (opt-in; nothing in the engine knows of it, no record is
+ * rewritten, and no existing entry point, struct or byte changes).  The network's input is the board and the side to move, so two
+ * records with the same board and side are one training input; a buffer of self-play games holds the opening positions many
+ * times over, with contradictory z.  The merged form lives in index arrays only: keys per record (xq_position_keys), a stable
+ * sort by key (the caller's), group heads in the sorted order (xq_position_group_heads), and a batch kernel that reads groups of
+ * records instead of records (xq_groups_to_batch).
+ *
+ * MIRROR      mir(sq) = (sq / 9) * 9 + 8 - sq % 9; on an action both squares are mirrored (xq_samples_to_batch's arithmetic).
+ * CANONICAL ORIENTATION, with flag XQ_POSITION_KEY_MIRROR (= 1): let sq* be the smallest square with board[sq*] != board[mir(sq*)].
+ *             No such square (the board is its own mirror image): mirrored = 0 and the canonical board c = board.  Otherwise
+ *             mirrored = (board[mir(sq*)] < board[sq*]), compared as int8, and c[sq] = board[mir(sq)] when mirrored is set,
+ *             c = board otherwise.  Without the flag mirrored = 0 and c = board.  A position and its mirror image share one c.
+ * KEY         all arithmetic uint64 with wrap-around:
+ *             mix(x):      x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *             term(i, b) = mix(0x9E3779B97F4A7C15 * (uint64)(i * 256 + (uint8)b + 1))
+ *             key        = XOR over sq < 90 of term(sq, c[sq]), then ^ term(90, side)
+ *             XOR is order-free: the wave reduction, the host twin and a numpy loop agree bit for bit.
+ * GROUPS      rows are taken in the caller's order (oldest first), sorted STABLY by key; order[j] is the row at sorted place j.
+ *             Row order[j] starts a group iff j == 0, or its key, its side or its canonical board (90 bytes) differs from that
+ *             of row order[j-1].  The full compare makes a wrong merge impossible; two positions with one key can at worst split
+ *             a group (A, B, A gives three groups).  Members of a group are in the caller's order.
+ * MERGED SAMPLE of group g with members k = 0 .. n-1 (record indices members[offsets[g] + k]), output flip f and member
+ *             orientation o_k = member_mirrored_k XOR f:
+ *             planes  those of member 0 under o_0 (xq_samples_to_batch's planes with flip = o_0)
+ *             t_k[a]  exactly what xq_samples_to_batch writes into pi for member k with flip = o_k, in float64 before its cast
+ *                     (w_i / total_k at the member's actions, 0 elsewhere); total_k its sequential sum in move order; member k
+ *                     is VALID iff total_k > 0; n_pi = the number of valid members
+ *             pi[a] = (float)((0.0 + t_0[a] + t_1[a] + ...) / (double)n_pi) over the valid members in member order, float64,
+ *                     no fused multiply-add; all zeros when n_pi = 0
+ *             z     = (float)((0.0 + zt_0 + zt_1 + ...) / (double)n) with zt_k the float64 value xq_samples_to_batch_ex forms
+ *                     before its cast: (double)z, or (1 - q_mix) z + q_mix root_q for a member carrying root statistics
+ *             The definition is dense: members may name different actions.  No floating-point atomics are used.  A group of one
+ *             gives xq_samples_to_batch_ex's three outputs for that record with flip = o_0, byte for byte.  A record names an
+ *             action at most once; n_moves above XQ_MAXM is read as XQ_MAXM and an action id >= 8100 is skipped.
+ *
+ * xq_position_keys: dev_keys[j] and dev_mirrored[j] of row j = record dev_index[j] of dev_samples, or record j when dev_index is
+ *   NULL.  One wavefront per row, four rows per workgroup; sq* comes from a ballot over the 90 squares.
+ * xq_position_key_host: the same code on the host, bit for bit; needs no GPU.  *mirrored may be NULL.  A NULL board or flags
+ *   other than 0 or 1 give key 0 and mirrored 0.
+ * xq_position_group_heads: dev_head[j] = 1 iff row dev_order[j] starts a group (the rule above), else 0, for j < n.  dev_keys and
+ *   dev_mirrored are indexed by row and taken as given.  An entry of dev_order outside [0, n) makes places j and j + 1 heads and
+ *   is read nowhere.
+ * xq_groups_to_batch: output row j is group dev_group[j] under flip dev_flip[j]: dev_states[j] float32[15][10][9], dev_pi[j]
+ *   float32[8100], dev_z[j] float32, as defined above.  dev_group_offsets int32[n_groups + 1], dev_members int32[] record indices
+ *   into dev_samples, dev_member_mirrored uint8[] parallel to dev_members.  A row whose group id is outside [0, n_groups), or
+ *   whose group is empty, gets zero planes, zero pi and z = 0, and no record is read for it.  One 256-thread workgroup per row; a
+ *   group of one takes xq_samples_to_batch's path (zero fill and scatter), a larger one adds its members one after the other
+ *   into a float64 accumulator of 8100 entries in LDS (64 800 bytes) and writes the row from there as float4.
+ * XQ_ERR_ARG before any launch (no GPU needed): n < 0 or n_groups < 0; flags other than 0 or 1; with n > 0 a NULL pointer where
+ *   one is required (dev_index may always be NULL; with n_groups = 0 the record and group arrays may be); late_temperature not
+ *   positive, q_mix outside [0, 1] or NaN, a non-zero reserved word (opts may be NULL: q_mix = 0); dev_keys not 8-byte aligned;
+ *   dev_pi not 16-byte aligned.  n = 0 is a no-op. */
+#define XQ_POSITION_KEY_MIRROR 1
+int xq_position_keys(const void *dev_samples, const int32_t *dev_index /* int32[n] or NULL = 0..n-1 */, int n, int flags,
+                     uint64_t *dev_keys /* [n] */, uint8_t *dev_mirrored /* [n] */, void *stream);
+uint64_t xq_position_key_host(const int8_t *board /* [90] */, int8_t side, int flags, uint8_t *mirrored);
+int xq_position_group_heads(const void *dev_samples, const int32_t *dev_index /* int32[n] or NULL */,
+                            const int32_t *dev_order /* int32[n]: rows in sorted order */, const uint64_t *dev_keys /* [n] */,
+                            const uint8_t *dev_mirrored /* [n] */, int n, uint8_t *dev_head /* [n] */, void *stream);
+int xq_groups_to_batch(const void *dev_samples, const int32_t *dev_group_offsets /* int32[n_groups + 1] */,
+                       const int32_t *dev_members /* int32[]: record indices */,
+                       const uint8_t *dev_member_mirrored /* uint8[], parallel to members */, int n_groups,
+                       const int32_t *dev_group /* int32[n] */, const uint8_t *dev_flip /* uint8[n] */, int n,
+                       double late_temperature, const xq_batch_opts *opts, float *dev_states, float *dev_pi, float *dev_z,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

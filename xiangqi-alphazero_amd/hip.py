@@ -28,6 +28,7 @@ ARENA_MAX_OPENING = 16         # XQ_ARENA_MAX_OPENING
 REUSE_MAX_SIMS = 1600          # XQ_REUSE_MAX_SIMS
 RECORD_MAX_PLIES = 504         # XQ_RECORD_MAX_PLIES
 RECORD_BYTES = 1024            # XQ_RECORD_BYTES
+POSITION_KEY_MIRROR = 1        # XQ_POSITION_KEY_MIRROR
 
 
 class XqError(RuntimeError):
@@ -371,6 +372,11 @@ def lib():
     L.xq_surprise_counts.argtypes = [vp, i32, C.POINTER(SurpriseOpts), vp, vp, vp]
     L.xq_surprise_count_host.argtypes = [C.c_float, i32, C.c_uint64, C.c_uint64, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32,
                                          C.c_uint32, C.c_uint32]
+    L.xq_position_keys.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.xq_position_key_host.argtypes = [vp, C.c_int8, i32, vp]
+    L.xq_position_key_host.restype = C.c_uint64
+    L.xq_position_group_heads.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
+    L.xq_groups_to_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, C.c_double, C.POINTER(BatchOpts), vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -399,7 +405,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_workspace_bytes_em", "xq_engine_init_em", "xq_eval_mirror_bit_host", "xq_mirror_action_host",
            "xq_mirror_requests_batch", "xq_engine_workspace_bytes_gr", "xq_engine_init_gr", "xq_engine_drain_games",
            "xq_engine_drain_games_device", "xq_engine_game_records_stats_read", "xq_replay_games_batch",
-           "xq_samples_to_requests", "xq_score_samples", "xq_surprise_counts", "xq_surprise_count_host"]
+           "xq_samples_to_requests", "xq_score_samples", "xq_surprise_counts", "xq_surprise_count_host",
+           "xq_position_keys", "xq_position_key_host", "xq_position_group_heads", "xq_groups_to_batch"]
 
 
 def check(rc: int, what: str):
@@ -599,6 +606,76 @@ def surprise_count_host(policy_kl: float, marked, M: int, S: int, alpha: float, 
     if c < 0:
         raise XqError(f"xq_surprise_count_host failed: code {c} (alpha must be in [0, 1], got {alpha})")
     return c
+
+
+def position_key_host(board, side: int, mirror: bool = True):
+    """One position's key by the device's own code on the host (xq_position_key_host; needs no GPU): board = 90 int8 values ->
+    (key as a Python int, mirrored 0 / 1); sample_format.position_key is the numpy reference."""
+    import numpy as np
+    b = np.ascontiguousarray(np.asarray(board, dtype=np.int8).reshape(90))
+    mirrored = C.c_uint8(0)
+    key = lib().xq_position_key_host(b.ctypes.data, int(side), POSITION_KEY_MIRROR if mirror else 0, C.addressof(mirrored))
+    return int(key), int(mirrored.value)
+
+
+def position_keys(samples: torch.Tensor, index=None, mirror: bool = True):
+    """Position keys of compact records (xq_position_keys): samples uint8[r, 640] on the GPU, index int32[n] there or None (the
+    records in order) -> (keys int64[n] holding the uint64 bit patterns, mirrored uint8[n])."""
+    p_s = _records_arg(samples, "position_keys")
+    dev = samples.device
+    p_i = _index_arg(index, dev, "position_keys")
+    n = samples.shape[0] if index is None else index.shape[0]
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    mirrored = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n:
+        check(lib().xq_position_keys(p_s, p_i, n, POSITION_KEY_MIRROR if mirror else 0, _dev(keys), _dev(mirrored), stream_ptr(dev)),
+              "xq_position_keys")
+    return keys, mirrored
+
+
+def position_group_heads(samples: torch.Tensor, index, order: torch.Tensor, keys: torch.Tensor, mirrored: torch.Tensor) -> torch.Tensor:
+    """Group heads in sorted order (xq_position_group_heads): order int32[n] = the rows in (stably) sorted order, keys int64[n]
+    and mirrored uint8[n] per row as `position_keys` returns them (taken as given) -> head uint8[n], 1 where row order[j] starts
+    a group: its key, side or canonical board differs from that of row order[j - 1]."""
+    p_s = _records_arg(samples, "position_group_heads")
+    dev = samples.device
+    p_i = _index_arg(index, dev, "position_group_heads")
+    n = samples.shape[0] if index is None else index.shape[0]
+    if order.shape != (n,) or order.dtype != torch.int32 or keys.shape != (n,) or keys.dtype != torch.int64 \
+            or mirrored.shape != (n,) or mirrored.dtype != torch.uint8:
+        raise XqError(f"position_group_heads: order int32[{n}], keys int64[{n}] and mirrored uint8[{n}] required")
+    head = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n:
+        check(lib().xq_position_group_heads(p_s, p_i, _dev(order), _dev(keys), _dev(mirrored), n, _dev(head), stream_ptr(dev)),
+              "xq_position_group_heads")
+    return head
+
+
+def groups_to_batch(samples: torch.Tensor, offsets: torch.Tensor, members: torch.Tensor, member_mirrored: torch.Tensor,
+                    group: torch.Tensor, flip: torch.Tensor, late_temperature: float = 0.3, q_mix: float = 0.0, out=None):
+    """Merged training samples (xq_groups_to_batch): offsets int32[n_groups + 1], members int32[] (record indices into samples) and
+    member_mirrored uint8[] describe the groups; output row j is group group[j] (int32[n]) under flip[j] (uint8[n]) ->
+    (states float32[n,15,10,9], pi float32[n,8100], z float32[n,1]); sample_format.merged_targets is the numpy reference."""
+    p_s = _records_arg(samples, "groups_to_batch")
+    dev = samples.device
+    n, n_groups = group.shape[0], offsets.shape[0] - 1
+    if offsets.dtype != torch.int32 or members.dtype != torch.int32 or member_mirrored.dtype != torch.uint8 \
+            or member_mirrored.shape != members.shape or n_groups < 0:
+        raise XqError("groups_to_batch: offsets int32[n_groups + 1], members int32[m] and member_mirrored uint8[m] required")
+    if group.dtype != torch.int32 or flip.dtype != torch.uint8 or flip.shape != (n,):
+        raise XqError(f"groups_to_batch: group int32[{n}] and flip uint8[{n}] required")
+    if out is None:
+        out = (torch.empty((n, 15, 10, 9), dtype=torch.float32, device=dev),
+               torch.empty((n, ACTION_SPACE), dtype=torch.float32, device=dev), torch.empty((n, 1), dtype=torch.float32, device=dev))
+    states, pi, z = out
+    opts = BatchOpts(float(q_mix))
+    if members.numel() == 0:                       # only empty groups: the arrays are never read, but the ABI wants pointers
+        members, member_mirrored = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.uint8, device=dev)
+    if n:
+        check(lib().xq_groups_to_batch(p_s, _dev(offsets), _dev(members), _dev(member_mirrored), n_groups, _dev(group), _dev(flip), n,
+                                       float(late_temperature), C.byref(opts), _dev(states), _dev(pi), _dev(z), stream_ptr(dev)),
+              "xq_groups_to_batch")
+    return states, pi, z
 
 
 def eval_mirror_bit(seed: int, rank: int, slot: int, game_seq: int, ply: int, is_root, sims_done: int, row: int = 0) -> int:

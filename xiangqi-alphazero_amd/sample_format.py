@@ -319,3 +319,157 @@ def records_from_text(text: str) -> np.ndarray:
             rec[k] = int(keys[k])
         out.append(rec)
     return np.array(out, dtype=GAME_RECORD_DTYPE).reshape(-1)
+
+
+# ---- merging the records of one position (xq_position_keys, xq_position_group_heads, xq_groups_to_batch) --------------------
+POSITION_KEY_MIRROR = 1           # XQ_POSITION_KEY_MIRROR
+MIR_SQ = np.array([(sq // 9) * 9 + 8 - sq % 9 for sq in range(90)], dtype=np.int64)      # mir(sq) of the header
+
+
+def _key_mix(x: np.ndarray) -> np.ndarray:
+    """mix(x) of the header over a uint64 array (numpy's uint64 arithmetic wraps around)."""
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def _key_term(i: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """term(i, b) = mix(0x9E3779B97F4A7C15 * (uint64)(i * 256 + (uint8)b + 1))."""
+    arg = np.asarray(i, dtype=np.uint64) * np.uint64(256) + np.asarray(b, dtype=np.int8).view(np.uint8).astype(np.uint64) + np.uint64(1)
+    return _key_mix(np.uint64(0x9E3779B97F4A7C15) * arg)
+
+
+def canonical_board(board: np.ndarray, mirror: bool = True):
+    """-> (canonical board int8[90], mirrored 0 / 1): with `mirror`, the board or its left-right mirror image, whichever has the
+    smaller int8 at the first square where the two differ (a board that is its own image: itself, mirrored = 0)."""
+    b = np.asarray(board, dtype=np.int8).reshape(90)
+    if not mirror:
+        return b, 0
+    m = b[MIR_SQ]
+    diff = np.nonzero(b != m)[0]
+    if len(diff) == 0:
+        return b, 0
+    sq = int(diff[0])
+    mirrored = 1 if int(m[sq]) < int(b[sq]) else 0
+    return (m if mirrored else b), mirrored
+
+
+def position_key(board: np.ndarray, side: int, mirror: bool = True):
+    """The numpy reference of xq_position_keys / xq_position_key_host -> (key as a Python int in [0, 2^64), mirrored 0 / 1):
+    key = XOR over sq < 90 of term(sq, c[sq]), then ^ term(90, side), over the canonical board c."""
+    c, mirrored = canonical_board(board, mirror)
+    with np.errstate(over="ignore"):
+        terms = _key_term(np.arange(90), c)
+        key = np.bitwise_xor.reduce(terms) ^ _key_term(np.array([90]), np.array([side], dtype=np.int8))[0]
+    return int(key), mirrored
+
+
+def position_group_heads(samples: np.ndarray, order: np.ndarray, keys: np.ndarray, mirrored: np.ndarray) -> np.ndarray:
+    """The numpy reference of xq_position_group_heads, uint8 per sorted place: row order[j] starts a group iff j == 0 or its key,
+    its side or its canonical board differs from that of row order[j - 1].  Keys and mirrored flags are taken as given."""
+    samples = np.asarray(samples).reshape(-1)
+    head = np.ones(len(order), dtype=np.uint8)
+    for j in range(1, len(order)):
+        r, p = int(order[j]), int(order[j - 1])
+        if int(keys[r]) != int(keys[p]) or samples["side"][r] != samples["side"][p]:
+            continue
+        ca = samples["board"][r][MIR_SQ] if mirrored[r] else samples["board"][r]
+        cb = samples["board"][p][MIR_SQ] if mirrored[p] else samples["board"][p]
+        head[j] = 0 if np.array_equal(ca, cb) else 1
+    return head
+
+
+def position_groups(samples: np.ndarray, mirror: bool = True, keys=None):
+    """The numpy reference of the grouping -> (offsets int32[n_groups + 1], members int32[n], member_mirrored uint8[n]): the rows
+    (oldest first) are sorted stably by key, the heads found by the predecessor rule, the groups numbered by the age of their
+    oldest member; members of a group are in age order.  `keys` replaces the computed keys (a test's made-up equal keys); the
+    mirrored flags are always the computed ones."""
+    samples = np.asarray(samples).reshape(-1)
+    n = len(samples)
+    km = [position_key(s["board"], int(s["side"]), mirror) for s in samples]
+    mirrored = np.array([m for _, m in km], dtype=np.uint8).reshape(n)
+    if keys is None:
+        keys = np.array([k for k, _ in km], dtype=np.uint64).reshape(n)
+    keys = np.asarray(keys, dtype=np.uint64)
+    order = np.argsort(keys, kind="stable")
+    head = position_group_heads(samples, order, keys, mirrored)
+    gid_sorted = np.cumsum(head, dtype=np.int64) - 1                     # group of sorted place j, in sorted numbering
+    n_groups = int(gid_sorted[-1]) + 1 if n else 0
+    first_row = order[head == 1]                                         # the oldest member of each group: the sort is stable
+    label = np.empty(n_groups, dtype=np.int64)
+    label[np.argsort(first_row, kind="stable")] = np.arange(n_groups)
+    row_label = np.empty(n, dtype=np.int64)
+    row_label[order] = label[gid_sorted] if n else []
+    members = np.argsort(row_label, kind="stable").astype(np.int32)     # by group, age order inside a group
+    sizes = np.bincount(row_label, minlength=n_groups)
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    return offsets, members, mirrored[members]
+
+
+def member_target(s, flip: bool, late_temperature: float):
+    """One record's policy target as xq_samples_to_batch forms it before its cast -> (actions int64[m] under `flip`,
+    t float64[m], total): w = visits, or visits^(1/T) for a late-temperature record; total = their sequential sum in move order;
+    t = w / total (zeros when total is not above 0).  n_moves above 128 reads as 128; an action id >= 8100 is dropped."""
+    m = min(int(s["n_moves"]), 128)
+    c = s["visits"][:m].astype(np.float64)
+    if s["late_temp"]:
+        with np.errstate(over="ignore"):
+            w = np.where(c > 0.0, c ** (1.0 / float(late_temperature)), 0.0)
+    else:
+        w = c
+    total = 0.0
+    for x in w:
+        total += float(x)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        t = w / total if total > 0.0 else np.zeros(m)
+    a = s["actions"][:m].astype(np.int64)
+    keep = a < ACTION_SPACE
+    a, t = a[keep], t[keep]
+    return (FLIP_PERM[a] if flip else a), t, total
+
+
+def merged_targets(samples: np.ndarray, groups, group: np.ndarray, flip: np.ndarray, late_temperature: float = 0.3,
+                   q_mix: float = 0.0):
+    """The numpy reference of xq_groups_to_batch -> (states float32[n,15,10,9], pi float32[n,8100], z float32[n]).  `groups` =
+    (offsets, members, member_mirrored) as `position_groups` returns them, members indexing `samples`; output row j is group
+    group[j] under flip[j].  Member k enters under orientation o_k = member_mirrored_k XOR flip: planes of member 0 under o_0;
+    pi = (float32)((0.0 + t_0 + t_1 + ...) / n_pi) over the valid members (total > 0) in member order, float64; z =
+    (float32)((0.0 + zt_0 + ...) / n) with zt the float64 value of `mixed_z` before its cast.  A group id outside
+    [0, n_groups) and an empty group give zeros."""
+    samples = np.asarray(samples).reshape(-1)
+    offsets, members, member_mirrored = (np.asarray(a) for a in groups)
+    q_mix = float(q_mix)
+    if not 0.0 <= q_mix <= 1.0:
+        raise ValueError(f"q_mix must be in [0, 1], got {q_mix}")
+    n, n_groups = len(group), len(offsets) - 1
+    states = np.zeros((n, 15, 10, 9), dtype=np.float32)
+    pi = np.zeros((n, ACTION_SPACE), dtype=np.float32)
+    z = np.zeros(n, dtype=np.float32)
+    for j in range(n):
+        g = int(group[j])
+        if not 0 <= g < n_groups or offsets[g + 1] <= offsets[g]:
+            continue
+        f = bool(flip[j])
+        mem = [(samples[int(members[i])], bool(member_mirrored[i]) != f) for i in range(int(offsets[g]), int(offsets[g + 1]))]
+        s0, o0 = mem[0]
+        st = encode_planes(s0["board"], int(s0["side"]))
+        states[j] = np.flip(st, axis=2) if o0 else st
+        acc = np.zeros(ACTION_SPACE)
+        zsum, n_pi = 0.0, 0
+        for s, o in mem:
+            a, t, total = member_target(s, o, late_temperature)
+            if total > 0.0:
+                n_pi += 1
+                acc[a] = acc[a] + t                   # a dense sum: a member adds 0.0 at every action it does not name
+            zt = float(s["z"])
+            if q_mix != 0.0:
+                rs = root_stats(np.asarray(s).reshape(1))[0]
+                if rs["has_root_stats"] == 1:
+                    zt = (1.0 - q_mix) * float(s["z"]) + q_mix * float(np.float64(rs["root_q"]))
+            zsum += zt
+        if n_pi:
+            pi[j] = (acc / float(n_pi)).astype(np.float32)
+        z[j] = np.float32(zsum / float(len(mem)))
+    return states, pi, z

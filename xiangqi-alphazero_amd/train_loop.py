@@ -35,7 +35,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import arena, distributed as xdist, selfplay, training
+from . import arena, distributed as xdist, hip, selfplay, training
 from .model import XiangqiNet
 from .sample_format import GAME_RECORD_DTYPE, RESULT_DTYPE, records_to_text
 
@@ -73,6 +73,13 @@ class AlphaZeroLoop:
         self.score_samples = bool(getattr(config, "score_samples", False)) or self.surprise_weight > 0.0
         self._shard_scores = None
         self._score_ev = None
+        # merging the records of one position into one training sample (config.merge_duplicate_positions, absent: off;
+        # config.merge_mirror_positions, absent: on), read once; the train step's stats carry the counts of every iteration
+        # (distinct_positions, merged_records, largest_group) into training_stats.json
+        self.merge_duplicates = training.merge_duplicate_positions(config)
+        self.merge_mirror = training.merge_mirror_positions(config)
+        if self.merge_duplicates and self.surprise_weight > 0.0:
+            raise hip.XqError("config.merge_duplicate_positions and config.policy_surprise_weight > 0 cannot be combined")
         torch.manual_seed(seed)                        # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -178,7 +185,8 @@ class AlphaZeroLoop:
         if ddp or self.rank == 0:
             stats = training.train_network(self.current_model, self.optimizer, self.scheduler, self.buffer, self.config,
                                            generator=gen, ddp=ddp, native_bn=bool(getattr(self.config, "native_sync_bn", False)),
-                                           q_mix=self.q_mix, surprise_weight=self.surprise_weight)
+                                           q_mix=self.q_mix, surprise_weight=self.surprise_weight,
+                                           merge_duplicates=self.merge_duplicates, merge_mirror=self.merge_mirror)
         if self.grouped:
             xdist.broadcast_weights(self.current_model, src=0, device=self.device)
         return stats

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 from typing import Dict, Optional
 
 import numpy as np
@@ -23,6 +24,19 @@ import torch.nn.functional as F
 
 from . import hip, selfplay
 from .sample_format import SAMPLE_DTYPE
+
+
+@dataclass
+class PositionGroups:
+    """The records of a buffer grouped by position (`ReplayBuffer.position_groups`), on the device: group g holds the records
+    members[offsets[g]:offsets[g + 1]] (ring indices, oldest first; member_mirrored says which of them enter mirrored), groups
+    numbered by the age of their oldest member.  Valid for the buffer as it was when the groups were built."""
+    offsets: torch.Tensor            # int32[n_groups + 1]
+    members: torch.Tensor            # int32[n_records]
+    member_mirrored: torch.Tensor    # uint8[n_records]
+    n_groups: int
+    sizes: torch.Tensor              # int64[n_groups]
+    n_records: int
 
 
 class ReplayBuffer:
@@ -112,6 +126,56 @@ class ReplayBuffer:
         return states, pi, z
 
 
+    def position_groups(self, mirror: bool = True) -> PositionGroups:
+        """The live records grouped by position (board and side to move; with `mirror`, a position and its left-right mirror
+        image are one group): keys by xq_position_keys over the records oldest first, a stable sort by key, the group heads by
+        xq_position_group_heads (a full compare of side and canonical board: a key collision cannot merge two positions), a
+        cumulative sum, and a relabelling by the oldest member.  sample_format.position_groups is the numpy reference."""
+        n = self.count
+        dev = self.device
+        if n == 0:
+            return PositionGroups(torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                                  torch.zeros(0, dtype=torch.uint8, device=dev), 0, torch.zeros(0, dtype=torch.int64, device=dev), 0)
+        oldest = (self.head - self.count) % self.cap
+        ring = ((torch.arange(n, device=dev) + oldest) % self.cap).to(torch.int32)      # row (age) -> ring index
+        keys, mirrored = hip.position_keys(self.store, ring, mirror)
+        order = torch.sort(keys, stable=True)[1]                 # any total order of the keys groups equal keys, in age order
+        head = hip.position_group_heads(self.store, ring, order.to(torch.int32), keys, mirrored).to(torch.int64)
+        gid_sorted = torch.cumsum(head, 0) - 1
+        n_groups = int(gid_sorted[-1].item()) + 1
+        first_row = order[head == 1]                             # the oldest member of each group: the sort is stable
+        label = torch.empty(n_groups, dtype=torch.int64, device=dev)
+        label[torch.sort(first_row, stable=True)[1]] = torch.arange(n_groups, device=dev)
+        row_label = torch.empty(n, dtype=torch.int64, device=dev)
+        row_label[order] = label[gid_sorted]
+        rows = torch.sort(row_label, stable=True)[1]             # by group, age order inside a group
+        sizes = torch.bincount(row_label, minlength=n_groups)
+        offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(sizes, 0)]).to(torch.int32)
+        return PositionGroups(offsets, ring[rows].contiguous(), mirrored[rows].contiguous(), n_groups, sizes, n)
+
+    def batch_groups(self, groups: PositionGroups, logical: torch.Tensor, q_mix: float = 0.0):
+        """-> states f32[B,15,10,9], pi f32[B,8100], z f32[B,1] of merged samples (xq_groups_to_batch): logical index 2 g + f is
+        group g of `groups` under flip f; policy and value targets are the means over the group's records."""
+        logical = logical.to(self.device)
+        group = torch.div(logical, 2, rounding_mode="floor").to(torch.int32)
+        flip = (logical % 2).to(torch.uint8)
+        out = hip.groups_to_batch(self.store, groups.offsets, groups.members, groups.member_mirrored, group, flip,
+                                  self.late_temperature, q_mix)
+        self._keep = (group, flip)
+        return out
+
+
+def merge_duplicate_positions(config) -> bool:
+    """`config.merge_duplicate_positions` (a reference TrainingConfig has no such key: off)."""
+    return bool(getattr(config, "merge_duplicate_positions", False))
+
+
+def merge_mirror_positions(config) -> bool:
+    """`config.merge_mirror_positions` (absent: on): whether merging takes a position and its mirror image as one."""
+    v = getattr(config, "merge_mirror_positions", True)
+    return True if v is None else bool(v)
+
+
 def prepare_ddp(model, device, group=None, native_bn: bool = False):
     """The data-parallel form of `model`, built ONCE and kept for the model's lifetime: BatchNorm -> SyncBatchNorm IN PLACE
     (same Parameters and buffers, same state_dict keys: checkpoints, `broadcast_weights` and the evaluators are unaffected)
@@ -155,7 +219,8 @@ def revert_sync_batchnorm(model) -> None:
 def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shuffle: bool = True,
                   generator: Optional[torch.Generator] = None, ddp: bool = False, group=None,
                   native_bn: bool = False, q_mix: Optional[float] = None,
-                  surprise_weight: Optional[float] = None) -> Dict[str, float]:
+                  surprise_weight: Optional[float] = None, merge_duplicates: Optional[bool] = None,
+                  merge_mirror: Optional[bool] = None) -> Dict[str, float]:
     """One call of the reference's train_network (train.py:376-447) on the device-resident buffer.
 
     `ddp=True` under an initialised torch.distributed group (every rank holds the same buffer and the same weights, as
@@ -178,7 +243,15 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     weighting); an epoch then has about as many samples as before, in expectation.  The seed of the counts' rounding draws is
     one `torch.randint` draw from `generator` per call -- equal on every rank, so the data-parallel path needs nothing else.  With
     alpha > 0 a buffer without a single scored record is refused.  Off, the epoch loop is unchanged.  The stats gain
-    "policy_surprise_weight", "policy_stats_coverage" (None when off: not measured) and "epoch_samples" (per epoch)."""
+    "policy_surprise_weight", "policy_stats_coverage" (None when off: not measured) and "epoch_samples" (per epoch).
+
+    `merge_duplicates` (default: the config's `merge_duplicate_positions`; absent means off): the records of one position -- and,
+    unless `merge_mirror` (default: the config's `merge_mirror_positions`, absent: on) is False, of its mirror image -- are trained on as ONE sample per orientation whose
+    policy and value targets are the means over those records (`ReplayBuffer.position_groups`, built once per call: the buffer
+    does not change during a call, and every rank of a data-parallel step holds the same buffer, hence the same groups).  An epoch
+    is then a permutation of 2 * n_groups logical samples (`ReplayBuffer.batch_groups`).  Together with policy_surprise_weight > 0
+    it is refused.  The stats gain "merge_duplicate_positions", "distinct_positions", "merged_records" (records minus groups) and
+    "largest_group" (False / None / None / None when off, and the epoch loop is unchanged)."""
     if len(buffer) < config.min_buffer_size:
         return {}
     if q_mix is None:                                  # self-play's reader of the key: None, the range, the Gumbel refusal
@@ -194,6 +267,12 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     alpha = float(surprise_weight or 0.0)
     if not 0.0 <= alpha <= 1.0:
         raise hip.XqError(f"policy_surprise_weight must be in [0, 1], got {alpha}")
+    if merge_duplicates is None:
+        merge_duplicates = merge_duplicate_positions(config)
+    merge = bool(merge_duplicates)
+    if merge and alpha > 0.0:
+        raise hip.XqError("merge_duplicate_positions and policy_surprise_weight > 0 cannot be combined: which of a merged group's "
+                          "KLs should weight it is not defined")
     coverage = None
     if alpha > 0.0:
         coverage = buffer.policy_stats_coverage()
@@ -223,6 +302,10 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     epoch_samples = []
     if alpha > 0.0:                                                    # one draw per call keys every epoch's rounding decisions
         surprise_seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator).item())
+    groups = None
+    if merge:                                                          # once per call: the buffer does not change during a call
+        groups = buffer.position_groups(merge_mirror_positions(config) if merge_mirror is None else bool(merge_mirror))
+        n = 2 * groups.n_groups
     for epoch in range(config.num_epochs):
         if alpha > 0.0:
             order = buffer.epoch_order(alpha, surprise_seed, epoch, generator, shuffle)
@@ -237,7 +320,10 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
             if use_ddp and full >= world:                              # this rank's slice of the batch
                 idx = idx.tensor_split(world)[rank]
                 scale = float(world)                                   # DDP averages the ranks' gradients
-            states, target_pi, target_z = buffer.batch(idx, q_mix)
+            if groups is not None:
+                states, target_pi, target_z = buffer.batch_groups(groups, idx, q_mix)
+            else:
+                states, target_pi, target_z = buffer.batch(idx, q_mix)
             logits, value = net(states)
             if use_ddp and full >= world:
                 # sums over the local slice, scaled so that DDP's average over ranks is the full-batch mean loss
@@ -262,7 +348,10 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
     return {"policy_loss": total_p / max(batches, 1), "value_loss": total_v / max(batches, 1),
             "total_loss": (total_p + total_v) / max(batches, 1), "learning_rate": optimizer.param_groups[0]["lr"],
             "value_target_q_mix": q_mix, "policy_surprise_weight": alpha, "policy_stats_coverage": coverage,
-            "epoch_samples": epoch_samples}
+            "epoch_samples": epoch_samples, "merge_duplicate_positions": merge,
+            "distinct_positions": groups.n_groups if merge else None,
+            "merged_records": groups.n_records - groups.n_groups if merge else None,
+            "largest_group": int(groups.sizes.max().item()) if merge else None}
 
 
 def save_checkpoint(checkpoint_dir: str, iteration: int, current_model, best_model, optimizer, scheduler, total_games: int,
