@@ -1066,6 +1066,44 @@ int xq_replay_games_batch(const void *dev_records /* xq_game_record[n] */, const
                           int8_t *dev_hist12 /* [n][12][90], oldest first, xq_engine_set_position's layout */,
                           int32_t *dev_status, int8_t *dev_over_kind, int8_t *dev_winner, void *stream);
 
+/* A fixed alpha-beta opponent (nothing in the engine knows of it, and no existing entry point, struct or byte changes): a batched
+ * fixed-depth minimax search over the material evaluation, one wavefront per (position, root move).  A non-learning yardstick for
+ * a training run (baseline.py plays a network against it), and a per-move tactical score for any batch of positions.
+ * ROOT MOVES.  dev_moves[i][0..dev_counts[i]) are the ordered legal moves of the side to move: xq_movegen_batch's output exactly.
+ * SCORE OF ROOT MOVE j.  dev_scores[i][j] = -V(child_j, depth - 1, 1).  V(pos, d, ply) is taken from the view of the side to move
+ * in pos:
+ *     d == 0:    V = material(side to move) - material(other), xq_material_batch's piece values; no moves are generated and there
+ *                is no quiescence;
+ *     otherwise  generate the ordered legal moves; none: V = -(XQ_AB_MATE - ply) (a side without a legal move has lost, and a
+ *                quicker mate scores higher); else V = the maximum over the moves of -V(child, d - 1, ply + 1).
+ * Repetition, the no-capture count and the ply-200 rule do not enter the search.
+ * DEPTH 0.  Every root move scores 0 and nothing is searched: with draws the uniformly random player, without them the player of
+ * the first legal move.  0 <= depth <= XQ_AB_MAX_DEPTH.
+ * PRUNING.  Each root move is searched on its own under a full window; below it the search is fail-soft alpha-beta in move order,
+ * and the level whose children are leaves scores all of them at once.  dev_scores[i][j] is exactly the plain minimax value of
+ * every root move: the tie-break needs it and an analysis caller wants it.
+ * PICK.  dev_best_score[i] is the largest score; B = the root moves that reach it, in move order; dev_best_action[i] =
+ * B[dev_draws[i] % |B|], or B[0] when dev_draws is NULL.
+ * EVERY OUTPUT IS WRITTEN.  At and past the count dev_scores[i][j] = XQ_AB_UNSCORED, dev_nodes[i][j] = 0, dev_moves[i][j] = 0.
+ * dev_nodes[i][j] (or NULL) is the number of positions visited below root move j, the child itself included: between 1 and the
+ * plain minimax count for depth >= 1, 0 at depth 0.
+ * dev_status[i]: 0 fine; 1 a move-generation capacity was exceeded somewhere in the tree, by xq_movegen_batch's rule; 2 a king is
+ * missing on the input board: no search is done, the count is 0, dev_best_action[i] = XQ_AB_NO_MOVE and dev_best_score[i] = 0.
+ * A root without legal moves has count 0, dev_best_action[i] = XQ_AB_NO_MOVE and dev_best_score[i] = -XQ_AB_MATE.
+ * XQ_ERR_ARG before any launch: n < 0, a depth outside the range, with n > 0 a NULL pointer other than dev_draws and dev_nodes.
+ * n == 0 is a no-op that returns XQ_OK.  Three launches on `stream` (two at depth 0) per 2^18 positions, no atomics, no
+ * workspace. */
+#define XQ_AB_MAX_DEPTH 4
+#define XQ_AB_MATE      30000
+#define XQ_AB_UNSCORED  INT32_MIN
+#define XQ_AB_NO_MOVE   0xFFFF
+int xq_alphabeta_batch(const int8_t *dev_boards /* [n][90] */, const int8_t *dev_side /* [n] */, int n, int depth,
+                       const uint32_t *dev_draws /* [n] or NULL */,
+                       uint16_t *dev_moves /* [n][XQ_MAXM] */, uint16_t *dev_counts /* [n] */,
+                       int32_t *dev_scores /* [n][XQ_MAXM] */, uint32_t *dev_nodes /* [n][XQ_MAXM] or NULL */,
+                       uint16_t *dev_best_action /* [n] */, int32_t *dev_best_score /* [n] */,
+                       uint8_t *dev_status /* [n] */, void *stream);
+
 /* Scoring samples against a network, and policy-surprise weighted training (opt-in; nothing in the engine knows of it, and no
  * existing entry point, struct or byte changes).  A finished sample is turned back into an evaluation request, a network answers
  * it, and the answer is compared with the sample's search target: how well does network X predict the samples in buffer Y, and

@@ -29,6 +29,10 @@ REUSE_MAX_SIMS = 1600          # XQ_REUSE_MAX_SIMS
 RECORD_MAX_PLIES = 504         # XQ_RECORD_MAX_PLIES
 RECORD_BYTES = 1024            # XQ_RECORD_BYTES
 POSITION_KEY_MIRROR = 1        # XQ_POSITION_KEY_MIRROR
+AB_MAX_DEPTH = 4               # XQ_AB_MAX_DEPTH
+AB_MATE = 30000                # XQ_AB_MATE
+AB_UNSCORED = -2 ** 31         # XQ_AB_UNSCORED
+AB_NO_MOVE = 0xFFFF            # XQ_AB_NO_MOVE
 
 
 class XqError(RuntimeError):
@@ -302,6 +306,7 @@ def lib():
     L.xq_engine_drain_games_device.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
     L.xq_engine_game_records_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(GameRecordsStats), vp]
     L.xq_replay_games_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.xq_alphabeta_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.xq_eval_mirror_bit_host.argtypes = [C.c_uint64, i32, i32, C.c_uint32, i32, i32, i32, i32]
     L.xq_mirror_action_host.argtypes = [i32]
     L.xq_mirror_requests_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
@@ -406,7 +411,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_mirror_requests_batch", "xq_engine_workspace_bytes_gr", "xq_engine_init_gr", "xq_engine_drain_games",
            "xq_engine_drain_games_device", "xq_engine_game_records_stats_read", "xq_replay_games_batch",
            "xq_samples_to_requests", "xq_score_samples", "xq_surprise_counts", "xq_surprise_count_host",
-           "xq_position_keys", "xq_position_key_host", "xq_position_group_heads", "xq_groups_to_batch"]
+           "xq_position_keys", "xq_position_key_host", "xq_position_group_heads", "xq_groups_to_batch",
+           "xq_alphabeta_batch"]
 
 
 def check(rc: int, what: str):
@@ -527,6 +533,38 @@ def replay_games(records: torch.Tensor, stop_ply=None, perpetual_check: bool = F
                                           _dev(out["board"]), _dev(out["side"]), _dev(out["move_count"]), _dev(out["no_capture"]),
                                           _dev(out["hist12"]), _dev(out["status"]), _dev(out["over_kind"]), _dev(out["winner"]),
                                           stream_ptr(dev)), "xq_replay_games_batch")
+    return out
+
+
+def alphabeta_batch(boards: torch.Tensor, side: torch.Tensor, depth: int, draws=None):
+    """The fixed alpha-beta opponent (xq_alphabeta_batch): boards int8[n,90] (or [n,10,9]) and side int8[n] on the GPU, 0 <= depth
+    <= AB_MAX_DEPTH, draws None (the first best move) or one uint32 per position (an int32 / int64 device tensor, or anything
+    numpy turns into uint32) -> dict of device tensors: moves (u16-as-int16 [n,128], as `movegen`), counts int16[n], scores
+    int32[n,128] (the exact minimax score of every root move, AB_UNSCORED past the count), nodes int32[n,128], best_action
+    (u16-as-int16 [n]; AB_NO_MOVE reads -1), best_score int32[n], status uint8[n] (0 fine, 1 capacity, 2 a king is missing)."""
+    if not 0 <= int(depth) <= AB_MAX_DEPTH:
+        raise XqError(f"alphabeta_batch: depth must be in [0, {AB_MAX_DEPTH}], got {depth}")
+    n, dev = boards.shape[0], boards.device
+    if boards.dtype != torch.int8 or boards.numel() != n * 90 or side.dtype != torch.int8 or tuple(side.shape) != (n,):
+        raise XqError(f"alphabeta_batch: boards must be int8[n, 90] and side int8[n], got {tuple(boards.shape)} and {tuple(side.shape)}")
+    d = None
+    if draws is not None:
+        if isinstance(draws, torch.Tensor):
+            d = (draws.to(dev).to(torch.int64) & 0xFFFFFFFF)
+        else:
+            import numpy as np
+            d = torch.from_numpy(np.asarray(draws, dtype=np.uint64).astype(np.int64) & 0xFFFFFFFF).to(dev)
+        d = torch.where(d >= 2 ** 31, d - 2 ** 32, d).to(torch.int32).contiguous()      # the uint32's bits
+        if tuple(d.shape) != (n,):
+            raise XqError(f"alphabeta_batch: draws must hold one value per position ({n}), got {tuple(d.shape)}")
+    out = {"moves": torch.zeros((n, MAXM), dtype=torch.int16, device=dev), "counts": torch.zeros(n, dtype=torch.int16, device=dev),
+           "scores": torch.zeros((n, MAXM), dtype=torch.int32, device=dev), "nodes": torch.zeros((n, MAXM), dtype=torch.int32, device=dev),
+           "best_action": torch.zeros(n, dtype=torch.int16, device=dev), "best_score": torch.zeros(n, dtype=torch.int32, device=dev),
+           "status": torch.zeros(n, dtype=torch.uint8, device=dev)}
+    if n:
+        check(lib().xq_alphabeta_batch(_dev(boards), _dev(side), n, int(depth), None if d is None else _dev(d), _dev(out["moves"]),
+                                       _dev(out["counts"]), _dev(out["scores"]), _dev(out["nodes"]), _dev(out["best_action"]),
+                                       _dev(out["best_score"]), _dev(out["status"]), stream_ptr(dev)), "xq_alphabeta_batch")
     return out
 
 

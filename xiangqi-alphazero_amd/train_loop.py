@@ -13,6 +13,9 @@ Per iteration, exactly the reference's order:
                    ranks (`arena.evaluate_models`); promote at win_rate >= eval_win_rate, else the candidate reverts to
                    the best weights (train.py:525-533).  Every rank derives the verdict from the same all-reduced table
                    and rank 0's decision is broadcast on top, so the replicas cannot drift apart;
+  3b. baseline     opt-in (`config.baseline_games` > 0): every `baseline_interval`-th iteration rank 0 plays the best model
+                   against the fixed alpha-beta opponent (`baseline.play_vs_baseline`) and logs the result under "baseline" in
+                   that iteration's entry: an absolute yardstick next to the gate's relative one; it decides nothing;
   4. checkpoint    every `save_interval` iterations and once more after the last one (train.py:613-615, 636-637), the
                    reference's file format; `training_stats.json` like train.py:620-634.
 `resume(path)` is the reference's `--resume` (train.py:569-579, 759-761): iteration, total_games, both models, optimizer
@@ -38,6 +41,36 @@ import torch.distributed as dist
 from . import arena, distributed as xdist, hip, selfplay, training
 from .model import XiangqiNet
 from .sample_format import GAME_RECORD_DTYPE, RESULT_DTYPE, records_to_text
+
+
+def _baseline_options(config):
+    """The baseline gate's keys (all optional; absent means off): None when config.baseline_games is absent or 0, else a dict of
+    games, depth, simulations, opening_plies, interval.  A key outside its range raises XqError with the key's name."""
+    def key(name, default):
+        v = getattr(config, name, None)
+        v = default if v is None else v
+        if isinstance(v, bool) or int(v) != v:
+            raise hip.XqError(f"config.{name} must be an integer, got {v!r}")
+        return int(v)
+
+    games = key("baseline_games", 0)
+    if games < 0 or games % 2:
+        raise hip.XqError(f"config.baseline_games must be even and >= 0 (games come in colour-swapped pairs), got {games}")
+    depth = key("baseline_depth", 2)
+    if not 0 <= depth <= hip.AB_MAX_DEPTH:
+        raise hip.XqError(f"config.baseline_depth must be in [0, {hip.AB_MAX_DEPTH}], got {depth}")
+    plies = key("baseline_opening_plies", 4)
+    if not 0 <= plies <= hip.ARENA_MAX_OPENING:
+        raise hip.XqError(f"config.baseline_opening_plies must be in [0, {hip.ARENA_MAX_OPENING}], got {plies}")
+    interval = key("baseline_interval", 2)
+    if interval < 1:
+        raise hip.XqError(f"config.baseline_interval must be >= 1, got {interval}")
+    if games == 0:
+        return None
+    sims = key("baseline_simulations", int(config.eval_simulations))
+    if sims < 1:
+        raise hip.XqError(f"config.baseline_simulations must be >= 1, got {sims}")
+    return {"games": games, "depth": depth, "simulations": sims, "opening_plies": plies, "interval": interval}
 
 
 class AlphaZeroLoop:
@@ -80,6 +113,9 @@ class AlphaZeroLoop:
         self.merge_mirror = training.merge_mirror_positions(config)
         if self.merge_duplicates and self.surprise_weight > 0.0:
             raise hip.XqError("config.merge_duplicate_positions and config.policy_surprise_weight > 0 cannot be combined")
+        # the baseline gate (config.baseline_games; absent or 0: off), read once and checked here: every baseline_interval-th
+        # iteration rank 0 plays best_model against the fixed alpha-beta opponent (baseline.py): no promotion, no collective
+        self.baseline = _baseline_options(config)
         torch.manual_seed(seed)                        # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -135,13 +171,15 @@ class AlphaZeroLoop:
             self._score_ev.update(self.best_model)
         return self._score_ev
 
-    def _write_records(self, stage: str, records) -> None:
-        """This rank's game records of one stage of the current iteration, as text, when config.game_records_dir is set."""
-        if not self.game_records_dir:
+    def _write_records(self, stage: str, records, folder=None) -> None:
+        """This rank's game records of one stage of the current iteration, as text, when config.game_records_dir is set (`folder`:
+        the directory of a stage that has records without config.record_games)."""
+        folder = folder or self.game_records_dir
+        if not folder:
             return
-        os.makedirs(self.game_records_dir, exist_ok=True)
+        os.makedirs(folder, exist_ok=True)
         name = "iter%04d_%s_rank%d.txt" % (self.iteration, stage, self.rank)
-        with open(os.path.join(self.game_records_dir, name), "w") as f:
+        with open(os.path.join(folder, name), "w") as f:
             f.write(records_to_text(records))
 
     def self_play(self) -> dict:
@@ -218,6 +256,20 @@ class AlphaZeroLoop:
             self.current_model.load_state_dict(self.best_model.state_dict())
         return stats
 
+    def play_baseline(self) -> dict:
+        """best_model against the fixed alpha-beta opponent (baseline.play_vs_baseline), seed + iteration as the match's seed.
+        The records go to config.game_records_dir, when set, like the other stages'; the rest is this iteration's "baseline"
+        entry."""
+        from . import baseline
+        b = self.baseline
+        out = baseline.play_vs_baseline(self.best_model, b["games"], b["depth"], b["simulations"], opening_plies=b["opening_plies"],
+                                        seed=self.seed + self.iteration, max_game_length=int(self.config.max_game_length),
+                                        c_puct=float(self.config.c_puct), perpetual_check=self.perpetual_check, solver=self.solver,
+                                        device=self.device, evaluator_kind=self.evaluator_kind)
+        # the match keeps its records whatever config.record_games says: they are its state
+        self._write_records("baseline", out["game_records"], getattr(self.config, "game_records_dir", None))
+        return {k: out[k] for k in ("depth", "games", "wins", "losses", "draws", "win_rate", "win_rate_se", "seconds")}
+
     def _save(self, iteration: int) -> None:
         if self.rank == 0:
             training.save_checkpoint(self.config.checkpoint_dir, iteration, self.current_model, self.best_model,
@@ -267,10 +319,13 @@ class AlphaZeroLoop:
             ev = {}
             if iteration % 2 == 0 and len(self.buffer) >= cfg.min_buffer_size:
                 ev = self.evaluate()
+            bl = None
+            if self.baseline is not None and self.rank == 0 and iteration % self.baseline["interval"] == 0:
+                bl = self.play_baseline()
             if iteration % cfg.save_interval == 0:
                 self._save(iteration)
             self.training_stats.append({"iteration": iteration, "time": time.time() - t0, "self_play": sp,
-                                        "training": tr, "evaluation": ev})
+                                        "training": tr, "evaluation": ev, **({} if bl is None else {"baseline": bl})})
             if self.rank == 0:
                 os.makedirs(cfg.checkpoint_dir, exist_ok=True)
                 with open(os.path.join(cfg.checkpoint_dir, "training_stats.json"), "w") as f:
