@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from eval_cache_model import fixture_positions as _fixture_positions, key_numpy as _key_numpy
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["xq_evcache_bytes", "xq_evcache_init", "xq_evcache_hit_flags", "xq_evcache_probe", "xq_engine_compact_misses",
        "xq_evcache_commit", "xq_evcache_invalidate", "xq_evcache_stats_read", "xq_evcache_key_host"]
@@ -126,23 +128,6 @@ def _key_host(lib, planes):
     out = np.zeros(12, np.uint32)
     assert lib.xq_evcache_key_host(np.ascontiguousarray(planes, np.float32).ctypes.data, out.ctypes.data) == 0
     return out
-
-
-def _key_numpy(board, side):
-    """Independent re-derivation from the board: nibble = |piece| for the side to move's pieces, |piece| + 7 for the
-    opponent's, 0 when empty (the planes' order, game.py:618-640); nibble 90 = red to move."""
-    b = np.asarray(board, np.int64).reshape(90)
-    nib = np.where(b == 0, 0, np.where(b * side > 0, np.abs(b), np.abs(b) + 7))
-    nib = np.concatenate([nib, [1 if side == 1 else 0], np.zeros(5, np.int64)])
-    return np.array([sum(int(nib[8 * w + j]) << (4 * j) for j in range(8)) for w in range(12)], np.uint32)
-
-
-def _fixture_positions():
-    corpus = np.load(os.path.join(ROOT, "tests", "golden", "corpus.npz"))
-    crafted = np.load(os.path.join(ROOT, "tests", "golden", "crafted.npz"))
-    boards = np.concatenate([corpus["board"], crafted["board"]])
-    sides = np.concatenate([corpus["side"], crafted["side"]]).astype(np.int64)
-    return boards, sides
 
 
 def test_key_matches_numpy_and_is_injective_over_the_fixtures(lib):
