@@ -20,13 +20,12 @@ only the win rate is given).
 """
 import argparse
 import json
-import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import measure_common as mc
+
+sys.path.insert(0, mc.ROOT)
 CHANNELS, BLOCKS, GAIN, OPENING = 128, 6, 8.0, 4
 JOBS = {
     "a": [dict(part="a", games=10, opening_plies=0, modes=["default", "masked"])],
@@ -37,13 +36,8 @@ JOBS = {
 
 
 def _evaluators():
-    from xiangqi_alphazero_amd import evaluator, model, weights
-    out = []
-    for seed in (1, 2):
-        net = model.XiangqiNet(CHANNELS, BLOCKS)
-        net.load_state_dict(weights.make_state_dict(CHANNELS, BLOCKS, seed=seed, policy_gain=GAIN))
-        out.append(evaluator.make_evaluator(net, "cuda", "hip")[0])
-    return out
+    from xiangqi_alphazero_amd import evaluator
+    return [evaluator.make_evaluator(mc.make_net(CHANNELS, BLOCKS, GAIN, seed), "cuda", "hip")[0] for seed in (1, 2)]
 
 
 def child(job):
@@ -111,36 +105,16 @@ def main():
     ap.add_argument("--child", default=None)
     args = ap.parse_args()
     if args.child:
-        print("RESULT " + json.dumps(child(json.loads(args.child))), flush=True)
+        mc.emit_result(child(json.loads(args.child)))
         return
     import torch
     if not torch.cuda.is_available():
         sys.exit("tools/measure_arena.py needs a GPU")
     out = {"tool": "tools/measure_arena.py", "net": f"{CHANNELS}x{BLOCKS}", "policy_gain": GAIN, "simulations": args.sims,
            "max_game_length": args.max_game_length, "seed": args.seed, "runs": []}
-    for part in args.parts:
-        for job in JOBS[part]:
-            job = dict(job, sims=args.sims, max_game_length=args.max_game_length, seed=args.seed)
-            t0 = time.time()
-            cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", json.dumps(job)]
-            r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-            line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
-            if r.returncode != 0 or line is None:
-                print(r.stdout[-3000:], file=sys.stderr)
-                print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
-                out["failed"] = dict(job=job, exit=r.returncode)
-                break
-            for row in json.loads(line[7:]):
-                print(json.dumps(row), flush=True)
-                out["runs"].append(row)
-            out["runs"][-1]["child_wall_s"] = round(time.time() - t0, 1)
-        if "failed" in out:
-            break
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    jobs = [dict(job, sims=args.sims, max_game_length=args.max_game_length, seed=args.seed)
+            for part in args.parts for job in JOBS[part]]
+    sys.exit(0 if mc.run_children(__file__, jobs, args.timeout, out, args.out) else 1)
 
 
 if __name__ == "__main__":

@@ -13,32 +13,21 @@ at a hit rate of 0.  --games adds complete games through run_games (games/hour, 
 """
 import argparse
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import measure_common as mc
+from measure_common import GAINS
+
+sys.path.insert(0, mc.ROOT)
 CONFIGS = {1: dict(slots=1024, sims=400, channels=128, blocks=6), 2: dict(slots=8192, sims=800, channels=256, blocks=10)}
-GAINS = {"random": 1.0, "peaked": 8.0}
 
 
-class Cfg:                                      # "full" preset of training/train.py:692-704
-    c_puct = 1.5
-    temperature_threshold = 20
-    max_game_length = 400
-    random_opening_moves = 8
-    enable_resign = True
-    resign_threshold = -0.9
-    resign_check_steps = 5
+def _cfg(c):                                    # cfg1's game settings ("full" preset of training/train.py:692-704) at c's simulations
+    return mc.selfplay_config(dict(mc.PRESETS["cfg1"], sims=c["sims"]))
 
 
 def _net(c, weights_name):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(c["channels"], c["blocks"])
-    net.load_state_dict(weights.make_state_dict(c["channels"], c["blocks"], policy_gain=GAINS[weights_name]))
-    return net
+    return mc.make_net(c["channels"], c["blocks"], GAINS[weights_name])
 
 
 def child_steps(job):
@@ -47,7 +36,7 @@ def child_steps(job):
     from xiangqi_alphazero_amd import engine, evaluator, hip
     c = CONFIGS[job["config"]]
     ev, ev_name = evaluator.make_evaluator(_net(c, job["weights"]), "cuda", "hip")
-    cfg = Cfg()
+    cfg = _cfg(c)
     ecfg = engine.make_config(c["slots"], c["sims"], c_puct=cfg.c_puct, temperature_threshold=cfg.temperature_threshold,
                               max_game_length=cfg.max_game_length, random_opening_moves=cfg.random_opening_moves,
                               enable_resign=cfg.enable_resign, resign_threshold=cfg.resign_threshold,
@@ -96,8 +85,7 @@ def child_games(job):
     import torch
     from xiangqi_alphazero_amd import engine, selfplay
     c = CONFIGS[job["config"]]
-    cfg = Cfg()
-    cfg.num_simulations = c["sims"]
+    cfg = _cfg(c)
     K = engine.recommended_cache_entries(c["sims"]) if job["mode"] == "on" else 0
     samples, results, st, elapsed = selfplay.run_games(_net(c, job["weights"]), cfg, c["slots"], "cuda", n_slots=c["slots"],
                                                        seed=11, poll_every=256, eval_cache_entries=K)
@@ -125,7 +113,7 @@ def main():
     args = ap.parse_args()
     if args.child:
         job = json.loads(args.child)
-        print("RESULT " + json.dumps(child_games(job) if job.get("kind") == "games" else child_steps(job)), flush=True)
+        mc.emit_result(child_games(job) if job.get("kind") == "games" else child_steps(job))
         return
     steps = args.steps or (2000 if args.config == 1 else 200)
     jobs = []
@@ -141,24 +129,7 @@ def main():
     options = dict(config=args.config, games=args.games, warm_moves=args.warm_moves, steps=steps, reps=args.reps)
     out = {"tool": "tools/measure_eval_cache.py", "options": options, "config": dict(CONFIGS[args.config], name=args.config),
            "runs": []}
-    for job in jobs:
-        t0 = time.time()
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", json.dumps(job)]
-        p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        line = next((l for l in p.stdout.splitlines() if l.startswith("RESULT ")), None)
-        if p.returncode != 0 or line is None:
-            print(p.stdout[-3000:], file=sys.stderr)
-            print(f"child failed (exit {p.returncode}) on {job}: stopping", file=sys.stderr)
-            out["failed"] = dict(job=job, exit=p.returncode)
-            break
-        r = json.loads(line[7:])
-        r["child_wall_s"] = round(time.time() - t0, 1)
-        print(json.dumps(r), flush=True)
-        out["runs"].append(r)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    sys.exit(0 if mc.run_children(__file__, jobs, args.timeout, out, args.out) else 1)
 
 
 if __name__ == "__main__":

@@ -37,40 +37,21 @@ Whether a network trained from such games is stronger is NOT measured here: that
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PEAKED_GAIN = 8.0
-PRESETS = {
-    "cfg1": dict(slots=1024, games=1024, sims=400, channels=128, blocks=6, temperature_threshold=20, max_game_length=400,
-                 random_opening_moves=8),
-    "small": dict(slots=256, games=256, sims=64, channels=64, blocks=2, temperature_threshold=20, max_game_length=120,
-                  random_opening_moves=6),
-}
+import measure_common as mc
+from measure_common import ROOT
 
-
-def _net(channels, blocks, peaked=True, seed=0):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(channels, blocks)
-    kw = dict(policy_gain=PEAKED_GAIN) if peaked else {}
-    net.load_state_dict(weights.make_state_dict(channels, blocks, seed=seed, **kw))
-    return net
+PRESETS = {k: mc.PRESETS[k] for k in ("cfg1", "small")}
 
 
 def child_a(job):
     import torch
-    from xiangqi_alphazero_amd import engine, evaluator, selfplay
+    from xiangqi_alphazero_amd import selfplay
     p = PRESETS[job["preset"]]
     on = job["mirror"] == "on"
-    net = _net(p["channels"], p["blocks"])
-    cfg = types.SimpleNamespace(num_simulations=p["sims"], c_puct=1.5, temperature_threshold=p["temperature_threshold"],
-                                max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
-                                enable_resign=True, resign_threshold=-0.9, resign_check_steps=5)
-    if on:
-        cfg.eval_random_mirror = True                  # through the config key, as a training loop sets it
+    net = mc.make_net(p["channels"], p["blocks"])
+    cfg = mc.selfplay_config(p, **({"eval_random_mirror": True} if on else {}))   # the config key, as a training loop sets it
     samples, results, st, elapsed = selfplay.run_games(net, cfg, p["games"], "cuda", n_slots=p["slots"], seed=11, poll_every=256)
     torch.cuda.synchronize()
     assert bool(st.get("eval_mirror", False)) == on and int(st["overflow"]) == 0
@@ -80,9 +61,7 @@ def child_a(job):
            "moves": int(st["moves_played"]), "sims": int(st["sims"]), "steps": int(st["steps"]),
            "rows_evaluated": int(st["rows_evaluated"])}
     # the replayed step from a staggered start: one graph launch per step between two device events
-    ev = evaluator.make_evaluator(net, "cuda", "hip")[0]
-    ecfg = engine.make_config(p["slots"], p["sims"], seed=5, start_stagger=True, max_out_samples=p["slots"] * 16)
-    eng = engine.SelfPlayEngine(ecfg, evaluator=ev, **({"eval_mirror": True} if on else {}))
+    eng = mc.staggered_engine(p, net, **({"eval_mirror": True} if on else {}))
     assert eng.capture_step() and eng.launch_mode == "graph"
     steps, warm, chunk = int(job["step_steps"]), 64, 100
     for _ in range(warm):
@@ -118,7 +97,7 @@ def child_b(job):
     moves, counts, _, _ = hip.movegen(boards, sides)
     counts = counts.to(torch.int32)
     mx, mmoves = hip.mirror_requests(x, moves, counts, torch.ones(len(x), dtype=torch.uint8, device="cuda"))
-    net = _net(job["channels"], job["blocks"], peaked=job["weights"] == "peaked")
+    net = mc.make_net(job["channels"], job["blocks"], mc.GAINS[job["weights"]])
     ev = evaluator.make_evaluator(net, "cuda", "hip")[0]
     ll, v = (t.clone().double() for t in ev.evaluate_legal(x, moves, counts))
     mll, mv = (t.clone().double() for t in ev.evaluate_legal(mx, mmoves, counts))
@@ -135,18 +114,10 @@ def child_b(job):
 
 
 def child_steps(job):
-    import torch
-    from xiangqi_alphazero_amd import engine, evaluator
     p = PRESETS[job["preset"]]
     on = job["mirror"] == "on"
-    ev = evaluator.make_evaluator(_net(p["channels"], p["blocks"]), "cuda", "hip")[0]
-    cfg = engine.make_config(p["slots"], p["sims"], seed=5, start_stagger=True, max_out_samples=p["slots"] * 64)
-    eng = engine.SelfPlayEngine(cfg, evaluator=ev, **({"eval_mirror": True} if on else {}))
-    for i in range(int(job["steps"])):
-        eng.step()
-        if i % 256 == 255:
-            eng.drain_device()
-    torch.cuda.synchronize()
+    eng = mc.staggered_engine(p, out_rows_per_slot=64, **({"eval_mirror": True} if on else {}))
+    mc.replay_steps(eng, int(job["steps"]))                      # eager: no step is captured here
     st = eng.stats()
     assert int(st["overflow"]) == 0
     return {"eval_mirror": on, "steps": int(job["steps"]), "rows_evaluated": int(st["rows_evaluated"]), "slots": p["slots"],
@@ -156,24 +127,8 @@ def child_steps(job):
 CHILDREN = {"a": child_a, "b": child_b, "steps": child_steps}
 
 
-def _group(rows, key):
-    v = [r[key] for r in rows]
-    return {"runs": v, "min": min(v), "max": max(v), "mean": round(sum(v) / len(v), 3), "spread": round(max(v) - min(v), 3)}
-
-
-def _run_child(job, cwd, timeout):
-    t0 = time.time()
-    cmd = ["timeout", "-k", "10", str(timeout), sys.executable, os.path.abspath(__file__), job["mode"], "--child", json.dumps(job)]
-    r = subprocess.run(cmd, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
-    if r.returncode != 0 or line is None:
-        print(r.stdout[-3000:], file=sys.stderr)
-        print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
-        return None, r.returncode
-    row = json.loads(line[7:])
-    row["child_wall_s"] = round(time.time() - t0, 1)
-    print(json.dumps(row), flush=True)
-    return row, 0
+def summarise(out, job, row):
+    mc.parent_this_summary(out, ("games_per_hour", "step_us_mean", "step_us_median"))
 
 
 def main():
@@ -193,7 +148,7 @@ def main():
     if args.child:
         job = json.loads(args.child)
         sys.path.insert(0, job["tree_path"])
-        print("RESULT " + json.dumps(CHILDREN[args.mode](job)), flush=True)
+        mc.emit_result(CHILDREN[args.mode](job))
         return
     out = {"tool": "tools/measure_eval_mirror.py", "mode": args.mode, "runs": []}
     if args.mode == "a":
@@ -208,29 +163,11 @@ def main():
                 for w in ("random", "peaked")]
     else:
         jobs = [dict(mode="steps", tree="this", tree_path=ROOT, preset=args.preset, mirror=args.mirror, steps=args.steps)]
-    for job in jobs:
-        row, rc = _run_child(job, job["tree_path"], args.timeout)
-        if row is None:
-            out["failed"] = dict(job=job, exit=rc)
-            break
-        out["runs"].append(row)
-        if args.mode == "a":
-            out["order"].append(job["tree"])
-    if args.mode == "a":
-        par, this = [r for r in out["runs"] if r["tree"] == "parent"], [r for r in out["runs"] if r["tree"] == "this"]
-        if par and this:
-            out["summary"] = {}
-            for key in ("games_per_hour", "step_us_mean", "step_us_median"):
-                p, t = _group(par, key), _group(this, key)
-                out["summary"][key] = {"parent_off": p, "this_on": t, "delta_of_means": round(t["mean"] - p["mean"], 3),
-                                       "margin_parent_spread": p["spread"],
-                                       "within_margin": abs(t["mean"] - p["mean"]) <= p["spread"]}
-            print(json.dumps(out["summary"], indent=1))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    ok = mc.run_children(__file__, jobs, args.timeout, out, args.out, argv=lambda job: [job["mode"]],
+                         cwd=lambda job: job["tree_path"], after_each=summarise if args.mode == "a" else None)
+    if "summary" in out:
+        print(json.dumps(out["summary"], indent=1))
+    sys.exit(0 if ok else 1)
 
 
 if __name__ == "__main__":

@@ -19,32 +19,14 @@ instance the same engine launches without the option: the comparison figure) and
 """
 import argparse
 import json
-import os
-import subprocess
 import sys
-import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-GAINS = {"random": 1.0, "peaked": 8.0}
-PRESETS = {
-    "cfg1": dict(slots=1024, games=1024, sims=400, channels=128, blocks=6, temperature_threshold=20, max_game_length=400,
-                 random_opening_moves=8),
-    "standard_train": dict(slots=20, games=20, sims=200, channels=128, blocks=6, temperature_threshold=20, max_game_length=300,
-                           random_opening_moves=6),
-    "small": dict(slots=256, games=256, sims=64, channels=64, blocks=2, temperature_threshold=20, max_game_length=120,
-                  random_opening_moves=6),
-}
+import measure_common as mc
+from measure_common import GAINS, PRESETS
+
+sys.path.insert(0, mc.ROOT)
 MODES = ("off", "on", "cap", "cap+on")
 K_FORCED, CAP_PROB = 2.0, 0.25
-
-
-def _net(channels, blocks, gain):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(channels, blocks)
-    net.load_state_dict(weights.make_state_dict(channels, blocks, policy_gain=gain))
-    return net
 
 
 def child_games(job):
@@ -53,14 +35,11 @@ def child_games(job):
     from xiangqi_alphazero_amd import selfplay
     p = PRESETS[job["preset"]]
     S = p["sims"]
-    cfg = types.SimpleNamespace(num_simulations=S, c_puct=1.5, temperature_threshold=p["temperature_threshold"],
-                                max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
-                                enable_resign=True, resign_threshold=-0.9, resign_check_steps=5)
     cap = (CAP_PROB, max(1, S // 4)) if job["mode"].startswith("cap") else None
     forced = K_FORCED if job["mode"].endswith("on") else None
-    samples, results, st, elapsed = selfplay.run_games(_net(p["channels"], p["blocks"], GAINS[job["weights"]]), cfg, p["games"],
-                                                       "cuda", n_slots=p["slots"], seed=11, poll_every=64 if p["slots"] < 64 else 256,
-                                                       playout_cap=cap, forced_playouts=forced)
+    samples, results, st, elapsed = selfplay.run_games(mc.make_net(p["channels"], p["blocks"], GAINS[job["weights"]]),
+                                                       mc.selfplay_config(p), p["games"], "cuda", n_slots=p["slots"], seed=11,
+                                                       poll_every=mc.poll_every(p), playout_cap=cap, forced_playouts=forced)
     torch.cuda.synchronize()
     moves = int(st["moves_played"])
     full = moves - int(st["fast_moves"])
@@ -82,25 +61,10 @@ def child_games(job):
 
 
 def trace(preset, forced, steps, with_cap):
-    import torch
-    from xiangqi_alphazero_amd import engine, evaluator
     c = PRESETS[preset]
-    ev = evaluator.make_evaluator(_net(c["channels"], c["blocks"], GAINS["peaked"]), "cuda", "hip")[0]
-    cfg = engine.make_config(c["slots"], c["sims"], seed=5, start_stagger=True, max_out_samples=c["slots"] * 16)
-    eng = engine.SelfPlayEngine(cfg, evaluator=ev, forced_playouts=forced if forced > 0 else None,
-                                playout_cap=(CAP_PROB, max(1, c["sims"] // 4)) if with_cap else None)
-    assert eng.capture_step()
-    t0 = time.time()
-    for i in range(steps):
-        eng.step()
-        if i % 256 == 255:
-            eng.drain_device()
-    torch.cuda.synchronize()
-    st = eng.stats()
-    print(json.dumps({"preset": preset, "k": eng.forced_playouts, "playout_cap": eng.playout_cap, "steps": eng.steps,
-                      "launch": eng.launch_mode, "wall_s": round(time.time() - t0, 1), "moves": st["moves_played"],
-                      "sims": st["sims"], "forced_sims": st["forced_sims"], "pruned_visits": st["pruned_visits"],
-                      "overflow": st["overflow"]}), flush=True)
+    kw = dict(forced_playouts=forced if forced > 0 else None, playout_cap=(CAP_PROB, max(1, c["sims"] // 4)) if with_cap else None)
+    mc.trace(c, steps, kw, lambda eng, st: {"preset": preset, "k": eng.forced_playouts, "playout_cap": eng.playout_cap,
+                                            "forced_sims": st["forced_sims"], "pruned_visits": st["pruned_visits"]})
 
 
 def main():
@@ -120,30 +84,12 @@ def main():
         trace(args.preset, args.forced, args.steps, args.cap)
         return
     if args.child:
-        print("RESULT " + json.dumps(child_games(json.loads(args.child))), flush=True)
+        mc.emit_result(child_games(json.loads(args.child)))
         return
     p = PRESETS[args.preset]
     jobs = [dict(preset=args.preset, weights=w, mode=m) for w in args.weights for m in args.modes]   # off / on alternate
     out = {"tool": "tools/measure_forced_playouts.py", "preset": dict(p, name=args.preset), "k": K_FORCED, "runs": []}
-    for job in jobs:
-        t0 = time.time()
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "games", "--child", json.dumps(job)]
-        r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
-        if r.returncode != 0 or line is None:
-            print(r.stdout[-3000:], file=sys.stderr)
-            print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
-            out["failed"] = dict(job=job, exit=r.returncode)
-            break
-        row = json.loads(line[7:])
-        row["child_wall_s"] = round(time.time() - t0, 1)
-        print(json.dumps(row), flush=True)
-        out["runs"].append(row)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    sys.exit(0 if mc.run_children(__file__, jobs, args.timeout, out, args.out, argv=lambda job: ["games"]) else 1)
 
 
 if __name__ == "__main__":

@@ -23,37 +23,13 @@ formula: the share of the target's mass that lies on unvisited children.
 """
 import argparse
 import json
-import os
-import subprocess
 import sys
-import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-GAINS = {"random": 1.0, "peaked": 8.0}
-PRESETS = {
-    "cfg1": dict(slots=1024, games=1024, sims=400, channels=128, blocks=6, temperature_threshold=20, max_game_length=400,
-                 random_opening_moves=8),
-    "standard_train": dict(slots=20, games=20, sims=200, channels=128, blocks=6, temperature_threshold=20, max_game_length=300,
-                           random_opening_moves=6),
-    "small": dict(slots=256, games=256, sims=64, channels=64, blocks=2, temperature_threshold=20, max_game_length=120,
-                  random_opening_moves=6),
-}
+import measure_common as mc
+from measure_common import GAINS, PRESETS
+
+sys.path.insert(0, mc.ROOT)
 M, C_VISIT, C_SCALE = 16, 50.0, 1.0
-
-
-def _net(channels, blocks, gain):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(channels, blocks)
-    net.load_state_dict(weights.make_state_dict(channels, blocks, policy_gain=gain))
-    return net
-
-
-def _config(p, sims):
-    return types.SimpleNamespace(num_simulations=sims, c_puct=1.5, temperature_threshold=p["temperature_threshold"],
-                                 max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
-                                 enable_resign=True, resign_threshold=-0.9, resign_check_steps=5)
 
 
 def _mode(mode, preset_sims):
@@ -69,9 +45,9 @@ def child_games(job):
     from xiangqi_alphazero_amd import selfplay
     p = PRESETS[job["preset"]]
     gumbel, S = _mode(job["mode"], p["sims"])
-    samples, results, st, elapsed = selfplay.run_games(_net(p["channels"], p["blocks"], GAINS[job["weights"]]), _config(p, S),
-                                                       p["games"], "cuda", n_slots=p["slots"], seed=11,
-                                                       poll_every=64 if p["slots"] < 64 else 256, gumbel=gumbel)
+    samples, results, st, elapsed = selfplay.run_games(mc.make_net(p["channels"], p["blocks"], GAINS[job["weights"]]),
+                                                       mc.selfplay_config(p, num_simulations=S), p["games"], "cuda",
+                                                       n_slots=p["slots"], seed=11, poll_every=mc.poll_every(p), gumbel=gumbel)
     torch.cuda.synchronize()
     moves, gm = int(st["moves_played"]), int(st["gumbel_moves"])
     return {"preset": job["preset"], "weights": job["weights"], "mode": job["mode"], "gumbel": st["gumbel"], "sims_per_move": S,
@@ -94,10 +70,10 @@ def shape(preset, sims, weights, positions):
     import torch
     from xiangqi_alphazero_amd import engine, evaluator, selfplay
     p = PRESETS[preset]
-    net = _net(p["channels"], p["blocks"], GAINS[weights])
+    net = mc.make_net(p["channels"], p["blocks"], GAINS[weights])
     gumbel = (M, C_VISIT, C_SCALE)
-    samples, results, st, _ = selfplay.run_games(net, _config(p, sims), p["games"], "cuda", n_slots=p["slots"], seed=11,
-                                                 gumbel=gumbel)
+    samples, results, st, _ = selfplay.run_games(net, mc.selfplay_config(p, num_simulations=sims), p["games"], "cuda",
+                                                 n_slots=p["slots"], seed=11, gumbel=gumbel)
     pick = samples[np.linspace(0, len(samples) - 1, min(positions, len(samples))).astype(np.int64)]
     ev = evaluator.make_evaluator(net, "cuda", "hip")[0]
     eng = engine.SelfPlayEngine(engine.make_config(len(pick), sims, seed=23, manual_moves=1), evaluator=ev, gumbel=gumbel)
@@ -140,23 +116,8 @@ def shape(preset, sims, weights, positions):
 
 
 def trace(preset, m, steps):
-    import torch
-    from xiangqi_alphazero_amd import engine, evaluator
-    c = PRESETS[preset]
-    ev = evaluator.make_evaluator(_net(c["channels"], c["blocks"], GAINS["peaked"]), "cuda", "hip")[0]
-    cfg = engine.make_config(c["slots"], c["sims"], seed=5, start_stagger=True, max_out_samples=c["slots"] * 16)
-    eng = engine.SelfPlayEngine(cfg, evaluator=ev, gumbel=(m, C_VISIT, C_SCALE) if m > 0 else None)
-    assert eng.capture_step()
-    t0 = time.time()
-    for i in range(steps):
-        eng.step()
-        if i % 256 == 255:
-            eng.drain_device()
-    torch.cuda.synchronize()
-    st = eng.stats()
-    print(json.dumps({"preset": preset, "gumbel": eng.gumbel, "steps": eng.steps, "launch": eng.launch_mode,
-                      "wall_s": round(time.time() - t0, 1), "moves": st["moves_played"], "sims": st["sims"],
-                      "gumbel_moves": st["gumbel_moves"], "overflow": st["overflow"]}), flush=True)
+    mc.trace(PRESETS[preset], steps, dict(gumbel=(m, C_VISIT, C_SCALE) if m > 0 else None),
+             lambda eng, st: {"preset": preset, "gumbel": eng.gumbel, "gumbel_moves": st["gumbel_moves"]})
 
 
 def main():
@@ -179,7 +140,7 @@ def main():
     if args.child:
         job = json.loads(args.child)
         row = shape(job["preset"], job["sims"], job["weights"], job["positions"]) if job.get("shape") else child_games(job)
-        print("RESULT " + json.dumps(row), flush=True)
+        mc.emit_result(row)
         return
     p = PRESETS[args.preset]
     if args.part == "shape":
@@ -188,25 +149,7 @@ def main():
         jobs = [dict(preset=args.preset, weights=args.weights, mode=m) for m in args.modes]
     out = {"tool": "tools/measure_gumbel.py", "part": args.part, "preset": dict(p, name=args.preset),
            "gumbel": [M, C_VISIT, C_SCALE], "runs": []}
-    for job in jobs:
-        t0 = time.time()
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), args.part, "--child", json.dumps(job)]
-        r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
-        if r.returncode != 0 or line is None:
-            print(r.stdout[-3000:], file=sys.stderr)
-            print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
-            out["failed"] = dict(job=job, exit=r.returncode)
-            break
-        row = json.loads(line[7:])
-        row["child_wall_s"] = round(time.time() - t0, 1)
-        print(json.dumps(row), flush=True)
-        out["runs"].append(row)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    sys.exit(0 if mc.run_children(__file__, jobs, args.timeout, out, args.out, argv=lambda job: [args.part]) else 1)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """How many records of a real replay buffer are duplicates of one position, and what merging them costs, measured on the GPU.
 Everything runs in one fresh child process under `timeout -k` (the games are played once and every figure is taken over the same
-samples); the output file is rewritten after every stage, so a measurement cut short keeps what it has.
+samples); the child rewrites the output file after every stage, so a measurement cut short keeps what it has.
 
     python tools/measure_merge_duplicates.py --preset cfg1 --parent-lib <libxq_hip.so built from the parent commit> \\
         --out profiles/r20_merge_duplicates_cfg1.json
@@ -29,44 +29,29 @@ import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 import time
 import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PEAKED_GAIN = 8.0
+import measure_common as mc
+from measure_common import ROOT
+
+PEAKED_GAIN = mc.GAINS["peaked"]
 BATCH = 256
-PRESETS = {
-    "cfg1": dict(slots=1024, games=1024, sims=400, channels=128, blocks=6, temperature_threshold=20, max_game_length=400,
-                 random_opening_moves=8),
-    "small": dict(slots=64, games=64, sims=32, channels=64, blocks=2, temperature_threshold=20, max_game_length=60,
-                  random_opening_moves=6),
-}
+PRESETS = {"cfg1": mc.PRESETS["cfg1"], "small": dict(mc.PRESETS["small"], slots=64, games=64, sims=32, max_game_length=60)}
 PLY_BUCKETS = [(i, i + 1) for i in range(10)] + [(10, 20), (20, 40), (40, 80), (80, 1 << 16)]
-
-
-def _net(channels, blocks, seed=0):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(channels, blocks)
-    net.load_state_dict(weights.make_state_dict(channels, blocks, seed=seed, policy_gain=PEAKED_GAIN))
-    return net
 
 
 def _play(p, seed=11):
     from xiangqi_alphazero_amd import selfplay
-    cfg = types.SimpleNamespace(num_simulations=p["sims"], c_puct=1.5, temperature_threshold=p["temperature_threshold"],
-                                max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
-                                enable_resign=True, resign_threshold=-0.9, resign_check_steps=5)
-    net = _net(p["channels"], p["blocks"])
-    samples, results, st, elapsed = selfplay.run_games(net, cfg, p["games"], "cuda", n_slots=p["slots"], seed=seed,
-                                                       poll_every=64 if p["slots"] < 64 else 256, device_records=True)
+    samples, results, st, elapsed = selfplay.run_games(mc.make_net(p["channels"], p["blocks"]), mc.selfplay_config(p), p["games"],
+                                                       "cuda", n_slots=p["slots"], seed=seed, poll_every=mc.poll_every(p),
+                                                       device_records=True)
     return samples, results, elapsed
 
 
 def _group(runs):
-    return {"runs": [round(x, 4) for x in runs], "min": round(min(runs), 4), "max": round(max(runs), 4),
-            "spread": round(max(runs) - min(runs), 4), "mean": round(sum(runs) / len(runs), 4)}
+    return mc.group(runs, digits=4, round_values=True)
 
 
 def _events(fn, reps):
@@ -204,7 +189,7 @@ def stage_batch(buf, parent_lib, launches, runs, BATCH=BATCH, singletons_only=Fa
     if parent_lib:
         t, p = out["us_per_row"]["this_groups_to_batch_singletons"], out["us_per_row"]["parent_samples_to_batch_ex"]
         out["singletons_over_parent_mean"] = round(t["mean"] / p["mean"], 4)
-        out["this_mean_within_parent_spread"] = p["min"] <= t["mean"] <= p["max"]
+        out["this_mean_within_parent_spread"] = mc.within_spread(p, t)
     if singletons_only:
         return out
     real = buf.position_groups(True)
@@ -221,10 +206,8 @@ def stage_batch(buf, parent_lib, launches, runs, BATCH=BATCH, singletons_only=Fa
 
 def stage_train(buf, runs):
     import torch
-    from xiangqi_alphazero_amd import model, training, weights
-    net = model.XiangqiNet(128, 6)
-    net.load_state_dict(weights.make_state_dict(128, 6))
-    net = net.cuda()
+    from xiangqi_alphazero_amd import training
+    net = mc.make_net(128, 6, mc.GAINS["random"]).cuda()
     net.use_native_conv(True)
     opt = torch.optim.Adam(net.parameters(), lr=2e-3, weight_decay=1e-4, fused=True)
     sch = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=[5000], gamma=0.1)
@@ -255,12 +238,6 @@ def child(job):
     p = PRESETS[job["preset"]]
     out = {"tool": "tools/measure_merge_duplicates.py", "preset": job["preset"], "weights": "peaked (policy_gain %g)" % PEAKED_GAIN}
 
-    def save():
-        if job.get("out"):
-            os.makedirs(os.path.dirname(os.path.abspath(job["out"])), exist_ok=True)
-            with open(job["out"], "w") as f:
-                json.dump(out, f, indent=1)
-
     samples, results, elapsed = _play(p)
     torch.cuda.synchronize()
     out.update(games=int(results.shape[0]), records=int(samples.shape[0]), selfplay_wall_s=round(elapsed, 2),
@@ -277,7 +254,7 @@ def child(job):
         if name in job["stages"]:
             out[name] = fn()
             print(name, json.dumps(out[name]), flush=True)
-            save()
+            mc.save_json(out, job.get("out"))
     return out
 
 
@@ -298,15 +275,11 @@ def main():
         import torch
         if not torch.cuda.is_available():
             sys.exit("no GPU: nothing here is measured without one")
-        child(json.loads(args.child))
+        mc.emit_result(child(json.loads(args.child)))
         return
     job = dict(preset=args.preset, parent_lib=os.path.abspath(args.parent_lib) if args.parent_lib else None, stages=args.stages,
                reps=args.reps, launches=args.launches, runs=args.runs, out=os.path.abspath(args.out) if args.out else None)
-    cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", json.dumps(job)]
-    r = subprocess.run(cmd, cwd=ROOT)
-    if r.returncode != 0:
-        print(f"child failed (exit {r.returncode}): stopping", file=sys.stderr)
-    sys.exit(1 if r.returncode else 0)
+    sys.exit(0 if mc.run_children(__file__, [job], args.timeout, {}) else 1)       # the child writes --out itself, stage by stage
 
 
 if __name__ == "__main__":

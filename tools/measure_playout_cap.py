@@ -17,43 +17,27 @@ reuse.  Whether training gains from the trade is not measured here.
 """
 import argparse
 import json
-import os
-import subprocess
 import sys
-import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-GAINS = {"random": 1.0, "peaked": 8.0}
-PRESETS = {
-    "cfg1": dict(slots=1024, games=1024, sims=400, fast_sims=100, full_prob=0.25, channels=128, blocks=6,
-                 temperature_threshold=20, max_game_length=400, random_opening_moves=8),
-    "standard_train": dict(slots=20, games=20, sims=200, fast_sims=50, full_prob=0.25, channels=128, blocks=6,
-                           temperature_threshold=20, max_game_length=300, random_opening_moves=6),
-}
+import measure_common as mc
+from measure_common import GAINS
+
+sys.path.insert(0, mc.ROOT)
+# the common presets with the cap: p = 0.25, S_fast = S / 4
+PRESETS = {k: dict(mc.PRESETS[k], fast_sims=mc.PRESETS[k]["sims"] // 4, full_prob=0.25)
+           for k in ("cfg1", "standard_train")}
 MODES = ("off", "on", "reuse", "reuse+on")
-TRACE = dict(slots=1024, sims=400, fast_sims=100, full_prob=0.25, channels=128, blocks=6, steps=700)
-
-
-def _net(channels, blocks, gain):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(channels, blocks)
-    net.load_state_dict(weights.make_state_dict(channels, blocks, policy_gain=gain))
-    return net
+TRACE = dict(PRESETS["cfg1"], steps=700)
 
 
 def child_games(job):
     import torch
     from xiangqi_alphazero_amd import selfplay
     p = PRESETS[job["preset"]]
-    cfg = types.SimpleNamespace(num_simulations=p["sims"], c_puct=1.5, temperature_threshold=p["temperature_threshold"],
-                                max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
-                                enable_resign=True, resign_threshold=-0.9, resign_check_steps=5)
     cap = (p["full_prob"], p["fast_sims"]) if job["mode"].endswith("on") else None
-    samples, results, st, elapsed = selfplay.run_games(_net(p["channels"], p["blocks"], GAINS[job["weights"]]), cfg, p["games"],
-                                                       "cuda", n_slots=p["slots"], seed=11, poll_every=64 if p["slots"] < 64 else 256,
-                                                       tree_reuse=job["mode"].startswith("reuse"), playout_cap=cap)
+    samples, results, st, elapsed = selfplay.run_games(mc.make_net(p["channels"], p["blocks"], GAINS[job["weights"]]),
+                                                       mc.selfplay_config(p), p["games"], "cuda", n_slots=p["slots"], seed=11,
+                                                       poll_every=mc.poll_every(p), tree_reuse=job["mode"].startswith("reuse"), playout_cap=cap)
     torch.cuda.synchronize()
     moves = int(st["moves_played"])
     return {"preset": job["preset"], "weights": job["weights"], "mode": job["mode"], "path": st["path"], "launch": st["launch"],
@@ -68,23 +52,8 @@ def child_games(job):
 
 
 def trace():
-    import torch
-    from xiangqi_alphazero_amd import engine, evaluator
-    c = TRACE
-    ev = evaluator.make_evaluator(_net(c["channels"], c["blocks"], GAINS["peaked"]), "cuda", "hip")[0]
-    cfg = engine.make_config(c["slots"], c["sims"], seed=5, start_stagger=True, max_out_samples=c["slots"] * 16)
-    eng = engine.SelfPlayEngine(cfg, evaluator=ev, playout_cap=(c["full_prob"], c["fast_sims"]))
-    assert eng.capture_step()
-    t0 = time.time()
-    for i in range(c["steps"]):
-        eng.step()
-        if i % 256 == 255:
-            eng.drain_device()
-    torch.cuda.synchronize()
-    st = eng.stats()
-    print(json.dumps({"steps": eng.steps, "launch": eng.launch_mode, "wall_s": round(time.time() - t0, 1),
-                      "moves": st["moves_played"], "fast_moves": st["fast_moves"], "sims": st["sims"],
-                      "fast_sims": st["fast_sims"], "overflow": st["overflow"]}), flush=True)
+    mc.trace(TRACE, TRACE["steps"], dict(playout_cap=(TRACE["full_prob"], TRACE["fast_sims"])),
+             lambda eng, st: {"fast_moves": st["fast_moves"], "fast_sims": st["fast_sims"]})
 
 
 def main():
@@ -101,32 +70,14 @@ def main():
         trace()
         return
     if args.child:
-        print("RESULT " + json.dumps(child_games(json.loads(args.child))), flush=True)
+        mc.emit_result(child_games(json.loads(args.child)))
         return
     p = PRESETS[args.preset]
     jobs = [dict(preset=args.preset, weights=w, mode=m) for w in args.weights for m in args.modes]   # off / on alternate
     S, Sf, pf = p["sims"], p["fast_sims"], p["full_prob"]
     out = {"tool": "tools/measure_playout_cap.py", "preset": dict(p, name=args.preset),
            "steps_per_game_ratio_expected_without_reuse": round((pf * S + (1 - pf) * Sf + 1) / (S + 1), 4), "runs": []}
-    for job in jobs:
-        t0 = time.time()
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "games", "--child", json.dumps(job)]
-        r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
-        if r.returncode != 0 or line is None:
-            print(r.stdout[-3000:], file=sys.stderr)
-            print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
-            out["failed"] = dict(job=job, exit=r.returncode)
-            break
-        row = json.loads(line[7:])
-        row["child_wall_s"] = round(time.time() - t0, 1)
-        print(json.dumps(row), flush=True)
-        out["runs"].append(row)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    sys.exit(0 if mc.run_children(__file__, jobs, args.timeout, out, args.out, argv=lambda job: ["games"]) else 1)
 
 
 if __name__ == "__main__":

@@ -28,40 +28,24 @@ Whether a network trained with alpha > 0 is stronger is not measured here: that 
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PEAKED_GAIN = 8.0
+import measure_common as mc
+from measure_common import ROOT
+
+PEAKED_GAIN = mc.GAINS["peaked"]
 HBM_PEAK_TBS = 8.0
-PRESETS = {
-    "cfg1": dict(slots=1024, games=1024, sims=400, channels=128, blocks=6, temperature_threshold=20, max_game_length=400,
-                 random_opening_moves=8),
-    "standard_train": dict(slots=20, games=20, sims=200, channels=128, blocks=6, temperature_threshold=20, max_game_length=300,
-                           random_opening_moves=6),
-    "small": dict(slots=64, games=64, sims=32, channels=64, blocks=2, temperature_threshold=20, max_game_length=60,
-                  random_opening_moves=6),
-}
+PRESETS = dict(mc.PRESETS, small=dict(mc.PRESETS["small"], slots=64, games=64, sims=32, max_game_length=60))
 CHUNKS = (256, 1024, 4096)
-
-
-def _net(channels, blocks, seed=0):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(channels, blocks)
-    net.load_state_dict(weights.make_state_dict(channels, blocks, seed=seed, policy_gain=PEAKED_GAIN))
-    return net
 
 
 def _play(p, seed=11):
     from xiangqi_alphazero_amd import selfplay
-    cfg = types.SimpleNamespace(num_simulations=p["sims"], c_puct=1.5, temperature_threshold=p["temperature_threshold"],
-                                max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
-                                enable_resign=True, resign_threshold=-0.9, resign_check_steps=5)
-    net = _net(p["channels"], p["blocks"])
-    samples, results, st, elapsed = selfplay.run_games(net, cfg, p["games"], "cuda", n_slots=p["slots"], seed=seed,
-                                                       poll_every=64 if p["slots"] < 64 else 256, device_records=True)
+    net = mc.make_net(p["channels"], p["blocks"])
+    samples, results, st, elapsed = selfplay.run_games(net, mc.selfplay_config(p), p["games"], "cuda", n_slots=p["slots"],
+                                                       seed=seed, poll_every=mc.poll_every(p), device_records=True)
     return net, samples, results, st, elapsed
 
 
@@ -162,17 +146,13 @@ def child_kernels(job):
 
 def child_train(job):
     import torch
-    from xiangqi_alphazero_amd import model, selfplay, training, weights
-    cfg = types.SimpleNamespace(num_simulations=16, c_puct=1.5, temperature_threshold=20, max_game_length=120,
-                                random_opening_moves=8, enable_resign=False, resign_threshold=-0.9, resign_check_steps=5)
-    gen = model.XiangqiNet(64, 3)
-    gen.load_state_dict(weights.make_state_dict(64, 3))
-    samples, _, _, _ = selfplay.run_games(gen, cfg, 64, "cuda", seed=5)
+    from xiangqi_alphazero_amd import selfplay, training
+    cfg = mc.selfplay_config(dict(sims=16, temperature_threshold=20, max_game_length=120, random_opening_moves=8),
+                             enable_resign=False)
+    samples, _, _, _ = selfplay.run_games(mc.make_net(64, 3, mc.GAINS["random"]), cfg, 64, "cuda", seed=5)
     buf = training.ReplayBuffer(10 ** 6, "cuda")
     buf.extend(samples[:2048])
-    net = model.XiangqiNet(128, 6)
-    net.load_state_dict(weights.make_state_dict(128, 6))
-    net = net.cuda()
+    net = mc.make_net(128, 6, mc.GAINS["random"]).cuda()
     net.use_native_conv(True)
     opt = torch.optim.Adam(net.parameters(), lr=2e-3, weight_decay=1e-4, fused=True)
     sch = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=[50, 80], gamma=0.1)
@@ -193,9 +173,11 @@ def child_train(job):
 CHILDREN = {"pass": child_pass, "kernels": child_kernels, "train": child_train}
 
 
-def _group(runs):
-    return {"runs": runs, "min": min(runs), "max": max(runs), "spread": round(max(runs) - min(runs), 3),
-            "mean": round(sum(runs) / len(runs), 3)} if runs else None
+def summarise(out, job, row):
+    g = out["summary"] = {k: mc.group([x["samples_per_s"] for x in out["runs"] if x["kind"] == k]) for k in ("parent", "this")}
+    if g["parent"] and g["this"]:
+        g["this_within_parent_spread"] = mc.within_spread(g["parent"], g["this"])
+        g["this_over_parent_mean"] = round(g["this"]["mean"] / g["parent"]["mean"], 4)
 
 
 def main():
@@ -216,7 +198,7 @@ def main():
         import torch
         if not torch.cuda.is_available():
             sys.exit("no GPU: nothing here is measured without one")
-        print("RESULT " + json.dumps(CHILDREN[args.part](job)), flush=True)
+        mc.emit_result(CHILDREN[args.part](job))
         return
     if args.part == "train":
         if "parent" in args.runs and not args.parent_tree:
@@ -225,31 +207,9 @@ def main():
     else:
         jobs = [dict(preset=args.preset, rows=args.rows)]
     out = {"tool": "tools/measure_policy_surprise.py " + args.part, "weights": "peaked (policy_gain %g)" % PEAKED_GAIN, "runs": []}
-    for job in jobs:
-        t0 = time.time()
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), args.part, "--child", json.dumps(job)]
-        r = subprocess.run(cmd, cwd=job.get("tree") or ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        line = next((x for x in r.stdout.splitlines() if x.startswith("RESULT ")), None)
-        if r.returncode != 0 or line is None:
-            print(r.stdout[-3000:], file=sys.stderr)
-            print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
-            out["failed"] = dict(job=job, exit=r.returncode)
-            break
-        row = json.loads(line[7:])
-        row["child_wall_s"] = round(time.time() - t0, 1)
-        print(json.dumps(row), flush=True)
-        out["runs"].append(row)
-        if args.part == "train":
-            g = {k: _group([x["samples_per_s"] for x in out["runs"] if x["kind"] == k]) for k in ("parent", "this")}
-            out["summary"] = g
-            if g["parent"] and g["this"]:
-                out["summary"]["this_within_parent_spread"] = g["parent"]["min"] <= g["this"]["mean"] <= g["parent"]["max"]
-                out["summary"]["this_over_parent_mean"] = round(g["this"]["mean"] / g["parent"]["mean"], 4)
-        if args.out:                                     # after every run: a measurement cut short keeps what it has
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "w") as f:
-                json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    ok = mc.run_children(__file__, jobs, args.timeout, out, args.out, argv=lambda job: [args.part],
+                         cwd=lambda job: job.get("tree") or ROOT, after_each=summarise if args.part == "train" else None)
+    sys.exit(0 if ok else 1)
 
 
 if __name__ == "__main__":

@@ -28,27 +28,13 @@ Whether a network trained on the mixed target is stronger is NOT measured here: 
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PEAKED_GAIN = 8.0
-PRESETS = {
-    "cfg1": dict(slots=1024, games=1024, sims=400, channels=128, blocks=6, temperature_threshold=20, max_game_length=400,
-                 random_opening_moves=8),
-    "small": dict(slots=256, games=256, sims=64, channels=64, blocks=2, temperature_threshold=20, max_game_length=120,
-                  random_opening_moves=6),
-}
+import measure_common as mc
+from measure_common import ROOT
+
+PRESETS = {k: mc.PRESETS[k] for k in ("cfg1", "small")}
 BUCKETS = ((0, 20), (20, 40), (40, 80), (80, 120), (120, 1 << 16))
-
-
-def _net(channels, blocks, seed=0):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(channels, blocks)
-    net.load_state_dict(weights.make_state_dict(channels, blocks, seed=seed, policy_gain=PEAKED_GAIN))
-    return net
 
 
 def _ply_buckets(samples):
@@ -69,15 +55,11 @@ def _ply_buckets(samples):
 
 def child(job):
     import torch
-    from xiangqi_alphazero_amd import engine, evaluator, selfplay
+    from xiangqi_alphazero_amd import selfplay
     p = PRESETS[job["preset"]]
     on = job["root_stats"] == "on"
-    net = _net(p["channels"], p["blocks"])
-    cfg = types.SimpleNamespace(num_simulations=p["sims"], c_puct=1.5, temperature_threshold=p["temperature_threshold"],
-                                max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
-                                enable_resign=True, resign_threshold=-0.9, resign_check_steps=5)
-    if on:
-        cfg.record_root_stats = True                   # through the config key, as a training loop sets it
+    net = mc.make_net(p["channels"], p["blocks"])
+    cfg = mc.selfplay_config(p, **({"record_root_stats": True} if on else {}))    # the config key, as a training loop sets it
     samples, results, st, elapsed = selfplay.run_games(net, cfg, p["games"], "cuda", n_slots=p["slots"], seed=11, poll_every=256)
     torch.cuda.synchronize()
     assert bool(st.get("root_stats", False)) == on and int(st["overflow"]) == 0
@@ -88,9 +70,7 @@ def child(job):
     if on:
         row["root_q_against_z"] = _ply_buckets(samples)
     # k_select alone: eager steps from a staggered start, the stages called one by one, events around the select launch
-    ev = evaluator.make_evaluator(net, "cuda", "hip")[0]
-    ecfg = engine.make_config(p["slots"], p["sims"], seed=5, start_stagger=True, max_out_samples=p["slots"] * 16)
-    eng = engine.SelfPlayEngine(ecfg, evaluator=ev, **({"root_stats": True} if on else {}))
+    eng = mc.staggered_engine(p, net, **({"root_stats": True} if on else {}))
     steps, warm = int(job["select_steps"]), 32
     pairs = []
     for i in range(warm + steps):
@@ -112,9 +92,10 @@ def child(job):
     return row
 
 
-def _group(rows, key):
-    v = [r[key] for r in rows]
-    return {"runs": v, "min": min(v), "max": max(v), "mean": round(sum(v) / len(v), 3), "spread": round(max(v) - min(v), 3)}
+def summarise(out, job, row):
+    mc.parent_this_summary(out, ("games_per_hour", "k_select_us_mean", "k_select_us_median"))
+    if "summary" in out:
+        out["summary"]["root_q_against_z"] = [r for r in out["runs"] if r["tree"] == "this"][-1].get("root_q_against_z")
 
 
 def main():
@@ -130,47 +111,19 @@ def main():
     if args.child:
         job = json.loads(args.child)
         sys.path.insert(0, job["tree_path"])
-        print("RESULT " + json.dumps(child(job)), flush=True)
+        mc.emit_result(child(job))
         return
     if not args.parent_tree or not os.path.isdir(os.path.join(args.parent_tree, "xiangqi-alphazero_amd")):
         sys.exit("--parent-tree: a built checkout of the parent commit is required (the `off` runs are taken on it)")
     trees = {"parent": os.path.abspath(args.parent_tree), "this": ROOT}
     out = {"tool": "tools/measure_root_stats.py", "preset": dict(PRESETS[args.preset], name=args.preset), "weights": "peaked",
            "order": [], "runs": []}
-    for _ in range(args.repeats):
-        for tree, rs in (("parent", "off"), ("this", "on")):
-            job = dict(preset=args.preset, tree=tree, tree_path=trees[tree], root_stats=rs, select_steps=args.select_steps)
-            t0 = time.time()
-            cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", json.dumps(job)]
-            r = subprocess.run(cmd, cwd=trees[tree], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-            line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
-            if r.returncode != 0 or line is None:
-                print(r.stdout[-3000:], file=sys.stderr)
-                print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
-                out["failed"] = dict(job=job, exit=r.returncode)
-                break
-            row = json.loads(line[7:])
-            row["child_wall_s"] = round(time.time() - t0, 1)
-            print(json.dumps(row), flush=True)
-            out["order"].append(tree)
-            out["runs"].append(row)
-        if "failed" in out:
-            break
-    par, this = [r for r in out["runs"] if r["tree"] == "parent"], [r for r in out["runs"] if r["tree"] == "this"]
-    if par and this:
-        out["summary"] = {}
-        for key in ("games_per_hour", "k_select_us_mean", "k_select_us_median"):
-            p, t = _group(par, key), _group(this, key)
-            out["summary"][key] = {"parent_off": p, "this_on": t, "delta_of_means": round(t["mean"] - p["mean"], 3),
-                                   "margin_parent_spread": p["spread"],
-                                   "within_margin": abs(t["mean"] - p["mean"]) <= p["spread"]}
-        out["summary"]["root_q_against_z"] = this[-1].get("root_q_against_z")
+    jobs = [dict(preset=args.preset, tree=tree, tree_path=trees[tree], root_stats=rs, select_steps=args.select_steps)
+            for _ in range(args.repeats) for tree, rs in (("parent", "off"), ("this", "on"))]
+    ok = mc.run_children(__file__, jobs, args.timeout, out, args.out, cwd=lambda job: job["tree_path"], after_each=summarise)
+    if "summary" in out:
         print(json.dumps(out["summary"], indent=1))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    sys.exit(0 if ok else 1)
 
 
 if __name__ == "__main__":

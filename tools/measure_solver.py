@@ -21,45 +21,24 @@ on alternated, one seed): the result tables, the steps each arena took and the o
 comparison) and writes k_select's mean time per launch of every run with each group's own run-to-run spread.
 """
 import argparse
-import csv
 import json
-import os
-import subprocess
 import sys
 import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-PEAKED_GAIN = 8.0
-PRESETS = {
-    "cfg1": dict(slots=1024, games=1024, sims=400, channels=128, blocks=6, temperature_threshold=20, max_game_length=400,
-                 random_opening_moves=8),
-    "standard_train": dict(slots=20, games=20, sims=200, channels=128, blocks=6, temperature_threshold=20, max_game_length=300,
-                           random_opening_moves=6),
-    "small": dict(slots=256, games=256, sims=64, channels=64, blocks=2, temperature_threshold=20, max_game_length=120,
-                  random_opening_moves=6),
-}
+import measure_common as mc
+from measure_common import PRESETS
+
+sys.path.insert(0, mc.ROOT)
 SOLVER_KEYS = ("proven_nodes", "proven_stops", "proven_moves", "unspent_sims", "removed_visits")
-
-
-def _net(channels, blocks, seed=0):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(channels, blocks)
-    net.load_state_dict(weights.make_state_dict(channels, blocks, seed=seed, policy_gain=PEAKED_GAIN))
-    return net
 
 
 def child_games(job):
     import torch
     from xiangqi_alphazero_amd import selfplay
     p = PRESETS[job["preset"]]
-    cfg = types.SimpleNamespace(num_simulations=p["sims"], c_puct=1.5, temperature_threshold=p["temperature_threshold"],
-                                max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
-                                enable_resign=True, resign_threshold=-0.9, resign_check_steps=5,
-                                mcts_solver=job["solver"] == "on")               # through the config key, as a training loop sets it
-    samples, results, st, elapsed = selfplay.run_games(_net(p["channels"], p["blocks"]), cfg, p["games"], "cuda", n_slots=p["slots"],
-                                                       seed=11, poll_every=64 if p["slots"] < 64 else 256)
+    cfg = mc.selfplay_config(p, mcts_solver=job["solver"] == "on")             # through the config key, as a training loop sets it
+    samples, results, st, elapsed = selfplay.run_games(mc.make_net(p["channels"], p["blocks"]), cfg, p["games"], "cuda",
+                                                       n_slots=p["slots"], seed=11, poll_every=mc.poll_every(p))
     torch.cuda.synchronize()
     moves = max(int(st["moves_played"]), 1)
     return {"preset": job["preset"], "solver": bool(st["solver"]), "path": st["path"], "launch": st["launch"],
@@ -78,8 +57,8 @@ def child_arena(job):
     from xiangqi_alphazero_amd import arena, evaluator
     p = PRESETS[job["preset"]]
     games = max(2, p["games"] - p["games"] % 2)
-    en = evaluator.make_evaluator(_net(p["channels"], p["blocks"], seed=1), "cuda", "hip")[0]
-    eo = evaluator.make_evaluator(_net(p["channels"], p["blocks"], seed=2), "cuda", "hip")[0]
+    en = evaluator.make_evaluator(mc.make_net(p["channels"], p["blocks"], seed=1), "cuda", "hip")[0]
+    eo = evaluator.make_evaluator(mc.make_net(p["channels"], p["blocks"], seed=2), "cuda", "hip")[0]
     info = {}
     t0 = time.time()
     res = arena.play_arena(en, eo, games, p["sims"], p["max_game_length"], opening_plies=4, seed=17, info=info,
@@ -95,52 +74,17 @@ def child_arena(job):
 
 
 def trace(preset, solver, steps):
-    import torch
-    from xiangqi_alphazero_amd import engine, evaluator
-    c = PRESETS[preset]
-    ev = evaluator.make_evaluator(_net(c["channels"], c["blocks"]), "cuda", "hip")[0]
-    cfg = engine.make_config(c["slots"], c["sims"], seed=5, start_stagger=True, max_out_samples=c["slots"] * 16)
     kw = {"solver": True} if solver else {}            # solver 0 also runs on a tree without the option (the parent commit's)
-    eng = engine.SelfPlayEngine(cfg, evaluator=ev, **kw)
-    assert eng.capture_step()
-    t0 = time.time()
-    for i in range(steps):
-        eng.step()
-        if i % 256 == 255:
-            eng.drain_device()
-    torch.cuda.synchronize()
-    st = eng.stats()
-    print(json.dumps({"preset": preset, "solver": bool(solver), "steps": eng.steps, "launch": eng.launch_mode,
-                      "wall_s": round(time.time() - t0, 1), "moves": st["moves_played"], "sims": st["sims"],
-                      "terminal_sims": st["terminal_sims"], **{k: st.get(k, 0) for k in SOLVER_KEYS}, "overflow": st["overflow"]}),
-          flush=True)
-
-
-def _k_select_mean_us(path):
-    """Mean time per launch of the k_select instances in a rocprofv3 `*_kernel_stats.csv` (calls-weighted), in microseconds."""
-    calls = total = 0
-    with open(path, newline="") as f:
-        for row in csv.DictReader(f):
-            if "k_select" in row["Name"] and "k_select_multi" not in row["Name"]:
-                calls += int(row["Calls"])
-                total += float(row["TotalDurationNs"])
-    return round(total / calls / 1000.0, 3) if calls else None
+    mc.trace(PRESETS[preset], steps, kw, lambda eng, st: {"preset": preset, "solver": bool(solver),
+                                                          "terminal_sims": st["terminal_sims"],
+                                                          **{k: st.get(k, 0) for k in SOLVER_KEYS}})
 
 
 def spread(groups, out_path):
-    out = {"tool": "tools/measure_solver.py spread", "unit": "microseconds per k_select launch, mean of a run", "groups": {}}
-    for spec in groups:
-        name, files = spec.split("=", 1)
-        runs = [_k_select_mean_us(p) for p in files.split(",")]
-        out["groups"][name] = {"runs": runs, "min": min(runs), "max": max(runs), "spread": round(max(runs) - min(runs), 3),
-                               "mean": round(sum(runs) / len(runs), 3)}
-    g = out["groups"]
-    if "on" in g and "parent" in g:
-        out["on_within_parent_spread"] = g["parent"]["min"] <= g["on"]["mean"] <= g["parent"]["max"]
+    out = {"tool": "tools/measure_solver.py spread", "unit": "microseconds per k_select launch, mean of a run",
+           **mc.spread_groups(groups, {"groups": ("k_select", ("k_select_multi",))})}
     print(json.dumps(out, indent=1))
-    if out_path:
-        with open(out_path, "w") as f:
-            json.dump(out, f, indent=1)
+    mc.save_json(out, out_path)
 
 
 def main():
@@ -163,30 +107,12 @@ def main():
         return
     if args.child:
         job = json.loads(args.child)
-        print("RESULT " + json.dumps(child_arena(job) if args.part == "arena" else child_games(job)), flush=True)
+        mc.emit_result(child_arena(job) if args.part == "arena" else child_games(job))
         return
     out = {"tool": f"tools/measure_solver.py {args.part}", "preset": dict(PRESETS[args.preset], name=args.preset), "weights": "peaked",
            "runs": []}
-    for solver in args.runs:
-        job = dict(preset=args.preset, solver=solver)
-        t0 = time.time()
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), args.part, "--child", json.dumps(job)]
-        r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
-        if r.returncode != 0 or line is None:
-            print(r.stdout[-3000:], file=sys.stderr)
-            print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
-            out["failed"] = dict(job=job, exit=r.returncode)
-            break
-        row = json.loads(line[7:])
-        row["child_wall_s"] = round(time.time() - t0, 1)
-        print(json.dumps(row), flush=True)
-        out["runs"].append(row)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    jobs = [dict(preset=args.preset, solver=solver) for solver in args.runs]
+    sys.exit(0 if mc.run_children(__file__, jobs, args.timeout, out, args.out, argv=lambda job: [args.part]) else 1)
 
 
 if __name__ == "__main__":

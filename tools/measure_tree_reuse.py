@@ -15,30 +15,17 @@ start, long enough that slots end moves every step, for a kernel trace of k_rero
 """
 import argparse
 import json
-import os
-import subprocess
 import sys
-import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-GAINS = {"random": 1.0, "peaked": 8.0}
-PRESETS = {
-    "cfg1": dict(slots=1024, games=1024, sims=400, channels=128, blocks=6, temperature_threshold=20, max_game_length=400,
-                 random_opening_moves=8, modes=("off", "on", "on+cache")),
-    "standard_train": dict(slots=20, games=20, sims=200, channels=128, blocks=6, temperature_threshold=20, max_game_length=300,
-                           random_opening_moves=6, modes=("off", "on")),
-}
-TRACE = {1: dict(slots=1024, sims=400, channels=128, blocks=6, steps=700),
+import measure_common as mc
+from measure_common import GAINS
+
+sys.path.insert(0, mc.ROOT)
+# the common presets with the modes each is measured in
+PRESETS = {"cfg1": dict(mc.PRESETS["cfg1"], modes=("off", "on", "on+cache")),
+           "standard_train": dict(mc.PRESETS["standard_train"], modes=("off", "on"))}
+TRACE = {1: dict(mc.PRESETS["cfg1"], steps=700),
          2: dict(slots=8192, sims=800, channels=256, blocks=10, steps=1000)}
-
-
-def _net(channels, blocks, gain):
-    from xiangqi_alphazero_amd import model, weights
-    net = model.XiangqiNet(channels, blocks)
-    net.load_state_dict(weights.make_state_dict(channels, blocks, policy_gain=gain))
-    return net
 
 
 def child_games(job):
@@ -47,13 +34,10 @@ def child_games(job):
     import torch
     from xiangqi_alphazero_amd import engine, selfplay
     p = PRESETS[job["preset"]]
-    cfg = types.SimpleNamespace(num_simulations=p["sims"], c_puct=1.5, temperature_threshold=p["temperature_threshold"],
-                                max_game_length=p["max_game_length"], random_opening_moves=p["random_opening_moves"],
-                                enable_resign=True, resign_threshold=-0.9, resign_check_steps=5)
     K = engine.recommended_cache_entries(p["sims"]) if job["mode"] == "on+cache" else 0
-    samples, results, st, elapsed = selfplay.run_games(_net(p["channels"], p["blocks"], GAINS[job["weights"]]), cfg, p["games"],
-                                                       "cuda", n_slots=p["slots"], seed=11, poll_every=64 if p["slots"] < 64 else 256,
-                                                       eval_cache_entries=K, tree_reuse=job["mode"] != "off")
+    samples, results, st, elapsed = selfplay.run_games(mc.make_net(p["channels"], p["blocks"], GAINS[job["weights"]]),
+                                                       mc.selfplay_config(p), p["games"], "cuda", n_slots=p["slots"], seed=11,
+                                                       poll_every=mc.poll_every(p), eval_cache_entries=K, tree_reuse=job["mode"] != "off")
     torch.cuda.synchronize()
     digest = hashlib.sha256(np.sort(results, order=["slot", "game_seq"]).tobytes() +
                             np.sort(samples, order=["slot", "game_seq", "ply"]).tobytes()).hexdigest()[:16]
@@ -69,23 +53,8 @@ def child_games(job):
 
 
 def trace(config):
-    import torch
-    from xiangqi_alphazero_amd import engine, evaluator
-    c = TRACE[config]
-    ev = evaluator.make_evaluator(_net(c["channels"], c["blocks"], GAINS["peaked"]), "cuda", "hip")[0]
-    cfg = engine.make_config(c["slots"], c["sims"], seed=5, start_stagger=True, max_out_samples=c["slots"] * 16)
-    eng = engine.SelfPlayEngine(cfg, evaluator=ev, tree_reuse=True)
-    assert eng.capture_step()
-    t0 = time.time()
-    for i in range(c["steps"]):
-        eng.step()
-        if i % 256 == 255:
-            eng.drain_device()
-    torch.cuda.synchronize()
-    st = eng.stats()
-    print(json.dumps({"config": config, "steps": eng.steps, "launch": eng.launch_mode, "wall_s": round(time.time() - t0, 1),
-                      "moves": st["moves_played"], "reroots": st["reroots"], "reused_visits": st["reused_visits"],
-                      "sims": st["sims"], "overflow": st["overflow"]}), flush=True)
+    mc.trace(TRACE[config], TRACE[config]["steps"], dict(tree_reuse=True),
+             lambda eng, st: {"config": config, "reroots": st["reroots"], "reused_visits": st["reused_visits"]})
 
 
 def main():
@@ -101,30 +70,12 @@ def main():
         trace(args.config)
         return
     if args.child:
-        print("RESULT " + json.dumps(child_games(json.loads(args.child))), flush=True)
+        mc.emit_result(child_games(json.loads(args.child)))
         return
     p = PRESETS[args.preset]
     jobs = [dict(preset=args.preset, weights=w, mode=m) for w in GAINS for m in p["modes"]]   # alternated within each weight set
     out = {"tool": "tools/measure_tree_reuse.py", "preset": dict(p, name=args.preset), "runs": []}
-    for job in jobs:
-        t0 = time.time()
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "games", "--child", json.dumps(job)]
-        r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
-        if r.returncode != 0 or line is None:
-            print(r.stdout[-3000:], file=sys.stderr)
-            print(f"child failed (exit {r.returncode}) on {job}: stopping", file=sys.stderr)
-            out["failed"] = dict(job=job, exit=r.returncode)
-            break
-        row = json.loads(line[7:])
-        row["child_wall_s"] = round(time.time() - t0, 1)
-        print(json.dumps(row), flush=True)
-        out["runs"].append(row)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    sys.exit(1 if "failed" in out else 0)
+    sys.exit(0 if mc.run_children(__file__, jobs, args.timeout, out, args.out, argv=lambda job: ["games"]) else 1)
 
 
 if __name__ == "__main__":
