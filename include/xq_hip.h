@@ -1254,6 +1254,48 @@ int xq_groups_to_batch(const void *dev_samples, const int32_t *dev_group_offsets
                        double late_temperature, const xq_batch_opts *opts, float *dev_states, float *dev_pi, float *dev_z,
                        void *stream);
 
+/* Game records as training samples (opt-in; nothing in the engine knows of it, and no existing entry point, struct or byte
+ * changes): a supervised warm start from recorded games.  A record (xq_game_record) holds every move of a game, whoever chose it;
+ * these two calls turn the plies a caller selects into ordinary xq_sample rows, which the batch kernels read as one-hot policy
+ * targets.
+ * SELECTION   ply p of record i is selected when lo_i <= p < n_moves_i, with lo_i = skip_opening ? opening_plies_i : 0; the mover
+ *             of p is in the record's mover set (red moves the even plies): the set is dev_movers[i] when that pointer is given,
+ *             else opts->movers: 0 every ply, 1 the winner's plies only (a drawn game selects none), 2 red's plies, 3 black's;
+ *             and the record is not dropped by skip_draws (winner 0 selects no ply).
+ * MALFORMED   n_moves > XQ_RECORD_MAX_PLIES, opening_plies > n_moves, winner outside {-1, 0, 1}, or a dev_movers entry outside
+ *             [0, 3]: the record selects nothing (count 0) and its status is -1.  Both calls apply the same rule.
+ * xq_records_sample_counts: dev_counts[i] = the number of selected plies of record i.  Arithmetic over the headers, one thread per
+ *             record, no replay: an illegal ply does not change a count.
+ * PLACEMENT   the caller forms the exclusive prefix sum of the counts (dev_offsets int32[n + 1], the dev_group_offsets style of
+ *             xq_groups_to_batch): the rows of record i are exactly [dev_offsets[i], dev_offsets[i + 1]), in ply order.  No atomics;
+ *             the same bytes on every run.  xq_records_to_samples recomputes the count: when dev_offsets[i + 1] - dev_offsets[i]
+ *             differs from it, or the range leaves [0, dev_offsets[n]], nothing is written for the record and its status is -2
+ *             (-1 goes first on a malformed record).
+ * xq_records_to_samples: one wavefront per record, four per workgroup.  The record is played from the initial position as
+ *             xq_replay_games_batch plays it (no repetition, no-capture or length rule is judged: the record's winner is trusted);
+ *             at every ply the ordered legal moves are generated and the record's action is looked up among them.  A selected ply
+ *             writes one xq_sample, all 640 bytes: board, side and ply (the move count) before the move; z = 0 for winner 0, else
+ *             +1 when the winner is the side to move, else -1; n_moves and actions[0 .. n_moves) = the ordered legal moves
+ *             (xq_movegen_batch's output for the position); visits = 1 at the move played, 0 elsewhere; late_temp, reserved0 and
+ *             reserved1 = 0; slot and game_seq the record's; pad and the tails of actions and visits zero.  Rows are written with
+ *             16-byte vector stores.
+ *   dev_status[i]   0: the record was written whole; k > 0: ply k - 1 is no legal move of its position: the rows of selected
+ *                   plies before it are complete, those of selected plies from it on are 640 zero bytes; -1 malformed; -2 the
+ *                   offsets do not fit the record.  A well-formed record that selects nothing is still replayed for its status.
+ * XQ_ERR_ARG before any launch (no GPU needed): n < 0; opts NULL, movers outside [0, 3], a flag outside {0, 1}, a non-zero reserved
+ * word; with n > 0 a NULL pointer other than dev_movers; dev_samples not 16-byte aligned.  n = 0 is a no-op. */
+typedef struct xq_supervise_opts {
+    int32_t movers;        /* 0 every ply, 1 the winner's plies only (a drawn game selects none), 2 red's plies, 3 black's plies */
+    int32_t skip_opening;  /* 1: plies < record.opening_plies are replayed but select no sample */
+    int32_t skip_draws;    /* 1: a record with winner 0 selects no ply */
+    int32_t reserved;
+} xq_supervise_opts;
+int xq_records_sample_counts(const void *dev_records /* xq_game_record[n] */, const uint8_t *dev_movers /* [n] or NULL */, int n,
+                             const xq_supervise_opts *opts, int32_t *dev_counts /* [n] */, void *stream);
+int xq_records_to_samples(const void *dev_records /* xq_game_record[n] */, const uint8_t *dev_movers /* [n] or NULL */,
+                          const int32_t *dev_offsets /* [n + 1] */, int n, const xq_supervise_opts *opts,
+                          void *dev_samples /* xq_sample[dev_offsets[n]] */, int32_t *dev_status /* [n] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

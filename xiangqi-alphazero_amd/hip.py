@@ -165,6 +165,12 @@ class GameRecord(C.Structure):
 assert GAME_RECORD_DTYPE.itemsize == RECORD_BYTES == C.sizeof(GameRecord)
 
 
+class SuperviseOpts(C.Structure):
+    """xq_supervise_opts: which plies of a game record become samples (xq_records_sample_counts / xq_records_to_samples): movers
+    0 every ply, 1 the winner's, 2 red's, 3 black's; skip_opening and skip_draws 0 / 1."""
+    _fields_ = [("movers", C.c_int32), ("skip_opening", C.c_int32), ("skip_draws", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BatchOpts(C.Structure):
     """xq_batch_opts: the q-mixed value target of xq_samples_to_batch_ex: q_mix in [0, 1]."""
     _fields_ = [("q_mix", C.c_double), ("reserved", C.c_int32 * 2)]
@@ -382,6 +388,8 @@ def lib():
     L.xq_position_key_host.restype = C.c_uint64
     L.xq_position_group_heads.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
     L.xq_groups_to_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, C.c_double, C.POINTER(BatchOpts), vp, vp, vp, vp]
+    L.xq_records_sample_counts.argtypes = [vp, vp, i32, C.POINTER(SuperviseOpts), vp, vp]
+    L.xq_records_to_samples.argtypes = [vp, vp, vp, i32, C.POINTER(SuperviseOpts), vp, vp, vp]
     _lib = L
     return L
 
@@ -412,7 +420,7 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_drain_games_device", "xq_engine_game_records_stats_read", "xq_replay_games_batch",
            "xq_samples_to_requests", "xq_score_samples", "xq_surprise_counts", "xq_surprise_count_host",
            "xq_position_keys", "xq_position_key_host", "xq_position_group_heads", "xq_groups_to_batch",
-           "xq_alphabeta_batch"]
+           "xq_alphabeta_batch", "xq_records_sample_counts", "xq_records_to_samples"]
 
 
 def check(rc: int, what: str):
@@ -534,6 +542,57 @@ def replay_games(records: torch.Tensor, stop_ply=None, perpetual_check: bool = F
                                           _dev(out["hist12"]), _dev(out["status"]), _dev(out["over_kind"]), _dev(out["winner"]),
                                           stream_ptr(dev)), "xq_replay_games_batch")
     return out
+
+
+def records_to_samples(records, movers: int = 0, per_record_movers=None, skip_opening: bool = True, skip_draws: bool = False,
+                       device="cuda"):
+    """Game records as training samples (xq_records_sample_counts, one torch.cumsum, xq_records_to_samples): records = host
+    records (GAME_RECORD_DTYPE; copied to `device`) or a uint8[n, 1024] tensor on the GPU; movers 0 every ply, 1 the winner's
+    plies, 2 red's, 3 black's, or per_record_movers = one such value per record (anything numpy turns into uint8[n], or a uint8
+    device tensor); skip_opening leaves out the plies before record.opening_plies, skip_draws the drawn games -> dict of device
+    tensors: samples uint8[total, 640] (the rows of record i are offsets[i] .. offsets[i + 1], in ply order), offsets
+    int32[n + 1], status int32[n] (0 whole; k > 0: ply k - 1 is illegal, the rows from it on are zero; -1 malformed).  One host
+    synchronisation, to read the total."""
+    if isinstance(records, torch.Tensor):
+        rec = records
+    else:
+        import numpy as np
+        host = np.ascontiguousarray(records)
+        if host.dtype != GAME_RECORD_DTYPE:
+            raise XqError(f"records_to_samples: host records must be GAME_RECORD_DTYPE, got {host.dtype}")
+        rec = torch.from_numpy(host.reshape(-1).view(np.uint8).reshape(-1, RECORD_BYTES).copy()).to(device)
+    if rec.dtype != torch.uint8 or rec.dim() != 2 or rec.shape[1] != RECORD_BYTES:
+        raise XqError(f"records_to_samples: records must be uint8[n, {RECORD_BYTES}], got {rec.dtype} {tuple(rec.shape)}")
+    n, dev = rec.shape[0], rec.device
+    if isinstance(movers, bool) or int(movers) != movers or not 0 <= int(movers) <= 3:
+        raise XqError(f"records_to_samples: movers must be 0, 1, 2 or 3, got {movers!r}")
+    opts = SuperviseOpts(int(movers), 1 if skip_opening else 0, 1 if skip_draws else 0, 0)
+    per = None
+    if per_record_movers is not None:
+        if isinstance(per_record_movers, torch.Tensor):
+            per = per_record_movers.to(dev).contiguous()
+        else:
+            import numpy as np
+            per = torch.from_numpy(np.ascontiguousarray(per_record_movers, dtype=np.uint8)).to(dev)
+        if per.dtype != torch.uint8 or tuple(per.shape) != (n,):
+            raise XqError(f"records_to_samples: per_record_movers must be uint8[{n}], got {per.dtype} {tuple(per.shape)}")
+    offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return {"samples": torch.zeros((0, SAMPLE_BYTES), dtype=torch.uint8, device=dev), "offsets": offsets, "status": status}
+    counts = torch.zeros(n, dtype=torch.int32, device=dev)
+    p_per = None if per is None else _dev(per)
+    check(lib().xq_records_sample_counts(_dev(rec), p_per, n, C.byref(opts), _dev(counts), stream_ptr(dev)),
+          "xq_records_sample_counts")
+    running = torch.cumsum(counts, 0, dtype=torch.int64)
+    total = int(running[n - 1].item())
+    if total >= 2 ** 31:
+        raise XqError(f"records_to_samples: {total} rows do not fit the int32 offsets of xq_records_to_samples; convert in parts")
+    offsets[1:] = running.to(torch.int32)
+    rows = torch.empty((max(total, 1), SAMPLE_BYTES), dtype=torch.uint8, device=dev)
+    check(lib().xq_records_to_samples(_dev(rec), p_per, _dev(offsets), n, C.byref(opts), _dev(rows), _dev(status), stream_ptr(dev)),
+          "xq_records_to_samples")
+    return {"samples": rows[:total], "offsets": offsets, "status": status}
 
 
 def alphabeta_batch(boards: torch.Tensor, side: torch.Tensor, depth: int, draws=None):

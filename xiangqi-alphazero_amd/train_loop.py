@@ -40,7 +40,7 @@ import torch.distributed as dist
 
 from . import arena, distributed as xdist, hip, selfplay, training
 from .model import XiangqiNet
-from .sample_format import GAME_RECORD_DTYPE, RESULT_DTYPE, records_to_text
+from .sample_format import GAME_RECORD_DTYPE, RESULT_DTYPE, records_from_text, records_to_text
 
 
 def _baseline_options(config):
@@ -71,6 +71,42 @@ def _baseline_options(config):
     if sims < 1:
         raise hip.XqError(f"config.baseline_simulations must be >= 1, got {sims}")
     return {"games": games, "depth": depth, "simulations": sims, "opening_plies": plies, "interval": interval}
+
+
+def _pretrain_options(config):
+    """The supervised warm start's keys (all optional; absent means off): None when config.pretrain_records is absent or empty,
+    else a dict of paths, epochs, movers, skip_draws and records (the games of every file, read here: a missing file raises at
+    construction).  A key outside its range raises XqError with the key's name."""
+    paths = getattr(config, "pretrain_records", None)
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    if paths is not None and (not isinstance(paths, (list, tuple)) or not all(isinstance(p, (str, os.PathLike)) for p in paths)):
+        raise hip.XqError(f"config.pretrain_records must be a path or a list of paths, got {paths!r}")
+
+    def key(name, default):
+        v = getattr(config, name, None)
+        v = default if v is None else v
+        if isinstance(v, bool) or int(v) != v:
+            raise hip.XqError(f"config.{name} must be an integer, got {v!r}")
+        return int(v)
+
+    epochs = key("pretrain_epochs", 1)
+    if epochs < 1:
+        raise hip.XqError(f"config.pretrain_epochs must be >= 1, got {epochs}")
+    movers = key("pretrain_movers", 0)
+    if not 0 <= movers <= 3:
+        raise hip.XqError(f"config.pretrain_movers must be 0 (every ply), 1 (the winner's), 2 (red's) or 3 (black's), got {movers}")
+    skip_draws = getattr(config, "pretrain_skip_draws", None)
+    if skip_draws is not None and not isinstance(skip_draws, bool):
+        raise hip.XqError(f"config.pretrain_skip_draws must be a bool, got {skip_draws!r}")
+    if not paths:
+        return None
+    games = []
+    for p in paths:
+        with open(p) as f:
+            games.append(records_from_text(f.read()))
+    return {"paths": [os.fspath(p) for p in paths], "epochs": epochs, "movers": movers, "skip_draws": bool(skip_draws),
+            "records": np.concatenate(games)}
 
 
 class AlphaZeroLoop:
@@ -116,7 +152,10 @@ class AlphaZeroLoop:
         # the baseline gate (config.baseline_games; absent or 0: off), read once and checked here: every baseline_interval-th
         # iteration rank 0 plays best_model against the fixed alpha-beta opponent (baseline.py): no promotion, no collective
         self.baseline = _baseline_options(config)
-        torch.manual_seed(seed)                        # identical initial weights on every rank
+        # the supervised warm start (config.pretrain_records; absent: off), read once and checked here, the game files included: a
+        # fresh run trains current_model on their samples before iteration 1 (training.pretrain_from_records)
+        self.pretrain = _pretrain_options(config)
+        torch.manual_seed(seed)                       # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
         on_gpu = self.device.type == "cuda"
@@ -270,6 +309,25 @@ class AlphaZeroLoop:
         self._write_records("baseline", out["game_records"], getattr(self.config, "game_records_dir", None))
         return {k: out[k] for k in ("depth", "games", "wins", "losses", "draws", "win_rate", "win_rate_se", "seconds")}
 
+    def pretrain_from_records(self) -> dict:
+        """The supervised warm start of a fresh run: config.pretrain_epochs epochs of current_model on the samples of the games of
+        config.pretrain_records (every ply after the opening of the movers chosen), then best_model takes the weights.  Every rank
+        holds the same games and draws the batch order from the same seed, so every rank ends with the same weights and no
+        collective is needed; the loop's scheduler is not stepped.  A record that does not convert is dropped and counted.
+        -> the "pretrain" entry of the first iteration's stats."""
+        p = self.pretrain
+        t0 = time.time()
+        gen = torch.Generator().manual_seed(self.seed * 1000003 + 17)
+        info = {}
+        epochs = training.pretrain_from_records(self.current_model, self.optimizer, p["records"], self.config, p["epochs"],
+                                                invalid="drop", generator=gen, merge_duplicates=self.merge_duplicates,
+                                                device=self.device, info=info, movers=p["movers"], skip_opening=True,
+                                                skip_draws=p["skip_draws"])
+        self.best_model.load_state_dict(self.current_model.state_dict())
+        return {"games": info["games"], "samples": info["samples"], "invalid": info["invalid"], "epochs": p["epochs"],
+                "policy_loss": [e["policy_loss"] for e in epochs], "value_loss": [e["value_loss"] for e in epochs],
+                "seconds": time.time() - t0}
+
     def _save(self, iteration: int) -> None:
         if self.rank == 0:
             training.save_checkpoint(self.config.checkpoint_dir, iteration, self.current_model, self.best_model,
@@ -311,6 +369,9 @@ class AlphaZeroLoop:
     def train(self, num_iterations: Optional[int] = None) -> list:
         cfg = self.config
         last = num_iterations if num_iterations is not None else cfg.num_iterations
+        pre = None
+        if self.pretrain is not None and self.iteration == 0 and last >= 1:       # a fresh run: a resumed one has its weights
+            pre = self.pretrain_from_records()
         for iteration in range(self.iteration + 1, last + 1):
             self.iteration = iteration
             t0 = time.time()
@@ -325,7 +386,9 @@ class AlphaZeroLoop:
             if iteration % cfg.save_interval == 0:
                 self._save(iteration)
             self.training_stats.append({"iteration": iteration, "time": time.time() - t0, "self_play": sp,
-                                        "training": tr, "evaluation": ev, **({} if bl is None else {"baseline": bl})})
+                                        "training": tr, "evaluation": ev, **({} if bl is None else {"baseline": bl}),
+                                        **({} if pre is None else {"pretrain": pre})})
+            pre = None
             if self.rank == 0:
                 os.makedirs(cfg.checkpoint_dir, exist_ok=True)
                 with open(os.path.join(cfg.checkpoint_dir, "training_stats.json"), "w") as f:

@@ -72,6 +72,16 @@ class ReplayBuffer:
         self.head = (self.head + n) % self.cap
         self.count = min(self.cap, self.count + n)
 
+    def extend_from_records(self, records, invalid: str = "raise", **selection) -> Dict[str, int]:
+        """Append the samples of game records (`hip.records_to_samples`; `selection` = its movers, per_record_movers,
+        skip_opening and skip_draws): one row per selected ply, a one-hot policy target at the move played and the game's
+        result as the value target.  A record that does not convert (a malformed header, an illegal ply) raises XqError naming
+        the record and the ply with invalid="raise"; with invalid="drop" it is left out whole, its rows masked out on the device
+        before the extend.  -> {"games", "samples", "invalid"}: records read, rows appended, records that did not convert."""
+        rows, info = rows_from_records(records, self.device, invalid, **selection)
+        self.extend(rows)
+        return info
+
     def _record_of(self, logical: torch.Tensor):
         """logical index (oldest first, s0, s0', s1, ...) -> (ring record index, flip flag)."""
         rec = torch.div(logical, 2, rounding_mode="floor")
@@ -352,6 +362,77 @@ def train_network(model, optimizer, scheduler, buffer: ReplayBuffer, config, shu
             "distinct_positions": groups.n_groups if merge else None,
             "merged_records": groups.n_records - groups.n_groups if merge else None,
             "largest_group": int(groups.sizes.max().item()) if merge else None}
+
+
+def rows_from_records(records, device, invalid: str = "raise", **selection):
+    """The sample rows of game records, on the device (`hip.records_to_samples`), with the records that do not convert (a
+    malformed header, an illegal ply) either refused (invalid="raise": XqError naming the first such record and its ply) or left
+    out whole (invalid="drop": their rows are masked out on the device) -> (rows uint8[m, 640], {"games", "samples", "invalid"})."""
+    if invalid not in ("raise", "drop"):
+        raise hip.XqError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
+    out = hip.records_to_samples(records, device=device, **selection)
+    status, offsets, rows = out["status"], out["offsets"], out["samples"]
+    bad = torch.nonzero(status != 0).reshape(-1)
+    n_bad = int(bad.numel())
+    if n_bad:
+        if invalid == "raise":
+            i = int(bad[0].item())
+            st = int(status[i].item())
+            what = f"ply {st - 1} is no legal move of its position" if st > 0 else "its header is malformed"
+            raise hip.XqError(f"record {i} does not convert to samples: {what} ({n_bad} of {status.numel()} records do not; "
+                              "invalid='drop' leaves them out)")
+        counts = (offsets[1:] - offsets[:-1]).to(torch.int64)
+        rows = rows[torch.repeat_interleave(status == 0, counts)]
+    return rows, {"games": int(status.numel()), "samples": int(rows.shape[0]), "invalid": n_bad}
+
+
+class _ConstantRate:
+    """The scheduler of a supervised warm start: the learning rate stays what the optimizer holds, and the loop's own scheduler
+    (whose lr_milestones count self-play iterations) is not stepped."""
+    last_epoch = 0
+
+    def step(self) -> None:
+        pass
+
+
+class _PretrainConfig:
+    """The caller's config as `train_network` reads it for one supervised epoch: one epoch per call, no minimum buffer size,
+    every other key the caller's."""
+
+    def __init__(self, config):
+        self._config = config
+        self.num_epochs = 1
+        self.min_buffer_size = 0
+
+    def __getattr__(self, name):
+        return getattr(self._config, name)
+
+
+def pretrain_from_records(model, optimizer, records, config, epochs: int, invalid: str = "raise",
+                          generator: Optional[torch.Generator] = None, merge_duplicates: Optional[bool] = None,
+                          device=None, info: Optional[dict] = None, **selection) -> list:
+    """A supervised warm start: `epochs` epochs of `train_network` over the samples of game records (`rows_from_records`;
+    `selection` = hip.records_to_samples' movers, per_record_movers, skip_opening, skip_draws), in a fresh ReplayBuffer that
+    holds every row (max_size = 2 x rows: the buffer counts logical samples, a position and its mirror).  The policy target of
+    such a row is one-hot at the move played and the value target the game's result; `merge_duplicates` (default: the config's
+    `merge_duplicate_positions`) averages the records of one position, which turns a teacher's tie-breaking draws into the
+    distribution over its tied best moves.  q-mixing and policy-surprise weighting are off: the rows carry neither mark.  The
+    learning rate is the optimizer's own throughout (a throwaway constant-rate scheduler).  -> one stats dict of
+    `train_network` per epoch; `info`, when given, receives {"games", "samples", "invalid"}."""
+    if isinstance(epochs, bool) or int(epochs) != epochs or int(epochs) < 1:
+        raise hip.XqError(f"pretrain_from_records: epochs must be an integer >= 1, got {epochs!r}")
+    if device is None:
+        device = next(model.parameters()).device
+    rows, counts = rows_from_records(records, device, invalid, **selection)
+    if info is not None:
+        info.update(counts)
+    if rows.shape[0] == 0:
+        raise hip.XqError("pretrain_from_records: the records select no sample")
+    buffer = ReplayBuffer(2 * int(rows.shape[0]), device)       # late_temp is 0 in every row: the temperature is never read
+    buffer.extend(rows)
+    cfg, scheduler = _PretrainConfig(config), _ConstantRate()
+    return [train_network(model, optimizer, scheduler, buffer, cfg, generator=generator, q_mix=0.0, surprise_weight=0.0,
+                          merge_duplicates=merge_duplicates) for _ in range(int(epochs))]
 
 
 def save_checkpoint(checkpoint_dir: str, iteration: int, current_model, best_model, optimizer, scheduler, total_games: int,
