@@ -1104,6 +1104,48 @@ int xq_alphabeta_batch(const int8_t *dev_boards /* [n][90] */, const int8_t *dev
                        uint16_t *dev_best_action /* [n] */, int32_t *dev_best_score /* [n] */,
                        uint8_t *dev_status /* [n] */, void *stream);
 
+/* A forced-mate search (nothing in the engine knows of it, and no existing entry point, struct or byte changes): does the side to
+ * move, the attacker, force mate within N of its own moves, by checks only (the classic puzzle, a mate forced by an unbroken
+ * series of checks) or by any move?  A boolean AND/OR search in move order, one wavefront per (position, root move): the labels of
+ * a tactics puzzle set (tactics.py), and a per-move mate distance for any batch of positions.
+ * ROOT MOVES.  dev_moves[i][0..dev_counts[i]) are the ordered legal moves of the side to move: xq_movegen_batch's output exactly.
+ * RESULT OF ROOT MOVE j with child c, N = opts->max_moves:
+ *     if checks_only and the defender is not in check in c:  mate_in = 0, nodes = 0
+ *     else for m = 1 .. N:  if D(c, m - 1): mate_in = m, stop                                    (none: mate_in = 0)
+ *     D(pos, k)  the defender to move, k attacker moves left:  visit; no legal move -> true; k == 0 -> false;
+ *                for each reply in move order: if not A(child, k) -> false;   -> true
+ *     A(pos, k)  the attacker to move:  visit; for each move in move order: (checks_only: skip a move that gives no check)
+ *                if D(child, k - 1) -> true;   -> false
+ * A side without a legal move has lost, whether it is in check or not.  Repetition, the no-capture count and the ply-200 rule do
+ * not enter the search.  dev_mate_in[i][j] in 1..N: root move j forces mate in that many attacker moves, itself included.
+ * VISITS.  A visit is one move generation; dev_nodes[i][j] (or NULL) counts them over all m.  A move that fails the check test
+ * costs no visit.
+ * NODE LIMIT.  A search that would make visit number opts->node_limit + 1 stops with dev_mate_in[i][j] = XQ_MATE_UNKNOWN and
+ * dev_nodes[i][j] = node_limit.
+ * EXACT ORDER.  The traversal order above is part of the contract: visit counts and the limit's outcome are exact.  There is no
+ * move reordering and no transposition table.
+ * BEST.  dev_best_mate_in[i] is the smallest value in 1..N over the root moves, or 0 when there is none; dev_best_action[i] is the
+ * first move in move order that reaches it, or XQ_MATE_NO_MOVE.
+ * EVERY OUTPUT IS WRITTEN.  At and past the count dev_mate_in[i][j] = 0, dev_nodes[i][j] = 0, dev_moves[i][j] = 0.
+ * dev_status[i]: 0 fine; 1 a move-generation capacity was exceeded somewhere in the tree, by xq_movegen_batch's rule; 2 a king is
+ * missing on the input board: nothing is searched, the count is 0, the best mate-in is 0 and the action XQ_MATE_NO_MOVE; +4 some
+ * root move ended XQ_MATE_UNKNOWN.  A root without legal moves has count 0, best 0 and XQ_MATE_NO_MOVE.
+ * XQ_ERR_ARG before any launch: n < 0, NULL opts, max_moves outside 1..XQ_MATE_MAX_MOVES, checks_only outside {0, 1}, node_limit
+ * == 0, reserved != 0, with n > 0 a NULL pointer other than dev_nodes.  n == 0 is a no-op that returns XQ_OK.  Three launches on
+ * `stream` per 2^18 positions, no atomics, no workspace. */
+#define XQ_MATE_MAX_MOVES 5
+#define XQ_MATE_UNKNOWN   255
+#define XQ_MATE_NO_MOVE   0xFFFF
+typedef struct xq_mate_opts { int32_t max_moves;   /* N, 1..XQ_MATE_MAX_MOVES */
+                              int32_t checks_only; /* 0 | 1 */
+                              uint32_t node_limit; /* per root move, >= 1 */
+                              uint32_t reserved;   /* 0 */ } xq_mate_opts;
+int xq_mate_search_batch(const int8_t *dev_boards /* [n][90] */, const int8_t *dev_side /* [n] */, int n, const xq_mate_opts *opts,
+                         uint16_t *dev_moves /* [n][XQ_MAXM] */, uint16_t *dev_counts /* [n] */,
+                         uint8_t *dev_mate_in /* [n][XQ_MAXM] */, uint32_t *dev_nodes /* [n][XQ_MAXM] or NULL */,
+                         uint16_t *dev_best_action /* [n] */, uint8_t *dev_best_mate_in /* [n] */, uint8_t *dev_status /* [n] */,
+                         void *stream);
+
 /* Scoring samples against a network, and policy-surprise weighted training (opt-in; nothing in the engine knows of it, and no
  * existing entry point, struct or byte changes).  A finished sample is turned back into an evaluation request, a network answers
  * it, and the answer is compared with the sample's search target: how well does network X predict the samples in buffer Y, and

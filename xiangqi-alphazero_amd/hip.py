@@ -33,6 +33,10 @@ AB_MAX_DEPTH = 4               # XQ_AB_MAX_DEPTH
 AB_MATE = 30000                # XQ_AB_MATE
 AB_UNSCORED = -2 ** 31         # XQ_AB_UNSCORED
 AB_NO_MOVE = 0xFFFF            # XQ_AB_NO_MOVE
+MATE_MAX_MOVES = 5             # XQ_MATE_MAX_MOVES
+MATE_UNKNOWN = 255             # XQ_MATE_UNKNOWN
+MATE_NO_MOVE = 0xFFFF          # XQ_MATE_NO_MOVE
+MATE_DEFAULT_NODE_LIMIT = 10000    # visits per root move
 
 
 class XqError(RuntimeError):
@@ -169,6 +173,11 @@ class SuperviseOpts(C.Structure):
     """xq_supervise_opts: which plies of a game record become samples (xq_records_sample_counts / xq_records_to_samples): movers
     0 every ply, 1 the winner's, 2 red's, 3 black's; skip_opening and skip_draws 0 / 1."""
     _fields_ = [("movers", C.c_int32), ("skip_opening", C.c_int32), ("skip_draws", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MateOpts(C.Structure):
+    """xq_mate_opts: the forced-mate search (xq_mate_search_batch): N attacker moves, checks only 0 / 1, visits per root move."""
+    _fields_ = [("max_moves", C.c_int32), ("checks_only", C.c_int32), ("node_limit", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class BatchOpts(C.Structure):
@@ -313,6 +322,7 @@ def lib():
     L.xq_engine_game_records_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(GameRecordsStats), vp]
     L.xq_replay_games_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.xq_alphabeta_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.xq_mate_search_batch.argtypes = [vp, vp, i32, C.POINTER(MateOpts), vp, vp, vp, vp, vp, vp, vp, vp]
     L.xq_eval_mirror_bit_host.argtypes = [C.c_uint64, i32, i32, C.c_uint32, i32, i32, i32, i32]
     L.xq_mirror_action_host.argtypes = [i32]
     L.xq_mirror_requests_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
@@ -420,7 +430,7 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_drain_games_device", "xq_engine_game_records_stats_read", "xq_replay_games_batch",
            "xq_samples_to_requests", "xq_score_samples", "xq_surprise_counts", "xq_surprise_count_host",
            "xq_position_keys", "xq_position_key_host", "xq_position_group_heads", "xq_groups_to_batch",
-           "xq_alphabeta_batch", "xq_records_sample_counts", "xq_records_to_samples"]
+           "xq_alphabeta_batch", "xq_records_sample_counts", "xq_records_to_samples", "xq_mate_search_batch"]
 
 
 def check(rc: int, what: str):
@@ -624,6 +634,38 @@ def alphabeta_batch(boards: torch.Tensor, side: torch.Tensor, depth: int, draws=
         check(lib().xq_alphabeta_batch(_dev(boards), _dev(side), n, int(depth), None if d is None else _dev(d), _dev(out["moves"]),
                                        _dev(out["counts"]), _dev(out["scores"]), _dev(out["nodes"]), _dev(out["best_action"]),
                                        _dev(out["best_score"]), _dev(out["status"]), stream_ptr(dev)), "xq_alphabeta_batch")
+    return out
+
+
+def mate_search_batch(boards: torch.Tensor, side: torch.Tensor, max_moves: int, checks_only: bool = True, node_limit=None):
+    """The forced-mate search (xq_mate_search_batch): boards int8[n,90] (or [n,10,9]) and side int8[n] on the GPU, the side to move
+    attacks; 1 <= max_moves <= MATE_MAX_MOVES, checks_only restricts the attacker to checking moves, node_limit (None:
+    MATE_DEFAULT_NODE_LIMIT) bounds the visits per root move -> dict of device tensors: moves (u16-as-int16 [n,128], as
+    `movegen`), counts int16[n], mate_in uint8[n,128] (1..max_moves: the root move forces mate in that many moves; 0 none;
+    MATE_UNKNOWN cut by the limit), nodes int32[n,128] (the uint32's bits), best_action (u16-as-int16 [n]; MATE_NO_MOVE reads
+    -1), best_mate_in uint8[n], status uint8[n] (0 fine, 1 capacity, 2 a king is missing, +4 some root move was cut)."""
+    if isinstance(max_moves, bool) or int(max_moves) != max_moves or not 1 <= int(max_moves) <= MATE_MAX_MOVES:
+        raise XqError(f"mate_search_batch: max_moves must be an integer in [1, {MATE_MAX_MOVES}], got {max_moves!r}")
+    if checks_only not in (True, False, 0, 1):
+        raise XqError(f"mate_search_batch: checks_only must be a bool, got {checks_only!r}")
+    if node_limit is None:
+        node_limit = MATE_DEFAULT_NODE_LIMIT
+    if isinstance(node_limit, bool) or int(node_limit) != node_limit or not 1 <= int(node_limit) < 2 ** 32:
+        raise XqError(f"mate_search_batch: node_limit must be an integer in [1, 2^32), got {node_limit!r}")
+    n, dev = boards.shape[0], boards.device
+    if boards.dtype != torch.int8 or boards.numel() != n * 90 or side.dtype != torch.int8 or tuple(side.shape) != (n,):
+        raise XqError(f"mate_search_batch: boards must be int8[n, 90] and side int8[n], got {tuple(boards.shape)} and "
+                      f"{tuple(side.shape)}")
+    opts = MateOpts(int(max_moves), 1 if checks_only else 0, int(node_limit), 0)
+    out = {"moves": torch.zeros((n, MAXM), dtype=torch.int16, device=dev), "counts": torch.zeros(n, dtype=torch.int16, device=dev),
+           "mate_in": torch.zeros((n, MAXM), dtype=torch.uint8, device=dev),
+           "nodes": torch.zeros((n, MAXM), dtype=torch.int32, device=dev),
+           "best_action": torch.zeros(n, dtype=torch.int16, device=dev), "best_mate_in": torch.zeros(n, dtype=torch.uint8, device=dev),
+           "status": torch.zeros(n, dtype=torch.uint8, device=dev)}
+    if n:
+        check(lib().xq_mate_search_batch(_dev(boards), _dev(side), n, C.byref(opts), _dev(out["moves"]), _dev(out["counts"]),
+                                         _dev(out["mate_in"]), _dev(out["nodes"]), _dev(out["best_action"]),
+                                         _dev(out["best_mate_in"]), _dev(out["status"]), stream_ptr(dev)), "xq_mate_search_batch")
     return out
 
 

@@ -321,6 +321,57 @@ def records_from_text(text: str) -> np.ndarray:
     return np.array(out, dtype=GAME_RECORD_DTYPE).reshape(-1)
 
 
+# ---- positions as text: the standard Xiangqi FEN ---------------------------------------------------------------------------
+_FEN_LETTERS = "KABNRCP"          # piece codes 1..7; red is upper case
+_FEN_READ = {**{c: i + 1 for i, c in enumerate(_FEN_LETTERS)}, "E": 3, "H": 4}
+_FEN_SIDES = {"w": 1, "r": 1, "b": -1}
+
+
+def board_to_fen(board, side: int) -> str:
+    """A position as a Xiangqi FEN: ranks 9 down to 0 (row 0 is red's back rank) separated by '/', files a-i for columns 0-8
+    (`action_to_iccs`'s squares), red in upper case (K A B N R C P for codes 1..7), runs of empty squares as digits, then 'w'
+    when red is to move and 'b' when black is."""
+    b = np.asarray(board, dtype=np.int64).reshape(10, 9)
+    if int(side) not in (1, -1) or (np.abs(b) > 7).any():
+        raise ValueError(f"no position: side {side!r}, pieces {int(b.min())}..{int(b.max())}")
+    ranks = []
+    for r in range(9, -1, -1):
+        text, run = "", 0
+        for p in b[r].tolist():
+            if p == 0:
+                run += 1
+                continue
+            text += (str(run) if run else "") + (_FEN_LETTERS[p - 1] if p > 0 else _FEN_LETTERS[-p - 1].lower())
+            run = 0
+        ranks.append(text + (str(run) if run else ""))
+    return "/".join(ranks) + (" w" if int(side) == 1 else " b")
+
+
+def board_from_fen(text: str):
+    """-> (board int8[90], side): the inverse of `board_to_fen`.  Reading also takes E for B and H for N, 'w', 'r' or 'b' for
+    the side, and ignores the fields behind it.  A malformed line raises ValueError naming it."""
+    words = str(text).split()
+    if len(words) < 2 or words[1] not in _FEN_SIDES:
+        raise ValueError(f"a FEN line holds a board and a side (w, r or b): {text!r}")
+    ranks = words[0].split("/")
+    if len(ranks) != 10:
+        raise ValueError(f"a FEN board holds 10 ranks: {text!r}")
+    board = np.zeros((10, 9), dtype=np.int8)
+    for k, rank in enumerate(ranks):
+        c = 0
+        for ch in rank:
+            if ch in "123456789":
+                c += int(ch)
+                continue
+            if ch.upper() not in _FEN_READ or c >= 9:
+                raise ValueError(f"rank {9 - k} of a FEN board is malformed: {text!r}")
+            board[9 - k, c] = _FEN_READ[ch.upper()] * (1 if ch.isupper() else -1)
+            c += 1
+        if c != 9:
+            raise ValueError(f"rank {9 - k} of a FEN board does not hold 9 files: {text!r}")
+    return board.reshape(90), _FEN_SIDES[words[1]]
+
+
 # ---- merging the records of one position (xq_position_keys, xq_position_group_heads, xq_groups_to_batch) --------------------
 POSITION_KEY_MIRROR = 1           # XQ_POSITION_KEY_MIRROR
 MIR_SQ = np.array([(sq // 9) * 9 + 8 - sq % 9 for sq in range(90)], dtype=np.int64)      # mir(sq) of the header

@@ -16,6 +16,8 @@ Per iteration, exactly the reference's order:
   3b. baseline     opt-in (`config.baseline_games` > 0): every `baseline_interval`-th iteration rank 0 plays the best model
                    against the fixed alpha-beta opponent (`baseline.play_vs_baseline`) and logs the result under "baseline" in
                    that iteration's entry: an absolute yardstick next to the gate's relative one; it decides nothing;
+  3c. tactics      opt-in (`config.tactics_file`): every `tactics_interval`-th iteration rank 0 scores the best model on the
+                   file's forced mates (`tactics.solve_rate`) and logs the result under "tactics"; it decides nothing;
   4. checkpoint    every `save_interval` iterations and once more after the last one (train.py:613-615, 636-637), the
                    reference's file format; `training_stats.json` like train.py:620-634.
 `resume(path)` is the reference's `--resume` (train.py:569-579, 759-761): iteration, total_games, both models, optimizer
@@ -71,6 +73,44 @@ def _baseline_options(config):
     if sims < 1:
         raise hip.XqError(f"config.baseline_simulations must be >= 1, got {sims}")
     return {"games": games, "depth": depth, "simulations": sims, "opening_plies": plies, "interval": interval}
+
+
+def _tactics_options(config):
+    """The tactics yardstick's keys (all optional; absent means off): None when config.tactics_file is absent or None, else a dict
+    of file, max_moves, checks_only, simulations, interval and positions (the file's positions, read here: a missing file raises
+    at construction).  A key outside its range raises XqError with the key's name, whether the yardstick is on or not."""
+    def key(name, default):
+        v = getattr(config, name, None)
+        v = default if v is None else v
+        if isinstance(v, bool) or int(v) != v:
+            raise hip.XqError(f"config.{name} must be an integer, got {v!r}")
+        return int(v)
+
+    path = getattr(config, "tactics_file", None)
+    if path is not None and not isinstance(path, (str, os.PathLike)):
+        raise hip.XqError(f"config.tactics_file must be a path, got {path!r}")
+    max_moves = key("tactics_max_moves", 3)
+    if not 1 <= max_moves <= hip.MATE_MAX_MOVES:
+        raise hip.XqError(f"config.tactics_max_moves must be in [1, {hip.MATE_MAX_MOVES}], got {max_moves}")
+    checks_only = getattr(config, "tactics_checks_only", None)
+    if checks_only is not None and not isinstance(checks_only, bool):
+        raise hip.XqError(f"config.tactics_checks_only must be a bool, got {checks_only!r}")
+    interval = key("tactics_interval", 1)
+    if interval < 1:
+        raise hip.XqError(f"config.tactics_interval must be >= 1, got {interval}")
+    sims = key("tactics_simulations", int(config.eval_simulations))
+    if sims < 1:
+        raise hip.XqError(f"config.tactics_simulations must be >= 1, got {sims}")
+    if path is None:
+        return None
+    from . import tactics
+    with open(path) as f:
+        try:
+            positions = tactics.puzzles_from_text(f.read())
+        except ValueError as e:
+            raise hip.XqError(f"config.tactics_file {os.fspath(path)!r}: {e}") from None
+    return {"file": os.fspath(path), "max_moves": max_moves, "checks_only": True if checks_only is None else checks_only,
+            "simulations": sims, "interval": interval, "positions": positions}
 
 
 def _pretrain_options(config):
@@ -155,6 +195,11 @@ class AlphaZeroLoop:
         # the supervised warm start (config.pretrain_records; absent: off), read once and checked here, the game files included: a
         # fresh run trains current_model on their samples before iteration 1 (training.pretrain_from_records)
         self.pretrain = _pretrain_options(config)
+        # the tactics yardstick (config.tactics_file; absent: off), read once and checked here, the file included: every
+        # tactics_interval-th iteration rank 0 scores best_model on the file's forced mates (tactics.py): it decides nothing and
+        # uses no collective.  The positions are labelled on the device at first use
+        self.tactics = _tactics_options(config)
+        self._tactics_puzzles = None
         torch.manual_seed(seed)                       # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -309,6 +354,25 @@ class AlphaZeroLoop:
         self._write_records("baseline", out["game_records"], getattr(self.config, "game_records_dir", None))
         return {k: out[k] for k in ("depth", "games", "wins", "losses", "draws", "win_rate", "win_rate_se", "seconds")}
 
+    def score_tactics(self) -> dict:
+        """best_model on the puzzles of config.tactics_file (tactics.solve_rate) under the loop's solver and perpetual-check
+        values, seed + iteration as the search's seed -> this iteration's "tactics" entry.  The first call labels the file's
+        positions with one mate search; a position without a mate in [1, tactics_max_moves] is dropped and counted."""
+        from . import tactics
+        t = self.tactics
+        if self._tactics_puzzles is None:
+            labelled = tactics.label(t["positions"]["board"], t["positions"]["side"], t["max_moves"], t["checks_only"],
+                                     device=self.device)
+            self._tactics_puzzles = tactics.select(labelled, t["max_moves"], 1, unique=False)
+            t["dropped"] = len(labelled) - len(self._tactics_puzzles)
+        out = tactics.solve_rate(self.best_model, self._tactics_puzzles, t["simulations"], c_puct=float(self.config.c_puct),
+                                 solver=self.solver, perpetual_check=self.perpetual_check, seed=self.seed + self.iteration,
+                                 device=self.device, evaluator_kind=self.evaluator_kind)
+        # by_mate_in keyed by text, as the JSON file holds it: the entry in memory equals the entry on disk
+        return {**{k: out[k] for k in ("puzzles", "solved", "optimal", "solve_rate")},
+                "by_mate_in": {str(m): v for m, v in out["by_mate_in"].items()}, "max_moves": t["max_moves"],
+                "simulations": out["simulations"], "seconds": out["seconds"]}
+
     def pretrain_from_records(self) -> dict:
         """The supervised warm start of a fresh run: config.pretrain_epochs epochs of current_model on the samples of the games of
         config.pretrain_records (every ply after the opening of the movers chosen), then best_model takes the weights.  Every rank
@@ -383,10 +447,14 @@ class AlphaZeroLoop:
             bl = None
             if self.baseline is not None and self.rank == 0 and iteration % self.baseline["interval"] == 0:
                 bl = self.play_baseline()
+            tc = None
+            if self.tactics is not None and self.rank == 0 and iteration % self.tactics["interval"] == 0:
+                tc = self.score_tactics()
             if iteration % cfg.save_interval == 0:
                 self._save(iteration)
             self.training_stats.append({"iteration": iteration, "time": time.time() - t0, "self_play": sp,
                                         "training": tr, "evaluation": ev, **({} if bl is None else {"baseline": bl}),
+                                        **({} if tc is None else {"tactics": tc}),
                                         **({} if pre is None else {"pretrain": pre})})
             pre = None
             if self.rank == 0:
