@@ -1,16 +1,14 @@
 // xq_alphabeta.hip -- the fixed, non-learning opponent (include/xq_hip.h, xq_alphabeta_batch): a batched fixed-depth minimax search
-// with alpha-beta pruning over the material evaluation.  Three launches on one stream:
-//   k_ab_root    one wavefront per position: the king test, the ordered root moves, and every per-move output's default value;
-//   k_ab_search  one wavefront per (position, root move), four per 256-thread workgroup, LDS carved per wave and no workgroup
-//                barrier (xq_rules.cuh); a wave whose move index is at or past the count exits at once.  Root move j is searched on
-//                its own under a full window, fail-soft alpha-beta in move order below it: its score is the plain minimax value;
+// with alpha-beta pruning over the material evaluation.  Three launches on one stream, the search per root move of xq_tools.cuh:
+//   k_ab_root    the root moves, and every per-move output's default value;
+//   k_ab_search  root move j is searched on its own under a full window, fail-soft alpha-beta in move order below it: its score
+//                is the plain minimax value;
 //   k_ab_pick    one wavefront per position: the largest score and the draw-th of the moves that reach it.
 // The search keeps an explicit stack of at most XQ_AB_MAX_DEPTH - 1 levels in LDS: a board and a move list per level (boards are
 // copied per ply, never unmade), five state words per level.  Level l holds the position l + 1 plies below the root.  The last
 // level that generates moves scores all its children at once, a lane per move: a leaf's value is the material balance, which a
 // move changes by the captured piece's value only, so no leaf board is ever built.  No recursion, no atomics, no scratch.
-#include "xq_common.h"
-#include "xq_rules.cuh"
+#include "xq_tools.cuh"
 
 #pragma clang fp contract(off)
 
@@ -18,7 +16,6 @@ using namespace xq;
 
 namespace {
 
-constexpr int WPW = 4;
 constexpr int AB_LEVELS = XQ_AB_MAX_DEPTH - 1;      // levels that generate moves below a root move
 constexpr int AB_INF = 1 << 30;
 // every level's node is entered once and revisited once per child and once to leave: a bound no search reaches
@@ -35,28 +32,11 @@ struct AbLds {
     AbLevel st[AB_LEVELS];
 };
 
-struct RootLds {
-    __attribute__((aligned(16))) int8_t board[XQ_BS];
-    MoveGenLds mg;
-    uint16_t moves[XQ_MAXM];
-};
-
 // wave_material's piece values (game.py:552-563); the king counts 0
 __device__ __forceinline__ int piece_value(int p) {
     const int a = p < 0 ? -p : p;
     return (a == 2 || a == 3) ? 20 : (a == 4) ? 40 : (a == 5) ? 90 : (a == 6) ? 45 : (a == 7) ? 10 : 0;
 }
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int ld_uniform(const int *p) { return __builtin_amdgcn_readfirstlane(*p); }
 
 // The material balance from `side`'s view after its best capture: max over the `cnt` moves of the captured piece's value, added to
 // the balance before the move.  This is max over the moves of -V(child, 0, .) of the header's rule.
@@ -81,33 +61,11 @@ __global__ __launch_bounds__(64 * WPW) void k_ab_root(const int8_t *__restrict__
                                                       int32_t *__restrict__ scores, uint32_t *__restrict__ nodes,
                                                       uint8_t *__restrict__ status) {
     __shared__ RootLds Ls[WPW];
-    const int wv = (int)(threadIdx.x >> 6);
-    const int i = blockIdx.x * WPW + wv;
-    if (i >= n) return;
-    RootLds &L = Ls[wv];
-    const int lane = lane_id();
-    wave_load_board(boards + (size_t)i * 90, L.board);
-    wave_sync();
-    const VMove none{-1, -1, 0};
-    int cnt = 0, st = 0;
-    if (find_king(L.board, none, 1) < 0 || find_king(L.board, none, -1) < 0) {
-        st = 2;
-    } else {
-        int ovf = 0;
-        cnt = wave_movegen(L.board, (int)side[i], L.mg, L.moves, &ovf);       // cnt <= XQ_MAXM
-        st = ovf;
-    }
-    // every per-move word gets its value here; the search overwrites scores and nodes below the count (depth 0 searches nothing)
-    for (int j = lane; j < XQ_MAXM; j += 64) {
-        const size_t o = (size_t)i * XQ_MAXM + j;
-        moves[o] = j < cnt ? L.moves[j] : (uint16_t)0;
-        scores[o] = j < cnt ? 0 : XQ_AB_UNSCORED;
+    XQ_WAVE_ITEM(n)
+    wave_root_moves(boards, side, i, Ls[wv], moves, counts, status, [&](size_t o, bool live) {
+        scores[o] = live ? 0 : XQ_AB_UNSCORED;      // depth 0 searches nothing
         if (nodes) nodes[o] = 0u;
-    }
-    if (lane == 0) {
-        counts[i] = (uint16_t)cnt;
-        status[i] = (uint8_t)st;
-    }
+    });
 }
 
 __global__ __launch_bounds__(64 * WPW) void k_ab_search(const int8_t *__restrict__ boards, const int8_t *__restrict__ side, int n,
@@ -115,16 +73,8 @@ __global__ __launch_bounds__(64 * WPW) void k_ab_search(const int8_t *__restrict
                                                         const uint16_t *__restrict__ counts, int32_t *__restrict__ scores,
                                                         uint32_t *__restrict__ nodes, uint8_t *__restrict__ status) {
     __shared__ AbLds Ls[WPW];
-    const int wv = (int)(threadIdx.x >> 6);
-    const int w = (int)blockIdx.x * WPW + wv;                  // < n * XQ_MAXM <= 2^25 (the host launches in chunks)
-    const int i = w / XQ_MAXM, j = w % XQ_MAXM;
-    if (i >= n) return;
-    if (j >= __builtin_amdgcn_readfirstlane((int)counts[i])) return;
+    XQ_WAVE_ROOT_MOVE(n, side, moves, counts)
     AbLds &L = Ls[wv];
-    const int lane = lane_id();
-    const int root_side = __builtin_amdgcn_readfirstlane((int)side[i]);
-    const int action = __builtin_amdgcn_readfirstlane((int)moves[(size_t)i * XQ_MAXM + j]);
-    const int from = action / 90, to = action - from * 90;      // a legal move of the root: both below 90
 
     wave_load_board(boards + (size_t)i * 90, L.board[0]);
     wave_sync();
@@ -135,9 +85,7 @@ __global__ __launch_bounds__(64 * WPW) void k_ab_search(const int8_t *__restrict
         wave_material(L.board[0], red, black);
         score = root_side * (red - black) + piece_value(L.board[0][to]);
     } else {
-        const int mover = L.board[0][from];
-        wave_sync();
-        if (lane == 0) { L.board[0][to] = (int8_t)mover; L.board[0][from] = 0; }
+        wave_play(L.board[0], L.board[0], from, to);
         if (lane == 0) { L.st[0].alpha = -AB_INF; L.st[0].beta = AB_INF; }
         wave_sync();
         const int last = depth - 2;                              // the level whose children are leaves; last < AB_LEVELS
@@ -172,13 +120,8 @@ __global__ __launch_bounds__(64 * WPW) void k_ab_search(const int8_t *__restrict
                 } else {
                     // l < last <= AB_LEVELS - 1: level l + 1 exists
                     const int a = __builtin_amdgcn_readfirstlane((int)L.moves[l][idx]);
-                    const int f = a / 90, t = a - f * 90;
-                    lds_copy_dwords(L.board[l + 1], L.board[l], XQ_BS / 4);
-                    const int mv = L.board[l][f];
-                    wave_sync();
+                    wave_child_board(L.board[l + 1], L.board[l], a);
                     if (lane == 0) {
-                        L.board[l + 1][t] = (int8_t)mv;
-                        L.board[l + 1][f] = 0;
                         L.st[l + 1].alpha = -beta;
                         L.st[l + 1].beta = -(alpha > best ? alpha : best);
                     }
@@ -215,9 +158,7 @@ __global__ __launch_bounds__(64 * WPW) void k_ab_pick(int n, const uint32_t *__r
                                                       const uint16_t *__restrict__ counts, const int32_t *__restrict__ scores,
                                                       const uint8_t *__restrict__ status, uint16_t *__restrict__ best_action,
                                                       int32_t *__restrict__ best_score) {
-    const int wv = (int)(threadIdx.x >> 6);
-    const int i = blockIdx.x * WPW + wv;
-    if (i >= n) return;
+    XQ_WAVE_ITEM(n)
     const int lane = lane_id();
     const int cnt = __builtin_amdgcn_readfirstlane((int)counts[i]);       // <= XQ_MAXM
     if (cnt == 0) {
@@ -252,13 +193,9 @@ int xq_alphabeta_batch(const int8_t *dev_boards, const int8_t *dev_side, int n, 
                   !dev_status))
         return XQ_ERR_ARG;
     if (n == 0) return XQ_OK;
-    // in chunks of positions, so that no grid passes 2^31 threads (the search's has XQ_MAXM * 64 per position)
-    constexpr int CHUNK = 1 << 18;
-    const dim3 block(64 * WPW);
-    for (int base = 0; base < n; base += CHUNK) {
-        const int m = n - base < CHUNK ? n - base : CHUNK;
-        const size_t o = (size_t)base, om = o * XQ_MAXM;
-        const dim3 per_pos((m + WPW - 1) / WPW);
+    for_position_chunks(n, [&](size_t o, int m) {
+        const size_t om = o * XQ_MAXM;
+        const dim3 per_pos((m + WPW - 1) / WPW), block(64 * WPW);
         hipLaunchKernelGGL(k_ab_root, per_pos, block, 0, (hipStream_t)stream, dev_boards + o * 90, dev_side + o, m, dev_moves + om,
                            dev_counts + o, dev_scores + om, dev_nodes ? dev_nodes + om : nullptr, dev_status + o);
         if (depth >= 1)
@@ -267,7 +204,7 @@ int xq_alphabeta_batch(const int8_t *dev_boards, const int8_t *dev_side, int n, 
                                dev_nodes ? dev_nodes + om : nullptr, dev_status + o);
         hipLaunchKernelGGL(k_ab_pick, per_pos, block, 0, (hipStream_t)stream, m, dev_draws ? dev_draws + o : nullptr, dev_moves + om,
                            dev_counts + o, dev_scores + om, dev_status + o, dev_best_action + o, dev_best_score + o);
-    }
+    });
     return launch_status();
 }
 

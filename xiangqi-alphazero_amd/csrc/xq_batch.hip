@@ -1,8 +1,7 @@
 // xq_batch.hip -- stateless batched rules kernels behind the B1 plug point (include/xq_hip.h).
 // One 64-lane wavefront per position, four positions per 256-thread workgroup (LDS carved per wave, no workgroup
 // barrier: lane-to-lane traffic of one wave through LDS only needs program order, see xq_rules.cuh).  Integer/LDS-bound work: 90 bytes in, <= 2*L bytes out per position.
-#include "xq_common.h"
-#include "xq_rules.cuh"
+#include "xq_tools.cuh"
 
 #pragma clang fp contract(off)
 
@@ -11,13 +10,6 @@ thread_local hipError_t g_last_error = hipSuccess;
 }
 
 using namespace xq;
-
-// four positions per 256-thread workgroup, one per wave; LDS carved per wave, no workgroup barrier (see xq_rules.cuh)
-constexpr int WPW = 4;
-#define XQ_WAVE_ITEM(n)                                             \
-    const int wv = (int)(threadIdx.x >> 6);                         \
-    const int i = blockIdx.x * WPW + wv;                            \
-    if (i >= (n)) return;
 
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * WPW) void k_movegen(const int8_t *__restrict__ boards, const int8_t *__restrict__ side,
@@ -109,55 +101,39 @@ __global__ void k_apply_moves(const int8_t *__restrict__ boards, const int8_t *_
     out_boards[(size_t)j * 90 + b] = v;
 }
 
-// game.py:565-616 for independent states; hist = last min(12,mc) pre-move boards, oldest first.  `perpetual`: the opt-in
-// perpetual-check rule (xq_rules_opts); `kind` (or NULL): which test ended the game (XQ_OVER_*).
+// game.py:565-616 for independent states; hist = last k = min(12, mc) pre-move boards, oldest first: entry e is the pre-move
+// board of ply mc - k + e and goes to that ply's row of a per-wave ring, the layout wave_game_over judges (an mc below 6, a
+// negative one included, stages nothing and is no repetition).  `perpetual`: the opt-in perpetual-check rule (xq_rules_opts);
+// `kind` (or NULL): which test ended the game.
 __global__ __launch_bounds__(64 * WPW) void k_game_over(const int8_t *__restrict__ boards, const int8_t *__restrict__ side,
                                                   const int32_t *__restrict__ move_count,
                                                   const int32_t *__restrict__ no_capture, const int8_t *__restrict__ hist,
                                                   int n, int perpetual, int8_t *__restrict__ out, uint8_t *__restrict__ kind) {
     __shared__ __attribute__((aligned(16))) int8_t s_boards[WPW][XQ_BS];
+    __shared__ __attribute__((aligned(16))) int8_t s_rings[WPW][XQ_HIST][XQ_BS];
     __shared__ MoveGenLds s_mgs[WPW];
     __shared__ uint16_t s_outs[WPW][XQ_MAXM];
     XQ_WAVE_ITEM(n)
-    int8_t *s_board = s_boards[wv];
+    wave_load_board(boards + (size_t)i * 90, s_boards[wv]);
+    const int mc = __builtin_amdgcn_readfirstlane(move_count[i]);
+    const int k = mc < 6 ? 0 : (mc < XQ_HIST ? mc : XQ_HIST);      // below ply 6 nothing repeats: wave_game_over reads no row
+    // 45 byte pairs and a zero pair of padding per row; every row's load is issued before the first is stored
+    typedef uint16_t __attribute__((aligned(1))) pair_t;
+    const pair_t *hk = (const pair_t *)(hist + (size_t)i * XQ_HIST * 90);
     const int lane = lane_id();
-    wave_load_board(boards + (size_t)i * 90, s_board);
+    uint16_t row[XQ_HIST];
+#pragma unroll
+    for (int e = 0; e < XQ_HIST; ++e) row[e] = (e < k && lane < 45) ? hk[e * 45 + lane] : (uint16_t)0;
+#pragma unroll
+    for (int e = 0; e < XQ_HIST; ++e)
+        if (e < k && lane < XQ_BS / 2) ((uint16_t *)s_rings[wv][(mc - k + e) % XQ_HIST])[lane] = row[e];
     wave_sync();
-    const int player = side[i], mc = move_count[i], nc = no_capture[i];
-    const VMove none{-1, -1, 0};
-    int over = XQ_OVER_NONE, winner = 2;
-    if (find_king(s_board, none, 1) < 0) { over = XQ_OVER_KING; winner = -1; }
-    else if (find_king(s_board, none, -1) < 0) { over = XQ_OVER_KING; winner = 1; }
-    else {
-        int ovf = 0;
-        const int cnt = wave_movegen(s_board, player, s_mgs[wv], s_outs[wv], &ovf);
-        if (cnt == 0) { over = XQ_OVER_NO_MOVE; winner = -player; }
-        else if (nc >= 120) { over = XQ_OVER_NO_CAPTURE; winner = 0; }
-        else if (mc >= 200) {
-            int red, black;
-            wave_material(s_board, red, black);
-            const int diff = red - black;
-            over = XQ_OVER_PLY200; winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
-        } else if (mc >= 6) {
-            const int k = mc < XQ_HIST ? mc : XQ_HIST;
-            const int8_t *hk = hist + (size_t)i * XQ_HIST * 90;
-            int rep = 0;
-            for (int e = 0; e < k; ++e) {
-                const int8_t *h = hk + (size_t)e * 90;
-                bool diff = h[lane] != s_board[lane];
-                if (lane + 64 < 90) diff = diff || (h[lane + 64] != s_board[lane + 64]);
-                if (__ballot(diff) == 0ull) ++rep;
-            }
-            if (rep >= 3) {
-                // the board e + 1 plies ago is row k - 1 - e of the oldest-first history
-                winner = perpetual ? wave_perpetual_winner(s_board, hk, 90, k - 1, k, player) : 0;
-                over = winner != 0 ? XQ_OVER_PERPETUAL : XQ_OVER_REPETITION;
-            }
-        }
-    }
-    const int done = over != XQ_OVER_NONE;
+    int cnt = 0, winner = 2, ovf = 0;
+    const int player = __builtin_amdgcn_readfirstlane((int)side[i]), nc = __builtin_amdgcn_readfirstlane(no_capture[i]);
+    const int over = wave_game_over<true>(s_boards[wv], s_rings[wv], player, mc, nc, perpetual != 0, s_mgs[wv], s_outs[wv], &cnt,
+                                          &winner, &ovf);
     if (lane == 0) {
-        out[(size_t)i * 2] = (int8_t)done; out[(size_t)i * 2 + 1] = (int8_t)winner;
+        out[(size_t)i * 2] = (int8_t)(over != XQ_OVER_NONE); out[(size_t)i * 2 + 1] = (int8_t)winner;
         if (kind) kind[i] = (uint8_t)over;
     }
 }

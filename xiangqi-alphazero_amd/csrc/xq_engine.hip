@@ -9,6 +9,8 @@
 //                          xq_engine_init*, and the host-side readers (stats, drain, set_position, read_root).
 //   xq_engine_packed.hip : the packed steps -- compaction, gather, scatter, and the arena's two-set variant.
 //   xq_evcache.hip       : the evaluation cache (xq_evcache_*, xq_engine_compact_misses).
+//   xq_rules.cuh         : the wave-level rules, shared with the stateless tools (xq_batch, xq_replay, xq_supervise, xq_alphabeta,
+//                          xq_mate .hip); what only those five share is in xq_tools.cuh, which nothing of the engine includes.
 //
 //   k_select : per game, advance the game/search state machine until ONE network evaluation is needed:
 //                finish games (flush samples with z), start games (random opening), finish moves (visit

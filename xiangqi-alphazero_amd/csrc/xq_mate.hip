@@ -1,22 +1,19 @@
 // xq_mate.hip -- the forced-mate search (include/xq_hip.h, xq_mate_search_batch): does the side to move force mate within N of its
 // own moves, by checks only or by any move?  A boolean AND/OR search in move order, iteratively deepened per root move, with an
-// exact visit count and a node limit.  Three launches on one stream, the shape of xq_alphabeta.hip:
-//   k_mate_root    one wavefront per position: the king test, the ordered root moves, and every per-move output's default value;
-//   k_mate_search  one wavefront per (position, root move), four per 256-thread workgroup, LDS carved per wave and no workgroup
-//                  barrier (xq_rules.cuh); a wave whose move index is at or past the count exits at once;
+// exact visit count and a node limit.  Three launches on one stream, the search per root move of xq_tools.cuh:
+//   k_mate_root    the root moves, and every per-move output's default value;
+//   k_mate_search  the search below one root move;
 //   k_mate_pick    one wavefront per position: the quickest mate, the first move that reaches it, and the +4 of the status.
 // The search keeps an explicit stack of 2N - 1 levels in LDS: a board and a move list per level (boards are copied per ply, never
 // unmade) and two state words.  Level l holds the position l + 1 plies below the root: even levels are the defender's (AND nodes),
 // odd levels the attacker's (OR nodes).  Level, mode, result and the visit counter are wave-uniform.  No recursion, no atomics, no
 // scratch.
-#include "xq_common.h"
-#include "xq_rules.cuh"
+#include "xq_tools.cuh"
 
 using namespace xq;
 
 namespace {
 
-constexpr int WPW = 4;
 constexpr int MATE_LEVELS = 2 * XQ_MATE_MAX_MOVES - 1;
 // a visit costs one iteration to enter, one per move of its list, one to find the list exhausted and one to return; every
 // deepening adds one more: a bound no search under its node limit reaches
@@ -35,56 +32,17 @@ struct MateLds {
     MateLevel st[MATE_LEVELS];
 };
 
-struct RootLds {
-    __attribute__((aligned(16))) int8_t board[XQ_BS];
-    MoveGenLds mg;
-    uint16_t moves[XQ_MAXM];
-};
-
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int ld_uniform(const int *p) { return __builtin_amdgcn_readfirstlane(*p); }
-
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * WPW) void k_mate_root(const int8_t *__restrict__ boards, const int8_t *__restrict__ side, int n,
                                                         uint16_t *__restrict__ moves, uint16_t *__restrict__ counts,
                                                         uint8_t *__restrict__ mate_in, uint32_t *__restrict__ nodes,
                                                         uint8_t *__restrict__ status) {
     __shared__ RootLds Ls[WPW];
-    const int wv = (int)(threadIdx.x >> 6);
-    const int i = blockIdx.x * WPW + wv;
-    if (i >= n) return;
-    RootLds &L = Ls[wv];
-    const int lane = lane_id();
-    wave_load_board(boards + (size_t)i * 90, L.board);
-    wave_sync();
-    const VMove none{-1, -1, 0};
-    int cnt = 0, st = 0;
-    if (find_king(L.board, none, 1) < 0 || find_king(L.board, none, -1) < 0) {
-        st = 2;
-    } else {
-        int ovf = 0;
-        cnt = wave_movegen(L.board, (int)side[i], L.mg, L.moves, &ovf);       // cnt <= XQ_MAXM
-        st = ovf;
-    }
-    // every per-move word gets its value here; the search overwrites mate_in and nodes below the count
-    for (int j = lane; j < XQ_MAXM; j += 64) {
-        const size_t o = (size_t)i * XQ_MAXM + j;
-        moves[o] = j < cnt ? L.moves[j] : (uint16_t)0;
+    XQ_WAVE_ITEM(n)
+    wave_root_moves(boards, side, i, Ls[wv], moves, counts, status, [&](size_t o, bool) {
         mate_in[o] = (uint8_t)0;
         if (nodes) nodes[o] = 0u;
-    }
-    if (lane == 0) {
-        counts[i] = (uint16_t)cnt;
-        status[i] = (uint8_t)st;
-    }
+    });
 }
 
 __global__ __launch_bounds__(64 * WPW) void k_mate_search(const int8_t *__restrict__ boards, const int8_t *__restrict__ side, int n,
@@ -93,22 +51,12 @@ __global__ __launch_bounds__(64 * WPW) void k_mate_search(const int8_t *__restri
                                                           uint8_t *__restrict__ mate_in, uint32_t *__restrict__ nodes,
                                                           uint8_t *__restrict__ status) {
     __shared__ MateLds Ls[WPW];
-    const int wv = (int)(threadIdx.x >> 6);
-    const int w = (int)blockIdx.x * WPW + wv;                  // < n * XQ_MAXM <= 2^25 (the host launches in chunks)
-    const int i = w / XQ_MAXM, j = w % XQ_MAXM;
-    if (i >= n) return;
-    if (j >= __builtin_amdgcn_readfirstlane((int)counts[i])) return;
+    XQ_WAVE_ROOT_MOVE(n, side, moves, counts)
     MateLds &L = Ls[wv];
-    const int lane = lane_id();
-    const int attacker = __builtin_amdgcn_readfirstlane((int)side[i]);
-    const int action = __builtin_amdgcn_readfirstlane((int)moves[(size_t)i * XQ_MAXM + j]);
-    const int from = action / 90, to = action - from * 90;      // a legal move of the root: both below 90
-
+    const int attacker = root_side;
     wave_load_board(boards + (size_t)i * 90, L.board[0]);
     wave_sync();
-    const int mover = L.board[0][from];
-    wave_sync();
-    if (lane == 0) { L.board[0][to] = (int8_t)mover; L.board[0][from] = 0; }
+    wave_play(L.board[0], L.board[0], from, to);
     wave_sync();
 
     int result = 0, ovf = 0;
@@ -145,11 +93,7 @@ __global__ __launch_bounds__(64 * WPW) void k_mate_search(const int8_t *__restri
                     break;
                 } else {
                     const int a = __builtin_amdgcn_readfirstlane((int)L.moves[l][idx]);
-                    const int f = a / 90, t = a - f * 90;
-                    lds_copy_dwords(L.board[l + 1], L.board[l], XQ_BS / 4);
-                    const int mv = L.board[l][f];
-                    wave_sync();
-                    if (lane == 0) { L.board[l + 1][t] = (int8_t)mv; L.board[l + 1][f] = 0; }
+                    wave_child_board(L.board[l + 1], L.board[l], a);
                     wave_sync();
                     if (or_node && checks_only && !wave_in_check(L.board[l + 1], -attacker)) {
                         if (lane == 0) L.st[l].idx = idx + 1;     // a move that gives no check: skipped, no visit
@@ -191,9 +135,7 @@ __global__ __launch_bounds__(64 * WPW) void k_mate_pick(int n, int max_moves, co
                                                         const uint16_t *__restrict__ counts, const uint8_t *__restrict__ mate_in,
                                                         uint16_t *__restrict__ best_action, uint8_t *__restrict__ best_mate_in,
                                                         uint8_t *__restrict__ status) {
-    const int wv = (int)(threadIdx.x >> 6);
-    const int i = blockIdx.x * WPW + wv;
-    if (i >= n) return;
+    XQ_WAVE_ITEM(n)
     const int lane = lane_id();
     const int cnt = __builtin_amdgcn_readfirstlane((int)counts[i]);       // <= XQ_MAXM
     const uint8_t *mi = mate_in + (size_t)i * XQ_MAXM;
@@ -230,13 +172,9 @@ int xq_mate_search_batch(const int8_t *dev_boards, const int8_t *dev_side, int n
                   !dev_status))
         return XQ_ERR_ARG;
     if (n == 0) return XQ_OK;
-    // in chunks of positions, so that no grid passes 2^31 threads (the search's has XQ_MAXM * 64 per position)
-    constexpr int CHUNK = 1 << 18;
-    const dim3 block(64 * WPW);
-    for (int base = 0; base < n; base += CHUNK) {
-        const int m = n - base < CHUNK ? n - base : CHUNK;
-        const size_t o = (size_t)base, om = o * XQ_MAXM;
-        const dim3 per_pos((m + WPW - 1) / WPW);
+    for_position_chunks(n, [&](size_t o, int m) {
+        const size_t om = o * XQ_MAXM;
+        const dim3 per_pos((m + WPW - 1) / WPW), block(64 * WPW);
         hipLaunchKernelGGL(k_mate_root, per_pos, block, 0, (hipStream_t)stream, dev_boards + o * 90, dev_side + o, m, dev_moves + om,
                            dev_counts + o, dev_mate_in + om, dev_nodes ? dev_nodes + om : nullptr, dev_status + o);
         hipLaunchKernelGGL(k_mate_search, dim3((unsigned)m * (XQ_MAXM / WPW)), block, 0, (hipStream_t)stream, dev_boards + o * 90,
@@ -244,7 +182,7 @@ int xq_mate_search_batch(const int8_t *dev_boards, const int8_t *dev_side, int n
                            dev_counts + o, dev_mate_in + om, dev_nodes ? dev_nodes + om : nullptr, dev_status + o);
         hipLaunchKernelGGL(k_mate_pick, per_pos, block, 0, (hipStream_t)stream, m, (int)opts->max_moves, dev_moves + om,
                            dev_counts + o, dev_mate_in + om, dev_best_action + o, dev_best_mate_in + o, dev_status + o);
-    }
+    });
     return launch_status();
 }
 

@@ -2,16 +2,13 @@
 // four records per 256-thread workgroup, LDS carved per wave and no workgroup barrier (xq_rules.cuh).  A record is played from
 // the initial position on an LDS board with the 12-board ring the engine's real game keeps: every ply generates the ordered legal
 // moves and looks the record's action up among them, so a record replays only if every move of it was legal where it was played.
-#include "xq_common.h"
-#include "xq_rules.cuh"
+#include "xq_tools.cuh"
 
 #pragma clang fp contract(off)
 
 using namespace xq;
 
 namespace {
-
-constexpr int WPW = 4;
 
 static_assert(sizeof(xq_game_record) == XQ_RECORD_BYTES && offsetof(xq_game_record, moves) == 16, "xq_game_record layout");
 
@@ -28,9 +25,7 @@ __global__ __launch_bounds__(64 * WPW) void k_replay_games(const xq_game_record 
                                                            int8_t *__restrict__ hist12, int32_t *__restrict__ status,
                                                            int8_t *__restrict__ over_kind, int8_t *__restrict__ out_winner) {
     __shared__ ReplayLds Ls[WPW];
-    const int wv = (int)(threadIdx.x >> 6);
-    const int i = blockIdx.x * WPW + wv;
-    if (i >= n) return;
+    XQ_WAVE_ITEM(n)
     ReplayLds &L = Ls[wv];
     const int lane = lane_id();
     const xq_game_record *rec = records + i;

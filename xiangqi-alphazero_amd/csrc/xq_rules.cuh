@@ -54,6 +54,18 @@ __device__ __forceinline__ int wave_sum(int v) {
     return v;
 }
 
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(v, off); v = o > v ? o : v; }
+    return v;
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(v, off); v = o < v ? o : v; }
+    return v;
+}
+
 struct VMove {
     int from, to, mover;  // from = -1: no virtual move
 };
@@ -376,9 +388,9 @@ enum : int { XQ_OVER_NONE = 0, XQ_OVER_KING = 1, XQ_OVER_NO_MOVE = 2, XQ_OVER_NO
              XQ_OVER_REPETITION = 5, XQ_OVER_PERPETUAL = 6 };
 
 // The opt-in perpetual-check rule (include/xq_hip.h, xq_rules_opts) for a position whose repetition test has fired (three or
-// more of the last k <= XQ_HIST pre-move boards equal the current board `b`); one copy for wave_game_over (below) and
-// k_game_over (xq_batch.hip).  Entry e, the board e + 1 plies ago, is row (newest - e) mod XQ_HIST of `hist` (rows `stride`
-// bytes apart, LDS or global); `side` is to move in `b`, so by ply parity -side is to move in the even entries and side in the
+// more of the last k <= XQ_HIST pre-move boards equal the current board `b`), called by wave_game_over (below) alone.
+// Entry e, the board e + 1 plies ago, is row (newest - e) mod XQ_HIST of `hist` (rows `stride` bytes apart, LDS or
+// global); `side` is to move in `b`, so by ply parity -side is to move in the even entries and side in the
 // odd ones.  Returns the winner: the side that did NOT check on every one of its moves of the span (entries 0 .. E, E the
 // oldest entry equal to b) when exactly one side did, else 0.  Wave-uniform; all 64 lanes call it together.
 // At most 13 wave_in_check calls, in a branch almost no position enters.  Inlined: as a __noinline__ function the call's
@@ -455,24 +467,26 @@ __device__ __forceinline__ void init_board_lds(int8_t *b) {
 
 // game.py:565-616 on an LDS position.  Leaves the ordered legal moves in `moves` (count in *cnt) whenever both
 // kings stand.  Wave-uniform result: 0 not over, 1 over, 4 over by the perpetual-check rule (`perpetual`: the engine's
-// xq_rules_opts flag) -- the values of a root's status word and a result's reason.
+// xq_rules_opts flag) -- the values of a root's status word and a result's reason.  KIND: the test that ended the game
+// instead (XQ_OVER_*), for k_game_over (xq_batch.hip); the one copy of the rules' verdict serves both.
+template <bool KIND = false>
 __device__ inline int wave_game_over(const int8_t *b, const int8_t (*ring)[XQ_BS], int side, int mc, int nocap, bool perpetual,
                                      MoveGenLds &mg, uint16_t *moves, int *cnt, int *winner, int *ovf) {
     const VMove none{-1, -1, 0};
     const int lane = lane_id();
     *cnt = 0;
-    if (find_king(b, none, 1) < 0) { *winner = -1; return 1; }
-    if (find_king(b, none, -1) < 0) { *winner = 1; return 1; }
+    if (find_king(b, none, 1) < 0) { *winner = -1; return KIND ? XQ_OVER_KING : 1; }
+    if (find_king(b, none, -1) < 0) { *winner = 1; return KIND ? XQ_OVER_KING : 1; }
     const int n = wave_movegen(b, side, mg, moves, ovf);
     *cnt = n;
-    if (n == 0) { *winner = -side; return 1; }
-    if (nocap >= 120) { *winner = 0; return 1; }
+    if (n == 0) { *winner = -side; return KIND ? XQ_OVER_NO_MOVE : 1; }
+    if (nocap >= 120) { *winner = 0; return KIND ? XQ_OVER_NO_CAPTURE : 1; }
     if (mc >= 200) {
         int red, black;
         wave_material(b, red, black);
         const int diff = red - black;
         *winner = diff > 30 ? 1 : (diff < -30 ? -1 : 0);
-        return 1;
+        return KIND ? XQ_OVER_PLY200 : 1;
     }
     if (mc >= 6) {
         const int k = mc < XQ_HIST ? mc : XQ_HIST;
@@ -485,11 +499,11 @@ __device__ inline int wave_game_over(const int8_t *b, const int8_t (*ring)[XQ_BS
         if (rep >= 3) {
             const int w = perpetual ? wave_perpetual_winner(b, ring[0], XQ_BS, (mc - 1) % XQ_HIST, k, side) : 0;
             *winner = w;
-            return w != 0 ? 4 : 1;
+            return KIND ? (w != 0 ? XQ_OVER_PERPETUAL : XQ_OVER_REPETITION) : (w != 0 ? 4 : 1);
         }
     }
     *winner = 2;
-    return 0;
+    return KIND ? XQ_OVER_NONE : 0;
 }
 
 // game.py:528-550 on an LDS position + ring.  Wave-uniform scalars updated by reference.

@@ -4,8 +4,7 @@
 // ordered legal moves and looks the record's action up among them, and a selected ply leaves one xq_sample: the position, the
 // legal moves and one visit at the move played.  Rows are placed by the caller's prefix sum of the counts: no atomics, and the
 // same bytes on every run.
-#include "xq_common.h"
-#include "xq_rules.cuh"
+#include "xq_tools.cuh"
 
 #pragma clang fp contract(off)
 
@@ -13,7 +12,6 @@ using namespace xq;
 
 namespace {
 
-constexpr int WPW = 4;
 constexpr int ROW_CHUNKS = XQ_SAMPLE_BYTES / 16;    // a row is 40 16-byte stores, one per lane
 
 static_assert(sizeof(xq_sample) == XQ_SAMPLE_BYTES && XQ_SAMPLE_BYTES % 16 == 0, "xq_sample layout");
@@ -68,9 +66,7 @@ __global__ __launch_bounds__(64 * WPW) void k_records_to_samples(const xq_game_r
                                                                  int skip_opening, int skip_draws, uint4 *__restrict__ samples,
                                                                  int32_t *__restrict__ status) {
     __shared__ SuperviseLds Ls[WPW];
-    const int wv = (int)(threadIdx.x >> 6);
-    const int i = blockIdx.x * WPW + wv;
-    if (i >= n) return;
+    XQ_WAVE_ITEM(n)
     SuperviseLds &L = Ls[wv];
     const int lane = lane_id();
     const xq_game_record *rec = records + i;

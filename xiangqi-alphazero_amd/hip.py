@@ -605,6 +605,11 @@ def records_to_samples(records, movers: int = 0, per_record_movers=None, skip_op
     return {"samples": rows[:total], "offsets": offsets, "status": status}
 
 
+def _positions_arg(boards, side, what: str):
+    if boards.dtype != torch.int8 or boards.numel() != len(boards) * 90 or side.dtype != torch.int8 or side.shape != boards.shape[:1]:
+        raise XqError(f"{what}: boards must be int8[n, 90] and side int8[n], got {tuple(boards.shape)} and {tuple(side.shape)}")
+    return len(boards), boards.device
+
 def alphabeta_batch(boards: torch.Tensor, side: torch.Tensor, depth: int, draws=None):
     """The fixed alpha-beta opponent (xq_alphabeta_batch): boards int8[n,90] (or [n,10,9]) and side int8[n] on the GPU, 0 <= depth
     <= AB_MAX_DEPTH, draws None (the first best move) or one uint32 per position (an int32 / int64 device tensor, or anything
@@ -613,9 +618,7 @@ def alphabeta_batch(boards: torch.Tensor, side: torch.Tensor, depth: int, draws=
     (u16-as-int16 [n]; AB_NO_MOVE reads -1), best_score int32[n], status uint8[n] (0 fine, 1 capacity, 2 a king is missing)."""
     if not 0 <= int(depth) <= AB_MAX_DEPTH:
         raise XqError(f"alphabeta_batch: depth must be in [0, {AB_MAX_DEPTH}], got {depth}")
-    n, dev = boards.shape[0], boards.device
-    if boards.dtype != torch.int8 or boards.numel() != n * 90 or side.dtype != torch.int8 or tuple(side.shape) != (n,):
-        raise XqError(f"alphabeta_batch: boards must be int8[n, 90] and side int8[n], got {tuple(boards.shape)} and {tuple(side.shape)}")
+    n, dev = _positions_arg(boards, side, "alphabeta_batch")
     d = None
     if draws is not None:
         if isinstance(draws, torch.Tensor):
@@ -652,10 +655,7 @@ def mate_search_batch(boards: torch.Tensor, side: torch.Tensor, max_moves: int, 
         node_limit = MATE_DEFAULT_NODE_LIMIT
     if isinstance(node_limit, bool) or int(node_limit) != node_limit or not 1 <= int(node_limit) < 2 ** 32:
         raise XqError(f"mate_search_batch: node_limit must be an integer in [1, 2^32), got {node_limit!r}")
-    n, dev = boards.shape[0], boards.device
-    if boards.dtype != torch.int8 or boards.numel() != n * 90 or side.dtype != torch.int8 or tuple(side.shape) != (n,):
-        raise XqError(f"mate_search_batch: boards must be int8[n, 90] and side int8[n], got {tuple(boards.shape)} and "
-                      f"{tuple(side.shape)}")
+    n, dev = _positions_arg(boards, side, "mate_search_batch")
     opts = MateOpts(int(max_moves), 1 if checks_only else 0, int(node_limit), 0)
     out = {"moves": torch.zeros((n, MAXM), dtype=torch.int16, device=dev), "counts": torch.zeros(n, dtype=torch.int16, device=dev),
            "mate_in": torch.zeros((n, MAXM), dtype=torch.uint8, device=dev),
