@@ -1338,6 +1338,67 @@ int xq_records_to_samples(const void *dev_records /* xq_game_record[n] */, const
                           const int32_t *dev_offsets /* [n + 1] */, int n, const xq_supervise_opts *opts,
                           void *dev_samples /* xq_sample[dev_offsets[n]] */, int32_t *dev_status /* [n] */, void *stream);
 
+/* Endgame tablebases (nothing in the engine knows of them, and no existing entry point, struct or byte changes): the exact value
+ * of every position with both kings and up to XQ_TB_MAX_PIECES further pieces, by retrograde analysis over a dense index.
+ * SIGNATURE   P <= XQ_TB_MAX_PIECES non-king pieces as signed codes (2 advisor, 3 elephant, 4 knight, 5 rook, 6 cannon, 7 pawn;
+ *             red positive), in the caller's order.  Both kings are implicit.
+ * INDEX       dense, mixed radix, most significant digit first: the side to move (0 red, 1 black); the red king (9 palace squares,
+ *             rows 0-2, columns 3-5, row-major); the black king (9 squares, rows 7-9); then one digit per piece in signature order.
+ *             A piece's digits are its admissible squares in row-major order of the actual square, followed by one extra digit
+ *             meaning "captured".  Admissible for red: advisor (0,3) (0,5) (1,4) (2,3) (2,5); elephant (0,2) (0,6) (2,0) (2,4) (2,8)
+ *             (4,2) (4,6); pawn rows 3-4 on columns 0, 2, 4, 6, 8 and every square of rows 5-9 (55); knight, rook and cannon all 90.
+ *             For black the sets are the 180-degree rotation of red's (square s becomes 89 - s).  The captured digit makes every
+ *             sub-ending part of the same table: a capture is an index transition, there is no chain of tables.  Two equal pieces
+ *             are two digits; no symmetry is reduced.
+ *             xq_tb_entries: the entry count, on the host (no GPU needed); 0 for a bad signature (a code outside 2..7, P outside
+ *             0..XQ_TB_MAX_PIECES, NULL pieces with P > 0) or one beyond XQ_TB_MAX_ENTRIES.
+ * RULES       the move generator alone (xq_movegen_batch's moves).  The side to move without a legal move has lost, mated or
+ *             stalemated, as in the engine.  No repetition rule, no 120-ply no-capture rule, no ply-200 rule.
+ * VALUE       one int16 per entry, from the view of the side to move: 0 a draw; +p (p odd, >= 1) a win: with best play the loser
+ *             is without a move p plies from now; -(p + 1) (p even, >= 0) a loss in p plies, -1 no legal move now; XQ_TB_INVALID
+ *             an entry that is no position: two men on one square, or the side not to move in check, which includes facing kings.
+ *             Every legal move from a valid entry leads to a valid entry, so a king is never captured.
+ * xq_tb_init  pass 0, one wavefront per entry: the index is decoded into a board; XQ_TB_INVALID, -1 or 0 is written.
+ * xq_tb_pass  pass k in 1..XQ_TB_MAX_PASSES, in place on the one table, one wavefront per entry.  A wavefront whose entry is not 0
+ *             exits after one load.  Otherwise it generates the moves; every lane computes the child index of its move from the
+ *             parent's digits (the mover's digit changes, a captured piece's digit becomes "captured", the side flips) and loads
+ *             the child's value.  Odd k: the entry becomes +k when some child equals -k.  Even k: the entry becomes -(k + 1) when
+ *             every child is positive and the largest is k - 1.  A wavefront that decides an entry stores 1 into *dev_changed (a
+ *             plain store; the caller zeroes the word before the pass and reads it after).  The caller runs k = 1, 2, ... and stops
+ *             at the first pass that decided nothing.
+ *             IN PLACE IS EXACT.  Pass k writes only values of distance k (+k for odd k, -(k + 1) for even k) and only over a 0,
+ *             and it tests children only for distance k - 1 (-k written by pass k - 1 for odd k; a largest child of k - 1 for even
+ *             k).  A value written earlier in the same pass is +k or -(k + 1): it is never -k, and in an even pass it is negative,
+ *             which fails "every child is positive" exactly as the 0 it replaced did.  So a test gives the same answer whether it
+ *             sees a child's word from before this pass or from within it.  An aligned 2-byte load or store is atomic, so a word
+ *             is never seen half written.  Values of distance k - 1 and below never change again.
+ *             Neither call synchronises or allocates.  Launches go over chunks so that no grid passes 2^31 threads.
+ * xq_tb_probe_batch   one wavefront per position.  The board is matched against the signature greedily in signature order (the r-th
+ *             piece of a code in the signature takes the r-th such piece of the board, row-major); a signature piece absent from
+ *             the board is "captured".  dev_value[i] is the entry's value; dev_moves / dev_counts the ordered legal moves;
+ *             dev_move_value[i][j] (or NULL) what the side to move gets by playing root move j: a child lost in p plies gives
+ *             +(p + 1), a child won in p plies gives -(p + 2), a drawn child 0.  dev_best_action[i] is the first move in move order
+ *             whose move value equals dev_value[i], XQ_TB_NO_MOVE when there is no move.
+ *   dev_status[i]   a bit set: +1 the position is not in this table (a piece the signature lacks, or a piece on a square outside its
+ *                   list); +2 a king is missing; +4 the entry is XQ_TB_INVALID.  With any bit set the value is 0, the count 0 and
+ *                   the action XQ_TB_NO_MOVE.  Every output word is written; past the count moves and move values are zeros.
+ * XQ_ERR_ARG before any launch: n < 0; NULL pointers where n > 0 (dev_move_value may be NULL), a NULL table or flag; a bad
+ * signature; k outside 1..XQ_TB_MAX_PASSES.  An empty batch is a no-op returning 0. */
+#define XQ_TB_MAX_PIECES  5
+#define XQ_TB_MAX_ENTRIES (1 << 28)
+#define XQ_TB_MAX_PASSES  32000
+#define XQ_TB_INVALID     (-32768)
+#define XQ_TB_NO_MOVE     0xFFFF
+int64_t xq_tb_entries(const int8_t *pieces /* [n_pieces] */, int n_pieces);
+int xq_tb_init(const int8_t *pieces, int n_pieces, int16_t *dev_table /* [entries] */, void *stream);
+int xq_tb_pass(const int8_t *pieces, int n_pieces, int16_t *dev_table /* [entries] */, int k, int32_t *dev_changed /* [1] */,
+               void *stream);
+int xq_tb_probe_batch(const int8_t *pieces, int n_pieces, const int16_t *dev_table /* [entries] */,
+                      const int8_t *dev_boards /* [n][90] */, const int8_t *dev_side /* [n] */, int n, int16_t *dev_value /* [n] */,
+                      uint16_t *dev_moves /* [n][XQ_MAXM] */, uint16_t *dev_counts /* [n] */,
+                      int16_t *dev_move_value /* [n][XQ_MAXM] or NULL */, uint16_t *dev_best_action /* [n] */,
+                      uint8_t *dev_status /* [n] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

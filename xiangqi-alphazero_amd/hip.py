@@ -37,6 +37,11 @@ MATE_MAX_MOVES = 5             # XQ_MATE_MAX_MOVES
 MATE_UNKNOWN = 255             # XQ_MATE_UNKNOWN
 MATE_NO_MOVE = 0xFFFF          # XQ_MATE_NO_MOVE
 MATE_DEFAULT_NODE_LIMIT = 10000    # visits per root move
+TB_MAX_PIECES = 5              # XQ_TB_MAX_PIECES
+TB_MAX_ENTRIES = 1 << 28       # XQ_TB_MAX_ENTRIES
+TB_MAX_PASSES = 32000          # XQ_TB_MAX_PASSES
+TB_INVALID = -32768            # XQ_TB_INVALID
+TB_NO_MOVE = 0xFFFF            # XQ_TB_NO_MOVE
 
 
 class XqError(RuntimeError):
@@ -400,6 +405,11 @@ def lib():
     L.xq_groups_to_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, C.c_double, C.POINTER(BatchOpts), vp, vp, vp, vp]
     L.xq_records_sample_counts.argtypes = [vp, vp, i32, C.POINTER(SuperviseOpts), vp, vp]
     L.xq_records_to_samples.argtypes = [vp, vp, vp, i32, C.POINTER(SuperviseOpts), vp, vp, vp]
+    L.xq_tb_entries.argtypes = [vp, i32]
+    L.xq_tb_entries.restype = C.c_int64
+    L.xq_tb_init.argtypes = [vp, i32, vp, vp]
+    L.xq_tb_pass.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.xq_tb_probe_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -430,7 +440,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_engine_drain_games_device", "xq_engine_game_records_stats_read", "xq_replay_games_batch",
            "xq_samples_to_requests", "xq_score_samples", "xq_surprise_counts", "xq_surprise_count_host",
            "xq_position_keys", "xq_position_key_host", "xq_position_group_heads", "xq_groups_to_batch",
-           "xq_alphabeta_batch", "xq_records_sample_counts", "xq_records_to_samples", "xq_mate_search_batch"]
+           "xq_alphabeta_batch", "xq_records_sample_counts", "xq_records_to_samples", "xq_mate_search_batch",
+           "xq_tb_entries", "xq_tb_init", "xq_tb_pass", "xq_tb_probe_batch"]
 
 
 def check(rc: int, what: str):
@@ -666,6 +677,130 @@ def mate_search_batch(boards: torch.Tensor, side: torch.Tensor, max_moves: int, 
         check(lib().xq_mate_search_batch(_dev(boards), _dev(side), n, C.byref(opts), _dev(out["moves"]), _dev(out["counts"]),
                                          _dev(out["mate_in"]), _dev(out["nodes"]), _dev(out["best_action"]),
                                          _dev(out["best_mate_in"]), _dev(out["status"]), stream_ptr(dev)), "xq_mate_search_batch")
+    return out
+
+
+# ---- endgame tablebases (xq_tb_*; endgame.py holds the numpy reference of the layout and the Tablebase class) ----------------
+
+_TB_LETTERS = {"A": 2, "B": 3, "E": 3, "N": 4, "H": 4, "R": 5, "C": 6, "P": 7}
+
+
+def tb_signature(signature, what: str = "tb_signature"):
+    """A signature -> its signed piece codes (a tuple).  A string of FEN letters as `sample_format.board_to_fen` writes them (A B
+    N R C P, upper case for red, lower case for black; E and H are read too), or a sequence of signed codes (2 advisor, 3
+    elephant, 4 knight, 5 rook, 6 cannon, 7 pawn).  Both kings are implicit.  Refused: an unknown letter or code, more than
+    TB_MAX_PIECES pieces."""
+    if isinstance(signature, str):
+        bad = [ch for ch in signature if ch.upper() not in _TB_LETTERS]
+        if bad:
+            raise XqError(f"{what}: signature {signature!r} holds {bad[0]!r}; the letters are A B N R C P (E, H), lower case for black")
+        codes = tuple(_TB_LETTERS[ch.upper()] * (1 if ch.isupper() else -1) for ch in signature)
+    else:
+        try:
+            codes = tuple(int(c) for c in signature)
+        except (TypeError, ValueError):
+            raise XqError(f"{what}: signature must be a string of piece letters or a sequence of piece codes, got {signature!r}")
+        if any(isinstance(c, bool) or int(c) != c for c in signature) or any(not 2 <= abs(c) <= 7 for c in codes):
+            raise XqError(f"{what}: signature codes must be integers with 2 <= |code| <= 7, got {signature!r}")
+    if len(codes) > TB_MAX_PIECES:
+        raise XqError(f"{what}: signature {signature!r} holds {len(codes)} pieces, at most {TB_MAX_PIECES} fit")
+    return codes
+
+
+def _tb_pieces(codes):
+    return (C.c_int8 * max(len(codes), 1))(*codes), len(codes)
+
+
+def tb_entries(signature) -> int:
+    """xq_tb_entries: the entry count of a signature's table, on the host (no GPU needed).  A signature beyond TB_MAX_ENTRIES
+    is refused."""
+    codes = tb_signature(signature, "tb_entries")
+    arr, P = _tb_pieces(codes)
+    n = int(lib().xq_tb_entries(arr, P))
+    if n <= 0:
+        raise XqError(f"tb_entries: signature {signature!r} is beyond {TB_MAX_ENTRIES} entries")
+    return n
+
+
+def _tb_table_arg(signature, table, what: str):
+    codes = tb_signature(signature, what)
+    entries = tb_entries(signature)
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int16 or tuple(table.shape) != (entries,):
+        got = (table.dtype, tuple(table.shape)) if isinstance(table, torch.Tensor) else type(table).__name__
+        raise XqError(f"{what}: table must be an int16 tensor of {entries} entries for signature {signature!r}, got {got}")
+    return codes, entries
+
+
+def tb_init(signature, table: torch.Tensor) -> torch.Tensor:
+    """Pass 0 (xq_tb_init) over `table`, an int16 device tensor of tb_entries(signature) words: TB_INVALID, -1 (no legal move) or
+    0 per entry.  On the current stream; does not synchronise.  -> table."""
+    codes, _ = _tb_table_arg(signature, table, "tb_init")
+    arr, P = _tb_pieces(codes)
+    check(lib().xq_tb_init(arr, P, _dev(table), stream_ptr(table.device)), "xq_tb_init")
+    return table
+
+
+def tb_pass(signature, table: torch.Tensor, k: int, changed: torch.Tensor) -> torch.Tensor:
+    """Pass k >= 1 (xq_tb_pass), in place on `table`; `changed` is an int32[1] device tensor that a deciding wavefront sets to 1
+    (the caller zeroes it before and reads it after).  On the current stream; does not synchronise.  -> changed."""
+    codes, _ = _tb_table_arg(signature, table, "tb_pass")
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= TB_MAX_PASSES:
+        raise XqError(f"tb_pass: k must be an integer in [1, {TB_MAX_PASSES}], got {k!r}")
+    if not isinstance(changed, torch.Tensor) or changed.dtype != torch.int32 or changed.numel() != 1 or changed.device != table.device:
+        raise XqError("tb_pass: changed must be an int32 tensor of one word on the table's device")
+    arr, P = _tb_pieces(codes)
+    check(lib().xq_tb_pass(arr, P, _dev(table), int(k), _dev(changed), stream_ptr(table.device)), "xq_tb_pass")
+    return changed
+
+
+def tb_generate(signature, device="cuda", max_passes=None):
+    """The whole table of a signature -> (table int16 device tensor, passes).  tb_init, then tb_pass for k = 1, 2, ...; the flag is
+    read after each pass and the loop stops at the first pass that decided nothing (or at max_passes); `passes` is that pass's
+    number.  THIS CALL SYNCHRONISES: it reads the flag on the host once per pass."""
+    codes = tb_signature(signature, "tb_generate")
+    entries = tb_entries(signature)
+    if max_passes is None:
+        max_passes = TB_MAX_PASSES
+    if isinstance(max_passes, bool) or int(max_passes) != max_passes or not 1 <= int(max_passes) <= TB_MAX_PASSES:
+        raise XqError(f"tb_generate: max_passes must be an integer in [1, {TB_MAX_PASSES}], got {max_passes!r}")
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        table = torch.empty(entries, dtype=torch.int16, device=dev)
+        changed = torch.zeros(1, dtype=torch.int32, device=dev)
+        tb_init(codes, table)
+        k = 0
+        while k < int(max_passes):
+            k += 1
+            changed.zero_()
+            tb_pass(codes, table, k, changed)
+            if int(changed.item()) == 0:
+                break
+    return table, k
+
+
+def tb_probe_batch(signature, table: torch.Tensor, boards: torch.Tensor, side: torch.Tensor, move_values: bool = True):
+    """The probe (xq_tb_probe_batch): boards int8[n,90] (or [n,10,9]) and side int8[n] on the table's device -> dict of device
+    tensors: value int16[n] (0 draw, +p a win in p plies, -(p + 1) a loss in p plies), moves (u16-as-int16 [n,128], as `movegen`),
+    counts int16[n], move_value int16[n,128] (what the side to move gets by each root move; absent with move_values=False),
+    best_action (u16-as-int16 [n]; TB_NO_MOVE reads -1), status uint8[n] (+1 not in this table, +2 a king is missing, +4 the
+    entry is TB_INVALID; with any bit the value is 0, the count 0 and the action TB_NO_MOVE)."""
+    codes, _ = _tb_table_arg(signature, table, "tb_probe_batch")
+    if move_values not in (True, False, 0, 1):
+        raise XqError(f"tb_probe_batch: move_values must be a bool, got {move_values!r}")
+    n, _ = _positions_arg(boards, side, "tb_probe_batch")
+    dev = table.device
+    if n and (boards.device != dev or side.device != dev):
+        raise XqError(f"tb_probe_batch: boards and side must be on the table's device {dev}, got {boards.device} and {side.device}")
+    out = {"value": torch.zeros(n, dtype=torch.int16, device=dev), "moves": torch.zeros((n, MAXM), dtype=torch.int16, device=dev),
+           "counts": torch.zeros(n, dtype=torch.int16, device=dev),
+           "best_action": torch.zeros(n, dtype=torch.int16, device=dev), "status": torch.zeros(n, dtype=torch.uint8, device=dev)}
+    if move_values:
+        out["move_value"] = torch.zeros((n, MAXM), dtype=torch.int16, device=dev)
+    if n:
+        arr, P = _tb_pieces(codes)
+        check(lib().xq_tb_probe_batch(arr, P, _dev(table), _dev(boards), _dev(side), n, _dev(out["value"]), _dev(out["moves"]),
+                                      _dev(out["counts"]), _dev(out["move_value"]) if move_values else None,
+                                      _dev(out["best_action"]), _dev(out["status"]), stream_ptr(dev)), "xq_tb_probe_batch")
     return out
 
 

@@ -18,6 +18,10 @@ Per iteration, exactly the reference's order:
                    that iteration's entry: an absolute yardstick next to the gate's relative one; it decides nothing;
   3c. tactics      opt-in (`config.tactics_file`): every `tactics_interval`-th iteration rank 0 scores the best model on the
                    file's forced mates (`tactics.solve_rate`) and logs the result under "tactics"; it decides nothing;
+  3d. endgame      opt-in (`config.endgame_signature`): every `endgame_interval`-th iteration rank 0 scores the best model on
+                   won (or drawn) positions of the signature's tablebase (`endgame.hold_rate`) and logs the result under
+                   "endgame"; it decides nothing.  With `endgame_rescore` the samples the table covers get their exact outcome
+                   before they enter the buffer (`endgame.rescore_samples`);
   4. checkpoint    every `save_interval` iterations and once more after the last one (train.py:613-615, 636-637), the
                    reference's file format; `training_stats.json` like train.py:620-634.
 `resume(path)` is the reference's `--resume` (train.py:569-579, 759-761): iteration, total_games, both models, optimizer
@@ -42,7 +46,7 @@ import torch.distributed as dist
 
 from . import arena, distributed as xdist, hip, selfplay, training
 from .model import XiangqiNet
-from .sample_format import GAME_RECORD_DTYPE, RESULT_DTYPE, records_from_text, records_to_text
+from .sample_format import GAME_RECORD_DTYPE, RESULT_DTYPE, SAMPLE_DTYPE, records_from_text, records_to_text
 
 
 def _baseline_options(config):
@@ -111,6 +115,46 @@ def _tactics_options(config):
             raise hip.XqError(f"config.tactics_file {os.fspath(path)!r}: {e}") from None
     return {"file": os.fspath(path), "max_moves": max_moves, "checks_only": True if checks_only is None else checks_only,
             "simulations": sims, "interval": interval, "positions": positions}
+
+
+def _endgame_options(config):
+    """The endgame yardstick's keys (all optional; absent means off): None when config.endgame_signature is absent or None, else a
+    dict of signature, positions, kind, simulations, interval and rescore.  A key outside its range raises XqError with the key's
+    name, whether the yardstick is on or not.  The table is generated at first use."""
+    def key(name, default):
+        v = getattr(config, name, None)
+        v = default if v is None else v
+        if isinstance(v, bool) or int(v) != v:
+            raise hip.XqError(f"config.{name} must be an integer, got {v!r}")
+        return int(v)
+
+    from . import endgame
+    sig = getattr(config, "endgame_signature", None)
+    if sig is not None:
+        try:
+            hip.tb_entries(sig)
+        except hip.XqError as e:
+            raise hip.XqError(f"config.endgame_signature: {e}") from None
+    positions = key("endgame_positions", 256)
+    if positions < 1:
+        raise hip.XqError(f"config.endgame_positions must be >= 1, got {positions}")
+    kind = getattr(config, "endgame_kind", None)
+    kind = "win" if kind is None else kind
+    if kind not in ("win", "draw"):
+        raise hip.XqError(f"config.endgame_kind must be 'win' or 'draw' (a lost position cannot be held), got {kind!r}")
+    sims = key("endgame_simulations", int(config.eval_simulations))
+    if sims < 1:
+        raise hip.XqError(f"config.endgame_simulations must be >= 1, got {sims}")
+    interval = key("endgame_interval", 1)
+    if interval < 1:
+        raise hip.XqError(f"config.endgame_interval must be >= 1, got {interval}")
+    rescore = getattr(config, "endgame_rescore", None)
+    if rescore is not None and not isinstance(rescore, bool):
+        raise hip.XqError(f"config.endgame_rescore must be a bool, got {rescore!r}")
+    if sig is None:
+        return None
+    return {"signature": endgame.signature_text(sig), "positions": positions, "kind": kind, "simulations": sims,
+            "interval": interval, "rescore": bool(rescore)}
 
 
 def _pretrain_options(config):
@@ -200,7 +244,14 @@ class AlphaZeroLoop:
         # uses no collective.  The positions are labelled on the device at first use
         self.tactics = _tactics_options(config)
         self._tactics_puzzles = None
-        torch.manual_seed(seed)                       # identical initial weights on every rank
+        # the endgame yardstick (config.endgame_signature; absent: off), read once and checked here: every endgame_interval-th
+        # iteration rank 0 scores best_model on positions of the signature's tablebase (endgame.hold_rate): it decides nothing and
+        # uses no collective.  With endgame_rescore every iteration's samples the table covers get their exact outcome before
+        # they enter the buffer.  The table is generated on the device at first use
+        self.endgame = _endgame_options(config)
+        self._endgame_tb = None
+        self._endgame_positions = None
+        torch.manual_seed(seed)                      # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
         on_gpu = self.device.type == "cuda"
@@ -283,6 +334,15 @@ class AlphaZeroLoop:
             results = xdist.all_gather_records_device(results)
             if scores is not None:
                 scores = xdist.all_gather_records_device(scores)
+        rescored = {}
+        if self.endgame is not None and self.endgame["rescore"]:
+            # after the gather: every rank holds the same samples and the same table, so every buffer gets the same bytes
+            from . import endgame
+            host = np.ascontiguousarray(samples.cpu().numpy()).reshape(-1).view(SAMPLE_DTYPE)
+            new, covered, changed = endgame.rescore_samples(host, self._endgame_table())
+            if changed:
+                samples = torch.from_numpy(new.view(np.uint8).reshape(-1, 640)).to(samples.device)
+            rescored = {"endgame_covered": covered, "endgame_changed": changed}
         self.buffer.extend(samples)
         res = results.cpu().numpy().reshape(-1).view(RESULT_DTYPE) if len(results) else np.zeros(0, RESULT_DTYPE)
         self.total_games += len(res)
@@ -292,7 +352,8 @@ class AlphaZeroLoop:
         scored = selfplay.score_summary(scores, samples) if scores is not None else {}
         return {"games": len(res), "red_wins": wins[1], "black_wins": wins[-1], "draws": wins[0],
                 "avg_steps": float(res["steps"].mean()) if len(res) else 0.0, "new_samples": 2 * int(samples.shape[0]),
-                "total_time": time.time() - t0, "num_workers": self.world, "mode": "hip", "buffer_size": len(self.buffer), **scored}
+                "total_time": time.time() - t0, "num_workers": self.world, "mode": "hip", "buffer_size": len(self.buffer), **scored,
+                **rescored}
 
     def train_network(self) -> dict:
         """World 1: the reference's step.  World > 1: the same full-batch update computed data-parallel -- every rank
@@ -373,6 +434,31 @@ class AlphaZeroLoop:
                 "by_mate_in": {str(m): v for m, v in out["by_mate_in"].items()}, "max_moves": t["max_moves"],
                 "simulations": out["simulations"], "seconds": out["seconds"]}
 
+    def _endgame_table(self):
+        """The tablebase of config.endgame_signature, generated on self.device at first use and kept."""
+        if self._endgame_tb is None:
+            from . import endgame
+            self._endgame_tb = endgame.Tablebase.generate(self.endgame["signature"], self.device)
+        return self._endgame_tb
+
+    def score_endgame(self) -> dict:
+        """best_model on endgame_positions entries of kind endgame_kind of the signature's table (endgame.hold_rate) under the
+        loop's solver and perpetual-check values, seed + iteration as the search's seed -> this iteration's "endgame" entry.  The
+        first call generates the table and draws the positions (the loop's seed); a table with fewer such entries gives all of
+        them."""
+        from . import endgame
+        e = self.endgame
+        tb = self._endgame_table()
+        if self._endgame_positions is None:
+            t = tb.table
+            have = int((t > 0).sum()) if e["kind"] == "win" else int((t == 0).sum())
+            boards, sides, _ = tb.positions(e["kind"], min(e["positions"], have), seed=self.seed)
+            self._endgame_positions = (boards, sides)
+        out = endgame.hold_rate(self.best_model, tb, *self._endgame_positions, e["simulations"], c_puct=float(self.config.c_puct),
+                                solver=self.solver, perpetual_check=self.perpetual_check, seed=self.seed + self.iteration,
+                                evaluator_kind=self.evaluator_kind)
+        return {"signature": e["signature"], "kind": e["kind"], **{k: v for k, v in out.items() if k != "chosen"}}
+
     def pretrain_from_records(self) -> dict:
         """The supervised warm start of a fresh run: config.pretrain_epochs epochs of current_model on the samples of the games of
         config.pretrain_records (every ply after the opening of the movers chosen), then best_model takes the weights.  Every rank
@@ -450,11 +536,15 @@ class AlphaZeroLoop:
             tc = None
             if self.tactics is not None and self.rank == 0 and iteration % self.tactics["interval"] == 0:
                 tc = self.score_tactics()
+            eg = None
+            if self.endgame is not None and self.rank == 0 and iteration % self.endgame["interval"] == 0:
+                eg = self.score_endgame()
             if iteration % cfg.save_interval == 0:
                 self._save(iteration)
             self.training_stats.append({"iteration": iteration, "time": time.time() - t0, "self_play": sp,
                                         "training": tr, "evaluation": ev, **({} if bl is None else {"baseline": bl}),
                                         **({} if tc is None else {"tactics": tc}),
+                                        **({} if eg is None else {"endgame": eg}),
                                         **({} if pre is None else {"pretrain": pre})})
             pre = None
             if self.rank == 0:
