@@ -1399,6 +1399,49 @@ int xq_tb_probe_batch(const int8_t *pieces, int n_pieces, const int16_t *dev_tab
                       int16_t *dev_move_value /* [n][XQ_MAXM] or NULL */, uint16_t *dev_best_action /* [n] */,
                       uint8_t *dev_status /* [n] */, void *stream);
 
+/* The table as opponent and as teacher (opt-in; xq_tb_init, xq_tb_pass and xq_tb_probe_batch are what they were, byte for byte).
+ * Both calls run one wavefront per item, four per workgroup, LDS carved per wave, no atomics, no scratch, no workgroup barrier;
+ * neither synchronises or allocates, and launches go over chunks as the probe's do.
+ * xq_tb_play_batch   one move per position.  The board is matched against the signature exactly as xq_tb_probe_batch matches it,
+ *             and status bits 1, 2 and 4 have the probe's meaning.  dev_action[i] is the move to play, or XQ_TB_NO_MOVE: the table
+ *             chooses the probe's best_action, the first move in move order whose move value equals the position's value (the
+ *             quickest win, a draw-holding move, or the longest defence).  dev_action == NULL: the table chooses everywhere.
+ *   dev_status[i]   the probe's bits, and +8 the position has no legal move; +16 the given action is not among the position's
+ *                   ordered legal moves.
+ *             With status 0: dev_boards_out[i] = the board after the move (`to` takes the man of `from`, `from` becomes empty),
+ *             dev_side_out[i] = -side, dev_played[i] = the action, dev_value[i] = the entry's value before the move,
+ *             dev_move_value[i] = what the mover gets by it (the probe's convention), dev_value_out[i] = the child entry's table
+ *             word, from the new side's view.  With any bit set: dev_boards_out[i] and dev_side_out[i] copy the input, dev_played[i]
+ *             = XQ_TB_NO_MOVE, dev_move_value[i] = dev_value_out[i] = 0, and dev_value[i] is the entry's value when only bits 8 or
+ *             16 are set, else 0.  Every output word is written for every item.
+ *   ALIASING  dev_boards_out may be dev_boards and dev_side_out may be dev_side (the same pointers, for a walk in place): a
+ *             wavefront reads its item's board and side into LDS and registers before it writes them, and touches no other item's.
+ * xq_tb_samples   table entries as xq_sample rows.  Row i is entry dev_index[i], decoded as xq_tb_pass decodes it; all 640 bytes
+ *             are written, with 16-byte vector stores as xq_records_to_samples writes its rows: board and side the entry's; z the
+ *             sign of the entry's value; n_moves and actions[0 .. n_moves) the ordered legal moves; visits[j] = 1 where move j's
+ *             value equals the entry's value (policy 1: only at the first such j), else 0; ply, late_temp, reserved0, reserved1
+ *             and slot = 0; game_seq = the entry index (a unique identity for the Philox-keyed draws over samples); pad and the
+ *             tails of actions and visits zero.
+ *   dev_status[i]   0 written; 1 the index is outside [0, entries); 4 the entry is XQ_TB_INVALID; 8 the entry has no legal move,
+ *                   so there is no policy target.  With a non-zero status the row is 640 zero bytes, the zero-row convention of
+ *                   xq_records_to_samples.
+ * XQ_ERR_ARG before any launch (no GPU needed): n < 0; a bad signature; with n > 0 a NULL pointer (dev_action may be NULL);
+ * xq_tb_samples: opts NULL, policy outside {0, 1}, a non-zero reserved word, dev_samples not 16-byte aligned.  n = 0 is a no-op
+ * returning 0. */
+typedef struct xq_tb_sample_opts {
+    int32_t policy;        /* 0: every optimal move is a policy target; 1: the first one in move order */
+    int32_t reserved[3];
+} xq_tb_sample_opts;
+int xq_tb_play_batch(const int8_t *pieces, int n_pieces, const int16_t *dev_table /* [entries] */,
+                     const int8_t *dev_boards /* [n][90] */, const int8_t *dev_side /* [n] */,
+                     const uint16_t *dev_action /* [n] or NULL; XQ_TB_NO_MOVE: the table chooses */, int n,
+                     int8_t *dev_boards_out /* [n][90], may alias dev_boards */, int8_t *dev_side_out /* [n], may alias dev_side */,
+                     uint16_t *dev_played /* [n] */, int16_t *dev_value /* [n] */, int16_t *dev_move_value /* [n] */,
+                     int16_t *dev_value_out /* [n] */, uint8_t *dev_status /* [n] */, void *stream);
+int xq_tb_samples(const int8_t *pieces, int n_pieces, const int16_t *dev_table /* [entries] */, const int32_t *dev_index /* [n] */,
+                  int n, const xq_tb_sample_opts *opts, void *dev_samples /* xq_sample[n], 16-byte aligned */,
+                  uint8_t *dev_status /* [n] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

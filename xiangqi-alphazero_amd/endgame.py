@@ -9,7 +9,12 @@ in p plies, from the view of the side to move, under the move generator's rules 
 `parse_signature`, `index_to_board` and `board_to_index` are the numpy reference of the index layout, vectorised over an index
 array.  `Tablebase` generates, saves, loads, probes and draws positions.  `hold_rate` runs one search-only `MCTS` over positions
 of a table (`search_many`: move count 0, no history, no noise) and asks the probe about the move the search chose.
-`rescore_samples` replaces the game outcome of every sample the table covers by the exact one."""
+`rescore_samples` replaces the game outcome of every sample the table covers by the exact one.
+
+The table is also an opponent and a teacher.  `Tablebase.play` applies one move per position on the
+device, the table's best or the caller's; `play_out_with` plays won endings out against the table's best defence, and `play_out`
+does so with one search-only `MCTS` choosing the winner's moves.  `Tablebase.entries_of` draws entries, and `Tablebase.samples`
+turns them into training samples whose policy target is the optimal moves and whose value target is the exact outcome."""
 from __future__ import annotations
 
 import time
@@ -258,8 +263,89 @@ class Tablebase:
         return boards, sides, pick
 
 
+    def play(self, boards, sides, actions=None) -> Dict[str, np.ndarray]:
+        """`hip.tb_play_batch` over host positions -> host arrays: boards and side after the move, played (uint16), value,
+        move_value, value_out and status.  `actions` None: the table plays its best move everywhere; else one action per position,
+        NO_MOVE (or -1) where the table chooses."""
+        b, s = _positions(boards, sides)
+        table = self.device_table()
+        act = None
+        if actions is not None:
+            a = np.asarray(actions, dtype=np.int64).reshape(-1)
+            if len(a) != len(b) or bool(((a < -1) | (a > NO_MOVE)).any()):
+                raise hip.XqError(f"play: actions must hold one action in [0, {NO_MOVE}] (or -1) per position ({len(b)}), got "
+                                  f"{len(a)} values in [{a.min() if len(a) else 0}, {a.max() if len(a) else 0}]")
+            act = torch.from_numpy((a & 0xFFFF).astype(np.uint16).view(np.int16)).to(table.device)
+        with torch.cuda.device(table.device):
+            r = hip.tb_play_batch(self.codes, table, torch.from_numpy(b).to(table.device), torch.from_numpy(s).to(table.device), act)
+            r = {k: v.cpu().numpy() for k, v in r.items()}
+        r["played"] = r["played"].view(np.uint16)
+        return r
+
+    def entries_of(self, kinds=KINDS, n: int = 256, seed: int = 0, side=None, min_plies: int = 0):
+        """`positions` over several kinds at once, for entries one can move from: a seeded draw without replacement of `n` valid
+        entries that have a legal move and whose kind ("win", "draw" or "loss" for the side to move) is in `kinds`, decoded ->
+        (boards int8[n, 90], sides int8[n], index int64[n]), in ascending index order.  `side` (1 red, -1 black) keeps one side to
+        move; `min_plies` keeps wins and losses of at least that many plies.  Fewer than n such entries: XqError."""
+        kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+        if not kinds or any(k not in KINDS for k in kinds):
+            raise hip.XqError(f"entries_of: kinds must be taken from {KINDS}, got {kinds!r}")
+        if side not in (None, 1, -1):
+            raise hip.XqError(f"entries_of: side must be None, 1 or -1, got {side!r}")
+        if isinstance(n, bool) or int(n) != n or int(n) < 0:
+            raise hip.XqError(f"entries_of: n must be an integer >= 0, got {n!r}")
+        if isinstance(min_plies, bool) or int(min_plies) != min_plies or int(min_plies) < 0:
+            raise hip.XqError(f"entries_of: min_plies must be an integer >= 0, got {min_plies!r}")
+        t = self.table.astype(np.int64)
+        keep = np.zeros(len(t), dtype=bool)
+        if "win" in kinds:
+            keep |= t >= max(int(min_plies), 1)
+        if "loss" in kinds:           # -1 is a loss in 0 plies: no legal move
+            keep |= (t != INVALID) & (t < -1) & (-t - 1 >= int(min_plies))
+        if "draw" in kinds:
+            keep |= t == 0
+        half = len(t) // 2
+        if side == 1:
+            keep[half:] = False
+        elif side == -1:
+            keep[:half] = False
+        pool = np.nonzero(keep)[0]
+        if len(pool) < int(n):
+            raise hip.XqError(f"entries_of: {self.signature!r} holds {len(pool)} such entries of {kinds}, {n} were asked for")
+        pick = np.sort(np.random.default_rng(int(seed)).choice(pool, size=int(n), replace=False))
+        boards, sides = index_to_board(self.codes, pick)
+        return boards, sides, pick
+
+    def samples(self, index, policy: int = 0, invalid: str = "raise", as_tensor: bool = False):
+        """`hip.tb_samples` over the entries `index` -> SAMPLE_DTYPE rows on the host, or with as_tensor the uint8[m, 640] device
+        tensor that `ReplayBuffer.extend` takes.  An entry that gives no sample (an index outside the table, an invalid entry, one
+        without a legal move) is refused by name (invalid="raise") or left out (invalid="drop"), as `rows_from_records` treats a
+        record that does not convert."""
+        if invalid not in ("raise", "drop"):
+            raise hip.XqError(f"samples: invalid must be 'raise' or 'drop', got {invalid!r}")
+        idx = np.asarray(index).reshape(-1)
+        if idx.dtype.kind not in "iu":
+            raise hip.XqError(f"samples: index must hold integers, got {idx.dtype}")
+        idx = idx.astype(np.int64)
+        inside = (idx >= 0) & (idx < len(self.table))
+        table = self.device_table()
+        with torch.cuda.device(table.device):
+            rows, status = hip.tb_samples(self.codes, table, torch.from_numpy(np.where(inside, idx, -1).astype(np.int32)).to(table.device),
+                                          policy)
+            bad = torch.nonzero(status != 0).reshape(-1)
+            if int(bad.numel()):
+                if invalid == "raise":
+                    i = int(bad[0].item())
+                    why = {1: "is outside the table", 4: "is no position", 8: "has no legal move"}[int(status[i].item())]
+                    raise hip.XqError(f"samples: entry {int(idx[i])} of {self.signature!r} {why} ({int(bad.numel())} of {len(idx)} "
+                                      "entries give no sample; invalid='drop' leaves them out)")
+                rows = rows[status == 0]
+            if as_tensor:
+                return rows
+            return rows.cpu().numpy().reshape(-1).view(SAMPLE_DTYPE)
+
 class _Position:
-    """One position as `MCTS.search_many` takes it: the start of a game, nothing behind it."""
+    """One position as `MCTS.search_many` takes it: the start of a game, nothing behind it, until `push` plays a move."""
 
     def __init__(self, board, side):
         self.board = board
@@ -267,6 +353,35 @@ class _Position:
         self.move_count = 0
         self.no_capture_count = 0
         self.history = []
+
+    def push(self, action: int, board_after) -> None:
+        """One ply of a play-out: the board before it joins the history, the counters move on as a game's do."""
+        self.history.append(np.ascontiguousarray(self.board, dtype=np.int8).tobytes())
+        self.no_capture_count = 0 if self.board[int(action) % 90] != 0 else self.no_capture_count + 1
+        self.board = board_after
+        self.current_player = -self.current_player
+        self.move_count += 1
+
+
+def _searched_moves(mcts, games, width: int, solver: bool, what: str):
+    """The move one search-only `MCTS` gives every game of `games`, `width` at a time (the last chunk padded with its first game):
+    the first maximum of the visits in move order, or `solver_choice` under `solver`."""
+    from .mcts import solver_choice
+    chosen = np.zeros(len(games), dtype=np.int64)
+    for base in range(0, len(games), width):
+        part = list(games[base:base + width])
+        count = len(part)
+        mcts.search_many(part + [part[0]] * (width - count), temperature=1.0, add_noise=False)
+        eng = mcts._engine(width, False)
+        for slot in range(count):
+            r = eng.read_root(slot)
+            if len(r["actions"]) == 0:
+                raise hip.XqError(f"{what}: a position has no legal move")
+            if solver:
+                chosen[base + slot] = solver_choice(r["actions"], r["visits"], eng.read_root_states(slot)["children"])
+            else:
+                chosen[base + slot] = int(r["actions"][int(np.argmax(r["visits"]))])
+    return chosen
 
 
 def score(probe: Dict[str, np.ndarray], chosen) -> Dict[str, object]:
@@ -298,7 +413,7 @@ def hold_rate(model_or_evaluator, tb: Tablebase, boards, sides, num_simulations:
     the first maximum of the visits in move order, or `solver_choice` under `solver`; the probe's move value scores it (`score`).
     Refused: a position the table does not cover, an invalid one, a lost one.  -> positions, held, optimal, hold_rate, by_kind,
     simulations, seconds, chosen (the action per position)."""
-    from .mcts import MCTS, solver_choice
+    from .mcts import MCTS
     t0 = time.time()
     if not isinstance(tb, Tablebase):
         raise hip.XqError(f"hold_rate: tb must be a Tablebase, got {type(tb).__name__}")
@@ -319,23 +434,116 @@ def hold_rate(model_or_evaluator, tb: Tablebase, boards, sides, num_simulations:
         device = tb.device_table().device
         mcts = MCTS(model_or_evaluator, int(num_simulations), c_puct, device, evaluator_kind, seed=int(seed),
                     perpetual_check=perpetual_check, solver=solver)
-        width = min(int(chunk), n)
         with torch.cuda.device(device):
-            for base in range(0, n, width):
-                games = [_Position(b[j], s[j]) for j in range(base, min(base + width, n))]
-                count = len(games)
-                mcts.search_many(games + [games[0]] * (width - count), temperature=1.0, add_noise=False)
-                eng = mcts._engine(width, False)
-                for slot in range(count):
-                    r = eng.read_root(slot)
-                    if len(r["actions"]) == 0:
-                        raise hip.XqError("hold_rate: a position has no legal move")
-                    if solver:
-                        chosen[base + slot] = solver_choice(r["actions"], r["visits"], eng.read_root_states(slot)["children"])
-                    else:
-                        chosen[base + slot] = int(r["actions"][int(np.argmax(r["visits"]))])
+            chosen = _searched_moves(mcts, [_Position(b[j], s[j]) for j in range(n)], min(int(chunk), n), solver, "hold_rate")
     return {**score(probe, chosen), "simulations": int(num_simulations), "seconds": time.time() - t0, "chosen": chosen}
 
+
+OUTCOMES = ("converted", "dropped", "repeated", "unfinished")
+
+
+def play_out_with(choose, tb: Tablebase, boards, sides, max_plies: int) -> Dict[str, object]:
+    """Won endings played out against the table's best defence, one game per position.  `choose(games)` returns one action per
+    game for the side that is winning (`games` carry board, current_player, move_count, no_capture_count and history as
+    `MCTS.search_many` reads them, counted from the start of the play-out); the table answers through `Tablebase.play`.  A game
+    ends converted (the defender has no move), dropped (the mover's move has a value <= 0: the table defends perfectly, so the
+    win is gone for good), repeated (a mover-to-move position of this game recurs) or unfinished (`max_plies` plies played and
+    still won).  Refused: a position that is not a won entry of the table, max_plies < 1, a chosen action that is no legal move.
+    -> positions, the four counts, conversion_rate, conversion_se (binomial), mean_plies_ratio (plies used over the table's
+    distance, over the converted games; 0.0 without one) and games: per game its outcome, plies, distance (the table's at the
+    start) and moves (every ply, both sides')."""
+    if not isinstance(tb, Tablebase):
+        raise hip.XqError(f"play_out_with: tb must be a Tablebase, got {type(tb).__name__}")
+    if isinstance(max_plies, bool) or int(max_plies) != max_plies or int(max_plies) < 1:
+        raise hip.XqError(f"play_out_with: max_plies must be an integer >= 1, got {max_plies!r}")
+    b, s = _positions(boards, sides)
+    n = len(b)
+    start = tb.probe(b, s, move_values=False) if n else {"status": np.zeros(0, np.uint8), "value": np.zeros(0, np.int16)}
+    if bool((start["status"] != 0).any()):
+        raise hip.XqError(f"play_out_with: {int((start['status'] != 0).sum())} positions are not valid entries of {tb.signature!r}")
+    if bool((start["value"] <= 0).any()):
+        raise hip.XqError(f"play_out_with: {int((start['value'] <= 0).sum())} positions are drawn or lost for the side to move; "
+                          "only won positions can be played out")
+    games = [_Position(b[j].copy(), s[j]) for j in range(n)]
+    seen = [{g.board.tobytes()} for g in games]
+    report = [{"outcome": None, "plies": 0, "distance": int(start["value"][j]), "moves": []} for j in range(n)]
+    live = list(range(n))
+
+    def end(j, outcome):
+        report[j]["outcome"], report[j]["plies"] = outcome, games[j].move_count
+
+    while live:
+        acts = np.asarray(choose([games[j] for j in live]), dtype=np.int64).reshape(-1)
+        if len(acts) != len(live):
+            raise hip.XqError(f"play_out_with: choose returned {len(acts)} actions for {len(live)} games")
+        r = tb.play(np.stack([games[j].board for j in live]), [games[j].current_player for j in live], acts)
+        if bool((r["status"] != 0).any()):
+            k = int(np.nonzero(r["status"] != 0)[0][0])
+            raise hip.XqError(f"play_out_with: action {int(acts[k])} is no legal move of game {live[k]} at ply "
+                              f"{games[live[k]].move_count} (status {int(r['status'][k])})")
+        defend = []
+        for k, j in enumerate(live):
+            games[j].push(int(acts[k]), r["boards"][k].copy())
+            report[j]["moves"].append(int(acts[k]))
+            if r["move_value"][k] <= 0:
+                end(j, "dropped")
+            elif r["value_out"][k] == -1:
+                end(j, "converted")
+            elif games[j].move_count >= int(max_plies):
+                end(j, "unfinished")
+            else:
+                defend.append(j)
+        live = []
+        if defend:
+            r = tb.play(np.stack([games[j].board for j in defend]), [games[j].current_player for j in defend])
+            for k, j in enumerate(defend):
+                games[j].push(int(r["played"][k]), r["boards"][k].copy())
+                report[j]["moves"].append(int(r["played"][k]))
+                key = games[j].board.tobytes()
+                if key in seen[j]:
+                    end(j, "repeated")
+                elif games[j].move_count >= int(max_plies):
+                    end(j, "unfinished")
+                else:
+                    seen[j].add(key)
+                    live.append(j)
+    counts = {o: sum(1 for g in report if g["outcome"] == o) for o in OUTCOMES}
+    rate = counts["converted"] / n if n else 0.0
+    ratios = [g["plies"] / g["distance"] for g in report if g["outcome"] == "converted"]
+    return {"positions": n, **counts, "conversion_rate": rate, "conversion_se": float(np.sqrt(rate * (1.0 - rate) / n)) if n else 0.0,
+            "mean_plies_ratio": float(np.mean(ratios)) if ratios else 0.0, "games": report}
+
+
+def play_out(model_or_evaluator, tb: Tablebase, boards, sides, num_simulations: int, max_plies: int = 100, c_puct: float = 1.5,
+             solver: bool = False, perpetual_check: bool = False, seed: int = 0, chunk: int = 256,
+             evaluator_kind: str = "hip") -> Dict[str, object]:
+    """`play_out_with` with one search-only `MCTS` of `num_simulations` simulations choosing the winner's moves as `hold_rate`
+    chooses them (the first maximum of the visits in move order, or `solver_choice` under `solver`), except that every search
+    sees its game's move count, no-capture count and history.  -> play_out_with's result and simulations, max_plies, seconds."""
+    from .mcts import MCTS
+    t0 = time.time()
+    if not isinstance(tb, Tablebase):
+        raise hip.XqError(f"play_out: tb must be a Tablebase, got {type(tb).__name__}")
+    if int(num_simulations) < 1:
+        raise hip.XqError(f"play_out: num_simulations must be >= 1, got {num_simulations}")
+    if int(chunk) < 1:
+        raise hip.XqError(f"play_out: chunk must be >= 1, got {chunk}")
+    if isinstance(max_plies, bool) or int(max_plies) != max_plies or int(max_plies) < 1:
+        raise hip.XqError(f"play_out: max_plies must be an integer >= 1, got {max_plies!r}")
+    b, s = _positions(boards, sides)
+    device = tb.device_table().device
+    width = max(1, min(int(chunk), len(b)))
+    mcts = []
+
+    def choose(games):
+        if not mcts:            # built at the first move: a refused set of positions builds no engine
+            mcts.append(MCTS(model_or_evaluator, int(num_simulations), c_puct, device, evaluator_kind, seed=int(seed),
+                             perpetual_check=perpetual_check, solver=solver))
+        with torch.cuda.device(device):
+            return _searched_moves(mcts[0], games, width, solver, "play_out")
+
+    out = play_out_with(choose, tb, b, s, int(max_plies))
+    return {**out, "simulations": int(num_simulations), "max_plies": int(max_plies), "seconds": time.time() - t0}
 
 def rescore_samples(samples, tb: Tablebase):
     """-> (new array, covered, changed): a copy of `samples` (SAMPLE_DTYPE) in which every record whose position the table covers

@@ -180,6 +180,11 @@ class SuperviseOpts(C.Structure):
     _fields_ = [("movers", C.c_int32), ("skip_opening", C.c_int32), ("skip_draws", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TbSampleOpts(C.Structure):
+    """xq_tb_sample_opts: table entries as samples (xq_tb_samples): policy 0 every optimal move is a target, 1 the first one."""
+    _fields_ = [("policy", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class MateOpts(C.Structure):
     """xq_mate_opts: the forced-mate search (xq_mate_search_batch): N attacker moves, checks only 0 / 1, visits per root move."""
     _fields_ = [("max_moves", C.c_int32), ("checks_only", C.c_int32), ("node_limit", C.c_uint32), ("reserved", C.c_uint32)]
@@ -410,6 +415,8 @@ def lib():
     L.xq_tb_init.argtypes = [vp, i32, vp, vp]
     L.xq_tb_pass.argtypes = [vp, i32, vp, i32, vp, vp]
     L.xq_tb_probe_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.xq_tb_play_batch.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.xq_tb_samples.argtypes = [vp, i32, vp, vp, i32, C.POINTER(TbSampleOpts), vp, vp, vp]
     _lib = L
     return L
 
@@ -441,7 +448,7 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_samples_to_requests", "xq_score_samples", "xq_surprise_counts", "xq_surprise_count_host",
            "xq_position_keys", "xq_position_key_host", "xq_position_group_heads", "xq_groups_to_batch",
            "xq_alphabeta_batch", "xq_records_sample_counts", "xq_records_to_samples", "xq_mate_search_batch",
-           "xq_tb_entries", "xq_tb_init", "xq_tb_pass", "xq_tb_probe_batch"]
+           "xq_tb_entries", "xq_tb_init", "xq_tb_pass", "xq_tb_probe_batch", "xq_tb_play_batch", "xq_tb_samples"]
 
 
 def check(rc: int, what: str):
@@ -802,6 +809,64 @@ def tb_probe_batch(signature, table: torch.Tensor, boards: torch.Tensor, side: t
                                       _dev(out["counts"]), _dev(out["move_value"]) if move_values else None,
                                       _dev(out["best_action"]), _dev(out["status"]), stream_ptr(dev)), "xq_tb_probe_batch")
     return out
+
+
+def tb_play_batch(signature, table: torch.Tensor, boards: torch.Tensor, side: torch.Tensor, action=None, out=None):
+    """One move per position (xq_tb_play_batch): boards int8[n,90] (or [n,10,9]) and side int8[n] on the table's device; action
+    None (the table plays its best move everywhere) or int16[n] there holding uint16 action ids, TB_NO_MOVE (-1) where the table
+    chooses -> dict of device tensors: boards int8[n,90] and side int8[n] after the move, played (u16-as-int16 [n]; TB_NO_MOVE
+    reads -1), value int16[n] (the entry's before the move), move_value int16[n] (what the mover gets by it), value_out int16[n]
+    (the new entry's, from the new side's view), status uint8[n] (the probe's bits, +8 no legal move, +16 the action is no legal
+    move; with any bit the position is copied and nothing is played).  `out` = such a dict to write into; its boards and side may
+    be the inputs themselves (a walk in place)."""
+    codes, _ = _tb_table_arg(signature, table, "tb_play_batch")
+    n, _ = _positions_arg(boards, side, "tb_play_batch")
+    dev = table.device
+    if n and (boards.device != dev or side.device != dev):
+        raise XqError(f"tb_play_batch: boards and side must be on the table's device {dev}, got {boards.device} and {side.device}")
+    if action is not None and (not isinstance(action, torch.Tensor) or action.dtype != torch.int16 or tuple(action.shape) != (n,) or
+                               (n and action.device != dev)):
+        got = (action.dtype, tuple(action.shape), action.device) if isinstance(action, torch.Tensor) else type(action).__name__
+        raise XqError(f"tb_play_batch: action must be None or int16[{n}] on the table's device, got {got}")
+    shapes = {"boards": ((n, 90), torch.int8), "side": ((n,), torch.int8), "played": ((n,), torch.int16), "value": ((n,), torch.int16),
+              "move_value": ((n,), torch.int16), "value_out": ((n,), torch.int16), "status": ((n,), torch.uint8)}
+    if out is None:
+        out = {k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+    else:
+        for k, (shape, dt) in shapes.items():
+            t = out.get(k) if isinstance(out, dict) else None
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != n * (90 if k == "boards" else 1) or (n and t.device != dev):
+                raise XqError(f"tb_play_batch: out[{k!r}] must be a {dt} tensor of shape {shape} on the table's device")
+    if n:
+        arr, P = _tb_pieces(codes)
+        check(lib().xq_tb_play_batch(arr, P, _dev(table), _dev(boards), _dev(side), None if action is None else _dev(action), n,
+                                     _dev(out["boards"]), _dev(out["side"]), _dev(out["played"]), _dev(out["value"]),
+                                     _dev(out["move_value"]), _dev(out["value_out"]), _dev(out["status"]), stream_ptr(dev)),
+              "xq_tb_play_batch")
+    return out
+
+
+def tb_samples(signature, table: torch.Tensor, index: torch.Tensor, policy: int = 0):
+    """Table entries as training samples (xq_tb_samples): index int32[n] on the table's device -> (samples uint8[n, 640], status
+    uint8[n]) there.  Row i is entry index[i]: its board and side, z the sign of its value, the ordered legal moves, one visit at
+    every optimal move (policy 0) or at the first one (policy 1), game_seq the entry index.  status 0 written; 1 the index is
+    outside the table; 4 an invalid entry; 8 no legal move: such a row is 640 zero bytes."""
+    codes, _ = _tb_table_arg(signature, table, "tb_samples")
+    if isinstance(policy, bool) or not isinstance(policy, int) or policy not in (0, 1):
+        raise XqError(f"tb_samples: policy must be 0 (every optimal move) or 1 (the first one), got {policy!r}")
+    dev = table.device
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or (len(index) and index.device != dev):
+        got = (index.dtype, tuple(index.shape), index.device) if isinstance(index, torch.Tensor) else type(index).__name__
+        raise XqError(f"tb_samples: index must be int32[n] on the table's device, got {got}")
+    n = len(index)
+    rows = torch.empty((n, SAMPLE_BYTES), dtype=torch.uint8, device=dev)
+    status = torch.zeros(n, dtype=torch.uint8, device=dev)
+    if n:
+        arr, P = _tb_pieces(codes)
+        opts = TbSampleOpts(int(policy), (C.c_int32 * 3)(0, 0, 0))
+        check(lib().xq_tb_samples(arr, P, _dev(table), _dev(index), n, C.byref(opts), _dev(rows), _dev(status), stream_ptr(dev)),
+              "xq_tb_samples")
+    return rows, status
 
 
 def _records_arg(samples: torch.Tensor, what: str):

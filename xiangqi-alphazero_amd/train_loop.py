@@ -21,7 +21,9 @@ Per iteration, exactly the reference's order:
   3d. endgame      opt-in (`config.endgame_signature`): every `endgame_interval`-th iteration rank 0 scores the best model on
                    won (or drawn) positions of the signature's tablebase (`endgame.hold_rate`) and logs the result under
                    "endgame"; it decides nothing.  With `endgame_rescore` the samples the table covers get their exact outcome
-                   before they enter the buffer (`endgame.rescore_samples`);
+                   before they enter the buffer (`endgame.rescore_samples`).  With `endgame_playout_positions` rank 0 also plays
+                   won entries out against the table's best defence (`endgame.play_out`, logged under "endgame_playout"), and with
+                   `endgame_teacher_samples` every rank appends that many table samples to its buffer after self-play's;
   4. checkpoint    every `save_interval` iterations and once more after the last one (train.py:613-615, 636-637), the
                    reference's file format; `training_stats.json` like train.py:620-634.
 `resume(path)` is the reference's `--resume` (train.py:569-579, 759-761): iteration, total_games, both models, optimizer
@@ -157,6 +159,36 @@ def _endgame_options(config):
             "interval": interval, "rescore": bool(rescore)}
 
 
+def _endgame_play_options(config):
+    """The keys that use the table as opponent and as teacher (all optional; absent means off) -> (playout, teacher): playout None
+    or a dict of positions and max_plies (config.endgame_playout_positions, endgame_playout_max_plies); teacher None or a dict of
+    samples and policy (config.endgame_teacher_samples, endgame_teacher_policy).  Both need config.endgame_signature.  A key
+    outside its range raises XqError with the key's name."""
+    def key(name):
+        v = getattr(config, name, None)
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+            raise hip.XqError(f"config.{name} must be an integer, got {v!r}")
+        return None if v is None else int(v)
+
+    positions, max_plies = key("endgame_playout_positions"), key("endgame_playout_max_plies")
+    samples, policy = key("endgame_teacher_samples"), key("endgame_teacher_policy")
+    if positions is not None and positions < 1:
+        raise hip.XqError(f"config.endgame_playout_positions must be >= 1, got {positions}")
+    if max_plies is not None and max_plies < 1:
+        raise hip.XqError(f"config.endgame_playout_max_plies must be >= 1, got {max_plies}")
+    if samples is not None and samples < 1:
+        raise hip.XqError(f"config.endgame_teacher_samples must be >= 1, got {samples}")
+    if policy is not None and policy not in (0, 1):
+        raise hip.XqError(f"config.endgame_teacher_policy must be 0 (every optimal move) or 1 (the first one), got {policy}")
+    if getattr(config, "endgame_signature", None) is None:
+        for name, v in (("endgame_playout_positions", positions), ("endgame_teacher_samples", samples)):
+            if v is not None:
+                raise hip.XqError(f"config.{name} needs config.endgame_signature")
+        return None, None
+    playout = None if positions is None else {"positions": positions, "max_plies": 100 if max_plies is None else max_plies}
+    teacher = None if samples is None else {"samples": samples, "policy": 0 if policy is None else policy}
+    return playout, teacher
+
 def _pretrain_options(config):
     """The supervised warm start's keys (all optional; absent means off): None when config.pretrain_records is absent or empty,
     else a dict of paths, epochs, movers, skip_draws and records (the games of every file, read here: a missing file raises at
@@ -251,6 +283,11 @@ class AlphaZeroLoop:
         self.endgame = _endgame_options(config)
         self._endgame_tb = None
         self._endgame_positions = None
+        # the table as opponent and as teacher (config.endgame_playout_positions, config.endgame_teacher_samples; absent: off):
+        # on the yardstick's iterations rank 0 also plays won entries out against the table's best defence (endgame.play_out), and
+        # every iteration every rank appends the same table samples to its buffer after self-play's
+        self.endgame_playout, self.endgame_teacher = _endgame_play_options(config)
+        self._endgame_playout_positions = None
         torch.manual_seed(seed)                      # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -344,6 +381,16 @@ class AlphaZeroLoop:
                 samples = torch.from_numpy(new.view(np.uint8).reshape(-1, 640)).to(samples.device)
             rescored = {"endgame_covered": covered, "endgame_changed": changed}
         self.buffer.extend(samples)
+        taught = {}
+        if self.endgame_teacher is not None:
+            # seeded by the loop's seed and the iteration, no rank term: every rank appends the same rows, so the buffers stay
+            # identical without a collective
+            tb = self._endgame_table()
+            have = int(((tb.table != -1) & (tb.table != hip.TB_INVALID)).sum())
+            index = tb.entries_of(n=min(self.endgame_teacher["samples"], have), seed=self.seed + self.iteration)[2]
+            rows = tb.samples(index, self.endgame_teacher["policy"], as_tensor=True)
+            self.buffer.extend(rows)
+            taught = {"endgame_teacher_samples": int(rows.shape[0])}
         res = results.cpu().numpy().reshape(-1).view(RESULT_DTYPE) if len(results) else np.zeros(0, RESULT_DTYPE)
         self.total_games += len(res)
         wins = {1: 0, -1: 0, 0: 0}
@@ -353,7 +400,7 @@ class AlphaZeroLoop:
         return {"games": len(res), "red_wins": wins[1], "black_wins": wins[-1], "draws": wins[0],
                 "avg_steps": float(res["steps"].mean()) if len(res) else 0.0, "new_samples": 2 * int(samples.shape[0]),
                 "total_time": time.time() - t0, "num_workers": self.world, "mode": "hip", "buffer_size": len(self.buffer), **scored,
-                **rescored}
+                **rescored, **taught}
 
     def train_network(self) -> dict:
         """World 1: the reference's step.  World > 1: the same full-batch update computed data-parallel -- every rank
@@ -459,6 +506,22 @@ class AlphaZeroLoop:
                                 evaluator_kind=self.evaluator_kind)
         return {"signature": e["signature"], "kind": e["kind"], **{k: v for k, v in out.items() if k != "chosen"}}
 
+    def play_out_endgame(self) -> dict:
+        """best_model playing endgame_playout_positions won entries of the signature's table out against the table's best
+        defence (endgame.play_out) with the yardstick's simulations, under the loop's solver and perpetual-check values, seed +
+        iteration as the search's seed -> this iteration's "endgame_playout" entry.  The first call draws the entries (the
+        loop's seed); a table with fewer won entries gives all of them."""
+        from . import endgame
+        e, p = self.endgame, self.endgame_playout
+        tb = self._endgame_table()
+        if self._endgame_playout_positions is None:
+            boards, sides, _ = tb.entries_of(("win",), min(p["positions"], int((tb.table > 0).sum())), seed=self.seed)
+            self._endgame_playout_positions = (boards, sides)
+        out = endgame.play_out(self.best_model, tb, *self._endgame_playout_positions, e["simulations"], max_plies=p["max_plies"],
+                               c_puct=float(self.config.c_puct), solver=self.solver, perpetual_check=self.perpetual_check,
+                               seed=self.seed + self.iteration, evaluator_kind=self.evaluator_kind)
+        return {"signature": e["signature"], **{k: v for k, v in out.items() if k != "games"}}
+
     def pretrain_from_records(self) -> dict:
         """The supervised warm start of a fresh run: config.pretrain_epochs epochs of current_model on the samples of the games of
         config.pretrain_records (every ply after the opening of the movers chosen), then best_model takes the weights.  Every rank
@@ -536,15 +599,18 @@ class AlphaZeroLoop:
             tc = None
             if self.tactics is not None and self.rank == 0 and iteration % self.tactics["interval"] == 0:
                 tc = self.score_tactics()
-            eg = None
+            eg = po = None
             if self.endgame is not None and self.rank == 0 and iteration % self.endgame["interval"] == 0:
                 eg = self.score_endgame()
+                if self.endgame_playout is not None:
+                    po = self.play_out_endgame()
             if iteration % cfg.save_interval == 0:
                 self._save(iteration)
             self.training_stats.append({"iteration": iteration, "time": time.time() - t0, "self_play": sp,
                                         "training": tr, "evaluation": ev, **({} if bl is None else {"baseline": bl}),
                                         **({} if tc is None else {"tactics": tc}),
                                         **({} if eg is None else {"endgame": eg}),
+                                        **({} if po is None else {"endgame_playout": po}),
                                         **({} if pre is None else {"pretrain": pre})})
             pre = None
             if self.rank == 0:
