@@ -1442,6 +1442,74 @@ int xq_tb_samples(const int8_t *pieces, int n_pieces, const int16_t *dev_table /
                   int n, const xq_tb_sample_opts *opts, void *dev_samples /* xq_sample[n], 16-byte aligned */,
                   uint8_t *dev_status /* [n] */, void *stream);
 
+/* Start-position pool (opt-in, xq_engine_init_sp): self-play games from given positions, and the check that says whether a board
+ * is a position the rules code can safely run on.
+ * THE CHECK: xq_positions_check_batch, one wavefront per position, the board in LDS, no atomics, no scratch.  dev_status[i] is a
+ * set of bits:
+ *    1  a square outside -7..7, or a side outside {1, -1}
+ *    2  a colour without exactly one king, or a king outside its palace (red rows 0-2, black rows 7-9, columns 3-5)
+ *    4  a piece on a square it can never stand on, or more of a kind than a set has: advisor and elephant on their own points
+ *       only; a red pawn never on rows 0-2 and on rows 3-4 only on columns 0, 2, 4, 6, 8, black mirrored; at most 2 of advisor,
+ *       elephant, knight, rook, cannon and 5 pawns per colour
+ *    8  the side not to move is in check (facing kings included)
+ *   16  the side to move has no legal move
+ * With bit 1 or 2 set the later bits are not evaluated and stay 0: the rules code is not run on such a board.  Bits 1, 2, 4 and 8
+ * are fatal (XQ_POSITION_FATAL); bit 16 (XQ_POSITION_NO_MOVE) is information: such a game is over at ply 0.  n == 0 is a no-op;
+ * XQ_ERR_ARG before any launch for n < 0, or for a NULL pointer with n > 0.
+ * THE ENGINE: xq_engine_workspace_bytes_sp / xq_engine_init_sp are the widest pair: everything the _gr pair takes, then the pool.
+ * NULL or n == 0 is exactly the _gr pair: the same workspace size, the same bytes, the same launches.  XQ_ERR_ARG before any
+ * launch (xq_engine_workspace_bytes_sp: 0): n < 0 or n > XQ_START_POOL_MAX; reserved != 0; and, with n > 0, prob not in (0, 1]
+ * (a NaN included), a NULL array, manual_moves != 0 (search-only and arena engines), game records enabled (a record has no room
+ * for a start position and its replay starts from the initial one); and whatever xq_engine_init_gr refuses.  It goes with every
+ * other option: leaf batching, tree reuse, the playout cap, forced playouts, Gumbel root search, the solver, root statistics, the
+ * perpetual-check rule, the evaluation cache, the evaluation mirror and graph capture.
+ * Init runs the check over the pool and returns XQ_ERR_ARG when an entry has a fatal bit: no unchecked board reaches a slot.  It
+ * then copies the pool into the workspace; the caller's arrays need not outlive the call.  Workspace: behind the engine's
+ * square-root table (behind every other option's words there), the pool as 96-byte rows (the board, its side in byte 90),
+ * int32 start_index[G] (the entry the slot's current game started from, -1 for the initial position) and 256 bytes holding n,
+ * prob and the counter; "start-position pool on" lives in the handle (pad0, bit 22).  The handle's layout and size do not change.
+ * THE DRAW for the game of a slot that will carry game_seq (the slot's previous game_seq + 1) is stateless:
+ *           x0 = philox_u64(seed, rank, slot, 11, game_seq, 0),   x1 = philox_u64(seed, rank, slot, 11, game_seq, 1)
+ * (the engine's Philox4x32-10, see the evaluation mirror above); the game starts from the pool iff (x0 >> 11) * 2^-53 < prob, at
+ * entry x1 % n.  An engine with injected draws draws the same way: the pool draw is never injected.  xq_start_pool_draw_host runs
+ * the same code on the host and returns the entry, or -1 for the initial position (also for n < 1 or a prob outside (0, 1]).
+ * A game is started by xq_engine_select, in a kernel of its own ahead of the select kernel (one more launch per step, on a pool
+ * engine only), one wavefront per slot: a slot whose game is finished has it flushed (samples with z, result, counters, exactly as
+ * the select kernel does), then the draw is made.  Not from the pool: the select kernel that follows starts the game as ever
+ * (quota, random opening, its draws).  From the pool: the game takes its ticket of games_target (none left: the slot idles),
+ * game_seq + 1, no samples, the entry's board and side, move_count 0, no_capture 0, an empty history -- no random opening and no
+ * draw of the opening's streams -- and the select kernel issues its root request.  An entry without a legal move therefore
+ * finishes at ply 0 with no sample.  max_game_length, temperature_threshold and the rules' own limits count from the pool position.
+ * xq_engine_start_indices: the device address of start_index.  xq_engine_start_pool_stats_read: synchronises; pool_games counts
+ * the games started from the pool.  Both return XQ_ERR_ARG on an engine without the option. */
+#define XQ_POSITION_FATAL 15
+#define XQ_POSITION_NO_MOVE 16
+#define XQ_START_POOL_MAX (1 << 20)
+#define XQ_RNG_KIND_START_POOL 11
+typedef struct xq_start_pool {
+    const int8_t *dev_boards;    /* [n][90] */
+    const int8_t *dev_side;      /* [n] */
+    int32_t n;
+    int32_t reserved;
+    double prob;                 /* a new game starts from the pool with this probability, (0, 1] */
+} xq_start_pool;
+typedef struct xq_start_pool_stats { uint64_t pool_games, reserved[3]; } xq_start_pool_stats;
+int xq_positions_check_batch(const int8_t *dev_boards /* [n][90] */, const int8_t *dev_side /* [n] */, int n,
+                             uint8_t *dev_status /* [n] */, void *stream);
+size_t xq_engine_workspace_bytes_sp(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                                    const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records,
+                                    const xq_start_pool *pool);
+int xq_engine_init_sp(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                      const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records, const xq_start_pool *pool, void *ws,
+                      size_t ws_bytes, const uint64_t *dev_inject, void *stream);
+int xq_start_pool_draw_host(uint64_t seed, int rank, int slot, uint32_t game_seq, int n, double prob);
+int xq_engine_start_indices(const xq_engine *eng, const int32_t **dev_index /* [n_games] */);
+int xq_engine_start_pool_stats_read(const xq_engine *eng, xq_start_pool_stats *host_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

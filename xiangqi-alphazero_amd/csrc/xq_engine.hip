@@ -25,6 +25,8 @@
 //                (parallel_selfplay.py:110-121), backup along the recorded path (mcts.py:66-73).
 //   k_flush_records : game records (opt-in, xq_engine_init_gr): the record of every finished game, ahead of the select kernel
 //                that starts the slot's next game; the moves themselves are logged by the select kernels (slot_log_move).
+//   k_start_pool : start-position pool (opt-in, xq_engine_init_sp): the games that start from a pool entry, ahead of the select
+//                kernel, which starts the others and issues every root request.
 //   k_reroot : tree reuse (opt-in, XQ_ENGINE_TREE_REUSE; k_select<true> / k_expand<true>): the chosen child's subtree moved to the
 //                front of the slot's arena, in place, between select and expand of the step that ends a move.
 //
@@ -1709,6 +1711,56 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_flush_records(Dev E) {
     }
 }
 
+// Start-position pool (xq_engine_init_sp): one wavefront per slot, launched ahead of the select kernel.  A slot that stands at
+// PH_FINISHED, or at PH_NEWGAME with its stagger run down, is where a game begins: the finished game is flushed as the select
+// kernel flushes it, then the stateless draw for the game that will carry game_seq + 1 says where from.  Not from the pool: the
+// slot is left at PH_NEWGAME and the select kernel starts the game as ever.  From the pool: what slot_new_game does, with the
+// entry in place of the initial board and no opening -- the quota ticket, the new game's state words, the entry's board to the
+// slot's row (its side, byte 90, and the padding masked to zero, as init_board_lds leaves them), an empty history -- and the slot
+// goes to PH_NEWPOS: the select kernel issues the root request.  The rows are copied global to global, so the kernel needs no LDS
+// at all.  Its own kernel ahead of k_select, not a branch of slot_new_game: the select instances have no register to spare
+// (XQ_SELECT_OCC), and so no existing kernel's arguments or code change.
+__global__ __launch_bounds__(64 * WAVES_PER_WG) void k_start_pool(Dev E, SpDev P) {
+    const int slot = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
+    if (slot >= E.cfg.n_games) return;
+    const int lane = lane_id();
+    Slot s;
+    s.slot = slot; s.lane = lane; s.gi = E.gi + (size_t)slot * GI_N; s.st = E.stats + (size_t)slot * ST_N; s.T = slot_tree(E, slot);
+    int32_t *gi = s.gi;
+    const int phase = __builtin_amdgcn_readfirstlane(gi[GI_PHASE]);
+    if (phase != PH_FINISHED && phase != PH_NEWGAME) return;
+    if (__builtin_amdgcn_readfirstlane(gi[GI_DELAY]) > 0) return;      // start_stagger: the select kernel keeps the countdown
+    slot_load(s);
+    if (phase == PH_FINISHED) slot_flush_finished(E, s);
+    const int n = __builtin_amdgcn_readfirstlane(P.head->n);
+    const int idx = start_pool_draw(E.cfg.seed, (uint32_t)E.cfg.rank, (uint32_t)slot, (uint32_t)(s.game_seq + 1), n, P.head->prob);
+    if (idx < 0 || idx >= n) {                         // the initial position (idx >= n: n < 1, which init never lets in)
+        if (lane == 0) { gi[GI_PHASE] = PH_NEWGAME; P.start_index[slot] = -1; }
+        return;
+    }
+    unsigned long long ticket = 0;
+    if (lane == 0) ticket = atomicAdd(E.started, 1ull);
+    ticket = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(ticket >> 32)) << 32) |
+             (unsigned)__builtin_amdgcn_readfirstlane((unsigned)ticket);
+    if (E.cfg.games_target > 0 && ticket >= (unsigned long long)E.cfg.games_target) {
+        if (lane == 0) gi[GI_PHASE] = PH_IDLE;         // the games quota is used up: the slot idles
+        return;
+    }
+    const uint32_t *row = (const uint32_t *)(sp_rows(P.start_index, (size_t)n) + (size_t)idx * XQ_BS);
+    const int side = (int)(int8_t)(__builtin_amdgcn_readfirstlane((int)row[22]) >> 16);
+    uint32_t *board = (uint32_t *)(E.board + (size_t)slot * XQ_BS);
+    if (lane < XQ_BS / 4) board[lane] = lane < 22 ? row[lane] : (lane == 22 ? row[22] & 0xFFFFu : 0u);
+    uint32_t *hist = (uint32_t *)(E.hist + (size_t)slot * XQ_HIST * XQ_BS);
+    for (int i = lane; i < XQ_HIST * XQ_BS / 4; i += 64) hist[i] = 0u;
+    if (lane == 0) {
+        gi[GI_SIDE] = side; gi[GI_MC] = 0; gi[GI_NOCAP] = 0; gi[GI_NSAMP] = 0; gi[GI_GSEQ] = s.game_seq + 1;
+        gi[GI_RESIGN_N] = 0; gi[GI_RR_NODE] = 0; gi[GI_PHASE] = PH_NEWPOS;
+        s.st[ST_STARTED] += 1;
+        P.start_index[slot] = idx;
+        atomicAdd(&P.head->pool_games, 1ull);
+    }
+}
+
 Mx make_mx(const xq_engine *e) {
     Mx x;
     x.K = leaves_of(e);
@@ -1728,6 +1780,13 @@ int xq_engine_select(const xq_engine *eng, float *dev_nn_input, void *stream) {
         // game records: the finished games' records first, before the select kernel starts the slots' next games
         hipLaunchKernelGGL(k_flush_records, dim3((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), dim3(64 * WAVES_PER_WG), 0,
                            (hipStream_t)stream, d);
+        const int rc = launch_status();
+        if (rc != XQ_OK) return rc;
+    }
+    if (pool_of(eng)) {
+        // start-position pool: the games that start from a pool entry first; the select kernel starts the others
+        hipLaunchKernelGGL(k_start_pool, dim3((eng->cfg.n_games + WAVES_PER_WG - 1) / WAVES_PER_WG), dim3(64 * WAVES_PER_WG), 0,
+                           (hipStream_t)stream, d, make_sp(eng));
         const int rc = launch_status();
         if (rc != XQ_OK) return rc;
     }

@@ -20,6 +20,8 @@ struct Opts {
     const xq_root_stats_opts *root_stats;   // absent, NULL or enabled = 0: the samples' pad bytes stay zero
     const xq_eval_mirror_opts *mirror;      // absent, NULL or mode = 0: every request is evaluated as it stands
     const xq_game_records_opts *records;    // absent, NULL or enabled = 0: no game is recorded
+    const xq_start_pool *pool;              // absent, NULL or n = 0: every game starts from the initial position
+    bool pool_on() const { return pool && pool->n != 0; }
     bool solver_on() const { return solver && solver->enabled != 0; }
     bool mirror_on() const { return mirror && mirror->mode != 0; }
     bool root_stats_on() const { return root_stats && root_stats->enabled != 0; }
@@ -37,7 +39,8 @@ struct Layout {
 // square-root table's region also holds the Gumbel words (gz_bytes); every other engine has the layout it had.
 // Arena options (K = 1, never Gumbel): that region holds the arena words instead (ar_off).  Proven-result search (K = 1, never
 // Gumbel): its counters follow in the same region (sv_off, sv_bytes).  Game records (every engine that plays games): their words
-// close the region, from its next 256-byte boundary (gr_bytes).
+// close the region, from its next 256-byte boundary (gr_bytes).  The start-position pool (self-play, never with game records):
+// its words close the region instead (sp_bytes).
 Layout make_layout(const xq_engine_config *c, const Opts &opts) {
     const int K = opts.K, gz_m = opts.gumbel ? opts.gumbel->considered : 0;
     const bool arena = opts.arena != nullptr;
@@ -72,7 +75,9 @@ Layout make_layout(const xq_engine_config *c, const Opts &opts) {
     const size_t sqrt_bytes = opts.solver_on() ? sv_off(G, S, arena) + sv_bytes(G)
                               : arena          ? ar_off(G, S).end
                                                : (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0);
-    put(P_SQRT, opts.records_on() ? gr_align(sqrt_bytes) + gr_bytes(G, (size_t)opts.records->max_out_games) : sqrt_bytes);
+    put(P_SQRT, opts.records_on() ? gr_align(sqrt_bytes) + gr_bytes(G, (size_t)opts.records->max_out_games)
+                : opts.pool_on()  ? gr_align(sqrt_bytes) + sp_bytes(G, (size_t)opts.pool->n)
+                                  : sqrt_bytes);
     put(P_MNOISE, G * XQ_MAXM * 8);
     put(P_STATSUM, ST_N * 8);
     put(P_REQ, GK * 4);
@@ -98,7 +103,9 @@ bool config_ok(const xq_engine_config *c) {
 
 bool leaves_ok(const xq_engine_config *c, int K) { return K >= 1 && K <= 64 && !(K > 1 && c->manual_moves == 2); }
 
-// tree reuse: self-play only, one leaf per step, S within k_reroot's LDS (64 KiB at S = XQ_REUSE_MAX_SIMS)
+// tree reuse: self-play only, one leaf per step, S within k_reroot's LDS (64 KiB at S = XQ_REUSE_MAX_SIMS).  Any other bit is
+// refused, so no caller's flag reaches the private bits of the handle's flag byte (PAD0_GAME_RECORDS, PAD0_START_POOL)
+static_assert((((unsigned)XQ_ENGINE_TREE_REUSE << 16) & (unsigned)(PAD0_GAME_RECORDS | PAD0_START_POOL)) == 0, "private pad0 bits");
 bool flags_ok(const xq_engine_config *c, int K, unsigned flags) {
     if (flags & ~(unsigned)XQ_ENGINE_TREE_REUSE) return false;
     if (!(flags & XQ_ENGINE_TREE_REUSE)) return true;
@@ -174,8 +181,18 @@ bool records_ok(const xq_engine_config *c, const Opts &o) {
            c->random_opening_moves <= XQ_RECORD_MAX_PLIES;
 }
 
+// start-position pool: 0 <= n <= XQ_START_POOL_MAX, reserved zero; n = 0 is off; on, prob in (0, 1] (a NaN fails both
+// comparisons), both arrays, a self-play engine, no game records
+bool pool_ok(const xq_engine_config *c, const Opts &o) {
+    const xq_start_pool *sp = o.pool;
+    if (sp->n < 0 || sp->n > XQ_START_POOL_MAX || sp->reserved != 0) return false;
+    if (sp->n == 0) return true;
+    return sp->prob > 0.0 && sp->prob <= 1.0 && sp->dev_boards && sp->dev_side && c && c->manual_moves == 0 && !o.records_on();
+}
+
 // every option check, in the order the entry points have always refused in; an absent option passes
 bool opts_ok(const xq_engine_config *c, const Opts &o) {
+    if (o.pool && !pool_ok(c, o)) return false;
     if (o.rules && !rules_ok(o.rules)) return false;
     if (o.solver && !solver_ok(o)) return false;
     if (o.root_stats && !root_stats_ok(c, o)) return false;
@@ -240,6 +257,15 @@ __global__ void k_init_fp(Dev E, float k) {
     E.gi[(size_t)slot * GI_N + GI_FP_K] = __float_as_int(k);
 }
 
+// xq_engine_init_sp: the caller's pool as the workspace's 96-byte rows, one thread per byte: the board, its side in byte 90, zeros
+__global__ void k_init_pool(const int8_t *__restrict__ boards, const int8_t *__restrict__ side, int n, int8_t *__restrict__ rows) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long j = gid / XQ_BS;
+    const int b = (int)(gid - j * XQ_BS);
+    if (j >= n) return;
+    rows[gid] = b < 90 ? boards[(size_t)j * 90 + b] : (b == 90 ? side[j] : (int8_t)0);
+}
+
 // Column sums of the per-slot counters [G][ST_N] (OR for the overflow word): each 256-thread block sweeps slot rows
 // (8 rows x 32 columns per pass, 256 contiguous bytes per row), folds its eight partial rows through LDS and adds the
 // result to the zeroed output with one atomic per column.
@@ -268,6 +294,21 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
     const int K = o.K;
     const Layout l = make_layout(cfg, o);
     if (ws_bytes < l.total) return XQ_ERR_WORKSPACE;
+    if (o.pool_on()) {
+        // the pool is checked before anything else is written: its status bytes borrow the head of the workspace (n <= the
+        // pool's own rows), and an entry with a fatal bit refuses the engine
+        const size_t n = (size_t)o.pool->n;
+        int rc = xq_positions_check_batch(o.pool->dev_boards, o.pool->dev_side, o.pool->n, (uint8_t *)ws, stream);
+        if (rc != XQ_OK) return rc;
+        uint8_t *st = (uint8_t *)malloc(n);
+        if (!st) return XQ_ERR_ARG;
+        rc = xq::check(hipMemcpyAsync(st, ws, n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        if (rc == XQ_OK) rc = xq::check(hipStreamSynchronize((hipStream_t)stream));
+        for (size_t i = 0; rc == XQ_OK && i < n; ++i)
+            if (st[i] & XQ_POSITION_FATAL) rc = XQ_ERR_ARG;
+        free(st);
+        if (rc != XQ_OK) return rc;
+    }
     memset(eng, 0, sizeof(*eng));
     eng->cfg = *cfg;
     eng->node_cap = l.node_cap; eng->path_cap = l.path_cap; eng->stage_cap = l.stage_cap;
@@ -275,7 +316,7 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
                 (o.gumbel ? PAD0_GUMBEL : 0) | (o.arena ? PAD0_ARENA : 0) |
                 (o.rules && o.rules->perpetual_check ? PAD0_PERPETUAL : 0) | (o.solver_on() ? PAD0_SOLVER : 0) |
                 (o.root_stats_on() ? PAD0_ROOT_STATS : 0) | (o.mirror_on() ? PAD0_EVAL_MIRROR : 0) |
-                (o.records_on() ? PAD0_GAME_RECORDS : 0);
+                (o.records_on() ? PAD0_GAME_RECORDS : 0) | (o.pool_on() ? PAD0_START_POOL : 0);
     for (int i = 0; i < 32; ++i) eng->p[i] = (char *)ws + l.off[i];
     eng->p[P_INJECT] = (void *)dev_inject;
     hipStream_t s = (hipStream_t)stream;
@@ -321,6 +362,22 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
         const size_t G = (size_t)cfg->n_games, M = (size_t)o.records->max_out_games;
         XQ_TRY(hipMemsetAsync(gr_ring(d.gr_log, M), 0, gr_bytes(G, M), s));
         XQ_TRY(hipMemcpyAsync(&gr_head(d.gr_log, G)->max_out_games, &o.records->max_out_games, 4, hipMemcpyHostToDevice, s));
+        XQ_TRY(hipStreamSynchronize(s));
+    }
+    if (o.pool_on()) {
+        // start-position pool: the checked entries as rows, every slot's index -1, then the head
+        const size_t G = (size_t)cfg->n_games, n = (size_t)o.pool->n;
+        const SpDev sp = make_sp(eng);
+        SpHead h;
+        memset(&h, 0, sizeof(h));
+        h.n = o.pool->n; h.prob = o.pool->prob;
+        const long long threads = (long long)n * XQ_BS;
+        hipLaunchKernelGGL(k_init_pool, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, o.pool->dev_boards, o.pool->dev_side,
+                           o.pool->n, sp_rows(sp.start_index, n));
+        const int rc = launch_status();
+        if (rc != XQ_OK) return rc;
+        XQ_TRY(hipMemsetAsync(sp.start_index, 0xFF, sp_index_bytes(G), s));
+        XQ_TRY(hipMemcpyAsync(sp.head, &h, sizeof(h), hipMemcpyHostToDevice, s));
         XQ_TRY(hipStreamSynchronize(s));
     }
     hipLaunchKernelGGL(k_init, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d);
@@ -483,6 +540,44 @@ int xq_engine_init_gr(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
                       const uint64_t *dev_inject, void *stream) {
     return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror, records},
                        ws, ws_bytes, dev_inject, stream);
+}
+
+size_t xq_engine_workspace_bytes_sp(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                                    const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                                    const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                                    const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records,
+                                    const xq_start_pool *pool) {
+    return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror, records, pool});
+}
+
+int xq_engine_init_sp(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                      const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                      const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                      const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records, const xq_start_pool *pool, void *ws,
+                      size_t ws_bytes, const uint64_t *dev_inject, void *stream) {
+    return engine_init(eng, cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror, records, pool},
+                       ws, ws_bytes, dev_inject, stream);
+}
+
+int xq_start_pool_draw_host(uint64_t seed, int rank, int slot, uint32_t game_seq, int n, double prob) {
+    if (n < 1 || !(prob > 0.0 && prob <= 1.0)) return -1;
+    return start_pool_draw(seed, (uint32_t)rank, (uint32_t)slot, game_seq, n, prob);
+}
+
+int xq_engine_start_indices(const xq_engine *eng, const int32_t **dev_index) {
+    if (!pool_of(eng) || !dev_index) return XQ_ERR_ARG;
+    *dev_index = make_sp(eng).start_index;
+    return XQ_OK;
+}
+
+int xq_engine_start_pool_stats_read(const xq_engine *eng, xq_start_pool_stats *host_out, void *stream) {
+    if (!pool_of(eng) || !host_out) return XQ_ERR_ARG;
+    SpHead h;
+    XQ_TRY(hipStreamSynchronize((hipStream_t)stream));
+    XQ_TRY(hipMemcpy(&h, make_sp(eng).head, 32, hipMemcpyDeviceToHost));
+    memset(host_out, 0, sizeof(*host_out));
+    host_out->pool_games = h.pool_games;
+    return XQ_OK;
 }
 
 // the pending records of a game-records engine: the head read back after a synchronise

@@ -55,6 +55,7 @@ constexpr int PAD0_PERPETUAL = 1 << 26;     // pad0 of the handle (encoding belo
 constexpr int PAD0_ROOT_STATS = 1 << 24;    // "root statistics per sample on" (xq_engine_init_rs)
 constexpr int PAD0_EVAL_MIRROR = (int)(1u << 31);   // "evaluation mirror on" (xq_engine_init_em): the last private bit, the sign
 constexpr int PAD0_GAME_RECORDS = 1 << 23;  // "game records on" (xq_engine_init_gr): the top bit of the public flag byte
+constexpr int PAD0_START_POOL = 1 << 22;    // "start-position pool on" (xq_engine_init_sp): the next bit of that byte
 
 // The node meta word tM: the child count in bits 0-11 (at most XQ_MAXM = 128), the node's proven state in bits 12-13 (always 0
 // without xq_engine_init_sv: every reader masks the count, and an engine without the solver stays byte-identical), the prior
@@ -110,6 +111,29 @@ __host__ __device__ inline size_t gr_bytes(size_t G, size_t max_out_games) {
 __host__ __device__ inline uint16_t *gr_opening(uint16_t *log, size_t G) { return (uint16_t *)((char *)log + gr_log_bytes(G)); }
 __host__ __device__ inline GrHead *gr_head(uint16_t *log, size_t G) { return (GrHead *)((char *)log + gr_log_bytes(G) + gr_open_bytes(G)); }
 __host__ __device__ inline xq_game_record *gr_ring(uint16_t *log, size_t max_out_games) { return (xq_game_record *)log - max_out_games; }
+
+// Start-position pool (xq_engine_init_sp; never with game records, so these words are the LAST of the square-root table's region
+// instead, found from the region that follows the same way):
+//   rows int8[n][XQ_BS] (a board, its side to move in byte 90) | start_index int32[G] | SpHead
+// each part rounded up to 256 bytes.  The pool's size is in the head.  The pool reaches k_start_pool as an argument of its own
+// (SpDev), not through Dev: every other kernel keeps its arguments.
+struct SpHead {
+    int32_t n, pad0;
+    double prob;
+    unsigned long long pool_games;      // games started from the pool
+    unsigned long long pad[29];
+};
+static_assert(sizeof(SpHead) == 256, "SpHead layout");
+
+struct SpDev {
+    int32_t *start_index;               // [G] the entry the slot's current game started from, or -1
+    SpHead *head;
+};
+
+__host__ __device__ inline size_t sp_rows_bytes(size_t n) { return gr_align(n * XQ_BS); }
+__host__ __device__ inline size_t sp_index_bytes(size_t G) { return gr_align(G * 4); }
+__host__ __device__ inline size_t sp_bytes(size_t G, size_t n) { return sp_rows_bytes(n) + sp_index_bytes(G) + sizeof(SpHead); }
+__host__ __device__ inline int8_t *sp_rows(int32_t *start_index, size_t n) { return (int8_t *)start_index - sp_rows_bytes(n); }
 
 Dev make_dev(const xq_engine *e) {
     Dev d;
@@ -192,8 +216,8 @@ __host__ __device__ inline size_t sv_bytes(size_t G) { return G * SV_WORDS * 8; 
 // (xq_engine_init_gz), "arena options on" (xq_engine_init_ar), "perpetual-check rule on" (xq_engine_init_ru), "proven-result
 // search on" (xq_engine_init_sv), "root statistics per sample on" (xq_engine_init_rs, PAD0_ROOT_STATS above) and, in bit 31,
 // "evaluation mirror on" (xq_engine_init_em, PAD0_EVAL_MIRROR above).  Bits 24-31 are now all taken; of the public flag byte
-// (bits 16-23) bit 16 is, and bit 23 says "game records on" (xq_engine_init_gr, PAD0_GAME_RECORDS above): flags_ok lets no
-// caller's flag reach it.
+// (bits 16-23) bit 16 is, bit 23 says "game records on" (xq_engine_init_gr, PAD0_GAME_RECORDS above) and bit 22 "start-position
+// pool on" (xq_engine_init_sp, PAD0_START_POOL above): flags_ok lets no caller's flag reach either.
 constexpr int PAD0_CAP = 1 << 30;
 constexpr int PAD0_FORCED = 1 << 29;
 constexpr int PAD0_GUMBEL = 1 << 28;
@@ -207,6 +231,13 @@ bool gumbel_of(const xq_engine *e) { return (e->pad0 & PAD0_GUMBEL) != 0; }
 bool solver_of(const xq_engine *e) { return (e->pad0 & PAD0_SOLVER) != 0; }
 bool mirror_of(const xq_engine *e) { return (e->pad0 & PAD0_EVAL_MIRROR) != 0; }
 bool records_of(const xq_engine *e) { return e && (e->pad0 & PAD0_GAME_RECORDS) != 0 && e->cfg.n_games > 0 && e->p[P_MNOISE]; }
+bool pool_of(const xq_engine *e) { return e && (e->pad0 & PAD0_START_POOL) != 0 && e->cfg.n_games > 0 && e->p[P_MNOISE]; }
+SpDev make_sp(const xq_engine *e) {
+    SpDev p;
+    p.head = (SpHead *)((char *)e->p[P_MNOISE] - sizeof(SpHead));
+    p.start_index = (int32_t *)((char *)p.head - sp_index_bytes((size_t)e->cfg.n_games));
+    return p;
+}
 bool arena_of(const xq_engine *e) { return e && (e->pad0 & PAD0_ARENA) != 0 && e->cfg.n_games > 0 && e->p[P_SQRT]; }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -227,6 +258,15 @@ __host__ __device__ inline uint64_t philox_u64(uint64_t seed, uint32_t rank, uin
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
     return ((uint64_t)c0 << 32) | c1;
+}
+
+// The start-position pool's draw for the game that will carry `game_seq` (xq_engine_init_sp): stateless, never injected.  The entry
+// the game starts from, or -1 for the initial position.  xq_start_pool_draw_host runs this code.
+constexpr uint32_t RNG_START_POOL = (uint32_t)XQ_RNG_KIND_START_POOL;
+__host__ __device__ inline int start_pool_draw(uint64_t seed, uint32_t rank, uint32_t slot, uint32_t game_seq, int n, double prob) {
+    const uint64_t x0 = philox_u64(seed, rank, slot, RNG_START_POOL, game_seq, 0u);
+    if (!((double)(x0 >> 11) * (1.0 / 9007199254740992.0) < prob)) return -1;      // u64_to_unit(x0) < prob
+    return (int)(philox_u64(seed, rank, slot, RNG_START_POOL, game_seq, 1u) % (uint64_t)n);
 }
 
 // waiting for an evaluation: k_expand's own predicate

@@ -99,6 +99,15 @@ the games finished since its last call (at most `max_out_games`, default the con
 `game_records_stats()['dropped']`), `drain_games_device()` the same as a device tensor.  `replay_games` plays records on the
 device: legality of every move, the position at any ply in `set_position`'s form, and the rules' verdict there.  Games, samples,
 results and statistics are byte-identical with and without it.  Self-play and arena engines, every other option.
+
+With `start_pool=(boards, sides, prob)` (opt-in; xq_engine_init_sp) a new game starts, with probability
+`prob`, from an entry of the pool instead of the initial position: `boards` int8[n, 90] and `sides` int8[n], numpy arrays or
+device tensors (`start_pool.py` makes them from FEN lines, tablebase entries or game records).  The draw is a function of seed,
+rank, slot and the game's number (`hip.start_pool_index`).  A pool game plays no random opening, starts at ply 0 with an empty
+history, and every ply counter counts from there.  The engine checks the pool first (`hip.positions_check`) and refuses an entry
+the rules code cannot run on; an entry without a legal move is a game that finishes at ply 0 with no sample.  `start_indices()`
+reads the entry every slot's current game started from (-1: the initial position), `start_pool_stats()` the number of pool games.
+Self-play only; not with record_games, whose record has no room for a start position; every other option.
 """
 from __future__ import annotations
 
@@ -161,6 +170,38 @@ class EngineOptions(collections.namedtuple("EngineOptions", "K flags cap forced 
 
 
 RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_game_over, and its perpetual-check verdict
+
+
+def parse_start_pool(cfg: hip.EngineConfig, start_pool, record_games: bool = False):
+    """The `start_pool=(boards, sides, prob)` argument checked, without a GPU -> (boards, sides, prob) with numpy arrays made
+    int8[n, 90] / int8[n] and device tensors left as they are, or None.  Every rule of xq_engine_init_sp's refusal list but the
+    check of the positions themselves, which needs the device (`SelfPlayEngine` runs it)."""
+    if start_pool is None:
+        return None
+    try:
+        boards, sides, prob = start_pool
+        prob = float(prob)
+    except (TypeError, ValueError):
+        raise hip.XqError("start_pool must be (boards, sides, prob)")
+    if not isinstance(boards, torch.Tensor):
+        boards = np.ascontiguousarray(boards, dtype=np.int8)
+    if not isinstance(sides, torch.Tensor):
+        sides = np.ascontiguousarray(sides, dtype=np.int8)
+    n = int(boards.shape[0]) if boards.ndim >= 1 else -1
+    bad_dtype = any(isinstance(a, torch.Tensor) and a.dtype != torch.int8 for a in (boards, sides))    # numpy: cast above
+    if n < 0 or bad_dtype or int(np.prod(tuple(boards.shape))) != n * 90 or tuple(sides.shape) != (n,):
+        raise hip.XqError(f"start_pool: boards must be int8[n, 90] and sides int8[n], got {tuple(boards.shape)} and "
+                          f"{tuple(sides.shape)}")
+    if not 1 <= n <= hip.START_POOL_MAX:
+        raise hip.XqError(f"start_pool: the pool must hold 1 to {hip.START_POOL_MAX} positions, got {n}")
+    if not 0.0 < prob <= 1.0:                          # a NaN fails both comparisons
+        raise hip.XqError(f"start_pool: prob must be in (0, 1], got {prob}")
+    if int(cfg.manual_moves) != 0:
+        raise hip.XqError("start_pool is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena)")
+    if record_games:
+        raise hip.XqError("start_pool cannot be combined with record_games: a record has no room for a start position and its "
+                          "replay starts from the initial one")
+    return boards.reshape(n, 90), sides, prob
 
 
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
@@ -313,7 +354,7 @@ class SelfPlayEngine:
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
                  perpetual_check: bool = False, solver: bool = False, root_stats: bool = False, eval_mirror: bool = False,
-                 record_games: bool = False, max_out_games=None):
+                 record_games: bool = False, max_out_games=None, start_pool=None):
         opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
             gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check,
@@ -322,10 +363,24 @@ class SelfPlayEngine:
         rules, sv, rs, em, gr = opts.rules, opts.solver, opts.root_stats, opts.eval_mirror, opts.game_records
         if em is not None and not getattr(evaluator, "live_rows", False):
             raise hip.XqError("eval_mirror acts in the packed step only: it needs an evaluator with live_rows (the HIP evaluators)")
+        pool = parse_start_pool(cfg, start_pool, record_games=gr is not None)
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
         self.device = torch.device(device)
+        sp = None
+        if pool is not None:
+            # the pool on the device, checked there: the first entry the rules code cannot run on is named
+            pb, ps = (a.to(self.device).contiguous() if isinstance(a, torch.Tensor) else torch.from_numpy(a).to(self.device)
+                      for a in pool[:2])
+            with torch.cuda.device(self.device):
+                status = hip.positions_check(pb, ps).cpu().numpy()
+            bad = np.flatnonzero(status & hip.POSITION_FATAL)
+            if len(bad):
+                raise hip.XqError(f"start_pool: row {int(bad[0])} is no position the rules can run on (positions_check bits "
+                                  f"{int(status[bad[0]])}; {len(bad)} of {len(status)} rows are refused)")
+            sp = hip.StartPool(pb.data_ptr(), ps.data_ptr(), len(status), 0, pool[2])
+        self.start_pool = None if sp is None else (int(sp.n), float(sp.prob))
         self.cfg = cfg
         self.G = cfg.n_games
         self.K = K
@@ -343,8 +398,8 @@ class SelfPlayEngine:
         self.rows = self.G * K                         # request rows: slot-major, row slot * K + j
         self.evaluator = evaluator
         # every entry point is the widest one with NULL for the options it does not take (include/xq_hip.h)
-        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules, sv, rs, em, gr)]
-        nbytes = self.lib.xq_engine_workspace_bytes_gr(C.byref(cfg), K, flags, *refs)
+        refs = [None if o is None else C.byref(o) for o in (cap, forced, gz, ar, rules, sv, rs, em, gr, sp)]
+        nbytes = self.lib.xq_engine_workspace_bytes_sp(C.byref(cfg), K, flags, *refs)
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
@@ -360,8 +415,14 @@ class SelfPlayEngine:
         self.h = hip.Engine()
         self.nn_input = torch.zeros((self.rows, 15, 10, 9), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            hip.check(self.lib.xq_engine_init_gr(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
-                                                 hip.stream_ptr(self.device)), "xq_engine_init_gr")
+            hip.check(self.lib.xq_engine_init_sp(C.byref(self.h), C.byref(cfg), K, flags, *refs, base, self.workspace_bytes, inj_ptr,
+                                                 hip.stream_ptr(self.device)), "xq_engine_init_sp")
+        self._start_index = None
+        if sp is not None:                             # init copied the pool into the workspace: pb and ps may go
+            pi = C.c_void_p()
+            hip.check(self.lib.xq_engine_start_indices(C.byref(self.h), C.byref(pi)), "xq_engine_start_indices")
+            off = int(pi.value) - int(self.ws.data_ptr())
+            self._start_index = self.ws[off:off + self.G * 4].view(torch.int32)
         # zero-copy int32 view of the per-slot state words (columns hip.GI_*: side to move of the REAL game, move_count, phase,
         # simulations done): host-side policies such as the arena's model choice read it between stages
         gi_off = int(self.h.p[hip.P_GI]) - int(self.ws.data_ptr())
@@ -740,6 +801,22 @@ class SelfPlayEngine:
         hip.check(self.lib.xq_engine_game_records_stats_read(C.byref(self.h), C.byref(s), hip.stream_ptr(self.device)),
                   "xq_engine_game_records_stats_read")
         return dict(recorded=int(s.recorded), dropped=int(s.dropped))
+
+    def start_indices(self) -> np.ndarray:
+        """-> int32[G] on the host: the pool entry every slot's current game started from, -1 for the initial position (and
+        before the slot's first game).  Synchronises.  Needs start_pool=."""
+        if self._start_index is None:
+            raise hip.XqError("start_indices needs an engine with start_pool=")
+        return self._start_index.cpu().numpy().copy()
+
+    def start_pool_stats(self) -> dict:
+        """pool_games: the games started from a pool entry (xq_engine_start_pool_stats_read).  Synchronises."""
+        if self._start_index is None:
+            raise hip.XqError("start_pool_stats needs an engine with start_pool=")
+        s = hip.StartPoolStats()
+        hip.check(self.lib.xq_engine_start_pool_stats_read(C.byref(self.h), C.byref(s), hip.stream_ptr(self.device)),
+                  "xq_engine_start_pool_stats_read")
+        return dict(pool_games=int(s.pool_games))
 
     def game_record_views(self) -> dict:
         """Zero-copy views of the game records' words in the workspace (csrc/xq_engine_state.cuh: the last words of the square-root

@@ -42,6 +42,10 @@ TB_MAX_ENTRIES = 1 << 28       # XQ_TB_MAX_ENTRIES
 TB_MAX_PASSES = 32000          # XQ_TB_MAX_PASSES
 TB_INVALID = -32768            # XQ_TB_INVALID
 TB_NO_MOVE = 0xFFFF            # XQ_TB_NO_MOVE
+POSITION_FATAL = 15            # XQ_POSITION_FATAL: the bits of positions_check that refuse a position
+POSITION_NO_MOVE = 16          # XQ_POSITION_NO_MOVE: the side to move has no legal move (the game is over at ply 0)
+START_POOL_MAX = 1 << 20       # XQ_START_POOL_MAX
+RNG_KIND_START_POOL = 11       # XQ_RNG_KIND_START_POOL
 
 
 class XqError(RuntimeError):
@@ -161,6 +165,18 @@ class GameRecordsOpts(C.Structure):
 class GameRecordsStats(C.Structure):
     """xq_game_records_stats: games whose record found a row of the ring, and games that did not (xq_engine_game_records_stats_read)."""
     _fields_ = [("recorded", C.c_uint64), ("dropped", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+class StartPool(C.Structure):
+    """xq_start_pool: the start-position pool (xq_engine_init_sp): n boards int8[n][90] and sides int8[n] on the device, and the
+    probability that a new game starts from one of them."""
+    _fields_ = [("dev_boards", C.c_void_p), ("dev_side", C.c_void_p), ("n", C.c_int32), ("reserved", C.c_int32),
+                ("prob", C.c_double)]
+
+
+class StartPoolStats(C.Structure):
+    """xq_start_pool_stats: games started from the pool (xq_engine_start_pool_stats_read)."""
+    _fields_ = [("pool_games", C.c_uint64), ("reserved", C.c_uint64 * 3)]
 
 
 class GameRecord(C.Structure):
@@ -327,6 +343,13 @@ def lib():
     L.xq_engine_workspace_bytes_gr.argtypes = L.xq_engine_workspace_bytes_em.argtypes + [C.POINTER(GameRecordsOpts)]
     L.xq_engine_workspace_bytes_gr.restype = C.c_size_t
     L.xq_engine_init_gr.argtypes = L.xq_engine_init_em.argtypes[:12] + [C.POINTER(GameRecordsOpts)] + L.xq_engine_init_em.argtypes[12:]
+    L.xq_engine_workspace_bytes_sp.argtypes = L.xq_engine_workspace_bytes_gr.argtypes + [C.POINTER(StartPool)]
+    L.xq_engine_workspace_bytes_sp.restype = C.c_size_t
+    L.xq_engine_init_sp.argtypes = L.xq_engine_init_gr.argtypes[:13] + [C.POINTER(StartPool)] + L.xq_engine_init_gr.argtypes[13:]
+    L.xq_positions_check_batch.argtypes = [vp, vp, i32, vp, vp]
+    L.xq_start_pool_draw_host.argtypes = [C.c_uint64, i32, i32, C.c_uint32, i32, C.c_double]
+    L.xq_engine_start_indices.argtypes = [C.POINTER(Engine), C.POINTER(vp)]
+    L.xq_engine_start_pool_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(StartPoolStats), vp]
     L.xq_engine_drain_games.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
     L.xq_engine_drain_games_device.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
     L.xq_engine_game_records_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(GameRecordsStats), vp]
@@ -448,7 +471,9 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_samples_to_requests", "xq_score_samples", "xq_surprise_counts", "xq_surprise_count_host",
            "xq_position_keys", "xq_position_key_host", "xq_position_group_heads", "xq_groups_to_batch",
            "xq_alphabeta_batch", "xq_records_sample_counts", "xq_records_to_samples", "xq_mate_search_batch",
-           "xq_tb_entries", "xq_tb_init", "xq_tb_pass", "xq_tb_probe_batch", "xq_tb_play_batch", "xq_tb_samples"]
+           "xq_tb_entries", "xq_tb_init", "xq_tb_pass", "xq_tb_probe_batch", "xq_tb_play_batch", "xq_tb_samples",
+           "xq_positions_check_batch", "xq_engine_workspace_bytes_sp", "xq_engine_init_sp", "xq_start_pool_draw_host",
+           "xq_engine_start_indices", "xq_engine_start_pool_stats_read"]
 
 
 def check(rc: int, what: str):
@@ -627,6 +652,30 @@ def _positions_arg(boards, side, what: str):
     if boards.dtype != torch.int8 or boards.numel() != len(boards) * 90 or side.dtype != torch.int8 or side.shape != boards.shape[:1]:
         raise XqError(f"{what}: boards must be int8[n, 90] and side int8[n], got {tuple(boards.shape)} and {tuple(side.shape)}")
     return len(boards), boards.device
+
+
+def positions_check(boards: torch.Tensor, side: torch.Tensor) -> torch.Tensor:
+    """Is each board a position the rules code can safely run on (xq_positions_check_batch)?  boards int8[n,90] (or [n,10,9]) and
+    side int8[n] on the GPU -> uint8[n] of bits: 1 a square outside -7..7 or a side outside {1, -1}; 2 not exactly one king per
+    colour, or a king outside its palace; 4 a piece where it can never stand, or more of a kind than a set has; 8 the side not to
+    move is in check; 16 the side to move has no legal move.  With bit 1 or 2 the later bits stay 0.  POSITION_FATAL (15) refuses a
+    position; POSITION_NO_MOVE (16) alone is a game that is over at ply 0."""
+    n, dev = _positions_arg(boards, side, "positions_check")
+    status = torch.zeros(n, dtype=torch.uint8, device=dev)
+    if n:
+        check(lib().xq_positions_check_batch(_dev(boards), _dev(side), n, _dev(status), stream_ptr(dev)), "xq_positions_check_batch")
+    return status
+
+
+def start_pool_index(seed: int, rank: int, slot: int, game_seq: int, n: int, prob: float) -> int:
+    """The start-position pool's draw on the host (xq_start_pool_draw_host, the device's own code; no GPU needed): the pool entry
+    the game `game_seq` of `slot` starts from, or -1 for the initial position."""
+    if n < 1 or not 0.0 < float(prob) <= 1.0:
+        raise XqError(f"start_pool_index: n >= 1 and prob in (0, 1] required, got {n}, {prob}")
+    if min(int(rank), int(slot), int(game_seq)) < 0:
+        raise XqError(f"start_pool_index: rank, slot and game_seq must not be negative, got {rank}, {slot}, {game_seq}")
+    return int(lib().xq_start_pool_draw_host(int(seed) & (2 ** 64 - 1), int(rank), int(slot), int(game_seq), int(n), float(prob)))
+
 
 def alphabeta_batch(boards: torch.Tensor, side: torch.Tensor, depth: int, draws=None):
     """The fixed alpha-beta opponent (xq_alphabeta_batch): boards int8[n,90] (or [n,10,9]) and side int8[n] on the GPU, 0 <= depth

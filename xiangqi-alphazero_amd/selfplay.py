@@ -97,7 +97,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
               eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None,
               tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None,
               perpetual_check: Optional[bool] = None, solver: Optional[bool] = None, root_stats: Optional[bool] = None,
-              eval_mirror: Optional[bool] = None, record_games: Optional[bool] = None):
+              eval_mirror: Optional[bool] = None, record_games: Optional[bool] = None, start_pool=None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -130,7 +130,10 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     orientation (stats `eval_mirror`); it needs the packed step and excludes the evaluation cache.
     `record_games` (None: `config.record_games`, absent = off) keeps every finished game's moves: stats
     `record_games`, `game_records` (a hip.GAME_RECORD_DTYPE array, or under `device_records` a uint8 device tensor [n, 1024]; None
-    when off), `game_records_recorded` and `game_records_dropped` (0 when off).  The games do not change; every other option."""
+    when off), `game_records_recorded` and `game_records_dropped` (0 when off).  The games do not change; every other option.
+    `start_pool` = (boards, sides, prob) (an argument only: `start_pool.py` makes the arrays, `AlphaZeroLoop` reads the config
+    keys) starts a new game from an entry of the pool with probability prob: stats `start_pool`
+    ((positions, prob), None when off) and `start_pool_games` (0 when off).  Not with record_games; every other option."""
     if record_games is None:
         record_games = bool(getattr(config, "record_games", False))
     if eval_mirror is None:
@@ -174,7 +177,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries,
                                 leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
                                 forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check, solver=solver,
-                                root_stats=root_stats, eval_mirror=eval_mirror, record_games=record_games)
+                                root_stats=root_stats, eval_mirror=eval_mirror, record_games=record_games, start_pool=start_pool)
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -205,6 +208,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
         st["game_records"] = eng.drain_games_device() if device_records else eng.drain_games()
         gs = eng.game_records_stats()
         st["game_records_recorded"], st["game_records_dropped"] = gs["recorded"], gs["dropped"]
+    st["start_pool"] = eng.start_pool                  # None, or (positions, prob)
+    st["start_pool_games"] = eng.start_pool_stats()["pool_games"] if eng.start_pool else 0
     for k in hip.SOLVER_KEYS:                          # the solver's keys are present (0) when it is off
         st.setdefault(k, 0)
     if device_records:
@@ -225,7 +230,8 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
                        tree_reuse: Optional[bool] = None, playout_cap=None,
                        forced_playouts: Optional[float] = None, gumbel=None,
                        perpetual_check: Optional[bool] = None, solver: Optional[bool] = None,
-                       record_games: Optional[bool] = None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
+                       record_games: Optional[bool] = None,
+                       start_pool=None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
     for k in _CFG_KEYS + ("num_games_per_iter",):
         if not hasattr(config, k):
             raise AttributeError(f"config lacks '{k}' (see training/train.py:55-111)")
@@ -238,7 +244,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
                                               eval_cache_entries=eval_cache_entries, leaves_per_step=leaves_per_step,
                                               tree_reuse=tree_reuse, playout_cap=playout_cap,
                                               forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check,
-                                              solver=solver, record_games=record_games)
+                                              solver=solver, record_games=record_games, start_pool=start_pool)
     all_data, per_game = to_reference_tuples(samples, results, augment=True, q_mix=root_stats_q_mix(config))
     wins = {1: 0, -1: 0, 0: 0}
     total_steps = 0
@@ -262,6 +268,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
         "solver": st["solver"], **{k: st[k] for k in hip.SOLVER_KEYS}, "root_stats": st["root_stats"],
         "record_games": st["record_games"], "game_records": st["game_records"],
         "game_records_recorded": st["game_records_recorded"], "game_records_dropped": st["game_records_dropped"],
+        "start_pool": st["start_pool"], "start_pool_games": st["start_pool_games"],
     }
     if return_compact:
         stats["compact_samples"], stats["compact_results"] = samples, results

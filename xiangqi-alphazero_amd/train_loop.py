@@ -189,6 +189,51 @@ def _endgame_play_options(config):
     teacher = None if samples is None else {"samples": samples, "policy": 0 if policy is None else policy}
     return playout, teacher
 
+
+def _start_pool_options(config):
+    """The start-position pool's keys (all optional; absent means off): None when neither config.start_positions_file nor
+    config.start_positions_endgame is set, else a dict of file, boards and sides (the file's positions, read here: a missing file
+    raises at construction), endgame (entries of config.endgame_signature's table per iteration, or None) and prob
+    (config.start_positions_prob: required with a source, no default).  A key outside its range raises XqError with the key's
+    name, whether the pool is on or not; either source with config.record_games or config.game_records_dir does as well."""
+    from . import start_pool
+    path = getattr(config, "start_positions_file", None)
+    if path is not None and not isinstance(path, (str, os.PathLike)):
+        raise hip.XqError(f"config.start_positions_file must be a path, got {path!r}")
+    n_end = getattr(config, "start_positions_endgame", None)
+    if n_end is not None and (isinstance(n_end, bool) or not isinstance(n_end, (int, np.integer))):
+        raise hip.XqError(f"config.start_positions_endgame must be an integer, got {n_end!r}")
+    if n_end is not None and not 1 <= int(n_end) <= hip.START_POOL_MAX:
+        raise hip.XqError(f"config.start_positions_endgame must be in [1, {hip.START_POOL_MAX}], got {n_end}")
+    prob = getattr(config, "start_positions_prob", None)
+    if prob is not None and (isinstance(prob, bool) or not isinstance(prob, (int, float, np.integer, np.floating))):
+        raise hip.XqError(f"config.start_positions_prob must be a number, got {prob!r}")
+    if prob is not None and not 0.0 < float(prob) <= 1.0:            # a NaN fails both comparisons
+        raise hip.XqError(f"config.start_positions_prob must be in (0, 1], got {prob}")
+    if path is None and n_end is None:
+        if prob is not None:
+            raise hip.XqError("config.start_positions_prob needs config.start_positions_file or config.start_positions_endgame")
+        return None
+    if prob is None:
+        raise hip.XqError("config.start_positions_prob is required with config.start_positions_file or "
+                          "config.start_positions_endgame: it has no default")
+    if n_end is not None and getattr(config, "endgame_signature", None) is None:
+        raise hip.XqError("config.start_positions_endgame needs config.endgame_signature")
+    if bool(getattr(config, "record_games", False)) or getattr(config, "game_records_dir", None):
+        raise hip.XqError("config.start_positions_file / config.start_positions_endgame cannot be combined with config.record_games "
+                          "or config.game_records_dir: a game record has no room for a start position")
+    boards, sides = np.zeros((0, 90), dtype=np.int8), np.zeros(0, dtype=np.int8)
+    if path is not None:
+        try:
+            boards, sides = start_pool.from_fens(os.fspath(path) if os.path.exists(path) else open(path).read())
+        except ValueError as e:
+            raise hip.XqError(f"config.start_positions_file: {e}") from None
+        if not 1 <= len(boards) <= hip.START_POOL_MAX:
+            raise hip.XqError(f"config.start_positions_file must hold 1 to {hip.START_POOL_MAX} positions, {path!r} holds {len(boards)}")
+    return {"file": None if path is None else os.fspath(path), "boards": boards, "sides": sides,
+            "endgame": None if n_end is None else int(n_end), "prob": float(prob)}
+
+
 def _pretrain_options(config):
     """The supervised warm start's keys (all optional; absent means off): None when config.pretrain_records is absent or empty,
     else a dict of paths, epochs, movers, skip_draws and records (the games of every file, read here: a missing file raises at
@@ -288,7 +333,13 @@ class AlphaZeroLoop:
         # every iteration every rank appends the same table samples to its buffer after self-play's
         self.endgame_playout, self.endgame_teacher = _endgame_play_options(config)
         self._endgame_playout_positions = None
-        torch.manual_seed(seed)                      # identical initial weights on every rank
+        # the start-position pool (config.start_positions_file, config.start_positions_endgame, config.start_positions_prob;
+        # absent: off), read once and checked here, the file included: self-play starts that share of its games from the file's
+        # positions and from entries of the endgame table, redrawn every iteration from seed + iteration with no rank term, so
+        # every rank holds the same pool; the ranks' draws differ through Philox's rank word
+        self.start_pool = _start_pool_options(config)
+        self._shard_pool = (0, 0)
+        torch.manual_seed(seed)                     # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
         on_gpu = self.device.type == "cuda"
@@ -323,7 +374,9 @@ class AlphaZeroLoop:
                                                     forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None,
                                                     perpetual_check=self.perpetual_check, solver=self.solver,
                                                     root_stats=self.record_root_stats, eval_mirror=self.eval_mirror,
-                                                    record_games=self.record_games)
+                                                    record_games=self.record_games, start_pool=self._iteration_pool())
+        if self.start_pool is not None:
+            self._shard_pool = (st["start_pool"][0], st["start_pool_games"])
         if self.record_games:
             self._write_records("selfplay", st["game_records"].cpu().numpy().reshape(-1).view(GAME_RECORD_DTYPE))
         # the Gumbel root search (config.gumbel_considered, gumbel_c_visit, gumbel_c_scale; absent or 0: off) reaches the engine
@@ -332,6 +385,22 @@ class AlphaZeroLoop:
             self._shard_scores = selfplay.score_samples(self._scoring_evaluator(), samples, self.buffer.late_temperature,
                                                         write_back=True)     # the target the batch kernel trains on
         return samples, results
+
+    def _iteration_pool(self):
+        """This iteration's start-position pool as run_games takes it, or None: the file's positions, then the endgame table's
+        entries of this iteration (every kind one can move from; as many as the table has when it has fewer)."""
+        p = self.start_pool
+        if p is None:
+            return None
+        boards, sides = p["boards"], p["sides"]
+        if p["endgame"] is not None:
+            from . import start_pool
+            tb = self._endgame_table()
+            have = int(((tb.table != -1) & (tb.table != hip.TB_INVALID)).sum())
+            from .endgame import KINDS
+            eb, es = start_pool.from_table(tb, min(p["endgame"], have), KINDS, seed=self.seed + self.iteration)
+            boards, sides = np.concatenate([boards, eb]), np.concatenate([sides, es])
+        return boards, sides, p["prob"]
 
     def _scoring_evaluator(self):
         """The evaluator of `best_model` that scores the shards: built once and kept (its activation and logits buffers with it);
@@ -358,7 +427,16 @@ class AlphaZeroLoop:
         cfg = self.config
         t0 = time.time()
         self._shard_scores = None
+        self._shard_pool = (0, 0)
         samples, results = self._play_shard(xdist.shard_games(cfg.num_games_per_iter, self.world, self.rank))
+        pooled = {}
+        if self.start_pool is not None:
+            # every rank's pool is the same; the games started from it are summed over the ranks
+            games = torch.tensor([self._shard_pool[1]], dtype=torch.int64, device=self.device)
+            if self.grouped:
+                dist.all_reduce(games)
+            positions = len(self.start_pool["boards"]) + (self.start_pool["endgame"] or 0)
+            pooled = {"start_pool_positions": self._shard_pool[0] or positions, "start_pool_games": int(games.item())}
         scores = None
         if self.score_samples:
             # one score row per sample of this shard; a shard without games (or a _play_shard that does not score) has none, and
@@ -400,7 +478,7 @@ class AlphaZeroLoop:
         return {"games": len(res), "red_wins": wins[1], "black_wins": wins[-1], "draws": wins[0],
                 "avg_steps": float(res["steps"].mean()) if len(res) else 0.0, "new_samples": 2 * int(samples.shape[0]),
                 "total_time": time.time() - t0, "num_workers": self.world, "mode": "hip", "buffer_size": len(self.buffer), **scored,
-                **rescored, **taught}
+                **rescored, **taught, **pooled}
 
     def train_network(self) -> dict:
         """World 1: the reference's step.  World > 1: the same full-batch update computed data-parallel -- every rank
