@@ -747,6 +747,66 @@ int xq_evcache_stats_read(const xq_evcache *cache, xq_evcache_stats *host_out, v
 /* The key the probe builds, computed on the host from one position's float32[15][90] planes (tests). */
 int xq_evcache_key_host(const float *host_planes, uint32_t *host_out12);
 
+/* Request dedup (opt-in): within one step, slots that ask for the same position share one evaluated row.  The packed step
+ * drops idle slots and the evaluation cache drops what the SAME slot asked before; this drops what DIFFERENT slots ask in the
+ * SAME step (a lockstep start, the first plies of every search).  It rests on the cache's two premises -- a request's output
+ * depends only on its 15 planes, and an evaluator kernel's arithmetic for a row does not depend on the row's place in the
+ * batch -- so the games do not change; rows_evaluated counts the rows the network really ran.  The dedup step, on one stream:
+ *     xq_engine_select(eng, nn_input)
+ *     xq_engine_compact_unique(dedup, eng, nn_input)  three kernels and the packed step's gather:
+ *                                                     keys     per waiting slot s: the cache's 12-word key of its planes, and
+ *                                                              atomicMin(&table[hash(key) & (T - 1)], s)
+ *                                                     resolve  with m = the bucket's minimum: rep[s] = m when m != s, all 12
+ *                                                              key words agree and the legal-move counts agree, else s
+ *                                                     compact  xq_engine_compact restricted to waiting slots with rep[s] == s,
+ *                                                              into the engine's own live count and row map; the buckets
+ *                                                              this step used are stored back to "empty"
+ *     <evaluator over the packed rows>                as in the packed step
+ *     xq_engine_expand_dedup(dedup, eng, logits, value)   per waiting slot s: the packed row of rep[s] goes to slot s of
+ *                                                     slot_logits / slot_value; then xq_engine_expand_legal
+ * Every count stays in device memory and every grid is sized by n_games: the sequence records into one graph.
+ * Table: T = the smallest power of two >= max(16, 4 n_slots) int32 buckets, empty (INT32_MAX) before and after every
+ * xq_engine_compact_unique / xq_dedup_rows_batch, eager or replayed; one caller-owned allocation of xq_evdedup_bytes(n_slots)
+ * bytes holds it with 92 B per slot (key, bucket, representative, packed row, four counters).  The minimum does not depend on
+ * the order of the atomics, so the representative of a group is its lowest slot, always.  Two different keys in one bucket are a
+ * "collision": the higher slot evaluates itself.  Equal keys under different legal-move counts are a "mismatch": never
+ * expected, counted, the slot evaluates itself.  Neither can change an answer.  Nothing is kept from one step to the next, so a
+ * weight update needs no invalidation.
+ * Refused with XQ_ERR_ARG before any launch: null pointers, logits not 8-byte aligned, a dedup whose n_slots differs from the
+ * engine's n_games, and an engine the dedup cannot serve: leaf batching (xq_engine_init_leaves, K > 1: a slot asks for several
+ * rows), the evaluation mirror (xq_engine_init_em: equal planes are evaluated under different orientations) and arena games
+ * (manual_moves = 2: two models answer).  The evaluation cache is an object of its own that neither handle knows of: its step
+ * (xq_evcache_probe / xq_engine_compact_misses) and this one are alternatives, and the Python engine refuses to own both.
+ * xq_evdedup_bytes returns 0 for n_slots <= 0 or above 2^24. */
+typedef struct xq_evdedup {
+    int32_t n_slots, table_size, reserved[2];
+    void *p[8];                   /* device addresses in the caller's allocation; treat as opaque */
+} xq_evdedup;
+typedef struct xq_evdedup_stats {
+    uint64_t requests;            /* waiting slots (or live rows) seen */
+    uint64_t merged;              /* requests answered by another slot's row: requests - merged rows were evaluated */
+    uint64_t collisions;          /* another key held the bucket: not merged, evaluated */
+    uint64_t mismatches;          /* the key matched, the legal-move count did not: must stay 0 */
+    uint64_t reserved[4];
+} xq_evdedup_stats;
+size_t xq_evdedup_bytes(int n_slots);
+/* Carves dev_mem (256-byte aligned, >= xq_evdedup_bytes), empties the table and zeroes the counters (asynchronous on stream). */
+int xq_evdedup_init(xq_evdedup *dedup, int n_slots, void *dev_mem, size_t bytes, void *stream);
+int xq_engine_compact_unique(const xq_evdedup *dedup, const xq_engine *eng, const float *dev_nn_input, void *stream);
+int xq_engine_expand_dedup(const xq_evdedup *dedup, const xq_engine *eng, const float *dev_packed_logits,
+                           const float *dev_packed_value, void *stream);
+/* Synchronises `stream`, sums the per-slot counters. */
+int xq_evdedup_stats_read(const xq_evdedup *dedup, xq_evdedup_stats *host_out, void *stream);
+/* The bucket of a 12-word key (xq_evcache_key_host) in a table of table_size buckets, a power of two; needs no GPU.
+ * XQ_ERR_ARG for a null key or another size. */
+int xq_evdedup_bucket_host(const uint32_t *key12, int table_size);
+/* The same keys / resolve / compact kernels over n <= n_slots caller-owned request rows (tests, tools): dev_x float32[n][15][90],
+ * dev_counts int32[n] legal-move counts, dev_live_flags int32[n] (0: the row asks for nothing and nothing of it is read past
+ * its flag or written).  dev_rep_out int32[n] receives rep[] of the live rows, dev_rows_out int32[n] the representatives in
+ * row order, dev_n_out int32[1] their number; the dedup's counters count the live rows.  n = 0 writes *dev_n_out = 0. */
+int xq_dedup_rows_batch(const float *dev_x, const int32_t *dev_counts, const int32_t *dev_live_flags, int n,
+                        const xq_evdedup *dedup, int32_t *dev_rep_out, int32_t *dev_rows_out, int32_t *dev_n_out, void *stream);
+
 /* Synchronises `stream`, copies the counters to host. */
 int xq_engine_stats_read(const xq_engine *eng, xq_engine_stats *host_out, void *stream);
 

@@ -19,7 +19,6 @@ over the pairs and the 95 % interval (arena.pair_statistics; without openings th
 only the win rate is given).
 """
 import argparse
-import json
 import sys
 import time
 
@@ -100,13 +99,7 @@ def main():
     ap.add_argument("--sims", type=int, default=100)
     ap.add_argument("--max-game-length", type=int, default=300)
     ap.add_argument("--seed", type=int, default=13)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=500, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
-    if args.child:
-        mc.emit_result(child(json.loads(args.child)))
-        return
+    args = mc.parse_args(ap, 500, child)
     import torch
     if not torch.cuda.is_available():
         sys.exit("tools/measure_arena.py needs a GPU")

@@ -61,6 +61,29 @@ def emit_result(row):
     print("RESULT " + json.dumps(row), flush=True)
 
 
+def parse_args(ap, timeout, child=None):
+    """The three arguments of every tool on the runner (`--out`, `--timeout` per child, `--child`), then the parse.  With `child`,
+    a child process (`--child <job>`) puts the job's `tree_path` (default: this tree) first on sys.path, emits `child(job)` and ends."""
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--timeout", type=int, default=timeout, help="seconds per child")
+    ap.add_argument("--child", default=None)
+    args = ap.parse_args()
+    if child and args.child:
+        job = json.loads(args.child)
+        sys.path.insert(0, job.get("tree_path", ROOT))
+        emit_result(child(job))
+        sys.exit(0)
+    return args
+
+
+def record_hash(samples, results):
+    """16 hex digits over the sorted results and samples of a run: equal for equal games, whatever order they finished in."""
+    import hashlib
+    import numpy as np
+    return hashlib.sha256(np.sort(results, order=["slot", "game_seq"]).tobytes() +
+                          np.sort(samples, order=["slot", "game_seq", "ply"]).tobytes()).hexdigest()[:16]
+
+
 def run_children(script, jobs, timeout, out, out_path=None, argv=lambda job: [], cwd=lambda job: ROOT, after_each=None):
     """Run `script <argv(job)> --child <json of job>` once per job, each in a fresh process under `timeout -k 10 <timeout>` in
     `cwd(job)`.  A child fails by a non-zero exit status or by printing no result line: the tail of its output is shown,
@@ -126,6 +149,74 @@ def trace(preset, steps, engine_kw, keys, drain=None):
     st = eng.stats()
     print(json.dumps({**keys(eng, st), "steps": eng.steps, "launch": eng.launch_mode, "wall_s": wall, "moves": st["moves_played"],
                       "sims": st["sims"], "overflow": st["overflow"]}), flush=True)
+
+
+def off_on_child(job, p, opt):
+    """One run of an off/on measurement of an engine option on the tree the child was started for (with the option off it uses
+    only what the parent commit's tree has too).  `opt`: the job's key that says "on" or "off", `config_key` (as a training loop
+    sets it), `engine_kw` (the engine's keyword and its key in the stats) and `extra(stats, steps)`, the option's own figures.
+    Complete games through run_games at preset `p` (packed step, replayed graph, weights job["weights"], default peaked):
+    games/hour and a hash of the sorted records; then `step_steps` graph replays from a staggered start in chunks of 100 between
+    two device events: microseconds per step, and `extra` again as step_*."""
+    import torch
+    from xiangqi_alphazero_amd import selfplay
+    on = job[opt["job_key"]] == "on"
+    net = make_net(p["channels"], p["blocks"], GAINS[job.get("weights", "peaked")])
+    cfg = selfplay_config(p, **({opt["config_key"]: True} if on else {}))
+    samples, results, st, elapsed = selfplay.run_games(net, cfg, p["games"], "cuda", n_slots=p["slots"], seed=11,
+                                                       poll_every=poll_every(p))
+    torch.cuda.synchronize()
+    assert bool(st.get(opt["engine_kw"], False)) == on and int(st["overflow"]) == 0
+    row = {"preset": job["preset"], "weights": job.get("weights", "peaked"), "tree": job["tree"], opt["engine_kw"]: on,
+           "path": st["path"], "launch": st["launch"], "games": int(len(results)), "samples": int(len(samples)),
+           "wall_s": round(elapsed, 2), "games_per_hour": round(len(results) * 3600.0 / elapsed, 1),
+           "mean_plies": round(float(results["steps"].mean()), 2), "moves": int(st["moves_played"]), "sims": int(st["sims"]),
+           "steps": int(st["steps"]), "rows_evaluated": int(st["rows_evaluated"]), "record_hash": record_hash(samples, results),
+           **opt["extra"](st, int(st["steps"]))}
+    eng = staggered_engine(p, net, **({opt["engine_kw"]: True} if on else {}))
+    assert eng.capture_step() and eng.launch_mode == "graph"
+    chunk = 100
+    for _ in range(64):
+        eng.step()
+    before, chunks = eng.stats(), []
+    for _ in range(int(job["step_steps"]) // chunk):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(chunk):
+            eng.step()
+        b.record()
+        chunks.append((a, b))
+        eng.drain_device()
+    torch.cuda.synchronize()
+    us = sorted(1000.0 * a.elapsed_time(b) / chunk for a, b in chunks)
+    est = eng.stats()
+    assert int(est["overflow"]) == 0
+    timed = {k: v - before[k] for k, v in est.items() if isinstance(v, int) and not isinstance(v, bool) and k in before}
+    row.update(step_us_mean=round(sum(us) / len(us), 3), step_us_median=round(us[len(us) // 2], 3), step_us_min=round(us[0], 3),
+               step_steps=len(us) * chunk, step_rows_evaluated=int(est["rows_evaluated"]),
+               **{"step_" + k: v for k, v in opt["extra"](timed, len(us) * chunk).items()})
+    return row
+
+
+def off_on_steps_child(job, p, opt):
+    """`steps` eager steps (packed, or the option's own) of a staggered engine at preset `p` with the option on or off and nothing else: the child to
+    take a kernel trace around, in a run of its own."""
+    on = job[opt["job_key"]] == "on"
+    eng = staggered_engine(p, out_rows_per_slot=64, **({opt["engine_kw"]: True} if on else {}))
+    replay_steps(eng, int(job["steps"]))                         # eager: no step is captured here
+    st = eng.stats()
+    assert int(st["overflow"]) == 0
+    return {opt["engine_kw"]: on, "steps": int(job["steps"]), "rows_evaluated": int(st["rows_evaluated"]), "slots": p["slots"],
+            "preset": job["preset"], **opt["extra"](st, int(job["steps"]))}
+
+
+def off_on_jobs(parent_tree, repeats, job_key, **job):
+    """The jobs of `repeats` alternated pairs: `off` on `parent_tree`, a built checkout of the parent commit, `on` on this tree."""
+    if not parent_tree or not os.path.isdir(os.path.join(parent_tree, "xiangqi-alphazero_amd")):
+        sys.exit("--parent-tree: a built checkout of the parent commit is required (the `off` runs are taken on it)")
+    trees = {"parent": os.path.abspath(parent_tree), "this": ROOT}
+    return [dict(job, tree=tree, tree_path=trees[tree], **{job_key: m})
+            for _ in range(repeats) for tree, m in (("parent", "off"), ("this", "on"))]
 
 
 def kernel_mean_us(csv_path, want, without=()):

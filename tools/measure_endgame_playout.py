@@ -102,10 +102,7 @@ def main():
     ap.add_argument("--samples", type=int, default=8192)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--timeout", type=int, default=500)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
+    args = measure_common.parse_args(ap, 500)
     if args.child:
         return child(json.loads(args.child))
     t0 = time.time()

@@ -12,7 +12,6 @@ evaluated per step, ms per step, simulations/s.  Mode "on-nohit" invalidates the
 at a hit rate of 0.  --games adds complete games through run_games (games/hour, the records' digest) -- configs[1] only.
 """
 import argparse
-import json
 import sys
 
 import measure_common as mc
@@ -80,8 +79,6 @@ def child_steps(job):
 
 
 def child_games(job):
-    import hashlib
-    import numpy as np
     import torch
     from xiangqi_alphazero_amd import engine, selfplay
     c = CONFIGS[job["config"]]
@@ -90,31 +87,22 @@ def child_games(job):
     samples, results, st, elapsed = selfplay.run_games(_net(c, job["weights"]), cfg, c["slots"], "cuda", n_slots=c["slots"],
                                                        seed=11, poll_every=256, eval_cache_entries=K)
     torch.cuda.synchronize()
-    digest = hashlib.sha256(np.sort(results, order=["slot", "game_seq"]).tobytes() +
-                            np.sort(samples, order=["slot", "game_seq", "ply"]).tobytes()).hexdigest()[:16]
     return {"config": job["config"], "weights": job["weights"], "mode": job["mode"], "kind": "games", "path": st["path"],
             "launch": st["launch"], "games": int(len(results)), "wall_s": round(elapsed, 2),
             "games_per_hour": round(len(results) * 3600.0 / elapsed, 1), "simulations_per_s": round(st["sims"] / elapsed, 1),
             "steps": int(st["steps"]), "rows_evaluated": int(st["rows_evaluated"]), "eval_cache_hits": int(st["eval_cache_hits"]),
             "eval_cache_probes": int(st["eval_cache_probes"]), "mismatches": int(st.get("eval_cache_mismatches", 0)),
-            "records_sha256_16": digest}
+            "records_sha256_16": mc.record_hash(samples, results)}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, choices=(1, 2), default=1)
-    ap.add_argument("--out", default=None)
     ap.add_argument("--games", action="store_true", help="also complete games through run_games (configs[1])")
     ap.add_argument("--warm-moves", type=int, default=2)
     ap.add_argument("--steps", type=int, default=0, help="timed steps (default: 2000 at configs[1], 200 at configs[2])")
     ap.add_argument("--reps", type=int, default=1, help="off/on pairs per weight set")
-    ap.add_argument("--timeout", type=int, default=600, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
-    if args.child:
-        job = json.loads(args.child)
-        mc.emit_result(child_games(job) if job.get("kind") == "games" else child_steps(job))
-        return
+    args = mc.parse_args(ap, 600, lambda job: child_games(job) if job.get("kind") == "games" else child_steps(job))
     steps = args.steps or (2000 if args.config == 1 else 200)
     jobs = []
     for w in GAINS:

@@ -9,11 +9,9 @@ asymmetric a network is -- the quantity the option averages away.
 Every run is a fresh child process under `timeout -k`; the first failing run ends the measurement.
 
 Mode a.  `--parent-tree` is a built checkout of the PARENT commit (its libxq_hip.so in place).  The "off" runs are taken there,
-the "on" runs on this tree, alternated parent, this, parent, this ... in one call.  A child is this file run with the tree it
-measures first on sys.path; on the parent's tree it uses only what both trees have.  Per run (preset cfg1 = BASELINE configs[1]:
-1024 slots x 400 simulations x 128x6, peaked weights, games_target 1024):
-  * complete games through run_games (packed step, replayed graph): games/hour;
-  * the replayed step: `--step-steps` graph replays from a staggered start between two device events, microseconds per step.
+the "on" runs on this tree, alternated parent, this, parent, this ... in one call, each measure_common.off_on_child with the tree
+it measures first on sys.path (preset cfg1 = BASELINE configs[1]: 1024 slots x 400 simulations x 128x6, peaked weights,
+games_target 1024): games/hour of complete games, and microseconds per replayed step over `--step-steps` graph replays.
 The margin of each figure is the spread (max - min) of the PARENT's own runs in this call: with `--repeats 2` the distance of two
 runs, a weak margin.  Read "within_margin" as "not distinguishable here", not as "no cost".  Games with the option on are other
 games (the network's answers differ), so games/hour also moves with the games' lengths; the step time does not.
@@ -43,45 +41,7 @@ import measure_common as mc
 from measure_common import ROOT
 
 PRESETS = {k: mc.PRESETS[k] for k in ("cfg1", "small")}
-
-
-def child_a(job):
-    import torch
-    from xiangqi_alphazero_amd import selfplay
-    p = PRESETS[job["preset"]]
-    on = job["mirror"] == "on"
-    net = mc.make_net(p["channels"], p["blocks"])
-    cfg = mc.selfplay_config(p, **({"eval_random_mirror": True} if on else {}))   # the config key, as a training loop sets it
-    samples, results, st, elapsed = selfplay.run_games(net, cfg, p["games"], "cuda", n_slots=p["slots"], seed=11, poll_every=256)
-    torch.cuda.synchronize()
-    assert bool(st.get("eval_mirror", False)) == on and int(st["overflow"]) == 0
-    row = {"preset": job["preset"], "tree": job["tree"], "eval_mirror": on, "path": st["path"], "launch": st["launch"],
-           "games": int(len(results)), "samples": int(len(samples)), "wall_s": round(elapsed, 2),
-           "games_per_hour": round(len(results) * 3600.0 / elapsed, 1), "mean_plies": round(float(results["steps"].mean()), 2),
-           "moves": int(st["moves_played"]), "sims": int(st["sims"]), "steps": int(st["steps"]),
-           "rows_evaluated": int(st["rows_evaluated"])}
-    # the replayed step from a staggered start: one graph launch per step between two device events
-    eng = mc.staggered_engine(p, net, **({"eval_mirror": True} if on else {}))
-    assert eng.capture_step() and eng.launch_mode == "graph"
-    steps, warm, chunk = int(job["step_steps"]), 64, 100
-    for _ in range(warm):
-        eng.step()
-    chunks = []
-    for _ in range(steps // chunk):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(chunk):
-            eng.step()
-        b.record()
-        chunks.append((a, b))
-        eng.drain_device()
-    torch.cuda.synchronize()
-    us = sorted(1000.0 * a.elapsed_time(b) / chunk for a, b in chunks)
-    est = eng.stats()
-    assert int(est["overflow"]) == 0
-    row.update(step_us_mean=round(sum(us) / len(us), 3), step_us_median=round(us[len(us) // 2], 3), step_us_min=round(us[0], 3),
-               step_steps=len(us) * chunk, step_rows_evaluated=int(est["rows_evaluated"]))
-    return row
+OPT = dict(job_key="mirror", config_key="eval_random_mirror", engine_kw="eval_mirror", extra=lambda st, steps: {})
 
 
 def child_b(job):
@@ -113,18 +73,8 @@ def child_b(job):
             "prior_total_variation": {"mean": round(float(tv.mean()), 6), "max": round(float(tv.max()), 6)}}
 
 
-def child_steps(job):
-    p = PRESETS[job["preset"]]
-    on = job["mirror"] == "on"
-    eng = mc.staggered_engine(p, out_rows_per_slot=64, **({"eval_mirror": True} if on else {}))
-    mc.replay_steps(eng, int(job["steps"]))                      # eager: no step is captured here
-    st = eng.stats()
-    assert int(st["overflow"]) == 0
-    return {"eval_mirror": on, "steps": int(job["steps"]), "rows_evaluated": int(st["rows_evaluated"]), "slots": p["slots"],
-            "preset": job["preset"]}
-
-
-CHILDREN = {"a": child_a, "b": child_b, "steps": child_steps}
+CHILDREN = {"a": lambda job: mc.off_on_child(job, PRESETS[job["preset"]], OPT), "b": child_b,
+            "steps": lambda job: mc.off_on_steps_child(job, PRESETS[job["preset"]], OPT)}
 
 
 def summarise(out, job, row):
@@ -141,23 +91,11 @@ def main():
     ap.add_argument("--positions", type=int, default=1024, help="mode b: corpus positions")
     ap.add_argument("--mirror", choices=("on", "off"), default="on", help="mode steps")
     ap.add_argument("--steps", type=int, default=400, help="mode steps")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
-    if args.child:
-        job = json.loads(args.child)
-        sys.path.insert(0, job["tree_path"])
-        mc.emit_result(CHILDREN[args.mode](job))
-        return
+    args = mc.parse_args(ap, 400, lambda job: CHILDREN[job["mode"]](job))
     out = {"tool": "tools/measure_eval_mirror.py", "mode": args.mode, "runs": []}
     if args.mode == "a":
-        if not args.parent_tree or not os.path.isdir(os.path.join(args.parent_tree, "xiangqi-alphazero_amd")):
-            sys.exit("--parent-tree: a built checkout of the parent commit is required (the `off` runs are taken on it)")
-        trees = {"parent": os.path.abspath(args.parent_tree), "this": ROOT}
         out.update(preset=dict(PRESETS[args.preset], name=args.preset), weights="peaked", order=[])
-        jobs = [dict(mode="a", preset=args.preset, tree=tree, tree_path=trees[tree], mirror=m, step_steps=args.step_steps)
-                for _ in range(args.repeats) for tree, m in (("parent", "off"), ("this", "on"))]
+        jobs = mc.off_on_jobs(args.parent_tree, args.repeats, "mirror", mode="a", preset=args.preset, step_steps=args.step_steps)
     elif args.mode == "b":
         jobs = [dict(mode="b", tree="this", tree_path=ROOT, weights=w, channels=128, blocks=6, positions=args.positions)
                 for w in ("random", "peaked")]

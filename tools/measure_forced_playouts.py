@@ -18,7 +18,6 @@ the option is not measured here.
 instance the same engine launches without the option: the comparison figure) and once with --forced 2.
 """
 import argparse
-import json
 import sys
 
 import measure_common as mc
@@ -76,15 +75,9 @@ def main():
     ap.add_argument("--forced", type=float, default=K_FORCED, help="trace: k, 0 = the engine without the option")
     ap.add_argument("--steps", type=int, default=700, help="trace: replayed steps")
     ap.add_argument("--cap", action="store_true", help="trace: with the playout cap")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
+    args = mc.parse_args(ap, 400, child_games)
     if args.part == "trace":
         trace(args.preset, args.forced, args.steps, args.cap)
-        return
-    if args.child:
-        mc.emit_result(child_games(json.loads(args.child)))
         return
     p = PRESETS[args.preset]
     jobs = [dict(preset=args.preset, weights=w, mode=m) for w in args.weights for m in args.modes]   # off / on alternate

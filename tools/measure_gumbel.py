@@ -22,7 +22,6 @@ formula: the share of the target's mass that lies on unvisited children.
 (the instances the same engine launches without the option: the comparison figure) and once with --gumbel 16.
 """
 import argparse
-import json
 import sys
 
 import measure_common as mc
@@ -130,17 +129,10 @@ def main():
     ap.add_argument("--steps", type=int, default=700, help="trace: replayed steps")
     ap.add_argument("--sims", type=int, default=32, help="shape: simulations per move")
     ap.add_argument("--positions", type=int, default=512, help="shape: positions searched again")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
+    args = mc.parse_args(ap, 400, lambda job: shape(job["preset"], job["sims"], job["weights"], job["positions"])
+                         if job.get("shape") else child_games(job))
     if args.part == "trace":
         trace(args.preset, args.gumbel, args.steps)
-        return
-    if args.child:
-        job = json.loads(args.child)
-        row = shape(job["preset"], job["sims"], job["weights"], job["positions"]) if job.get("shape") else child_games(job)
-        mc.emit_result(row)
         return
     p = PRESETS[args.preset]
     if args.part == "shape":

@@ -34,7 +34,6 @@ import time
 import types
 
 import measure_common as mc
-from measure_common import ROOT
 
 PEAKED_GAIN = mc.GAINS["peaked"]
 BATCH = 256
@@ -233,6 +232,8 @@ def stage_train(buf, runs):
 
 def child(job):
     import torch
+    if not torch.cuda.is_available():
+        sys.exit("no GPU: nothing here is measured without one")
     from xiangqi_alphazero_amd import training
     from xiangqi_alphazero_amd import sample_format as F
     p = PRESETS[job["preset"]]
@@ -266,17 +267,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20, help="grouping: repeats in the timed window")
     ap.add_argument("--launches", type=int, default=2000, help="batch: launches per run")
     ap.add_argument("--runs", type=int, default=3, help="batch and train: alternated runs per arm")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=540, help="seconds for the child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
-    if args.child:
-        sys.path.insert(0, ROOT)
-        import torch
-        if not torch.cuda.is_available():
-            sys.exit("no GPU: nothing here is measured without one")
-        mc.emit_result(child(json.loads(args.child)))
-        return
+    args = mc.parse_args(ap, 540, child)
     job = dict(preset=args.preset, parent_lib=os.path.abspath(args.parent_lib) if args.parent_lib else None, stages=args.stages,
                reps=args.reps, launches=args.launches, runs=args.runs, out=os.path.abspath(args.out) if args.out else None)
     sys.exit(0 if mc.run_children(__file__, [job], args.timeout, {}) else 1)       # the child writes --out itself, stage by stage

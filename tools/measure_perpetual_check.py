@@ -72,18 +72,12 @@ def main():
     ap.add_argument("--rule", type=int, default=1, help="trace: 1 = the rule on, 0 = the engine without the option")
     ap.add_argument("--steps", type=int, default=700, help="trace: replayed steps")
     ap.add_argument("--stats", nargs="*", default=[], help="spread: name=<kernel_stats.csv>,<kernel_stats.csv>,... per group")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
+    args = mc.parse_args(ap, 400, child_games)
     if args.part == "trace":
         trace(args.preset, args.rule, args.steps)
         return
     if args.part == "spread":
         spread(args.stats, args.out)
-        return
-    if args.child:
-        mc.emit_result(child_games(json.loads(args.child)))
         return
     out = {"tool": "tools/measure_perpetual_check.py", "preset": dict(PRESETS[args.preset], name=args.preset), "weights": "peaked",
            "seed": 11, "runs": []}

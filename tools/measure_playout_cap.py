@@ -16,7 +16,6 @@ reuse.  Whether training gains from the trade is not measured here.
 `trace` runs replayed cap-on steps at configs[1] from a staggered start for a kernel trace of k_select / k_expand.
 """
 import argparse
-import json
 import sys
 
 import measure_common as mc
@@ -62,15 +61,9 @@ def main():
     ap.add_argument("--preset", choices=sorted(PRESETS), default="cfg1")
     ap.add_argument("--weights", choices=sorted(GAINS), nargs="*", default=sorted(GAINS))
     ap.add_argument("--modes", choices=MODES, nargs="*", default=list(MODES))
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
+    args = mc.parse_args(ap, 400, child_games)
     if args.part == "trace":
         trace()
-        return
-    if args.child:
-        mc.emit_result(child_games(json.loads(args.child)))
         return
     p = PRESETS[args.preset]
     jobs = [dict(preset=args.preset, weights=w, mode=m) for w in args.weights for m in args.modes]   # off / on alternate

@@ -188,10 +188,7 @@ def main():
     ap.add_argument("--runs", choices=("parent", "this"), nargs="*", default=["parent", "this"] * 3, help="train: the alternation")
     ap.add_argument("--epochs", type=int, default=12, help="train: epochs in the timed window")
     ap.add_argument("--parent-tree", default=None, help="train: a checkout of the parent commit with its library built")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=300, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
+    args = mc.parse_args(ap, 300)
     if args.child:                                       # a child of a `parent` run imports the parent commit's package
         job = json.loads(args.child)
         sys.path.insert(0, job.get("tree") or ROOT)

@@ -27,11 +27,9 @@ Whether a network trained on the mixed target is stronger is NOT measured here: 
 """
 import argparse
 import json
-import os
 import sys
 
 import measure_common as mc
-from measure_common import ROOT
 
 PRESETS = {k: mc.PRESETS[k] for k in ("cfg1", "small")}
 BUCKETS = ((0, 20), (20, 40), (40, 80), (80, 120), (120, 1 << 16))
@@ -104,22 +102,10 @@ def main():
     ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit: the `off` runs are taken there")
     ap.add_argument("--repeats", type=int, default=2, help="parent/this pairs")
     ap.add_argument("--select-steps", type=int, default=600)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
-    if args.child:
-        job = json.loads(args.child)
-        sys.path.insert(0, job["tree_path"])
-        mc.emit_result(child(job))
-        return
-    if not args.parent_tree or not os.path.isdir(os.path.join(args.parent_tree, "xiangqi-alphazero_amd")):
-        sys.exit("--parent-tree: a built checkout of the parent commit is required (the `off` runs are taken on it)")
-    trees = {"parent": os.path.abspath(args.parent_tree), "this": ROOT}
+    args = mc.parse_args(ap, 400, child)
     out = {"tool": "tools/measure_root_stats.py", "preset": dict(PRESETS[args.preset], name=args.preset), "weights": "peaked",
            "order": [], "runs": []}
-    jobs = [dict(preset=args.preset, tree=tree, tree_path=trees[tree], root_stats=rs, select_steps=args.select_steps)
-            for _ in range(args.repeats) for tree, rs in (("parent", "off"), ("this", "on"))]
+    jobs = mc.off_on_jobs(args.parent_tree, args.repeats, "root_stats", preset=args.preset, select_steps=args.select_steps)
     ok = mc.run_children(__file__, jobs, args.timeout, out, args.out, cwd=lambda job: job["tree_path"], after_each=summarise)
     if "summary" in out:
         print(json.dumps(out["summary"], indent=1))

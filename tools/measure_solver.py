@@ -95,10 +95,7 @@ def main():
     ap.add_argument("--solver", type=int, default=1, help="trace: 1 = the solver on, 0 = the engine without the option")
     ap.add_argument("--steps", type=int, default=700, help="trace: replayed steps")
     ap.add_argument("--stats", nargs="*", default=[], help="spread: name=<kernel_stats.csv>,<kernel_stats.csv>,... per group")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
+    args = mc.parse_args(ap, 400)
     if args.part == "trace":
         trace(args.preset, args.solver, args.steps)
         return

@@ -14,10 +14,7 @@ def child(job):  # noqa: E302
 ap =argparse.ArgumentParser()
 ap.add_argument("--preset", choices=sorted(mc.PRESETS), default="small")
 ap.add_argument("--prob", type=float, nargs="*", default=[0.0, 1.0, 0.25], help="0 = the option off")
-ap.add_argument("--out", default=None)
-ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
-ap.add_argument("--child", default=None)
-args = ap.parse_args()
+args = mc.parse_args(ap, 400)
 if args.child:
     mc.emit_result(child(json.loads(args.child)))
 else:

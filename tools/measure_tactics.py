@@ -137,10 +137,7 @@ def main():
     ap.add_argument("--max-moves", type=int, default=3)
     ap.add_argument("--all-moves", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--timeout", type=int, default=300)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
+    args = measure_common.parse_args(ap, 300)
     if args.child:
         return solve_child(json.loads(args.child))
     t0 = time.time()

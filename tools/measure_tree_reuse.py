@@ -14,7 +14,6 @@ games/hour, steps, rows evaluated, new simulations, reused visits and the reused
 start, long enough that slots end moves every step, for a kernel trace of k_reroot.
 """
 import argparse
-import json
 import sys
 
 import measure_common as mc
@@ -29,8 +28,6 @@ TRACE = {1: dict(mc.PRESETS["cfg1"], steps=700),
 
 
 def child_games(job):
-    import hashlib
-    import numpy as np
     import torch
     from xiangqi_alphazero_amd import engine, selfplay
     p = PRESETS[job["preset"]]
@@ -39,8 +36,6 @@ def child_games(job):
                                                        mc.selfplay_config(p), p["games"], "cuda", n_slots=p["slots"], seed=11,
                                                        poll_every=mc.poll_every(p), eval_cache_entries=K, tree_reuse=job["mode"] != "off")
     torch.cuda.synchronize()
-    digest = hashlib.sha256(np.sort(results, order=["slot", "game_seq"]).tobytes() +
-                            np.sort(samples, order=["slot", "game_seq", "ply"]).tobytes()).hexdigest()[:16]
     visits = int(sum(int(s["visits"][:s["n_moves"]].sum()) for s in samples))
     total = st["sims"] + st["reused_visits"]
     return {"preset": job["preset"], "weights": job["weights"], "mode": job["mode"], "path": st["path"], "launch": st["launch"],
@@ -49,7 +44,7 @@ def child_games(job):
             "reused_visits": int(st["reused_visits"]), "reroots": int(st["reroots"]),
             "reused_share": round(st["reused_visits"] / total, 4) if total else 0.0, "moves": int(st["moves_played"]),
             "sample_visits_equal_sims_plus_reused": visits == total, "eval_cache_hits": int(st["eval_cache_hits"]),
-            "overflow": int(st["overflow"]), "records_sha256_16": digest}
+            "overflow": int(st["overflow"]), "records_sha256_16": mc.record_hash(samples, results)}
 
 
 def trace(config):
@@ -62,15 +57,9 @@ def main():
     ap.add_argument("part", choices=["games", "trace"])
     ap.add_argument("--preset", choices=sorted(PRESETS), default="cfg1")
     ap.add_argument("--config", type=int, choices=(1, 2), default=1)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--timeout", type=int, default=400, help="seconds per child")
-    ap.add_argument("--child", default=None)
-    args = ap.parse_args()
+    args = mc.parse_args(ap, 400, child_games)
     if args.part == "trace":
         trace(args.config)
-        return
-    if args.child:
-        mc.emit_result(child_games(json.loads(args.child)))
         return
     p = PRESETS[args.preset]
     jobs = [dict(preset=args.preset, weights=w, mode=m) for w in GAINS for m in p["modes"]]   # alternated within each weight set

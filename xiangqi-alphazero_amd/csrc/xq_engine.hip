@@ -9,6 +9,8 @@
 //                          xq_engine_init*, and the host-side readers (stats, drain, set_position, read_root).
 //   xq_engine_packed.hip : the packed steps -- compaction, gather, scatter, and the arena's two-set variant.
 //   xq_evcache.hip       : the evaluation cache (xq_evcache_*, xq_engine_compact_misses).
+//   xq_evdedup.hip       : the request dedup (xq_evdedup_*, xq_engine_compact_unique / _expand_dedup, xq_dedup_rows_batch); the
+//                          key both share is in xq_evkey.cuh.
 //   xq_rules.cuh         : the wave-level rules, shared with the stateless tools (xq_batch, xq_replay, xq_supervise, xq_alphabeta,
 //                          xq_mate .hip); what only those five share is in xq_tools.cuh, which nothing of the engine includes.
 //

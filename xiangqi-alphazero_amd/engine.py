@@ -108,6 +108,19 @@ history, and every ply counter counts from there.  The engine checks the pool fi
 the rules code cannot run on; an entry without a legal move is a game that finishes at ply 0 with no sample.  `start_indices()`
 reads the entry every slot's current game started from (-1: the initial position), `start_pool_stats()` the number of pool games.
 Self-play only; not with record_games, whose record has no room for a start position; every other option.
+
+With `eval_dedup=True` (opt-in; xq_evdedup_*) slots that ask for the same position in the same step share
+one evaluated row, and `step()` / `capture_step()` take the DEDUP step:
+
+    select  ->  keys + resolve (per waiting slot: the cache's exact 12-word key, the lowest slot with that key and count represents
+                it)  ->  compact the representatives + gather  ->  evaluator over n_live rows
+            ->  every waiting slot takes its representative's row + expand
+
+The row a slot is handed is bit-identical to the one it would have computed, so the games are those of the packed step;
+`rows_evaluated` counts only the rows the network ran on and `stats()` adds `eval_dedup_requests`, `eval_dedup_merged`,
+`eval_dedup_collisions` (two positions in one bucket: the higher slot evaluates itself) and `eval_dedup_mismatches` (must stay 0).
+Nothing is kept across steps, so a weight update needs no invalidation.  It needs the packed step (an evaluator with `live_rows`);
+not with the evaluation cache, leaves_per_step > 1, eval_mirror or arena games; every other option.
 """
 from __future__ import annotations
 
@@ -167,6 +180,7 @@ class EngineOptions(collections.namedtuple("EngineOptions", "K flags cap forced 
     root_stats = None          # hip.RootStatsOpts or None: what xq_engine_*_rs take after `solver`
     eval_mirror = None         # hip.EvalMirrorOpts or None: what xq_engine_*_em take after `root_stats`
     game_records = None        # hip.GameRecordsOpts or None: what xq_engine_*_gr take after `eval_mirror`
+    eval_dedup = False         # no C struct: the dedup is an object of its own (hip.DedupTable), like the evaluation cache
 
 
 RULES_REASONS = (1, 4)     # a result's `reason` for a game the rules ended: is_game_over, and its perpetual-check verdict
@@ -207,7 +221,8 @@ def parse_start_pool(cfg: hip.EngineConfig, start_pool, record_games: bool = Fal
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
                          forced_playouts=None, gumbel=None, arena_opts=None, eval_cache_entries: int = 0,
                          perpetual_check: bool = False, solver: bool = False, root_stats: bool = False,
-                         eval_mirror: bool = False, record_games: bool = False, max_out_games=None) -> EngineOptions:
+                         eval_mirror: bool = False, record_games: bool = False, max_out_games=None,
+                         eval_dedup: bool = False) -> EngineOptions:
     """The engine options of `SelfPlayEngine` checked and turned into the C structs; needs no GPU.  Every rule of the header's
     refusal lists (include/xq_hip.h; opts_ok in csrc/xq_engine_setup.hip) is refused here first, with a message that names the
     option; tests/test_engine_options.py holds the two side by side."""
@@ -316,6 +331,18 @@ def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tre
     if eval_mirror and eval_cache_entries:
         raise hip.XqError("eval_mirror cannot be combined with an evaluation cache (eval_cache_entries > 0): a hit would return "
                           "whichever orientation was evaluated first")
+    if eval_dedup not in (False, True, 0, 1):
+        raise hip.XqError(f"eval_dedup must be a bool, got {eval_dedup!r}")
+    if eval_dedup and eval_cache_entries:
+        raise hip.XqError("eval_dedup cannot be combined with an evaluation cache (eval_cache_entries > 0): the cached step "
+                          "compacts by its own hit flags")
+    if eval_dedup and K > 1:
+        raise hip.XqError("eval_dedup cannot be combined with leaves_per_step > 1: a slot then asks for several rows")
+    if eval_dedup and eval_mirror:
+        raise hip.XqError("eval_dedup cannot be combined with eval_mirror: equal planes are evaluated under different orientations")
+    if eval_dedup and int(cfg.manual_moves) == 2:
+        raise hip.XqError("eval_dedup is a self-play and search option: not available for arena games (manual_moves = 2), where "
+                          "two models answer")
     if record_games not in (False, True, 0, 1):
         raise hip.XqError(f"record_games must be a bool, got {record_games!r}")
     if max_out_games is not None and not record_games:
@@ -338,6 +365,7 @@ def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tre
         gr = hip.GameRecordsOpts(1, n_out)
     opts = EngineOptions(K, hip.ENGINE_TREE_REUSE if tree_reuse else 0, cap, forced, gz, ar)
     opts.game_records = gr
+    opts.eval_dedup = bool(eval_dedup)
     if eval_mirror:
         opts.eval_mirror = hip.EvalMirrorOpts(1)
     if solver:
@@ -354,15 +382,18 @@ class SelfPlayEngine:
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
                  perpetual_check: bool = False, solver: bool = False, root_stats: bool = False, eval_mirror: bool = False,
-                 record_games: bool = False, max_out_games=None, start_pool=None):
+                 record_games: bool = False, max_out_games=None, start_pool=None, eval_dedup: bool = False):
         opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
             gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check,
-            solver=solver, root_stats=root_stats, eval_mirror=eval_mirror, record_games=record_games, max_out_games=max_out_games)
+            solver=solver, root_stats=root_stats, eval_mirror=eval_mirror, record_games=record_games, max_out_games=max_out_games,
+            eval_dedup=eval_dedup)
         K, flags, cap, forced, gz, ar = opts
         rules, sv, rs, em, gr = opts.rules, opts.solver, opts.root_stats, opts.eval_mirror, opts.game_records
         if em is not None and not getattr(evaluator, "live_rows", False):
             raise hip.XqError("eval_mirror acts in the packed step only: it needs an evaluator with live_rows (the HIP evaluators)")
+        if opts.eval_dedup and not getattr(evaluator, "live_rows", False):
+            raise hip.XqError("eval_dedup acts in the packed step only: it needs an evaluator with live_rows (the HIP evaluators)")
         pool = parse_start_pool(cfg, start_pool, record_games=gr is not None)
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
@@ -466,6 +497,8 @@ class SelfPlayEngine:
         self.cache = None
         if eval_cache_entries:
             self._init_cache(int(eval_cache_entries))
+        self.eval_dedup = bool(opts.eval_dedup)
+        self.dedup = hip.DedupTable(self.G, self.device) if self.eval_dedup else None
         self._reuse_seen = (self.evaluator, getattr(self.evaluator, "weights_version", 0))
         self.steps = 0
         self._graph = None
@@ -574,6 +607,22 @@ class SelfPlayEngine:
         self._keep = (self.slot_logits, self.slot_value)    # slot-ordered, as the full-width step's (bench.py --dump-outputs)
         self._keep_packed = (legal_logits, value)          # keep alive until the stream has consumed them
 
+    def expand_dedup(self, legal_logits: torch.Tensor, value: torch.Tensor):
+        """Expansion from the PACKED outputs of the dedup step (rows [0, n_live): the representatives'): every waiting slot
+        takes its representative's row into `slot_logits` / `slot_value`, then xq_engine_expand_legal (xq_engine_expand_dedup)."""
+        if self.dedup is None:
+            raise hip.XqError("expand_dedup needs an engine with eval_dedup=True")
+        if legal_logits.dtype != torch.float32 or value.dtype != torch.float32:
+            raise hip.XqError("legal_logits/value must be float32")
+        legal_logits = legal_logits.contiguous()
+        value = value.contiguous().view(-1)
+        if legal_logits.shape != (self.rows, hip.MAXM) or value.shape != (self.rows,):
+            raise hip.XqError(f"bad evaluator output shapes {tuple(legal_logits.shape)} {tuple(value.shape)}")
+        hip.check(self.lib.xq_engine_expand_dedup(C.byref(self.dedup.h), C.byref(self.h), legal_logits.data_ptr(), value.data_ptr(),
+                                                  hip.stream_ptr(self.device)), "xq_engine_expand_dedup")
+        self._keep = (self.slot_logits, self.slot_value)
+        self._keep_packed = (legal_logits, value)          # keep alive until the stream has consumed them
+
     # ---- arena options (xq_engine_init_ar) -----------------------------------------------------------------
     def _need_arena_opts(self, what: str):
         if self.arena_packed is None:
@@ -613,10 +662,12 @@ class SelfPlayEngine:
 
     @property
     def path(self) -> str:
-        """The step `step()` runs: "cached" with an evaluation cache, "packed" when the evaluator evaluates a device-side live
-        row count, else "full"."""
+        """The step `step()` runs: "cached" with an evaluation cache, "dedup" with eval_dedup, "packed" when the evaluator
+        evaluates a device-side live row count, else "full"."""
         if self.cache is not None:
             return "cached"
+        if self.dedup is not None:
+            return "dedup"
         return "packed" if getattr(self.evaluator, "live_rows", False) else "full"
 
     def _one_step(self):
@@ -631,6 +682,15 @@ class SelfPlayEngine:
             ll, value = self._keep_packed                # checked float32 [G, 128] / [G], contiguous
             hip.check(self.lib.xq_evcache_commit(C.byref(self.cache), C.byref(self.h), ll.data_ptr(), value.data_ptr(), sp),
                       "xq_evcache_commit")
+        elif self.dedup is not None:
+            if not getattr(self.evaluator, "live_rows", False):    # the evaluator was swapped: an error, not a silent full-width step
+                raise hip.XqError("eval_dedup needs the packed step: the evaluator has no live_rows")
+            sp = hip.stream_ptr(self.device)
+            x = self.select()
+            hip.check(self.lib.xq_engine_compact_unique(C.byref(self.dedup.h), C.byref(self.h), x.data_ptr(), sp),
+                      "xq_engine_compact_unique")
+            ll, value = self.evaluator.evaluate_legal(self.packed_x, self.packed_moves, self.packed_counts, n_live=self.n_live)
+            self.expand_dedup(ll, value)
         elif self.path == "packed":
             self.select()
             self.compact()
@@ -716,6 +776,8 @@ class SelfPlayEngine:
             out.update({"eval_cache_" + k: v for k, v in cs.as_dict().items()})
             out["eval_cache_entries"] = self.cache_entries
             out["eval_cache_bytes"] = self.cache_bytes
+        if self.dedup is not None:
+            out.update({"eval_dedup_" + k: v for k, v in self.dedup.stats().items()})
         return out
 
     def solver_stats(self) -> dict:

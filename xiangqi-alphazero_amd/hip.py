@@ -275,6 +275,18 @@ class EvCacheStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class EvDedup(C.Structure):
+    """xq_evdedup: the request dedup's geometry and device addresses (opaque)."""
+    _fields_ = [("n_slots", C.c_int32), ("table_size", C.c_int32), ("reserved", C.c_int32 * 2), ("p", C.c_void_p * 8)]
+
+
+class EvDedupStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("requests", "merged", "collisions", "mismatches")] + [("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 _lib = None
 
 
@@ -421,6 +433,14 @@ def lib():
     L.xq_evcache_invalidate.argtypes = [C.POINTER(EvCache), vp]
     L.xq_evcache_stats_read.argtypes = [C.POINTER(EvCache), C.POINTER(EvCacheStats), vp]
     L.xq_evcache_key_host.argtypes = [vp, vp]
+    L.xq_evdedup_bytes.argtypes = [i32]
+    L.xq_evdedup_bytes.restype = C.c_size_t
+    L.xq_evdedup_init.argtypes = [C.POINTER(EvDedup), i32, vp, C.c_size_t, vp]
+    L.xq_engine_compact_unique.argtypes = [C.POINTER(EvDedup), C.POINTER(Engine), vp, vp]
+    L.xq_engine_expand_dedup.argtypes = [C.POINTER(EvDedup), C.POINTER(Engine), vp, vp, vp]
+    L.xq_evdedup_stats_read.argtypes = [C.POINTER(EvDedup), C.POINTER(EvDedupStats), vp]
+    L.xq_evdedup_bucket_host.argtypes = [vp, i32]
+    L.xq_dedup_rows_batch.argtypes = [vp, vp, vp, i32, C.POINTER(EvDedup), vp, vp, vp, vp]
     L.xq_samples_to_requests.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.xq_score_samples.argtypes = [vp, vp, i32, vp, vp, C.POINTER(ScoreOpts), vp, vp]
     L.xq_surprise_counts.argtypes = [vp, i32, C.POINTER(SurpriseOpts), vp, vp, vp]
@@ -473,7 +493,9 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_alphabeta_batch", "xq_records_sample_counts", "xq_records_to_samples", "xq_mate_search_batch",
            "xq_tb_entries", "xq_tb_init", "xq_tb_pass", "xq_tb_probe_batch", "xq_tb_play_batch", "xq_tb_samples",
            "xq_positions_check_batch", "xq_engine_workspace_bytes_sp", "xq_engine_init_sp", "xq_start_pool_draw_host",
-           "xq_engine_start_indices", "xq_engine_start_pool_stats_read"]
+           "xq_engine_start_indices", "xq_engine_start_pool_stats_read", "xq_evdedup_bytes", "xq_evdedup_init",
+           "xq_engine_compact_unique", "xq_engine_expand_dedup", "xq_evdedup_stats_read", "xq_evdedup_bucket_host",
+           "xq_dedup_rows_batch"]
 
 
 def check(rc: int, what: str):
@@ -1096,6 +1118,83 @@ def mirror_requests(x: torch.Tensor, moves: torch.Tensor, counts: torch.Tensor, 
         check(lib().xq_mirror_requests_batch(_dev(x), _dev(moves), _dev(counts), _dev(flags), n, _dev(xo), _dev(mo), stream_ptr(x.device)),
               "xq_mirror_requests_batch")
     return xo, mo
+
+
+def dedup_table_size(n_slots: int) -> int:
+    """The request dedup's bucket count for `n_slots` slots: the smallest power of two >= max(16, 4 n_slots)."""
+    t = 16
+    while t < 4 * int(n_slots):
+        t *= 2
+    return t
+
+
+def dedup_bucket(key12, table_size: int) -> int:
+    """The bucket of a 12-word evaluation key in a table of `table_size` buckets (xq_evdedup_bucket_host; needs no GPU)."""
+    import numpy as np
+    k = np.ascontiguousarray(key12, dtype=np.uint32)
+    if k.shape != (12,):
+        raise XqError(f"dedup_bucket: a key has 12 uint32 words, got shape {k.shape}")
+    b = lib().xq_evdedup_bucket_host(k.ctypes.data, int(table_size))
+    if b < 0:
+        raise XqError(f"xq_evdedup_bucket_host failed: code {b} (table_size must be a power of two, got {table_size})")
+    return b
+
+
+class DedupTable:
+    """A request dedup object (xq_evdedup) for up to `n_slots` requests per step, with the device memory it lives in."""
+
+    def __init__(self, n_slots: int, device="cuda"):
+        nbytes = int(lib().xq_evdedup_bytes(int(n_slots)))
+        if nbytes == 0:
+            raise XqError(f"eval_dedup: n_slots must be in [1, 2^24], got {n_slots}")
+        self.n_slots, self.bytes, self.device = int(n_slots), nbytes, torch.device(device)
+        self.ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        self.h = EvDedup()
+        with torch.cuda.device(self.device):
+            check(lib().xq_evdedup_init(C.byref(self.h), self.n_slots, (self.ws.data_ptr() + 255) & ~255, nbytes,
+                                        stream_ptr(self.device)), "xq_evdedup_init")
+        self.table_size = int(self.h.table_size)
+
+    def table(self) -> torch.Tensor:
+        """Zero-copy int32 [table_size] view of the buckets (2^31 - 1: empty).  For tests."""
+        off = int(self.h.p[0]) - int(self.ws.data_ptr())
+        return self.ws[off:off + 4 * self.table_size].view(torch.int32)
+
+    def keys(self) -> torch.Tensor:
+        """Zero-copy int32 [n_slots, 12] view of the keys of the last requests (uint32 bits; all 0 where no row ever asked).  For
+        tests."""
+        off = int(self.h.p[1]) - int(self.ws.data_ptr())
+        return self.ws[off:off + 48 * self.n_slots].view(torch.int32).view(self.n_slots, 12)
+
+    def stats(self) -> dict:
+        """requests, merged, collisions, mismatches (xq_evdedup_stats_read).  Synchronises."""
+        s = EvDedupStats()
+        check(lib().xq_evdedup_stats_read(C.byref(self.h), C.byref(s), stream_ptr(self.device)), "xq_evdedup_stats_read")
+        return s.as_dict()
+
+
+def dedup_requests(x: torch.Tensor, counts: torch.Tensor, live: torch.Tensor, table: DedupTable, out=None):
+    """The request dedup's kernels over caller-owned rows (xq_dedup_rows_batch): x float32[n,15,10,9], counts int32[n] legal-move
+    counts, live int32[n] flags -> (rep int32[n], rows int32[n], n_live int32[1]) on the device.  rep[r] of a live row is the
+    row that answers it (itself, or the lowest live row with the same planes and count); rows[:n_live] are the rows that
+    represent themselves, in row order.  Entries of idle rows, and rows[] past n_live, are not written: `out` = (rep, rows,
+    n_live) preallocated keeps whatever it held there."""
+    n = x.shape[0]
+    if x.shape[1:] != (15, 10, 9) or x.dtype != torch.float32 or counts.shape != (n,) or counts.dtype != torch.int32 \
+            or live.shape != (n,) or live.dtype != torch.int32:
+        raise XqError("dedup_requests: x float32[n,15,10,9], counts int32[n], live int32[n] required")
+    if n > table.n_slots:
+        raise XqError(f"dedup_requests: {n} rows do not fit a table made for {table.n_slots}")
+    if out is None:
+        out = (torch.zeros(n, dtype=torch.int32, device=x.device), torch.zeros(n, dtype=torch.int32, device=x.device),
+               torch.zeros(1, dtype=torch.int32, device=x.device))
+    rep, rows, n_live = out
+    if any(t.dtype != torch.int32 for t in out) or rep.shape != (n,) or rows.shape != (n,) or n_live.shape != (1,):
+        raise XqError("dedup_requests: out = (int32[n], int32[n], int32[1]) required")
+    check(lib().xq_dedup_rows_batch(_dev(x) if n else None, _dev(counts) if n else None, _dev(live) if n else None, n,
+                                    C.byref(table.h), _dev(rep) if n else None, _dev(rows) if n else None, _dev(n_live),
+                                    stream_ptr(x.device)), "xq_dedup_rows_batch")
+    return rep, rows, n_live
 
 
 def bias_act_(y: torch.Tensor, bias: torch.Tensor, residual=None, relu: bool = True) -> torch.Tensor:

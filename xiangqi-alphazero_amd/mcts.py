@@ -28,6 +28,10 @@ search's.
 `eval_mirror=True` (opt-in) evaluates every request of the search under a randomly chosen left-right orientation
 (engine.SelfPlayEngine).  The orientation is a function of the seed, the position's index in the call, its
 `move_count` and the request's place in the search, so the same call gives the same answer again: serving stays reproducible.
+
+`eval_dedup=True` (opt-in) evaluates every distinct position of a `search_many` step once (engine.SelfPlayEngine, DESIGN.md
+section 4.24): equal positions among the `n_parallel`, and searches that walk into the same position in the same step, share one
+row of the network's batch.  The visit counts are those of the search without it.
 """
 from __future__ import annotations
 
@@ -66,7 +70,7 @@ def root_value(visits, total_value) -> np.float32:
 class MCTS:
     def __init__(self, model, num_simulations: int = 200, c_puct: float = 1.5, device: str = "cuda",
                  evaluator_kind: str = "auto", seed: int = 0, leaves_per_step: int = 1, perpetual_check: bool = False,
-                 solver: bool = False, eval_mirror: bool = False):
+                 solver: bool = False, eval_mirror: bool = False, eval_dedup: bool = False):
         if not 1 <= int(leaves_per_step) <= 64:
             from .hip import XqError
             raise XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
@@ -74,6 +78,7 @@ class MCTS:
         self.perpetual_check = bool(perpetual_check)
         self.solver = bool(solver)
         self.eval_mirror = bool(eval_mirror)
+        self.eval_dedup = bool(eval_dedup)
         self.model = model
         self.num_simulations = num_simulations
         self.c_puct = c_puct
@@ -101,7 +106,7 @@ class MCTS:
             self._engines[key] = engine.SelfPlayEngine(cfg, self.device, evaluator=self.evaluator,
                                                        leaves_per_step=self.leaves_per_step,
                                                        perpetual_check=self.perpetual_check, solver=self.solver,
-                                                       eval_mirror=self.eval_mirror)
+                                                       eval_mirror=self.eval_mirror, eval_dedup=self.eval_dedup)
         return self._engines[key]
 
     def search_many(self, games: Sequence, temperature: float = 1.0, add_noise: bool = True, return_values: bool = False):

@@ -97,7 +97,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
               eval_cache_entries: Optional[int] = None, leaves_per_step: Optional[int] = None,
               tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None,
               perpetual_check: Optional[bool] = None, solver: Optional[bool] = None, root_stats: Optional[bool] = None,
-              eval_mirror: Optional[bool] = None, record_games: Optional[bool] = None, start_pool=None):
+              eval_mirror: Optional[bool] = None, record_games: Optional[bool] = None, start_pool=None,
+              eval_dedup: Optional[bool] = None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -133,7 +134,13 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     when off), `game_records_recorded` and `game_records_dropped` (0 when off).  The games do not change; every other option.
     `start_pool` = (boards, sides, prob) (an argument only: `start_pool.py` makes the arrays, `AlphaZeroLoop` reads the config
     keys) starts a new game from an entry of the pool with probability prob: stats `start_pool`
-    ((positions, prob), None when off) and `start_pool_games` (0 when off).  Not with record_games; every other option."""
+    ((positions, prob), None when off) and `start_pool_games` (0 when off).  Not with record_games; every other option.
+    `eval_dedup` (None: `config.eval_dedup`, absent = off) evaluates every distinct position once per step (DESIGN.md section
+    4.24): stats `eval_dedup`, `eval_dedup_requests`, `eval_dedup_merged`, `eval_dedup_collisions`, `eval_dedup_mismatches` (0
+    when off).  The games do not change, the network runs on fewer rows; it needs the packed step and excludes the evaluation
+    cache, leaves_per_step > 1 and eval_mirror."""
+    if eval_dedup is None:
+        eval_dedup = bool(getattr(config, "eval_dedup", False))
     if record_games is None:
         record_games = bool(getattr(config, "record_games", False))
     if eval_mirror is None:
@@ -177,7 +184,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     eng = engine.SelfPlayEngine(cfg, device, evaluator=ev, eval_cache_entries=eval_cache_entries,
                                 leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
                                 forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check, solver=solver,
-                                root_stats=root_stats, eval_mirror=eval_mirror, record_games=record_games, start_pool=start_pool)
+                                root_stats=root_stats, eval_mirror=eval_mirror, record_games=record_games, start_pool=start_pool,
+                                eval_dedup=eval_dedup)
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -203,6 +211,9 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     st["root_stats"] = eng.root_stats
     st["eval_mirror"] = eng.eval_mirror
     st["record_games"] = eng.record_games
+    st["eval_dedup"] = eng.eval_dedup
+    for k in ("requests", "merged", "collisions", "mismatches"):   # the dedup's keys are present (0) when it is off
+        st.setdefault("eval_dedup_" + k, 0)
     st["game_records"], st["game_records_recorded"], st["game_records_dropped"] = None, 0, 0
     if eng.record_games:
         st["game_records"] = eng.drain_games_device() if device_records else eng.drain_games()
@@ -231,7 +242,7 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
                        forced_playouts: Optional[float] = None, gumbel=None,
                        perpetual_check: Optional[bool] = None, solver: Optional[bool] = None,
                        record_games: Optional[bool] = None,
-                       start_pool=None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
+                       start_pool=None, eval_dedup: Optional[bool] = None) -> Tuple[List[Tuple[np.ndarray, np.ndarray, float]], Dict[str, Any]]:
     for k in _CFG_KEYS + ("num_games_per_iter",):
         if not hasattr(config, k):
             raise AttributeError(f"config lacks '{k}' (see training/train.py:55-111)")
@@ -244,7 +255,8 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
                                               eval_cache_entries=eval_cache_entries, leaves_per_step=leaves_per_step,
                                               tree_reuse=tree_reuse, playout_cap=playout_cap,
                                               forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check,
-                                              solver=solver, record_games=record_games, start_pool=start_pool)
+                                              solver=solver, record_games=record_games, start_pool=start_pool,
+                                              eval_dedup=eval_dedup)
     all_data, per_game = to_reference_tuples(samples, results, augment=True, q_mix=root_stats_q_mix(config))
     wins = {1: 0, -1: 0, 0: 0}
     total_steps = 0
@@ -269,6 +281,8 @@ def parallel_self_play(model, config, num_workers: Optional[int] = None, use_gpu
         "record_games": st["record_games"], "game_records": st["game_records"],
         "game_records_recorded": st["game_records_recorded"], "game_records_dropped": st["game_records_dropped"],
         "start_pool": st["start_pool"], "start_pool_games": st["start_pool_games"],
+        "eval_dedup": st["eval_dedup"],
+        **{"eval_dedup_" + k: st["eval_dedup_" + k] for k in ("requests", "merged", "collisions", "mismatches")},
     }
     if return_compact:
         stats["compact_samples"], stats["compact_results"] = samples, results
