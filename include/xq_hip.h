@@ -1570,6 +1570,28 @@ int xq_start_pool_draw_host(uint64_t seed, int rank, int slot, uint32_t game_seq
 int xq_engine_start_indices(const xq_engine *eng, const int32_t **dev_index /* [n_games] */);
 int xq_engine_start_pool_stats_read(const xq_engine *eng, xq_start_pool_stats *host_out, void *stream);
 
+/* Settled-move cutoff (opt-in): end a search whose first choice is fixed.  A move played at temperature 0 -- every arena move
+ * (manual_moves = 2), and a search-only engine's (manual_moves = 1) under get_action(temperature = 0) -- is the FIRST MAXIMUM of the
+ * root's visit counts in move order.  xq_engine_settle, called ahead of xq_engine_select in a step and on the same stream, ends
+ * the search of every slot whose remaining simulations cannot move that maximum: one kernel, one wavefront per slot, no LDS, no
+ * scratch, no atomics.  A slot that searches (sims_done < budget = num_simulations) with nch root children is SETTLED when
+ *     nch == 1                          the move is forced, or
+ *     n1 - n2 > budget - sims_done      n1 the largest child visit count, n2 the second largest counted with multiplicity (a tie
+ *                                       for first: lead 0).  Strict: at lead == remaining the runner-up can still tie, and the
+ *                                       first maximum in move order might then be the runner-up.
+ * A simulation adds one visit to one root child, so the rule is exact: no move, game or verdict changes.
+ * A settled slot of an arena engine gets sims_done = budget: the select kernel that follows plays the first maximum as at the end
+ * of a full search, and the next root request resets the word; the simulations not run are not counted in `sims`.  A settled
+ * slot of a search-only engine goes to phase HOLD and keeps its sims_done: xq_engine_read_root reports what was really run.
+ * Slots that wait for an evaluation, idle or hold are not touched.
+ * dev_counters: caller-owned, zeroed by the caller, uint64[n_games][2]; row s is written by slot s's wavefront only -- [0] searches
+ * settled, [1] simulations not run.  The caller sums the columns.
+ * XQ_ERR_ARG before any launch: a null engine or counter buffer; a self-play engine (manual_moves = 0: there the visit counts are
+ * the training target); leaf batching (K > 1: pending descents), proven-result search (its rule 5 plays the first maximum of
+ * adjusted counts, not of N), Gumbel root search, playout cap, forced playouts and tree reuse.  An engine that is never handed
+ * to this call launches exactly what it launched before. */
+int xq_engine_settle(const xq_engine *eng, unsigned long long *dev_counters /* [n_games][2] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,10 @@ reference's.
 Opt-in as well: `record_games` (`config.record_games` for `evaluate_models`) keeps every game's moves: an
 arena game writes no samples, so its record is all that is left of it besides winner and ply count.  `play_arena` then returns
 `(results, records)`, both ordered by game; `evaluate_models` adds `game_records` (this rank's games, `slot` = the game's index).
+
+Opt-in as well: `early_stop` (`config.early_stop_decided` for `evaluate_models`) ends a search as soon as the move it will play is
+fixed: one legal move, or a leader the simulations that are left cannot catch.  Every move is the first
+maximum of the visit counts, so the games are the same games; `info["stats"]` adds `settled_moves` and `simulations_saved`.
 """
 from __future__ import annotations
 
@@ -60,7 +64,7 @@ def _evaluate_subset(eng, ev, x, idx, policy_is_probs, dense, legal, value):
 def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_simulations: int, max_game_length: int,
                c_puct: float = 1.5, device="cuda", policy_is_probs: bool = False, first_game: int = 0,
                opening_plies: int = 0, seed: int = 0, packed: Optional[bool] = None, inject=None, info: Optional[dict] = None,
-               perpetual_check: bool = False, solver: bool = False, record_games: bool = False):
+               perpetual_check: bool = False, solver: bool = False, record_games: bool = False, early_stop: bool = False):
     """eval_*: evaluators in either protocol (`evaluate_legal`, or a callable float32[n,15,10,9] -> (policy
     float32[n,8100], value float32[n])); both must use the same one.  Plays games first_game .. first_game+eval_games-1
     of the arena (the new model is red in even games) and returns the results array ordered by game (slot == game -
@@ -71,19 +75,22 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
     `perpetual_check` builds the engine with the perpetual-check rule (results then may carry reason 4); `solver` with the
     proven-result search (a move shown to lose is not played while another is not, a move shown to win is
     played at once; `info["stats"]` then carries the five solver counters); `record_games` with game records: the return value is
-    then `(results, records)`, the records (hip.GAME_RECORD_DTYPE) ordered by game like the results."""
+    then `(results, records)`, the records (hip.GAME_RECORD_DTYPE) ordered by game like the results; `early_stop` with the
+    settled-move cutoff (a search ends as soon as its first choice is fixed; the same games, and
+    `info["stats"]` then carries `settled_moves` and `simulations_saved`)."""
     cfg = engine.make_config(eval_games, eval_simulations, c_puct=c_puct, max_game_length=max_game_length,
                              random_opening_moves=0, enable_resign=False, add_noise=False, games_target=eval_games,
                              manual_moves=2)
     opts = int(opening_plies) > 0 or bool(packed) or inject is not None or info is not None
     if not opts:
-        eng = engine.SelfPlayEngine(cfg, device, perpetual_check=perpetual_check, solver=solver, record_games=record_games)
+        eng = engine.SelfPlayEngine(cfg, device, perpetual_check=perpetual_check, solver=solver, record_games=record_games,
+                                    early_stop=early_stop)
     else:
         if inject is not None:
             cfg.inject_len = int(np.asarray(inject).shape[-1])
         cfg.seed = int(seed)
         eng = engine.arena_engine(cfg, device, opening_plies, first_game, inject, perpetual_check=perpetual_check, solver=solver,
-                                  record_games=record_games)
+                                  record_games=record_games, early_stop=early_stop)
     dev = eng.device
     new_is_red = ((torch.arange(eval_games, device=dev) + first_game) % 2 == 0)
     sparse = hasattr(eval_new, "evaluate_legal") and hasattr(eval_old, "evaluate_legal") and not policy_is_probs
@@ -187,6 +194,8 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
         if st["games_finished"] >= eval_games:
             break
     _, results = eng.drain()
+    if eng.early_stop:
+        st.update(eng.early_stop_stats())
     if info is not None:
         info["openings"], info["opening_counts"] = eng.arena_openings()
         info["steps"], info["stats"], info["packed"] = n_steps, st, bool(packed)
@@ -216,7 +225,8 @@ def pair_statistics(winners) -> Dict[str, object]:
 
 def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind: str = "hip", group=None,
                     seed: Optional[int] = None, perpetual_check: Optional[bool] = None,
-                    solver: Optional[bool] = None, record_games: Optional[bool] = None) -> Dict[str, object]:
+                    solver: Optional[bool] = None, record_games: Optional[bool] = None,
+                    early_stop: Optional[bool] = None) -> Dict[str, object]:
     """Same stats dict as the reference (`new_wins, old_wins, draws, win_rate, model_updated`); reads
     `eval_games, eval_simulations, c_puct, max_game_length, eval_win_rate` from `config` (train.py:97-100).
     Under torch.distributed the games are split over the ranks and the winners all-gathered.
@@ -227,7 +237,9 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
     result then adds `perpetual_check` = True.  Off, `play_arena` is called as before.
     `solver` (None: `config.mcts_solver`, absent: off) searches with proven results; the result then adds `solver` = True.
     `record_games` (None: `config.record_games`, absent: off) adds `game_records`: the records of the games THIS rank played
-    (hip.GAME_RECORD_DTYPE, `slot` = the game's index in the arena); records are not gathered across ranks."""
+    (hip.GAME_RECORD_DTYPE, `slot` = the game's index in the arena); records are not gathered across ranks.
+    `early_stop` (None: `config.early_stop_decided`, absent: off) plays with the settled-move cutoff; the result then adds
+    `early_stop` = True.  The games and the verdict are those without it."""
     import torch.distributed as dist
     from . import distributed as xdist
     total = int(config.eval_games)
@@ -248,6 +260,10 @@ def evaluate_models(new_model, old_model, config, device="cuda", evaluator_kind:
     records = np.zeros(0, dtype=hip.GAME_RECORD_DTYPE)
     if record_games:
         rule["record_games"] = True
+    if early_stop is None:
+        early_stop = bool(getattr(config, "early_stop_decided", False))
+    if early_stop:
+        rule["early_stop"] = True
     openings = np.zeros((total, max(plies, 0)), dtype=np.int64)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import arena, engine, hip
-from .mcts import MCTS, solver_choice
+from .mcts import as_mcts, solver_choice
 from .sample_format import GAME_RECORD_DTYPE
 
 MAX_DEPTH = hip.AB_MAX_DEPTH
@@ -106,6 +106,8 @@ def play_vs_baseline(model_or_evaluator, num_games: int, depth: int, num_simulat
     a draw with reason 2; one the rules decide has reason 1, or 4 for a perpetual-check loss.
     `model_or_evaluator` may be an integer depth instead: then both sides are baseline players, that depth in the network's seat,
     and `num_simulations` is ignored.
+    It may also be an `MCTS` the caller built: the match searches with it, under its simulations and options.  One built with
+    `early_stop=True` ends a search as soon as its first choice is fixed: the same match, sooner.
     Returns `wins, losses, draws, win_rate` from the network's view, `pairs, win_rate_se, win_rate_ci95`
     (`arena.pair_statistics`), `game_records` (GAME_RECORD_DTYPE, slot = game), `baseline_nodes` (positions the baseline visited),
     `baseline_draws` (int64 [moves, 3]: game, ply and draw of every baseline move, so a move can be recomputed) and `seconds`."""
@@ -127,8 +129,9 @@ def play_vs_baseline(model_or_evaluator, num_games: int, depth: int, num_simulat
     records["winner"] = 2
     mcts = None
     if not ladder:
-        mcts = MCTS(model_or_evaluator, int(num_simulations), c_puct, device, evaluator_kind, seed=int(seed),
-                    perpetual_check=perpetual_check, solver=solver)
+        mcts = as_mcts(model_or_evaluator, int(num_simulations), c_puct, device, evaluator_kind, seed=int(seed),
+                       perpetual_check=perpetual_check, solver=solver)
+        solver = mcts.solver
     seats = (num_games + 1) // 2
     nodes = 0
     drawn = []                                             # (game, ply, draw) of every baseline move
@@ -163,8 +166,7 @@ def play_vs_baseline(model_or_evaluator, num_games: int, depth: int, num_simulat
                 if len(mine) > seats:
                     raise hip.XqError("play_vs_baseline: more searching games than seats")
                 games = [_Position(boards[g], side[g], mc[g], nocap[g], hist[g]) for g in mine]
-                mcts.search_many(games + [pad] * (seats - len(games)), temperature=1.0, add_noise=False)
-                eng = mcts._engine(seats, False)
+                eng = mcts.search_decided(games + [pad] * (seats - len(games)))
                 for slot, g in enumerate(mine):
                     r = eng.read_root(slot)
                     if len(r["actions"]) == 0:

@@ -371,8 +371,7 @@ def _searched_moves(mcts, games, width: int, solver: bool, what: str):
     for base in range(0, len(games), width):
         part = list(games[base:base + width])
         count = len(part)
-        mcts.search_many(part + [part[0]] * (width - count), temperature=1.0, add_noise=False)
-        eng = mcts._engine(width, False)
+        eng = mcts.search_decided(part + [part[0]] * (width - count))
         for slot in range(count):
             r = eng.read_root(slot)
             if len(r["actions"]) == 0:
@@ -408,11 +407,13 @@ def score(probe: Dict[str, np.ndarray], chosen) -> Dict[str, object]:
 
 
 def hold_rate(model_or_evaluator, tb: Tablebase, boards, sides, num_simulations: int, c_puct: float = 1.5, solver: bool = False,
-              perpetual_check: bool = False, seed: int = 0, chunk: int = 256, evaluator_kind: str = "hip") -> Dict[str, object]:
+              perpetual_check: bool = False, seed: int = 0, chunk: int = 256, evaluator_kind: str = "hip",
+              early_stop: bool = False) -> Dict[str, object]:
     """How many won or drawn positions of a table a search of `num_simulations` simulations holds (module docstring).  The move is
     the first maximum of the visits in move order, or `solver_choice` under `solver`; the probe's move value scores it (`score`).
     Refused: a position the table does not cover, an invalid one, a lost one.  -> positions, held, optimal, hold_rate, by_kind,
-    simulations, seconds, chosen (the action per position)."""
+    simulations, seconds, chosen (the action per position).  `early_stop` ends a search as soon as its first choice is fixed
+    (MCTS): the same moves, sooner."""
     from .mcts import MCTS
     t0 = time.time()
     if not isinstance(tb, Tablebase):
@@ -433,7 +434,7 @@ def hold_rate(model_or_evaluator, tb: Tablebase, boards, sides, num_simulations:
     if n:
         device = tb.device_table().device
         mcts = MCTS(model_or_evaluator, int(num_simulations), c_puct, device, evaluator_kind, seed=int(seed),
-                    perpetual_check=perpetual_check, solver=solver)
+                    perpetual_check=perpetual_check, solver=solver, early_stop=early_stop)
         with torch.cuda.device(device):
             chosen = _searched_moves(mcts, [_Position(b[j], s[j]) for j in range(n)], min(int(chunk), n), solver, "hold_rate")
     return {**score(probe, chosen), "simulations": int(num_simulations), "seconds": time.time() - t0, "chosen": chosen}
@@ -516,10 +517,11 @@ def play_out_with(choose, tb: Tablebase, boards, sides, max_plies: int) -> Dict[
 
 def play_out(model_or_evaluator, tb: Tablebase, boards, sides, num_simulations: int, max_plies: int = 100, c_puct: float = 1.5,
              solver: bool = False, perpetual_check: bool = False, seed: int = 0, chunk: int = 256,
-             evaluator_kind: str = "hip") -> Dict[str, object]:
+             evaluator_kind: str = "hip", early_stop: bool = False) -> Dict[str, object]:
     """`play_out_with` with one search-only `MCTS` of `num_simulations` simulations choosing the winner's moves as `hold_rate`
     chooses them (the first maximum of the visits in move order, or `solver_choice` under `solver`), except that every search
-    sees its game's move count, no-capture count and history.  -> play_out_with's result and simulations, max_plies, seconds."""
+    sees its game's move count, no-capture count and history.  -> play_out_with's result and simulations, max_plies, seconds.
+    `early_stop` as in `hold_rate`."""
     from .mcts import MCTS
     t0 = time.time()
     if not isinstance(tb, Tablebase):
@@ -538,7 +540,7 @@ def play_out(model_or_evaluator, tb: Tablebase, boards, sides, num_simulations: 
     def choose(games):
         if not mcts:            # built at the first move: a refused set of positions builds no engine
             mcts.append(MCTS(model_or_evaluator, int(num_simulations), c_puct, device, evaluator_kind, seed=int(seed),
-                             perpetual_check=perpetual_check, solver=solver))
+                             perpetual_check=perpetual_check, solver=solver, early_stop=early_stop))
         with torch.cuda.device(device):
             return _searched_moves(mcts[0], games, width, solver, "play_out")
 

@@ -121,6 +121,13 @@ The row a slot is handed is bit-identical to the one it would have computed, so 
 `eval_dedup_collisions` (two positions in one bucket: the higher slot evaluates itself) and `eval_dedup_mismatches` (must stay 0).
 Nothing is kept across steps, so a weight update needs no invalidation.  It needs the packed step (an evaluator with `live_rows`);
 not with the evaluation cache, leaves_per_step > 1, eval_mirror or arena games; every other option.
+
+With `early_stop=True` (opt-in; xq_engine_settle) `select()` first ends every search whose first choice is
+fixed: one root child (a forced move), or a leader whose lead over the runner-up is larger than the simulations that are left.  An
+arena engine then plays that move at once, a search-only engine holds the search with its true `sims_done`; the move is the one the
+full search plays, always.  `early_stop_stats()` reads `settled_moves` and `simulations_saved`.  One more kernel per step, eager and
+recorded.  Arena (manual_moves = 2) and search-only (1) engines; not with leaves_per_step > 1, solver, gumbel, playout_cap,
+forced_playouts or tree_reuse.  A caller that reads a search-only engine's visit counts as a distribution wants the full search.
 """
 from __future__ import annotations
 
@@ -216,6 +223,33 @@ def parse_start_pool(cfg: hip.EngineConfig, start_pool, record_games: bool = Fal
         raise hip.XqError("start_pool cannot be combined with record_games: a record has no room for a start position and its "
                           "replay starts from the initial one")
     return boards.reshape(n, 90), sides, prob
+
+
+def parse_early_stop(cfg: hip.EngineConfig, early_stop, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
+                     forced_playouts=None, gumbel=None, solver: bool = False) -> bool:
+    """The `early_stop=` argument checked, without a GPU -> bool.  Every rule of xq_engine_settle's refusal list
+    (include/xq_hip.h), each with a message that names the option."""
+    if early_stop not in (False, True, 0, 1):
+        raise hip.XqError(f"early_stop must be a bool, got {early_stop!r}")
+    if not early_stop:
+        return False
+    if int(cfg.manual_moves) == 0:
+        raise hip.XqError("early_stop is an option of decided moves (arena games, manual_moves = 2, and searches read at "
+                          "temperature 0, manual_moves = 1): in self-play the visit counts are the training target")
+    if int(leaves_per_step) > 1:
+        raise hip.XqError("early_stop cannot be combined with leaves_per_step > 1: pending descents are not in the visit counts yet")
+    if solver:
+        raise hip.XqError("early_stop cannot be combined with solver: its move is the first maximum of adjusted counts, not of "
+                          "the visit counts")
+    if gumbel is not None:
+        raise hip.XqError("early_stop cannot be combined with gumbel: a Gumbel root does not play the first maximum of its visits")
+    if playout_cap is not None:
+        raise hip.XqError("early_stop cannot be combined with playout_cap: a fast move has another budget")
+    if forced_playouts is not None:
+        raise hip.XqError("early_stop cannot be combined with forced_playouts: its move is chosen from pruned counts")
+    if tree_reuse:
+        raise hip.XqError("early_stop cannot be combined with tree_reuse: a reused root starts with visits that are not this search's")
+    return True
 
 
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
@@ -382,7 +416,8 @@ class SelfPlayEngine:
                  inject: Optional[np.ndarray] = None, eval_cache_entries: int = 0, leaves_per_step: int = 1,
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
                  perpetual_check: bool = False, solver: bool = False, root_stats: bool = False, eval_mirror: bool = False,
-                 record_games: bool = False, max_out_games=None, start_pool=None, eval_dedup: bool = False):
+                 record_games: bool = False, max_out_games=None, start_pool=None, eval_dedup: bool = False,
+                 early_stop: bool = False):
         opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
             gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check,
@@ -395,6 +430,8 @@ class SelfPlayEngine:
         if opts.eval_dedup and not getattr(evaluator, "live_rows", False):
             raise hip.XqError("eval_dedup acts in the packed step only: it needs an evaluator with live_rows (the HIP evaluators)")
         pool = parse_start_pool(cfg, start_pool, record_games=gr is not None)
+        self.early_stop = parse_early_stop(cfg, early_stop, leaves_per_step=K, tree_reuse=tree_reuse, playout_cap=cap,
+                                           forced_playouts=forced, gumbel=gz, solver=sv is not None)
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
@@ -499,6 +536,8 @@ class SelfPlayEngine:
             self._init_cache(int(eval_cache_entries))
         self.eval_dedup = bool(opts.eval_dedup)
         self.dedup = hip.DedupTable(self.G, self.device) if self.eval_dedup else None
+        # settled-move cutoff: xq_engine_settle's counters, one row per slot (searches settled, simulations not run)
+        self._settle_counters = torch.zeros((self.G, 2), dtype=torch.int64, device=self.device) if self.early_stop else None
         self._reuse_seen = (self.evaluator, getattr(self.evaluator, "weights_version", 0))
         self.steps = 0
         self._graph = None
@@ -548,6 +587,9 @@ class SelfPlayEngine:
 
     # ---- the three stages of a step --------------------------------------------------------------------
     def select(self):
+        if self.early_stop:                            # ahead of the select kernel, which ends the settled arena searches
+            hip.check(self.lib.xq_engine_settle(C.byref(self.h), self._settle_counters.data_ptr(), hip.stream_ptr(self.device)),
+                      "xq_engine_settle")
         hip.check(self.lib.xq_engine_select(C.byref(self.h), self.nn_input.data_ptr(), hip.stream_ptr(self.device)),
                   "xq_engine_select")
         return self.nn_input
@@ -780,6 +822,14 @@ class SelfPlayEngine:
             out.update({"eval_dedup_" + k: v for k, v in self.dedup.stats().items()})
         return out
 
+    def early_stop_stats(self) -> dict:
+        """The settled-move cutoff's counters: settled_moves (searches ended before their budget) and simulations_saved (the
+        simulations they did not run).  Synchronises."""
+        if not self.early_stop:
+            raise hip.XqError("early_stop_stats needs an engine with early_stop=True")
+        s = self._settle_counters.sum(dim=0).cpu()
+        return dict(settled_moves=int(s[0]), simulations_saved=int(s[1]))
+
     def solver_stats(self) -> dict:
         """The proven-result search's counters (xq_engine_solver_stats_read): proven_nodes, proven_stops, proven_moves,
         unspent_sims, removed_visits.  Synchronises."""
@@ -972,10 +1022,11 @@ class SelfPlayEngine:
 
 
 def arena_engine(cfg: hip.EngineConfig, device, opening_plies: int, first_game: int, inject=None,
-                 perpetual_check: bool = False, solver: bool = False, record_games: bool = False) -> SelfPlayEngine:
+                 perpetual_check: bool = False, solver: bool = False, record_games: bool = False,
+                 early_stop: bool = False) -> SelfPlayEngine:
     """The arena's engine with arena options (paired openings from game index `first_game`, the per-model packed step)."""
     return SelfPlayEngine(cfg, device, inject=inject, arena_opts=(int(opening_plies), int(first_game)),
-                          perpetual_check=perpetual_check, solver=solver, record_games=record_games)
+                          perpetual_check=perpetual_check, solver=solver, record_games=record_games, early_stop=early_stop)
 
 
 def replay_games(records, stop_ply=None, perpetual_check: bool = False, device="cuda") -> dict:

@@ -362,6 +362,7 @@ def lib():
     L.xq_start_pool_draw_host.argtypes = [C.c_uint64, i32, i32, C.c_uint32, i32, C.c_double]
     L.xq_engine_start_indices.argtypes = [C.POINTER(Engine), C.POINTER(vp)]
     L.xq_engine_start_pool_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(StartPoolStats), vp]
+    L.xq_engine_settle.argtypes = [C.POINTER(Engine), vp, vp]
     L.xq_engine_drain_games.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
     L.xq_engine_drain_games_device.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
     L.xq_engine_game_records_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(GameRecordsStats), vp]
@@ -495,7 +496,7 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_positions_check_batch", "xq_engine_workspace_bytes_sp", "xq_engine_init_sp", "xq_start_pool_draw_host",
            "xq_engine_start_indices", "xq_engine_start_pool_stats_read", "xq_evdedup_bytes", "xq_evdedup_init",
            "xq_engine_compact_unique", "xq_engine_expand_dedup", "xq_evdedup_stats_read", "xq_evdedup_bucket_host",
-           "xq_dedup_rows_batch"]
+           "xq_dedup_rows_batch", "xq_engine_settle"]
 
 
 def check(rc: int, what: str):

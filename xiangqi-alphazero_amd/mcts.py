@@ -32,6 +32,11 @@ search's.
 `eval_dedup=True` (opt-in) evaluates every distinct position of a `search_many` step once (engine.SelfPlayEngine, DESIGN.md
 section 4.24): equal positions among the `n_parallel`, and searches that walk into the same position in the same step, share one
 row of the network's batch.  The visit counts are those of the search without it.
+
+`early_stop=True` (opt-in) lets `get_action(temperature=0)` end its search as soon as the first choice is fixed
+(engine.SelfPlayEngine): a forced move, or a leader the simulations that are left cannot catch.  The action
+is the full search's, always.  `search` / `search_many`, at any temperature, keep the full search: their pi and `root_value` are
+functions of all S simulations.  Not with leaves_per_step > 1 or solver.
 """
 from __future__ import annotations
 
@@ -67,10 +72,18 @@ def root_value(visits, total_value) -> np.float32:
     return np.float32(sum_w / float(sum_n)) if sum_n > 0 else np.float32(0.0)
 
 
+def as_mcts(model_or_evaluator, num_simulations: int, c_puct: float, device, evaluator_kind: str, **options) -> "MCTS":
+    """What a yardstick searches with: `model_or_evaluator` itself when the caller built the `MCTS` (its simulations and options
+    hold, `early_stop` for one), else a new `MCTS` of the model or evaluator with `options`."""
+    if isinstance(model_or_evaluator, MCTS):
+        return model_or_evaluator
+    return MCTS(model_or_evaluator, num_simulations, c_puct, device, evaluator_kind, **options)
+
+
 class MCTS:
     def __init__(self, model, num_simulations: int = 200, c_puct: float = 1.5, device: str = "cuda",
                  evaluator_kind: str = "auto", seed: int = 0, leaves_per_step: int = 1, perpetual_check: bool = False,
-                 solver: bool = False, eval_mirror: bool = False, eval_dedup: bool = False):
+                 solver: bool = False, eval_mirror: bool = False, eval_dedup: bool = False, early_stop: bool = False):
         if not 1 <= int(leaves_per_step) <= 64:
             from .hip import XqError
             raise XqError(f"leaves_per_step must be in [1, 64], got {leaves_per_step}")
@@ -79,6 +92,9 @@ class MCTS:
         self.solver = bool(solver)
         self.eval_mirror = bool(eval_mirror)
         self.eval_dedup = bool(eval_dedup)
+        # checked here, without a GPU: the engines are made at the first search
+        self.early_stop = engine.parse_early_stop(engine.make_config(1, int(num_simulations), manual_moves=1), early_stop,
+                                                  leaves_per_step=self.leaves_per_step, solver=self.solver)
         self.model = model
         self.num_simulations = num_simulations
         self.c_puct = c_puct
@@ -98,21 +114,28 @@ class MCTS:
         if hasattr(self.evaluator, "update") and hasattr(self.model, "state_dict"):
             self.evaluator.update(self.model)
 
-    def _engine(self, n: int, add_noise: bool):
-        key = (n, add_noise)
+    def _engine(self, n: int, add_noise: bool, early_stop: bool = False):
+        key = (n, add_noise, True) if early_stop else (n, add_noise)      # the full searches' engines keep their two-part key
         if key not in self._engines:
             cfg = engine.make_config(n, self.num_simulations, c_puct=self.c_puct, add_noise=add_noise, manual_moves=1,
                                      seed=self.seed)
             self._engines[key] = engine.SelfPlayEngine(cfg, self.device, evaluator=self.evaluator,
                                                        leaves_per_step=self.leaves_per_step,
                                                        perpetual_check=self.perpetual_check, solver=self.solver,
-                                                       eval_mirror=self.eval_mirror, eval_dedup=self.eval_dedup)
+                                                       eval_mirror=self.eval_mirror, eval_dedup=self.eval_dedup,
+                                                       early_stop=early_stop)
         return self._engines[key]
 
     def search_many(self, games: Sequence, temperature: float = 1.0, add_noise: bool = True, return_values: bool = False):
         """pi float64[8100] per position; with `return_values` (pis, float32[len(games)]): the search's value of every position
         as well (`root_value`), which `root_values` holds after any search."""
-        eng = self._engine(len(games), add_noise)
+        out, values = self._search(games, temperature, add_noise, False)
+        return (out, values) if return_values else out
+
+    def _search(self, games: Sequence, temperature: float, add_noise: bool, early_stop: bool):
+        """`search_many` on the engine keyed by `early_stop` -> (pis, values).  With it a search may hold before S simulations,
+        so the engine is stepped in chunks of 8 with a test after each from the start."""
+        eng = self._engine(len(games), add_noise, early_stop)
         for slot, g in enumerate(games):
             hist = [np.frombuffer(h, dtype=np.int8) for h in list(g.history)[-12:]]
             eng.set_position(slot, np.asarray(g.board, dtype=np.int8), int(g.current_player), int(g.move_count),
@@ -120,14 +143,15 @@ class MCTS:
         # the root, then S simulations in at least ceil(S / K) steps; collisions (K > 1) and long runs of terminal leaves
         # can add steps, so the engine is stepped on in small chunks until every slot holds its finished search
         K = self.leaves_per_step
-        for _ in range(-(-self.num_simulations // K) + 1):
+        blind = 0 if early_stop else -(-self.num_simulations // K) + 1      # a search that may settle is tested from the start
+        for _ in range(blind):
             eng.step()
-        extra = 0
+        extra, limit = 0, 4 * self.num_simulations + 64 + (self.num_simulations + 8 if early_stop else 0)
         while not eng.held():
             for _ in range(8):
                 eng.step()
             extra += 8
-            if extra > 4 * self.num_simulations + 64:
+            if extra > limit:
                 raise RuntimeError("search did not finish")
         out = []
         values = np.zeros(len(games), dtype=np.float32)
@@ -139,14 +163,22 @@ class MCTS:
             else:
                 out.append(dense_pi(r["actions"], r["visits"].astype(np.float64), temperature))
         self.root_values = values
-        return (out, values) if return_values else out
+        return out, values
+
+    def search_decided(self, games: Sequence, add_noise: bool = False):
+        """The searches behind the temperature-0 moves of many positions -> the engine whose slot i holds the search of games[i]
+        (`read_root`; the move is the first maximum of its visits in move order).  With `early_stop` a search may have ended
+        before S simulations: its first maximum is the full search's, its other counts are not.  What `get_action(temperature=0)`
+        runs for one position, and what the yardsticks (baseline, tactics, endgame) run for many."""
+        self._search(games, 0.0, add_noise, self.early_stop)
+        return self._engine(len(games), add_noise, self.early_stop)
 
     def search(self, game, temperature: float = 1.0, add_noise: bool = True) -> np.ndarray:
         return self.search_many([game], temperature, add_noise)[0]
 
     def get_action(self, game, temperature: float = 0.0, add_noise: bool = False) -> int:
         """mcts.py:166-174"""
-        probs = self.search(game, temperature, add_noise)
+        probs = self._search([game], temperature, add_noise, self.early_stop and temperature == 0)[0][0]
         if temperature == 0 and self.solver:
             eng = self._engine(1, add_noise)           # the engine `search` just used: slot 0 holds the finished search
             r = eng.read_root(0)

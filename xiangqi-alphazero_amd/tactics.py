@@ -128,8 +128,10 @@ def solve_rate(model_or_evaluator, puzzles, num_simulations: int, c_puct: float 
     """How many labelled puzzles a search of `num_simulations` simulations solves (module docstring).  The move is the first
     maximum of the visits in move order, or `solver_choice` under `solver`.  Solved: the chosen move's label is a mate-in (1..N
     of the labelling; 0 and UNKNOWN are not); optimal: it equals the puzzle's best.  -> puzzles, solved, optimal, solve_rate,
-    by_mate_in {m: [count, solved]}, simulations, seconds, chosen (the action per puzzle)."""
-    from .mcts import MCTS, solver_choice
+    by_mate_in {m: [count, solved]}, simulations, seconds, chosen (the action per puzzle).  `model_or_evaluator` may be an `MCTS`
+    the caller built: the pass searches with it, under its simulations and options; one built with `early_stop=True` ends a search
+    as soon as its first choice is fixed: the same moves, sooner."""
+    from .mcts import as_mcts, solver_choice
     t0 = time.time()
     puzzles = np.asarray(puzzles).reshape(-1)
     if puzzles.dtype != PUZZLE_DTYPE:
@@ -143,15 +145,15 @@ def solve_rate(model_or_evaluator, puzzles, num_simulations: int, c_puct: float 
         raise hip.XqError("solve_rate: every puzzle needs a best mate-in in 1..%d (label the positions first)" % MAX_MOVES)
     chosen = np.zeros(n, dtype=np.int64)
     if n:
-        mcts = MCTS(model_or_evaluator, int(num_simulations), c_puct, device, evaluator_kind, seed=int(seed),
-                    perpetual_check=perpetual_check, solver=solver)
+        mcts = as_mcts(model_or_evaluator, int(num_simulations), c_puct, device, evaluator_kind, seed=int(seed),
+                       perpetual_check=perpetual_check, solver=solver)
+        solver = mcts.solver
         width = min(int(chunk), n)
         with torch.cuda.device(torch.device(device)):
             for base in range(0, n, width):
                 part = puzzles[base:base + width]
                 games = [_Position(p["board"], p["side"]) for p in part]
-                mcts.search_many(games + [games[0]] * (width - len(games)), temperature=1.0, add_noise=False)
-                eng = mcts._engine(width, False)
+                eng = mcts.search_decided(games + [games[0]] * (width - len(games)))
                 for slot in range(len(part)):
                     r = eng.read_root(slot)
                     if len(r["actions"]) == 0:

@@ -284,6 +284,13 @@ class AlphaZeroLoop:
         self.perpetual_check = bool(getattr(config, "perpetual_check_loses", False))
         # the proven-result search (config.mcts_solver; absent: off), read once as well, for self-play and the gate alike
         self.solver = bool(getattr(config, "mcts_solver", False))
+        # the settled-move cutoff (config.early_stop_decided; absent: off), read once and checked here, for the searches whose move
+        # is played at temperature 0: the arena gate and the baseline, tactics and endgame yardsticks.  Never self-play
+        self.early_stop = bool(getattr(config, "early_stop_decided", False))
+        if self.early_stop and self.solver:
+            raise hip.XqError("config.early_stop_decided and config.mcts_solver cannot be combined: the solver's move is the first "
+                              "maximum of adjusted counts, not of the visit counts")
+        self._decided = {"early_stop": True} if self.early_stop else {}     # off: every call is the call without the key
         # the q-mixed value target (config.value_target_q_mix = lambda, absent: 0; config.record_root_stats): checked here, so a
         # lambda outside [0, 1] or one with Gumbel root search fails at construction; lambda > 0 turns the recording on.  Read
         # once: self-play and the train step below are handed these two values and do not read the keys again
@@ -505,9 +512,10 @@ class AlphaZeroLoop:
             seed = int(getattr(self.config, "arena_seed", 0) or 0) + self.iteration
             return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind,
                                          seed=seed, perpetual_check=self.perpetual_check, solver=self.solver,
-                                         record_games=self.record_games)
+                                         record_games=self.record_games, **self._decided)
         return arena.evaluate_models(self.current_model, self.best_model, self.config, self.device, self.evaluator_kind,
-                                     perpetual_check=self.perpetual_check, solver=self.solver, record_games=self.record_games)
+                                     perpetual_check=self.perpetual_check, solver=self.solver, record_games=self.record_games,
+                                     **self._decided)
 
     def evaluate(self) -> dict:
         stats = self._arena()
@@ -526,13 +534,23 @@ class AlphaZeroLoop:
             self.current_model.load_state_dict(self.best_model.state_dict())
         return stats
 
+    def _decided_search(self, simulations: int):
+        """What the baseline match and the tactics pass search with: best_model, or under config.early_stop_decided an `MCTS` of
+        it with early_stop=True and the options those calls would have given it (their signatures are closed; the endgame calls
+        take the keyword)."""
+        if not self.early_stop:
+            return self.best_model
+        from . import mcts
+        return mcts.MCTS(self.best_model, int(simulations), float(self.config.c_puct), self.device, self.evaluator_kind,
+                         seed=self.seed + self.iteration, perpetual_check=self.perpetual_check, solver=self.solver, early_stop=True)
+
     def play_baseline(self) -> dict:
         """best_model against the fixed alpha-beta opponent (baseline.play_vs_baseline), seed + iteration as the match's seed.
         The records go to config.game_records_dir, when set, like the other stages'; the rest is this iteration's "baseline"
         entry."""
         from . import baseline
         b = self.baseline
-        out = baseline.play_vs_baseline(self.best_model, b["games"], b["depth"], b["simulations"], opening_plies=b["opening_plies"],
+        out = baseline.play_vs_baseline(self._decided_search(b["simulations"]), b["games"], b["depth"], b["simulations"], opening_plies=b["opening_plies"],
                                         seed=self.seed + self.iteration, max_game_length=int(self.config.max_game_length),
                                         c_puct=float(self.config.c_puct), perpetual_check=self.perpetual_check, solver=self.solver,
                                         device=self.device, evaluator_kind=self.evaluator_kind)
@@ -551,7 +569,7 @@ class AlphaZeroLoop:
                                      device=self.device)
             self._tactics_puzzles = tactics.select(labelled, t["max_moves"], 1, unique=False)
             t["dropped"] = len(labelled) - len(self._tactics_puzzles)
-        out = tactics.solve_rate(self.best_model, self._tactics_puzzles, t["simulations"], c_puct=float(self.config.c_puct),
+        out = tactics.solve_rate(self._decided_search(t["simulations"]), self._tactics_puzzles, t["simulations"], c_puct=float(self.config.c_puct),
                                  solver=self.solver, perpetual_check=self.perpetual_check, seed=self.seed + self.iteration,
                                  device=self.device, evaluator_kind=self.evaluator_kind)
         # by_mate_in keyed by text, as the JSON file holds it: the entry in memory equals the entry on disk
@@ -581,7 +599,7 @@ class AlphaZeroLoop:
             self._endgame_positions = (boards, sides)
         out = endgame.hold_rate(self.best_model, tb, *self._endgame_positions, e["simulations"], c_puct=float(self.config.c_puct),
                                 solver=self.solver, perpetual_check=self.perpetual_check, seed=self.seed + self.iteration,
-                                evaluator_kind=self.evaluator_kind)
+                                evaluator_kind=self.evaluator_kind, **self._decided)
         return {"signature": e["signature"], "kind": e["kind"], **{k: v for k, v in out.items() if k != "chosen"}}
 
     def play_out_endgame(self) -> dict:
@@ -597,7 +615,7 @@ class AlphaZeroLoop:
             self._endgame_playout_positions = (boards, sides)
         out = endgame.play_out(self.best_model, tb, *self._endgame_playout_positions, e["simulations"], max_plies=p["max_plies"],
                                c_puct=float(self.config.c_puct), solver=self.solver, perpetual_check=self.perpetual_check,
-                               seed=self.seed + self.iteration, evaluator_kind=self.evaluator_kind)
+                               seed=self.seed + self.iteration, evaluator_kind=self.evaluator_kind, **self._decided)
         return {"signature": e["signature"], **{k: v for k, v in out.items() if k != "games"}}
 
     def pretrain_from_records(self) -> dict:
