@@ -1046,7 +1046,7 @@ typedef struct xq_game_result {
     uint32_t slot, game_seq;
     int8_t winner;      /* +1 / -1 / 0 */
     uint8_t reason;     /* 1 rules (is_game_over), 2 max_game_length adjudication, 3 resign, 4 rules: repetition, perpetual check
-                         * (xq_engine_init_ru only) */
+                         * (xq_engine_init_ru only), 5 an endgame table (xq_engine_adjudicate only) */
     uint16_t steps;     /* game.move_count */
     uint16_t n_samples;
     uint16_t reserved;
@@ -1591,6 +1591,46 @@ int xq_engine_start_pool_stats_read(const xq_engine *eng, xq_start_pool_stats *h
  * adjusted counts, not of N), Gumbel root search, playout cap, forced playouts and tree reuse.  An engine that is never handed
  * to this call launches exactly what it launched before. */
 int xq_engine_settle(const xq_engine *eng, unsigned long long *dev_counters /* [n_games][2] */, void *stream);
+
+/* Table adjudication (opt-in): a game whose real position an endgame table decides ends there, with the exact result.
+ * THE RULE (one device function for both calls).  The board is matched against the signature as xq_tb_probe_batch matches it.
+ * Where that says "not in this table" and opts->both_colours is 1, the colour-swapped image -- board'[i] = -board[89 - i], the
+ * other side to move -- is matched as well: the table of "Ra" also serves K+A against K+R.  A value is from the view of the side
+ * to move, so the swap does not change it.  With a match the entry is read: XQ_TB_INVALID is "not covered"; 0 is a draw,
+ * adjudicated only when opts->draws is 1; otherwise the winner is the side to move for v > 0 and the other side for v < 0.
+ *   status   0 decided; +1 not in the table under either colouring; +2 a king is missing; +4 the entry is XQ_TB_INVALID; +8 a
+ *            drawn entry with draws = 0; +16 matched through the swapped image (informational: beside 0 or 8 only).
+ *   winner   +1 / -1 / 0 with status 0 or 16, else 0.     value   the entry's word with status 0, 8, 16 or 24, else 0.
+ * xq_tb_adjudicate_batch: stateless, one wavefront per position; boards int8[n][90], side int8[n] (1 red, anything else black);
+ * every output word is written.  n = 0 is a no-op.
+ * xq_engine_adjudicate: the engine stage, called after xq_engine_select and ahead of the expand call of the same step, on the
+ * same stream, once per table.  One wavefront per slot, no scratch, no atomics.  A slot is looked at when it waits for its root's
+ * evaluation, its root status word is 0 (the rules' own verdicts -- game over, max_game_length -- and an earlier table's come
+ * first) and its game has at least opts->min_ply plies.  A decided slot gets root status XQ_REASON_TABLE and the winner, the two
+ * words the root request itself writes; nothing else of the engine's state is written.  The expand call that follows ends the game:
+ * its samples carry the exact z and its xq_game_result reason XQ_REASON_TABLE.  The slot's root row is still evaluated once: the
+ * resign rule reads its value before the status.  With enable_resign a resignation at that very position takes precedence, as it
+ * does over a position the rules end.
+ * dev_counters: caller-owned, zeroed by the caller, uint64[n_games][4]; row s is written by slot s's wavefront only -- [0] games
+ * ended decisive, [1] games ended drawn, [2] covered but left alone (a drawn entry with draws = 0), [3] matched through the
+ * swapped colours.  The caller sums the columns.
+ * XQ_ERR_ARG before any launch (no GPU needed): a null engine, table, opts or counter pointer (the batch call: with n > 0 a null
+ * pointer, and n < 0); a bad signature, or entries != xq_tb_entries(pieces, n_pieces); reserved != 0; min_ply < 0; draws or
+ * both_colours outside {0, 1}; manual_moves = 1 (a search-only engine's caller asked for a search) or outside 0..2.  Self-play
+ * (0) and arena (2) engines are accepted.  An engine that is never handed to this call launches exactly what it launched before. */
+#define XQ_REASON_TABLE 5      /* xq_game_result.reason of a game a table adjudicated */
+typedef struct xq_adjudicate_opts {
+    int32_t draws;          /* 1: a drawn entry ends the game as a draw */
+    int32_t both_colours;   /* 1: the colour-swapped image is matched as well */
+    int32_t min_ply;        /* games shorter than this are left alone */
+    int32_t reserved;       /* 0 */
+} xq_adjudicate_opts;
+int xq_tb_adjudicate_batch(const int8_t *pieces, int n_pieces, const int16_t *dev_table, int64_t entries,
+                           const int8_t *dev_boards /* [n][90] */, const int8_t *dev_side /* [n] */, int n,
+                           const xq_adjudicate_opts *opts, uint8_t *dev_status, int8_t *dev_winner, int16_t *dev_value,
+                           void *stream);
+int xq_engine_adjudicate(const xq_engine *eng, const int8_t *pieces, int n_pieces, const int16_t *dev_table, int64_t entries,
+                         const xq_adjudicate_opts *opts, unsigned long long *dev_counters /* [n_games][4] */, void *stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,9 @@ arena game writes no samples, so its record is all that is left of it besides wi
 Opt-in as well: `early_stop` (`config.early_stop_decided` for `evaluate_models`) ends a search as soon as the move it will play is
 fixed: one legal move, or a leader the simulations that are left cannot catch.  Every move is the first
 maximum of the visit counts, so the games are the same games; `info["stats"]` adds `settled_moves` and `simulations_saved`.
+
+Opt-in as well: `play_arena(adjudicate=(tables, options))` ends a game as soon as an endgame table decides its position (DESIGN.md
+section 4.26); the result then carries reason 5.  `evaluate_models` and the loop's gate do not use it.
 """
 from __future__ import annotations
 
@@ -64,7 +67,8 @@ def _evaluate_subset(eng, ev, x, idx, policy_is_probs, dense, legal, value):
 def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_simulations: int, max_game_length: int,
                c_puct: float = 1.5, device="cuda", policy_is_probs: bool = False, first_game: int = 0,
                opening_plies: int = 0, seed: int = 0, packed: Optional[bool] = None, inject=None, info: Optional[dict] = None,
-               perpetual_check: bool = False, solver: bool = False, record_games: bool = False, early_stop: bool = False):
+               perpetual_check: bool = False, solver: bool = False, record_games: bool = False, early_stop: bool = False,
+               adjudicate=None):
     """eval_*: evaluators in either protocol (`evaluate_legal`, or a callable float32[n,15,10,9] -> (policy
     float32[n,8100], value float32[n])); both must use the same one.  Plays games first_game .. first_game+eval_games-1
     of the arena (the new model is red in even games) and returns the results array ordered by game (slot == game -
@@ -77,20 +81,23 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
     played at once; `info["stats"]` then carries the five solver counters); `record_games` with game records: the return value is
     then `(results, records)`, the records (hip.GAME_RECORD_DTYPE) ordered by game like the results; `early_stop` with the
     settled-move cutoff (a search ends as soon as its first choice is fixed; the same games, and
-    `info["stats"]` then carries `settled_moves` and `simulations_saved`)."""
+    `info["stats"]` then carries `settled_moves` and `simulations_saved`); `adjudicate` = (tables, options) with table adjudication
+    (engine.SelfPlayEngine, DESIGN.md section 4.26: a game ends, with reason 5, as soon as an endgame table decides its position;
+    `info["stats"]` then carries the `adjudicated_*` counters)."""
     cfg = engine.make_config(eval_games, eval_simulations, c_puct=c_puct, max_game_length=max_game_length,
                              random_opening_moves=0, enable_resign=False, add_noise=False, games_target=eval_games,
                              manual_moves=2)
     opts = int(opening_plies) > 0 or bool(packed) or inject is not None or info is not None
+    adj = {} if adjudicate is None else {"adjudicate": adjudicate}      # off: the engine is built by the call without the key
     if not opts:
         eng = engine.SelfPlayEngine(cfg, device, perpetual_check=perpetual_check, solver=solver, record_games=record_games,
-                                    early_stop=early_stop)
+                                    early_stop=early_stop, **adj)
     else:
         if inject is not None:
             cfg.inject_len = int(np.asarray(inject).shape[-1])
         cfg.seed = int(seed)
         eng = engine.arena_engine(cfg, device, opening_plies, first_game, inject, perpetual_check=perpetual_check, solver=solver,
-                                  record_games=record_games, early_stop=early_stop)
+                                  record_games=record_games, early_stop=early_stop, **adj)
     dev = eng.device
     new_is_red = ((torch.arange(eval_games, device=dev) + first_game) % 2 == 0)
     sparse = hasattr(eval_new, "evaluate_legal") and hasattr(eval_old, "evaluate_legal") and not policy_is_probs
@@ -196,6 +203,8 @@ def play_arena(eval_new: Callable, eval_old: Callable, eval_games: int, eval_sim
     _, results = eng.drain()
     if eng.early_stop:
         st.update(eng.early_stop_stats())
+    if adjudicate is not None:
+        st.update(eng.adjudication_stats())
     if info is not None:
         info["openings"], info["opening_counts"] = eng.arena_openings()
         info["steps"], info["stats"], info["packed"] = n_steps, st, bool(packed)

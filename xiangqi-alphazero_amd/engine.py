@@ -71,7 +71,7 @@ With `perpetual_check=True` (opt-in; xq_engine_init_ru) 
 where the reference calls three repetitions in the 12-board window a draw, the side whose every move of the repetition span gave
 check loses when the other side's did not.  The verdict holds at the root, in the real game and at the leaves of the search; a
 game it decides has `reason` 4 in its result (1 rules, 2 max_game_length adjudication, 3 resign, 4 rules: repetition, perpetual
-check).  Every mode, every other option.
+check, 5 an endgame table: `adjudicate` below).  Every mode, every other option.
 
 With `solver=True` (opt-in; xq_engine_init_sv) the search keeps exact results (MCTS-solver): a terminal leaf
 sets its node's proven state and backs up the true +1 / 0 / -1, states propagate up the path, a descent stops at a decided node, a
@@ -128,6 +128,16 @@ arena engine then plays that move at once, a search-only engine holds the search
 full search plays, always.  `early_stop_stats()` reads `settled_moves` and `simulations_saved`.  One more kernel per step, eager and
 recorded.  Arena (manual_moves = 2) and search-only (1) engines; not with leaves_per_step > 1, solver, gumbel, playout_cap,
 forced_playouts or tree_reuse.  A caller that reads a search-only engine's visit counts as a distribution wants the full search.
+
+With `adjudicate=(tables, dict(draws=..., both_colours=..., min_ply=...))` (opt-in; xq_engine_adjudicate)
+a game stops as soon as its real position is in one of the `tables` (one to four `endgame.Tablebase` objects on the engine's
+device): `select()` then runs the public stage `adjudicate()` behind the select kernel, once per table in order, and the expand
+kernels end every game it decided with `reason` 5 and the table's winner, so every sample of the game carries the exact z.
+`both_colours` (default on) also matches the colour-swapped image, so the table of "Ra" serves K+A against K+R; `draws` (default
+on) ends drawn entries as draws; `min_ply` (default 1) leaves shorter games alone, so a start-pool game that begins inside a table
+still yields the one move that leads to its first adjudicated root (0: it ends at ply 0 with no sample).  The rules' own verdicts
+and, with enable_resign, a resignation at that position come first.  `adjudication_stats()` sums the counters.  One more kernel
+per table per step, in all four step paths, eager and recorded.  Self-play and arena engines, every other option.
 """
 from __future__ import annotations
 
@@ -250,6 +260,46 @@ def parse_early_stop(cfg: hip.EngineConfig, early_stop, *, leaves_per_step: int 
     if tree_reuse:
         raise hip.XqError("early_stop cannot be combined with tree_reuse: a reused root starts with visits that are not this search's")
     return True
+
+
+ADJUDICATE_MAX_TABLES = 4
+ADJUDICATE_DEFAULTS = dict(draws=True, both_colours=True, min_ply=1)
+
+
+def parse_adjudicate(cfg: hip.EngineConfig, adjudicate):
+    """The `adjudicate=(tables, options)` argument checked, without a GPU -> (tuple of endgame.Tablebase, hip.AdjudicateOpts), or
+    None.  `tables`: one `endgame.Tablebase` or a sequence of 1 to 4; `options`: a dict (or None) with draws, both_colours (bools,
+    default True) and min_ply (an integer >= 0, default 1).  Every rule of xq_engine_adjudicate's refusal list (include/xq_hip.h),
+    each with a message that names the option."""
+    if adjudicate is None:
+        return None
+    from .endgame import Tablebase
+    try:
+        tables, options = adjudicate
+    except (TypeError, ValueError):
+        raise hip.XqError("adjudicate must be (tables, options): endgame.Tablebase objects and a dict of draws, both_colours, min_ply")
+    if isinstance(tables, Tablebase):
+        tables = (tables,)
+    try:
+        tables = tuple(tables)
+    except TypeError:
+        raise hip.XqError(f"adjudicate: tables must be endgame.Tablebase objects, got {type(tables).__name__}")
+    if not 1 <= len(tables) <= ADJUDICATE_MAX_TABLES:
+        raise hip.XqError(f"adjudicate: 1 to {ADJUDICATE_MAX_TABLES} tables, got {len(tables)}")
+    for tb in tables:
+        if not isinstance(tb, Tablebase):
+            raise hip.XqError(f"adjudicate: tables must be endgame.Tablebase objects, got {type(tb).__name__}")
+    if options is None:
+        options = {}
+    if not isinstance(options, dict) or any(k not in ADJUDICATE_DEFAULTS for k in options):
+        raise hip.XqError(f"adjudicate: options must be a dict with keys from {sorted(ADJUDICATE_DEFAULTS)}, got {options!r}")
+    opts = hip.adjudicate_opts(**{**ADJUDICATE_DEFAULTS, **options}, what="adjudicate")
+    if int(cfg.manual_moves) == 1:
+        raise hip.XqError("adjudicate is an option of engines that play games (self-play, manual_moves = 0, and arena, 2): the "
+                          "caller of a search-only engine (manual_moves = 1) asked for a search")
+    if int(cfg.manual_moves) not in (0, 2):
+        raise hip.XqError(f"adjudicate: manual_moves must be 0 or 2, got {cfg.manual_moves}")
+    return tables, opts
 
 
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
@@ -417,7 +467,7 @@ class SelfPlayEngine:
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
                  perpetual_check: bool = False, solver: bool = False, root_stats: bool = False, eval_mirror: bool = False,
                  record_games: bool = False, max_out_games=None, start_pool=None, eval_dedup: bool = False,
-                 early_stop: bool = False):
+                 early_stop: bool = False, adjudicate=None):
         opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
             gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check,
@@ -432,6 +482,7 @@ class SelfPlayEngine:
         pool = parse_start_pool(cfg, start_pool, record_games=gr is not None)
         self.early_stop = parse_early_stop(cfg, early_stop, leaves_per_step=K, tree_reuse=tree_reuse, playout_cap=cap,
                                            forced_playouts=forced, gumbel=gz, solver=sv is not None)
+        adj = parse_adjudicate(cfg, adjudicate)
         if not torch.cuda.is_available():
             raise hip.XqError("SelfPlayEngine needs a GPU: the HIP engine has no CPU fallback")
         self.lib = hip.lib()
@@ -538,6 +589,18 @@ class SelfPlayEngine:
         self.dedup = hip.DedupTable(self.G, self.device) if self.eval_dedup else None
         # settled-move cutoff: xq_engine_settle's counters, one row per slot (searches settled, simulations not run)
         self._settle_counters = torch.zeros((self.G, 2), dtype=torch.int64, device=self.device) if self.early_stop else None
+        # table adjudication: the tables' device words, xq_engine_adjudicate's options and counters, one row per slot (games ended
+        # decisive, drawn, covered but left alone, matched through the swapped colours)
+        self.adjudicate_tables = None
+        if adj is not None:
+            tabs = []
+            for tb in adj[0]:
+                t = tb.device_table()
+                if t.device != self.ws.device:
+                    raise hip.XqError(f"adjudicate: the table of {tb.signature!r} is on {t.device}, the engine on {self.ws.device}")
+                tabs.append((tb.codes, t))
+            self.adjudicate_tables, self._adjudicate_opts = tuple(tabs), adj[1]
+            self._adjudicate_counters = torch.zeros((self.G, 4), dtype=torch.int64, device=self.device)
         self._reuse_seen = (self.evaluator, getattr(self.evaluator, "weights_version", 0))
         self.steps = 0
         self._graph = None
@@ -592,7 +655,18 @@ class SelfPlayEngine:
                       "xq_engine_settle")
         hip.check(self.lib.xq_engine_select(C.byref(self.h), self.nn_input.data_ptr(), hip.stream_ptr(self.device)),
                   "xq_engine_select")
+        if self.adjudicate_tables is not None:         # behind the select kernel's root requests, ahead of every expand kernel
+            self.adjudicate()
         return self.nn_input
+
+    def adjudicate(self):
+        """After `select`, ahead of the expand call: end every game whose real position one of the tables decides
+        (xq_engine_adjudicate, once per table, in order; a slot an earlier table decided is skipped by the later ones).  `select()`
+        calls it; public for callers that drive the stages themselves.  Asynchronous."""
+        if self.adjudicate_tables is None:
+            raise hip.XqError("adjudicate needs an engine with adjudicate=")
+        for codes, table in self.adjudicate_tables:
+            hip.engine_adjudicate(self.h, codes, table, self._adjudicate_opts, self._adjudicate_counters)
 
     def expand(self, policy: torch.Tensor, value: torch.Tensor, is_probs: bool = False):
         if policy.dtype != torch.float32 or value.dtype != torch.float32:
@@ -830,6 +904,16 @@ class SelfPlayEngine:
         s = self._settle_counters.sum(dim=0).cpu()
         return dict(settled_moves=int(s[0]), simulations_saved=int(s[1]))
 
+    def adjudication_stats(self) -> dict:
+        """Table adjudication's counters: adjudicated_decisive and adjudicated_drawn (games a table ended), adjudicated_left_alone
+        (root positions a table covers as drawn while draws is off) and adjudicated_swapped (matched through the colour-swapped
+        image, among all three).  Synchronises."""
+        if self.adjudicate_tables is None:
+            raise hip.XqError("adjudication_stats needs an engine with adjudicate=")
+        s = self._adjudicate_counters.sum(dim=0).cpu()
+        return dict(adjudicated_decisive=int(s[0]), adjudicated_drawn=int(s[1]), adjudicated_left_alone=int(s[2]),
+                    adjudicated_swapped=int(s[3]))
+
     def solver_stats(self) -> dict:
         """The proven-result search's counters (xq_engine_solver_stats_read): proven_nodes, proven_stops, proven_moves,
         unspent_sims, removed_visits.  Synchronises."""
@@ -1023,10 +1107,11 @@ class SelfPlayEngine:
 
 def arena_engine(cfg: hip.EngineConfig, device, opening_plies: int, first_game: int, inject=None,
                  perpetual_check: bool = False, solver: bool = False, record_games: bool = False,
-                 early_stop: bool = False) -> SelfPlayEngine:
+                 early_stop: bool = False, adjudicate=None) -> SelfPlayEngine:
     """The arena's engine with arena options (paired openings from game index `first_game`, the per-model packed step)."""
     return SelfPlayEngine(cfg, device, inject=inject, arena_opts=(int(opening_plies), int(first_game)),
-                          perpetual_check=perpetual_check, solver=solver, record_games=record_games, early_stop=early_stop)
+                          perpetual_check=perpetual_check, solver=solver, record_games=record_games, early_stop=early_stop,
+                          **({} if adjudicate is None else {"adjudicate": adjudicate}))
 
 
 def replay_games(records, stop_ply=None, perpetual_check: bool = False, device="cuda") -> dict:

@@ -46,6 +46,7 @@ POSITION_FATAL = 15            # XQ_POSITION_FATAL: the bits of positions_check 
 POSITION_NO_MOVE = 16          # XQ_POSITION_NO_MOVE: the side to move has no legal move (the game is over at ply 0)
 START_POOL_MAX = 1 << 20       # XQ_START_POOL_MAX
 RNG_KIND_START_POOL = 11       # XQ_RNG_KIND_START_POOL
+REASON_TABLE = 5               # XQ_REASON_TABLE: a result's reason for a game an endgame table adjudicated
 
 
 class XqError(RuntimeError):
@@ -199,6 +200,12 @@ class SuperviseOpts(C.Structure):
 class TbSampleOpts(C.Structure):
     """xq_tb_sample_opts: table entries as samples (xq_tb_samples): policy 0 every optimal move is a target, 1 the first one."""
     _fields_ = [("policy", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class AdjudicateOpts(C.Structure):
+    """xq_adjudicate_opts: table adjudication (xq_tb_adjudicate_batch / xq_engine_adjudicate): draws 1 a drawn entry ends the game,
+    both_colours 1 the colour-swapped image is matched too, min_ply the shortest game the engine stage looks at."""
+    _fields_ = [("draws", C.c_int32), ("both_colours", C.c_int32), ("min_ply", C.c_int32), ("reserved", C.c_int32)]
 
 
 class MateOpts(C.Structure):
@@ -363,6 +370,8 @@ def lib():
     L.xq_engine_start_indices.argtypes = [C.POINTER(Engine), C.POINTER(vp)]
     L.xq_engine_start_pool_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(StartPoolStats), vp]
     L.xq_engine_settle.argtypes = [C.POINTER(Engine), vp, vp]
+    L.xq_tb_adjudicate_batch.argtypes = [vp, i32, vp, C.c_int64, vp, vp, i32, C.POINTER(AdjudicateOpts), vp, vp, vp, vp]
+    L.xq_engine_adjudicate.argtypes = [C.POINTER(Engine), vp, i32, vp, C.c_int64, C.POINTER(AdjudicateOpts), vp, vp]
     L.xq_engine_drain_games.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
     L.xq_engine_drain_games_device.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
     L.xq_engine_game_records_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(GameRecordsStats), vp]
@@ -496,7 +505,7 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_positions_check_batch", "xq_engine_workspace_bytes_sp", "xq_engine_init_sp", "xq_start_pool_draw_host",
            "xq_engine_start_indices", "xq_engine_start_pool_stats_read", "xq_evdedup_bytes", "xq_evdedup_init",
            "xq_engine_compact_unique", "xq_engine_expand_dedup", "xq_evdedup_stats_read", "xq_evdedup_bucket_host",
-           "xq_dedup_rows_batch", "xq_engine_settle"]
+           "xq_dedup_rows_batch", "xq_engine_settle", "xq_tb_adjudicate_batch", "xq_engine_adjudicate"]
 
 
 def check(rc: int, what: str):
@@ -939,6 +948,60 @@ def tb_samples(signature, table: torch.Tensor, index: torch.Tensor, policy: int 
         check(lib().xq_tb_samples(arr, P, _dev(table), _dev(index), n, C.byref(opts), _dev(rows), _dev(status), stream_ptr(dev)),
               "xq_tb_samples")
     return rows, status
+
+
+def adjudicate_opts(draws=True, both_colours=True, min_ply=0, what: str = "adjudicate") -> AdjudicateOpts:
+    """The options of table adjudication checked -> AdjudicateOpts (no GPU needed): draws and both_colours bools, min_ply an
+    integer >= 0."""
+    for name, v in (("draws", draws), ("both_colours", both_colours)):
+        if v not in (False, True, 0, 1):
+            raise XqError(f"{what}: {name} must be a bool, got {v!r}")
+    try:
+        ok = not isinstance(min_ply, bool) and int(min_ply) == min_ply and 0 <= int(min_ply) <= 2 ** 31 - 1
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise XqError(f"{what}: min_ply must be an integer >= 0, got {min_ply!r}")
+    return AdjudicateOpts(int(bool(draws)), int(bool(both_colours)), int(min_ply), 0)
+
+
+def tb_adjudicate_batch(signature, table: torch.Tensor, boards: torch.Tensor, side: torch.Tensor, draws: bool = True,
+                        both_colours: bool = True):
+    """The adjudication rule over positions (xq_tb_adjudicate_batch): boards int8[n,90] (or [n,10,9]) and side int8[n] on the
+    table's device -> (status uint8[n], winner int8[n], value int16[n]) there.  status 0 decided; +1 not in the table under either
+    colouring; +2 a king is missing; +4 an invalid entry; +8 a drawn entry with draws off; +16 matched through the colour-swapped
+    image (beside 0 or 8).  winner is +1 / -1 / 0 where the position is decided, value the entry's word where one was read."""
+    codes, entries = _tb_table_arg(signature, table, "tb_adjudicate_batch")
+    opts = adjudicate_opts(draws, both_colours, 0, "tb_adjudicate_batch")
+    n, _ = _positions_arg(boards, side, "tb_adjudicate_batch")
+    dev = table.device
+    if n and (boards.device != dev or side.device != dev):
+        raise XqError(f"tb_adjudicate_batch: boards and side must be on the table's device {dev}, got {boards.device} and {side.device}")
+    status = torch.zeros(n, dtype=torch.uint8, device=dev)
+    winner = torch.zeros(n, dtype=torch.int8, device=dev)
+    value = torch.zeros(n, dtype=torch.int16, device=dev)
+    if n:
+        arr, P = _tb_pieces(codes)
+        check(lib().xq_tb_adjudicate_batch(arr, P, _dev(table), entries, _dev(boards), _dev(side), n, C.byref(opts), _dev(status),
+                                           _dev(winner), _dev(value), stream_ptr(dev)), "xq_tb_adjudicate_batch")
+    return status, winner, value
+
+
+def engine_adjudicate(engine_handle, signature, table: torch.Tensor, opts: AdjudicateOpts, counters: torch.Tensor) -> None:
+    """The engine stage (xq_engine_adjudicate) between select and expand: every slot that waits for its root's evaluation, whose
+    game the rules have not ended and whose real board `table` decides gets root status REASON_TABLE and the winner.
+    `engine_handle` is a `hip.Engine` (SelfPlayEngine.h), `counters` an int64 device tensor [n_games, 4] the caller zeroed
+    (decisive, drawn, left alone, swapped).  On the current stream; does not synchronise."""
+    codes, entries = _tb_table_arg(signature, table, "engine_adjudicate")
+    if not isinstance(opts, AdjudicateOpts):
+        raise XqError(f"engine_adjudicate: opts must be a hip.AdjudicateOpts, got {type(opts).__name__}")
+    G = int(engine_handle.cfg.n_games)
+    if not isinstance(counters, torch.Tensor) or counters.dtype != torch.int64 or tuple(counters.shape) != (G, 4) or \
+            counters.device != table.device:
+        raise XqError(f"engine_adjudicate: counters must be an int64 tensor [{G}, 4] on the table's device")
+    arr, P = _tb_pieces(codes)
+    check(lib().xq_engine_adjudicate(C.byref(engine_handle), arr, P, _dev(table), entries, C.byref(opts), _dev(counters),
+                                     stream_ptr(table.device)), "xq_engine_adjudicate")
 
 
 def _records_arg(samples: torch.Tensor, what: str):

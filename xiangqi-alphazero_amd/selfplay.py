@@ -98,7 +98,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
               tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None,
               perpetual_check: Optional[bool] = None, solver: Optional[bool] = None, root_stats: Optional[bool] = None,
               eval_mirror: Optional[bool] = None, record_games: Optional[bool] = None, start_pool=None,
-              eval_dedup: Optional[bool] = None):
+              eval_dedup: Optional[bool] = None, adjudicate=None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -138,7 +138,11 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     `eval_dedup` (None: `config.eval_dedup`, absent = off) evaluates every distinct position once per step (DESIGN.md section
     4.24): stats `eval_dedup`, `eval_dedup_requests`, `eval_dedup_merged`, `eval_dedup_collisions`, `eval_dedup_mismatches` (0
     when off).  The games do not change, the network runs on fewer rows; it needs the packed step and excludes the evaluation
-    cache, leaves_per_step > 1 and eval_mirror."""
+    cache, leaves_per_step > 1 and eval_mirror.
+    `adjudicate` = (tables, options) (an argument only: `AlphaZeroLoop` reads the config keys and generates the tables) ends a game
+    as soon as an endgame table decides its position (engine.SelfPlayEngine): stats `adjudicated_games`
+    (the finished games with reason 5), `adjudicated_decisive`, `adjudicated_drawn`, `adjudicated_left_alone` and
+    `adjudicated_swapped` (the engine's counters; all 0 when off).  Every other option."""
     if eval_dedup is None:
         eval_dedup = bool(getattr(config, "eval_dedup", False))
     if record_games is None:
@@ -185,7 +189,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
                                 leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
                                 forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check, solver=solver,
                                 root_stats=root_stats, eval_mirror=eval_mirror, record_games=record_games, start_pool=start_pool,
-                                eval_dedup=eval_dedup)
+                                eval_dedup=eval_dedup, **({} if adjudicate is None else {"adjudicate": adjudicate}))
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -227,6 +231,13 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
         st["perpetual_check_games"] = int((results[:, 9] == 4).sum().item()) if len(results) else 0   # byte 9: reason
     else:
         st["perpetual_check_games"] = int((results["reason"] == 4).sum())
+    if device_records:                                 # the games a table ended, counted the same way
+        st["adjudicated_games"] = int((results[:, 9] == hip.REASON_TABLE).sum().item()) if len(results) else 0
+    else:
+        st["adjudicated_games"] = int((results["reason"] == hip.REASON_TABLE).sum())
+    adj = eng.adjudication_stats() if adjudicate is not None else {}
+    for k in ("decisive", "drawn", "left_alone", "swapped"):       # the counters' keys are present (0) when it is off
+        st["adjudicated_" + k] = adj.get("adjudicated_" + k, 0)
     st.setdefault("eval_cache_probes", 0)              # the cache's keys are present (0) when it is off
     st.setdefault("eval_cache_hits", 0)
     if eng.capture_error:

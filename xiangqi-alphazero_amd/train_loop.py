@@ -5,8 +5,10 @@ Per iteration, exactly the reference's order:
   1. self-play     every rank plays `shard_games(num_games_per_iter, world, rank)` games on its own engine with the
                    current best weights (no collective during search); the finished compact samples stay on the device
                    (`xq_engine_drain_device`) and one padded all-gather of those device buffers brings every rank's
-                   records to every rank's device-resident replay buffer;
-  2. train         `train_network` data-parallel over the ranks (every batch split, SyncBatchNorm, bucketed gradient
+                   records to every rank's device-resident replay buffer.  Opt-in (`config.adjudicate_signatures`, with
+                   `adjudicate_draws` and `adjudicate_min_ply`): a game ends as soon as one of those endgame tables decides
+                   its position, and its samples get the exact result (engine.SelfPlayEngine's `adjudicate`);
+  2. train        `train_network` data-parallel over the ranks (every batch split, SyncBatchNorm, bucketed gradient
                    all-reduce: the reference's full-batch update) -- or on rank 0 alone with `config.ddp = False` -- then
                    ONE flat `broadcast_weights`;
   3. arena gate    every second iteration (train.py:609) the candidate plays the best model, the games sharded over the
@@ -190,6 +192,37 @@ def _endgame_play_options(config):
     return playout, teacher
 
 
+def _adjudicate_options(config):
+    """Table adjudication's keys (all optional; absent means off): None when config.adjudicate_signatures is absent, None or empty,
+    else a dict of signatures (FEN letters, one to four), draws (config.adjudicate_draws, default true) and min_ply
+    (config.adjudicate_min_ply, default 1).  A bad value raises XqError with the key's name, whether the option is on or not.  The
+    tables are generated at first use."""
+    from . import endgame, engine
+    draws = getattr(config, "adjudicate_draws", None)
+    if draws is not None and not isinstance(draws, bool):
+        raise hip.XqError(f"config.adjudicate_draws must be a bool, got {draws!r}")
+    min_ply = getattr(config, "adjudicate_min_ply", None)
+    min_ply = 1 if min_ply is None else min_ply
+    if isinstance(min_ply, bool) or not isinstance(min_ply, int) or min_ply < 0:
+        raise hip.XqError(f"config.adjudicate_min_ply must be an integer >= 0, got {min_ply!r}")
+    sigs = getattr(config, "adjudicate_signatures", None)
+    if sigs is None:
+        return None
+    if isinstance(sigs, str) or not isinstance(sigs, (list, tuple)):
+        raise hip.XqError(f"config.adjudicate_signatures must be a list of signatures such as ['Ra', 'CA'], got {sigs!r}")
+    if len(sigs) > engine.ADJUDICATE_MAX_TABLES:
+        raise hip.XqError(f"config.adjudicate_signatures: at most {engine.ADJUDICATE_MAX_TABLES} tables, got {len(sigs)}")
+    for sig in sigs:
+        try:
+            hip.tb_entries(sig)
+        except hip.XqError as e:
+            raise hip.XqError(f"config.adjudicate_signatures: {e}") from None
+    if not sigs:
+        return None
+    return {"signatures": [endgame.signature_text(sig) for sig in sigs], "draws": True if draws is None else draws,
+            "min_ply": int(min_ply)}
+
+
 def _start_pool_options(config):
     """The start-position pool's keys (all optional; absent means off): None when neither config.start_positions_file nor
     config.start_positions_endgame is set, else a dict of file, boards and sides (the file's positions, read here: a missing file
@@ -346,6 +379,12 @@ class AlphaZeroLoop:
         # every rank holds the same pool; the ranks' draws differ through Philox's rank word
         self.start_pool = _start_pool_options(config)
         self._shard_pool = (0, 0)
+        # table adjudication (config.adjudicate_signatures, adjudicate_draws, adjudicate_min_ply; absent: off), read once and
+        # checked here: a self-play game ends as soon as one of the signatures' tables decides its position.  The tables are
+        # generated on the device at first use; a signature equal to endgame_signature shares that table.  Self-play only
+        self.adjudicate = _adjudicate_options(config)
+        self._adjudicate_tbs = None
+        self._shard_adjudicated = (0, 0, 0)
         torch.manual_seed(seed)                     # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -381,9 +420,12 @@ class AlphaZeroLoop:
                                                     forced_playouts=float(getattr(self.config, "forced_playouts_k", 0) or 0) or None,
                                                     perpetual_check=self.perpetual_check, solver=self.solver,
                                                     root_stats=self.record_root_stats, eval_mirror=self.eval_mirror,
-                                                    record_games=self.record_games, start_pool=self._iteration_pool())
+                                                    record_games=self.record_games, start_pool=self._iteration_pool(),
+                                                    **self._adjudicate_arg())
         if self.start_pool is not None:
             self._shard_pool = (st["start_pool"][0], st["start_pool_games"])
+        if self.adjudicate is not None:
+            self._shard_adjudicated = (st["adjudicated_games"], st["adjudicated_decisive"], st["adjudicated_drawn"])
         if self.record_games:
             self._write_records("selfplay", st["game_records"].cpu().numpy().reshape(-1).view(GAME_RECORD_DTYPE))
         # the Gumbel root search (config.gumbel_considered, gumbel_c_visit, gumbel_c_scale; absent or 0: off) reaches the engine
@@ -408,6 +450,23 @@ class AlphaZeroLoop:
             eb, es = start_pool.from_table(tb, min(p["endgame"], have), KINDS, seed=self.seed + self.iteration)
             boards, sides = np.concatenate([boards, eb]), np.concatenate([sides, es])
         return boards, sides, p["prob"]
+
+    def _adjudicate_arg(self) -> dict:
+        """run_games' `adjudicate` keyword, or nothing: with the keys absent the call is the call without it.  The tables are
+        generated on self.device at first use and kept; the endgame yardstick's table serves its own signature."""
+        a = self.adjudicate
+        if a is None:
+            return {}
+        if self._adjudicate_tbs is None:
+            from . import endgame
+            tbs = []
+            for sig in a["signatures"]:
+                if self.endgame is not None and self.endgame["signature"] == sig:
+                    tbs.append(self._endgame_table())
+                else:
+                    tbs.append(endgame.Tablebase.generate(sig, self.device))
+            self._adjudicate_tbs = tuple(tbs)
+        return {"adjudicate": (self._adjudicate_tbs, dict(draws=a["draws"], min_ply=a["min_ply"]))}
 
     def _scoring_evaluator(self):
         """The evaluator of `best_model` that scores the shards: built once and kept (its activation and logits buffers with it);
@@ -435,6 +494,7 @@ class AlphaZeroLoop:
         t0 = time.time()
         self._shard_scores = None
         self._shard_pool = (0, 0)
+        self._shard_adjudicated = (0, 0, 0)
         samples, results = self._play_shard(xdist.shard_games(cfg.num_games_per_iter, self.world, self.rank))
         pooled = {}
         if self.start_pool is not None:
@@ -444,6 +504,12 @@ class AlphaZeroLoop:
                 dist.all_reduce(games)
             positions = len(self.start_pool["boards"]) + (self.start_pool["endgame"] or 0)
             pooled = {"start_pool_positions": self._shard_pool[0] or positions, "start_pool_games": int(games.item())}
+        if self.adjudicate is not None:
+            # the games the tables ended, summed over the ranks
+            ended = torch.tensor(list(self._shard_adjudicated), dtype=torch.int64, device=self.device)
+            if self.grouped:
+                dist.all_reduce(ended)
+            pooled.update(zip(("adjudicated_games", "adjudicated_decisive", "adjudicated_drawn"), (int(v) for v in ended.tolist())))
         scores = None
         if self.score_samples:
             # one score row per sample of this shard; a shard without games (or a _play_shard that does not score) has none, and
