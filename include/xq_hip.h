@@ -389,7 +389,7 @@ int xq_engine_init_fp(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
  * playout cap, forced playouts or leaves_per_step > 1; m outside [1, 128]; c_visit or c_scale not finite (as float32), c_visit < 0,
  * c_scale <= 0; reserved != 0; and whatever xq_engine_init_fp refuses.  The evaluation cache and manual_moves = 1 are allowed.
  * Workspace: the parameters, one double per slot and the tables for k = 1 .. m (2 m S bytes) lie behind the engine's square-root
- * table; only Gumbel engines grow, "gumbel on" lives in the handle (pad0, above the public flag bits). */
+ * table (THE OPTION WORDS below); only Gumbel engines grow, "gumbel on" lives in the handle (pad0, above the public flag bits). */
 typedef struct xq_gumbel { int32_t considered; int32_t reserved; double c_visit; double c_scale; } xq_gumbel;
 #define XQ_STAT_GUMBEL_MOVES 10
 #define XQ_STAT_GUMBEL_CONSIDERED 11
@@ -450,7 +450,7 @@ int xq_gumbel_considered_visits_host(int k, int num_simulations, uint16_t *host_
  * with arena options leaves_per_step = 1 and none of tree reuse, playout cap, forced playouts and Gumbel root search.  The three
  * xq_engine_*_arena calls and xq_engine_arena_openings return XQ_ERR_ARG on an engine without arena options.
  * Workspace: the parameters, the openings record and the two buffer sets (about 5.7 KB per slot and set) lie behind the engine's
- * square-root table; only arena-option engines grow, "arena options on" lives in the handle (pad0, above the public flag bits). */
+ * square-root table (THE OPTION WORDS below); only arena-option engines grow, "arena options on" lives in the handle (pad0, above the public flag bits). */
 #define XQ_ARENA_MAX_OPENING 16
 typedef struct xq_arena_opts { int32_t opening_plies; int32_t first_game; uint32_t reserved[2]; } xq_arena_opts;
 size_t xq_engine_workspace_bytes_ar(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
@@ -525,8 +525,8 @@ int xq_engine_init_ru(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
  * and without arena options; the perpetual-check rule.  XQ_ERR_ARG before any launch (xq_engine_workspace_bytes_sv: 0): enabled
  * outside {0, 1}, a non-zero reserved word; with enabled = 1: leaves_per_step > 1, Gumbel root search (its equal-visit candidates
  * cannot skip a child), forced playouts; and whatever xq_engine_init_ru refuses.  A LOSS root without a WIN child (a defect) sets
- * overflow bit 128 << 8.  Workspace: 64 bytes of counters per slot behind the engine's square-root table (behind the arena words
- * with arena options); only solver engines grow, "solver on" lives in the handle (pad0, above the public flag bits).
+ * overflow bit 128 << 8.  Workspace: 64 bytes of counters per slot behind the engine's square-root table (THE OPTION WORDS
+ * below); only solver engines grow, "solver on" lives in the handle (pad0, above the public flag bits).
  * xq_engine_read_root_states: the states at the root of `slot` from the view of the SIDE TO MOVE there: child_state[i] (move order,
  * XQ_MAXM entries, zero past the count) +1 this move wins, -1 it loses, 2 draw, 0 unknown; *root_state in the same code.  Returns
  * the child count; XQ_ERR_ARG on an engine without the option.  Synchronises, as xq_engine_solver_stats_read does. */
@@ -1064,7 +1064,7 @@ typedef struct xq_game_result {
  * before any launch (xq_engine_workspace_bytes_gr: 0): a non-zero reserved word; enabled outside {0, 1}; and, with enabled = 1,
  * max_out_games < 1, manual_moves = 1 (a search-only engine plays no games), max_game_length > XQ_RECORD_MAX_PLIES or
  * random_opening_moves > XQ_RECORD_MAX_PLIES; and whatever xq_engine_init_em refuses.  Every other option goes with it, leaf
- * batching included.  Workspace: behind the engine's square-root table (behind every other option's words there), a ring of
+ * batching included.  Workspace: behind the engine's square-root table (THE OPTION WORDS below: the region's tail), a ring of
  * max_out_games records, a move log uint16[G][XQ_RECORD_MAX_PLIES], the opening count of every slot, and 256 bytes holding the
  * ring's counter and the two statistics; "game records on" lives in the handle (pad0, bit 23).  The handle's layout and size do
  * not change.
@@ -1525,7 +1525,7 @@ int xq_tb_samples(const int8_t *pieces, int n_pieces, const int16_t *dev_table /
  * perpetual-check rule, the evaluation cache, the evaluation mirror and graph capture.
  * Init runs the check over the pool and returns XQ_ERR_ARG when an entry has a fatal bit: no unchecked board reaches a slot.  It
  * then copies the pool into the workspace; the caller's arrays need not outlive the call.  Workspace: behind the engine's
- * square-root table (behind every other option's words there), the pool as 96-byte rows (the board, its side in byte 90),
+ * square-root table (THE OPTION WORDS below: the region's tail), the pool as 96-byte rows (the board, its side in byte 90),
  * int32 start_index[G] (the entry the slot's current game started from, -1 for the initial position) and 256 bytes holding n,
  * prob and the counter; "start-position pool on" lives in the handle (pad0, bit 22).  The handle's layout and size do not change.
  * THE DRAW for the game of a slot that will carry game_seq (the slot's previous game_seq + 1) is stateless:
@@ -1569,6 +1569,42 @@ int xq_engine_init_sp(xq_engine *eng, const xq_engine_config *cfg, int leaves_pe
 int xq_start_pool_draw_host(uint64_t seed, int rank, int slot, uint32_t game_seq, int n, double prob);
 int xq_engine_start_indices(const xq_engine *eng, const int32_t **dev_index /* [n_games] */);
 int xq_engine_start_pool_stats_read(const xq_engine *eng, xq_start_pool_stats *host_out, void *stream);
+
+/* THE OPTION WORDS: where every option keeps its device words.  The handle is full, so Gumbel root search, arena options, the
+ * solver, game records and the start-position pool all keep theirs in one workspace region, the square-root table's; this is its
+ * map (csrc/xq_engine_state.cuh holds the functions every reader uses).  Offsets are bytes from the region's first byte, up()
+ * rounds up to 256; G = n_games, S = num_simulations, K = leaves_per_step.
+ *   the front, located from the region's first byte
+ *     0                  table      double[S + 2 + (K > 1 ? K : 0)]
+ *     (S + 2) * 8        gz_head 16 bytes (m, c_visit and c_scale as float32) | gz_vhat double[G] | gz_visits uint16[m][S]
+ *     up((S + 2) * 8)    ar_head 16 bytes (opening_plies, first_game) | ar_op_counts int32[G] |
+ *                        ar_op_actions uint16[G][XQ_ARENA_MAX_OPENING] | ar_n_live int32[2] | two sets (0 the new model's slots, 1
+ *                        the old model's) of ar_rows int32[G] | ar_x float[G][1350] | ar_moves uint16[G][128] | ar_counts int32[G],
+ *                        every part up()
+ *     up((S + 2) * 8), or the end of the arena words
+ *                        solver     uint64[G][8]
+ *   the tail, located from the region's end; it starts at up(the front's end), every part up()
+ *     game records       gr_ring xq_game_record[max_out_games] | gr_log uint16[G][XQ_RECORD_MAX_PLIES] | gr_opening uint16[G] |
+ *                        gr_head 256 bytes
+ *     start pool         sp_rows int8[n][96] | sp_index int32[G] | sp_head 256 bytes
+ * xq_engine_option_words_sp takes what xq_engine_workspace_bytes_sp takes and fills the map for that engine: offset and size of
+ * every block it has (a block it has not: 0, 0) and the region's size.  It needs no GPU and launches nothing.  XQ_ERR_ARG where
+ * xq_engine_workspace_bytes_sp returns 0, and for out == NULL. */
+typedef struct xq_words_block { uint64_t offset, bytes; } xq_words_block;
+typedef struct xq_option_words {
+    uint64_t bytes;              /* the region's */
+    xq_words_block table;
+    xq_words_block gz_head, gz_vhat, gz_visits;
+    xq_words_block ar_head, ar_op_counts, ar_op_actions, ar_n_live, ar_rows[2], ar_x[2], ar_moves[2], ar_counts[2];
+    xq_words_block solver;
+    xq_words_block gr_ring, gr_log, gr_opening, gr_head;
+    xq_words_block sp_rows, sp_index, sp_head;
+} xq_option_words;
+int xq_engine_option_words_sp(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                              const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                              const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                              const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records, const xq_start_pool *pool,
+                              xq_option_words *out);
 
 /* Settled-move cutoff (opt-in): end a search whose first choice is fixed.  A move played at temperature 0 -- every arena move
  * (manual_moves = 2), and a search-only engine's (manual_moves = 1) under get_action(temperature = 0) -- is the FIRST MAXIMUM of the

@@ -296,8 +296,10 @@ def test_two_tables_give_the_games_of_the_larger_one(tables):
 
 
 def test_none_is_the_engine_without_the_argument():
-    a = _play(None, None, n_games=6)
-    b = _play(None, None, n_games=6, adjudicate=None)
+    """One game per slot: with fewer games than slots, which slots win k_start_pool's race for the quota's tickets differs from run
+    to run, and so do the games played."""
+    a = _play(None, None, n_games=G)
+    b = _play(None, None, n_games=G, adjudicate=None)
     assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes() and a[2] == b[2] and len(a[0]) > 6
     assert not (a[1]["reason"] == 5).any() and a[3].adjudicate_tables is None
     from xiangqi_alphazero_amd import hip

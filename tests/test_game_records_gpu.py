@@ -183,12 +183,14 @@ def test_selfplay_records_replay(name, shape, kw):
     assert eng.game_records_stats() == dict(recorded=n_games, dropped=0) and len(eng.drain_games()) == 0
 
 
-@pytest.mark.parametrize("openings", [False, True], ids=["default", "paired_openings"])
-def test_arena_records_replay(openings):
+@pytest.mark.parametrize("openings,solver", [(False, False), (True, False), (True, True)],
+                         ids=["default", "paired_openings", "paired_openings_solver"])
+def test_arena_records_replay(openings, solver):
+    """paired_openings_solver is the fullest region of option words: arena words, solver counters and the records' tail."""
     from xiangqi_alphazero_amd import arena
     n_games, length = 4, 16
     info = {} if openings else None
-    kw = dict(opening_plies=4, seed=3, info=info) if openings else {}
+    kw = dict(opening_plies=4, seed=3, info=info, solver=solver) if openings else {}
     results, records = arena.play_arena(_TorchStub(), _TorchStub(), n_games, 8, length, record_games=True, **kw)
     assert len(results) == len(records) == n_games and records["slot"].tolist() == list(range(n_games))
     assert records["n_moves"].tolist() == results["steps"].tolist() and records["winner"].tolist() == results["winner"].tolist()

@@ -112,9 +112,11 @@ def _sorted_drain(eng):
     return np.sort(smp, order=["slot", "game_seq", "ply"]), np.sort(res, order=["slot", "game_seq"])
 
 
-@pytest.mark.parametrize("kw,graph", [({}, False), (dict(leaves_per_step=4), False), (dict(tree_reuse=True), False), ({}, True)],
-                         ids=["sequential", "leaves4", "tree_reuse", "graph"])
+@pytest.mark.parametrize("kw,graph", [({}, False), (dict(leaves_per_step=4), False), (dict(tree_reuse=True), False), ({}, True),
+                                      (dict(solver=True), False), (dict(gumbel=(8, 50.0, 1.0)), False)],
+                         ids=["sequential", "leaves4", "tree_reuse", "graph", "solver", "gumbel"])
 def test_initial_position_pool_is_the_plain_engine(kw, graph):
+    """solver and gumbel: the pool's tail of the option words sits behind the solver's counters or the Gumbel words."""
     from xiangqi_alphazero_amd import engine
     ev = _TorchStub()
     n_games, out = 6, []

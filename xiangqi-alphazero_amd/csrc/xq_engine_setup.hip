@@ -34,16 +34,46 @@ struct Layout {
     int node_cap, path_cap, stage_cap;
 };
 
+// the option words of an engine with these options: THE OPTION WORDS of xq_engine_state.cuh filled in, a block the engine has
+// not left {0, 0}.  make_layout, engine_init and xq_engine_option_words_sp all read this one record.
+xq_option_words option_words(const xq_engine_config *c, const Opts &o) {
+    const size_t G = (size_t)c->n_games, S = (size_t)c->num_simulations, K = (size_t)o.K;
+    const size_t m = o.gumbel ? (size_t)o.gumbel->considered : 0, M = o.records_on() ? (size_t)o.records->max_out_games : 0,
+                 n = o.pool_on() ? (size_t)o.pool->n : 0;
+    const bool arena = o.arena != nullptr, solver = o.solver_on();
+    xq_option_words w;
+    memset(&w, 0, sizeof(w));
+    w.table = {0, ow_table_bytes(S, K)};
+    if (m) {
+        w.gz_head = {ow_gz_head(S), sizeof(GzHead)}; w.gz_vhat = {ow_gz_vhat(S), G * 8}; w.gz_visits = {ow_gz_visits(G, S), m * S * 2};
+    }
+    if (arena) {
+        const ArOff a = ar_off(G, S);
+        w.ar_head = {a.head, sizeof(ArHead)}; w.ar_op_counts = {a.op_counts, G * 4};
+        w.ar_op_actions = {a.op_actions, G * XQ_ARENA_MAX_OPENING * 2}; w.ar_n_live = {a.n_live, 2 * 4};
+        for (int i = 0; i < 2; ++i) {
+            w.ar_rows[i] = {a.rows[i], G * 4}; w.ar_x[i] = {a.x[i], G * XQ_STATE_FLOATS * 4};
+            w.ar_moves[i] = {a.moves[i], G * XQ_MAXM * 2}; w.ar_counts[i] = {a.counts[i], G * 4};
+        }
+    }
+    if (solver) w.solver = {sv_off(G, S, arena), sv_bytes(G)};
+    const size_t end = ow_region_bytes(ow_front_end(G, S, K, m, arena, solver), G, M, n);
+    w.bytes = end;
+    if (M) {
+        w.gr_ring = {ow_gr_ring(end, G, M), M * XQ_RECORD_BYTES}; w.gr_log = {ow_gr_log(end, G), G * XQ_RECORD_MAX_PLIES * 2};
+        w.gr_opening = {ow_gr_opening(end, G), G * 2}; w.gr_head = {ow_tail_head(end), sizeof(GrHead)};
+    } else if (n) {
+        w.sp_rows = {ow_sp_rows(end, G, n), n * XQ_BS}; w.sp_index = {ow_sp_index(end, G), G * 4};
+        w.sp_head = {ow_tail_head(end), sizeof(SpHead)};
+    }
+    return w;
+}
+
 // K > 1 (leaf batching): the request rows (moves, counts, paths, packed buffers) are G K, slot-major; the virtual-loss
-// counters and the pending-leaf records follow the K = 1 layout, which is unchanged.  Gumbel root search (K = 1): the
-// square-root table's region also holds the Gumbel words (gz_bytes); every other engine has the layout it had.
-// Arena options (K = 1, never Gumbel): that region holds the arena words instead (ar_off).  Proven-result search (K = 1, never
-// Gumbel): its counters follow in the same region (sv_off, sv_bytes).  Game records (every engine that plays games): their words
-// close the region, from its next 256-byte boundary (gr_bytes).  The start-position pool (self-play, never with game records):
-// its words close the region instead (sp_bytes).
+// counters and the pending-leaf records follow the K = 1 layout, which is unchanged.  The square-root table's region holds every
+// option's words (option_words): only an engine with such an option grows there.
 Layout make_layout(const xq_engine_config *c, const Opts &opts) {
-    const int K = opts.K, gz_m = opts.gumbel ? opts.gumbel->considered : 0;
-    const bool arena = opts.arena != nullptr;
+    const int K = opts.K;
     Layout l;
     memset(&l, 0, sizeof(l));
     const size_t G = (size_t)c->n_games, S = (size_t)c->num_simulations, GK = G * (size_t)K;
@@ -72,12 +102,7 @@ Layout make_layout(const xq_engine_config *c, const Opts &opts) {
     put(P_OUTR, (size_t)(c->max_out_results > 0 ? c->max_out_results : 1) * XQ_RESULT_BYTES);
     put(P_CNT, 64);
     put(P_STATS, G * ST_N * 8);
-    const size_t sqrt_bytes = opts.solver_on() ? sv_off(G, S, arena) + sv_bytes(G)
-                              : arena          ? ar_off(G, S).end
-                                               : (S + 2 + (K > 1 ? (size_t)K : 0)) * 8 + (gz_m > 0 ? gz_bytes(G, S, (size_t)gz_m) : 0);
-    put(P_SQRT, opts.records_on() ? gr_align(sqrt_bytes) + gr_bytes(G, (size_t)opts.records->max_out_games)
-                : opts.pool_on()  ? gr_align(sqrt_bytes) + sp_bytes(G, (size_t)opts.pool->n)
-                                  : sqrt_bytes);
+    put(P_SQRT, option_words(c, opts).bytes);
     put(P_MNOISE, G * XQ_MAXM * 8);
     put(P_STATSUM, ST_N * 8);
     put(P_REQ, GK * 4);
@@ -329,55 +354,52 @@ int engine_init(xq_engine *eng, const xq_engine_config *cfg, const Opts &o, void
     // with K > 1 the virtual-loss counters and pending-leaf records behind them as well
     XQ_TRY(hipMemsetAsync(eng->p[P_PK_N], 0, l.off[P_PK_X] - l.off[P_PK_N], s));
     XQ_TRY(hipMemsetAsync(eng->p[P_PK_MOVES], 0, l.total - l.off[P_PK_MOVES], s));
+    const xq_option_words w = option_words(cfg, o);
+    char *words = (char *)eng->p[P_SQRT];
     {
-        const int n = cfg->num_simulations + 2 + (K > 1 ? K : 0);   // K > 1: N_parent + vl_parent < S + K
-        // Gumbel root search: the parameters, a zeroed v_hat per slot and the considered-visit tables for k = 1 .. m follow the table
-        const size_t S = (size_t)cfg->num_simulations, G = (size_t)cfg->n_games;
-        // arena options: the whole region zeroed (openings record, both sets' counts and rows), then the table and the parameters
-        const ArOff ao = ar_off(G, S);
-        if (o.arena) XQ_TRY(hipMemsetAsync(eng->p[P_SQRT], 0, ao.end, s));
-        if (o.solver_on()) XQ_TRY(hipMemsetAsync((char *)eng->p[P_SQRT] + sv_off(G, S, o.arena != nullptr), 0, sv_bytes(G), s));
-        const size_t bytes = o.arena ? ao.head + sizeof(ArHead) : sizeof(double) * n + (o.gumbel ? gz_bytes(G, S, (size_t)o.gumbel->considered) : 0);
-        double *tab = (double *)calloc(bytes, 1);
-        if (!tab) return XQ_ERR_ARG;
-        for (int i = 0; i < n; ++i) tab[i] = sqrt((double)i);   // math.sqrt(visit_count), mcts.py:49
+        // arena options: their words zeroed whole (openings record, both sets' counts and rows); the solver's counters zeroed
+        if (o.arena) XQ_TRY(hipMemsetAsync(words, 0, ar_off((size_t)cfg->n_games, (size_t)cfg->num_simulations).end, s));
+        if (o.solver_on()) XQ_TRY(hipMemsetAsync(words + w.solver.offset, 0, w.solver.bytes, s));
+        // one host image: the table (K > 1: N_parent + vl_parent < S + K) and, behind it, the Gumbel words (the parameters, a zeroed
+        // v_hat per slot, the considered-visit tables for k = 1 .. m) or the arena's parameters
+        const size_t bytes = o.arena ? w.ar_head.offset + w.ar_head.bytes : o.gumbel ? w.gz_visits.offset + w.gz_visits.bytes : w.table.bytes;
+        char *img = (char *)calloc(bytes, 1);
+        if (!img) return XQ_ERR_ARG;
+        for (size_t i = 0; i < w.table.bytes / 8; ++i) ((double *)img)[i] = sqrt((double)i);   // math.sqrt(visit_count), mcts.py:49
         if (o.gumbel) {
-            GzHead *h = (GzHead *)(tab + n);
+            GzHead *h = (GzHead *)(img + w.gz_head.offset);
             h->m = o.gumbel->considered; h->c_visit = (float)o.gumbel->c_visit; h->c_scale = (float)o.gumbel->c_scale;
-            uint16_t *vis = (uint16_t *)((char *)(h + 1) + G * 8);
-            for (int k = 1; k <= o.gumbel->considered; ++k) gz_considered_visits(k, (int)S, vis + (size_t)(k - 1) * S);
+            const int S = cfg->num_simulations;
+            for (int k = 1; k <= o.gumbel->considered; ++k) gz_considered_visits(k, S, (uint16_t *)(img + w.gz_visits.offset) + (size_t)(k - 1) * S);
         }
         if (o.arena) {
-            ArHead *h = (ArHead *)((char *)tab + ao.head);
+            ArHead *h = (ArHead *)(img + w.ar_head.offset);
             h->opening_plies = o.arena->opening_plies; h->first_game = o.arena->first_game;
         }
-        const int rc = xq::check(hipMemcpyAsync(eng->p[P_SQRT], tab, bytes, hipMemcpyHostToDevice, s));
+        const int rc = xq::check(hipMemcpyAsync(words, img, bytes, hipMemcpyHostToDevice, s));
         if (rc == XQ_OK) (void)hipStreamSynchronize(s);
-        free(tab);
+        free(img);
         if (rc != XQ_OK) return rc;
     }
     const Dev d = make_dev(eng);
     if (o.records_on()) {
         // game records: the ring, the log, the opening counts and the head zeroed, then the ring's size
-        const size_t G = (size_t)cfg->n_games, M = (size_t)o.records->max_out_games;
-        XQ_TRY(hipMemsetAsync(gr_ring(d.gr_log, M), 0, gr_bytes(G, M), s));
-        XQ_TRY(hipMemcpyAsync(&gr_head(d.gr_log, G)->max_out_games, &o.records->max_out_games, 4, hipMemcpyHostToDevice, s));
+        XQ_TRY(hipMemsetAsync(words + w.gr_ring.offset, 0, w.bytes - w.gr_ring.offset, s));
+        XQ_TRY(hipMemcpyAsync(words + w.gr_head.offset + offsetof(GrHead, max_out_games), &o.records->max_out_games, 4, hipMemcpyHostToDevice, s));
         XQ_TRY(hipStreamSynchronize(s));
     }
     if (o.pool_on()) {
         // start-position pool: the checked entries as rows, every slot's index -1, then the head
-        const size_t G = (size_t)cfg->n_games, n = (size_t)o.pool->n;
-        const SpDev sp = make_sp(eng);
         SpHead h;
         memset(&h, 0, sizeof(h));
         h.n = o.pool->n; h.prob = o.pool->prob;
-        const long long threads = (long long)n * XQ_BS;
+        const long long threads = (long long)o.pool->n * XQ_BS;
         hipLaunchKernelGGL(k_init_pool, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, o.pool->dev_boards, o.pool->dev_side,
-                           o.pool->n, sp_rows(sp.start_index, n));
+                           o.pool->n, (int8_t *)(words + w.sp_rows.offset));
         const int rc = launch_status();
         if (rc != XQ_OK) return rc;
-        XQ_TRY(hipMemsetAsync(sp.start_index, 0xFF, sp_index_bytes(G), s));
-        XQ_TRY(hipMemcpyAsync(sp.head, &h, sizeof(h), hipMemcpyHostToDevice, s));
+        XQ_TRY(hipMemsetAsync(words + w.sp_index.offset, 0xFF, w.sp_head.offset - w.sp_index.offset, s));
+        XQ_TRY(hipMemcpyAsync(words + w.sp_head.offset, &h, sizeof(h), hipMemcpyHostToDevice, s));
         XQ_TRY(hipStreamSynchronize(s));
     }
     hipLaunchKernelGGL(k_init, dim3((cfg->n_games + 255) / 256), dim3(256), 0, s, d);
@@ -550,6 +572,17 @@ size_t xq_engine_workspace_bytes_sp(const xq_engine_config *cfg, int leaves_per_
     return workspace_bytes(cfg, Opts{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror, records, pool});
 }
 
+int xq_engine_option_words_sp(const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
+                              const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
+                              const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
+                              const xq_eval_mirror_opts *mirror, const xq_game_records_opts *records, const xq_start_pool *pool,
+                              xq_option_words *out) {
+    const Opts o{leaves_per_step, flags, cap, forced, gumbel, arena, rules, solver, root_stats, mirror, records, pool};
+    if (!out || !opts_ok(cfg, o)) return XQ_ERR_ARG;
+    *out = option_words(cfg, o);
+    return XQ_OK;
+}
+
 int xq_engine_init_sp(xq_engine *eng, const xq_engine_config *cfg, int leaves_per_step, unsigned flags, const xq_playout_cap *cap,
                       const xq_forced_playouts *forced, const xq_gumbel *gumbel, const xq_arena_opts *arena,
                       const xq_rules_opts *rules, const xq_solver_opts *solver, const xq_root_stats_opts *root_stats,
@@ -630,7 +663,7 @@ int xq_engine_solver_stats_read(const xq_engine *eng, xq_solver_stats *host_out,
     XQ_TRY(hipStreamSynchronize((hipStream_t)stream));
     unsigned long long *h = (unsigned long long *)malloc(sv_bytes(G));
     if (!h) return XQ_ERR_ARG;
-    const int rc = xq::check(hipMemcpy(h, (char *)eng->p[P_SQRT] + sv_off(G, S, arena_of(eng)), sv_bytes(G), hipMemcpyDeviceToHost));
+    const int rc = xq::check(hipMemcpy(h, ow_base(eng) + sv_off(G, S, arena_of(eng)), sv_bytes(G), hipMemcpyDeviceToHost));
     memset(host_out, 0, sizeof(*host_out));
     if (rc == XQ_OK)
         for (size_t g = 0; g < G; ++g) {

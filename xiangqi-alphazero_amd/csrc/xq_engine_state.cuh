@@ -51,9 +51,17 @@ enum Ptr : int { P_BOARD = 0, P_HIST, P_GI, P_RESIGN, P_PMOVES, P_PATH, P_TN, P_
 
 enum Rng : int { RNG_RANDINT = 0, RNG_CHOICE = 1, RNG_DIRICHLET = 2, RNG_UNIFORM = 3 };
 
-constexpr int PAD0_PERPETUAL = 1 << 26;     // pad0 of the handle (encoding below): "perpetual-check rule on"
-constexpr int PAD0_ROOT_STATS = 1 << 24;    // "root statistics per sample on" (xq_engine_init_rs)
+// pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags in the public flag byte above them
+// (bits 16-23), and one private bit per option that is on.  Bits 24-31 are all taken; of the flag byte bit 16 is public and bits
+// 23 and 22 are private: flags_ok lets no caller's flag reach either.
 constexpr int PAD0_EVAL_MIRROR = (int)(1u << 31);   // "evaluation mirror on" (xq_engine_init_em): the last private bit, the sign
+constexpr int PAD0_CAP = 1 << 30;           // "playout cap on" (xq_engine_init_cap)
+constexpr int PAD0_FORCED = 1 << 29;        // "forced playouts on" (xq_engine_init_fp)
+constexpr int PAD0_GUMBEL = 1 << 28;        // "Gumbel root search on" (xq_engine_init_gz)
+constexpr int PAD0_ARENA = 1 << 27;         // "arena options on" (xq_engine_init_ar)
+constexpr int PAD0_PERPETUAL = 1 << 26;     // "perpetual-check rule on" (xq_engine_init_ru)
+constexpr int PAD0_SOLVER = 1 << 25;        // "proven-result search on" (xq_engine_init_sv)
+constexpr int PAD0_ROOT_STATS = 1 << 24;    // "root statistics per sample on" (xq_engine_init_rs)
 constexpr int PAD0_GAME_RECORDS = 1 << 23;  // "game records on" (xq_engine_init_gr): the top bit of the public flag byte
 constexpr int PAD0_START_POOL = 1 << 22;    // "start-position pool on" (xq_engine_init_sp): the next bit of that byte
 
@@ -89,51 +97,112 @@ struct Dev {
     uint16_t *gr_log;               // xq_engine_init_gr: the move log [G][XQ_RECORD_MAX_PLIES]; NULL without game records (wave-uniform)
 };
 
-// Game records (xq_engine_init_gr): their words are the LAST of the square-root table's region, behind whatever another option
-// keeps there, so the handle finds them from the region that follows (P_MNOISE) without knowing the ring's size:
-//   ring  xq_game_record[max_out_games] | log uint16[G][XQ_RECORD_MAX_PLIES] | opening uint16[G] | GrHead
-// each part rounded up to 256 bytes.  The ring's size is in the head.
-struct GrHead {
+// ---------------------------------------------------------------------------------------------------------
+// THE OPTION WORDS.  The handle, the config struct and the per-slot state words are full, so every option that needs device
+// words keeps them in ONE workspace region, the square-root table's (P_SQRT).  This is the one description of that region:
+// include/xq_hip.h repeats it for callers (xq_engine_option_words_sp fills it in for an engine's shape), and every reader and
+// writer, host or device, takes its addresses from the functions below.  Offsets are bytes from the region's first byte, up()
+// rounds up to 256 (align_up); G slots, S simulations, K leaves per step.
+//   the front, located from the region's first byte
+//     0                  table    double[S + 2 + (K > 1 ? K : 0)]: sqrt(i)                                    every engine
+//     (S + 2) * 8        GzHead | v_hat double[G] | visits uint16[m][S], row k - 1 for k considered moves     Gumbel
+//     up((S + 2) * 8)    ArHead | op_counts int32[G] | op_actions uint16[G][XQ_ARENA_MAX_OPENING] | n_live int32[2] |
+//                        2 x (rows int32[G] | x float[G][XQ_STATE_FLOATS] | moves uint16[G][XQ_MAXM] | counts int32[G]),
+//                        every part up(): set 0 the new model's slots, set 1 the old model's                  arena
+//     up((S + 2) * 8), or the arena words' end:  counters uint64[G][SV_WORDS]                                 solver
+//   the tail, located from the region's end (where P_MNOISE begins); it starts at up(the front's end), every part up()
+//     ring xq_game_record[max_out_games] | log uint16[G][XQ_RECORD_MAX_PLIES] | opening uint16[G] | GrHead   records
+//     rows int8[n][XQ_BS] (a board, its side in byte 90) | start_index int32[G] | SpHead                      pool, never with records
+// Gumbel, arena and solver words start behind a table of S + 2 entries: opts_ok accepts none of them with K > 1, Gumbel with
+// neither of the other two, and tests/test_workspace_map.py holds the blocks of every accepted combination disjoint.  m,
+// max_out_games and n exist only on the device (in the heads), so they are arguments only where an end is asked for: every start
+// follows from cfg, pad0, p[P_SQRT] and p[P_MNOISE].
+// Gumbel root search (xq_engine_init_gz): considered moves at most; c_visit, c_scale rounded to float32 once, widened at every use
+struct GzHead { int32_t m; float c_visit, c_scale; int32_t pad; };
+struct ArHead { int32_t opening_plies, first_game, pad[2]; };       // arena options (xq_engine_init_ar)
+// proven-result search (xq_engine_init_sv): per slot proven_nodes, proven_stops, proven_moves, unspent_sims, removed_visits, 3 spare
+constexpr int SV_WORDS = 8;
+enum Sv : int { SV_NODES = 0, SV_STOPS, SV_MOVES, SV_UNSPENT, SV_REMOVED };
+struct GrHead {                     // game records (xq_engine_init_gr)
     int32_t max_out_games;
-    unsigned int count;                 // games flushed since the last xq_engine_drain_games: the ring's cursor
-    unsigned long long recorded, dropped;
-    unsigned long long pad[29];
+    unsigned int count;             // games flushed since the last xq_engine_drain_games: the ring's cursor
+    unsigned long long recorded, dropped, pad[29];
 };
-static_assert(sizeof(GrHead) == 256, "GrHead layout");
+struct SpHead {                     // start-position pool (xq_engine_init_sp)
+    int32_t n, pad0;
+    double prob;
+    unsigned long long pool_games, pad[29];     // games started from the pool
+};
+// the pool reaches k_start_pool as an argument of its own: every other kernel keeps its arguments.  start_index [G]: the entry the
+// slot's current game started from, or -1
+struct SpDev { int32_t *start_index; SpHead *head; };
+static_assert(sizeof(GzHead) == 16 && sizeof(ArHead) == 16 && sizeof(GrHead) == 256 && sizeof(SpHead) == 256, "the heads' layout");
 static_assert(sizeof(xq_game_record) == XQ_RECORD_BYTES && offsetof(xq_game_record, moves) == 16, "xq_game_record layout");
 
-__host__ __device__ inline size_t gr_align(size_t x) { return (x + 255) & ~(size_t)255; }
-__host__ __device__ inline size_t gr_log_bytes(size_t G) { return gr_align(G * XQ_RECORD_MAX_PLIES * 2); }
-__host__ __device__ inline size_t gr_open_bytes(size_t G) { return gr_align(G * 2); }
-__host__ __device__ inline size_t gr_bytes(size_t G, size_t max_out_games) {
-    return max_out_games * XQ_RECORD_BYTES + gr_log_bytes(G) + gr_open_bytes(G) + sizeof(GrHead);
+__host__ __device__ constexpr size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+__host__ __device__ constexpr size_t ow_max(size_t a, size_t b) { return a > b ? a : b; }
+__host__ __device__ constexpr size_t ow_table_bytes(size_t S, size_t K) { return (S + 2 + (K > 1 ? K : 0)) * 8; }
+__host__ __device__ constexpr size_t ow_gz_head(size_t S) { return ow_table_bytes(S, 1); }
+__host__ __device__ constexpr size_t ow_gz_vhat(size_t S) { return ow_gz_head(S) + sizeof(GzHead); }
+__host__ __device__ constexpr size_t ow_gz_visits(size_t G, size_t S) { return ow_gz_vhat(S) + G * 8; }
+struct ArOff { size_t head, op_counts, op_actions, n_live, rows[2], x[2], moves[2], counts[2], end; };
+__host__ __device__ constexpr ArOff ar_off(size_t G, size_t S) {
+    ArOff a{};
+    size_t o = align_up(ow_table_bytes(S, 1));
+    a.head = o; o = align_up(o + sizeof(ArHead));
+    a.op_counts = o; o = align_up(o + G * 4);
+    a.op_actions = o; o = align_up(o + G * XQ_ARENA_MAX_OPENING * 2);
+    a.n_live = o; o = align_up(o + 2 * 4);
+    for (int m = 0; m < 2; ++m) {
+        a.rows[m] = o; o = align_up(o + G * 4);
+        a.x[m] = o; o = align_up(o + G * XQ_STATE_FLOATS * 4);
+        a.moves[m] = o; o = align_up(o + G * XQ_MAXM * 2);
+        a.counts[m] = o; o = align_up(o + G * 4);
+    }
+    a.end = o;
+    return a;
 }
+__host__ __device__ constexpr size_t sv_off(size_t G, size_t S, bool arena_opts) { return arena_opts ? ar_off(G, S).end : align_up(ow_table_bytes(S, 1)); }
+__host__ __device__ constexpr size_t sv_bytes(size_t G) { return G * SV_WORDS * 8; }
+// the end of the front's last block (m = 0: no Gumbel words), and the region's size (max_out_games = 0: no records, n = 0: no pool)
+__host__ __device__ constexpr size_t ow_front_end(size_t G, size_t S, size_t K, size_t m, bool arena_opts, bool solver) {
+    return ow_max(ow_max(ow_table_bytes(S, K), m ? ow_gz_visits(G, S) + m * S * 2 : 0),
+                  ow_max(arena_opts ? ar_off(G, S).end : 0, solver ? sv_off(G, S, arena_opts) + sv_bytes(G) : 0));
+}
+__host__ __device__ constexpr size_t gr_log_bytes(size_t G) { return align_up(G * XQ_RECORD_MAX_PLIES * 2); }
+__host__ __device__ constexpr size_t gr_open_bytes(size_t G) { return align_up(G * 2); }
+__host__ __device__ constexpr size_t sp_rows_bytes(size_t n) { return align_up(n * XQ_BS); }
+__host__ __device__ constexpr size_t sp_index_bytes(size_t G) { return align_up(G * 4); }
+__host__ __device__ constexpr size_t ow_region_bytes(size_t front_end, size_t G, size_t max_out_games, size_t n) {
+    return max_out_games ? align_up(front_end) + max_out_games * XQ_RECORD_BYTES + gr_log_bytes(G) + gr_open_bytes(G) + sizeof(GrHead)
+           : n           ? align_up(front_end) + sp_rows_bytes(n) + sp_index_bytes(G) + sizeof(SpHead)
+                         : front_end;
+}
+// the tail, from the region's end
+__host__ __device__ constexpr size_t ow_tail_head(size_t end) { return end - 256; }      // GrHead or SpHead
+__host__ __device__ constexpr size_t ow_gr_opening(size_t end, size_t G) { return ow_tail_head(end) - gr_open_bytes(G); }
+__host__ __device__ constexpr size_t ow_gr_log(size_t end, size_t G) { return ow_gr_opening(end, G) - gr_log_bytes(G); }
+__host__ __device__ constexpr size_t ow_gr_ring(size_t end, size_t G, size_t max_out_games) { return ow_gr_log(end, G) - max_out_games * XQ_RECORD_BYTES; }
+__host__ __device__ constexpr size_t ow_sp_index(size_t end, size_t G) { return ow_tail_head(end) - sp_index_bytes(G); }
+__host__ __device__ constexpr size_t ow_sp_rows(size_t end, size_t G, size_t n) { return ow_sp_index(end, G) - sp_rows_bytes(n); }
+
+// The kernels hold one start of the tail (Dev.gr_log, SpDev.start_index) and step from it, and reach the Gumbel words by pointer
+// steps from the table (written through the map's functions, k_select<GUMBEL> schedules differently); every step is the map's.
 __host__ __device__ inline uint16_t *gr_opening(uint16_t *log, size_t G) { return (uint16_t *)((char *)log + gr_log_bytes(G)); }
 __host__ __device__ inline GrHead *gr_head(uint16_t *log, size_t G) { return (GrHead *)((char *)log + gr_log_bytes(G) + gr_open_bytes(G)); }
 __host__ __device__ inline xq_game_record *gr_ring(uint16_t *log, size_t max_out_games) { return (xq_game_record *)log - max_out_games; }
-
-// Start-position pool (xq_engine_init_sp; never with game records, so these words are the LAST of the square-root table's region
-// instead, found from the region that follows the same way):
-//   rows int8[n][XQ_BS] (a board, its side to move in byte 90) | start_index int32[G] | SpHead
-// each part rounded up to 256 bytes.  The pool's size is in the head.  The pool reaches k_start_pool as an argument of its own
-// (SpDev), not through Dev: every other kernel keeps its arguments.
-struct SpHead {
-    int32_t n, pad0;
-    double prob;
-    unsigned long long pool_games;      // games started from the pool
-    unsigned long long pad[29];
-};
-static_assert(sizeof(SpHead) == 256, "SpHead layout");
-
-struct SpDev {
-    int32_t *start_index;               // [G] the entry the slot's current game started from, or -1
-    SpHead *head;
-};
-
-__host__ __device__ inline size_t sp_rows_bytes(size_t n) { return gr_align(n * XQ_BS); }
-__host__ __device__ inline size_t sp_index_bytes(size_t G) { return gr_align(G * 4); }
-__host__ __device__ inline size_t sp_bytes(size_t G, size_t n) { return sp_rows_bytes(n) + sp_index_bytes(G) + sizeof(SpHead); }
 __host__ __device__ inline int8_t *sp_rows(int32_t *start_index, size_t n) { return (int8_t *)start_index - sp_rows_bytes(n); }
+__device__ __forceinline__ const GzHead *gz_head(const Dev &E) { return (const GzHead *)(E.sqrt_tab + E.cfg.num_simulations + 2); }
+__device__ __forceinline__ double *gz_vhat(const Dev &E) { return (double *)(gz_head(E) + 1); }
+__device__ __forceinline__ const uint16_t *gz_table(const Dev &E) { return (const uint16_t *)(gz_vhat(E) + E.cfg.n_games); }
+static_assert(ow_gr_log(1 << 20, 5) + gr_log_bytes(5) == ow_gr_opening(1 << 20, 5) &&
+              ow_gr_log(1 << 20, 200) + gr_log_bytes(200) + gr_open_bytes(200) == ow_tail_head(1 << 20) &&
+              ow_gr_log(1 << 20, 5) - 3 * sizeof(xq_game_record) == ow_gr_ring(1 << 20, 5, 3) &&
+              ow_sp_index(1 << 20, 5) - sp_rows_bytes(3) == ow_sp_rows(1 << 20, 5, 3), "gr_opening, gr_head, gr_ring, sp_rows step as the map does");
+static_assert(ow_gz_head(800) == (800 + 2) * sizeof(double) && ow_gz_vhat(7) == ow_gz_head(7) + 1 * sizeof(GzHead) &&
+              ow_gz_visits(5, 7) == ow_gz_vhat(7) + 5 * sizeof(double), "gz_head, gz_vhat, gz_table step as the map does");
+char *ow_base(const xq_engine *e) { return (char *)e->p[P_SQRT]; }
+size_t ow_end(const xq_engine *e) { return (size_t)((char *)e->p[P_MNOISE] - (char *)e->p[P_SQRT]); }    // the region, from the handle
 
 Dev make_dev(const xq_engine *e) {
     Dev d;
@@ -150,79 +219,10 @@ Dev make_dev(const xq_engine *e) {
     d.sqrt_tab = (const double *)e->p[P_SQRT]; d.mnoise = (double *)e->p[P_MNOISE]; d.req = (int32_t *)e->p[P_REQ];
     d.perpetual = (e->pad0 & PAD0_PERPETUAL) != 0;
     d.root_stats = (e->pad0 & PAD0_ROOT_STATS) != 0;
-    d.gr_log = (e->pad0 & PAD0_GAME_RECORDS)
-                   ? (uint16_t *)((char *)e->p[P_MNOISE] - sizeof(GrHead) - gr_open_bytes((size_t)e->cfg.n_games) - gr_log_bytes((size_t)e->cfg.n_games))
-                   : nullptr;
+    d.gr_log = (e->pad0 & PAD0_GAME_RECORDS) ? (uint16_t *)(ow_base(e) + ow_gr_log(ow_end(e), (size_t)e->cfg.n_games)) : nullptr;
     return d;
 }
 
-// Gumbel root search (xq_engine_init_gz): its words live behind the square-root table, in that table's workspace region (the handle,
-// the config struct and the per-slot state words are full): the parameters, the root's network value of every slot, and the
-// considered-visit tables, row k - 1 for k considered moves.  K = 1 always, so the square-root table has S + 2 entries.
-struct GzHead {
-    int32_t m;                      // considered moves at most
-    float c_visit, c_scale;         // rounded to float32 once, widened at every use
-    int32_t pad;
-};
-static_assert(sizeof(GzHead) == 16, "GzHead layout");
-
-size_t gz_bytes(size_t G, size_t S, size_t m) { return sizeof(GzHead) + G * 8 + m * S * 2; }
-
-__device__ __forceinline__ const GzHead *gz_head(const Dev &E) { return (const GzHead *)(E.sqrt_tab + E.cfg.num_simulations + 2); }
-__device__ __forceinline__ double *gz_vhat(const Dev &E) { return (double *)(gz_head(E) + 1); }
-__device__ __forceinline__ const uint16_t *gz_table(const Dev &E) { return (const uint16_t *)(gz_vhat(E) + E.cfg.n_games); }
-
-// Arena options (xq_engine_init_ar; manual_moves = 2, so never a Gumbel engine): their words lie behind the square-root table as
-// well, from the next 256-byte boundary on: the parameters, what every slot played as its opening, and the two buffer sets of the
-// per-model packed step (set 0: the new model's slots, set 1: the old model's).  Offsets from the table's first byte.
-struct ArHead {
-    int32_t opening_plies, first_game, pad[2];
-};
-static_assert(sizeof(ArHead) == 16, "ArHead layout");
-
-struct ArOff {
-    size_t head, op_counts, op_actions, n_live, rows[2], x[2], moves[2], counts[2], end;
-};
-
-__host__ __device__ inline size_t ar_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-__host__ __device__ inline ArOff ar_off(size_t G, size_t S) {
-    ArOff a;
-    size_t o = ar_align((S + 2) * 8);
-    a.head = o; o = ar_align(o + sizeof(ArHead));
-    a.op_counts = o; o = ar_align(o + G * 4);
-    a.op_actions = o; o = ar_align(o + G * XQ_ARENA_MAX_OPENING * 2);
-    a.n_live = o; o = ar_align(o + 2 * 4);
-    for (int m = 0; m < 2; ++m) {
-        a.rows[m] = o; o = ar_align(o + G * 4);
-        a.x[m] = o; o = ar_align(o + G * XQ_STATE_FLOATS * 4);
-        a.moves[m] = o; o = ar_align(o + G * XQ_MAXM * 2);
-        a.counts[m] = o; o = ar_align(o + G * 4);
-    }
-    a.end = o;
-    return a;
-}
-
-// Proven-result search (xq_engine_init_sv): its counters lie behind the square-root table too -- never a Gumbel engine, K = 1 --
-// from the next 256-byte boundary behind the table, or behind the arena words of an engine with arena options: SV_WORDS uint64
-// per slot (proven_nodes, proven_stops, proven_moves, unspent_sims, removed_visits, 3 spare).  Only solver engines grow.
-constexpr int SV_WORDS = 8;
-enum Sv : int { SV_NODES = 0, SV_STOPS, SV_MOVES, SV_UNSPENT, SV_REMOVED };
-__host__ __device__ inline size_t sv_off(size_t G, size_t S, bool arena_opts) { return arena_opts ? ar_off(G, S).end : ar_align((S + 2) * 8); }
-__host__ __device__ inline size_t sv_bytes(size_t G) { return G * SV_WORDS * 8; }
-
-// pad0 of an engine handle: leaves per step in the low 16 bits (0 = 1), the XQ_ENGINE_* flags above them, and above the public
-// flag bits "playout cap on" (xq_engine_init_cap), "forced playouts on" (xq_engine_init_fp) and "Gumbel root search on"
-// (xq_engine_init_gz), "arena options on" (xq_engine_init_ar), "perpetual-check rule on" (xq_engine_init_ru), "proven-result
-// search on" (xq_engine_init_sv), "root statistics per sample on" (xq_engine_init_rs, PAD0_ROOT_STATS above) and, in bit 31,
-// "evaluation mirror on" (xq_engine_init_em, PAD0_EVAL_MIRROR above).  Bits 24-31 are now all taken; of the public flag byte
-// (bits 16-23) bit 16 is, bit 23 says "game records on" (xq_engine_init_gr, PAD0_GAME_RECORDS above) and bit 22 "start-position
-// pool on" (xq_engine_init_sp, PAD0_START_POOL above): flags_ok lets no caller's flag reach either.
-constexpr int PAD0_CAP = 1 << 30;
-constexpr int PAD0_FORCED = 1 << 29;
-constexpr int PAD0_GUMBEL = 1 << 28;
-constexpr int PAD0_ARENA = 1 << 27;
-constexpr int PAD0_SOLVER = 1 << 25;
 int leaves_of(const xq_engine *e) { return (e->pad0 & 0xFFFF) > 1 ? (e->pad0 & 0xFFFF) : 1; }
 bool reuse_of(const xq_engine *e) { return ((unsigned)e->pad0 >> 16) & XQ_ENGINE_TREE_REUSE; }
 bool cap_of(const xq_engine *e) { return (e->pad0 & PAD0_CAP) != 0; }
@@ -234,8 +234,8 @@ bool records_of(const xq_engine *e) { return e && (e->pad0 & PAD0_GAME_RECORDS) 
 bool pool_of(const xq_engine *e) { return e && (e->pad0 & PAD0_START_POOL) != 0 && e->cfg.n_games > 0 && e->p[P_MNOISE]; }
 SpDev make_sp(const xq_engine *e) {
     SpDev p;
-    p.head = (SpHead *)((char *)e->p[P_MNOISE] - sizeof(SpHead));
-    p.start_index = (int32_t *)((char *)p.head - sp_index_bytes((size_t)e->cfg.n_games));
+    p.head = (SpHead *)(ow_base(e) + ow_tail_head(ow_end(e)));
+    p.start_index = (int32_t *)(ow_base(e) + ow_sp_index(ow_end(e), (size_t)e->cfg.n_games));
     return p;
 }
 bool arena_of(const xq_engine *e) { return e && (e->pad0 & PAD0_ARENA) != 0 && e->cfg.n_games > 0 && e->p[P_SQRT]; }
@@ -310,7 +310,5 @@ __device__ __forceinline__ void block_compact(const Dev &E, int R, Live live, in
         E.stats[ST_ROWS] += (unsigned long long)total;   // slot 0's counter row: k_reduce_stats sums the column
     }
 }
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace

@@ -143,6 +143,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import math
 from typing import Callable, Optional
 
 import numpy as np
@@ -522,6 +523,8 @@ class SelfPlayEngine:
         if nbytes == 0:
             raise hip.XqError("invalid engine configuration")
         self.workspace_bytes = int(nbytes)
+        self._words = hip.OptionWords()                # where the options' device words lie behind the square-root table
+        hip.check(self.lib.xq_engine_option_words_sp(C.byref(cfg), K, flags, *refs, C.byref(self._words)), "xq_engine_option_words_sp")
         self.ws = torch.empty(self.workspace_bytes + 256, dtype=torch.uint8, device=self.device)
         base = (self.ws.data_ptr() + 255) & ~255
         self._inject = None
@@ -540,48 +543,38 @@ class SelfPlayEngine:
         if sp is not None:                             # init copied the pool into the workspace: pb and ps may go
             pi = C.c_void_p()
             hip.check(self.lib.xq_engine_start_indices(C.byref(self.h), C.byref(pi)), "xq_engine_start_indices")
-            off = int(pi.value) - int(self.ws.data_ptr())
-            self._start_index = self.ws[off:off + self.G * 4].view(torch.int32)
+            self._start_index = self._ws_view(pi.value, self.G, torch.int32)
         # zero-copy int32 view of the per-slot state words (columns hip.GI_*: side to move of the REAL game, move_count, phase,
         # simulations done): host-side policies such as the arena's model choice read it between stages
-        gi_off = int(self.h.p[hip.P_GI]) - int(self.ws.data_ptr())
-        self.slot_ints = self.ws[gi_off:gi_off + self.G * 32 * 4].view(torch.int32).view(self.G, 32)
+        self.slot_ints = self._ws_view(self.h.p[hip.P_GI], (self.G, 32), torch.int32)
         # sparse hand-off to the evaluator (xq_engine_requests): ordered legal moves + their number per pending evaluation
         pm, pc = C.c_void_p(), C.c_void_p()
         hip.check(self.lib.xq_engine_requests(C.byref(self.h), C.byref(pm), C.byref(pc)), "xq_engine_requests")
-        mo, co = int(pm.value) - int(self.ws.data_ptr()), int(pc.value) - int(self.ws.data_ptr())
-        self.req_moves = self.ws[mo:mo + self.rows * hip.MAXM * 2].view(torch.int16).view(self.rows, hip.MAXM)
-        self.req_counts = self.ws[co:co + self.rows * 4].view(torch.int32)
+        self.req_moves = self._ws_view(pm.value, (self.rows, hip.MAXM), torch.int16)
+        self.req_counts = self._ws_view(pc.value, self.rows, torch.int32)
         # packed-step buffers (xq_engine_packed): live count, row -> slot map, packed planes / requests, slot-ordered hand-back
         pb = hip.PackedBuffers()
         hip.check(self.lib.xq_engine_packed(C.byref(self.h), C.byref(pb)), "xq_engine_packed")
-
-        def ws_view(addr, nbytes, dtype):
-            off = int(addr) - int(self.ws.data_ptr())
-            return self.ws[off:off + nbytes].view(dtype)
-
-        G = self.rows                                  # packed buffers hold request rows (= slots when K = 1)
-        self.n_live = ws_view(pb.n_live, 4, torch.int32)
-        self.packed_rows = ws_view(pb.rows, G * 4, torch.int32)
-        self.packed_x = ws_view(pb.x, G * hip.STATE_FLOATS * 4, torch.float32).view(G, 15, 10, 9)
-        self.packed_moves = ws_view(pb.moves, G * hip.MAXM * 2, torch.int16).view(G, hip.MAXM)
-        self.packed_counts = ws_view(pb.counts, G * 4, torch.int32)
-        self.slot_logits = ws_view(pb.slot_logits, G * hip.MAXM * 4, torch.float32).view(G, hip.MAXM)
-        self.slot_value = ws_view(pb.slot_value, G * 4, torch.float32)
+        G, view = self.rows, self._ws_view              # packed buffers hold request rows (= slots when K = 1)
+        self.n_live = view(pb.n_live, 1, torch.int32)
+        self.packed_rows = view(pb.rows, G, torch.int32)
+        self.packed_x = view(pb.x, (G, 15, 10, 9), torch.float32)
+        self.packed_moves = view(pb.moves, (G, hip.MAXM), torch.int16)
+        self.packed_counts = view(pb.counts, G, torch.int32)
+        self.slot_logits = view(pb.slot_logits, (G, hip.MAXM), torch.float32)
+        self.slot_value = view(pb.slot_value, G, torch.float32)
         self.arena_packed = None
         if ar is not None:
             # the per-model packed step's two buffer sets (xq_engine_packed_arena) and the openings record
             pbs = (hip.PackedBuffers * 2)()
             hip.check(self.lib.xq_engine_packed_arena(C.byref(self.h), pbs), "xq_engine_packed_arena")
             self.arena_packed = tuple(dict(
-                n_live=ws_view(b.n_live, 4, torch.int32), rows=ws_view(b.rows, G * 4, torch.int32),
-                x=ws_view(b.x, G * hip.STATE_FLOATS * 4, torch.float32).view(G, 15, 10, 9),
-                moves=ws_view(b.moves, G * hip.MAXM * 2, torch.int16).view(G, hip.MAXM),
-                counts=ws_view(b.counts, G * 4, torch.int32)) for b in pbs)
+                n_live=view(b.n_live, 1, torch.int32), rows=view(b.rows, G, torch.int32), x=view(b.x, (G, 15, 10, 9), torch.float32),
+                moves=view(b.moves, (G, hip.MAXM), torch.int16), counts=view(b.counts, G, torch.int32)) for b in pbs)
             pa, pc = C.c_void_p(), C.c_void_p()
             hip.check(self.lib.xq_engine_arena_openings(C.byref(self.h), C.byref(pa), C.byref(pc)), "xq_engine_arena_openings")
-            self._opening_actions = ws_view(pa.value, G * hip.ARENA_MAX_OPENING * 2, torch.int16).view(G, hip.ARENA_MAX_OPENING)
-            self._opening_counts = ws_view(pc.value, G * 4, torch.int32)
+            self._opening_actions = view(pa.value, (G, hip.ARENA_MAX_OPENING), torch.int16)
+            self._opening_counts = view(pc.value, G, torch.int32)
         self.cache = None
         if eval_cache_entries:
             self._init_cache(int(eval_cache_entries))
@@ -989,6 +982,17 @@ class SelfPlayEngine:
                       "xq_engine_drain_games_device")
         return rec[:n.value]
 
+    def _ws_view(self, addr, shape, dtype) -> torch.Tensor:
+        """Zero-copy view of the workspace from device address `addr` on: `shape` (an int or a tuple) elements of `dtype`."""
+        shape = (shape,) if isinstance(shape, int) else tuple(shape)
+        off = int(addr) - int(self.ws.data_ptr())
+        nbytes = math.prod(shape) * torch.empty(0, dtype=dtype).element_size()
+        return self.ws[off:off + nbytes].view(dtype).view(shape)
+
+    def _words_view(self, block, shape, dtype) -> torch.Tensor:
+        """_ws_view of one block of the option words (hip.OptionWords), which lie in the square-root table's region."""
+        return self._ws_view(int(self.h.p[hip.P_SQRT]) + int(block.offset), shape, dtype)
+
     def game_records_stats(self) -> dict:
         """recorded: games whose record found a row of the ring; dropped: games that finished on a full ring."""
         if not self.record_games:
@@ -1015,35 +1019,24 @@ class SelfPlayEngine:
         return dict(pool_games=int(s.pool_games))
 
     def game_record_views(self) -> dict:
-        """Zero-copy views of the game records' words in the workspace (csrc/xq_engine_state.cuh: the last words of the square-root
-        table's region, in front of P_MNOISE): `ring` int16 [max_out_games, 512] (uint16 bits: 8 header words, then the moves),
-        `log` int16 [G, 504] (the running games' moves so far) and `opening` int16 [G].  For tests and tools."""
+        """Zero-copy views of the game records' words in the workspace (the tail of the option words, include/xq_hip.h): `ring`
+        int16 [max_out_games, 512] (uint16 bits: 8 header words, then the moves), `log` int16 [G, 504] (the running games' moves
+        so far) and `opening` int16 [G].  For tests and tools."""
         if not self.record_games:
             raise hip.XqError("game_record_views needs an engine with record_games=True")
-
-        def up(n):
-            return (n + 255) & ~255
-
-        G, M = self.G, self.max_out_games
-        head = int(self.h.p[hip.P_MNOISE]) - int(self.ws.data_ptr()) - 256
-        opening = head - up(G * 2)
-        log = opening - up(G * hip.RECORD_MAX_PLIES * 2)
-        ring = log - M * hip.RECORD_BYTES
-        return dict(ring=self.ws[ring:ring + M * hip.RECORD_BYTES].view(torch.int16).view(M, hip.RECORD_BYTES // 2),
-                    log=self.ws[log:log + G * hip.RECORD_MAX_PLIES * 2].view(torch.int16).view(G, hip.RECORD_MAX_PLIES),
-                    opening=self.ws[opening:opening + G * 2].view(torch.int16))
+        w = self._words
+        return dict(ring=self._words_view(w.gr_ring, (self.max_out_games, hip.RECORD_BYTES // 2), torch.int16),
+                    log=self._words_view(w.gr_log, (self.G, hip.RECORD_MAX_PLIES), torch.int16),
+                    opening=self._words_view(w.gr_opening, self.G, torch.int16))
 
     def arena_views(self) -> dict:
         """Zero-copy torch views of the SoA tree arenas in the workspace, [G, node_cap] each:
         N int32, W float64, P float32, action int16 (uint16 bits), first int32 (first child, -1 = none), meta int16
         (uint16 bits: child count, mask hip.META_COUNT_MASK | proven state << 12 (solver=True only) | kind << 14), plus the root boards int8 [G, 96] (90 squares + pad).  For inspection and tests."""
-        base = int(self.ws.data_ptr())
         cap = int(self.h.node_cap)
 
         def view(idx, dtype, cols):
-            off = int(self.h.p[idx]) - base
-            nbytes = self.G * cols * torch.empty(0, dtype=dtype).element_size()
-            return self.ws[off:off + nbytes].view(dtype).view(self.G, cols)
+            return self._ws_view(self.h.p[idx], (self.G, cols), dtype)
 
         out = dict(N=view(hip.P_TN, torch.int32, cap), W=view(hip.P_TW, torch.float64, cap), P=view(hip.P_TP, torch.float32, cap),
                    action=view(hip.P_TA, torch.int16, cap), first=view(hip.P_TC, torch.int32, cap),
@@ -1057,16 +1050,14 @@ class SelfPlayEngine:
         pending leaves handed out, 21: slot-steps that handed leaves, 22: reused visits, 23: re-rooted searches, 24: fast moves,
         25: simulations of fast searches, 26: forced simulations, 27: pruned visits, 28: pruned children, 29: Gumbel moves, 30: the sum
         of their considered moves, 31: Gumbel moves off the prior's first maximum).  For tests."""
-        off = int(self.h.p[hip.P_STATS]) - int(self.ws.data_ptr())
-        return self.ws[off:off + self.G * 32 * 8].view(torch.int64).view(self.G, 32)
+        return self._ws_view(self.h.p[hip.P_STATS], (self.G, 32), torch.int64)
 
     def gumbel_root_values(self) -> torch.Tensor:
         """Gumbel engines: zero-copy float64 [G] view of v_hat, the root's network value every slot keeps for the end of its
-        move (behind the square-root table and the 16 bytes of parameters, include/xq_hip.h).  For tools and tests."""
+        move (gz_vhat of the option words, include/xq_hip.h).  For tools and tests."""
         if self.gumbel is None:
             raise hip.XqError("gumbel_root_values needs an engine with gumbel=")
-        off = int(self.h.p[hip.P_SQRT]) - int(self.ws.data_ptr()) + (int(self.cfg.num_simulations) + 2) * 8 + 16
-        return self.ws[off:off + self.G * 8].view(torch.float64)
+        return self._words_view(self._words.gz_vhat, self.G, torch.float64)
 
     def held(self) -> bool:
         """Search-only engines: every slot holds its finished search (phase HOLD).  Synchronises."""

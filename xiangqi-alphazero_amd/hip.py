@@ -86,8 +86,7 @@ P_TN, P_TW, P_TP, P_TA, P_TC, P_TM = 6, 7, 8, 9, 10, 11   # mirror P_TN .. P_TM 
 P_ROOTP = 12       # mirrors P_ROOTP of enum Ptr: the float64 root priors
 P_OUTS, P_OUTR = 14, 15   # mirror P_OUTS, P_OUTR of enum Ptr: the sample ring and the result ring that the drains read
 P_STATS = 17       # mirrors P_STATS of enum Ptr: the per-slot counters
-P_SQRT = 19        # mirrors P_SQRT of enum Ptr: the square-root table and the Gumbel / arena words behind it
-P_MNOISE = 20      # mirrors P_MNOISE of enum Ptr: the injected-noise table; the game records' words end where it begins
+P_SQRT = 19        # mirrors P_SQRT of enum Ptr: the square-root table's region, which holds every option's words (OptionWords)
 P_VL = 30          # mirrors P_VL of enum Ptr: the virtual-loss counters (leaves_per_step > 1)
 GI_SIDE = 0        # mirrors GI_SIDE of enum Gi in csrc/xq_engine_state.cuh: side to move of the real game
 GI_MC = 1          # mirrors GI_MC of enum Gi: its move count
@@ -178,6 +177,21 @@ class StartPool(C.Structure):
 class StartPoolStats(C.Structure):
     """xq_start_pool_stats: games started from the pool (xq_engine_start_pool_stats_read)."""
     _fields_ = [("pool_games", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class WordsBlock(C.Structure):
+    """xq_words_block: a block of the option words, offset from the region's first byte; bytes = 0: the engine has no such block."""
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class OptionWords(C.Structure):
+    """xq_option_words: where every option's device words lie in the square-root table's region (xq_engine_option_words_sp;
+    include/xq_hip.h: THE OPTION WORDS)."""
+    _fields_ = [("bytes", C.c_uint64)] + \
+               [(n, WordsBlock) for n in ("table", "gz_head", "gz_vhat", "gz_visits", "ar_head", "ar_op_counts", "ar_op_actions",
+                                          "ar_n_live")] + \
+               [(n, WordsBlock * 2) for n in ("ar_rows", "ar_x", "ar_moves", "ar_counts")] + \
+               [(n, WordsBlock) for n in ("solver", "gr_ring", "gr_log", "gr_opening", "gr_head", "sp_rows", "sp_index", "sp_head")]
 
 
 class GameRecord(C.Structure):
@@ -365,6 +379,7 @@ def lib():
     L.xq_engine_workspace_bytes_sp.argtypes = L.xq_engine_workspace_bytes_gr.argtypes + [C.POINTER(StartPool)]
     L.xq_engine_workspace_bytes_sp.restype = C.c_size_t
     L.xq_engine_init_sp.argtypes = L.xq_engine_init_gr.argtypes[:13] + [C.POINTER(StartPool)] + L.xq_engine_init_gr.argtypes[13:]
+    L.xq_engine_option_words_sp.argtypes = L.xq_engine_workspace_bytes_sp.argtypes + [C.POINTER(OptionWords)]
     L.xq_positions_check_batch.argtypes = [vp, vp, i32, vp, vp]
     L.xq_start_pool_draw_host.argtypes = [C.c_uint64, i32, i32, C.c_uint32, i32, C.c_double]
     L.xq_engine_start_indices.argtypes = [C.POINTER(Engine), C.POINTER(vp)]
@@ -503,7 +518,7 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_alphabeta_batch", "xq_records_sample_counts", "xq_records_to_samples", "xq_mate_search_batch",
            "xq_tb_entries", "xq_tb_init", "xq_tb_pass", "xq_tb_probe_batch", "xq_tb_play_batch", "xq_tb_samples",
            "xq_positions_check_batch", "xq_engine_workspace_bytes_sp", "xq_engine_init_sp", "xq_start_pool_draw_host",
-           "xq_engine_start_indices", "xq_engine_start_pool_stats_read", "xq_evdedup_bytes", "xq_evdedup_init",
+           "xq_engine_start_indices", "xq_engine_start_pool_stats_read", "xq_engine_option_words_sp", "xq_evdedup_bytes", "xq_evdedup_init",
            "xq_engine_compact_unique", "xq_engine_expand_dedup", "xq_evdedup_stats_read", "xq_evdedup_bucket_host",
            "xq_dedup_rows_batch", "xq_engine_settle", "xq_tb_adjudicate_batch", "xq_engine_adjudicate"]
 
