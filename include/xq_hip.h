@@ -1668,6 +1668,74 @@ int xq_tb_adjudicate_batch(const int8_t *pieces, int n_pieces, const int16_t *de
 int xq_engine_adjudicate(const xq_engine *eng, const int8_t *pieces, int n_pieces, const int16_t *dev_table, int64_t entries,
                          const xq_adjudicate_opts *opts, unsigned long long *dev_counters /* [n_games][4] */, void *stream);
 
+/* Per-side resign rule with a no-resign holdout (opt-in).  The engine's own rule (enable_resign; the reference's) asks that the
+ * last resign_check_steps root values, each seen from its own side to move, all lie below the threshold: for K >= 2 both sides
+ * must judge themselves lost on neighbouring plies.  That rule stays as it is.  This option reads the same values per side.
+ * THE RULE (one device function for both calls).  v_0, v_1, .. are a game's root values in the order the engine records them: one
+ * per real position once the game has more than 10 samples, written into the slot's ring of 16 doubles (a float32 widened) and
+ * counted per game.  The sides to move alternate.  With K = check_steps, 1 <= K <= XQ_RESIGN_MAX_STEPS,
+ *     w_n = max(v_n, v_{n-2}, .., v_{n-2(K-1)})      the K latest values of the side to move at n; defined for n >= 2(K-1); a
+ *                                                    window that holds a NaN is NaN.  2K - 1 <= 15: the ring holds every window.
+ *   level       level[s] is the minimum of w_n over the positions where s was to move ([0] red, [1] black), +inf while there is
+ *               none; level_ply[s] is the game ply where that minimum was FIRST reached (strict <; a NaN window lowers nothing).
+ *   resign      a game that is not exempt is resigned by the side to move at the first n with w_n < threshold: strict, the
+ *               recorded double against the double threshold, a NaN never.  The result: winner -side, reason 3.  The position
+ *               gets no sample -- the engine's own rule likewise ends a game before a move is searched there.
+ *   holdout     a game is exempt iff (philox_u64(seed, rank, slot, XQ_RNG_KIND_RESIGN_HOLDOUT, game_seq, 0) >> 11) * 2^-53 <
+ *               holdout_prob: the engine's Philox4x32-10, the start pool's kind of draw; stateless, never injected, repeated on
+ *               the host by xq_resign_exempt_host (1 exempt, 0 not; XQ_ERR_ARG for rank or slot < 0 or a probability outside
+ *               [0, 1]).  An exempt game is never resigned.
+ *   row         when an exempt game finishes, by whatever ending, one xq_resign_row is appended to dev_rows: the row index is
+ *               atomicAdd(dev_row_count, 1); a row at or past max_rows is not written and counts as dropped.  The caller reads
+ *               min(*dev_row_count, max_rows) rows and zeroes the counter between steps.
+ * xq_engine_resign: the engine stage, called once per step ahead of xq_engine_select and on the same stream: behind the previous
+ * step's expand call, which recorded the value and expanded the root, and ahead of the select call's own kernels, which flush a
+ * finished game.  One wavefront per slot, no LDS, no scratch, no workgroup barrier; the row index is the only atomic.  A slot is
+ * looked at when its game number changed (the state is reset), when a new value was recorded, or when it stands finished and is
+ * not yet closed.  A slot that searches, whose new window is below the threshold and whose game is not exempt, gets the three
+ * words a finished game has (winner -side, reason 3, phase finished); the select call that follows flushes the game and counts it
+ * in xq_engine_stats.resigns.  A slot the rules (or a table) ended at this very position stays theirs.
+ * The engine's own rule must be the recorder: cfg.enable_resign = 1 with cfg.resign_threshold = -INFINITY fills the ring and never
+ * fires.  dev_state: caller-owned, zeroed by the caller, xq_resign_state_bytes(n_games) bytes (0 for n_games < 1): per slot the
+ * values seen, the game number, the two levels and plies and a closed mark.  dev_counters: caller-owned, zeroed by the caller,
+ * uint64[n_games][4]; row s is written by slot s's wavefront only -- [0] games resigned, [1] holdout games closed, [2] rows
+ * dropped, [3] values seen.  The caller sums the columns.
+ * xq_resign_scan_batch: the stateless twin over n sequences, one wavefront each: values float[n][max_len], len int32[n] (clamped
+ * to [0, max_len]), first_side int8[n] (1 red, anything else black: the side to move at index 0).  Every output word is written:
+ * resign_index int32[n] (the first n with w_n < threshold, -1 for none), resigner int8[n] (that side, 0 for none), level
+ * float[n][2] and level_index int32[n][2] (the index the level was first reached at, -1 while +inf) over the WHOLE sequence, as for
+ * an exempt game.  n = 0 is a no-op.
+ * XQ_ERR_ARG before any launch (no GPU needed): a null pointer (dev_rows may be NULL with max_rows = 0; the batch call: with n > 0,
+ * dev_values may be NULL with max_len = 0); reserved != 0; check_steps outside 1..XQ_RESIGN_MAX_STEPS; holdout_prob outside [0, 1]
+ * or NaN; a NaN threshold; max_rows < 0 (the batch call: n < 0, max_len < 0); manual_moves != 0 (arena and search-only engines
+ * record no values); an engine whose enable_resign is 0 or whose own resign_threshold is not -INFINITY.  Every other engine option
+ * is accepted: the words an expanded root leaves behind are rewritten by the next root request.  An
+ * engine that is never handed to this call launches exactly what it launched before. */
+#define XQ_RNG_KIND_RESIGN_HOLDOUT 12
+#define XQ_RESIGN_MAX_STEPS 8
+typedef struct xq_resign_opts {
+    double threshold;       /* resign when the window is below this; -INFINITY: nobody resigns */
+    double holdout_prob;    /* the share of games played out, in [0, 1] */
+    int32_t check_steps;    /* K */
+    int32_t reserved;       /* 0 */
+} xq_resign_opts;
+typedef struct xq_resign_row {      /* 32 bytes: one finished exempt game */
+    uint32_t slot, game_seq;
+    float level[2];         /* red, black; +inf: that side never had a full window */
+    uint16_t level_ply[2];  /* the game ply the level was first reached at (0 with +inf) */
+    int8_t winner;          /* as in xq_game_result */
+    uint8_t reason;
+    uint16_t plies;
+    uint32_t zero[2];
+} xq_resign_row;
+size_t xq_resign_state_bytes(int n_games);
+int xq_resign_exempt_host(uint64_t seed, int rank, int slot, uint32_t game_seq, double holdout_prob);
+int xq_resign_scan_batch(const float *dev_values /* [n][max_len] */, const int32_t *dev_len, const int8_t *dev_first_side, int n,
+                         int max_len, int check_steps, double threshold, int32_t *dev_resign_index, int8_t *dev_resigner,
+                         float *dev_level /* [n][2] */, int32_t *dev_level_index /* [n][2] */, void *stream);
+int xq_engine_resign(const xq_engine *eng, const xq_resign_opts *opts, void *dev_state, xq_resign_row *dev_rows, int max_rows,
+                     unsigned int *dev_row_count, unsigned long long *dev_counters /* [n_games][4] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,16 @@ on) ends drawn entries as draws; `min_ply` (default 1) leaves shorter games alon
 still yields the one move that leads to its first adjudicated root (0: it ends at ply 0 with no sample).  The rules' own verdicts
 and, with enable_resign, a resignation at that position come first.  `adjudication_stats()` sums the counters.  One more kernel
 per table per step, in all four step paths, eager and recorded.  Self-play and arena engines, every other option.
+
+With `resign=dict(threshold=, check_steps=, holdout_prob=, max_rows=)` (opt-in; xq_engine_resign) a side
+resigns when its own last `check_steps` root values -- every second recorded value -- all lie below `threshold`; the engine's own
+rule, which asks that of both sides at once, is turned into the recorder of those values (enable_resign with threshold -inf) and
+never fires.  `select()` first runs the public stage `resign_stage()`; a resigned game has `reason` 3 and counts in `resigns`.  A
+share `holdout_prob` of the games, drawn statelessly per (slot, game_seq) (`hip.resign_exempt` repeats the draw), is exempt and
+played out; `drain_resign_rows()` returns, per finished holdout game, the lowest window each side ever had and the result, which
+`resign.false_positive_curve` and `resign.calibrate` turn into a threshold.  `resign_stats()` sums the counters,
+`set_resign_threshold()` plays on under another threshold.  One more kernel per step, in all four step paths, eager and recorded.
+Self-play engines only, every other option.
 """
 from __future__ import annotations
 
@@ -301,6 +311,34 @@ def parse_adjudicate(cfg: hip.EngineConfig, adjudicate):
     if int(cfg.manual_moves) not in (0, 2):
         raise hip.XqError(f"adjudicate: manual_moves must be 0 or 2, got {cfg.manual_moves}")
     return tables, opts
+
+
+RESIGN_KEYS = ("threshold", "check_steps", "holdout_prob", "max_rows")
+
+
+def parse_resign(cfg: hip.EngineConfig, resign):
+    """The `resign=dict(threshold=, check_steps=, holdout_prob=, max_rows=)` argument checked, without a GPU -> (hip.ResignOpts,
+    max_rows), or None.  threshold is required (-inf: nobody resigns); check_steps defaults to 5, holdout_prob to 0.1, max_rows
+    (the holdout rows kept between two drains) to max(1024, 8 n_games).  Every rule of xq_engine_resign's refusal list
+    (include/xq_hip.h) but the engine's own rule as recorder, which `SelfPlayEngine` sets itself."""
+    if resign is None:
+        return None
+    if not isinstance(resign, dict) or not set(resign) <= set(RESIGN_KEYS) or "threshold" not in resign:
+        raise hip.XqError(f"resign must be a dict with threshold and keys from {list(RESIGN_KEYS)}, got {resign!r}")
+    opts = hip.resign_opts(resign["threshold"], resign.get("check_steps", 5), resign.get("holdout_prob", 0.1), what="resign")
+    max_rows = resign.get("max_rows")
+    if max_rows is None:
+        max_rows = max(1024, 8 * int(cfg.n_games))
+    try:
+        ok = not isinstance(max_rows, bool) and int(max_rows) == max_rows and 0 <= int(max_rows) <= 2 ** 31 - 1
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise hip.XqError(f"resign: max_rows must be an integer >= 0, got {max_rows!r}")
+    if int(cfg.manual_moves) != 0:
+        raise hip.XqError("resign is a self-play option: not available with manual_moves = 1 (search only) or 2 (arena), whose "
+                          "engines record no root values")
+    return opts, int(max_rows)
 
 
 def parse_engine_options(cfg: hip.EngineConfig, *, leaves_per_step: int = 1, tree_reuse: bool = False, playout_cap=None,
@@ -468,7 +506,12 @@ class SelfPlayEngine:
                  tree_reuse: bool = False, playout_cap=None, forced_playouts=None, gumbel=None, arena_opts=None,
                  perpetual_check: bool = False, solver: bool = False, root_stats: bool = False, eval_mirror: bool = False,
                  record_games: bool = False, max_out_games=None, start_pool=None, eval_dedup: bool = False,
-                 early_stop: bool = False, adjudicate=None):
+                 early_stop: bool = False, adjudicate=None, resign=None):
+        rsn = parse_resign(cfg, resign)
+        if rsn is not None:
+            # the engine's own rule becomes the recorder of the root values: it fills the ring and never fires
+            cfg = hip.EngineConfig.from_buffer_copy(cfg)
+            cfg.enable_resign, cfg.resign_threshold = 1, float("-inf")
         opts = parse_engine_options(
             cfg, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap, forced_playouts=forced_playouts,
             gumbel=gumbel, arena_opts=arena_opts, eval_cache_entries=eval_cache_entries, perpetual_check=perpetual_check,
@@ -594,6 +637,17 @@ class SelfPlayEngine:
                 tabs.append((tb.codes, t))
             self.adjudicate_tables, self._adjudicate_opts = tuple(tabs), adj[1]
             self._adjudicate_counters = torch.zeros((self.G, 4), dtype=torch.int64, device=self.device)
+        # per-side resign rule: xq_engine_resign's options, per-slot state, holdout rows with their counter, and counters, one row
+        # per slot (games resigned, holdout games closed, rows dropped, values seen)
+        self.resign = None
+        if rsn is not None:
+            self._resign_opts, self._resign_max_rows = rsn
+            self.resign = dict(threshold=float(rsn[0].threshold), check_steps=int(rsn[0].check_steps),
+                               holdout_prob=float(rsn[0].holdout_prob), max_rows=int(rsn[1]))
+            self._resign_state = torch.zeros(int(self.lib.xq_resign_state_bytes(self.G)), dtype=torch.uint8, device=self.device)
+            self._resign_rows = torch.zeros((max(1, rsn[1]), hip.RESIGN_ROW_BYTES), dtype=torch.uint8, device=self.device)
+            self._resign_row_count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._resign_counters = torch.zeros((self.G, 4), dtype=torch.int64, device=self.device)
         self._reuse_seen = (self.evaluator, getattr(self.evaluator, "weights_version", 0))
         self.steps = 0
         self._graph = None
@@ -646,6 +700,8 @@ class SelfPlayEngine:
         if self.early_stop:                            # ahead of the select kernel, which ends the settled arena searches
             hip.check(self.lib.xq_engine_settle(C.byref(self.h), self._settle_counters.data_ptr(), hip.stream_ptr(self.device)),
                       "xq_engine_settle")
+        if self.resign is not None:                    # behind the last expand kernel, ahead of the kernels that flush a finished game
+            self.resign_stage()
         hip.check(self.lib.xq_engine_select(C.byref(self.h), self.nn_input.data_ptr(), hip.stream_ptr(self.device)),
                   "xq_engine_select")
         if self.adjudicate_tables is not None:         # behind the select kernel's root requests, ahead of every expand kernel
@@ -660,6 +716,25 @@ class SelfPlayEngine:
             raise hip.XqError("adjudicate needs an engine with adjudicate=")
         for codes, table in self.adjudicate_tables:
             hip.engine_adjudicate(self.h, codes, table, self._adjudicate_opts, self._adjudicate_counters)
+
+    def resign_stage(self):
+        """Ahead of `select`: update every slot's levels from the root value the last expand call recorded, end the games the
+        per-side rule resigns and write the row of every finished holdout game (xq_engine_resign).  `select()` calls it; public
+        for callers that drive the stages themselves.  Asynchronous."""
+        if self.resign is None:
+            raise hip.XqError("resign_stage needs an engine with resign=")
+        hip.check(self.lib.xq_engine_resign(C.byref(self.h), C.byref(self._resign_opts), self._resign_state.data_ptr(),
+                                            self._resign_rows.data_ptr(), self._resign_max_rows, self._resign_row_count.data_ptr(),
+                                            self._resign_counters.data_ptr(), hip.stream_ptr(self.device)), "xq_engine_resign")
+
+    def set_resign_threshold(self, threshold: float):
+        """Play on under another threshold (a calibrated one): a kernel argument, so a recorded step is released."""
+        if self.resign is None:
+            raise hip.XqError("set_resign_threshold needs an engine with resign=")
+        self._resign_opts = hip.resign_opts(threshold, self.resign["check_steps"], self.resign["holdout_prob"], what="resign")
+        self.resign["threshold"] = float(self._resign_opts.threshold)
+        if self._graph is not None:
+            self.release_graph()
 
     def expand(self, policy: torch.Tensor, value: torch.Tensor, is_probs: bool = False):
         if policy.dtype != torch.float32 or value.dtype != torch.float32:
@@ -906,6 +981,25 @@ class SelfPlayEngine:
         s = self._adjudicate_counters.sum(dim=0).cpu()
         return dict(adjudicated_decisive=int(s[0]), adjudicated_drawn=int(s[1]), adjudicated_left_alone=int(s[2]),
                     adjudicated_swapped=int(s[3]))
+
+    def resign_stats(self) -> dict:
+        """The per-side resign rule's counters: resigned (games it ended), holdout_games (exempt games that finished),
+        rows_dropped (their rows that found the row array full) and values_seen, with the threshold in use.  Synchronises."""
+        if self.resign is None:
+            raise hip.XqError("resign_stats needs an engine with resign=")
+        s = self._resign_counters.sum(dim=0).cpu()
+        return dict(resigned=int(s[0]), holdout_games=int(s[1]), rows_dropped=int(s[2]), values_seen=int(s[3]),
+                    threshold=self.resign["threshold"])
+
+    def drain_resign_rows(self) -> np.ndarray:
+        """-> the rows of the holdout games finished since the last call (sample_format.RESIGN_ROW_DTYPE, sorted by slot and
+        game_seq, at most max_rows); empties the row array.  Synchronises; call it between steps."""
+        if self.resign is None:
+            raise hip.XqError("drain_resign_rows needs an engine with resign=")
+        n = min(int(self._resign_row_count.item()), self._resign_max_rows)
+        rows = self._resign_rows[:n].cpu().numpy().reshape(-1).view(hip.RESIGN_ROW_DTYPE).copy()
+        self._resign_row_count.zero_()
+        return rows[np.lexsort((rows["game_seq"], rows["slot"]))]
 
     def solver_stats(self) -> dict:
         """The proven-result search's counters (xq_engine_solver_stats_read): proven_nodes, proven_stops, proven_moves,

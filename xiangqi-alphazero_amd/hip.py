@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("XQ_HIP_LIB", os.path.join(_HERE, "libxq_hip.so"))   #
 CSRC = os.path.join(_HERE, "csrc")
 
 # numpy only: the records' layouts live with the other formats
-from .sample_format import GAME_RECORD_DTYPE, POLICY_STATS_DTYPE, SCORE_DTYPE  # noqa: E402,F401
+from .sample_format import GAME_RECORD_DTYPE, POLICY_STATS_DTYPE, RESIGN_ROW_DTYPE, SCORE_DTYPE  # noqa: E402,F401
 
 MAXM = 128
 SAMPLE_BYTES = 640
@@ -47,6 +47,8 @@ POSITION_NO_MOVE = 16          # XQ_POSITION_NO_MOVE: the side to move has no le
 START_POOL_MAX = 1 << 20       # XQ_START_POOL_MAX
 RNG_KIND_START_POOL = 11       # XQ_RNG_KIND_START_POOL
 REASON_TABLE = 5               # XQ_REASON_TABLE: a result's reason for a game an endgame table adjudicated
+RNG_KIND_RESIGN_HOLDOUT = 12   # XQ_RNG_KIND_RESIGN_HOLDOUT
+RESIGN_MAX_STEPS = 8           # XQ_RESIGN_MAX_STEPS
 
 
 class XqError(RuntimeError):
@@ -222,6 +224,23 @@ class AdjudicateOpts(C.Structure):
     _fields_ = [("draws", C.c_int32), ("both_colours", C.c_int32), ("min_ply", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ResignOpts(C.Structure):
+    """xq_resign_opts: the per-side resign rule (xq_engine_resign): resign when the K latest values of the side to move are all
+    below threshold; holdout_prob the share of games that are exempt and played out."""
+    _fields_ = [("threshold", C.c_double), ("holdout_prob", C.c_double), ("check_steps", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ResignRow(C.Structure):
+    """xq_resign_row: one finished holdout game: the lowest window of each side and the ply it was first reached at."""
+    _fields_ = [("slot", C.c_uint32), ("game_seq", C.c_uint32), ("level", C.c_float * 2), ("level_ply", C.c_uint16 * 2),
+                ("winner", C.c_int8), ("reason", C.c_uint8), ("plies", C.c_uint16), ("zero", C.c_uint32 * 2)]
+
+
+RESIGN_ROW_BYTES = 32            # sizeof(xq_resign_row)
+RESIGN_STATE_BYTES = 32          # xq_resign_state_bytes(1)
+assert C.sizeof(ResignRow) == RESIGN_ROW_BYTES == RESIGN_ROW_DTYPE.itemsize and C.sizeof(ResignOpts) == 24
+
+
 class MateOpts(C.Structure):
     """xq_mate_opts: the forced-mate search (xq_mate_search_batch): N attacker moves, checks only 0 / 1, visits per root move."""
     _fields_ = [("max_moves", C.c_int32), ("checks_only", C.c_int32), ("node_limit", C.c_uint32), ("reserved", C.c_uint32)]
@@ -387,6 +406,11 @@ def lib():
     L.xq_engine_settle.argtypes = [C.POINTER(Engine), vp, vp]
     L.xq_tb_adjudicate_batch.argtypes = [vp, i32, vp, C.c_int64, vp, vp, i32, C.POINTER(AdjudicateOpts), vp, vp, vp, vp]
     L.xq_engine_adjudicate.argtypes = [C.POINTER(Engine), vp, i32, vp, C.c_int64, C.POINTER(AdjudicateOpts), vp, vp]
+    L.xq_resign_state_bytes.argtypes = [i32]
+    L.xq_resign_state_bytes.restype = C.c_size_t
+    L.xq_resign_exempt_host.argtypes = [C.c_uint64, i32, i32, C.c_uint32, C.c_double]
+    L.xq_resign_scan_batch.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp]
+    L.xq_engine_resign.argtypes = [C.POINTER(Engine), C.POINTER(ResignOpts), vp, vp, i32, vp, vp, vp]
     L.xq_engine_drain_games.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
     L.xq_engine_drain_games_device.argtypes = [C.POINTER(Engine), vp, i32, C.POINTER(C.c_int), vp]
     L.xq_engine_game_records_stats_read.argtypes = [C.POINTER(Engine), C.POINTER(GameRecordsStats), vp]
@@ -520,7 +544,8 @@ EXPORTS = ["xq_version", "xq_last_hip_error", "xq_movegen_batch", "xq_attack_map
            "xq_positions_check_batch", "xq_engine_workspace_bytes_sp", "xq_engine_init_sp", "xq_start_pool_draw_host",
            "xq_engine_start_indices", "xq_engine_start_pool_stats_read", "xq_engine_option_words_sp", "xq_evdedup_bytes", "xq_evdedup_init",
            "xq_engine_compact_unique", "xq_engine_expand_dedup", "xq_evdedup_stats_read", "xq_evdedup_bucket_host",
-           "xq_dedup_rows_batch", "xq_engine_settle", "xq_tb_adjudicate_batch", "xq_engine_adjudicate"]
+           "xq_dedup_rows_batch", "xq_engine_settle", "xq_tb_adjudicate_batch", "xq_engine_adjudicate",
+           "xq_resign_state_bytes", "xq_resign_exempt_host", "xq_resign_scan_batch", "xq_engine_resign"]
 
 
 def check(rc: int, what: str):
@@ -1017,6 +1042,65 @@ def engine_adjudicate(engine_handle, signature, table: torch.Tensor, opts: Adjud
     arr, P = _tb_pieces(codes)
     check(lib().xq_engine_adjudicate(C.byref(engine_handle), arr, P, _dev(table), entries, C.byref(opts), _dev(counters),
                                      stream_ptr(table.device)), "xq_engine_adjudicate")
+
+
+def resign_opts(threshold, check_steps, holdout_prob=0.0, what: str = "resign") -> ResignOpts:
+    """The options of the per-side resign rule checked -> ResignOpts (no GPU needed): threshold a float that is no NaN (-inf:
+    nobody resigns), check_steps an integer in 1..RESIGN_MAX_STEPS, holdout_prob in [0, 1]."""
+    try:
+        t, p = float(threshold), float(holdout_prob)
+    except (TypeError, ValueError):
+        raise XqError(f"{what}: threshold and holdout_prob must be numbers, got {threshold!r} and {holdout_prob!r}")
+    if t != t:
+        raise XqError(f"{what}: threshold must not be NaN")
+    if not 0.0 <= p <= 1.0:                            # a NaN fails both comparisons
+        raise XqError(f"{what}: holdout_prob must be in [0, 1], got {holdout_prob!r}")
+    try:
+        ok = not isinstance(check_steps, bool) and int(check_steps) == check_steps and 1 <= int(check_steps) <= RESIGN_MAX_STEPS
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise XqError(f"{what}: check_steps must be an integer in 1..{RESIGN_MAX_STEPS}, got {check_steps!r}")
+    return ResignOpts(t, p, int(check_steps), 0)
+
+
+def resign_exempt(seed: int, rank: int, slot: int, game_seq: int, holdout_prob: float) -> bool:
+    """The holdout draw on the host (xq_resign_exempt_host, the device's own code; no GPU needed): is game `game_seq` of `slot`
+    exempt from resignation?"""
+    if not 0.0 <= float(holdout_prob) <= 1.0:
+        raise XqError(f"resign_exempt: holdout_prob must be in [0, 1], got {holdout_prob!r}")
+    if min(int(rank), int(slot), int(game_seq)) < 0:
+        raise XqError(f"resign_exempt: rank, slot and game_seq must not be negative, got {rank}, {slot}, {game_seq}")
+    rc = int(lib().xq_resign_exempt_host(int(seed) & (2 ** 64 - 1), int(rank), int(slot), int(game_seq), float(holdout_prob)))
+    if rc < 0:
+        check(rc, "xq_resign_exempt_host")
+    return rc == 1
+
+
+def resign_scan(values: torch.Tensor, lengths: torch.Tensor, first_side: torch.Tensor, threshold: float, check_steps: int):
+    """The per-side resign rule over sequences of values (xq_resign_scan_batch): values float32[n, max_len], lengths int32[n] and
+    first_side int8[n] (1 red, else black: the side to move at index 0) on the GPU -> (resign_index int32[n], the first index whose
+    window is below the threshold or -1; resigner int8[n], that side or 0; level float32[n, 2], the lowest window of red and of
+    black over the whole sequence, +inf for none; level_index int32[n, 2], where it was first reached, or -1)."""
+    opts = resign_opts(threshold, check_steps, 0.0, "resign_scan")
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.dim() != 2:
+        raise XqError("resign_scan: values must be a float32 tensor [n, max_len]")
+    n, max_len = int(values.shape[0]), int(values.shape[1])
+    dev = values.device
+    if not (isinstance(lengths, torch.Tensor) and lengths.dtype == torch.int32 and tuple(lengths.shape) == (n,) and
+            isinstance(first_side, torch.Tensor) and first_side.dtype == torch.int8 and tuple(first_side.shape) == (n,) and
+            lengths.device == dev and first_side.device == dev):
+        raise XqError(f"resign_scan: lengths must be int32[{n}] and first_side int8[{n}] on the values' device")
+    index = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    resigner = torch.zeros(n, dtype=torch.int8, device=dev)
+    level = torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev)
+    level_index = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            check(lib().xq_resign_scan_batch(_dev(values) if max_len else None, _dev(lengths), _dev(first_side), n, max_len,
+                                             opts.check_steps, opts.threshold, _dev(index), _dev(resigner), _dev(level),
+                                             _dev(level_index), stream_ptr(dev)), "xq_resign_scan_batch")
+    return index, resigner, level, level_index
 
 
 def _records_arg(samples: torch.Tensor, what: str):

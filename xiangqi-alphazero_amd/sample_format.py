@@ -28,6 +28,11 @@ GAME_RECORD_DTYPE = np.dtype([("slot", np.uint32), ("game_seq", np.uint32), ("wi
                               ("n_moves", np.uint16), ("opening_plies", np.uint16), ("n_samples", np.uint16),
                               ("moves", np.uint16, RECORD_MAX_PLIES)])
 assert GAME_RECORD_DTYPE.itemsize == 1024 and GAME_RECORD_DTYPE.fields["moves"][1] == 16
+# xq_resign_row: what the per-side resign rule (xq_engine_resign) keeps of every finished holdout game: the lowest window of red
+# and of black (+inf: none) and the ply each was first reached at
+RESIGN_ROW_DTYPE = np.dtype([("slot", np.uint32), ("game_seq", np.uint32), ("level", np.float32, 2), ("level_ply", np.uint16, 2),
+                             ("winner", np.int8), ("reason", np.uint8), ("plies", np.uint16), ("zero", np.uint32, 2)])
+assert RESIGN_ROW_DTYPE.itemsize == 32
 # xq_sample_root_stats: what an engine with root_stats=True (xq_engine_init_rs) writes into a sample's `pad` bytes
 ROOT_STATS_DTYPE = np.dtype([("root_q", np.float32), ("root_visits", np.uint32), ("has_root_stats", np.uint8),
                              ("zero", np.uint8, 11)])

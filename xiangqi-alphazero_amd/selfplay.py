@@ -98,7 +98,7 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
               tree_reuse: Optional[bool] = None, playout_cap=None, forced_playouts: Optional[float] = None, gumbel=None,
               perpetual_check: Optional[bool] = None, solver: Optional[bool] = None, root_stats: Optional[bool] = None,
               eval_mirror: Optional[bool] = None, record_games: Optional[bool] = None, start_pool=None,
-              eval_dedup: Optional[bool] = None, adjudicate=None):
+              eval_dedup: Optional[bool] = None, adjudicate=None, resign=None):
     """Play `num_games` complete games; returns (samples, results, stats dict, elapsed seconds) in compact form:
     structured numpy arrays, or -- `device_records` -- uint8 device tensors [n, 640] / [m, 16] that never left the GPU.
     `eval_cache_entries` (None: `config.eval_cache_entries`, absent = 0 = off) gives every slot an evaluation cache of that
@@ -142,7 +142,13 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     `adjudicate` = (tables, options) (an argument only: `AlphaZeroLoop` reads the config keys and generates the tables) ends a game
     as soon as an endgame table decides its position (engine.SelfPlayEngine): stats `adjudicated_games`
     (the finished games with reason 5), `adjudicated_decisive`, `adjudicated_drawn`, `adjudicated_left_alone` and
-    `adjudicated_swapped` (the engine's counters; all 0 when off).  Every other option."""
+    `adjudicated_swapped` (the engine's counters; all 0 when off).  Every other option.
+    `resign` = dict(threshold=, check_steps=, holdout_prob=, max_rows=) (an argument only: `AlphaZeroLoop` reads the config keys)
+    lets a side resign on its own last `check_steps` root values and plays a share `holdout_prob` of the games out
+    (engine.SelfPlayEngine); max_rows defaults to num_games + 8, one row per game.  Stats `resign` (the
+    options in use, None when off), `resign_rows` (sample_format.RESIGN_ROW_DTYPE, one row per finished holdout game; None when
+    off), `resign_resigned`, `resign_holdout_games`, `resign_rows_dropped` and `resign_values_seen` (0 when off).  Self-play
+    with every other option; `config.enable_resign`'s own rule is then only the recorder of the values."""
     if eval_dedup is None:
         eval_dedup = bool(getattr(config, "eval_dedup", False))
     if record_games is None:
@@ -189,7 +195,8 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
                                 leaves_per_step=leaves_per_step, tree_reuse=tree_reuse, playout_cap=playout_cap,
                                 forced_playouts=forced_playouts, gumbel=gumbel, perpetual_check=perpetual_check, solver=solver,
                                 root_stats=root_stats, eval_mirror=eval_mirror, record_games=record_games, start_pool=start_pool,
-                                eval_dedup=eval_dedup, **({} if adjudicate is None else {"adjudicate": adjudicate}))
+                                eval_dedup=eval_dedup, **({} if adjudicate is None else {"adjudicate": adjudicate}),
+                                **({} if resign is None else {"resign": {"max_rows": num_games + 8, **resign}}))
     t0 = time.time()
     if use_graph and hasattr(ev, "evaluate_legal"):
         eng.capture_step()                             # one graph launch per step (short steps are launch-bound otherwise)
@@ -238,6 +245,11 @@ def run_games(model, config, num_games: int, device="cuda", n_slots: Optional[in
     adj = eng.adjudication_stats() if adjudicate is not None else {}
     for k in ("decisive", "drawn", "left_alone", "swapped"):       # the counters' keys are present (0) when it is off
         st["adjudicated_" + k] = adj.get("adjudicated_" + k, 0)
+    rsn = eng.resign_stats() if eng.resign is not None else {}
+    st["resign"] = None if eng.resign is None else dict(eng.resign)
+    st["resign_rows"] = eng.drain_resign_rows() if eng.resign is not None else None
+    for k in ("resigned", "holdout_games", "rows_dropped", "values_seen"):     # the counters' keys are present (0) when it is off
+        st["resign_" + k] = rsn.get(k, 0)
     st.setdefault("eval_cache_probes", 0)              # the cache's keys are present (0) when it is off
     st.setdefault("eval_cache_hits", 0)
     if eng.capture_error:

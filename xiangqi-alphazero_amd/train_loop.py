@@ -7,7 +7,11 @@ Per iteration, exactly the reference's order:
                    (`xq_engine_drain_device`) and one padded all-gather of those device buffers brings every rank's
                    records to every rank's device-resident replay buffer.  Opt-in (`config.adjudicate_signatures`, with
                    `adjudicate_draws` and `adjudicate_min_ply`): a game ends as soon as one of those endgame tables decides
-                   its position, and its samples get the exact result (engine.SelfPlayEngine's `adjudicate`);
+                   its position, and its samples get the exact result (engine.SelfPlayEngine's `adjudicate`).  Opt-in
+                   (`config.resign_per_side`): a side resigns on its own last root values, a share `resign_holdout_prob` of
+                   the games is played out, and the iteration logs under "resign" the threshold used, the games resigned, the
+                   holdout games, the pairs below the threshold with their false-positive rate and the calibrated threshold
+                   (`resign.calibrate`); with `resign_calibrate` the next iteration plays under it;
   2. train        `train_network` data-parallel over the ranks (every batch split, SyncBatchNorm, bucketed gradient
                    all-reduce: the reference's full-batch update) -- or on rank 0 alone with `config.ddp = False` -- then
                    ONE flat `broadcast_weights`;
@@ -190,6 +194,44 @@ def _endgame_play_options(config):
     playout = None if positions is None else {"positions": positions, "max_plies": 100 if max_plies is None else max_plies}
     teacher = None if samples is None else {"samples": samples, "policy": 0 if policy is None else policy}
     return playout, teacher
+
+
+def _resign_options(config):
+    """The per-side resign rule's keys (all optional; absent means off): None unless config.resign_per_side is true, else a dict
+    of threshold (config.resign_threshold), check_steps (config.resign_check_steps), holdout_prob (config.resign_holdout_prob,
+    default 0.1), calibrate (config.resign_calibrate, default false), fp_target (config.resign_fp_target, default 0.05),
+    min_pairs (config.resign_min_pairs, default 20) and threshold_max (config.resign_threshold_max, default the larger of -0.5 and
+    the threshold).  A bad value raises XqError with the key's name, whether the option is on or not."""
+    on = getattr(config, "resign_per_side", None)
+    calibrate = getattr(config, "resign_calibrate", None)
+    for key, v in (("resign_per_side", on), ("resign_calibrate", calibrate)):
+        if v is not None and not isinstance(v, bool):
+            raise hip.XqError(f"config.{key} must be a bool, got {v!r}")
+
+    def number(key, default, lo, hi):
+        v = getattr(config, key, None)
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= float(v) <= hi:      # a NaN fails the comparison
+            raise hip.XqError(f"config.{key} must be a number in [{lo}, {hi}], got {v!r}")
+        return float(v)
+
+    prob = number("resign_holdout_prob", 0.1, 0.0, 1.0)
+    target = number("resign_fp_target", 0.05, 0.0, 1.0)
+    min_pairs = getattr(config, "resign_min_pairs", None)
+    min_pairs = 20 if min_pairs is None else min_pairs
+    if isinstance(min_pairs, bool) or not isinstance(min_pairs, int) or min_pairs < 1:
+        raise hip.XqError(f"config.resign_min_pairs must be an integer >= 1, got {min_pairs!r}")
+    t_max = getattr(config, "resign_threshold_max", None)
+    if t_max is not None and (isinstance(t_max, bool) or not isinstance(t_max, (int, float)) or t_max != t_max):
+        raise hip.XqError(f"config.resign_threshold_max must be a number, got {t_max!r}")
+    if not on:
+        return None
+    if not bool(getattr(config, "enable_resign", False)):
+        raise hip.XqError("config.resign_per_side needs config.enable_resign: the engine's own rule records the root values")
+    opts = hip.resign_opts(config.resign_threshold, config.resign_check_steps, prob, what="config.resign_per_side")
+    return {"threshold": float(opts.threshold), "check_steps": int(opts.check_steps), "holdout_prob": prob,
+            "calibrate": bool(calibrate), "fp_target": target, "min_pairs": int(min_pairs),
+            "threshold_max": max(-0.5, float(opts.threshold)) if t_max is None else float(t_max)}
 
 
 def _adjudicate_options(config):
@@ -385,6 +427,14 @@ class AlphaZeroLoop:
         self.adjudicate = _adjudicate_options(config)
         self._adjudicate_tbs = None
         self._shard_adjudicated = (0, 0, 0)
+        # the per-side resign rule (config.resign_per_side with resign_holdout_prob, resign_calibrate, resign_fp_target,
+        # resign_min_pairs, resign_threshold_max; absent: off), read once and checked here: a side resigns on its own last
+        # resign_check_steps root values, a share of the games is played out, and every iteration logs what the holdout says of
+        # the threshold; with resign_calibrate the next iteration plays under the threshold it gives.  Self-play only
+        self.resign = _resign_options(config)
+        self.resign_threshold = None if self.resign is None else self.resign["threshold"]
+        self._shard_resign = None
+        self._iteration_resign = None
         torch.manual_seed(seed)                     # identical initial weights on every rank
         self.current_model = XiangqiNet(config.num_channels, config.num_res_blocks).to(self.device)
         self.best_model = copy.deepcopy(self.current_model)
@@ -421,7 +471,9 @@ class AlphaZeroLoop:
                                                     perpetual_check=self.perpetual_check, solver=self.solver,
                                                     root_stats=self.record_root_stats, eval_mirror=self.eval_mirror,
                                                     record_games=self.record_games, start_pool=self._iteration_pool(),
-                                                    **self._adjudicate_arg())
+                                                    **self._adjudicate_arg(), **self._resign_arg())
+        if self.resign is not None:
+            self._shard_resign = (st["resign_rows"], st["resign_resigned"], st["resign_holdout_games"], st["resign_rows_dropped"])
         if self.start_pool is not None:
             self._shard_pool = (st["start_pool"][0], st["start_pool_games"])
         if self.adjudicate is not None:
@@ -468,6 +520,36 @@ class AlphaZeroLoop:
             self._adjudicate_tbs = tuple(tbs)
         return {"adjudicate": (self._adjudicate_tbs, dict(draws=a["draws"], min_ply=a["min_ply"]))}
 
+    def _resign_arg(self) -> dict:
+        """run_games' `resign` keyword, or nothing: with the keys absent the call is the call without it."""
+        r = self.resign
+        if r is None:
+            return {}
+        return {"resign": dict(threshold=self.resign_threshold, check_steps=r["check_steps"], holdout_prob=r["holdout_prob"])}
+
+    def _resign_entry(self) -> dict:
+        """This iteration's "resign" entry, and the next threshold.  Every rank's holdout rows are gathered with the records'
+        all-gather and the counters summed, so every rank computes the same entry from the same rows."""
+        from . import resign as rsn
+        from .sample_format import RESIGN_ROW_DTYPE
+        r = self.resign
+        rows, *counts = self._shard_resign if self._shard_resign is not None else (np.zeros(0, RESIGN_ROW_DTYPE), 0, 0, 0)
+        if self.grouped:
+            dev = self.device
+            packed = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).reshape(-1, RESIGN_ROW_DTYPE.itemsize).copy()).to(dev)
+            rows = xdist.all_gather_records_device(packed).cpu().numpy().reshape(-1).view(RESIGN_ROW_DTYPE)
+            total = torch.tensor(counts, dtype=torch.int64, device=dev)
+            dist.all_reduce(total)
+            counts = [int(v) for v in total.tolist()]
+        below, bad = rsn.rate_below(rows, self.resign_threshold)
+        nxt = rsn.calibrate(rows, r["fp_target"], r["min_pairs"], r["threshold_max"])
+        entry = {"threshold": self.resign_threshold, "resigned": int(counts[0]), "holdout_games": int(counts[1]),
+                 "rows_dropped": int(counts[2]), "pairs_below": below, "fp_rate": bad / below if below else None,
+                 "calibrated_threshold": nxt, "calibrate": r["calibrate"]}
+        if r["calibrate"]:
+            self.resign_threshold = nxt
+        return entry
+
     def _scoring_evaluator(self):
         """The evaluator of `best_model` that scores the shards: built once and kept (its activation and logits buffers with it);
         every iteration refreshes its weights in place, which is one more filter transform per iteration beside run_games' own."""
@@ -495,7 +577,9 @@ class AlphaZeroLoop:
         self._shard_scores = None
         self._shard_pool = (0, 0)
         self._shard_adjudicated = (0, 0, 0)
+        self._shard_resign = None
         samples, results = self._play_shard(xdist.shard_games(cfg.num_games_per_iter, self.world, self.rank))
+        self._iteration_resign = None if self.resign is None else self._resign_entry()
         pooled = {}
         if self.start_pool is not None:
             # every rank's pool is the same; the games started from it are summed over the ranks
@@ -738,6 +822,11 @@ class AlphaZeroLoop:
                     self.training_stats = [e for e in json.load(f) if int(e.get("iteration", 0)) <= self.iteration]
             except (ValueError, OSError):
                 self.training_stats = []
+        if self.resign is not None and self.resign["calibrate"]:
+            # a resumed run plays on under the threshold its last logged iteration calibrated
+            logged = [e["resign"] for e in self.training_stats if isinstance(e.get("resign"), dict)]
+            if logged:
+                self.resign_threshold = float(logged[-1]["calibrated_threshold"])
         return info
 
     # ---- train.py:581-638 ------------------------------------------------------------------------------------
@@ -773,7 +862,8 @@ class AlphaZeroLoop:
                                         **({} if tc is None else {"tactics": tc}),
                                         **({} if eg is None else {"endgame": eg}),
                                         **({} if po is None else {"endgame_playout": po}),
-                                        **({} if pre is None else {"pretrain": pre})})
+                                        **({} if pre is None else {"pretrain": pre}),
+                                        **({} if self._iteration_resign is None else {"resign": self._iteration_resign})})
             pre = None
             if self.rank == 0:
                 os.makedirs(cfg.checkpoint_dir, exist_ok=True)
