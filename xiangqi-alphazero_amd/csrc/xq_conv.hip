@@ -38,7 +38,10 @@
 // Blocks are dealt so that each XCD works on one 64-channel slice of U at a time (1.3 MB at C=256: L2-resident).
 // The WIDE variant (NT = 4, one workgroup per CU, 128 output channels, 320 accumulators in VGPRs + AGPRs) differs in three
 // places, each explained where it happens: 16 weight-fragment registers (a fragment is fetched 64 MFMAs ahead), the input
-// loads of the prologue before everything else, and an epilogue pipelined against its own global stores.  Cost model used
+// loads of the prologue before everything else, and an epilogue pipelined against its own global stores, instantiated with
+// and without a residual (k_wino_conv<4, HAS_RES>: a launch without one issues no residual loads and adds no zeros; the
+// narrow variant is k_wino_conv<2, true> and takes the residual at run time), whose reader shares one set of four LDS
+// reads between the two pixel rows and fetches the next set ahead.  Cost model used
 // throughout (measured, tests/microbench/valu_rates.hip): the fp32 MFMA runs on the vector ALU's multipliers, so every
 // vector instruction beside it costs its ~5 issue cycles; an LDS read ~6; a store or load issued into a full queue blocks
 // the wave (~260 / ~130 cycles each when all CUs do it), a spaced one costs its slot.
@@ -96,7 +99,19 @@ constexpr int ESTR = 32 + XQ_EPAD_NARROW;                             // floats 
                                                      // lane halves of an accumulator write land on different banks)
 constexpr int E_BYTES = 4 * 3 * TILES * ESTR * 4;  // epilogue exchange for one 32-channel half: [row p][b][tile][co]
 constexpr int LDS_BYTES = 2 * XRAW > E_BYTES ? 2 * XRAW : E_BYTES;
-constexpr int LDS_BYTES_WIDE = 4 * 3 * TILES * (64 + XQ_EPAD_WIDE) * 4;             // exchange planes of a 64-channel round
+// Rounds of the wide epilogue's exchange: 2 (shipped: two N-tiles = 64 channels per round, one set of 64-channel planes) or 4
+// (-DXQ_EPI_ROUNDS=4, lab builds only: one N-tile per round, two plane sets used in turn; bit-identical and no faster, see the
+// epilogue).
+#ifndef XQ_EPI_ROUNDS
+#define XQ_EPI_ROUNDS 2
+#endif
+static_assert(XQ_EPI_ROUNDS == 2 || XQ_EPI_ROUNDS == 4, "XQ_EPI_ROUNDS must be 2 or 4");
+#ifndef XQ_EPI_PIPE
+#define XQ_EPI_PIPE 1         // 0: the wide variant runs the plain (narrow-style) epilogue in two 64-channel rounds
+#endif
+constexpr int LDS_BYTES_WIDE = XQ_EPI_ROUNDS == 4 && XQ_EPI_PIPE ? 2 * (4 * 3 * TILES * 32 * 4)    // two sets of 32-channel planes
+
+                                                  : 4 * 3 * TILES * (64 + XQ_EPAD_WIDE) * 4;   // planes of a 64-channel round
 
 __device__ __forceinline__ f32x4 ld4(const char *p) { return *(const f32x4 *)p; }
 __device__ __forceinline__ f32x4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
@@ -183,11 +198,14 @@ __device__ __forceinline__ f32x4 pk_fms4(f32x4 x, f32x2 c, f32x4 y) {
 // two workgroups per CU (the round-1 shape).  NT = 4 ("wide"): 128 output channels per workgroup, 320 accumulators per
 // wave (VGPRs + AGPRs of the unified 512-entry file), ONE workgroup per CU: every staged input chunk and every transformed
 // A operand feeds twice as many MFMAs, and the input is fetched by half as many workgroups.
-template <int NT>
+// HAS_RES (wide variant only): the launch has a residual.  Without one the wide epilogue issues no residual loads, holds no
+// residual registers and adds no zeros; the narrow variant takes R at run time and exists as <2, true> alone.
+template <int NT, bool HAS_RES>
 __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void k_wino_conv(const float *__restrict__ X, const float *__restrict__ Ug,
                                                    const float *__restrict__ bias, const float *__restrict__ R,
                                                    float *__restrict__ Y, int B, int C, int flags, int n_groups,
                                                    const int32_t *__restrict__ live) {
+    static_assert(NT == 4 || HAS_RES, "the narrow variant takes its residual at run time");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char *Xr = lds;
     // live-row variant: the grid is sized for the capacity B, the batch is the first *live boards of it.  Everything below --
@@ -434,21 +452,41 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void k_wino_conv(const float 
         // per workgroup; the narrow == wide bit-identity test (tests/test_nn_parity.py) stays the functional guard.
         asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(acc[4][3]));
     }
-#ifndef XQ_EPI_PIPE
-#define XQ_EPI_PIPE 1
-#endif
     if constexpr (NT == 4 && XQ_EPI_PIPE) {
         // ---- wide epilogue, software-pipelined against its own stores ------------------------------------------------------
-        // Same exchange as below (two rounds of 64 channels through the planes, thread (tile, channel quad) finishes six
-        // pixels), re-ordered around one measured fact: a 1-KB store instruction takes the CU's store path ~260 cycles with four
-        // waves storing, and a wave whose store finds the queue full issues NOTHING meanwhile -- 24 stores back to back are
-        // ~3 us of a 6.6 us epilogue (profiles/r03_instruction_costs_one_wave_per_simd.log).  So the twelve output vectors of
-        // round 0 are kept in registers and stored one by one between the segments of round 1's column transform (16 segments
-        // of ~20 vector instructions), round 1's are stored as each is finished, and the next round's residual loads are
-        // issued one per finished vector.  Scheduling fences keep the compiler from re-clustering them.  No divergent branch:
-        // lanes of tiles past the end carry an out-of-range buffer offset (dropped by the hardware), a null residual is a
-        // descriptor of zero records (loads return 0.0f), ReLU-or-identity is one v_max_f32 against 0 / -inf.
-        const int etile = tid >> 3, co = (tid & 7) * 4;
+        // The exchange of the plain epilogue below (column half in registers, row half across the four waves through LDS, thread
+        // (tile, channel quad) finishes six pixels per N-tile), ordered around one measured fact: a 1-KB store instruction takes
+        // the CU's store path ~260 cycles with four waves storing, and a wave whose store finds the queue full issues NOTHING
+        // meanwhile -- 24 stores back to back are ~3 us of a 6.6 us epilogue
+        // (profiles/r03_instruction_costs_one_wave_per_simd.log).  So a round's output vectors wait in registers (`pend`) and are
+        // stored one by one between the segments of the NEXT round's column transform (~20 vector instructions each), the last
+        // round's are stored as each is finished, and the next round's residual loads go out one per finished vector.
+        // ROUNDS = 2 (shipped): two N-tiles per round, 16 segments, 12 vectors, one set of 64-channel planes (row stride 96
+        // floats) and a second barrier before round 1 overwrites it.
+        // ROUNDS = 4 (-DXQ_EPI_ROUNDS=4): one N-tile (32 channels) per round, 8 segments, 6 vectors; the planes of round r are
+        // set r mod 2 of two [row p 4][b 3][tile 32][co 32] sets (row stride 32 floats: conflict-free for the reader's lane
+        // groups, as in the narrow variant; 96 KB).  ONE barrier per round.  Why set r mod 2 is free when round r + 2 writes
+        // it: a wave writes round r + 2 only after it has passed the barrier of round r + 1, and no wave arrives at that barrier
+        // before it has finished its reads of round r -- they precede it in program order and their values are consumed (added
+        // into `pend`) before the round's last scheduling fence.  Round r + 1 writes the OTHER set, so it needs no barrier
+        // against round r's readers.  The first store goes out 8 segments earlier and only 6 stores remain behind the last
+        // segment -- and the launch is no faster, with or without residual (profiles/r32_conv_epilogue_ab.json, DESIGN.md
+        // section 4.1; nor with any other spacing of the stores that was tried): when a CU issues its stores is not what
+        // bounds them.  Not shipped.
+        // Scheduling fences keep the compiler from re-clustering the stores.  No divergent branch: lanes of tiles past the end
+        // carry an out-of-range buffer offset (dropped by the hardware), ReLU-or-identity is one v_max_f32 against 0 / -inf.
+        // Without a residual (HAS_RES false) there are no residual loads, registers or additions: y + bias + 0.0f == y + bias
+        // bit for bit here, because y + bias is -0.0f only if both are, and y -- sums and differences of accumulators that
+        // started from +0.0f -- never is.
+        constexpr int ROUNDS = XQ_EPI_ROUNDS, RW = NT / ROUNDS;          // N-tiles per round
+        constexpr int NV = 6 * RW;                                        // output vectors per thread and round
+        constexpr int ESTR_R = RW == 2 ? 64 + XQ_EPAD_WIDE : 32;          // floats per tile row of a plane
+        constexpr int ESET = RW == 1 ? 4 * 3 * TILES * ESTR_R : 0;        // floats from plane set 0 to set 1 (two rounds: one set)
+        // every lane role of the epilogue is derived afresh from the thread id (made opaque here), so that none of the main
+        // loop's lane values has to stay live across it for the epilogue's sake: two of them spilled to scratch otherwise
+        int etid = tid;
+        asm volatile("" : "+v"(etid));
+        const int etile = etid >> 3, co = (etid & 7) * 4;
         const int eg = t0 + etile, egc = eg < T ? eg : T - 1;
         const int ebd = egc / 15, et2 = egc - ebd * 15, ety = et2 / 3, etx = et2 - ety * 3;
         const int Cs = __builtin_amdgcn_readfirstlane(C);
@@ -456,30 +494,29 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void k_wino_conv(const float 
         const unsigned ooff = eg < T ? ooff_in : 0xFFFFFFF0u;
         const unsigned nbytes = (unsigned)B * 90u * (unsigned)C * 4u;
         const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)Y, 0, (int)nbytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)(R != nullptr ? R : X), 0, R != nullptr ? (int)nbytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)(HAS_RES ? R : X), 0, HAS_RES ? (int)nbytes : 0, 0x00020000);
         const float rlo = relu ? 0.0f : -__builtin_inff();
-        constexpr int ESTR_R = 64 + XQ_EPAD_WIDE;
         auto goff = [&](int n, int it) __attribute__((always_inline)) { return (unsigned)(32 * n + ((it / 3) * 9 + it % 3) * Cs) * 4u; };
 #ifndef XQ_RES_SPREAD
-#define XQ_RES_SPREAD 2       // round 0's residual loads go out this many per column-transform segment (0: all twelve up front, -0.5 %: the issue of twelve back-to-back loads blocks the wave like stores do)
+#define XQ_RES_SPREAD 2       // round 0's residual loads go out this many per column-transform segment (0: all up front, -0.5 %: the issue of twelve back-to-back loads blocks the wave like stores do)
 #endif
-        f32x4 resv[2][6], bv[4], pend[12];
-        if (!XQ_RES_SPREAD) {
+        f32x4 resv[HAS_RES ? NV : 1], bv[4], pend[NV];
+        if constexpr (HAS_RES && !XQ_RES_SPREAD) {
 #pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int it = 0; it < 6; ++it) resv[s][it] = buf_ld4(rrs, ooff, goff(s, it));
+            for (int j = 0; j < NV; ++j) resv[j] = buf_ld4(rrs, ooff, goff(j / 6, j % 6));
         }
 #pragma unroll
         for (int n = 0; n < 4; ++n) bv[n] = *(const f32x4 *)(bias + cog * NCO + 32 * n + co);
         float *E = (float *)lds;
-        float *ew = E + ((wp * 3) * TILES + 4 * h) * ESTR_R + l31;
-        const float *er = E + etile * ESTR_R + co;
+        float *ew0 = E + (((etid >> 6) * 3) * TILES + 4 * ((etid >> 5) & 1)) * ESTR_R + (etid & 31);   // (wp, h, l31)
+        const float *er0 = E + etile * ESTR_R + co;
 #pragma unroll
-        for (int rd = 0; rd < 2; ++rd) {
+        for (int rd = 0; rd < ROUNDS; ++rd) {
+            float *ew = ew0 + (rd & 1) * ESET;
+            const float *er = er0 + (rd & 1) * ESET;
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int n = rd * 2 + s;
+            for (int s = 0; s < RW; ++s) {
+                const int n = rd * RW + s;
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
                     const f32x2 m0 = {acc[0][n][e], acc[0][n][e + 1]}, m1 = {acc[1][n][e], acc[1][n][e + 1]};
@@ -496,39 +533,71 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void k_wino_conv(const float 
                         ew[(1 * TILES + tile) * ESTR_R + 32 * s] = y1[k];
                         ew[(2 * TILES + tile) * ESTR_R + 32 * s] = y2[k];
                     }
-                    const int seg = s * 8 + e / 2;                               // 0 .. 15
-                    if (rd == 1 && seg < 12) buf_st4(yrs, ooff, goff(seg / 6, seg % 6), pend[seg]);   // round 0's vector `seg`
-                    if (XQ_RES_SPREAD && rd == 0) {
+                    const int seg = s * 8 + e / 2;                               // 0 .. 8 RW - 1
+                    if (rd > 0 && seg < NV) buf_st4(yrs, ooff, goff((rd - 1) * RW + seg / 6, seg % 6), pend[seg]);   // the round before's vector `seg`
+                    if constexpr (HAS_RES && XQ_RES_SPREAD) {
+                        if (rd == 0) {
 #pragma unroll
-                        for (int j = seg * XQ_RES_SPREAD; j < (seg + 1) * XQ_RES_SPREAD && j < 12; ++j) resv[j / 6][j % 6] = buf_ld4(rrs, ooff, goff(j / 6, j % 6));
+                            for (int j = seg * XQ_RES_SPREAD; j < (seg + 1) * XQ_RES_SPREAD && j < NV; ++j) resv[j] = buf_ld4(rrs, ooff, goff(j / 6, j % 6));
+                        }
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
             __syncthreads();
+            // Reader: thread (tile, channel quad) finishes the six pixels of each N-tile of the round.  Pixel column yb needs the
+            // four row planes p = 0..3 at (b = yb): ONE set of four reads serves both pixel rows (ya = 0: p0 + p1 + p2, ya = 1:
+            // p1 - p2 - p3), and the reads of the next column (of the next N-tile after the last) are issued before the current
+            // column is finished.  XQ_EPI_PREFETCH=0 is the order before: per pixel its own three reads, issued when it is their
+            // turn -- with one wave per SIMD nothing covers an LDS round trip, and 24 pixels exposed two of them each.
+#ifndef XQ_EPI_PREFETCH
+#define XQ_EPI_PREFETCH 1
+#endif
+            constexpr int pstride = 3 * TILES * ESTR_R;          // next Winograd row p
+            auto finish = [&](f32x4 y, int s, int it) __attribute__((always_inline)) {
+                const int n = rd * RW + s;
+                y = pk_add4(y, bv[n]);
+                if constexpr (HAS_RES) y = pk_add4(y, resv[s * 6 + it]);
+                y.x = max1(rlo, y.x); y.y = max1(rlo, y.y); y.z = max1(rlo, y.z); y.w = max1(rlo, y.w);
+                if (rd + 1 < ROUNDS) {
+                    pend[s * 6 + it] = y;
+                    if constexpr (HAS_RES) resv[s * 6 + it] = buf_ld4(rrs, ooff, goff(n + RW, it));   // the next round's residual, one per finished vector
+                } else {
+                    buf_st4(yrs, ooff, goff(n, it), y);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            if constexpr (XQ_EPI_PREFETCH) {
+                f32x4 ec[4], en[4];
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int n = rd * 2 + s;
+                for (int p = 0; p < 4; ++p) ec[p] = *(const f32x4 *)(er + p * pstride);
 #pragma unroll
-                for (int it = 0; it < 6; ++it) {
-                    const int ya = it / 3, yb = it % 3;
-                    const float *e0 = er + yb * TILES * ESTR_R + 32 * s;
-                    const int pstride = 3 * TILES * ESTR_R;      // next Winograd row p
-                    f32x4 y;
-                    if (ya == 0) y = pk_add4(pk_add4(*(const f32x4 *)(e0), *(const f32x4 *)(e0 + pstride)), *(const f32x4 *)(e0 + 2 * pstride));
-                    else y = pk_sub4(pk_sub4(*(const f32x4 *)(e0 + pstride), *(const f32x4 *)(e0 + 2 * pstride)), *(const f32x4 *)(e0 + 3 * pstride));
-                    y = pk_add4(pk_add4(y, bv[n]), resv[s][it]);
-                    y.x = max1(rlo, y.x); y.y = max1(rlo, y.y); y.z = max1(rlo, y.z); y.w = max1(rlo, y.w);
-                    if (rd == 0) {
-                        pend[s * 6 + it] = y;
-                        resv[s][it] = buf_ld4(rrs, ooff, goff(2 + s, it));      // round 1's residual, one per finished vector
-                    } else {
-                        buf_st4(yrs, ooff, goff(n, it), y);
+                for (int c = 0; c < 3 * RW; ++c) {               // column c = 3 s + yb
+                    const int s = c / 3, yb = c % 3;
+                    if (c + 1 < 3 * RW) {
+#pragma unroll
+                        for (int p = 0; p < 4; ++p) en[p] = *(const f32x4 *)(er + ((c + 1) % 3) * TILES * ESTR_R + 32 * ((c + 1) / 3) + p * pstride);
                     }
-                    __builtin_amdgcn_sched_barrier(0);
+                    finish(pk_add4(pk_add4(ec[0], ec[1]), ec[2]), s, yb);
+                    finish(pk_sub4(pk_sub4(ec[1], ec[2]), ec[3]), s, 3 + yb);
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) ec[p] = en[p];
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < RW; ++s) {
+#pragma unroll
+                    for (int it = 0; it < 6; ++it) {
+                        const int ya = it / 3, yb = it % 3;
+                        const float *e0 = er + yb * TILES * ESTR_R + 32 * s;
+                        f32x4 y;
+                        if (ya == 0) y = pk_add4(pk_add4(*(const f32x4 *)(e0), *(const f32x4 *)(e0 + pstride)), *(const f32x4 *)(e0 + 2 * pstride));
+                        else y = pk_sub4(pk_sub4(*(const f32x4 *)(e0 + pstride), *(const f32x4 *)(e0 + 2 * pstride)), *(const f32x4 *)(e0 + 3 * pstride));
+                        finish(y, s, it);
+                    }
                 }
             }
-            if (rd == 0) __syncthreads();             // round 1 overwrites the planes
+            if (RW == 2 && rd + 1 < ROUNDS) __syncthreads();   // one plane set: the next round overwrites it
         }
         return;
     }
@@ -687,19 +756,23 @@ static int wino_conv3x3(const float *dev_x, const float *dev_u, const float *dev
     if ((unsigned long long)batch * 90ull * (unsigned)channels * 4ull >= (1ull << 32)) return XQ_ERR_ARG;
     static thread_local bool attr_set = false;
     if (!attr_set) {
-        XQ_TRY(hipFuncSetAttribute((const void *)k_wino_conv<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-        XQ_TRY(hipFuncSetAttribute((const void *)k_wino_conv<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_WIDE));
+        XQ_TRY(hipFuncSetAttribute((const void *)k_wino_conv<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
+        XQ_TRY(hipFuncSetAttribute((const void *)k_wino_conv<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_WIDE));
+        XQ_TRY(hipFuncSetAttribute((const void *)k_wino_conv<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_WIDE));
         attr_set = true;
     }
     const int n_groups = (batch * 15 + TILES - 1) / TILES;
     const int lds_bytes = (XQ_ABL & 65536) ? 100 * 1024 : LDS_BYTES;      // ablation: one workgroup per CU
     const int per = 8 / (channels / nco);
     const int rows = (n_groups + per - 1) / per;
-    if (wide)
-        hipLaunchKernelGGL(k_wino_conv<4>, dim3(rows * 8), dim3(256), LDS_BYTES_WIDE, (hipStream_t)stream, dev_x, dev_u, dev_bias,
+    if (wide && dev_residual)
+        hipLaunchKernelGGL((k_wino_conv<4, true>), dim3(rows * 8), dim3(256), LDS_BYTES_WIDE, (hipStream_t)stream, dev_x, dev_u, dev_bias,
+                           dev_residual, dev_y, batch, channels, flags, n_groups, dev_live);
+    else if (wide)                                  // no residual: the epilogue without its loads and additions
+        hipLaunchKernelGGL((k_wino_conv<4, false>), dim3(rows * 8), dim3(256), LDS_BYTES_WIDE, (hipStream_t)stream, dev_x, dev_u, dev_bias,
                            dev_residual, dev_y, batch, channels, flags, n_groups, dev_live);
     else
-        hipLaunchKernelGGL(k_wino_conv<2>, dim3(rows * 8), dim3(256), lds_bytes, (hipStream_t)stream, dev_x, dev_u, dev_bias,
+        hipLaunchKernelGGL((k_wino_conv<2, true>), dim3(rows * 8), dim3(256), lds_bytes, (hipStream_t)stream, dev_x, dev_u, dev_bias,
                            dev_residual, dev_y, batch, channels, flags, n_groups, dev_live);
     return xq::launch_status();
 }
